@@ -18,9 +18,15 @@ mc_search / mc_search_files issue their batches: mc_range_end(i), mc_range_begin
 of the next step is enqueued before the host sums up (--one-at-a-time: mc_run_range per step).  The timed region holds exactly
 K steps, each from its first kernel to its results on the host.
 
-Rank 0 prints ONE JSON line: metric / value (whole-job reads/s), `roofline` for the dominant kernel and, at N = 1, `cpu_baseline`
-(the reference's own RAPsearch2 binary on this host's cores on bounded samples of the same reads, m8 compared by md5) and `e2e`
-(file -> AGS through run_pipeline).
+Rank 0 prints ONE JSON line: metric / value (whole-job reads/s), ms_per_step (the wall time of one timed step), `roofline` for the
+dominant kernel and, at N = 1, `cpu_baseline` (the reference's own RAPsearch2 binary on this host's cores on bounded samples of the same
+reads, m8 compared by md5) and `e2e` (file -> AGS through run_pipeline).
+
+--dump-outputs DIR: rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy (float64): the m8 rows
+(rows_<field>), the best hits (best_hits_<field>) and the per-family accumulators of the step (family_hits, family_aln: summed over
+the ranks; family_aln_by_target_len: rank 0's).  Rows and best hits are cut to the whole reads that come first in a seeded permutation
+of the batch (DUMP_ROWS / DUMP_BEST_HITS records at most, under 64 MB in all).  The reads are a function of the arguments alone, so
+two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import hashlib
@@ -34,7 +40,6 @@ import time
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 import microbecensus_amd  # noqa: E402
-microbecensus_amd.configure_process_env()     # bench.py owns its process (and its ranks inherit the environment): GPU_MAX_HW_QUEUES=8 unless set
 
 METRIC = "reads/sec searched vs marker DB + AGS abs-error, 150 bp @ 1/2/4/8 GPU"
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
@@ -44,6 +49,35 @@ def seed_positions(L):
 
 
 SURVEY_A = {100: 127403, 150: 207923, 300: 452893}   # modelled algorithmic bytes per read of the whole path
+
+
+DUMP_ROWS, DUMP_BEST_HITS, DUMP_SEED = 400_000, 300_000, 20261015     # 14 x 8 B per row, 5 x 8 B per best hit: 57 MB at most
+
+
+def read_sample(read_ids, first, n_batch, cap):
+    """Mask of the records (rows or best hits: one read id each) of the reads that come first in a seeded permutation of the batch,
+    as many whole reads as hold at most `cap` records; every record when there are no more than `cap`."""
+    import numpy as np
+    if read_ids.size <= cap:
+        return np.ones(read_ids.size, bool)
+    local = read_ids.astype(np.int64) - first
+    if local.min() < 0 or local.max() >= n_batch:
+        raise RuntimeError("bench.py: read id outside the step's batch")
+    key = np.random.default_rng(DUMP_SEED).permutation(n_batch)[local]
+    return key < np.sort(key)[cap]
+
+
+def dump_outputs(path, first, n_batch, rows, best, hits, aln, bylen):
+    """--dump-outputs: the arrays of one step as float64 .npy files under path (see the module's docstring)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"family_hits": hits, "family_aln": aln, "family_aln_by_target_len": bylen}
+    for tag, rec, ids, cap in (("rows", rows, "query", DUMP_ROWS), ("best_hits", best, "read", DUMP_BEST_HITS)):
+        keep = read_sample(rec[ids], first, n_batch, cap)
+        for f in rec.dtype.names:
+            out["%s_%s" % (tag, f)] = rec[f][keep]
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def spawn_ranks(n, argv):
@@ -610,7 +644,10 @@ def main():
     ap.add_argument("--one-at-a-time", action="store_true", help="mc_run_range per step (the device idles while the host sums the best hits up) instead of mc_range_end / mc_range_begin / results")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="nccl = RCCL, one GPU per rank (the measurement); gloo: all ranks on GPU 0, reductions on the host - "
                                                                                "only to exercise the N > 1 code path on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see the module's docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -676,6 +713,7 @@ def main():
     eng.attach(reads.data_ptr(), per_rank)
     nf = len(fams)
     tot_hits = np.zeros(nf, np.int64); tot_aln = np.zeros(nf, np.int64); tot_bylen = np.zeros((nf, mcd.MAX_TARGET_LEN), np.int64)
+    last_acc = []                           # the per-family accumulators of the last step collected
 
     def collect_results(collect=True):
         best = eng.best_hits(copy=False)    # the rows of the batch are in host memory too (mc_result_rows); the aggregation needs the best hits
@@ -685,6 +723,7 @@ def main():
             dist.all_reduce(t)
             t = t.cpu().numpy()
             hits, aln = t[:nf], t[nf:]
+        last_acc[:] = [hits, aln, bylen]
         if collect:
             tot_hits.__iadd__(hits); tot_aln.__iadd__(aln); tot_bylen.__iadd__(bylen)
         return eng.stats()
@@ -724,6 +763,8 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.time() - t0
+    if args.dump_outputs and rank == 0:     # (the engine still holds the last timed step's results: the step of batch (K - 1) % nres)
+        dump_outputs(args.dump_outputs, ((K - 1) % nres) * args.batch, args.batch, eng.rows(copy=False), eng.best_hits(copy=False), *last_acc)
     # the same steps with mc_set_best_hits_only (run_pipeline's path: only the reads that can be classified are ranked, no rows)
     dt_only, st_only = None, None
     if not args.no_best_only_leg:

@@ -193,8 +193,8 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
     // (the handle's), one for the rows on their way to the host, one for the
     // uploads of the streaming calls.  HIP multiplexes its streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless the environment
     // says otherwise) and streams that share one wait for each other: with nine streams the front of a range could land behind the
-    // 5 ms copy of the rows of the range before (measured: 51.2 instead of 53.6 M reads/s) - hence few streams, and GPU_MAX_HW_QUEUES=8
-    // exported by the entry points (microbecensus_amd.configure_process_env(); never by this library).
+    // 5 ms copy of the rows of the range before (measured: 51.2 instead of 53.6 M reads/s) - hence few streams.  The queue count is
+    // the environment's: neither this library nor the package's entry points set it.
     HIPCK(hipStreamCreate(&h->side)); HIPCK(hipStreamCreate(&h->side2));
     for (McCtx &c : h->ctx) {
         HIPCK(hipStreamCreate(&c.stream)); c.side = h->side; c.side2 = h->side2;

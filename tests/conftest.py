@@ -1,3 +1,5 @@
+import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -7,7 +9,6 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import microbecensus_amd  # noqa: E402
-microbecensus_amd.configure_process_env()     # the test process is ours (child processes inherit it): see the function's docstring
 
 
 def pytest_configure(config):
@@ -50,4 +51,20 @@ def ref_dir(repo):
     d = os.path.join(repo, "oracle", "_ref")
     if not os.path.isfile(os.path.join(d, "rapdb_2.15")):
         pytest.skip("oracle/_ref not built (needs /root/reference once: python oracle/build_ref.py)")
+    return d
+
+
+@pytest.fixture(scope="session")
+def rapdb_dir(repo, tmp_path_factory):
+    """Directory of the marker database in prerapsearch's format (rapdb_2.15 + rapdb_2.15.info): oracle/_ref where it was built, else
+    the pair the library's writer (mc_rapdb_write) makes from the packaged markers.  Either is accepted only with the md5s of the files
+    prerapsearch_Linux_2.15 wrote (tests/golden/rapdb_2.15.json), so both are those files, byte for byte."""
+    d = os.path.join(repo, "oracle", "_ref")
+    if not os.path.isfile(os.path.join(d, "rapdb_2.15")):
+        from microbecensus_amd import _native
+        d = str(tmp_path_factory.mktemp("rapdb"))
+        names, seqs = _native.load_markers()
+        _native.rapdb_write(names, seqs, os.path.join(d, "rapdb_2.15"))
+    for f, md5 in json.load(open(os.path.join(repo, "tests", "golden", "rapdb_2.15.json"))).items():
+        assert hashlib.md5(open(os.path.join(d, f), "rb").read()).hexdigest() == md5, f
     return d

@@ -67,7 +67,7 @@ def test_device_code_on_a_database_with_a_seed_threshold(emul_bin, tmp_path):
     assert hashlib.md5(out.read_bytes()).hexdigest() == meta["m8_md5"]
 
 
-def test_index_builder_matches_prerapsearch(emul_bin, markers_faa, ref_dir, tmp_path):
+def test_index_builder_matches_prerapsearch(emul_bin, markers_faa, rapdb_dir, tmp_path):
     """Bucket starts, posting order, suffix keys, residue codes, frequency threshold and letter frequencies of
     the product's index builder against the database prerapsearch wrote (oracle/_ref/rapdb_2.15[.info])."""
     fa = tmp_path / "one.fa"
@@ -85,7 +85,7 @@ def test_index_builder_matches_prerapsearch(emul_bin, markers_faa, ref_dir, tmp_
     thr = struct.unpack_from("<I", b, p)[0]; p += 4
     letter_p = np.frombuffer(b, "<f8", 10, p)
     # parse the boost archive prerapsearch wrote
-    r = open(os.path.join(ref_dir, "rapdb_2.15"), "rb").read()
+    r = open(os.path.join(rapdb_dir, "rapdb_2.15"), "rb").read()
     q = 0x28
     n = struct.unpack_from("<Q", r, q)[0]; q += 8
     ref_codes = np.frombuffer(r, "u1", n, q); q += n
@@ -116,7 +116,7 @@ def test_index_builder_matches_prerapsearch(emul_bin, markers_faa, ref_dir, tmp_
     assert np.array_equal(bstart.astype(np.int64), ref_start)
     assert np.array_equal(post, ref_post)
     assert np.array_equal(keys, ref_keys)
-    info = open(os.path.join(ref_dir, "rapdb_2.15.info"), "rb").read()
+    info = open(os.path.join(rapdb_dir, "rapdb_2.15.info"), "rb").read()
     assert thr == struct.unpack_from("<I", info, 68 + 4000000)[0]
     ref_p = np.frombuffer(info, "<f8", 10, 68 + 4000000 + 4 + 8)
     assert np.allclose(letter_p, ref_p, rtol=0, atol=1e-6)

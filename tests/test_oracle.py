@@ -44,10 +44,10 @@ def _trimmed_reads_fasta(case, tmp_path):
 
 
 @pytest.mark.parametrize("case", ["config1_example_fq", "unittest_metagenome"])
-def test_oracle_reproduces_reference_m8(case, oracle_bin, ref_dir, tmp_path):
+def test_oracle_reproduces_reference_m8(case, oracle_bin, rapdb_dir, tmp_path):
     fasta, meta = _trimmed_reads_fasta(case, tmp_path)
     out = str(tmp_path / "out.m8")
-    subprocess.check_call([oracle_bin, os.path.join(ref_dir, "rapdb_2.15"), fasta, out])
+    subprocess.check_call([oracle_bin, os.path.join(rapdb_dir, "rapdb_2.15"), fasta, out])
     got = open(out, "rb").read()
     assert got.count(b"\n") == meta["m8_rows"]
     assert hashlib.md5(got).hexdigest() == meta["m8_md5"]
@@ -56,7 +56,7 @@ def test_oracle_reproduces_reference_m8(case, oracle_bin, ref_dir, tmp_path):
 
 
 @pytest.mark.parametrize("case", ["c2_100bp", "c4_paired", "c5_300bp_q20_dups", "c1_phred64_q_m"])
-def test_oracle_on_the_small_baseline_configs(case, oracle_bin, ref_dir, tmp_path):
+def test_oracle_on_the_small_baseline_configs(case, oracle_bin, rapdb_dir, tmp_path):
     """Small versions of BASELINE configs[1], [3], [4] (goldens from the reference, tests/golden/make_golden.py): the native
     sampler re-creates the temp FASTA the reference fed to rapsearch (md5), the oracle its m8 (md5).  c1_phred64_q_m: a phred+64
     FASTQ through -q 10 -m 25 (tests/golden/make_phred64_golden.py; the golden's own quality_offset, 64, is what the reference detected)."""
@@ -70,11 +70,11 @@ def test_oracle_on_the_small_baseline_configs(case, oracle_bin, ref_dir, tmp_pat
     assert st["sampled"] == meta["sampled_reads"]
     assert hashlib.md5(open(fa, "rb").read()).hexdigest() == meta["reads_md5"]
     out = str(tmp_path / "out.m8")
-    subprocess.check_call([oracle_bin, os.path.join(ref_dir, "rapdb_2.15"), fa, out])
+    subprocess.check_call([oracle_bin, os.path.join(rapdb_dir, "rapdb_2.15"), fa, out])
     assert hashlib.md5(open(out, "rb").read()).hexdigest() == meta["m8_md5"]
 
 
-def test_oracle_on_dirty_reads(oracle_bin, ref_dir, tmp_path):
+def test_oracle_on_dirty_reads(oracle_bin, rapdb_dir, tmp_path):
     """Reads with lower case, IUPAC codes, `*`, `-`, digits, blanks (tests/golden/make_dirty_golden.py: 3,012 variants of the
     config-1 reads that hit, searched by the reference's binary): the engine's byte tables (`CHashSearch` ctor
     0x4169bd-0x416a62, `BuildQHash@0x40b530`) as the oracle restates them."""
@@ -83,7 +83,7 @@ def test_oracle_on_dirty_reads(oracle_bin, ref_dir, tmp_path):
     fa.write_bytes(gzip.open(os.path.join(GOLD, "dirty_reads.fa.gz"), "rb").read())
     assert hashlib.md5(fa.read_bytes()).hexdigest() == meta["reads_md5"]
     out = str(tmp_path / "out.m8")
-    subprocess.check_call([oracle_bin, os.path.join(ref_dir, "rapdb_2.15"), str(fa), out])
+    subprocess.check_call([oracle_bin, os.path.join(rapdb_dir, "rapdb_2.15"), str(fa), out])
     got = open(out, "rb").read()
     assert got.count(b"\n") == meta["m8_rows"] and hashlib.md5(got).hexdigest() == meta["m8_md5"]
     assert got == gzip.open(os.path.join(GOLD, "dirty_reads.m8.gz"), "rb").read()

@@ -13,19 +13,19 @@ RAPDB = os.path.join(REPO, "oracle", "_ref", "rapdb_2.15")
 needs_db = pytest.mark.skipif(not os.path.exists(RAPDB), reason="oracle/_ref/rapdb_2.15 (built from the reference's prerapsearch) not present")
 
 
-@needs_db
-def test_rapdb_is_the_index_we_build_from_the_fasta():
+def test_rapdb_is_the_index_we_build_from_the_fasta(rapdb_dir):
     """No GPU: the file prerapsearch_Linux_2.15 wrote holds exactly the residues, buckets, posting order and suffix keys
     that mc_open() derives from the marker FASTA."""
     from microbecensus_amd import _native
     names, seqs = _native.load_markers()
-    assert _native.rapdb_verify(RAPDB, names, seqs) == 0
+    db = os.path.join(rapdb_dir, "rapdb_2.15")
+    assert _native.rapdb_verify(db, names, seqs) == 0
     # and it notices a difference: swap two residues of one marker
     seqs2 = list(seqs)
     s = seqs2[10]
     seqs2[10] = s[:20] + s[21] + s[20] + s[22:]
     if seqs2[10] != s:
-        assert _native.rapdb_verify(RAPDB, names, seqs2) > 0
+        assert _native.rapdb_verify(db, names, seqs2) > 0
 
 
 def test_rapdb_reader_rejects_garbage(tmp_path):
@@ -38,7 +38,7 @@ def test_rapdb_reader_rejects_garbage(tmp_path):
 
 @needs_db
 @pytest.mark.gpu
-def test_engine_on_the_prerapsearch_database():
+def test_engine_on_the_prerapsearch_database(tmp_path):
     """The engine opened on the prerapsearch database gives the reference's m8, byte for byte (config 1)."""
     from microbecensus_amd import _native
     meta = json.load(open(os.path.join(HERE, "golden", "config1_example_fq.json")))
@@ -50,7 +50,7 @@ def test_engine_on_the_prerapsearch_database():
         model = _native.load_model()
         eng.set_run(L, model["pars"][str(L)], model["families"])
         rows, best = eng.search(reads)
-        out = os.path.join(os.environ.get("TMPDIR", "/tmp"), "rapdb_engine.m8")
+        out = str(tmp_path / "rapdb_engine.m8")
         eng.write_m8(out)
         assert hashlib.md5(open(out, "rb").read()).hexdigest() == meta["m8_md5"]
         assert len(best) == len(meta["best_hits"])
@@ -58,17 +58,17 @@ def test_engine_on_the_prerapsearch_database():
         eng.close()
 
 
-@needs_db
 def test_writer_reproduces_prerapsearch_byte_for_byte(tmp_path):
     """mc_rapdb_write (index built from the FASTA, written in RAPSearch2 2.15's on-disk format) == the two files
-    `prerapsearch_Linux_2.15 -d markers.faa -n rapdb_2.15` wrote, byte for byte: bucket order, suffix keys, .info median and
-    letter frequencies included."""
+    `prerapsearch_Linux_2.15 -d markers.faa -n rapdb_2.15` wrote, byte for byte (their md5s: tests/golden/rapdb_2.15.json): bucket
+    order, suffix keys, .info median and letter frequencies included."""
     from microbecensus_amd import _native
     names, seqs = _native.load_markers()
     out = str(tmp_path / "db")
     _native.rapdb_write(names, seqs, out)
+    want = json.load(open(os.path.join(HERE, "golden", "rapdb_2.15.json")))
     for suffix in ("", ".info"):
-        assert hashlib.md5(open(out + suffix, "rb").read()).hexdigest() == hashlib.md5(open(RAPDB + suffix, "rb").read()).hexdigest(), suffix
+        assert hashlib.md5(open(out + suffix, "rb").read()).hexdigest() == want["rapdb_2.15" + suffix], suffix
 
 
 def test_index_cache_round_trip(tmp_path):

@@ -5,7 +5,6 @@ import json, os, subprocess, sys, tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import bench
-import microbecensus_amd; microbecensus_amd.configure_process_env()
 from microbecensus_amd import synth
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 8_000_000
 worlds = [int(a) for a in sys.argv[2:]] or [2, 4]

@@ -4,7 +4,6 @@ repetition.  The difference is what the memory side costs."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-import microbecensus_amd; microbecensus_amd.configure_process_env()
 from microbecensus_amd import _native, synth
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 n = 1_000_000
