@@ -151,6 +151,26 @@ int mc_write_m8_named(mc_handle *h, const char *path, int append, const char *co
 int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_cov, const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score,
                      int64_t *count_hits, int64_t *count_aln, double *count_cov);
 
+/* ---- training (the reference's training/ workflow, TRAINING.txt steps 1 - 3, on the device) --------------------------------
+ * A genome resident in HBM: bases = contig_off[ncontig] bytes, the contigs one after another as the FASTA holds them (line breaks
+ * dropped, case kept); contig_off[0] = 0.  mc_simulate() writes reads [first, first + n) of library (seed, library_id) at
+ * read_len to dst_host (n x read_len bytes): error-free single-end reads of training/seq_sim.py, uniform over every (contig,
+ * start) with start + read_len <= contig length, forward strand; each read a pure function of (seed, library_id, read index) -
+ * csrc/k_simulate.h states the formula.  A genome without a contig of read_len bases is refused. */
+typedef struct mc_genome mc_genome;
+mc_genome *mc_genome_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, int32_t device);
+void mc_genome_close(mc_genome *g);
+int mc_simulate(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host);
+/* One library pass: reads [0, nreads) of library (seed, library_id) at mc_set_run()'s read length and E-value threshold, simulated
+ * straight into the handle's resident read buffer range by range (MC_STREAM_BATCH reads; mc_upload's buffer: the resident read set
+ * is the last range afterwards), searched, and grid-classified on the device as mc_grid_classify() does it (same arguments and
+ * outputs).  No m8 row leaves the device; only the grid's bins come back.  The genome must lie on the handle's device.  The
+ * last run's rows and best hits are empty afterwards; mc_result_stats() holds the search's totals. */
+int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint64_t seed, uint64_t library_id, const double *aln_covs, int32_t n_cov,
+                     const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score, int64_t *count_hits, int64_t *count_aln, double *count_cov);
+/* Milliseconds of the last mc_train_library() from HIP events: [0] simulation, [1] search (the stages' own events), [2] grid. */
+int mc_train_times(const mc_handle *h, float *ms);
+
 /* ---- host stage in front of the search: native read sampler (csrc/mc_reader.cpp; no GPU involved) ----------------
  * Replaces open_file / parse_seqs / quality_filter / process_seqfile (microbe_census.py:47-59, :294-325, :265-279,
  * :328-367) and count_bases (:573-584) with identical results, quirks included (see the header of mc_reader.cpp).

@@ -164,6 +164,14 @@ def load_library():
     lib.mc_set_best_hits_only.argtypes = [C.c_void_p, C.c_int]
     lib.mc_grid_classify.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.c_int32,
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.mc_genome_open.restype = C.c_void_p
+    lib.mc_genome_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+    lib.mc_genome_close.restype = None
+    lib.mc_genome_close.argtypes = [C.c_void_p]
+    lib.mc_simulate.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]
+    lib.mc_train_library.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                     C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.mc_train_times.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     _lib = lib
     return lib
 
@@ -171,7 +179,8 @@ def load_library():
 EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "mc_set_index_cache", "mc_index_cache_check", "mc_open_rapdb", "mc_marker_count", "mc_marker_name", "mc_set_families", "mc_rapdb_verify", "mc_rapdb_write", "mc_index_view", "mc_set_run", "mc_search",
                     "mc_upload", "mc_attach", "mc_run", "mc_run_range", "mc_set_counting", "mc_debug_stage", "mc_range_begin", "mc_range_end", "mc_ranges_in_flight", "mc_result_rows", "mc_result_best_hits", "mc_result_stats", "mc_write_m8", "mc_write_m8_named",
                     "mc_reader_last_error", "mc_set_host_threads", "mc_reader_open", "mc_reader_open_range", "mc_reader_open_bz2_part", "mc_bz2_blocks", "mc_gz_chunks", "mc_reader_open_gz_part", "mc_reader_gz_provide", "mc_reader_gz_end_state", "mc_reader_gz_finish", "mc_reader_run", "mc_reader_reads", "mc_reader_get_stats", "mc_reader_times", "mc_reader_describe", "mc_dupset_open", "mc_dupset_close", "mc_dupset_walk", "mc_reader_take", "mc_reader_close", "mc_reader_trim", "mc_count_bases", "mc_quality_offset",
-                    "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify"]
+                    "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify",
+                    "mc_genome_open", "mc_genome_close", "mc_simulate", "mc_train_library", "mc_train_times"]
 
 
 class DupSet:
@@ -414,6 +423,9 @@ def load_markers(path=None):
 
 
 def load_model(path=None):
+    """The packaged model.json, or the one at `path` (a file, or a model directory holding model.json)."""
+    if path and os.path.isdir(path):
+        path = os.path.join(path, "model.json")
     with open(path or os.path.join(DATA_DIR, "model.json")) as f:
         return json.load(f)
 
@@ -458,6 +470,61 @@ def use_index_cache():
     d = _private_dir(v) if v else user_cache_dir()      # (a directory named in the environment passes the same test: this user's, not group / world writable)
     if d:
         load_library().mc_set_index_cache(d.encode())
+
+
+def read_fasta_genome(path):
+    """(bases, contig_off) of a .fna[.gz]: every record's sequence, line breaks dropped, case kept, one after another."""
+    opener = gzip.open if path.endswith(".gz") else open
+    parts, off = [], [0]
+    cur = None
+    with opener(path, "rb") as f:
+        for line in f:
+            if line.startswith(b">"):
+                if cur is not None:
+                    parts.append(b"".join(cur)); off.append(off[-1] + len(parts[-1]))
+                cur = []
+            elif cur is not None:
+                cur.append(line.strip())
+    if cur is not None:
+        parts.append(b"".join(cur)); off.append(off[-1] + len(parts[-1]))
+    return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), np.array(off, dtype=np.int64)
+
+
+class Genome:
+    """A genome resident on one device (mc_genome_open): Genome(bases, contig_off) or Genome.from_fasta(path)."""
+
+    def __init__(self, bases, contig_off, device=0):
+        lib = load_library()
+        self.lib = lib
+        self.bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        self.contig_off = np.ascontiguousarray(contig_off, dtype=np.int64)
+        assert self.contig_off.ndim == 1 and len(self.contig_off) >= 2 and self.contig_off[-1] == len(self.bases)
+        self.device = device
+        self.g = lib.mc_genome_open(self.bases.ctypes.data_as(C.c_void_p), self.contig_off.ctypes.data_as(C.c_void_p), len(self.contig_off) - 1, device)
+        if not self.g:
+            raise RuntimeError("mc_genome_open failed: %s" % lib.mc_last_error().decode())
+
+    @classmethod
+    def from_fasta(cls, path, device=0):
+        bases, off = read_fasta_genome(path)
+        return cls(bases, off, device)
+
+    def simulate(self, read_len, n, seed, library_id, first=0):
+        out = np.empty((int(n), int(read_len)), dtype=np.uint8)
+        if self.lib.mc_simulate(self.g, int(read_len), int(first), int(n), int(seed), int(library_id), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("mc_simulate failed: %s" % self.lib.mc_last_error().decode())
+        return out
+
+    def close(self):
+        if getattr(self, "g", None):
+            self.lib.mc_genome_close(self.g)
+            self.g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:
@@ -644,6 +711,29 @@ class Engine:
                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), aln.ctypes.data_as(C.POINTER(C.c_int64)), cov.ctypes.data_as(C.POINTER(C.c_double))),
                     "mc_grid_classify")
         return hits, aln, cov
+
+    def simulate(self, genome, n, seed, library_id, first=0):
+        """Reads [first, first + n) of library (seed, library_id) at this engine's read length: uint8 array (n, read_len)."""
+        return genome.simulate(self.read_len, n, seed, library_id, first)
+
+    def train_library(self, genome, nreads, seed, library_id, aln_covs, max_pids, min_scores):
+        """One library pass on the device (mc_train_library): simulate, search and grid-classify nreads reads of the genome at this
+        engine's read length.  (hits, aln, cov) arrays of shape (len(aln_covs), len(max_pids), len(min_scores), nfam), as
+        grid_classify returns them."""
+        nc, npid, ns = len(aln_covs), len(max_pids), len(min_scores)
+        shape = (nc, npid, ns, self.nfam)
+        hits = np.zeros(shape, np.int64); aln = np.zeros(shape, np.int64); cov = np.zeros(shape, np.float64)
+        self._check(self.lib.mc_train_library(self.h, genome.g, int(nreads), int(seed), int(library_id), (C.c_double * nc)(*aln_covs), nc,
+                                              (C.c_int32 * npid)(*[int(p) for p in max_pids]), npid, (C.c_double * ns)(*min_scores), ns,
+                                              hits.ctypes.data_as(C.POINTER(C.c_int64)), aln.ctypes.data_as(C.POINTER(C.c_int64)), cov.ctypes.data_as(C.POINTER(C.c_double))),
+                    "mc_train_library")
+        return hits, aln, cov
+
+    def train_times(self):
+        """{'simulate', 'search', 'grid'}: milliseconds of the last train_library (HIP events)."""
+        ms = (C.c_float * 3)()
+        self._check(self.lib.mc_train_times(self.h, ms), "mc_train_times")
+        return {"simulate": ms[0], "search": ms[1], "grid": ms[2]}
 
     def index_view(self):
         p = [C.c_void_p() for _ in range(5)]

@@ -8,6 +8,7 @@
 //   k_order.h          C   HSPs binned per read (no global sort), ordered and stacked for the reads that can print
 //   k_finish.h         D   sum statistics, std::sort / heap sort replayed, 500-row cap, classification; rows in m8 order
 //   k_grid.h               the training workflow's grid classification
+//   k_simulate.h           the training workflow's library simulator
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
 // ranges from a host-side source (mc_search, mc_search_files, mc_search_files_multi) with upload and search overlapped.
@@ -19,6 +20,7 @@
 #include "k_order.h"
 #include "k_finish.h"
 #include "k_grid.h"
+#include "k_simulate.h"
 
 // ------------------------------------------------------------------------------------------------
 // handle
@@ -66,6 +68,8 @@ struct mc_handle {
     int pipe_nout = 0;                    // mc_range_begin / mc_range_end: 1 while a range has been begun and not ended
     bool keep_rows = true;                // mc_search / mc_search_files hand out the m8 rows (mc_set_keep_rows)
     bool best_only = false;               // only the reads that can be classified are ranked; no rows (mc_set_best_hits_only)
+    bool rows_stay = false;               // mc_train_library: the rows of a range stay in the context's d_rows (no copy to the host)
+    float train_ms[3] = {0, 0, 0};        // mc_train_library: simulate, search, grid of the last library (HIP events)
     uint8_t *stage_pin[2] = {}, *stage_dev[2] = {}; size_t stage_bytes = 0; hipStream_t copy_stream = nullptr;   // run_stream
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -810,7 +814,7 @@ static int stage_d(mc_handle *h, McCtx &c)
 static int stage_e(mc_handle *h, McCtx &c)
 {
     hipStream_t st = c.stream;
-    if (c.nrows) HIPCK(hipMemcpyAsync(h->pin_rows, c.d_rows, sizeof(McRow) * c.nrows, hipMemcpyDeviceToHost, h->rows_stream));   // (the range's stream has been waited for: d_rows is final)
+    if (c.nrows && !h->rows_stay) HIPCK(hipMemcpyAsync(h->pin_rows, c.d_rows, sizeof(McRow) * c.nrows, hipMemcpyDeviceToHost, h->rows_stream));   // (the range's stream has been waited for: d_rows is final)
     if (c.nbest) HIPCK(hipMemcpyAsync(c.h_best, c.d_best, sizeof(McBestHit) * c.nbest, hipMemcpyDeviceToHost, st));
     return 0;
 }
@@ -904,7 +908,7 @@ static int range_end(mc_handle *h, McCtx &c)
     if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
     h->pin_cur ^= 1; h->pin_rows = h->pin_slot[h->pin_cur]; h->pin_cap = h->pin_slot_cap[h->pin_cur];   // (the other slot may still be receiving the rows of the run before)
     c.nrows = (c.nh && !h->best_only) ? c.h_c[C_ROWS] : 0u; c.nsegs = c.h_c[C_SEGS]; c.nbest = c.h_c[C_BEST];
-    if ((size_t)c.nrows > h->pin_cap) {                          // grow the pinned row buffer
+    if ((size_t)c.nrows > h->pin_cap && !h->rows_stay) {         // grow the pinned row buffer
         (void)hipStreamSynchronize(h->rows_stream);                  // (the copy of the run before writes into the other buffer: let it finish before anything is freed)
         const size_t want = (size_t)c.nrows + c.nrows / 4 + 1024;
         mc_row *nb = nullptr;
@@ -922,9 +926,9 @@ static int range_end(mc_handle *h, McCtx &c)
     }
     rc = stage_e(h, c);
     if (rc) { (void)hipStreamSynchronize(c.stream); (void)hipStreamSynchronize(h->rows_stream); return rc; }
-    if (c.nrows) { HIPCK(hipEventRecord(h->ev_rows, h->rows_stream)); h->rows_pending = true; h->rows_ever = true; }
+    if (c.nrows && !h->rows_stay) { HIPCK(hipEventRecord(h->ev_rows, h->rows_stream)); h->rows_pending = true; h->rows_ever = true; }
     if ((rc = stage_wait(c)) != 0) return rc;
-    h->res_rows = h->pin_rows; h->n_res_rows = (int64_t)c.nrows;
+    h->res_rows = h->rows_stay ? nullptr : h->pin_rows; h->n_res_rows = h->rows_stay ? 0 : (int64_t)c.nrows;
     h->best_from = &c; h->best_count = c.nbest;                  // (mc_result_best_hits / whoever needs them: best_materialize)
 #ifdef MC_EXP_TIMING
     { const char *nm[6] = {"staging/other", "append", "lookup", "push", "setup", "expand"}; for (int k = 0; k < 6; k++) fprintf(stderr, "timing %-14s %8.3f Mcycles/wave-avg  %10llu entries\n", nm[k], (double)c.h_stats[4 + k] / 4096.0 / 1e6, c.h_stats[10 + k]); }
@@ -1198,22 +1202,49 @@ extern "C" int mc_search_files_multi(mc_handle *const *handles, int32_t n_dev, m
 
 extern "C" int mc_search_files(mc_handle *h, mc_reader *r, int64_t first_read_id) { return mc_search_files_multi(&h, 1, r, first_read_id); }
 
+// bin nk = reads whose best row passes exactly the first nk (ascending) cut-offs: cut-off j (ascending) counts the bins nk > j
+static void grid_counts(const std::vector<unsigned long long> &bins, size_t nbins, int ncp, int n_score, int nfam, const std::vector<int> &order,
+                        int64_t *count_hits, int64_t *count_aln, double *count_cov)
+{
+    const double *bcov = (const double *)(bins.data() + 2 * nbins);
+    for (int c = 0; c < ncp; c++)
+        for (int f = 0; f < nfam; f++) {
+            unsigned long long sh = 0, sa = 0; double sc = 0.0;
+            for (int j = n_score - 1; j >= 0; j--) {
+                const size_t o = ((size_t)c * (MC_GRID_MAXS + 1) + (size_t)(j + 1)) * (size_t)nfam + (size_t)f;
+                sh += bins[o]; sa += bins[nbins + o]; sc += bcov[o];
+                const size_t out = ((size_t)c * n_score + (size_t)order[(size_t)j]) * (size_t)nfam + (size_t)f;
+                count_hits[out] = (int64_t)sh; count_aln[out] = (int64_t)sa; count_cov[out] = sc;
+            }
+        }
+}
+
+// the grid's parameters, cut-offs in ascending order (order[j]: the caller's index of the j-th smallest)
+static int grid_pars(const mc_handle *h, const double *aln_covs, int32_t n_cov, const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score,
+                     McGridPars &G, std::vector<int> &order)
+{
+    if (n_cov < 1 || n_cov > MC_GRID_MAXC || n_pid < 1 || n_pid > MC_GRID_MAXP || n_score < 1 || n_score > MC_GRID_MAXS) { g_err = "grid larger than 8 x 8 x 64"; return -1; }
+    if (!aln_covs || !max_pids || !min_scores) { g_err = "null argument"; return -1; }
+    memset(&G, 0, sizeof G);
+    G.read_len = h->read_len; G.n_cov = n_cov; G.n_pid = n_pid; G.n_score = n_score; G.nfam = h->nfam;
+    for (int i = 0; i < n_cov; i++) G.cov[i] = aln_covs[i];
+    for (int i = 0; i < n_pid; i++) G.pid[i] = max_pids[i];
+    order.resize((size_t)n_score);
+    for (int i = 0; i < n_score; i++) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return min_scores[a] < min_scores[b]; });
+    for (int i = 0; i < n_score; i++) G.score[i] = min_scores[order[(size_t)i]];
+    return 0;
+}
+
 extern "C" int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_cov, const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score,
                                 int64_t *count_hits, int64_t *count_aln, double *count_cov)
 {
     if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
-    if (n_cov < 1 || n_cov > MC_GRID_MAXC || n_pid < 1 || n_pid > MC_GRID_MAXP || n_score < 1 || n_score > MC_GRID_MAXS) { g_err = "grid larger than 8 x 8 x 64"; return -1; }
-    if (!aln_covs || !max_pids || !min_scores || !count_hits || !count_aln || !count_cov) { g_err = "null argument"; return -1; }
+    if (!count_hits || !count_aln || !count_cov) { g_err = "null argument"; return -1; }
+    McGridPars G; std::vector<int> order;
+    if (grid_pars(h, aln_covs, n_cov, max_pids, n_pid, min_scores, n_score, G, order)) return -1;
     HIPCK(hipSetDevice(h->device));
     const int nfam = h->nfam;
-    McGridPars G; memset(&G, 0, sizeof G);
-    G.read_len = h->read_len; G.n_cov = n_cov; G.n_pid = n_pid; G.n_score = n_score; G.nfam = nfam;
-    for (int i = 0; i < n_cov; i++) G.cov[i] = aln_covs[i];
-    for (int i = 0; i < n_pid; i++) G.pid[i] = max_pids[i];
-    std::vector<int> order((size_t)n_score);
-    for (int i = 0; i < n_score; i++) order[(size_t)i] = i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return min_scores[a] < min_scores[b]; });
-    for (int i = 0; i < n_score; i++) G.score[i] = min_scores[order[(size_t)i]];
     const size_t nbins = (size_t)n_cov * n_pid * (MC_GRID_MAXS + 1) * nfam;
     const size_t nout = (size_t)n_cov * n_pid * n_score * nfam;
     memset(count_hits, 0, nout * 8); memset(count_aln, 0, nout * 8); memset(count_cov, 0, nout * 8);
@@ -1231,18 +1262,7 @@ extern "C" int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_
     HIPCK(hipMemcpyAsync(bins.data(), d_bins, nbins * 24, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
     (void)hipFree(d_rows); (void)hipFree(d_bins);
-    const double *bcov = (const double *)(bins.data() + 2 * nbins);
-    // bin nk = reads whose best row passes exactly the first nk (ascending) cut-offs: cut-off j (ascending) counts the bins nk > j
-    for (int c = 0; c < n_cov * n_pid; c++)
-        for (int f = 0; f < nfam; f++) {
-            unsigned long long sh = 0, sa = 0; double sc = 0.0;
-            for (int j = n_score - 1; j >= 0; j--) {
-                const size_t o = ((size_t)c * (MC_GRID_MAXS + 1) + (size_t)(j + 1)) * (size_t)nfam + (size_t)f;
-                sh += bins[o]; sa += bins[nbins + o]; sc += bcov[o];
-                const size_t out = ((size_t)c * n_score + (size_t)order[(size_t)j]) * (size_t)nfam + (size_t)f;
-                count_hits[out] = (int64_t)sh; count_aln[out] = (int64_t)sa; count_cov[out] = sc;
-            }
-        }
+    grid_counts(bins, nbins, n_cov * n_pid, n_score, nfam, order, count_hits, count_aln, count_cov);
     return 0;
 }
 
@@ -1289,4 +1309,176 @@ extern "C" int mc_write_m8_named(mc_handle *h, const char *path, int append, con
 {
     if (!query_names) { g_err = "null names"; return -1; }
     return write_m8(h, path, append, query_names, n_names, first_read_id);
+}
+
+// ------------------------------------------------------------------------------------------------
+// training: device-resident genomes, simulated libraries, the fused library pass
+// ------------------------------------------------------------------------------------------------
+struct mc_genome {
+    int device = 0, ncontig = 0;
+    std::vector<int64_t> off;                                       // contig offsets (host)
+    uint8_t *d_bases = nullptr; int64_t *d_off = nullptr, *d_vstart = nullptr;
+    int vstart_len = 0; int64_t total = 0;                          // the read length d_vstart was made for, and its valid starts
+};
+
+extern "C" mc_genome *mc_genome_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, int32_t device)
+{
+    if (!bases || !contig_off || ncontig < 1) { g_err = "mc_genome_open: bad argument"; return nullptr; }
+    if (contig_off[0] != 0) { g_err = "mc_genome_open: contig_off[0] must be 0"; return nullptr; }
+    for (int i = 0; i < ncontig; i++) if (contig_off[i + 1] < contig_off[i]) { g_err = "mc_genome_open: contig offsets must not decrease"; return nullptr; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "no HIP device visible"; return nullptr; }
+    if (device < 0 || device >= ndev) { g_err = "mc_genome_open: no such device"; return nullptr; }
+    if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return nullptr; }
+    mc_genome *g = new mc_genome();
+    g->device = device; g->ncontig = ncontig; g->off.assign(contig_off, contig_off + ncontig + 1);
+    const size_t nb = (size_t)contig_off[ncontig];
+    if (hipMalloc((void **)&g->d_bases, nb + 64) != hipSuccess || hipMalloc((void **)&g->d_off, sizeof(int64_t) * (ncontig + 1)) != hipSuccess ||
+        hipMalloc((void **)&g->d_vstart, sizeof(int64_t) * (ncontig + 1)) != hipSuccess ||
+        hipMemcpy(g->d_bases, bases, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(g->d_off, contig_off, sizeof(int64_t) * (ncontig + 1), hipMemcpyHostToDevice) != hipSuccess) {
+        g_err = "mc_genome_open: out of device memory";
+        mc_genome_close(g);
+        return nullptr;
+    }
+    return g;
+}
+
+extern "C" void mc_genome_close(mc_genome *g)
+{
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    for (void *p : {(void *)g->d_bases, (void *)g->d_off, (void *)g->d_vstart}) if (p) (void)hipFree(p);
+    delete g;
+}
+
+// the valid starts of every contig for reads of L bases (prefix sums on the device); refuses a genome without a contig of L bases
+static int genome_for_len(mc_genome *g, int L)
+{
+    if (g->vstart_len == L) return 0;
+    std::vector<int64_t> vs((size_t)g->ncontig + 1, 0);
+    for (int c = 0; c < g->ncontig; c++) vs[(size_t)c + 1] = vs[(size_t)c] + std::max<int64_t>(0, g->off[(size_t)c + 1] - g->off[(size_t)c] - L + 1);
+    if (vs.back() == 0) { g_err = "the genome has no contig of at least the read length (" + std::to_string(L) + " bp)"; return -1; }
+    HIPCK(hipMemcpy(g->d_vstart, vs.data(), sizeof(int64_t) * vs.size(), hipMemcpyHostToDevice));
+    g->vstart_len = L; g->total = vs.back();
+    return 0;
+}
+
+static uint64_t sim_key(uint64_t seed, uint64_t library_id) { return mc_mix64(seed ^ mc_mix64(library_id)); }
+
+static int launch_simulate(const mc_genome *g, int L, uint64_t key, int64_t first, int64_t n, uint8_t *dst, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    k_simulate<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, L, key, first, n, dst);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mc_simulate(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host)
+{
+    if (!g || first < 0 || n < 0 || (n > 0 && !dst_host)) { g_err = "mc_simulate: bad argument"; return -1; }
+    if (read_len < 18 || read_len > 3 * MC_MAXAA) { g_err = "read_len out of range (18..510)"; return -1; }
+    HIPCK(hipSetDevice(g->device));
+    if (genome_for_len(g, read_len)) return -1;
+    const int64_t B = std::min<int64_t>(n, stream_batch());
+    if (n == 0) return 0;
+    uint8_t *d = nullptr;
+    HIPCK(hipMalloc((void **)&d, (size_t)(B * read_len)));
+    const uint64_t key = sim_key(seed, library_id);
+    int rc = 0;
+    for (int64_t at = 0; at < n && rc == 0; at += B) {               // ranges of the streaming batch size, as mc_train_library makes them
+        const int64_t cnt = std::min(B, n - at);
+        rc = launch_simulate(g, read_len, key, first + at, cnt, d, nullptr);
+        if (rc == 0 && hipMemcpy(dst_host + at * read_len, d, (size_t)(cnt * read_len), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "mc_simulate: copy failed"; rc = -1; }
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+// one range of the resident reads through the pipeline with its rows left on the device, then the grid over those rows into the
+// bins; a range that overflows a pool is run in halves (the grid's bins do not care how the reads were cut)
+static int train_range(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id, const McGridPars &G, unsigned long long *d_bins, size_t nbins,
+                       hipEvent_t e0, hipEvent_t e1, mc_stats &tot)
+{
+    if (count <= 0) return 0;
+    McCtx &c = h->ctx[0];
+    int rc = range_begin(h, c, first, count, first_read_id);
+    if (rc == 0) rc = range_end(h, c);
+    if (rc == -2 && count > 1) {
+        tot.range_splits++;
+        const int64_t a = count / 2;
+        if ((rc = train_range(h, first, a, first_read_id, G, d_bins, nbins, e0, e1, tot)) != 0) return rc;
+        return train_range(h, first + a, count - a, first_read_id + a, G, d_bins, nbins, e0, e1, tot);
+    }
+    if (rc) return rc;
+    stats_add(tot, h->stats);
+    const int64_t nrows = (int64_t)c.nrows;
+    HIPCK(hipEventRecord(e0, c.stream));
+    if (nrows) k_grid_classify<<<dim3((unsigned)((nrows + 127) / 128)), dim3(128), 0, c.stream>>>(G, dev_index(h), h->d_fam, c.d_rows, nrows, d_bins, d_bins + nbins, (double *)(d_bins + 2 * nbins));
+    HIPCK(hipEventRecord(e1, c.stream));
+    HIPCK(hipEventSynchronize(e1));
+    h->train_ms[2] += ev_ms(e0, e1);
+    return 0;
+}
+
+extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint64_t seed, uint64_t library_id, const double *aln_covs, int32_t n_cov,
+                                const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score, int64_t *count_hits, int64_t *count_aln, double *count_cov)
+{
+    if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
+    if (!g || nreads < 0 || !count_hits || !count_aln || !count_cov) { g_err = "mc_train_library: bad argument"; return -1; }
+    if (g->device != h->device) { g_err = "mc_train_library: the genome lies on another device than the handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_train_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
+    McGridPars G; std::vector<int> order;
+    if (grid_pars(h, aln_covs, n_cov, max_pids, n_pid, min_scores, n_score, G, order)) return -1;
+    HIPCK(hipSetDevice(h->device));
+    const int L = h->read_len;
+    if (genome_for_len(g, L)) return -1;
+    const int nfam = h->nfam;
+    const size_t nbins = (size_t)n_cov * n_pid * (MC_GRID_MAXS + 1) * nfam;
+    const size_t nout = (size_t)n_cov * n_pid * n_score * nfam;
+    memset(count_hits, 0, nout * 8); memset(count_aln, 0, nout * 8); memset(count_cov, 0, nout * 8);
+    h->train_ms[0] = h->train_ms[1] = h->train_ms[2] = 0.f;
+    mc_stats tot; memset(&tot, 0, sizeof tot);
+    if (nreads == 0) { h->stats = tot; return 0; }
+    const int64_t B = std::min<int64_t>(nreads, stream_batch());
+    // the resident read buffer (mc_upload's) holds one range at a time: the simulator writes it, the search reads it
+    const int64_t need = B * L + 16;
+    if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
+    if (ensure_capacity(h, h->ctx[0], B)) return -1;
+    unsigned long long *d_bins = nullptr;
+    if (hipMalloc((void **)&d_bins, nbins * 24) != hipSuccess) { g_err = "out of device memory"; return -1; }
+    hipEvent_t ev[4] = {};
+    for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { g_err = "hipEventCreate failed"; return -1; }
+    hipStream_t st = h->ctx[0].stream;
+    const bool saved_best_only = h->best_only;
+    h->best_only = false; h->rows_stay = true;                       // (the grid needs every row of a read)
+    int rc = hipMemsetAsync(d_bins, 0, nbins * 24, st) == hipSuccess ? 0 : -1;
+    if (rc) g_err = "hipMemsetAsync failed";
+    const uint64_t key = sim_key(seed, library_id);
+    for (int64_t at = 0; at < nreads && rc == 0; at += B) {
+        const int64_t cnt = std::min(B, nreads - at);
+        if (hipEventRecord(ev[0], st) != hipSuccess || launch_simulate(g, L, key, at, cnt, h->d_reads, st) || hipEventRecord(ev[1], st) != hipSuccess) { rc = -1; break; }
+        h->reads_dev = h->d_reads; h->nreads = cnt;
+        rc = train_range(h, 0, cnt, at, G, d_bins, nbins, ev[2], ev[3], tot);
+        if (rc) break;
+        h->train_ms[0] += ev_ms(ev[0], ev[1]);
+    }
+    h->best_only = saved_best_only; h->rows_stay = false;
+    h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
+    std::vector<unsigned long long> bins(nbins * 3);
+    if (rc == 0 && (hipMemcpyAsync(bins.data(), d_bins, nbins * 24, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { g_err = "mc_train_library: copy of the bins failed"; rc = -1; }
+    if (rc) (void)hipStreamSynchronize(st);
+    (void)hipFree(d_bins);
+    for (auto &e : ev) (void)hipEventDestroy(e);
+    if (rc) return rc;
+    grid_counts(bins, nbins, n_cov * n_pid, n_score, nfam, order, count_hits, count_aln, count_cov);
+    h->stats = tot; h->train_ms[1] = tot.ms_total;
+    return 0;
+}
+
+extern "C" int mc_train_times(const mc_handle *h, float *ms)
+{
+    if (!h || !ms) { g_err = "null argument"; return -1; }
+    for (int k = 0; k < 3; k++) ms[k] = h->train_ms[k];
+    return 0;
 }

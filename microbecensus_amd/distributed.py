@@ -877,6 +877,8 @@ def run_pipeline_distributed(args, device=None):
     world = dist.get_world_size() if dist.is_initialized() else 1
     if device is None:
         device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
+    if args.get("model_dir"):
+        mc.check_model_dir(args["model_dir"])
     paths = mc.get_relative_paths(args)                                        # (mkstemp: every rank has its own temp file)
     mc.check_paths(paths)
     mc.check_input(args)
@@ -895,9 +897,9 @@ def run_pipeline_distributed(args, device=None):
         torch.cuda.set_device(device)
     try:
         L = args["read_length"]
-        model = mc._model()
+        model = mc._model(args.get("model_dir"))
         fams = model["families"]
-        eng = mc._engine(device)
+        eng = mc._engine(device, args.get("model_dir"))
         eng.set_run(L, model["pars"][str(L)], fams)
         parts = []
 
@@ -965,7 +967,7 @@ def run_pipeline_distributed(args, device=None):
         best = np.concatenate(parts) if parts else np.zeros(0, _native.BEST_DTYPE)
         acc = family_accumulators(best, len(fams))
         acc = all_reduce_accumulators(*acc, device=dev)
-        agg = aggregate_from_accumulators(*acc, fams, mc.find_opt_pars(None, L))
+        agg = aggregate_from_accumulators(*acc, fams, mc.find_opt_pars(args.get("model_dir"), L))
         if not agg:
             raise SystemExit("\nError: No hits to marker proteins - cannot estimate genome size! Rerun program with more reads.")
         est = mc.estimate_average_genome_size(args, paths, agg)

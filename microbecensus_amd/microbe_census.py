@@ -45,7 +45,7 @@ __version__ = "1.1.0"
 
 VALID_READ_LENGTHS = [50, 60, 70, 80, 90, 100, 110, 120, 130, 140, 150, 175, 200, 225, 250, 300, 350, 400, 450, 500]
 
-_engines = {}       # device -> Engine
+_engines = {}       # device -> Engine on the packaged model; (model_dir, device) -> Engine on a trained one (args['model_dir'])
 _run_cache = {}          # tempfile -> dict(reads=ndarray | None, best=ndarray | None, families=[...])
 _bases_cache = {}        # seqfiles -> total bases, when the sampler happened to read every record
 
@@ -69,16 +69,30 @@ def open_file(inpath):
     return open(inpath)
 
 
-def _model():
+def _model(model_dir=None):
+    """The packaged model, or (model_dir) a trained one: model_dir holds markers.faa.gz and model.json (training.py writes them)."""
     from . import _native
-    if "model" not in _run_cache:
-        _run_cache["model"] = _native.load_model()
-    return _run_cache["model"]
+    key = "model" if model_dir is None else ("model", os.path.abspath(model_dir))
+    if key not in _run_cache:
+        _run_cache[key] = _native.load_model(None if model_dir is None else os.path.join(model_dir, "model.json"))
+    return _run_cache[key]
+
+
+def _valid_read_lengths(model_dir=None):
+    return VALID_READ_LENGTHS if model_dir is None else sorted(int(L) for L in _model(model_dir)["read_lengths"])
+
+
+def check_model_dir(model_dir):
+    """A model directory must hold markers.faa.gz and model.json (get_relative_paths names both)."""
+    for f in ("markers.faa.gz", "model.json"):
+        if not os.path.isfile(os.path.join(model_dir, f)):
+            sys.exit("Model directory %s lacks %s (train one with scripts/train_microbe_census.py)" % (model_dir, f))
 
 
 def find_opt_pars(path_optpars, read_length):
-    """{family: {'min_cov','max_aaid','min_score','aln_stat'}} for one read length (reference :61-72)."""
-    pars = _model()["pars"].get(str(read_length), {})
+    """{family: {'min_cov','max_aaid','min_score','aln_stat'}} for one read length (reference :61-72).  path_optpars: None for the
+    packaged model, or a model directory."""
+    pars = _model(path_optpars)["pars"].get(str(read_length), {})
     return {fam: {"min_cov": p[0], "max_aaid": p[1], "min_score": p[2], "aln_stat": p[3]} for fam, p in pars.items()}
 
 
@@ -99,7 +113,8 @@ def check_os():
 def get_relative_paths(args):
     """Data locations + a fresh temp file (reference :106-123); the maps live in package data."""
     pkg_dir = os.path.dirname(os.path.abspath(__file__))
-    paths = {"db": os.path.join(pkg_dir, "data", "markers.faa.gz"), "model": os.path.join(pkg_dir, "data", "model.json"),
+    data_dir = args["model_dir"] if args.get("model_dir") else os.path.join(pkg_dir, "data")
+    paths = {"db": os.path.join(data_dir, "markers.faa.gz"), "model": os.path.join(data_dir, "model.json"),
              "tempfile": mkstemp()[1]}
     if args.get("rapsearch"):                     # the reference's -r hook (:110-111): an external RAPsearch2-compatible executable
         paths["rapsearch"] = args["rapsearch"]
@@ -117,7 +132,7 @@ def check_rapsearch(rapsearch):
         sys.exit("Incorrect version of rapsearch2 detected:'%s\nMicrobeCensus requires rapsearch v2.15" % rapsearch)
 
 
-def _rapdb_for_external_search():
+def _rapdb_for_external_search(model_dir=None):
     """The marker database in RAPsearch2's on-disk format (what `prerapsearch -d markers.faa -n rapdb_2.15` writes), produced once
     per user by the library's own writer (mc_rapdb_write) from the packaged markers.  It lives in a directory only this user can
     write (~/.cache/microbecensus_amd, mode 0700); the pair of files is written into a fresh directory and renamed into place as a
@@ -126,7 +141,7 @@ def _rapdb_for_external_search():
     import shutil
     import tempfile
     from . import _native
-    names, seqs = _native.load_markers()
+    names, seqs = _native.load_markers(None if model_dir is None else os.path.join(model_dir, "markers.faa.gz"))
     tag = hashlib.md5(("".join(names) + "".join(seqs)).encode()).hexdigest()[:16]
     root = os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "microbecensus_amd")
     os.makedirs(root, mode=0o700, exist_ok=True)
@@ -153,7 +168,7 @@ def _rapdb_for_external_search():
 def _search_seqs_external(args, paths):
     """search_seqs exactly as the reference runs it (:369-389), with the executable given by -r / args['rapsearch']."""
     import subprocess
-    command = "%s -q %s -d %s -o %s -z %s -e 1 -t n -p f -b 0" % (paths["rapsearch"], paths["tempfile"], _rapdb_for_external_search(), paths["tempfile"], args["threads"])
+    command = "%s -q %s -d %s -o %s -z %s -e 1 -t n -p f -b 0" % (paths["rapsearch"], paths["tempfile"], _rapdb_for_external_search(args.get("model_dir")), paths["tempfile"], args["threads"])
     process = subprocess.Popen(command, shell=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     output, error = process.communicate()
     if process.returncode != 0:
@@ -264,7 +279,7 @@ def auto_detect_quality_offset(seqfile):
     return 32
 
 
-def auto_detect_read_length(seqfile, file_type):
+def auto_detect_read_length(seqfile, file_type, valid=None):
     lengths = []
     try:
         with open_file(seqfile) as f_in:
@@ -275,12 +290,13 @@ def auto_detect_read_length(seqfile, file_type):
     except Exception:
         sys.exit("Could not detect read length of: %s\nThis may be due to an invalid format\nTry specifying it with -l" % seqfile)
     med = int(median(lengths))
-    if med < VALID_READ_LENGTHS[0]:
-        sys.exit("Median read length is %s. Cannot compute AGS using reads shorter than 50 bp." % med)
-    best = VALID_READ_LENGTHS[-1]
-    for i, L in enumerate(VALID_READ_LENGTHS):
+    valid = VALID_READ_LENGTHS if valid is None else valid
+    if med < valid[0]:
+        sys.exit("Median read length is %s. Cannot compute AGS using reads shorter than %s bp." % (med, valid[0]))
+    best = valid[-1]
+    for i, L in enumerate(valid):
         if L > med:
-            best = VALID_READ_LENGTHS[i - 1]
+            best = valid[i - 1]
             break
     return best
 
@@ -294,7 +310,7 @@ def impute_missing_args(args):
     if args["file_type"] == "fastq":
         args["quality_offset"] = auto_detect_quality_offset(args["seqfiles"][0])
     if "read_length" not in args or args["read_length"] is None:
-        args["read_length"] = auto_detect_read_length(args["seqfiles"][0], args["file_type"])
+        args["read_length"] = auto_detect_read_length(args["seqfiles"][0], args["file_type"], _valid_read_lengths(args.get("model_dir")) if args.get("model_dir") else None)
 
 
 def check_input(args):
@@ -310,6 +326,8 @@ def check_arguments(args):
         sys.exit("Invalid number of threads: %s\nMust be a positive integer." % args["threads"])
     if args["nreads"] is not None and args["nreads"] < 1:
         sys.exit("Invalid number of reads: %s\nMust be a positive integer." % args["nreads"])
+    if args.get("model_dir") and args["read_length"] not in _valid_read_lengths(args["model_dir"]):
+        sys.exit("Read length %s is not one the model in %s was trained for: %s" % (args["read_length"], args["model_dir"], _valid_read_lengths(args["model_dir"])))
 
 
 def print_copyright():
@@ -423,14 +441,14 @@ def _sample_search_classify(args, paths):
     if args["verbose"]:
         print("====Estimating Average Genome Size====")
         print("Sampling & trimming reads...")
-    model = _model()
+    model = _model(args.get("model_dir"))
     fams = model["families"]
     rd = _native.Reader(args["seqfiles"], L, args["nreads"], args["file_type"] == "fastq", args.get("quality_offset") or 0,
                         args["min_quality"], args["mean_quality"], args["max_unknown"], args["filter_dups"])
     try:
         try:
             devs = _devices_for(args)
-            engs = _engines_on(devs)
+            engs = _engines_on(devs, args.get("model_dir"))
             for eng in engs:
                 eng.set_run(L, model["pars"][str(L)], fams)
             # (the count of reads with m8 rows is only printed when verbose: without it only the reads that can be classified are ranked)
@@ -474,11 +492,24 @@ def _cap_host_threads(threads):
         pass
 
 
-def _engine(device):
+def _open_engine(device, model_dir=None):
     from . import _native
-    if device not in _engines:
-        _engines[device] = _native.Engine(device=device)
-    return _engines[device]
+    if model_dir is None:
+        return _native.Engine(device=device)
+    names, seqs = _native.load_markers(os.path.join(model_dir, "markers.faa.gz"))
+    model = _model(model_dir)
+    return _native.Engine(device=device, names=names, seqs=seqs, marker_family=model["marker_family"], nfam=len(model["families"]))
+
+
+def _engine_key(device, model_dir=None):
+    return device if model_dir is None else (os.path.abspath(model_dir), device)
+
+
+def _engine(device, model_dir=None):
+    k = _engine_key(device, model_dir)
+    if k not in _engines:
+        _engines[k] = _open_engine(device, model_dir)
+    return _engines[k]
 
 
 STREAM_BATCH = 2000000      # accepted reads per batch of mc_search_files(_multi)
@@ -503,7 +534,7 @@ def _devices_for(args):
     return devs or [0]
 
 
-def _engines_on(devs):
+def _engines_on(devs, model_dir=None):
     """One engine per entry of devs (an index may repeat: several handles on one GPU), opened in parallel: mc_open builds the
     marker index on the host, a second of work per handle."""
     import threading
@@ -512,13 +543,14 @@ def _engines_on(devs):
     for d in devs:                                   # the second handle on device d is engine (d, 1) ...
         k = seen.get(d, 0)
         seen[d] = k + 1
-        keys.append(d if k == 0 else (d, k))
+        keys.append(_engine_key(d if k == 0 else (d, k), model_dir))
     missing = [k for k in keys if k not in _engines]
     errs = []
 
     def make(k):
         try:
-            _engines[k] = _native.Engine(device=k if isinstance(k, int) else k[0])
+            dev = k if model_dir is None else k[1]
+            _engines[k] = _open_engine(dev if isinstance(dev, int) else dev[0], model_dir)
         except Exception as e:          # noqa: BLE001
             errs.append(e)
     ths = [threading.Thread(target=make, args=(k,)) for k in missing]
@@ -549,10 +581,10 @@ def search_seqs(args, paths):
     if cache is None or "reads" not in cache:
         seqs = [r.seq for r in parse_seqs(open(paths["tempfile"]))]
         cache = _run_cache[paths["tempfile"]] = {"reads": _pack_reads(seqs, L)}
-    model = _model()
+    model = _model(args.get("model_dir"))
     fams = model["families"]
     try:
-        eng = _engine(args.get("device", 0) or 0)
+        eng = _engine(args.get("device", 0) or 0, args.get("model_dir"))
         eng.set_run(L, model["pars"][str(L)], fams)
         rows, best = eng.search(cache["reads"])
         with open(paths["tempfile"] + ".m8", "w") as f:
@@ -599,8 +631,8 @@ def _classify_m8_file(args, paths):
     """The reference's own classification of an m8 file (used when the file did not come from this process,
     and by the tests as the checker of the device classification)."""
     from . import _native
-    optpars = find_opt_pars(None, args["read_length"])
-    model = _model()
+    optpars = find_opt_pars(args.get("model_dir"), args["read_length"])
+    model = _model(args.get("model_dir"))
     names, seqs = _native.load_markers(paths.get("db"))
     fam_of = {n: model["families"][f] for n, f in zip(names, model["marker_family"])}
     len_of = {n: float(len(s)) for n, s in zip(names, seqs)}
@@ -671,7 +703,7 @@ def classify_reads(args, paths):
 
 def aggregate_hits(args, paths, best_hits):
     """Per family: number of hits, summed aln/target_len, or summed aln, as pars.map's aln_stat says."""
-    optpars = find_opt_pars(None, args["read_length"])
+    optpars = find_opt_pars(args.get("model_dir"), args["read_length"])
     if isinstance(best_hits, _BestHits) and not best_hits._built:
         # the same sums from the array: families in the order of their first hit (the dict's insertion order - estimate's weighted
         # sum runs over it), every family's increments added one after the other in read order (np.add.accumulate is that running sum)
@@ -700,7 +732,7 @@ def estimate_average_genome_size(args, paths, agg_hits):
     """AGS_j = coefficient_j / (hits_j / sampled bp); drop |AGS_j - median| >= 1.48 MAD; weighted mean."""
     if args["verbose"]:
         print("Computing average genome size...")
-    model = _model()
+    model = _model(args.get("model_dir"))
     L = str(args["read_length"])
     estimates = {}
     for fam, hits in agg_hits.items():
@@ -777,6 +809,8 @@ def run_pipeline(args):
     if "verbose" in args and args["verbose"]:
         print_copyright()
     check_os()
+    if args.get("model_dir"):
+        check_model_dir(args["model_dir"])
     paths = get_relative_paths(args)
     check_paths(paths)
     try:

@@ -1,0 +1,320 @@
+"""Training a model: the reference's training/ workflow (TRAINING.txt steps 1 - 4) with simulation, search and grid
+classification on the GPU (mc_train_library) and the parameter fit of optimize_parameters.py on the host.
+
+    genomes_dir/*.fna.gz  --simulate (seq_sim.py: single end, no errors, --cov), search (-e 1), grid-classify-->  per-family counts
+    counts / library bp   --x-fold cross-validation (training.py:71-169)-->  pars.map, coefficients.map, ...  + model.json
+
+Two orders the reference leaves to chance are fixed here: genomes are taken in sorted name order (the reference: os.listdir
+order, which decides the folds), and the candidates of one (read length, family) are enumerated min_score ascending, then
+max_pid ascending, then aln_cov ascending, then rate type hits / aln / cov - the FIRST strict minimum of the cross-validation
+error wins (the reference: whichever of its parallel processes finished first).  Weights are not fitted (optimize_weights.R):
+every (read length, family) gets weight 1.0.
+"""
+import glob
+import gzip
+import json
+import math
+import os
+import zlib
+
+import numpy as np
+
+# the grid of class_reads.py:51-53
+ALN_COVS = [0.0, 0.25, 0.5, 0.75]
+MAX_PIDS = [50, 60, 70, 80, 90, 100]
+MIN_SCORES = list(range(23, 50))
+RATE_TYPES = ("hits", "aln", "cov")
+MIN_READ_LEN, MAX_READ_LEN = 18, 510          # what the engine searches (mc_set_run)
+MAX_FAMILIES, MAX_MARKERS = 32, 32767          # the engine's limits
+
+
+class TrainingError(ValueError):
+    """A training run refused before any GPU work."""
+
+
+# ---- inputs -----------------------------------------------------------------------------------------------------------------
+def _listing(directory, ext, what):
+    if not os.path.isdir(directory):
+        raise TrainingError("%s directory %s does not exist" % (what, directory))
+    files = sorted(f for f in os.listdir(directory) if not f.startswith("."))
+    if not files:
+        raise TrainingError("%s directory %s is empty" % (what, directory))
+    bad = [f for f in files if not f.endswith(ext)]
+    if bad:
+        raise TrainingError("%s must have %s extension: %s" % (what, ext, ", ".join(bad[:5])))
+    return [(f[: -len(ext)], os.path.join(directory, f)) for f in files]
+
+
+def list_genomes(genomes_dir):
+    """[(name, path)] of genomes_dir/*.fna.gz in sorted name order (name = file stem)."""
+    return _listing(genomes_dir, ".fna.gz", "Genomes")
+
+
+def list_families(gene_fams_dir):
+    """[(family, path)] of gene_fams_dir/*.faa.gz in sorted order (family = file stem)."""
+    return _listing(gene_fams_dir, ".faa.gz", "Gene family files")
+
+
+def _fasta_records(path):
+    opener = gzip.open if path.endswith(".gz") else open
+    name, chunks = None, []
+    with opener(path, "rt") as f:
+        for line in f:
+            if line.startswith(">"):
+                if name is not None:
+                    yield name, "".join(chunks)
+                name, chunks = line[1:].split()[0], []
+            else:
+                chunks.append(line.strip())
+    if name is not None:
+        yield name, "".join(chunks)
+
+
+def build_marker_set(families):
+    """(names, seqs, marker_family, family_names) from [(family, path)]: files in the given (sorted) order, records in file order,
+    the first occurrence of each distinct sequence kept - the rule the packaged markers.faa.gz was built by."""
+    seen = set()
+    names, seqs, fam_of = [], [], []
+    fam_names = [f for f, _ in families]
+    for fi, (_, path) in enumerate(families):
+        for name, seq in _fasta_records(path):
+            if seq in seen:
+                continue
+            seen.add(seq)
+            names.append(name)
+            seqs.append(seq)
+            fam_of.append(fi)
+    return names, seqs, fam_of, fam_names
+
+
+def packaged_marker_set():
+    from . import _native
+    names, seqs = _native.load_markers()
+    model = _native.load_model()
+    return names, seqs, list(model["marker_family"]), list(model["families"])
+
+
+def py2_round(x):
+    """Python 2's round(x): halves away from zero (seq_sim.py sizes a library with it)."""
+    y = math.floor(abs(x))
+    r = y + 1.0 if abs(x) - y >= 0.5 else y
+    return math.copysign(r, x)
+
+
+def library_reads(coverage, genome_size, read_len):
+    """n = round(cov x G / L) (seq_sim.py:79); the library holds n x L bp (library_sizes)."""
+    return int(py2_round(coverage * genome_size / float(read_len)))
+
+
+def library_id(genome_name, read_len):
+    """The library of one genome at one read length: a stable id, independent of which other genomes are trained with it."""
+    return (int(read_len) << 32) | zlib.crc32(genome_name.encode())
+
+
+def check_request(genomes, read_lengths, xfolds, coverage, n_families, n_markers):
+    """Every refusal of a training run, before any GPU work."""
+    if not read_lengths:
+        raise TrainingError("no read length given (-l)")
+    for L in read_lengths:
+        if not MIN_READ_LEN <= L <= MAX_READ_LEN:
+            raise TrainingError("read length %s outside %d..%d" % (L, MIN_READ_LEN, MAX_READ_LEN))
+    if xfolds < 1:
+        raise TrainingError("cross-validation folds (-x) must be at least 1")
+    if xfolds > len(genomes):
+        raise TrainingError("%d-fold cross-validation needs at least %d genomes; %d given" % (xfolds, xfolds, len(genomes)))
+    if not coverage > 0:
+        raise TrainingError("coverage (-c) must be positive")
+    if n_families > MAX_FAMILIES:
+        raise TrainingError("%d gene families: the engine takes at most %d" % (n_families, MAX_FAMILIES))
+    if n_markers > MAX_MARKERS:
+        raise TrainingError("%d marker sequences: the engine takes at most %d" % (n_markers, MAX_MARKERS))
+    if n_markers == 0:
+        raise TrainingError("the gene family files hold no sequences")
+
+
+# ---- the fit (optimize_parameters.py, training.py:71-169) --------------------------------------------------------------------
+def xfold_indexes(n, x, i):
+    """training.py:100-115 with integer fold size n // x: genomes behind x * (n // x) are never in a test fold."""
+    fold = n // x
+    test = list(range(fold * i - fold, fold * i))
+    return [j for j in range(n) if j not in test], test
+
+
+def xval_errors(rates, sizes, xfolds):
+    """Cross-validation median percent error of every candidate.  rates: (genomes, candidates); sizes: (genomes,).  An error of 999
+    where a test genome's rate is 0 (test_error)."""
+    rates = np.asarray(rates, dtype=np.float64)
+    sizes = np.asarray(sizes, dtype=np.float64)
+    n = rates.shape[0]
+    errs = []
+    for i in range(1, xfolds + 1):
+        train, test = xfold_indexes(n, xfolds, i)
+        pc = np.median(sizes[train, None] * rates[train], axis=0)        # estimate_proportionality_constant
+        for j in test:
+            r = rates[j]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                e = 100 * np.abs(pc / r - sizes[j]) / sizes[j]
+            errs.append(np.where(r == 0, 999.0, e))
+    return np.median(np.array(errs), axis=0)
+
+
+def candidates():
+    """(min_score, max_pid, aln_cov, rate_type) in the order the fit walks them."""
+    return [(s, p, c, t) for s in MIN_SCORES for p in MAX_PIDS for c in ALN_COVS for t in RATE_TYPES]
+
+
+def rates_by_candidate(hits, aln, cov, library_bp):
+    """Per-genome count arrays of shape (aln_cov, max_pid, min_score, family) -> rates (genomes, family, candidates) in the order of
+    candidates()."""
+    r = np.stack([np.asarray(hits, np.float64), np.asarray(aln, np.float64), np.asarray(cov, np.float64)], axis=-1)   # (G, c, p, s, f, t)
+    r = r / np.asarray(library_bp, np.float64)[:, None, None, None, None, None]
+    r = r.transpose(0, 4, 3, 2, 1, 5)                                        # (G, f, s, p, c, t)
+    return r.reshape(r.shape[0], r.shape[1], -1)
+
+
+def fit(rates, sizes, xfolds):
+    """rates: (genomes, candidates) of one (read length, family).  Returns (index of the chosen candidate, its error, coefficient,
+    predictions, every candidate's error): the first strict minimum of the cross-validation error; the coefficient is the median
+    over ALL genomes of size x rate; a prediction is coefficient / rate, None where the rate is 0."""
+    rates = np.asarray(rates, dtype=np.float64)
+    sizes = np.asarray(sizes, dtype=np.float64)
+    err = xval_errors(rates, sizes, xfolds)
+    k = int(np.argmin(err))                                                  # (first occurrence of the minimum)
+    rk = rates[:, k]
+    coeff = float(np.median([s * r for s, r in zip(sizes.tolist(), rk.tolist())]))
+    preds = [coeff / r if r > 0 else None for r in rk.tolist()]
+    return k, float(err[k]), coeff, preds, err
+
+
+# ---- outputs ------------------------------------------------------------------------------------------------------------------
+def write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, genome_sizes=None, preds=None):
+    """markers.faa.gz + model.json (the packaged schema, tools/build_data.py) and the reference's tables."""
+    os.makedirs(out_dir, exist_ok=True)
+    with gzip.GzipFile(os.path.join(out_dir, "markers.faa.gz"), "wb", mtime=0) as f:
+        for name, seq in zip(names, seqs):
+            f.write((">%s\n%s\n" % (name, seq)).encode())
+    model = {"families": list(families), "marker_family": list(marker_family), "read_lengths": sorted(int(L) for L in read_lengths),
+             "pars": pars, "coefficients": coefficients, "weights": weights}
+    with open(os.path.join(out_dir, "model.json"), "w") as f:
+        json.dump(model, f, separators=(",", ":"), sort_keys=True)
+    with open(os.path.join(out_dir, "pars.map"), "w") as f:
+        f.write("\t".join(["gene_fam", "read_length", "aln_cov", "max_pid", "min_score", "aln_stat"]) + "\n")
+        for L in sorted(pars, key=int):
+            for fam in sorted(pars[L]):
+                cov, pid, score, stat = pars[L][fam]
+                f.write("\t".join(str(x) for x in [fam, L, cov, pid, score, stat]) + "\n")
+    with open(os.path.join(out_dir, "coefficients.map"), "w") as f:
+        for k in sorted(coefficients):
+            f.write("%s\t%r\n" % (k, coefficients[k]))
+    with open(os.path.join(out_dir, "weights.map"), "w") as f:
+        for k in sorted(weights):
+            f.write("%s\t%r\n" % (k, weights[k]))
+    with open(os.path.join(out_dir, "read_len.map"), "w") as f:
+        for L in sorted(int(L) for L in read_lengths):
+            f.write("%d\n" % L)
+    with open(os.path.join(out_dir, "gene_fam.map"), "w") as f:
+        for name, fi in zip(names, marker_family):
+            f.write("%s\t%s\n" % (name, families[fi]))
+    with open(os.path.join(out_dir, "gene_len.map"), "w") as f:
+        for name, seq in zip(names, seqs):
+            f.write("%s\t%d\n" % (name, len(seq)))
+    if preds is not None:
+        with open(os.path.join(out_dir, "training_preds.map"), "w") as f:
+            f.write("\t".join(["read_length", "fam", "genome_name", "true_ags", "est_ags"]) + "\n")
+            for L, fam, genome, est in preds:
+                f.write("%s\t%s\t%s\t%d\t%s\n" % (L, fam, genome, genome_sizes[genome], "NA" if est is None else repr(est)))
+    return model
+
+
+def read_map(path, header=False):
+    """The rows of a .map table, split on tabs."""
+    with open(path) as f:
+        lines = f.read().splitlines()
+    return [ln.split("\t") for ln in lines[1 if header else 0:] if ln]
+
+
+def write_reads(path, reads):
+    """A library in seq_sim.py's format: '>id\\nseq\\n', ids 0, 1, ..."""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as f:
+        for i in range(reads.shape[0]):
+            f.write(b">%d\n" % i)
+            f.write(reads[i].tobytes())
+            f.write(b"\n")
+
+
+def write_hits(path, families, hits, aln, cov):
+    """A library's grid counts as class_reads.py writes them (.hits: fam, aln_cov, max_pid, min_score, count_hits, count_aln, count_cov)."""
+    with open(path, "w") as f:
+        f.write("\t".join(["fam", "aln_cov", "max_pid", "min_score", "count_hits", "count_aln", "count_cov"]) + "\n")
+        for ic, c in enumerate(ALN_COVS):
+            for ip, p in enumerate(MAX_PIDS):
+                for isc, s in enumerate(MIN_SCORES):
+                    for fi, fam in enumerate(families):
+                        f.write("\t".join(str(x) for x in [fam, c, p, s, int(hits[ic, ip, isc, fi]), int(aln[ic, ip, isc, fi]), repr(float(cov[ic, ip, isc, fi]))]) + "\n")
+
+
+# ---- the run ------------------------------------------------------------------------------------------------------------------
+def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfolds=10, seed=0, device=0, write_reads_dir=None, log=print):
+    """TRAINING.txt steps 1 - 4 in one call.  Returns the model dict written to out_dir/model.json, with the run's rates under
+    '_rates' ({L: (genomes, families, candidates)}) and the genomes' sizes under '_sizes'."""
+    from . import _native
+    read_lengths = [int(L) for L in read_lengths]
+    genomes = list_genomes(genomes_dir)
+    if gene_fams_dir:
+        names, seqs, marker_family, families = build_marker_set(list_families(gene_fams_dir))
+    else:
+        names, seqs, marker_family, families = packaged_marker_set()
+    check_request(genomes, read_lengths, xfolds, coverage, len(families), len(names))
+    loaded = []
+    for gname, path in genomes:
+        bases, off = _native.read_fasta_genome(path)
+        longest = int(np.max(np.diff(off))) if len(off) > 1 else 0
+        for L in read_lengths:
+            if longest < L:
+                raise TrainingError("genome %s has no contig of at least %d bp" % (gname, L))
+        loaded.append((gname, bases, off))
+    sizes = {g: int(off[-1]) for g, _, off in loaded}
+    size_list = [sizes[g] for g, _, _ in loaded]
+    log("Training on %d genomes, %d gene families (%d markers), read lengths %s, %sx coverage, %d-fold cross-validation"
+        % (len(loaded), len(families), len(names), read_lengths, coverage, xfolds))
+    eng = _native.Engine(device=device, names=names, seqs=seqs, marker_family=marker_family, nfam=len(families))
+    gpu_genomes = [_native.Genome(bases, off, device) for _, bases, off in loaded]
+    cands = candidates()
+    pars, coefficients, weights, preds, all_rates = {}, {}, {}, [], {}
+    try:
+        for L in read_lengths:
+            eng.set_run(L)
+            counts, lib_bp = [], []
+            for (gname, _, _), g in zip(loaded, gpu_genomes):
+                n = library_reads(coverage, sizes[gname], L)
+                lid = library_id(gname, L)
+                hits, aln, cov = eng.train_library(g, n, seed, lid, ALN_COVS, MAX_PIDS, MIN_SCORES)
+                counts.append((hits, aln, cov))
+                lib_bp.append(n * L)
+                if write_reads_dir:
+                    write_reads(os.path.join(write_reads_dir, str(L), gname + "-reads.fa"), g.simulate(L, n, seed, lid))
+                    write_hits(os.path.join(write_reads_dir, str(L), gname + ".hits"), families, hits, aln, cov)
+                log("  L=%d %s: %d reads" % (L, gname, n))
+            rates = rates_by_candidate([c[0] for c in counts], [c[1] for c in counts], [c[2] for c in counts], lib_bp)
+            all_rates[L] = rates
+            pars[str(L)] = {}
+            for fi, fam in enumerate(families):
+                k, _, coeff, pr, _ = fit(rates[:, fi, :], size_list, xfolds)
+                s, p, c, t = cands[k]
+                pars[str(L)][fam] = [float(c), float(p), float(s), t]
+                coefficients["%d_%s" % (L, fam)] = coeff
+                weights["%d_%s" % (L, fam)] = 1.0
+                preds.extend((L, fam, gname, est) for (gname, _, _), est in zip(loaded, pr))
+    finally:
+        for g in gpu_genomes:
+            g.close()
+        eng.close()
+    model = write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, sizes, preds)
+    zero = sorted(k for k, v in coefficients.items() if v == 0)
+    if zero:
+        log("Families no genome's reads were assigned to (coefficient 0): %s" % ", ".join(zero))
+    log("Weights are not fitted (optimize_weights.R is out of scope): every read length and family has weight 1.0")
+    log("Model written to %s" % out_dir)
+    model["_rates"], model["_sizes"] = all_rates, sizes
+    return model

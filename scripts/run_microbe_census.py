@@ -9,7 +9,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from microbecensus_amd import microbe_census  # noqa: E402
 
 
+def _model_dir(argv):
+    """--model DIR, read ahead of the full parse: the read lengths -l accepts are the model's."""
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("--model", dest="model_dir", default=None)
+    return pre.parse_known_args(argv)[0].model_dir
+
+
 def parse_arguments(argv=None):
+    model_dir = _model_dir(argv)
+    if model_dir is not None:
+        microbe_census.check_model_dir(model_dir)
     p = argparse.ArgumentParser(usage="%s [-options] <seqfiles> <outfile>" % os.path.basename(__file__),
                                 description="Estimate average genome size from metagenomic data (GPU search path).")
     p.add_argument("seqfiles", type=str, help="path to input metagenome(s); comma separated; FASTA/FASTQ, optionally gz/bz2")
@@ -19,16 +29,19 @@ def parse_arguments(argv=None):
     p.add_argument("-n", dest="nreads", type=int, default=2000000, help="number of reads to sample (default = 2000000)")
     p.add_argument("-t", dest="threads", type=int, default=None, help="cap on the host threads of the read sampler (default: the machine's cores, up to 32; the reference's -t is the rapsearch thread count)")
     p.add_argument("-e", dest="no_equivs", action="store_true", default=False, help="skip the genome-equivalents pass over the input")
-    p.add_argument("-l", dest="read_length", type=int, choices=microbe_census.VALID_READ_LENGTHS, help="trim all reads to this length")
+    p.add_argument("-l", dest="read_length", type=int, choices=microbe_census._valid_read_lengths(model_dir), help="trim all reads to this length")
     p.add_argument("-q", dest="min_quality", type=int, default=-5, help="minimum base-level PHRED quality (default = -5; no filtering)")
     p.add_argument("-m", dest="mean_quality", type=int, default=-5, help="minimum read-level PHRED quality (default = -5; no filtering)")
     p.add_argument("-d", dest="filter_dups", action="store_true", default=False, help="filter duplicate reads")
     p.add_argument("-u", dest="max_unknown", type=int, default=100, help="max percent of unknown bases per read (default = 100)")
     p.add_argument("-g", dest="device", type=int, default=None, help="GPU index (default: every visible GPU the run has batches of 2 M reads for)")
+    p.add_argument("--model", dest="model_dir", type=str, default=None, help="directory of a trained model (markers.faa.gz, model.json: scripts/train_microbe_census.py) to use instead of the packaged one")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     if args["device"] is None:
         del args["device"]
+    if args["model_dir"] is None:
+        del args["model_dir"]
     if args["threads"] is None:
         del args["threads"]                      # impute_missing_args() fills in the reference's default (1) for the report; the sampler is not capped
     return args

@@ -1,0 +1,47 @@
+#!/usr/bin/env python3
+"""Train a MicrobeCensus model on the GPU: the reference's training/ workflow (TRAINING.txt steps 1 - 4) in one command.
+
+    train_microbe_census.py <genomes_dir> <out_dir> -l 100,150 -c 10 [--gene-fams DIR] [-x 10] [--seed S] [-g device] [--write-reads DIR]
+
+out_dir receives markers.faa.gz and model.json (use them with run_microbe_census.py --model out_dir) and the reference's tables
+(pars.map, coefficients.map, weights.map, read_len.map, gene_fam.map, gene_len.map, training_preds.map)."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from microbecensus_amd import training  # noqa: E402
+
+
+def parse_arguments(argv=None):
+    p = argparse.ArgumentParser(usage="%s <genomes_dir> <out_dir> -l L[,L...] -c COV [-options]" % os.path.basename(__file__),
+                                description="Simulate shotgun libraries of complete genomes, search and grid-classify them on the GPU, and fit "
+                                            "the per-family mapping parameters and proportionality constants of an AGS model.")
+    p.add_argument("genomes_dir", help="directory of complete genomes, one <name>.fna.gz per genome")
+    p.add_argument("out_dir", help="directory for the model (markers.faa.gz, model.json) and the .map tables")
+    p.add_argument("-l", dest="read_lengths", required=True, help="read lengths to train for, comma separated (18..510)")
+    p.add_argument("-c", dest="coverage", type=float, required=True, help="library coverage of every genome (TRAINING.txt suggests 10)")
+    p.add_argument("--gene-fams", dest="gene_fams", default=None, help="directory of marker gene families, one <family>.faa.gz each (default: the packaged markers)")
+    p.add_argument("-x", dest="xfolds", type=int, default=10, help="folds of the cross-validation (default 10)")
+    p.add_argument("--seed", dest="seed", type=int, default=0, help="seed of the read simulator (default 0)")
+    p.add_argument("-g", dest="device", type=int, default=0, help="GPU index (default 0)")
+    p.add_argument("--write-reads", dest="write_reads", default=None, help="also write every library as <DIR>/<L>/<genome>-reads.fa and its grid counts as <genome>.hits")
+    args = p.parse_args(argv)
+    try:
+        args.read_lengths = [int(x) for x in args.read_lengths.split(",") if x.strip()]
+    except ValueError:
+        p.error("-l takes integers separated by commas")
+    return args
+
+
+def main(argv=None):
+    a = parse_arguments(argv)
+    try:
+        training.train(a.genomes_dir, a.out_dir, a.read_lengths, a.coverage, gene_fams_dir=a.gene_fams, xfolds=a.xfolds, seed=a.seed,
+                       device=a.device, write_reads_dir=a.write_reads)
+    except training.TrainingError as e:
+        sys.exit("Error: %s" % e)
+
+
+if __name__ == "__main__":
+    main()
