@@ -161,6 +161,16 @@ typedef struct mc_genome mc_genome;
 mc_genome *mc_genome_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, int32_t device);
 void mc_genome_close(mc_genome *g);
 int mc_simulate(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host);
+/* The kind of library mc_simulate() and mc_train_library() make of this genome from now on (training/seq_sim.py -e, -r, -p, -i):
+ * error_model MC_ERR_NONE, MC_ERR_UNIFORM (error_rate per consumed base, in [0, 1]) or MC_ERR_ILLUMINA (position-dependent rate of
+ * sim_functions.py); paired_end with insert >= the read length: row 2k is mate 1 of fragment k (forward), row 2k + 1 mate 2 (the
+ * reverse complement of the fragment's last read_len bases).  Every read keeps read_len bases: the first read_len the error
+ * process emits (the reference's reads are read_len + insertions - deletions long).  csrc/mc_simlib.h states the formula.  NULL
+ * restores the default (single end, no errors).  Refused: an unknown model, a rate outside [0, 1], paired end with insert < 1 or
+ * longer than every contig; at simulation time, insert < read_len and (mc_train_library) an odd number of paired-end reads. */
+enum { MC_ERR_NONE = 0, MC_ERR_UNIFORM = 1, MC_ERR_ILLUMINA = 2 };
+typedef struct mc_library { int32_t paired_end, insert, error_model; double error_rate; } mc_library;
+int mc_genome_set_library(mc_genome *g, const mc_library *lib);
 /* One library pass: reads [0, nreads) of library (seed, library_id) at mc_set_run()'s read length and E-value threshold, simulated
  * straight into the handle's resident read buffer range by range (MC_STREAM_BATCH reads; mc_upload's buffer: the resident read set
  * is the last range afterwards), searched, and grid-classified on the device as mc_grid_classify() does it (same arguments and

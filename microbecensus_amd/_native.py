@@ -31,6 +31,13 @@ class McStats(C.Structure):
                [("_pad", C.c_float)] + [(n, C.c_int64) for n in ("seed_exact_asks", "seed_wild_asks", "seed_pair_asks", "seed_probes", "range_splits")]
 
 
+class McLibrary(C.Structure):
+    _fields_ = [("paired_end", C.c_int32), ("insert", C.c_int32), ("error_model", C.c_int32), ("error_rate", C.c_double)]
+
+
+ERROR_MODELS = {None: 0, "uniform": 1, "illumina": 2}       # mc_library.error_model (MC_ERR_NONE, MC_ERR_UNIFORM, MC_ERR_ILLUMINA)
+
+
 class McReaderStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("sampled", "too_short", "low_qual", "dups", "records", "bases", "exhausted", "ragged_end")]
 
@@ -168,6 +175,7 @@ def load_library():
     lib.mc_genome_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     lib.mc_genome_close.restype = None
     lib.mc_genome_close.argtypes = [C.c_void_p]
+    lib.mc_genome_set_library.argtypes = [C.c_void_p, C.c_void_p]
     lib.mc_simulate.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]
     lib.mc_train_library.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                      C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -180,7 +188,7 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_upload", "mc_attach", "mc_run", "mc_run_range", "mc_set_counting", "mc_debug_stage", "mc_range_begin", "mc_range_end", "mc_ranges_in_flight", "mc_result_rows", "mc_result_best_hits", "mc_result_stats", "mc_write_m8", "mc_write_m8_named",
                     "mc_reader_last_error", "mc_set_host_threads", "mc_reader_open", "mc_reader_open_range", "mc_reader_open_bz2_part", "mc_bz2_blocks", "mc_gz_chunks", "mc_reader_open_gz_part", "mc_reader_gz_provide", "mc_reader_gz_end_state", "mc_reader_gz_finish", "mc_reader_run", "mc_reader_reads", "mc_reader_get_stats", "mc_reader_times", "mc_reader_describe", "mc_dupset_open", "mc_dupset_close", "mc_dupset_walk", "mc_reader_take", "mc_reader_close", "mc_reader_trim", "mc_count_bases", "mc_quality_offset",
                     "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify",
-                    "mc_genome_open", "mc_genome_close", "mc_simulate", "mc_train_library", "mc_train_times"]
+                    "mc_genome_open", "mc_genome_close", "mc_genome_set_library", "mc_simulate", "mc_train_library", "mc_train_times"]
 
 
 class DupSet:
@@ -508,6 +516,18 @@ class Genome:
     def from_fasta(cls, path, device=0):
         bases, off = read_fasta_genome(path)
         return cls(bases, off, device)
+
+    def set_library(self, error_model=None, error_rate=None, paired_end=False, insert=None):
+        """The kind of library simulate() and Engine.train_library() make of this genome from now on (mc_genome_set_library):
+        error_model None, 'uniform' (error_rate per base) or 'illumina'; paired_end with an insert of at least the read length
+        (rows 2k, 2k + 1 are the mates of fragment k).  No argument: the default, single end without errors."""
+        if error_model not in ERROR_MODELS:
+            raise ValueError("unknown error model %r" % (error_model,))
+        lib = None
+        if error_model is not None or paired_end:
+            lib = C.byref(McLibrary(1 if paired_end else 0, int(insert or 0), ERROR_MODELS[error_model], float(error_rate or 0.0)))
+        if self.lib.mc_genome_set_library(self.g, lib) != 0:
+            raise RuntimeError("mc_genome_set_library failed: %s" % self.lib.mc_last_error().decode())
 
     def simulate(self, read_len, n, seed, library_id, first=0):
         out = np.empty((int(n), int(read_len)), dtype=np.uint8)

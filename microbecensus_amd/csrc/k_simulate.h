@@ -1,6 +1,7 @@
 // k_simulate.h - the training workflow's library simulator (training/seq_sim.py as sim_reads.py calls it: single end, no errors, --cov).
 #pragma once
 #include "mc_hip_common.h"
+#include "mc_simlib.h"                // mc_mix64 (the formula below), and the generator of the other library kinds
 
 // seq_sim.py picks a scaffold with probability proportional to its length, a start uniform in [0, len), and throws the fragment
 // away when fewer than L bases follow: the reads it keeps are uniform over every (contig, start) with start + L <= len, genome-wide.
@@ -12,14 +13,8 @@
 //     c       = the contig with vstart[c] <= u < vstart[c + 1]
 //     read    = bases[off[c] + (u - vstart[c]) ...][0 .. L)                     (forward strand, bytes as in the FASTA)
 // A read depends on (seed, lib, i) alone: how a library is cut into ranges, or which device makes it, never changes it.
-__host__ __device__ inline uint64_t mc_mix64(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
+// That is the default library (single end, no errors); the other kinds (mc_genome_set_library) are k_simulate_lib's below.
+//
 // 256 threads per block: every thread places one read, then each wave copies the 64 reads of its lanes, a byte per lane, so that
 // the loads and the stores of a read are contiguous.  dst row k = read first + k.
 __global__ void __launch_bounds__(256) k_simulate(const uint8_t *__restrict__ bases, const int64_t *__restrict__ off, const int64_t *__restrict__ vstart,
@@ -45,4 +40,47 @@ __global__ void __launch_bounds__(256) k_simulate(const uint8_t *__restrict__ ba
         uint8_t *out = dst + r * (int64_t)L;
         for (int b = lane; b < L; b += 64) out[b] = src[b];
     }
+}
+
+// Every other library kind: errors (uniform / illumina) and / or paired end.  mc_simlib.h states the formula (row i of the
+// library; the starts of `span` = insert or L bases are vstart's).  One wave per block, a lane per read: the lane walks its read into
+// its LDS row, fetching the genome through one aligned 8-byte word it keeps (a walk never leaves its contig, and the genome buffer
+// has 64 bytes of slack behind it, so every word read lies inside the allocation).  Then the block's rows - one contiguous span of
+// dst, starting at a multiple of 64 x L bytes - go out as 4-byte words.  Dynamic LDS: 64 x L bytes of rows, then the thresholds.
+struct McSimKind { int L, paired, span, errors; };
+
+__global__ void __launch_bounds__(64) k_simulate_lib(const uint8_t *__restrict__ bases, const int64_t *__restrict__ off, const int64_t *__restrict__ vstart,
+                                                     int ncontig, McSimKind kind, const uint64_t *__restrict__ thr, uint64_t key, uint64_t ekey, int64_t first,
+                                                     int64_t n, uint8_t *__restrict__ dst)
+{
+    const int L = kind.L;
+    uint8_t *s_rows = mc_smem;
+    uint64_t *s_thr = (uint64_t *)(mc_smem + 64 * L);                // (64 x L is a multiple of 8)
+    if (kind.errors) for (int t = threadIdx.x; t < MC_SIM_NTHR; t += 64) s_thr[t] = thr[t];
+    __syncthreads();
+    const int64_t k = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (k < n) {
+        const int64_t i = first + k;
+        const uint64_t u = mc_mix64(key + (uint64_t)(kind.paired ? i >> 1 : i)) % (uint64_t)vstart[ncontig];
+        const int c = mc_sim_contig(vstart, ncontig, u);
+        const int64_t cs = off[c], ce = off[c + 1], s = cs + (int64_t)(u - (uint64_t)vstart[c]);
+        const bool rev = kind.paired && (i & 1);
+        const uint64_t *words = (const uint64_t *)bases;
+        int64_t wi = -1;
+        uint64_t word = 0;
+        auto base = [&](int64_t p) -> uint8_t {
+            if ((p >> 3) != wi) { wi = p >> 3; word = words[wi]; }
+            return (uint8_t)(word >> (8 * (p & 7)));
+        };
+        uint8_t *row = s_rows + threadIdx.x * L;
+        auto emit = [&](int o, uint8_t x) { row[o] = x; };
+        McSimNoEvent ev;
+        mc_sim_walk(base, emit, ev, cs, ce, rev ? s + kind.span - 1 : s, rev ? -1 : 1, L, mc_mix64(ekey + (uint64_t)i), s_thr, kind.errors != 0);
+    }
+    __syncthreads();
+    const int64_t r0 = (int64_t)blockIdx.x * 64;
+    const int nb = (int)(n - r0 < 64 ? n - r0 : 64) * L;
+    uint8_t *out = dst + r0 * L;
+    for (int t = threadIdx.x; t < (nb >> 2); t += 64) ((uint32_t *)out)[t] = ((const uint32_t *)s_rows)[t];
+    for (int t = (nb & ~3) + threadIdx.x; t < nb; t += 64) out[t] = s_rows[t];
 }

@@ -1318,8 +1318,12 @@ struct mc_genome {
     int device = 0, ncontig = 0;
     std::vector<int64_t> off;                                       // contig offsets (host)
     uint8_t *d_bases = nullptr; int64_t *d_off = nullptr, *d_vstart = nullptr;
-    int vstart_len = 0; int64_t total = 0;                          // the read length d_vstart was made for, and its valid starts
+    int vstart_len = 0; int64_t total = 0;                          // the span (read length or insert) d_vstart was made for, and its valid starts
+    mc_library lib = {0, 0, MC_ERR_NONE, 0.0};                      // mc_genome_set_library's kind; d_thr: its error thresholds (mc_simlib.h)
+    uint64_t *d_thr = nullptr;
 };
+static_assert(MC_ERR_NONE == MC_SIM_ERR_NONE && MC_ERR_UNIFORM == MC_SIM_ERR_UNIFORM && MC_ERR_ILLUMINA == MC_SIM_ERR_ILLUMINA, "one numbering of the error models");
+static bool default_library(const mc_library &l) { return !l.paired_end && l.error_model == MC_ERR_NONE; }
 
 extern "C" mc_genome *mc_genome_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, int32_t device)
 {
@@ -1334,7 +1338,7 @@ extern "C" mc_genome *mc_genome_open(const uint8_t *bases, const int64_t *contig
     g->device = device; g->ncontig = ncontig; g->off.assign(contig_off, contig_off + ncontig + 1);
     const size_t nb = (size_t)contig_off[ncontig];
     if (hipMalloc((void **)&g->d_bases, nb + 64) != hipSuccess || hipMalloc((void **)&g->d_off, sizeof(int64_t) * (ncontig + 1)) != hipSuccess ||
-        hipMalloc((void **)&g->d_vstart, sizeof(int64_t) * (ncontig + 1)) != hipSuccess ||
+        hipMalloc((void **)&g->d_vstart, sizeof(int64_t) * (ncontig + 1)) != hipSuccess || hipMalloc((void **)&g->d_thr, sizeof(uint64_t) * MC_SIM_NTHR) != hipSuccess ||
         hipMemcpy(g->d_bases, bases, nb, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(g->d_off, contig_off, sizeof(int64_t) * (ncontig + 1), hipMemcpyHostToDevice) != hipSuccess) {
         g_err = "mc_genome_open: out of device memory";
@@ -1348,19 +1352,43 @@ extern "C" void mc_genome_close(mc_genome *g)
 {
     if (!g) return;
     (void)hipSetDevice(g->device);
-    for (void *p : {(void *)g->d_bases, (void *)g->d_off, (void *)g->d_vstart}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)g->d_bases, (void *)g->d_off, (void *)g->d_vstart, (void *)g->d_thr}) if (p) (void)hipFree(p);
     delete g;
 }
 
-// the valid starts of every contig for reads of L bases (prefix sums on the device); refuses a genome without a contig of L bases
+// the valid starts of every contig for reads of L bases - fragments of `insert` bases for a paired-end library (prefix sums on
+// the device); refuses a genome without a contig of that span, and an insert shorter than the read
 static int genome_for_len(mc_genome *g, int L)
 {
-    if (g->vstart_len == L) return 0;
+    if (g->lib.paired_end && g->lib.insert < L) { g_err = "the insert (" + std::to_string(g->lib.insert) + ") is shorter than the read length (" + std::to_string(L) + ")"; return -1; }
+    const int span = g->lib.paired_end ? g->lib.insert : L;
+    if (g->vstart_len == span) return 0;
     std::vector<int64_t> vs((size_t)g->ncontig + 1, 0);
-    for (int c = 0; c < g->ncontig; c++) vs[(size_t)c + 1] = vs[(size_t)c] + std::max<int64_t>(0, g->off[(size_t)c + 1] - g->off[(size_t)c] - L + 1);
-    if (vs.back() == 0) { g_err = "the genome has no contig of at least the read length (" + std::to_string(L) + " bp)"; return -1; }
+    for (int c = 0; c < g->ncontig; c++) vs[(size_t)c + 1] = vs[(size_t)c] + std::max<int64_t>(0, g->off[(size_t)c + 1] - g->off[(size_t)c] - span + 1);
+    if (vs.back() == 0) {
+        g_err = "the genome has no contig of at least the " + std::string(g->lib.paired_end ? "insert" : "read length") + " (" + std::to_string(span) + " bp)";
+        return -1;
+    }
     HIPCK(hipMemcpy(g->d_vstart, vs.data(), sizeof(int64_t) * vs.size(), hipMemcpyHostToDevice));
-    g->vstart_len = L; g->total = vs.back();
+    g->vstart_len = span; g->total = vs.back();
+    return 0;
+}
+
+extern "C" int mc_genome_set_library(mc_genome *g, const mc_library *lib)
+{
+    if (!g) { g_err = "mc_genome_set_library: bad argument"; return -1; }
+    const mc_library l = lib ? *lib : mc_library{0, 0, MC_ERR_NONE, 0.0};
+    if (l.error_model != MC_ERR_NONE && l.error_model != MC_ERR_UNIFORM && l.error_model != MC_ERR_ILLUMINA) { g_err = "unknown error model " + std::to_string(l.error_model); return -1; }
+    if (!(l.error_rate >= 0.0 && l.error_rate <= 1.0)) { g_err = "error rate " + std::to_string(l.error_rate) + " outside [0, 1]"; return -1; }
+    int64_t longest = 0;
+    for (int c = 0; c < g->ncontig; c++) longest = std::max(longest, g->off[(size_t)c + 1] - g->off[(size_t)c]);
+    if (l.paired_end && l.insert < 1) { g_err = "a paired-end library needs a positive insert"; return -1; }
+    if (l.paired_end && l.insert > longest) { g_err = "the genome has no contig of at least the insert (" + std::to_string(l.insert) + " bp)"; return -1; }
+    uint64_t thr[MC_SIM_NTHR];
+    mc_sim_thresholds(l.error_model, l.error_rate, thr);
+    HIPCK(hipSetDevice(g->device));
+    HIPCK(hipMemcpy(g->d_thr, thr, sizeof thr, hipMemcpyHostToDevice));
+    g->lib = l;
     return 0;
 }
 
@@ -1369,7 +1397,14 @@ static uint64_t sim_key(uint64_t seed, uint64_t library_id) { return mc_mix64(se
 static int launch_simulate(const mc_genome *g, int L, uint64_t key, int64_t first, int64_t n, uint8_t *dst, hipStream_t st)
 {
     if (n <= 0) return 0;
-    k_simulate<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, L, key, first, n, dst);
+    if (default_library(g->lib)) {
+        k_simulate<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, L, key, first, n, dst);
+    } else {
+        const McSimKind kind = {L, g->lib.paired_end ? 1 : 0, g->lib.paired_end ? g->lib.insert : L, g->lib.error_model != MC_ERR_NONE ? 1 : 0};
+        const size_t lds = (size_t)64 * L + sizeof(uint64_t) * MC_SIM_NTHR;
+        k_simulate_lib<<<dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, kind, g->d_thr, key,
+                                                                           mc_mix64(key ^ MC_SIM_EKEY), first, n, dst);
+    }
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1426,6 +1461,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
 {
     if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
     if (!g || nreads < 0 || !count_hits || !count_aln || !count_cov) { g_err = "mc_train_library: bad argument"; return -1; }
+    if (g->lib.paired_end && (nreads & 1)) { g_err = "a paired-end library has an even number of reads (" + std::to_string(nreads) + " given)"; return -1; }
     if (g->device != h->device) { g_err = "mc_train_library: the genome lies on another device than the handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_train_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
     McGridPars G; std::vector<int> order;

@@ -1,0 +1,111 @@
+// mc_simlib.h - the per-read generator of the training workflow's library simulator, for every library kind: error model none,
+// uniform(rate) or illumina (training/sim_functions.py:92-140), single end or paired end with an insert (training/seq_sim.py -p -i).
+// Host and device code alike: k_simulate.h runs it one read per lane, tests/emul/sim_library.cpp compiles it with g++.  No HIP
+// include here: under hipcc the includer has included the HIP runtime already (MC_SIM_HD then is __host__ __device__).
+//
+// A library of kind (L, paired, insert, model) under (seed, lib); key as in k_simulate.h, G = 0x9E3779B97F4A7C15:
+//     key     = mix(seed ^ mix(lib))                                    (starts)
+//     ekey    = mix(key ^ 0xA0761D6478BD642F)                           (errors: their own domain, so an error model never moves a start)
+//     span    = insert if paired else L;  vstart / total: the valid starts of span bases, as k_simulate.h makes them for L
+//     frag    = i >> 1 if paired else i;  u = mix(key + frag) % total;  c, s = contig and start of u as in k_simulate.h
+//     mate    = i & 1 if paired else 0
+//     mate 0: walks forward from s;  mate 1: walks leftward from s + span - 1 and complements (ACGT <-> TGCA, acgt <-> tgca, any other
+//             byte kept as it is)
+//     r       = mix(ekey + i)                                            (row i: each mate has its own errors)
+// The walk consumes fragment bases j = 0, 1, ... (b = the j-th base in the read's direction) and emits until the read has L bases:
+//     d       = mix(r + j * G)                                           (the splitmix64 stream of state r)
+//     error   = (d >> 32) < thr[min(j, MC_SIM_NTHR - 1)]                 (thr: mc_sim_thresholds; never drawn under model none)
+//     kind    = (d >> 16) & 0xFFFF:  < 52429 substitution (0.8),  < 58982 insertion (0.1),  else deletion (0.1)
+//     x       = "ACGT"[d & 3]
+//     no error: emit b;  substitution: emit x;  insertion: emit x, then b;  deletion: emit nothing - unless fewer bases lie past b in
+//     the read's direction inside its contig than the read still needs, and then b is emitted as if there were no error.
+// So the walk never leaves the contig and the start set is that of the error-free library.  Deviation: the reference's read is
+// the mutated L-base fragment prefix (L + insertions - deletions bases); here a read is the FIRST L bases the process emits (it
+// reads on past the L-th fragment base after deletions), since the engine searches reads of one length.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define MC_SIM_HD __host__ __device__ inline
+#else
+#define MC_SIM_HD inline
+#endif
+
+enum { MC_SIM_ERR_NONE = 0, MC_SIM_ERR_UNIFORM = 1, MC_SIM_ERR_ILLUMINA = 2 };
+#define MC_SIM_NTHR 235                        // p(j) of both models is constant for j >= 234
+#define MC_SIM_EKEY 0xA0761D6478BD642Full
+#define MC_SIM_GAMMA 0x9E3779B97F4A7C15ull
+#define MC_SIM_SUB 52429u                      // kind cut points of 65536: 0.8 and 0.9 within 2^-16
+#define MC_SIM_INS 58982u
+
+MC_SIM_HD uint64_t mc_mix64(uint64_t z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+MC_SIM_HD uint8_t mc_sim_comp(uint8_t b)
+{
+    switch (b) {
+    case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
+    case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a';
+    default: return b;
+    }
+}
+
+// The error thresholds of one model on the host (so that no compiler contracts p(j) differently on the device): thr[j] =
+// floor(p(j) x 2^32), 2^32 where p(j) >= 1; p(j) = (3e-3 + 3.3e-8 (j+1)^4) / 100 for illumina, rate for uniform, 0 for none.
+inline void mc_sim_thresholds(int model, double rate, uint64_t *thr)
+{
+    for (int j = 0; j < MC_SIM_NTHR; j++) {
+        const double t = (double)(j + 1);
+        const double t4 = t * t * t * t;                               // exact: (j+1)^4 < 2^53
+        const double a = 3.3e-8 * t4;
+        const double b = 3e-3 + a;
+        const double p = model == MC_SIM_ERR_ILLUMINA ? b / 100.0 : model == MC_SIM_ERR_UNIFORM ? rate : 0.0;
+        thr[j] = p >= 1.0 ? (1ull << 32) : (uint64_t)(p * 4294967296.0);
+    }
+}
+
+// the contig of valid start u: the last c with vstart[c] <= u
+MC_SIM_HD int mc_sim_contig(const int64_t *vstart, int ncontig, uint64_t u)
+{
+    int lo = 0, hi = ncontig;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if ((uint64_t)vstart[mid] <= u) lo = mid + 1; else hi = mid; }
+    return lo - 1;
+}
+
+// One read's walk.  base(p) returns the genome byte at absolute position p; emit(o, x) stores byte o of the read; event(j, e, x),
+// if the caller wants the log, sees every consumed base (e: 0 none, 1 substitution, 2 insertion, 3 deletion, 4 deletion refused).
+// [cs, ce) is the read's contig, p0 its first consumed base, dir +1 or -1.
+template <class Base, class Emit, class Event>
+MC_SIM_HD void mc_sim_walk(Base &base, Emit &emit, Event &event, int64_t cs, int64_t ce, int64_t p0, int dir, int L, uint64_t r, const uint64_t *thr, bool errors)
+{
+    int64_t p = p0;
+    int o = 0;
+    for (int j = 0; o < L; j++, p += dir) {
+        uint8_t b = base(p);
+        if (dir < 0) b = mc_sim_comp(b);
+        int e = 0;
+        uint8_t x = 0;
+        if (errors) {
+            const uint64_t d = mc_mix64(r + (uint64_t)j * MC_SIM_GAMMA);
+            if ((d >> 32) < thr[j < MC_SIM_NTHR ? j : MC_SIM_NTHR - 1]) {
+                const uint32_t kind = (uint32_t)(d >> 16) & 0xFFFFu;
+                x = (uint8_t)(0x54474341u >> (8 * (uint32_t)(d & 3)));     // "ACGT"[d & 3]
+                e = kind < MC_SIM_SUB ? 1 : kind < MC_SIM_INS ? 2 : 3;
+                if (e == 3 && (dir > 0 ? ce - 1 - p : p - cs) < (int64_t)(L - o)) e = 4;
+            }
+        }
+        event(j, e, x);
+        if (e == 0 || e == 4) emit(o++, b);
+        else if (e == 1) emit(o++, x);
+        else if (e == 2) { emit(o++, x); if (o < L) emit(o++, b); }
+    }
+}
+
+struct McSimNoEvent {
+    MC_SIM_HD void operator()(int, int, uint8_t) const {}
+};

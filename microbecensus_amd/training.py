@@ -1,7 +1,7 @@
 """Training a model: the reference's training/ workflow (TRAINING.txt steps 1 - 4) with simulation, search and grid
 classification on the GPU (mc_train_library) and the parameter fit of optimize_parameters.py on the host.
 
-    genomes_dir/*.fna.gz  --simulate (seq_sim.py: single end, no errors, --cov), search (-e 1), grid-classify-->  per-family counts
+    genomes_dir/*.fna.gz  --simulate (seq_sim.py --cov [-e -r] [-p -i]), search (-e 1), grid-classify-->  per-family counts
     counts / library bp   --x-fold cross-validation (training.py:71-169)-->  pars.map, coefficients.map, ...  + model.json
 
 Two orders the reference leaves to chance are fixed here: genomes are taken in sorted name order (the reference: os.listdir
@@ -9,6 +9,9 @@ order, which decides the folds), and the candidates of one (read length, family)
 max_pid ascending, then aln_cov ascending, then rate type hits / aln / cov - the FIRST strict minimum of the cross-validation
 error wins (the reference: whichever of its parallel processes finished first).  Weights are not fitted (optimize_weights.R):
 every (read length, family) gets weight 1.0.
+
+Libraries are single end without errors by default; error_model ('uniform' at error_rate, or 'illumina') and paired_end (with an
+insert) give seq_sim.py's other kinds (csrc/mc_simlib.h), with one deviation: every read keeps exactly L bases.
 """
 import glob
 import gzip
@@ -26,6 +29,7 @@ MIN_SCORES = list(range(23, 50))
 RATE_TYPES = ("hits", "aln", "cov")
 MIN_READ_LEN, MAX_READ_LEN = 18, 510          # what the engine searches (mc_set_run)
 MAX_FAMILIES, MAX_MARKERS = 32, 32767          # the engine's limits
+ERROR_MODELS = ("illumina", "uniform")
 
 
 class TrainingError(ValueError):
@@ -111,7 +115,14 @@ def library_id(genome_name, read_len):
     return (int(read_len) << 32) | zlib.crc32(genome_name.encode())
 
 
-def check_request(genomes, read_lengths, xfolds, coverage, n_families, n_markers):
+def library_record(error_model=None, error_rate=None, paired_end=False, insert=None):
+    """model.json's "library" record of a library kind; None for the default (single end, no errors)."""
+    if error_model is None and not paired_end:
+        return None
+    return {"error_model": error_model, "error_rate": error_rate, "paired_end": bool(paired_end), "insert": insert if paired_end else None}
+
+
+def check_request(genomes, read_lengths, xfolds, coverage, n_families, n_markers, error_model=None, error_rate=None, paired_end=False, insert=None):
     """Every refusal of a training run, before any GPU work."""
     if not read_lengths:
         raise TrainingError("no read length given (-l)")
@@ -130,6 +141,20 @@ def check_request(genomes, read_lengths, xfolds, coverage, n_families, n_markers
         raise TrainingError("%d marker sequences: the engine takes at most %d" % (n_markers, MAX_MARKERS))
     if n_markers == 0:
         raise TrainingError("the gene family files hold no sequences")
+    if error_model is not None and error_model not in ERROR_MODELS:
+        raise TrainingError("unknown error model %r (illumina or uniform)" % (error_model,))
+    if error_model == "uniform" and error_rate is None:
+        raise TrainingError("the uniform error model needs an error rate (--error-rate)")
+    if error_rate is not None and error_model != "uniform":
+        raise TrainingError("an error rate (--error-rate) goes only with the uniform error model")
+    if error_rate is not None and not 0 <= error_rate <= 1:
+        raise TrainingError("error rate %s outside [0, 1]" % error_rate)
+    if paired_end and insert is None:
+        raise TrainingError("a paired-end library needs an insert (--insert)")
+    if insert is not None and not paired_end:
+        raise TrainingError("an insert (--insert) goes only with a paired-end library (--paired-end)")
+    if paired_end and insert < max(read_lengths):
+        raise TrainingError("insert %d is shorter than the read length %d" % (insert, max(read_lengths)))
 
 
 # ---- the fit (optimize_parameters.py, training.py:71-169) --------------------------------------------------------------------
@@ -187,14 +212,17 @@ def fit(rates, sizes, xfolds):
 
 
 # ---- outputs ------------------------------------------------------------------------------------------------------------------
-def write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, genome_sizes=None, preds=None):
-    """markers.faa.gz + model.json (the packaged schema, tools/build_data.py) and the reference's tables."""
+def write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, genome_sizes=None, preds=None, library=None):
+    """markers.faa.gz + model.json (the packaged schema, tools/build_data.py, plus the "library" record of a kind other than the
+    default) and the reference's tables."""
     os.makedirs(out_dir, exist_ok=True)
     with gzip.GzipFile(os.path.join(out_dir, "markers.faa.gz"), "wb", mtime=0) as f:
         for name, seq in zip(names, seqs):
             f.write((">%s\n%s\n" % (name, seq)).encode())
     model = {"families": list(families), "marker_family": list(marker_family), "read_lengths": sorted(int(L) for L in read_lengths),
              "pars": pars, "coefficients": coefficients, "weights": weights}
+    if library is not None:
+        model["library"] = library
     with open(os.path.join(out_dir, "model.json"), "w") as f:
         json.dump(model, f, separators=(",", ":"), sort_keys=True)
     with open(os.path.join(out_dir, "pars.map"), "w") as f:
@@ -233,12 +261,12 @@ def read_map(path, header=False):
     return [ln.split("\t") for ln in lines[1 if header else 0:] if ln]
 
 
-def write_reads(path, reads):
-    """A library in seq_sim.py's format: '>id\\nseq\\n', ids 0, 1, ..."""
+def write_reads(path, reads, paired_end=False):
+    """A library in seq_sim.py's format: '>id\\nseq\\n', ids 0, 1, ...; paired end: '>k/1', '>k/2' for rows 2k, 2k + 1."""
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "wb") as f:
         for i in range(reads.shape[0]):
-            f.write(b">%d\n" % i)
+            f.write(b">%d/%d\n" % (i >> 1, 1 + (i & 1)) if paired_end else b">%d\n" % i)
             f.write(reads[i].tobytes())
             f.write(b"\n")
 
@@ -255,9 +283,12 @@ def write_hits(path, families, hits, aln, cov):
 
 
 # ---- the run ------------------------------------------------------------------------------------------------------------------
-def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfolds=10, seed=0, device=0, write_reads_dir=None, log=print):
-    """TRAINING.txt steps 1 - 4 in one call.  Returns the model dict written to out_dir/model.json, with the run's rates under
-    '_rates' ({L: (genomes, families, candidates)}) and the genomes' sizes under '_sizes'."""
+def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfolds=10, seed=0, device=0, write_reads_dir=None, log=print,
+          error_model=None, error_rate=None, paired_end=False, insert=None):
+    """TRAINING.txt steps 1 - 4 in one call.  A paired-end library at coverage c holds library_reads(c, G, L) pairs (seq_sim.py's
+    read_id counts pairs), so twice as many reads; a library's bp is its reads x L either way.  Returns the model dict written to
+    out_dir/model.json, with the run's rates under '_rates' ({L: (genomes, families, candidates)}) and the genomes' sizes under
+    '_sizes'."""
     from . import _native
     read_lengths = [int(L) for L in read_lengths]
     genomes = list_genomes(genomes_dir)
@@ -265,21 +296,28 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
         names, seqs, marker_family, families = build_marker_set(list_families(gene_fams_dir))
     else:
         names, seqs, marker_family, families = packaged_marker_set()
-    check_request(genomes, read_lengths, xfolds, coverage, len(families), len(names))
+    check_request(genomes, read_lengths, xfolds, coverage, len(families), len(names), error_model, error_rate, paired_end, insert)
+    library = library_record(error_model, error_rate, paired_end, insert)
     loaded = []
     for gname, path in genomes:
         bases, off = _native.read_fasta_genome(path)
         longest = int(np.max(np.diff(off))) if len(off) > 1 else 0
         for L in read_lengths:
-            if longest < L:
-                raise TrainingError("genome %s has no contig of at least %d bp" % (gname, L))
+            span = insert if paired_end else L
+            if longest < span:
+                raise TrainingError("genome %s has no contig of at least %d bp" % (gname, span))
         loaded.append((gname, bases, off))
     sizes = {g: int(off[-1]) for g, _, off in loaded}
     size_list = [sizes[g] for g, _, _ in loaded]
     log("Training on %d genomes, %d gene families (%d markers), read lengths %s, %sx coverage, %d-fold cross-validation"
         % (len(loaded), len(families), len(names), read_lengths, coverage, xfolds))
+    if library is not None:
+        log("Library: %s" % ", ".join("%s %s" % kv for kv in sorted(library.items()) if kv[1] not in (None, False)))
     eng = _native.Engine(device=device, names=names, seqs=seqs, marker_family=marker_family, nfam=len(families))
     gpu_genomes = [_native.Genome(bases, off, device) for _, bases, off in loaded]
+    if library is not None:
+        for g in gpu_genomes:
+            g.set_library(error_model, error_rate, paired_end, insert)
     cands = candidates()
     pars, coefficients, weights, preds, all_rates = {}, {}, {}, [], {}
     try:
@@ -287,13 +325,13 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
             eng.set_run(L)
             counts, lib_bp = [], []
             for (gname, _, _), g in zip(loaded, gpu_genomes):
-                n = library_reads(coverage, sizes[gname], L)
+                n = library_reads(coverage, sizes[gname], L) * (2 if paired_end else 1)
                 lid = library_id(gname, L)
                 hits, aln, cov = eng.train_library(g, n, seed, lid, ALN_COVS, MAX_PIDS, MIN_SCORES)
                 counts.append((hits, aln, cov))
                 lib_bp.append(n * L)
                 if write_reads_dir:
-                    write_reads(os.path.join(write_reads_dir, str(L), gname + "-reads.fa"), g.simulate(L, n, seed, lid))
+                    write_reads(os.path.join(write_reads_dir, str(L), gname + "-reads.fa"), g.simulate(L, n, seed, lid), paired_end)
                     write_hits(os.path.join(write_reads_dir, str(L), gname + ".hits"), families, hits, aln, cov)
                 log("  L=%d %s: %d reads" % (L, gname, n))
             rates = rates_by_candidate([c[0] for c in counts], [c[1] for c in counts], [c[2] for c in counts], lib_bp)
@@ -310,7 +348,7 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
         for g in gpu_genomes:
             g.close()
         eng.close()
-    model = write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, sizes, preds)
+    model = write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, sizes, preds, library)
     zero = sorted(k for k, v in coefficients.items() if v == 0)
     if zero:
         log("Families no genome's reads were assigned to (coefficient 0): %s" % ", ".join(zero))

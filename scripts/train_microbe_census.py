@@ -2,6 +2,7 @@
 """Train a MicrobeCensus model on the GPU: the reference's training/ workflow (TRAINING.txt steps 1 - 4) in one command.
 
     train_microbe_census.py <genomes_dir> <out_dir> -l 100,150 -c 10 [--gene-fams DIR] [-x 10] [--seed S] [-g device] [--write-reads DIR]
+        [--error-model illumina|uniform [--error-rate R]] [--paired-end --insert I]
 
 out_dir receives markers.faa.gz and model.json (use them with run_microbe_census.py --model out_dir) and the reference's tables
 (pars.map, coefficients.map, weights.map, read_len.map, gene_fam.map, gene_len.map, training_preds.map)."""
@@ -26,6 +27,11 @@ def parse_arguments(argv=None):
     p.add_argument("--seed", dest="seed", type=int, default=0, help="seed of the read simulator (default 0)")
     p.add_argument("-g", dest="device", type=int, default=0, help="GPU index (default 0)")
     p.add_argument("--write-reads", dest="write_reads", default=None, help="also write every library as <DIR>/<L>/<genome>-reads.fa and its grid counts as <genome>.hits")
+    p.add_argument("--error-model", dest="error_model", choices=training.ERROR_MODELS, default=None,
+                   help="sequencing errors of the simulated reads (seq_sim.py -e; default: none)")
+    p.add_argument("--error-rate", dest="error_rate", type=float, default=None, help="per-base error rate of --error-model uniform (seq_sim.py -r)")
+    p.add_argument("--paired-end", dest="paired_end", action="store_true", help="simulate mate pairs (seq_sim.py -p): reads k/1 and k/2 of every fragment")
+    p.add_argument("--insert", dest="insert", type=int, default=None, help="fragment length of --paired-end, at least the read length (seq_sim.py -i)")
     args = p.parse_args(argv)
     try:
         args.read_lengths = [int(x) for x in args.read_lengths.split(",") if x.strip()]
@@ -38,7 +44,8 @@ def main(argv=None):
     a = parse_arguments(argv)
     try:
         training.train(a.genomes_dir, a.out_dir, a.read_lengths, a.coverage, gene_fams_dir=a.gene_fams, xfolds=a.xfolds, seed=a.seed,
-                       device=a.device, write_reads_dir=a.write_reads)
+                       device=a.device, write_reads_dir=a.write_reads, error_model=a.error_model, error_rate=a.error_rate,
+                       paired_end=a.paired_end, insert=a.insert)
     except training.TrainingError as e:
         sys.exit("Error: %s" % e)
 
