@@ -147,7 +147,9 @@ int mc_write_m8_named(mc_handle *h, const char *path, int append, const char *co
  * that pass alignment coverage >= aln_cov, identity <= max_pid (integers, as in class_reads.py), bit score >= min_score; per
  * read the best-scoring survivor (the first on a tie); per family the number of such reads, the sum of their alignment lengths,
  * the sum of alignment length / target length.  Outputs are [n_cov][n_pid][n_score][nfam] arrays; hits and aln are exact, the
- * coverage sums are accumulated in no fixed order (1e-12 relative against the reference's sequential sum).  One device pass. */
+ * coverage sums are accumulated in no fixed order (1e-12 relative against the reference's sequential sum).  One device pass.
+ * Cut-offs may come in any order and repeat.  Refused: more than 8 aln_covs, 8 max_pids or 64 min_scores, and a NaN or infinite
+ * aln_cov or min_score. */
 int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_cov, const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score,
                      int64_t *count_hits, int64_t *count_aln, double *count_cov);
 

@@ -3,6 +3,7 @@ missing or no MI355X is visible, importing the engine fails loudly."""
 import ctypes as C
 import gzip
 import json
+import math
 import os
 import sys
 
@@ -547,6 +548,18 @@ class Genome:
             pass
 
 
+def _grid_pids(max_pids):
+    """The grid's max_pids as the C ints the ABI takes.  A non-integral value is refused: the reference's pid_filter compares the
+    printed identity with the float, and the kernel's integer test would not be that comparison."""
+    out = []
+    for p in max_pids:
+        f = float(p)
+        if not math.isfinite(f) or f != int(f):
+            raise ValueError("max_pids must be integers (%r given)" % (p,))
+        out.append(int(f))
+    return out
+
+
 class Engine:
     """One MI355X: marker index resident in HBM + the search/classify pipeline."""
 
@@ -727,7 +740,7 @@ class Engine:
         nc, npid, ns = len(aln_covs), len(max_pids), len(min_scores)
         shape = (nc, npid, ns, self.nfam)
         hits = np.zeros(shape, np.int64); aln = np.zeros(shape, np.int64); cov = np.zeros(shape, np.float64)
-        self._check(self.lib.mc_grid_classify(self.h, (C.c_double * nc)(*aln_covs), nc, (C.c_int32 * npid)(*[int(p) for p in max_pids]), npid, (C.c_double * ns)(*min_scores), ns,
+        self._check(self.lib.mc_grid_classify(self.h, (C.c_double * nc)(*aln_covs), nc, (C.c_int32 * npid)(*_grid_pids(max_pids)), npid, (C.c_double * ns)(*min_scores), ns,
                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), aln.ctypes.data_as(C.POINTER(C.c_int64)), cov.ctypes.data_as(C.POINTER(C.c_double))),
                     "mc_grid_classify")
         return hits, aln, cov
@@ -744,7 +757,7 @@ class Engine:
         shape = (nc, npid, ns, self.nfam)
         hits = np.zeros(shape, np.int64); aln = np.zeros(shape, np.int64); cov = np.zeros(shape, np.float64)
         self._check(self.lib.mc_train_library(self.h, genome.g, int(nreads), int(seed), int(library_id), (C.c_double * nc)(*aln_covs), nc,
-                                              (C.c_int32 * npid)(*[int(p) for p in max_pids]), npid, (C.c_double * ns)(*min_scores), ns,
+                                              (C.c_int32 * npid)(*_grid_pids(max_pids)), npid, (C.c_double * ns)(*min_scores), ns,
                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), aln.ctypes.data_as(C.POINTER(C.c_int64)), cov.ctypes.data_as(C.POINTER(C.c_double))),
                     "mc_train_library")
         return hits, aln, cov

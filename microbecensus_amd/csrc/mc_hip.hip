@@ -1225,6 +1225,9 @@ static int grid_pars(const mc_handle *h, const double *aln_covs, int32_t n_cov, 
 {
     if (n_cov < 1 || n_cov > MC_GRID_MAXC || n_pid < 1 || n_pid > MC_GRID_MAXP || n_score < 1 || n_score > MC_GRID_MAXS) { g_err = "grid larger than 8 x 8 x 64"; return -1; }
     if (!aln_covs || !max_pids || !min_scores) { g_err = "null argument"; return -1; }
+    // (NaN breaks the strict weak ordering std::sort needs; infinities are refused with it: no grid of the training workflow has one)
+    for (int i = 0; i < n_cov; i++) if (!std::isfinite(aln_covs[i])) { g_err = "aln_covs[" + std::to_string(i) + "] is not finite"; return -1; }
+    for (int i = 0; i < n_score; i++) if (!std::isfinite(min_scores[i])) { g_err = "min_scores[" + std::to_string(i) + "] is not finite"; return -1; }
     memset(&G, 0, sizeof G);
     G.read_len = h->read_len; G.n_cov = n_cov; G.n_pid = n_pid; G.n_score = n_score; G.nfam = h->nfam;
     for (int i = 0; i < n_cov; i++) G.cov[i] = aln_covs[i];
