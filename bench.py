@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - reads/s of the MI355X translated-search hot path on synthetic shotgun reads.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 With N > 1 and no torchrun environment, bench.py starts the N ranks itself (a child `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N ... bench.py ...`, started before anything touches the GPU), relays rank 0's JSON line and
@@ -18,9 +18,12 @@ mc_search / mc_search_files issue their batches: mc_range_end(i), mc_range_begin
 of the next step is enqueued before the host sums up (--one-at-a-time: mc_run_range per step).  The timed region holds exactly
 K steps, each from its first kernel to its results on the host.
 
-Rank 0 prints ONE JSON line: metric / value (whole-job reads/s), ms_per_step (the wall time of one timed step), `roofline` for the
-dominant kernel and, at N = 1, `cpu_baseline` (the reference's own RAPsearch2 binary on this host's cores on bounded samples of the same
-reads, m8 compared by md5) and `e2e` (file -> AGS through run_pipeline).
+Rank 0 prints ONE JSON line: metric / value (whole-job reads/s), ms_per_step (the wall time of one timed step) and `roofline` for the
+dominant kernel.  A plain run does only that: set-up, warm-up, the K timed steps, --dump-outputs, the line.  --full adds what takes
+runs of its own: `classification_only` (the same steps best hits only), `roofline.reference_pattern` (one counting launch), at N = 1
+`cpu_baseline` (the reference's own RAPsearch2 binary on this host's cores on bounded samples of the same reads, m8 compared by md5),
+`config.ags_abs_error_vs_reference` and `e2e` (file -> AGS through run_pipeline), at N > 1 `e2e` (run_pipeline_distributed) and `rccl`.
+Under --full each of these can still be switched off by its own option (--no-cpu-baseline, --e2e-reads 0, ...).
 
 --dump-outputs DIR: rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy (float64): the m8 rows
 (rows_<field>), the best hits (best_hits_<field>) and the per-family accumulators of the step (family_hits, family_aln: summed over
@@ -645,9 +648,14 @@ def main():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="nccl = RCCL, one GPU per rank (the measurement); gloo: all ranks on GPU 0, reductions on the host - "
                                                                                "only to exercise the N > 1 code path on a one-GPU box")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see the module's docstring)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: best-hits-only steps, the counting launch, cpu_baseline, the AGS check, "
+                                                        "e2e and, at N > 1, the rccl evidence (the --no-* / --*-reads options above apply only with --full)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                       # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line - nothing else
+        args.no_best_only_leg = args.no_reference_pattern = args.no_cpu_baseline = args.no_ags_check = True
+        args.e2e_reads = args.c5_reads = 0
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -815,7 +823,7 @@ def main():
                            "formula": "8 B x bucket lookups + 2 B x key reads of the binary searches + 20 B x seed hits + 6 x (L / 3) B of frames, per read; counted by one untimed "
                                       "launch of k_enumerate_count on batch 0"}
     rccl = None
-    if world > 1:
+    if world > 1 and args.full:
         # evidence that the collective really spanned `world` ranks: every rank contributes rank + 1 to a sum (must be N (N + 1) / 2) and its
         # LOCAL_RANK's device index to a bit mask; the crc of the reduced per-family vector the estimate is made from
         import zlib

@@ -178,7 +178,7 @@ def test_bench_four_ranks_on_one_gpu_equals_one_engine(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(W), "--backend", "gloo", "--batch", str(B), "--steps", str(K), "--warmup", "1",
-                          "--no-cpu-baseline", "--e2e-reads", "2000000", "--c5-reads", "0"], env=env, stdout=subprocess.PIPE, timeout=1500, check=True).stdout.decode()
+                          "--full", "--no-cpu-baseline", "--e2e-reads", "2000000", "--c5-reads", "0"], env=env, stdout=subprocess.PIPE, timeout=1500, check=True).stdout.decode()
     line = json.loads([l for l in out.splitlines() if l.startswith('{"metric"')][-1])
     r = line["rccl"]
     assert line["n_gpus"] == W and r["world_size"] == W and r["rank_sum"] == W * (W + 1) // 2 == r["rank_sum_expected"] and r["backend"] == "gloo"
