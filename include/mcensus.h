@@ -92,6 +92,17 @@ int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const double *mi
  * first_read_id is added to the read index to form the query id. */
 int mc_search(mc_handle *h, const uint8_t *reads, int64_t nreads, int64_t first_read_id);
 
+/* The same on reads of MIXED lengths, as a FASTA holds them: read i is bases[offsets[i] .. offsets[i + 1]) (offsets: nreads + 1
+ * ascending values; the reads lie back to back).  Each read is searched at its own length - translation, seeds, extension and the
+ * E-value (RAPsearch2's length adjustment of the query) - exactly as `rapsearch` searches it in a file of reads of many lengths;
+ * classification (best hits) uses mc_set_run()'s read_len, the nominal length class_reads.py and alignment_coverage divide by.
+ * A read shorter than 18 bases has no frame of more than 5 residues, which RAPsearch2 skips: it has no rows.  The reads are bucketed
+ * by length on the device and the fixed-length pipeline runs once per bucket; results as after mc_search() (rows in ascending read
+ * id = first_read_id + i, RAPsearch2's order within a read; best hits by read id), and mc_write_m8 / mc_write_m8_named take them.
+ * A batch whose reads all have mc_set_run()'s length is mc_search() itself.  Refused: an empty read, a read longer than 510 bases
+ * (the message names the read), more than 2^31 - 1 reads. */
+int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offsets, int64_t nreads, int64_t first_read_id);
+
 /* Same pipeline on reads that are already resident in HBM (bench / streaming):
  * mc_upload() copies a batch to the device, mc_run() executes the kernels on it (no host transfers of reads). */
 int mc_upload(mc_handle *h, const uint8_t *reads, int64_t nreads);
@@ -167,12 +178,25 @@ int mc_simulate(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64
  * error_model MC_ERR_NONE, MC_ERR_UNIFORM (error_rate per consumed base, in [0, 1]) or MC_ERR_ILLUMINA (position-dependent rate of
  * sim_functions.py); paired_end with insert >= the read length: row 2k is mate 1 of fragment k (forward), row 2k + 1 mate 2 (the
  * reverse complement of the fragment's last read_len bases).  Every read keeps read_len bases: the first read_len the error
- * process emits (the reference's reads are read_len + insertions - deletions long).  csrc/mc_simlib.h states the formula.  NULL
+ * process emits (the reference's reads are read_len + insertions - deletions long: mc_genome_set_read_lengths below gives those).
+ * csrc/mc_simlib.h states the formula.  NULL
  * restores the default (single end, no errors).  Refused: an unknown model, a rate outside [0, 1], paired end with insert < 1 or
  * longer than every contig; at simulation time, insert < read_len and (mc_train_library) an odd number of paired-end reads. */
 enum { MC_ERR_NONE = 0, MC_ERR_UNIFORM = 1, MC_ERR_ILLUMINA = 2 };
 typedef struct mc_library { int32_t paired_end, insert, error_model; double error_rate; } mc_library;
 int mc_genome_set_library(mc_genome *g, const mc_library *lib);
+/* The read lengths of the libraries mc_simulate_varlen() and mc_train_library() make of this genome from now on.  MC_READLEN_FIXED
+ * (default): every read keeps read_len bases, as above.  MC_READLEN_REFERENCE: seq_sim.py's reads - the walk consumes the fragment
+ * bases 0 .. read_len - 1 and emits what the error process makes of them, read_len + insertions - deletions bases (the same draws;
+ * under MC_ERR_NONE the two modes give the same reads); csrc/mc_simlib.h states the formula.  A read of more than 510 bases is refused
+ * when it is simulated (the message names it), never cut.  Refused: any other mode. */
+enum { MC_READLEN_FIXED = 0, MC_READLEN_REFERENCE = 1 };
+int mc_genome_set_read_lengths(mc_genome *g, int32_t mode);
+/* Reads [first, first + n) of library (seed, library_id) in the reference read-length mode (whatever the genome's mode): their bases
+ * back to back into dst_host (range by range while they fit in dst_cap bytes; dst_host NULL: none - call so to learn the size) and
+ * offsets[0 .. n] (offsets[0] = 0; always written).  Returns the total number of bases, or < 0. */
+int64_t mc_simulate_varlen(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host,
+                           int64_t dst_cap, int64_t *offsets);
 /* One library pass: reads [0, nreads) of library (seed, library_id) at mc_set_run()'s read length and E-value threshold, simulated
  * straight into the handle's resident read buffer range by range (MC_STREAM_BATCH reads; mc_upload's buffer: the resident read set
  * is the last range afterwards), searched, and grid-classified on the device as mc_grid_classify() does it (same arguments and
@@ -180,7 +204,12 @@ int mc_genome_set_library(mc_genome *g, const mc_library *lib);
  * last run's rows and best hits are empty afterwards; mc_result_stats() holds the search's totals. */
 int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint64_t seed, uint64_t library_id, const double *aln_covs, int32_t n_cov,
                      const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score, int64_t *count_hits, int64_t *count_aln, double *count_cov);
-/* Milliseconds of the last mc_train_library() from HIP events: [0] simulation, [1] search (the stages' own events), [2] grid. */
+/* In the reference read-length mode a range is simulated in two passes, bucketed by length on the device, and every bucket is searched
+ * at its own length (mc_search_varlen) and grid-classified into the same bins - classification at mc_set_run()'s read length, as
+ * class_reads.py passes it.  The bases of the last mc_train_library()'s reads: nreads x read_len in the fixed mode, their real
+ * total in the reference mode (the reference's rate denominator, training.py's library_sizes). */
+int64_t mc_train_library_bases(const mc_handle *h);
+/* Milliseconds of the last mc_train_library() from HIP events: [0] simulation (and, in the reference mode, bucketing), [1] search (the stages' own events), [2] grid. */
 int mc_train_times(const mc_handle *h, float *ms);
 
 /* ---- host stage in front of the search: native read sampler (csrc/mc_reader.cpp; no GPU involved) ----------------

@@ -100,6 +100,7 @@ def load_library():
     lib.mc_index_view.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     lib.mc_set_run.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.mc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+    lib.mc_search_varlen.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
     lib.mc_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.mc_run.argtypes = [C.c_void_p, C.c_int64]
     lib.mc_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -181,15 +182,21 @@ def load_library():
     lib.mc_train_library.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                      C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     lib.mc_train_times.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.mc_genome_set_read_lengths.argtypes = [C.c_void_p, C.c_int32]
+    lib.mc_simulate_varlen.restype = C.c_int64
+    lib.mc_simulate_varlen.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mc_train_library_bases.restype = C.c_int64
+    lib.mc_train_library_bases.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 
 
-EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "mc_set_index_cache", "mc_index_cache_check", "mc_open_rapdb", "mc_marker_count", "mc_marker_name", "mc_set_families", "mc_rapdb_verify", "mc_rapdb_write", "mc_index_view", "mc_set_run", "mc_search",
+EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "mc_set_index_cache", "mc_index_cache_check", "mc_open_rapdb", "mc_marker_count", "mc_marker_name", "mc_set_families", "mc_rapdb_verify", "mc_rapdb_write", "mc_index_view", "mc_set_run", "mc_search", "mc_search_varlen",
                     "mc_upload", "mc_attach", "mc_run", "mc_run_range", "mc_set_counting", "mc_debug_stage", "mc_range_begin", "mc_range_end", "mc_ranges_in_flight", "mc_result_rows", "mc_result_best_hits", "mc_result_stats", "mc_write_m8", "mc_write_m8_named",
                     "mc_reader_last_error", "mc_set_host_threads", "mc_reader_open", "mc_reader_open_range", "mc_reader_open_bz2_part", "mc_bz2_blocks", "mc_gz_chunks", "mc_reader_open_gz_part", "mc_reader_gz_provide", "mc_reader_gz_end_state", "mc_reader_gz_finish", "mc_reader_run", "mc_reader_reads", "mc_reader_get_stats", "mc_reader_times", "mc_reader_describe", "mc_dupset_open", "mc_dupset_close", "mc_dupset_walk", "mc_reader_take", "mc_reader_close", "mc_reader_trim", "mc_count_bases", "mc_quality_offset",
                     "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify",
-                    "mc_genome_open", "mc_genome_close", "mc_genome_set_library", "mc_simulate", "mc_train_library", "mc_train_times"]
+                    "mc_genome_open", "mc_genome_close", "mc_genome_set_library", "mc_simulate", "mc_train_library", "mc_train_times",
+                    "mc_genome_set_read_lengths", "mc_simulate_varlen", "mc_train_library_bases"]
 
 
 class DupSet:
@@ -530,6 +537,27 @@ class Genome:
         if self.lib.mc_genome_set_library(self.g, lib) != 0:
             raise RuntimeError("mc_genome_set_library failed: %s" % self.lib.mc_last_error().decode())
 
+    def set_read_lengths(self, reference):
+        """reference=True: the libraries of this genome have seq_sim.py's read lengths, read_len + insertions - deletions
+        (mc_genome_set_read_lengths MC_READLEN_REFERENCE); False: every read keeps read_len bases (the default)."""
+        self.set_read_length_mode(1 if reference else 0)
+
+    def set_read_length_mode(self, mode):
+        if self.lib.mc_genome_set_read_lengths(self.g, int(mode)) != 0:
+            raise RuntimeError("mc_genome_set_read_lengths failed: %s" % self.lib.mc_last_error().decode())
+
+    def simulate_varlen(self, read_len, n, seed, library_id, first=0):
+        """Reads [first, first + n) in the reference read-length mode: (bases uint8, offsets int64 of n + 1)."""
+        offsets = np.zeros(int(n) + 1, np.int64)
+        args = (self.g, int(read_len), int(first), int(n), int(seed), int(library_id))
+        total = self.lib.mc_simulate_varlen(*args, None, 0, offsets.ctypes.data_as(C.c_void_p))
+        if total < 0:
+            raise RuntimeError("mc_simulate_varlen failed: %s" % self.lib.mc_last_error().decode())
+        bases = np.empty(max(int(total), 1), np.uint8)
+        if self.lib.mc_simulate_varlen(*args, bases.ctypes.data_as(C.c_void_p), int(total), offsets.ctypes.data_as(C.c_void_p)) != total:
+            raise RuntimeError("mc_simulate_varlen failed: %s" % self.lib.mc_last_error().decode())
+        return bases[:int(total)], offsets
+
     def simulate(self, read_len, n, seed, library_id, first=0):
         out = np.empty((int(n), int(read_len)), dtype=np.uint8)
         if self.lib.mc_simulate(self.g, int(read_len), int(first), int(n), int(seed), int(library_id), out.ctypes.data_as(C.c_void_p)) != 0:
@@ -638,6 +666,26 @@ class Engine:
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         assert reads.ndim == 2 and reads.shape[1] == self.read_len
         self._check(self.lib.mc_search(self.h, reads.ctypes.data_as(C.c_void_p), reads.shape[0], first_read_id), "mc_search")
+        return self.results()
+
+    def search_varlen(self, reads, first_read_id=0):
+        """reads of mixed lengths (mc_search_varlen): a list of bytes / str, or (bases uint8 array, offsets int64 array of n + 1).
+        Each read is searched at its own length; best hits are classified at set_run()'s length.  Returns (rows, best_hits)."""
+        if isinstance(reads, tuple):
+            bases, offsets = reads
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            if bases.ndim != 1 or offsets.ndim != 1 or len(offsets) < 1:
+                raise ValueError("search_varlen: bases and offsets must be 1-D, offsets of n + 1 values")
+            if len(offsets) > 1 and (offsets[0] < 0 or offsets[-1] > len(bases) or (np.diff(offsets) < 0).any()):
+                raise ValueError("search_varlen: offsets must ascend from >= 0 to at most len(bases)")
+        else:
+            seqs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in reads]
+            bases = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+            offsets = np.zeros(len(seqs) + 1, np.int64)
+            np.cumsum([len(s) for s in seqs], out=offsets[1:])
+        self._check(self.lib.mc_search_varlen(self.h, bases.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), len(offsets) - 1, first_read_id),
+                    "mc_search_varlen")
         return self.results()
 
     def set_best_hits_only(self, on):
@@ -761,6 +809,10 @@ class Engine:
                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), aln.ctypes.data_as(C.POINTER(C.c_int64)), cov.ctypes.data_as(C.POINTER(C.c_double))),
                     "mc_train_library")
         return hits, aln, cov
+
+    def train_library_bases(self):
+        """bases of the last train_library's reads: nreads x read_len, or their real total in the reference read-length mode"""
+        return int(self.lib.mc_train_library_bases(self.h))
 
     def train_times(self):
         """{'simulate', 'search', 'grid'}: milliseconds of the last train_library (HIP events)."""

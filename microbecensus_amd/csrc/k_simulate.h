@@ -84,3 +84,60 @@ __global__ void __launch_bounds__(64) k_simulate_lib(const uint8_t *__restrict__
     for (int t = threadIdx.x; t < (nb >> 2); t += 64) ((uint32_t *)out)[t] = ((const uint32_t *)s_rows)[t];
     for (int t = (nb & ~3) + threadIdx.x; t < nb; t += 64) out[t] = s_rows[t];
 }
+
+// The reference read-length mode (mc_simlib.h, mc_sim_walk_ref): reads of L + insertions - deletions bases, back to back.  Two passes
+// over the same pure function of (seed, library, row): lens != NULL writes each read's length; otherwise the read is written at
+// dst + off[k] - off[0] (off: the exclusive scan of the lengths, k_sim_scan).  A lane per read.
+__global__ void __launch_bounds__(64) k_simulate_var(const uint8_t *__restrict__ bases, const int64_t *__restrict__ off, const int64_t *__restrict__ vstart,
+                                                     int ncontig, McSimKind kind, const uint64_t *__restrict__ thr, uint64_t key, uint64_t ekey, int64_t first,
+                                                     int64_t n, uint32_t *__restrict__ lens, const int64_t *__restrict__ roff, uint8_t *__restrict__ dst)
+{
+    __shared__ uint64_t s_thr[MC_SIM_NTHR];
+    if (kind.errors) for (int t = threadIdx.x; t < MC_SIM_NTHR; t += 64) s_thr[t] = thr[t];
+    __syncthreads();
+    const int64_t k = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (k >= n) return;
+    const int64_t i = first + k;
+    const uint64_t u = mc_mix64(key + (uint64_t)(kind.paired ? i >> 1 : i)) % (uint64_t)vstart[ncontig];
+    const int c = mc_sim_contig(vstart, ncontig, u);
+    const int64_t s = off[c] + (int64_t)(u - (uint64_t)vstart[c]);
+    const bool rev = kind.paired && (i & 1);
+    const uint64_t *words = (const uint64_t *)bases;
+    int64_t wi = -1;
+    uint64_t word = 0;
+    auto base = [&](int64_t p) -> uint8_t {
+        if ((p >> 3) != wi) { wi = p >> 3; word = words[wi]; }
+        return (uint8_t)(word >> (8 * (p & 7)));
+    };
+    const int64_t p0 = rev ? s + kind.span - 1 : s;
+    const uint64_t r = mc_mix64(ekey + (uint64_t)i);
+    if (lens) {
+        auto count = [](int, uint8_t) {};
+        lens[k] = (uint32_t)mc_sim_walk_ref(base, count, p0, rev ? -1 : 1, kind.L, r, thr ? s_thr : nullptr, kind.errors != 0);
+    } else {
+        uint8_t *row = dst + (roff[k] - roff[0]);
+        auto emit = [&](int o, uint8_t x) { row[o] = x; };
+        (void)mc_sim_walk_ref(base, emit, p0, rev ? -1 : 1, kind.L, r, thr ? s_thr : nullptr, kind.errors != 0);
+    }
+}
+
+// exclusive scan of n read lengths into off[0 .. n] (one workgroup of 1024 threads; n <= a streaming batch)
+__global__ void __launch_bounds__(1024) k_sim_scan(const uint32_t *__restrict__ lens, int64_t n, int64_t *__restrict__ off)
+{
+    __shared__ int64_t part[1024];
+    const int64_t t = threadIdx.x, chunk = (n + 1023) / 1024;
+    const int64_t lo = min(n, t * chunk), hi = min(n, lo + chunk);
+    int64_t s = 0;
+    for (int64_t i = lo; i < hi; i++) s += lens[i];
+    part[t] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int64_t v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int64_t run = part[t] - s;
+    for (int64_t i = lo; i < hi; i++) { off[i] = run; run += lens[i]; }
+    if (t == 1023) off[n] = part[1023];
+}

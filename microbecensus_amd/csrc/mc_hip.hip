@@ -9,6 +9,7 @@
 //   k_finish.h         D   sum statistics, std::sort / heap sort replayed, 500-row cap, classification; rows in m8 order
 //   k_grid.h               the training workflow's grid classification
 //   k_simulate.h           the training workflow's library simulator
+//   k_varlen.h             reads of mixed lengths bucketed by length (mc_search_varlen)
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
 // ranges from a host-side source (mc_search, mc_search_files, mc_search_files_multi) with upload and search overlapped.
@@ -21,6 +22,9 @@
 #include "k_finish.h"
 #include "k_grid.h"
 #include "k_simulate.h"
+#include "k_varlen.h"
+
+#include <map>
 
 // ------------------------------------------------------------------------------------------------
 // handle
@@ -33,7 +37,7 @@ struct McCtx {
     hipStream_t stream = nullptr, side = nullptr, side2 = nullptr;   // the pipeline of a range, and two side streams of the ordering / finishing kernels
     hipEvent_t ev[8] = {}, ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_part[16] = {}, ev_en[16] = {};
     hipStream_t tr_stream = nullptr;                               // the translation of the next part of a range beside the seed search of this one (stage_a, MC_A_PARTS)
-    int64_t cap_reads = 0;
+    int64_t cap_reads = 0; int pool_len = 0;                       // the pools hold cap_reads reads of up to pool_len bases
     uint32_t cap_tasks = 0, cap_gaps = 0, cap_hsps = 0, cap_rows = 0;
     uint8_t *d_frames = nullptr, *d_frames_base = nullptr;   // (64 bytes of room in front: k_eval_seeds reads 8 bytes at a time backwards from a seed)
     unsigned long long *d_stats = nullptr;
@@ -70,6 +74,7 @@ struct mc_handle {
     bool best_only = false;               // only the reads that can be classified are ranked; no rows (mc_set_best_hits_only)
     bool rows_stay = false;               // mc_train_library: the rows of a range stay in the context's d_rows (no copy to the host)
     float train_ms[3] = {0, 0, 0};        // mc_train_library: simulate, search, grid of the last library (HIP events)
+    int64_t train_bases = 0;              // mc_train_library: the bases of the last library's reads (mc_train_library_bases)
     uint8_t *stage_pin[2] = {}, *stage_dev[2] = {}; size_t stage_bytes = 0; hipStream_t copy_stream = nullptr;   // run_stream
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -87,6 +92,7 @@ struct mc_handle {
     const mc_row *res_rows = nullptr; int64_t n_res_rows = 0;
     std::vector<mc_best_hit> best; mc_stats stats;
     McCtx *best_from = nullptr; uint32_t best_count = 0;           // the context whose best hits (pinned, unordered) are those of the last range, and how many: best_materialize
+    std::map<int, McTables> vl_tables; double vl_thr = 0;           // mc_search_varlen: mc_fill_tables() per bucket length, for the E-value threshold vl_thr
 };
 
 static McIndex dev_index(const mc_handle *h)
@@ -404,7 +410,7 @@ extern "C" int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const
 static void best_materialize(mc_handle *h);
 static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
 {
-    if (nreads <= c.cap_reads) return 0;
+    if (nreads <= c.cap_reads && h->read_len <= c.pool_len) return 0;   // (pools sized for longer reads fit shorter ones: mc_search_varlen)
     if (h->best_from == &c) best_materialize(h);                   // (the best hits of the range before still lie in the pinned buffer that is about to be replaced)
     double t0 = mc_now();
     int64_t cap = nreads;
@@ -434,7 +440,7 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
     if (c.h_best) { (void)hipHostFree(c.h_best); c.h_best = nullptr; }
     HIPCK(hipHostMalloc((void **)&c.h_best, sizeof(McBestHit) * ((size_t)cap + 1), hipHostMallocDefault));
     c.h_best_cap = (size_t)cap + 1;
-    c.cap_reads = cap;
+    c.cap_reads = cap; c.pool_len = (int)L;
     HIPCK(hipStreamSynchronize(c.stream));
     MC_OT("ensure_capacity (pools)", t0);
     return 0;
@@ -1202,6 +1208,174 @@ extern "C" int mc_search_files_multi(mc_handle *const *handles, int32_t n_dev, m
 
 extern "C" int mc_search_files(mc_handle *h, mc_reader *r, int64_t first_read_id) { return mc_search_files_multi(&h, 1, r, first_read_id); }
 
+// ---- reads of mixed lengths (mc_search_varlen) ---------------------------------------------------------------------------------
+// The reads are bucketed by length on the device (k_varlen.h) and the fixed-length pipeline runs once per bucket, with the tables of
+// that length (mc_fill_tables: the query length enters the E-value through the length adjustment) and the classification length of
+// mc_set_run().  Ranges are numbered by sorted position (bucket start + rank): perm maps them back to the caller's reads.
+struct McVlBuf {
+    std::vector<void *> p;
+    template <class Tp> int get(Tp **x, size_t n) { HIPCK(hipMalloc((void **)x, std::max<size_t>(n, 1) * sizeof(Tp))); p.push_back(*x); return 0; }
+    ~McVlBuf() { for (void *q : p) (void)hipFree(q); }
+};
+
+// the handle runs bucket L from now on: its tables, read length and frame pitch (the pools were sized for the longest bucket)
+static int vl_use_length(mc_handle *h, int L)
+{
+    if (h->vl_thr != h->hT.loge_thr) { h->vl_tables.clear(); h->vl_thr = h->hT.loge_thr; }
+    auto it = h->vl_tables.find(L);
+    if (it == h->vl_tables.end()) { it = h->vl_tables.emplace(L, McTables()).first; mc_fill_tables(it->second, h->H, L, h->vl_thr); }
+    HIPCK(hipMemcpy(h->d_T, &it->second, sizeof(McTables), hipMemcpyHostToDevice));
+    h->read_len = L; h->FP = ((L / 3 + 2) + 3) & ~3;
+    return 0;
+}
+
+// Buckets the nreads reads at d_bases / d_off (offsets from 0, on the device) by length: d_sorted receives every bucket's reads back to
+// back at its pitch, start[L] the bucket's first sorted position (start[MC_VL_BINS] = nreads), boff[L] its first byte, perm (device)
+// the read index of every sorted position.  Every length has been checked to lie in 1 .. 510 before.
+static int vl_bucket(McVlBuf &B, hipStream_t st, const uint8_t *d_bases, const int64_t *d_off, int64_t nreads, int64_t total, uint8_t **d_sorted,
+                     uint32_t **d_perm, std::vector<uint32_t> &start, std::vector<int64_t> &boff)
+{
+    const uint32_t ntiles = (uint32_t)((nreads + MC_VL_TILE - 1) / MC_VL_TILE);
+    int64_t *d_boff = nullptr; uint32_t *d_cnt = nullptr, *d_start = nullptr;
+    if (B.get(d_sorted, (size_t)total + 64) || B.get(&d_boff, MC_VL_BINS) || B.get(&d_cnt, (size_t)MC_VL_BINS * ntiles) || B.get(&d_start, MC_VL_BINS + 1) ||
+        B.get(d_perm, (size_t)nreads)) return -1;
+    HIPCK(hipMemsetAsync(*d_sorted + total, 0, 64, st));
+    k_vl_hist<<<dim3(ntiles), dim3(MC_VL_BS), 0, st>>>(d_off, nreads, ntiles, d_cnt);
+    HIPCK(hipGetLastError());
+    k_vl_scan<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, (uint32_t)MC_VL_BINS * ntiles, ntiles, d_start);
+    HIPCK(hipGetLastError());
+    k_vl_scatter<<<dim3(ntiles), dim3(MC_VL_BS), 0, st>>>(d_off, nreads, ntiles, d_cnt, *d_perm);
+    HIPCK(hipGetLastError());
+    start.assign(MC_VL_BINS + 1, 0);
+    HIPCK(hipMemcpyAsync(start.data(), d_start, start.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (start[MC_VL_BINS] != (uint32_t)nreads) { g_err = "internal: the length buckets do not hold every read"; return -1; }
+    boff.assign(MC_VL_BINS, 0);
+    for (int L = 1; L < MC_VL_BINS; L++) boff[(size_t)L] = boff[(size_t)L - 1] + (int64_t)(start[(size_t)L] - start[(size_t)L - 1]) * (L - 1);
+    HIPCK(hipMemcpyAsync(d_boff, boff.data(), boff.size() * 8, hipMemcpyHostToDevice, st));
+    const int64_t waves = MC_VL_BS / 64;                             // (a bounded grid: the kernel strides over the sorted positions)
+    k_vl_gather<<<dim3((unsigned)std::min<int64_t>((nreads + waves - 1) / waves, MC_VL_GATHER_BLOCKS)), dim3(MC_VL_BS), 0, st>>>(d_bases, d_off, *d_perm, nreads, d_start, d_boff, *d_sorted);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+// the buckets' pieces: lengths of 18 bases and more (a shorter read has no frame of more than 5 residues, which RAPsearch2 skips:
+// hitless), each cut into ranges of at most `batch` reads; Lmax / nmax: the longest bucket's length and the largest piece
+struct McVlPiece { int L; int64_t first, n; };
+static void vl_pieces(const std::vector<uint32_t> &start, int64_t batch, std::vector<McVlPiece> &pieces, int &Lmax, int64_t &nmax, int64_t &nshort)
+{
+    pieces.clear(); Lmax = 0; nmax = 0; nshort = 0;
+    for (int L = 1; L < MC_VL_BINS; L++) {
+        const int64_t cnt = (int64_t)(start[(size_t)L + 1] - start[(size_t)L]);
+        if (!cnt) continue;
+        if (L < 18) { nshort += cnt; continue; }
+        for (int64_t a = 0; a < cnt; a += batch) pieces.push_back({L, a, std::min(batch, cnt - a)});
+        Lmax = L; nmax = std::max(nmax, std::min(batch, cnt));
+    }
+}
+
+// the pools for the pieces: sized once, for the longest bucket, and for the larger of the largest piece and what they held before (a
+// fixed-length run after this one then finds its pools in place)
+static int vl_pools(mc_handle *h, int Lmax, int64_t nmax)
+{
+    McCtx &c = h->ctx[0];
+    h->read_len = Lmax; h->FP = ((Lmax / 3 + 2) + 3) & ~3;
+    return ensure_capacity(h, c, std::min<int64_t>(std::max(c.cap_reads, nmax), (1 << 21) - 1));
+}
+
+static int search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offsets, int64_t nreads, int64_t first_read_id)
+{
+    McCtx &c = h->ctx[0];
+    const int64_t total = offsets[nreads] - offsets[0];
+    std::vector<int64_t> off((size_t)nreads + 1);
+    for (int64_t i = 0; i <= nreads; i++) off[(size_t)i] = offsets[i] - offsets[0];
+    McVlBuf B;
+    uint8_t *d_bases = nullptr, *d_sorted = nullptr; int64_t *d_off = nullptr; uint32_t *d_perm = nullptr;
+    if (B.get(&d_bases, (size_t)total + 64) || B.get(&d_off, (size_t)nreads + 1)) return -1;
+    hipStream_t st = c.stream;
+    HIPCK(hipMemcpyAsync(d_bases, bases + offsets[0], (size_t)total, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
+    std::vector<uint32_t> start; std::vector<int64_t> boff;
+    if (vl_bucket(B, st, d_bases, d_off, nreads, total, &d_sorted, &d_perm, start, boff)) { (void)hipStreamSynchronize(st); return -1; }
+    std::vector<uint32_t> perm((size_t)nreads);
+    HIPCK(hipMemcpyAsync(perm.data(), d_perm, perm.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    std::vector<McVlPiece> pieces;
+    int Lmax = 0; int64_t nmax = 0, nshort = 0;
+    vl_pieces(start, stream_batch(), pieces, Lmax, nmax, nshort);
+    std::vector<mc_row> rows; std::vector<mc_best_hit> best; mc_stats tot; memset(&tot, 0, sizeof tot);
+    const int L0 = h->read_len, FP0 = h->FP;
+    const uint8_t *saved_reads = h->reads_dev; const int64_t saved_n = h->nreads;
+    int rc = 0;
+    if (!pieces.empty()) {
+        rc = vl_pools(h, Lmax, nmax);
+        bool pending = false;
+        auto collect = [&]() {
+            if (!pending) return;
+            pending = false;
+            if (h->keep_rows) { rows_wait(h); rows.insert(rows.end(), h->res_rows, h->res_rows + h->n_res_rows); }
+            best_materialize(h);
+            best.insert(best.end(), h->best.begin(), h->best.end());
+            stats_add(tot, h->stats);
+        };
+        auto begin = [&](const McVlPiece &q) -> int {
+            if (vl_use_length(h, q.L)) return -1;
+            h->reads_dev = d_sorted + boff[(size_t)q.L]; h->nreads = (int64_t)(start[(size_t)q.L + 1] - start[(size_t)q.L]);
+            return mc_range_begin(h, q.first, q.n, (int64_t)start[(size_t)q.L] + q.first);
+        };
+        // end(k), begin(k + 1), collect(k): the front of the next piece runs while the host takes the results of this one.  A piece
+        // that overflowed a pool is run again in smaller ranges while its length is still the handle's.
+        for (size_t k = 0; rc == 0 && k < pieces.size(); k++) {
+            if (k == 0 && (rc = begin(pieces[0])) != 0) break;
+            const McVlPiece &q = pieces[k];
+            rc = mc_range_end(h);
+            if (rc == -2) rc = mc_run_range(h, q.first, q.n, (int64_t)start[(size_t)q.L] + q.first);
+            if (rc) break;
+            pending = true;
+            if (k + 1 < pieces.size() && (rc = begin(pieces[k + 1])) != 0) break;
+            collect();
+        }
+        if (rc == 0) collect();
+        if (h->pipe_nout) (void)mc_range_end(h);                     // (after an error: nothing stays in flight)
+        rows_wait(h);
+        h->read_len = L0; h->FP = FP0;
+        const hipError_t e = hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice);   // the run's own tables back
+        if (rc == 0 && e != hipSuccess) { g_err = std::string("restoring the run's tables: ") + hipGetErrorString(e); rc = -1; }
+    }
+    h->reads_dev = saved_reads; h->nreads = saved_n;
+    h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
+    if (rc) return rc;
+    // results in the caller's order: rows grouped by original read (stable: a read's rows keep RAPsearch2's order), best hits sorted
+    std::vector<int64_t> at((size_t)nreads + 1, 0);
+    for (const mc_row &r : rows) at[(size_t)perm[(size_t)r.query] + 1]++;
+    for (int64_t i = 0; i < nreads; i++) at[(size_t)i + 1] += at[(size_t)i];
+    std::vector<mc_row> &out = h->all_rows; out.resize(rows.size());
+    for (const mc_row &r : rows) { const uint32_t o = perm[(size_t)r.query]; mc_row &d = out[(size_t)at[o]++]; d = r; d.query = (int32_t)(first_read_id + o); }
+    for (mc_best_hit &b : best) b.read = (int32_t)(first_read_id + perm[(size_t)b.read]);
+    std::sort(best.begin(), best.end(), [](const mc_best_hit &x, const mc_best_hit &y) { return x.read < y.read; });
+    tot.reads += nshort;
+    h->res_rows = out.data(); h->n_res_rows = (int64_t)out.size(); h->best.swap(best); h->stats = tot;
+    return 0;
+}
+
+extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offsets, int64_t nreads, int64_t first_read_id)
+{
+    if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
+    if (nreads < 0 || !offsets || (nreads > 0 && !bases)) { g_err = "bad argument"; return -1; }
+    if (nreads > 0x7fffffff) { g_err = "more than 2^31 - 1 reads in one call"; return -1; }
+    if (h->pipe_nout) { g_err = "ranges begun with mc_range_begin() are still in flight"; return -1; }
+    bool one = true;
+    for (int64_t i = 0; i < nreads; i++) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        if (len <= 0) { g_err = "read " + std::to_string(i) + " is empty (offsets " + std::to_string(offsets[i]) + ", " + std::to_string(offsets[i + 1]) + ")"; return -1; }
+        if (len > 3 * MC_MAXAA) { g_err = "read " + std::to_string(i) + " is " + std::to_string(len) + " bases long: longer than 510"; return -1; }
+        one = one && len == h->read_len;
+    }
+    if (one) return mc_search(h, nreads ? bases + offsets[0] : nullptr, nreads, first_read_id);   // every read of the run's length: the fixed path as it is
+    HIPCK(hipSetDevice(h->device));
+    return search_varlen(h, bases, offsets, nreads, first_read_id);
+}
+
 // bin nk = reads whose best row passes exactly the first nk (ascending) cut-offs: cut-off j (ascending) counts the bins nk > j
 static void grid_counts(const std::vector<unsigned long long> &bins, size_t nbins, int ncp, int n_score, int nfam, const std::vector<int> &order,
                         int64_t *count_hits, int64_t *count_aln, double *count_cov)
@@ -1324,6 +1498,7 @@ struct mc_genome {
     int vstart_len = 0; int64_t total = 0;                          // the span (read length or insert) d_vstart was made for, and its valid starts
     mc_library lib = {0, 0, MC_ERR_NONE, 0.0};                      // mc_genome_set_library's kind; d_thr: its error thresholds (mc_simlib.h)
     uint64_t *d_thr = nullptr;
+    int read_lengths = MC_SIM_LEN_FIXED;                            // mc_genome_set_read_lengths
 };
 static_assert(MC_ERR_NONE == MC_SIM_ERR_NONE && MC_ERR_UNIFORM == MC_SIM_ERR_UNIFORM && MC_ERR_ILLUMINA == MC_SIM_ERR_ILLUMINA, "one numbering of the error models");
 static bool default_library(const mc_library &l) { return !l.paired_end && l.error_model == MC_ERR_NONE; }
@@ -1412,6 +1587,76 @@ static int launch_simulate(const mc_genome *g, int L, uint64_t key, int64_t firs
     return 0;
 }
 
+static_assert(MC_READLEN_FIXED == MC_SIM_LEN_FIXED && MC_READLEN_REFERENCE == MC_SIM_LEN_REFERENCE, "one numbering of the read-length modes");
+extern "C" int mc_genome_set_read_lengths(mc_genome *g, int32_t mode)
+{
+    if (!g) { g_err = "mc_genome_set_read_lengths: bad argument"; return -1; }
+    if (mode != MC_READLEN_FIXED && mode != MC_READLEN_REFERENCE) { g_err = "unknown read-length mode " + std::to_string(mode); return -1; }
+    g->read_lengths = mode;
+    return 0;
+}
+
+// Reads [first, first + n) of the reference read-length mode into d_dst (n x min(2L, 510) bytes + 64 of room), their offsets (from
+// 0) into d_roff (n + 1), in two passes: lengths (d_lens, n), checked on the host (a read over 510 bases is refused, named), scanned on
+// the device, then the reads.  *total: their bases.
+static int simulate_var(const mc_genome *g, int L, uint64_t key, int64_t first, int64_t n, uint32_t *d_lens, int64_t *d_roff, uint8_t *d_dst, hipStream_t st,
+                        int64_t *total)
+{
+    *total = 0;
+    if (n <= 0) return 0;
+    const McSimKind kind = {L, g->lib.paired_end ? 1 : 0, g->lib.paired_end ? g->lib.insert : L, g->lib.error_model != MC_ERR_NONE ? 1 : 0};
+    const uint64_t ekey = mc_mix64(key ^ MC_SIM_EKEY);
+    const dim3 grid((unsigned)((n + 63) / 64));
+    k_simulate_var<<<grid, dim3(64), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, kind, g->d_thr, key, ekey, first, n, d_lens, nullptr, nullptr);
+    HIPCK(hipGetLastError());
+    std::vector<uint32_t> lens((size_t)n);
+    HIPCK(hipMemcpyAsync(lens.data(), d_lens, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    int64_t sum = 0;
+    for (int64_t k = 0; k < n; k++) {
+        if (lens[(size_t)k] > 3 * MC_MAXAA) {
+            g_err = "read " + std::to_string(first + k) + " of the library is " + std::to_string(lens[(size_t)k]) + " bases long (read length " + std::to_string(L) +
+                    " plus its insertions): longer than 510";
+            return -1;
+        }
+        sum += lens[(size_t)k];
+    }
+    k_sim_scan<<<dim3(1), dim3(1024), 0, st>>>(d_lens, n, d_roff);
+    HIPCK(hipGetLastError());
+    k_simulate_var<<<grid, dim3(64), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, kind, g->d_thr, key, ekey, first, n, nullptr, d_roff, d_dst);
+    HIPCK(hipGetLastError());
+    *total = sum;
+    return 0;
+}
+
+extern "C" int64_t mc_simulate_varlen(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host,
+                                      int64_t dst_cap, int64_t *offsets)
+{
+    if (!g || first < 0 || n < 0 || !offsets) { g_err = "mc_simulate_varlen: bad argument"; return -1; }
+    if (read_len < 18 || read_len > 3 * MC_MAXAA) { g_err = "read_len out of range (18..510)"; return -1; }
+    HIPCK(hipSetDevice(g->device));
+    if (genome_for_len(g, read_len)) return -1;
+    offsets[0] = 0;
+    if (n == 0) return 0;
+    const int64_t B = std::min<int64_t>(n, stream_batch()), W = std::min(2 * read_len, 3 * MC_MAXAA);
+    McVlBuf buf;
+    uint8_t *d = nullptr; uint32_t *d_lens = nullptr; int64_t *d_roff = nullptr;
+    if (buf.get(&d, (size_t)(B * W + 64)) || buf.get(&d_lens, (size_t)B) || buf.get(&d_roff, (size_t)B + 1)) return -1;
+    const uint64_t key = sim_key(seed, library_id);
+    int64_t at_byte = 0;
+    for (int64_t at = 0; at < n; at += B) {                          // ranges of the streaming batch size, as mc_train_library makes them
+        const int64_t cnt = std::min(B, n - at);
+        int64_t total = 0;
+        if (simulate_var(g, read_len, key, first + at, cnt, d_lens, d_roff, d, nullptr, &total)) return -1;
+        std::vector<int64_t> ro((size_t)cnt + 1);
+        HIPCK(hipMemcpy(ro.data(), d_roff, ro.size() * 8, hipMemcpyDeviceToHost));
+        for (int64_t k = 1; k <= cnt; k++) offsets[at + k] = at_byte + ro[(size_t)k];
+        if (dst_host && at_byte + total <= dst_cap) HIPCK(hipMemcpy(dst_host + at_byte, d, (size_t)total, hipMemcpyDeviceToHost));
+        at_byte += total;
+    }
+    return at_byte;
+}
+
 extern "C" int mc_simulate(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host)
 {
     if (!g || first < 0 || n < 0 || (n > 0 && !dst_host)) { g_err = "mc_simulate: bad argument"; return -1; }
@@ -1480,10 +1725,19 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     mc_stats tot; memset(&tot, 0, sizeof tot);
     if (nreads == 0) { h->stats = tot; return 0; }
     const int64_t B = std::min<int64_t>(nreads, stream_batch());
-    // the resident read buffer (mc_upload's) holds one range at a time: the simulator writes it, the search reads it
-    const int64_t need = B * L + 16;
-    if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
-    if (ensure_capacity(h, h->ctx[0], B)) return -1;
+    const bool ref = g->read_lengths == MC_SIM_LEN_REFERENCE;
+    h->train_bases = 0;
+    if (!ref) {
+        // the resident read buffer (mc_upload's) holds one range at a time: the simulator writes it, the search reads it
+        const int64_t need = B * L + 16;
+        if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
+        if (ensure_capacity(h, h->ctx[0], B)) return -1;
+    }
+    // the reference read-length mode: reads of L + ins - del bases (two passes), bucketed by length, each bucket searched at its length
+    // and grid-classified into the same bins (a read lies in one bucket: its best survivor is the one of the whole library)
+    McVlBuf vb;
+    uint8_t *d_sim = nullptr; uint32_t *d_lens = nullptr; int64_t *d_roff = nullptr;
+    if (ref && (vb.get(&d_sim, (size_t)(B * std::min(2 * L, 3 * MC_MAXAA) + 64)) || vb.get(&d_lens, (size_t)B) || vb.get(&d_roff, (size_t)B + 1))) return -1;
     unsigned long long *d_bins = nullptr;
     if (hipMalloc((void **)&d_bins, nbins * 24) != hipSuccess) { g_err = "out of device memory"; return -1; }
     hipEvent_t ev[4] = {};
@@ -1494,13 +1748,41 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     int rc = hipMemsetAsync(d_bins, 0, nbins * 24, st) == hipSuccess ? 0 : -1;
     if (rc) g_err = "hipMemsetAsync failed";
     const uint64_t key = sim_key(seed, library_id);
-    for (int64_t at = 0; at < nreads && rc == 0; at += B) {
+    for (int64_t at = 0; at < nreads && rc == 0 && !ref; at += B) {
         const int64_t cnt = std::min(B, nreads - at);
         if (hipEventRecord(ev[0], st) != hipSuccess || launch_simulate(g, L, key, at, cnt, h->d_reads, st) || hipEventRecord(ev[1], st) != hipSuccess) { rc = -1; break; }
         h->reads_dev = h->d_reads; h->nreads = cnt;
         rc = train_range(h, 0, cnt, at, G, d_bins, nbins, ev[2], ev[3], tot);
         if (rc) break;
         h->train_ms[0] += ev_ms(ev[0], ev[1]);
+        h->train_bases += cnt * L;
+    }
+    const int FP0 = h->FP;
+    for (int64_t at = 0; at < nreads && rc == 0 && ref; at += B) {
+        const int64_t cnt = std::min(B, nreads - at);
+        int64_t bases = 0;
+        if (hipEventRecord(ev[0], st) != hipSuccess || simulate_var(g, L, key, at, cnt, d_lens, d_roff, d_sim, st, &bases)) { rc = -1; break; }
+        McVlBuf bb;
+        uint8_t *d_sorted = nullptr; uint32_t *d_perm = nullptr;
+        std::vector<uint32_t> start; std::vector<int64_t> boff;
+        if (vl_bucket(bb, st, d_sim, d_roff, cnt, bases, &d_sorted, &d_perm, start, boff) || hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess) { rc = -1; break; }
+        h->train_ms[0] += ev_ms(ev[0], ev[1]);
+        h->train_bases += bases;
+        std::vector<McVlPiece> pieces;
+        int Lmax = 0; int64_t nmax = 0, nshort = 0;
+        vl_pieces(start, B, pieces, Lmax, nmax, nshort);
+        tot.reads += nshort;
+        if (!pieces.empty() && (rc = vl_pools(h, Lmax, nmax)) != 0) break;
+        for (const McVlPiece &q : pieces) {
+            if ((rc = vl_use_length(h, q.L)) != 0) break;
+            h->reads_dev = d_sorted + boff[(size_t)q.L]; h->nreads = (int64_t)(start[(size_t)q.L + 1] - start[(size_t)q.L]);
+            if ((rc = train_range(h, q.first, q.n, at + (int64_t)start[(size_t)q.L] + q.first, G, d_bins, nbins, ev[2], ev[3], tot)) != 0) break;
+        }
+        (void)hipStreamSynchronize(st);                              // (the bucket buffers are freed at the end of the range)
+    }
+    if (ref) {                                                       // the run's own length and tables back
+        h->read_len = L; h->FP = FP0; h->reads_dev = nullptr; h->nreads = 0;
+        if (hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice) != hipSuccess && rc == 0) { g_err = "restoring the run's tables failed"; rc = -1; }
     }
     h->best_only = saved_best_only; h->rows_stay = false;
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
@@ -1514,6 +1796,8 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     h->stats = tot; h->train_ms[1] = tot.ms_total;
     return 0;
 }
+
+extern "C" int64_t mc_train_library_bases(const mc_handle *h) { if (!h) { g_err = "null handle"; return -1; } return h->train_bases; }
 
 extern "C" int mc_train_times(const mc_handle *h, float *ms)
 {

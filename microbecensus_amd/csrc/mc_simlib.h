@@ -22,6 +22,12 @@
 // So the walk never leaves the contig and the start set is that of the error-free library.  Deviation: the reference's read is
 // the mutated L-base fragment prefix (L + insertions - deletions bases); here a read is the FIRST L bases the process emits (it
 // reads on past the L-th fragment base after deletions), since the engine searches reads of one length.
+// Read-length mode "reference" (mc_genome_set_read_lengths(g, MC_READLEN_REFERENCE); mc_sim_walk_ref): the same draws, but the walk
+// consumes exactly the fragment bases j = 0 .. L-1 and emits whatever the errors produce - seq_sim.py's read of
+// L + insertions - deletions bases:
+//     no error: emit b;  substitution: emit x;  insertion: emit x, then b;  deletion: emit nothing (always: the walk never reads past
+//     the L-th base, so no deletion is refused)
+// Under error model none both modes give the same read.  A read longer than 510 bases is refused by the caller (never cut).
 #pragma once
 #include <stdint.h>
 
@@ -32,6 +38,7 @@
 #endif
 
 enum { MC_SIM_ERR_NONE = 0, MC_SIM_ERR_UNIFORM = 1, MC_SIM_ERR_ILLUMINA = 2 };
+enum { MC_SIM_LEN_FIXED = 0, MC_SIM_LEN_REFERENCE = 1 };
 #define MC_SIM_NTHR 235                        // p(j) of both models is constant for j >= 234
 #define MC_SIM_EKEY 0xA0761D6478BD642Full
 #define MC_SIM_GAMMA 0x9E3779B97F4A7C15ull
@@ -104,6 +111,33 @@ MC_SIM_HD void mc_sim_walk(Base &base, Emit &emit, Event &event, int64_t cs, int
         else if (e == 1) emit(o++, x);
         else if (e == 2) { emit(o++, x); if (o < L) emit(o++, b); }
     }
+}
+
+// The walk of the reference mode: fragment bases j = 0 .. L-1, every event emitted as drawn; returns the read's length.  emit may
+// be a counter only (the length pass of k_simulate.h).
+template <class Base, class Emit>
+MC_SIM_HD int mc_sim_walk_ref(Base &base, Emit &emit, int64_t p0, int dir, int L, uint64_t r, const uint64_t *thr, bool errors)
+{
+    int64_t p = p0;
+    int o = 0;
+    for (int j = 0; j < L; j++, p += dir) {
+        uint8_t b = base(p);
+        if (dir < 0) b = mc_sim_comp(b);
+        int e = 0;
+        uint8_t x = 0;
+        if (errors) {
+            const uint64_t d = mc_mix64(r + (uint64_t)j * MC_SIM_GAMMA);
+            if ((d >> 32) < thr[j < MC_SIM_NTHR ? j : MC_SIM_NTHR - 1]) {
+                const uint32_t kind = (uint32_t)(d >> 16) & 0xFFFFu;
+                x = (uint8_t)(0x54474341u >> (8 * (uint32_t)(d & 3)));     // "ACGT"[d & 3]
+                e = kind < MC_SIM_SUB ? 1 : kind < MC_SIM_INS ? 2 : 3;
+            }
+        }
+        if (e == 0) emit(o++, b);
+        else if (e == 1) emit(o++, x);
+        else if (e == 2) { emit(o++, x); emit(o++, b); }
+    }
+    return o;
 }
 
 struct McSimNoEvent {

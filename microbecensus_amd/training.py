@@ -11,7 +11,9 @@ error wins (the reference: whichever of its parallel processes finished first). 
 every (read length, family) gets weight 1.0.
 
 Libraries are single end without errors by default; error_model ('uniform' at error_rate, or 'illumina') and paired_end (with an
-insert) give seq_sim.py's other kinds (csrc/mc_simlib.h), with one deviation: every read keeps exactly L bases.
+insert) give seq_sim.py's other kinds (csrc/mc_simlib.h), with one deviation by default: every read keeps exactly L bases.
+reference_lengths=True (--reference-lengths) gives seq_sim.py's reads of L + insertions - deletions bases instead: each is searched
+at its own length (mc_search_varlen's buckets) and a library's bp is their real total, the reference's rate denominator.
 """
 import glob
 import gzip
@@ -115,11 +117,14 @@ def library_id(genome_name, read_len):
     return (int(read_len) << 32) | zlib.crc32(genome_name.encode())
 
 
-def library_record(error_model=None, error_rate=None, paired_end=False, insert=None):
-    """model.json's "library" record of a library kind; None for the default (single end, no errors)."""
-    if error_model is None and not paired_end:
+def library_record(error_model=None, error_rate=None, paired_end=False, insert=None, reference_lengths=False):
+    """model.json's "library" record of a library kind; None for the default (single end, no errors, reads of L bases)."""
+    if error_model is None and not paired_end and not reference_lengths:
         return None
-    return {"error_model": error_model, "error_rate": error_rate, "paired_end": bool(paired_end), "insert": insert if paired_end else None}
+    rec = {"error_model": error_model, "error_rate": error_rate, "paired_end": bool(paired_end), "insert": insert if paired_end else None}
+    if reference_lengths:
+        rec["reference_lengths"] = True
+    return rec
 
 
 def check_request(genomes, read_lengths, xfolds, coverage, n_families, n_markers, error_model=None, error_rate=None, paired_end=False, insert=None):
@@ -262,12 +267,18 @@ def read_map(path, header=False):
 
 
 def write_reads(path, reads, paired_end=False):
-    """A library in seq_sim.py's format: '>id\\nseq\\n', ids 0, 1, ...; paired end: '>k/1', '>k/2' for rows 2k, 2k + 1."""
+    """A library in seq_sim.py's format: '>id\\nseq\\n', ids 0, 1, ...; paired end: '>k/1', '>k/2' for rows 2k, 2k + 1.  reads: an
+    (n, L) array, or (bases, offsets) of reads at their own lengths."""
     os.makedirs(os.path.dirname(path), exist_ok=True)
+    if isinstance(reads, tuple):
+        bases, off = reads
+        rows = (bases[off[i]:off[i + 1]] for i in range(len(off) - 1))
+    else:
+        rows = (reads[i] for i in range(reads.shape[0]))
     with open(path, "wb") as f:
-        for i in range(reads.shape[0]):
+        for i, row in enumerate(rows):
             f.write(b">%d/%d\n" % (i >> 1, 1 + (i & 1)) if paired_end else b">%d\n" % i)
-            f.write(reads[i].tobytes())
+            f.write(row.tobytes())
             f.write(b"\n")
 
 
@@ -284,8 +295,9 @@ def write_hits(path, families, hits, aln, cov):
 
 # ---- the run ------------------------------------------------------------------------------------------------------------------
 def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfolds=10, seed=0, device=0, write_reads_dir=None, log=print,
-          error_model=None, error_rate=None, paired_end=False, insert=None):
-    """TRAINING.txt steps 1 - 4 in one call.  A paired-end library at coverage c holds library_reads(c, G, L) pairs (seq_sim.py's
+          error_model=None, error_rate=None, paired_end=False, insert=None, reference_lengths=False):
+    """TRAINING.txt steps 1 - 4 in one call.  reference_lengths: seq_sim.py's read lengths (L + insertions - deletions), the library's
+    bp their real total.  A paired-end library at coverage c holds library_reads(c, G, L) pairs (seq_sim.py's
     read_id counts pairs), so twice as many reads; a library's bp is its reads x L either way.  Returns the model dict written to
     out_dir/model.json, with the run's rates under '_rates' ({L: (genomes, families, candidates)}) and the genomes' sizes under
     '_sizes'."""
@@ -297,7 +309,7 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
     else:
         names, seqs, marker_family, families = packaged_marker_set()
     check_request(genomes, read_lengths, xfolds, coverage, len(families), len(names), error_model, error_rate, paired_end, insert)
-    library = library_record(error_model, error_rate, paired_end, insert)
+    library = library_record(error_model, error_rate, paired_end, insert, reference_lengths)
     loaded = []
     for gname, path in genomes:
         bases, off = _native.read_fasta_genome(path)
@@ -318,6 +330,8 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
     if library is not None:
         for g in gpu_genomes:
             g.set_library(error_model, error_rate, paired_end, insert)
+            if reference_lengths:
+                g.set_read_lengths(True)
     cands = candidates()
     pars, coefficients, weights, preds, all_rates = {}, {}, {}, [], {}
     try:
@@ -329,9 +343,10 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
                 lid = library_id(gname, L)
                 hits, aln, cov = eng.train_library(g, n, seed, lid, ALN_COVS, MAX_PIDS, MIN_SCORES)
                 counts.append((hits, aln, cov))
-                lib_bp.append(n * L)
+                lib_bp.append(eng.train_library_bases() if reference_lengths else n * L)
                 if write_reads_dir:
-                    write_reads(os.path.join(write_reads_dir, str(L), gname + "-reads.fa"), g.simulate(L, n, seed, lid), paired_end)
+                    reads = g.simulate_varlen(L, n, seed, lid) if reference_lengths else g.simulate(L, n, seed, lid)
+                    write_reads(os.path.join(write_reads_dir, str(L), gname + "-reads.fa"), reads, paired_end)
                     write_hits(os.path.join(write_reads_dir, str(L), gname + ".hits"), families, hits, aln, cov)
                 log("  L=%d %s: %d reads" % (L, gname, n))
             rates = rates_by_candidate([c[0] for c in counts], [c[1] for c in counts], [c[2] for c in counts], lib_bp)

@@ -31,6 +31,8 @@ def parse_arguments(argv=None):
                    help="sequencing errors of the simulated reads (seq_sim.py -e; default: none)")
     p.add_argument("--error-rate", dest="error_rate", type=float, default=None, help="per-base error rate of --error-model uniform (seq_sim.py -r)")
     p.add_argument("--paired-end", dest="paired_end", action="store_true", help="simulate mate pairs (seq_sim.py -p): reads k/1 and k/2 of every fragment")
+    p.add_argument("--reference-lengths", dest="reference_lengths", action="store_true",
+                   help="reads of seq_sim.py's lengths, L + insertions - deletions (default: every read keeps L bases); rates over the real bp")
     p.add_argument("--insert", dest="insert", type=int, default=None, help="fragment length of --paired-end, at least the read length (seq_sim.py -i)")
     args = p.parse_args(argv)
     try:
@@ -45,7 +47,7 @@ def main(argv=None):
     try:
         training.train(a.genomes_dir, a.out_dir, a.read_lengths, a.coverage, gene_fams_dir=a.gene_fams, xfolds=a.xfolds, seed=a.seed,
                        device=a.device, write_reads_dir=a.write_reads, error_model=a.error_model, error_rate=a.error_rate,
-                       paired_end=a.paired_end, insert=a.insert)
+                       paired_end=a.paired_end, insert=a.insert, reference_lengths=a.reference_lengths)
     except training.TrainingError as e:
         sys.exit("Error: %s" % e)
 
