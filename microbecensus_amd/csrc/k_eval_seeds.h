@@ -75,18 +75,19 @@ __device__ __forceinline__ bool mc_ev_gate(const McHot &T, const uint8_t *q, int
     return (double)score >= MC_SEED_SCORE && ident >= MC_SEED_IDENT;
 }
 // ... and the extension itself, from the grown seed: 1 = ungapped HSP complete, 2 = needs the gapped extension
-#ifndef MC_EV_XDROP_STEPWISE
 // One accumulator per walk carries what a step of AlignFwd / AlignBwd updates - the running score, the step's number and the identities
 // so far: P = run * 65536 + (255 - i) * 256 + id (i <= MC_MAXAA steps, id <= i).  A step adds ONE table word to it (sub32[a][b] =
 // score * 65536 - 256 + (a == b), 4 KB of LDS made at the kernel's start), and the best prefix is `max`: P' > Pbest <=> run > best
 // (the low 16 bits are below 65536, and on equal scores the EARLIER step has the larger low part - the reference's `run > best` keeps the
-// first one too).  best, its length and its identities are read off Pbest at the end.  The exit test best - run >= xdi is
-// Pbest - P >= xdi * 65536 exactly (the low parts differ by (i - bl) * 256 - (id - bid) in [0, 65535]: i > bl whenever best > run).
-// `run < -20` cannot fire first: best >= the seed's score >= MC_SEED_SCORE (the gate), so run < -20 has best - run > 31 >= xdi
-// (static_assert below).  The end of the shorter sequence: the bytes of the query's word at and behind it are set to 0xFF - row 31 of the
-// table, which no residue code uses (codes <= MC_INV = 20), holds - 100 * 65536: the step behind the last residue is an exit by the test
-// that is there anyway, with best untouched.  Per step: three instructions for the table's address, one LDS read, add, max, subtract,
-// compare, select - against fifteen and three exit tests (the step-by-step form, -DMC_EV_XDROP_STEPWISE: same results).
+// first one too).  best, its length and its identities are read off Pbest at the end.  The reference's exit test is
+// `(double)run < (double)best - xdrop` on two integers and a constant that is no integer (8.94 for BLOSUM62's ungapped lambda;
+// mc_fill_tables refuses one that is nearer than 1e-6 to an integer): best - run > xdrop <=> best - run >= xdi = floor(xdrop) + 1, and
+// that is Pbest - P >= xdi * 65536 exactly (the low parts differ by (i - bl) * 256 - (id - bid) in [0, 65535]: i > bl whenever best > run).
+// The reference's other exit, `run < -20`, cannot fire first: best >= the seed's score >= MC_SEED_SCORE (the gate), so run < -20 has
+// best - run > MC_SEED_SCORE + 20 = 31 >= xdi (mc_fill_tables aborts otherwise).  The end of the shorter sequence: the bytes of the query's
+// word at and behind it are set to 0xFF - row 31 of the table, which no residue code uses (codes <= MC_INV = 20), holds - 100 * 65536: the
+// step behind the last residue is an exit by the test that is there anyway, with best untouched.  Per step: three instructions for the
+// table's address, one LDS read, add, max, subtract, compare, select.
 static_assert(MC_MAXAA <= 250 && MC_INV < 31 && MC_SEED_SCORE >= -11.0, "the packed accumulator of mc_ev_xdrop");
 #define MC_EV_POISON (-100 * 65536 - 256)
 #define MC_EV_SUB32(a, b) (*(const int32_t *)((const char *)sub32 + ((((a) << 7) | ((b) << 2)) & 0xFFCu)))      // (the word's byte address straight from the two bytes)
@@ -163,84 +164,6 @@ __device__ __forceinline__ int mc_ev_xdrop(const McHot &T, const int32_t *sub32,
     gt->qfwd = (int16_t)qfwd; gt->qbwd = (int16_t)qbwd; gt->score = (int16_t)score; gt->nmatch = (int16_t)ident;
     return (!(T.gap_trigger > (double)score)) ? 2 : 1;
 }
-#else
-__device__ __forceinline__ void mc_ev_sub32(int32_t *, const McHot &) { }
-__device__ __forceinline__ int mc_ev_xdrop(const McHot &T, const int32_t *, const uint8_t *q, int qlen, const uint8_t *d, int dlen, int sidx, int qp, int dp, int L, int score, int ident, McGapTask *gt)
-{
-    // The reference's exit test is `(double)run < (double)best - xdrop` on two integers and a constant that is no integer (8.94 for BLOSUM62's
-    // ungapped lambda; mc_fill_tables refuses one that is nearer than 1e-6 to an integer): best - run > xdrop <=> best - run >= floor(xdrop) + 1,
-    // exactly.  (MC_EV_F64_XDROP: the reference's own form - two conversions and an f64 subtraction in the dependent chain of every step.)
-#ifdef MC_EV_F64_XDROP
-    const double xd = T.xdrop_ungapped;
-#define MC_EV_DROP(run, best) ((double)(run) < (double)(best) - xd)
-#else
-    const int xdi = (int)floor(T.xdrop_ungapped) + 1;
-#define MC_EV_DROP(run, best) ((best) - (run) >= xdi)
-#endif
-    int s0 = score, qfwd = 0, qbwd = 0, fgain = 0, bgain = 0;
-    { // forward
-        const int n1 = qlen - qp - L, n2 = dlen - dp - L;
-        int bl = 0, bi = 0;
-        if (n1 != 0 && n2 != 0 && !(s0 < -20)) {
-            const uint8_t *p1 = q + qp + L, *p2 = d + dp + L;
-            int run = s0, best = s0, id = 0, i = 0;
-            bool stop = false;
-            do {
-                MC_EV_TURN(0);
-                const uint64_t wa = mc_ld8(p1 + i), wb = mc_ld8(p2 + i);
-                int sc[8];
-                uint32_t eq = 0;
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const uint32_t a = (uint32_t)(wa >> (8 * k)) & 0xFFu, b = (uint32_t)(wb >> (8 * k)) & 0xFFu;
-                    sc[k] = (int)T.sub[((a << 5) | b) & 1023u]; eq |= (uint32_t)(a == b) << k;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    if (!stop) {
-                        run += sc[k]; id += (int)((eq >> k) & 1u); i++;
-                        if (run > best) { best = run; bl = i; bi = id; }
-                        stop = !(n2 > i) || n1 <= i || run < -20 || MC_EV_DROP(run, best);
-                    }
-            } while (!stop);
-            fgain = best - s0;
-        }
-        ident += bi; qfwd = bl;
-    }
-    { // backward, restarting from the seed score
-        int a = qp - 1, b = dp - 1, bl = 0, bi = 0;
-        if (a >= 0 && b >= 0 && !(s0 < -20)) {
-            int run = s0, best = s0, id = 0, cnt = 0;
-            bool stop = false;
-            do {
-                MC_EV_TURN(1);
-                const uint64_t wa = mc_ld8(q + a - 7), wb = mc_ld8(d + b - 7);       // residues a - 7 .. a: step k uses byte 7 - k
-                int sc[8];
-                uint32_t eq = 0;
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const uint32_t x = (uint32_t)(wa >> (8 * (7 - k))) & 0xFFu, y = (uint32_t)(wb >> (8 * (7 - k))) & 0xFFu;
-                    sc[k] = (int)T.sub[((x << 5) | y) & 1023u]; eq |= (uint32_t)(x == y) << k;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    if (!stop) {
-                        run += sc[k]; id += (int)((eq >> k) & 1u); cnt++;
-                        if (best < run) { best = run; bl = cnt; bi = id; }
-                        a--; b--;
-                        stop = b < 0 || a < 0 || run < -20 || MC_EV_DROP(run, best);
-                    }
-            } while (!stop);
-            bgain = best - s0;
-        }
-        ident += bi; qbwd = bl;
-    }
-    score = s0 + bgain + fgain;
-    gt->sidx = (uint32_t)sidx; gt->qp = (int16_t)qp; gt->dp = (int16_t)dp; gt->L = (int16_t)L;
-    gt->qfwd = (int16_t)qfwd; gt->qbwd = (int16_t)qbwd; gt->score = (int16_t)score; gt->nmatch = (int16_t)ident;
-    return (!(T.gap_trigger > (double)score)) ? 2 : 1;
-}
-#endif
 
 #ifdef MC_EXP_TIMING
 __device__ unsigned long long g_ev_acc[8];           // wave time per phase, summed over the waves (lane 0): 0 loop, next records asked for 1 survivors queued 2 X-drop extension (with the read of the queue) 3 HSP, marks 4 records written 5 wait for the residues + seed score 6 redundancy test, growth, gate
@@ -282,25 +205,21 @@ __device__ __forceinline__ uint32_t mc_ev_slots(uint32_t n, uint32_t r, uint32_t
 // RANGES (round 5, the product's seed kernel k_enumerate_q; the name is history: ranges of hits per record were built first and cost this
 // kernel more than they saved the other): a record holds the INDEX of its hit's posting instead of the posting, its place in the residue
 // array and the rest of the subject - the seed kernel is bound by the scattered lines its CUs fetch and a hit's posting and
-// offsets were 150 of the 810 lines a read cost it; this kernel was thought not to wait for memory (5.7; it does: MC_POST_WORDS below) and fetches the three in one 8-byte load.
+// offsets were 150 of the 810 lines a read cost it; this kernel was thought not to wait for memory (5.7; it does: k_post8 below) and fetches the three in one 8-byte load.
 // the postings with what the evaluation needs beside them (MC_POST8), made once per handle
-// MC_POST_WORDS = 4 (round 6): the 24 residues of the subject around the posting - dpos - 8 .. dpos + 15, what the gate reads of it - travel
+// Four words per posting (round 6): the 24 residues of the subject around the posting - dpos - 8 .. dpos + 15, what the gate reads of it - travel
 // WITH it: 32 bytes per posting (115 MB for the marker database instead of 29 + the 14 MB residue array asked at a scattered place), one
 // aligned item = ONE line per hit instead of 2.4, and no second trip (posting -> place -> residues).  The kernel takes the time the memory
 // system needs for its scattered lines (instructions, occupancy and loads ahead of time all left it where it was), so lines are
-// what pays.  The X-drop walks of the three hits in ten that pass the gate still read the residue array.  -DMC_POST_WORDS=1: the 8-byte form.
-#ifndef MC_POST_WORDS
-#define MC_POST_WORDS 4
-#endif
+// what pays.  The X-drop walks of the three hits in ten that pass the gate still read the residue array.
+#define MC_POST_WORDS 4      // 8-byte words per posting record
 __global__ void __launch_bounds__(256) k_post8(const uint32_t *__restrict__ post, const uint32_t *__restrict__ off, const uint8_t *__restrict__ res, uint32_t n, unsigned long long *post8)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint32_t pst = post[i], s = pst >> 11, abs = off[s] + (pst & 0x7ffu);
     post8[(size_t)i * MC_POST_WORDS] = MC_POST8(pst, abs, off[s + 1] - abs);
-#if MC_POST_WORDS == 4
     post8[(size_t)i * 4 + 1] = mc_ld8(res + abs - 8); post8[(size_t)i * 4 + 2] = mc_ld8(res + abs); post8[(size_t)i * 4 + 3] = mc_ld8(res + abs + 8);   // (the residue array has room on both sides)
-#endif
 }
 template <bool RANGES>
 __global__ void __attribute__((amdgpu_waves_per_eu(5, 5))) __launch_bounds__(MC_EV_BS) k_eval_seeds(const McTables *__restrict__ T, McIndex X, const uint8_t *__restrict__ frames, int FP, int L,
@@ -309,11 +228,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(5, 5))) __launch_bounds__(MC_
 {
     const uint32_t ntasks = *ntasks_p <= cap_tasks ? *ntasks_p : 0u;   // (device-side count of the seed kernel; after an overflow the host discards the batch)
     __shared__ McHot hot;
-#ifndef MC_EV_XDROP_STEPWISE
     __shared__ int32_t sub32[1024];
-#else
-    int32_t *const sub32 = nullptr;
-#endif
     const int lane = mc_lane(), wv = threadIdx.x >> 6;
     uint4 *Q = (uint4 *)(mc_smem + (size_t)wv * MC_EV_QCAP * 32);    // entry e: words 2 e, 2 e + 1
     mc_load_hot(&hot, T);
@@ -348,8 +263,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(5, 5))) __launch_bounds__(MC_
             const uint8_t *q = frames + ((int64_t)rd * 6 + frame) * FP, *d = X.res + o0;
             // residues pos - 8 .. pos + 15 of the frame and dpos - 8 .. dpos + 15 of the subject: six loads, one trip (rows and residue array have room on both sides)
             const uint64_t q0 = mc_ld8(q + pos - 8), q1 = mc_ld8(q + pos), q2 = mc_ld8(q + pos + 8);
-            uint64_t d0 = r0, d1 = r1, d2 = r2;                   // (with the posting's record: MC_POST_WORDS = 4)
-            if (!(RANGES && MC_POST_WORDS == 4)) { d0 = mc_ld8(d + dpos - 8); d1 = mc_ld8(d + dpos); d2 = mc_ld8(d + dpos + 8); }
+            uint64_t d0 = r0, d1 = r1, d2 = r2;                   // (RANGES: with the posting's record)
+            if (!RANGES) { d0 = mc_ld8(d + dpos - 8); d1 = mc_ld8(d + dpos); d2 = mc_ld8(d + dpos + 8); }
             const int qm1 = (int)(q0 >> 56), dm1 = (int)(d0 >> 56);
             const int dlen = dpos + rem;
             int score = 0, ident = 0;
@@ -453,14 +368,10 @@ __global__ void __attribute__((amdgpu_waves_per_eu(5, 5))) __launch_bounds__(MC_
         bool have_n = cur < nchunks, have_n2 = false;
         unsigned long long p8n = 0, r0n = 0, r1n = 0, r2n = 0;
         auto fetch = [&](uint32_t idx) {
-#if MC_POST_WORDS == 4
-            const mc_u32x4 *rp = (const mc_u32x4 *)(X.post8 + (size_t)idx * 4);
+            const mc_u32x4 *rp = (const mc_u32x4 *)(X.post8 + (size_t)idx * MC_POST_WORDS);
             const mc_u32x4 lo = rp[0], hi = rp[1];                // (not "nontemporal": the hits of a probe have neighbouring records - past the caches 2.12 -> 2.56 ms per 1 M reads)
             p8n = (unsigned long long)lo.x | ((unsigned long long)lo.y << 32); r0n = (unsigned long long)lo.z | ((unsigned long long)lo.w << 32);
             r1n = (unsigned long long)hi.x | ((unsigned long long)hi.y << 32); r2n = (unsigned long long)hi.z | ((unsigned long long)hi.w << 32);
-#else
-            p8n = X.post8[idx];
-#endif
         };
         if (have_n) {
             cur2 = advance(); have_n2 = cur2 < nchunks; tidn2 = cur2 * 64u + (uint32_t)lane;

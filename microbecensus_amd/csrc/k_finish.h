@@ -83,7 +83,7 @@ template <int TPB, int ITEMS, int CL0>
 __global__ void __launch_bounds__(TPB) k_finish(const McTables *__restrict__ T, McIndex X, const McClassPars *__restrict__ P, const int32_t *__restrict__ fam,
                                                 const uint32_t *__restrict__ nv, const uint32_t *__restrict__ heads, uint32_t nheads,
                                                 McHsp *v, McHsp *tmp, int64_t first_read_id, uint32_t *nrow_of, McBestHit *best,
-                                                const uint32_t *__restrict__ light, uint32_t light_pitch, const uint32_t *__restrict__ nlight, int use_lds)
+                                                const uint32_t *__restrict__ light, uint32_t light_pitch, const uint32_t *__restrict__ nlight)
 {
     // blockIdx.y = size class, the larger first: two classes in ONE launch (and the two launches side by side on two streams) - a
     // thread finishes its read alone and the reads that print anything fill a fraction of the GPU
@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(TPB) k_finish(const McTables *__restrict__ T, 
     double *myk = (double *)(myrows + n);
     McBestHit bh;
     int nr;
-    if (use_lds && vn <= ITEMS) nr = mc_finish_stacked_t<McSortsInl>(*T, X, *P, fam, (int)((int64_t)s + first_read_id), v + a, vn, tmp + 2 * (size_t)a, myrows, myk, (McSortItem *)(mc_smem + (size_t)threadIdx.x * STRIDE), &bh);
+    if (vn <= ITEMS) nr = mc_finish_stacked_t<McSortsInl>(*T, X, *P, fam, (int)((int64_t)s + first_read_id), v + a, vn, tmp + 2 * (size_t)a, myrows, myk, (McSortItem *)(mc_smem + (size_t)threadIdx.x * STRIDE), &bh);
     else nr = mc_finish_stacked(*T, X, *P, fam, (int)((int64_t)s + first_read_id), v + a, vn, tmp + 2 * (size_t)a, myrows, myk, (McSortItem *)(myk + n), &bh);   // (64 n + 8 n + 16 n = 88 n <= 96 n bytes of the read's tmp area)
     nrow_of[s] = (uint32_t)nr;
     best[s] = bh;                                                 // per read that has HSPs (family -1: none); k_emit_rows collects them

@@ -247,11 +247,13 @@ struct McGapLds {
     __device__ __forceinline__ int loadH(int c) const { return (int)(cell[c * 64].x << 20) >> 20; }
 };
 
-template <int W, int LANES>
+// REFILL: the idle lanes that start their next flanks together (MC_GAP_REFILL; the retry launch 1)
+template <int W, int LANES, int REFILL>
 __global__ void __launch_bounds__(64) k_gapped_lds(const McTables *__restrict__ T, McIndex X, const uint8_t *__restrict__ frames, int FP, int L,
                                                    const McGapTask *__restrict__ gaps, const uint32_t *__restrict__ list, const uint32_t *__restrict__ nitems_p, McFlankOut *fout,
-                                                   uint32_t *retry_count, uint32_t *retry, int refill, uint32_t *take)
+                                                   uint32_t *retry_count, uint32_t *retry, uint32_t *take)
 {
+    static_assert(REFILL >= 1 && REFILL <= LANES, "a refill is at most the lanes that take items");
     __shared__ McHot hot;
     __shared__ uint2 win[W * 64];
     const uint32_t nitems = *nitems_p;                            // device-side count
@@ -272,7 +274,6 @@ __global__ void __launch_bounds__(64) k_gapped_lds(const McTables *__restrict__ 
     uint32_t pend = 0;                                             // lane 0: the number of the next window
     bool asked = false, dry = false;                               // a window has been asked for / there are no more
     const unsigned long long lt = (1ull << lane) - 1;
-    const int REFILL = LANES < refill ? 1 : refill;
     // the flank being extended
     bool active = false;
     uint32_t it = 0;
@@ -290,7 +291,7 @@ __global__ void __launch_bounds__(64) k_gapped_lds(const McTables *__restrict__ 
         // here, so that no later use waits for it together with the requests of THIS iteration (the counter is in order).
         __builtin_amdgcn_s_waitcnt(0x0F70);                        // vmcnt(0)
         bool fin = false;
-        {   // ---- the idle lanes whose next flank is ready start it - MC_GAP_REFILL of them together, or when nothing else is left to do
+        {   // ---- the idle lanes whose next flank is ready start it - REFILL of them together, or when nothing else is left to do
             const bool ready = mine && !active && nstage == 5;
             const unsigned long long rm = __ballot(ready);
             if (rm && (__popcll(rm) >= REFILL || (dry && wpos >= wend) || __ballot(active) == 0)) {

@@ -29,14 +29,12 @@
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
-// Everything the range in flight needs: streams, events, the pools of the stages, the pinned mirrors of the device counters.  (Rounds 2 - 3
-// had two of them per handle for a range run as two interleaved halves; what overlaps now is the host's work on the results of one
-// range with the front of the next, and that needs no second set of pools - range_begin.)
-#define MC_NCTX 1
+// Everything the range in flight needs: streams, events, the pools of the stages, the pinned mirrors of the device counters.  One per
+// handle: what overlaps is the host's work on the results of one range with the front of the next, and that needs no second set of
+// pools - range_begin.
 struct McCtx {
     hipStream_t stream = nullptr, side = nullptr, side2 = nullptr;   // the pipeline of a range, and two side streams of the ordering / finishing kernels
-    hipEvent_t ev[8] = {}, ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_part[16] = {}, ev_en[16] = {};
-    hipStream_t tr_stream = nullptr;                               // the translation of the next part of a range beside the seed search of this one (stage_a, MC_A_PARTS)
+    hipEvent_t ev[8] = {}, ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
     int64_t cap_reads = 0; int pool_len = 0;                       // the pools hold cap_reads reads of up to pool_len bases
     uint32_t cap_tasks = 0, cap_gaps = 0, cap_hsps = 0, cap_rows = 0;
     uint8_t *d_frames = nullptr, *d_frames_base = nullptr;   // (64 bytes of room in front: k_eval_seeds reads 8 bytes at a time backwards from a seed)
@@ -80,7 +78,7 @@ struct mc_handle {
     int64_t nreads = 0, cap_own = 0;
     uint8_t *d_reads = nullptr;
     const uint8_t *reads_dev = nullptr;   // resident read set (own buffer or attached caller memory)
-    McCtx ctx[MC_NCTX];
+    McCtx ctx;
     // host results: rows of the last run land in pinned memory; mc_search() accumulates its batches in all_rows
     // The rows travel to the host while the caller goes on (two pinned buffers in turn, a stream and an event of their own):
     // mc_run_range() returns when the best hits are there; whoever looks at the rows waits for their copy (rows_wait).
@@ -108,11 +106,6 @@ template <class Tp> static int dalloc(Tp **p, size_t n)
     return 0;
 }
 
-// (Rounds 3 - 4 had a load-time constructor here that exported GPU_MAX_HW_QUEUES=8: a process-wide side effect on every other HIP
-// user of the host application, dependent on load order, and a setenv() that races with getenv() in other threads - ADVICE r04.  The
-// library no longer touches the environment; the entry points that own their process - scripts/*, bench.py, the tests - set the
-// variable before anything initialises HIP, and INTEGRATION.md section 3 tells an embedding application to do the same.)
-
 extern "C" int mc_device_count(void)
 {
     int n = 0;
@@ -128,9 +121,6 @@ static void ctx_free(McCtx &c)
     for (void *p : {(void *)c.h_c, (void *)c.h_stats, (void *)c.h_best}) if (p) (void)hipHostFree(p);
     for (auto &e : c.ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {c.ev_fork, c.ev_join, c.ev_join2}) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c.ev_part) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c.ev_en) if (e) (void)hipEventDestroy(e);
-    if (c.tr_stream) (void)hipStreamDestroy(c.tr_stream);
     if (c.stream) (void)hipStreamDestroy(c.stream);                // (side, side2: the handle's)
     c = McCtx();
 }
@@ -141,7 +131,7 @@ extern "C" void mc_close(mc_handle *h)
     (void)hipSetDevice(h->device);
     void *ptrs[] = {h->d_res_base, h->d_off, h->d_bstart, h->d_post, h->d_post8, h->d_keys, h->d_fam, h->d_T, h->d_P, h->d_reads, h->d_bitmap, h->d_rec, h->d_filt, h->d_wild, h->d_pair, h->d_rt, h->d_segtab};
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (McCtx &c : h->ctx) ctx_free(c);
+    ctx_free(h->ctx);
     for (int k = 0; k < 2; k++) { if (h->stage_pin[k]) (void)hipHostFree(h->stage_pin[k]); if (h->stage_dev[k]) (void)hipFree(h->stage_dev[k]); }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     for (hipStream_t q : {h->side, h->side2}) if (q) (void)hipStreamDestroy(q);
@@ -206,7 +196,8 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
     // 5 ms copy of the rows of the range before (measured: 51.2 instead of 53.6 M reads/s) - hence few streams.  The queue count is
     // the environment's: neither this library nor the package's entry points set it.
     HIPCK(hipStreamCreate(&h->side)); HIPCK(hipStreamCreate(&h->side2));
-    for (McCtx &c : h->ctx) {
+    {
+        McCtx &c = h->ctx;
         HIPCK(hipStreamCreate(&c.stream)); c.side = h->side; c.side2 = h->side2;
         for (auto &e : c.ev) HIPCK(hipEventCreate(&e));
         HIPCK(hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming)); HIPCK(hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming));
@@ -401,7 +392,7 @@ extern "C" int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const
     }
     HIPCK(hipMemcpy(h->d_P, &h->hP, sizeof(McClassPars), hipMemcpyHostToDevice));
     const int newFP = ((read_len / 3 + 2) + 3) & ~3;
-    if (newFP != h->FP || read_len != h->read_len) for (McCtx &c : h->ctx) c.cap_reads = 0;   // pools are sized by read length and frame pitch
+    if (newFP != h->FP || read_len != h->read_len) h->ctx.cap_reads = 0;   // pools are sized by read length and frame pitch
     h->read_len = read_len; h->FP = newFP; h->run_set = true;
     MC_OT("set_run: segtab, uploads", t0);
     return 0;
@@ -452,8 +443,8 @@ extern "C" int mc_upload(mc_handle *h, const uint8_t *reads, int64_t nreads)
     HIPCK(hipSetDevice(h->device));
     const int64_t need = nreads * (int64_t)h->read_len + 16;       // capacity in bytes: the read length may change between runs
     if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
-    if (nreads) HIPCK(hipMemcpyAsync(h->d_reads, reads, (size_t)nreads * h->read_len, hipMemcpyHostToDevice, h->ctx[0].stream));
-    HIPCK(hipStreamSynchronize(h->ctx[0].stream));
+    if (nreads) HIPCK(hipMemcpyAsync(h->d_reads, reads, (size_t)nreads * h->read_len, hipMemcpyHostToDevice, h->ctx.stream));
+    HIPCK(hipStreamSynchronize(h->ctx.stream));
     h->reads_dev = h->d_reads; h->nreads = nreads;
     return 0;
 }
@@ -473,303 +464,22 @@ static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; (void)hipEventEla
 static int stage_wait(McCtx &c) { HIPCK(hipStreamSynchronize(c.stream)); return 0; }
 static int counters_to_host(McCtx &c) { HIPCK(hipMemcpyAsync(c.h_c, c.d_counters, sizeof(uint32_t) * C_N, hipMemcpyDeviceToHost, c.stream)); return 0; }
 
-// A: translation + SEG, seed enumeration, seed evaluation (gate, growth, ungapped X-drop)
-static int stage_a(mc_handle *h, McCtx &c)
-{
-    const int64_t n = c.n;
-    const int L = h->read_len, FP = h->FP;
-    hipStream_t st = c.stream;
-    McIndex X = dev_index(h);
-    c.ntasks = c.ngaps = c.gpad = c.nh = c.nheads = c.nrows = c.nbest = c.nsegs = 0;
-    HIPCK(hipMemsetAsync(c.d_counters, 0, sizeof(uint32_t) * C_N, st));
-    HIPCK(hipMemsetAsync(c.d_stats, 0, sizeof(unsigned long long) * S_N, st));
-    if (h->best_only) HIPCK(hipMemsetAsync(c.d_cand, 0, (size_t)n, st));
-    HIPCK(hipMemsetAsync(c.d_low, 0, (size_t)n, st));
-    HIPCK(hipEventRecord(c.ev[0], st));
-    const int64_t threads = n * 6;
-    const size_t lds_rest = (size_t)MC_TS_NLNF(FP) * 8 + (size_t)MC_TS_THREADS * MC_TS_STRIDE(FP);
-    const size_t lds_staged = (size_t)MC_TS_STAGE(L) + lds_rest, lds_direct = (size_t)MC_TS_STAGE(0) + lds_rest;
-    static const int ts_force = getenv("MC_TS_STAGED") ? atoi(getenv("MC_TS_STAGED")) : -1;
-    const size_t cu_lds = 160 * 1024 - 1024;                      // (static LDS of the kernel and allocation granules)
-    const bool staged = ts_force >= 0 ? ts_force != 0 : cu_lds / lds_staged >= cu_lds / lds_direct;   // staging stays while it does not cost a resident workgroup
-    const size_t lds = staged ? lds_staged : lds_direct;
-    // The front in PARTS (MC_A_PARTS = P > 1): the translation of part p + 1 on a side stream beside the seed search of
-    // part p.  The translation is bound by VALU issue with the memory system idle, the seed search by scattered lines with two in five issue
-    // slots idle; side by side as equals they took from each other what they gained (a translation wave keeps its SIMD's
-    // issue slots busy and the seed waves beside it stand still) - so the seed kernel's waves run at a higher issue priority (MC_EN_PRIO,
-    // s_setprio) and the translation takes the slots they leave.
-    static const int a_parts = getenv("MC_A_PARTS") ? std::max(1, std::min(16, atoi(getenv("MC_A_PARTS")))) : 1;
-    static const int en_prio = getenv("MC_EN_PRIO") ? std::max(0, std::min(3, atoi(getenv("MC_EN_PRIO")))) : 0;
-    const bool in_parts = a_parts > 1 && h->fast_enum && !h->count_traffic && n >= (int64_t)a_parts * 4096;
-    int64_t part_n = n;
-    if (in_parts) part_n = (((n + a_parts - 1) / a_parts) + 1023) / 1024 * 1024;
-    auto translate = [&](hipStream_t s2, int64_t off, int64_t cnt) -> int {
-        if (staged) {
-            if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            k_translate_seg<true><<<dim3((unsigned)((cnt + MC_TS_READS - 1) / MC_TS_READS)), dim3(MC_TS_THREADS), lds, s2>>>(h->d_T, c.reads + off * L, L, cnt, c.d_frames + off * 6 * FP, FP, h->d_segtab);
-        } else {
-            if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            k_translate_seg<false><<<dim3((unsigned)((cnt + MC_TS_READS - 1) / MC_TS_READS)), dim3(MC_TS_THREADS), lds, s2>>>(h->d_T, c.reads + off * L, L, cnt, c.d_frames + off * 6 * FP, FP, h->d_segtab);
-        }
-        return 0;
-    };
-    if (!in_parts) { if (translate(st, 0, n)) return -1; }
-    else {
-        // T0 | E0 + T1 | E1 + T2 | ...: the translation of part p + 1 is released together with the seed search of part p (it waits for the
-        // search of part p - 1; left to itself the side stream would run ALL translations first - their small workgroups take every slot
-        // that frees up before a seed workgroup of 8 waves fits).  A stream of the lowest priority: the seed kernel's workgroups are placed first.
-        if (!c.tr_stream) { int lo = 0, hi = 0; HIPCK(hipDeviceGetStreamPriorityRange(&lo, &hi)); HIPCK(hipStreamCreateWithPriority(&c.tr_stream, hipStreamNonBlocking, lo)); }
-        for (int p = 0; (int64_t)p * part_n < n; p++) {
-            if (!c.ev_part[p]) HIPCK(hipEventCreateWithFlags(&c.ev_part[p], hipEventDisableTiming));
-            if (!c.ev_en[p]) HIPCK(hipEventCreateWithFlags(&c.ev_en[p], hipEventDisableTiming));
-        }
-        HIPCK(hipEventRecord(c.ev_fork, st));
-        HIPCK(hipStreamWaitEvent(c.tr_stream, c.ev_fork, 0));
-        if (translate(c.tr_stream, 0, std::min(part_n, n))) return -1;
-        HIPCK(hipEventRecord(c.ev_part[0], c.tr_stream));
-        HIPCK(hipStreamWaitEvent(st, c.ev_part[0], 0));               // (what the stage's first timer sees of the translation: its first part)
-    }
-    HIPCK(hipEventRecord(c.ev[1], st));
+// The cycle counters of the MC_EXP_TIMING build (DESIGN's cycle tables), printed to stderr and cleared: at the end of the translation
+// (stage 'a') and of the finishing (stage 'd').  Without that build: nothing.
 #ifdef MC_EXP_TIMING
-    {
-        HIPCK(hipStreamSynchronize(st));
+static int exp_timing_dump(McCtx &c, char stage)
+{
+    if (stage == 'a') {
+        HIPCK(hipStreamSynchronize(c.stream));
         unsigned long long acc[12], cnt[12];
         HIPCK(hipMemcpyFromSymbol(acc, HIP_SYMBOL(g_ts_acc), sizeof acc)); HIPCK(hipMemcpyFromSymbol(cnt, HIP_SYMBOL(g_ts_cnt), sizeof cnt));
         const char *nm[12] = {"flags", "advance", "numbering", "class-0 rounds", "class-1 rounds", "reduction", "owners", "mask", "staging", "translation", "write-out", ""};
-        const double waves = (double)((n + MC_TS_READS - 1) / MC_TS_READS) * MC_TS_WAVES;
+        const double waves = (double)((c.n + MC_TS_READS - 1) / MC_TS_READS) * MC_TS_WAVES;
         for (int k = 0; k < 11; k++) fprintf(stderr, "ts-timing %-15s %9.1f cycles/wave  %8.2f entries/wave  total %8.1f Mcycles\n", nm[k], (double)acc[k] / waves, (double)cnt[k] / waves, acc[k] / 1e6);
         unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         HIPCK(hipMemcpyToSymbol(HIP_SYMBOL(g_ts_acc), z, sizeof z)); HIPCK(hipMemcpyToSymbol(HIP_SYMBOL(g_ts_cnt), z, sizeof z));
-    }
-#endif
-    if (h->fast_enum) {
-        // k_enumerate_q (round 5: queues that persist across the reads of a chunk) is the kernel of the product path; the counting form
-        // (mc_set_counting: what the reference would read) is k_enumerate_count (rounds 2 - 4's one-wave-per-read kernel without filters).
-        const bool enq = !h->count_traffic;
-        const size_t per_wave = enq ? MC_ENQ_WAVE_LDS(FP, L) : sizeof(McEnWave) + MC_EN_WAVE_LDS(FP, L);
-        // Launch shape.  k_enumerate_q: SIXTEEN waves per CU (2 workgroups of 8) where the LDS holds them - the kernel is bound by the
-        // scattered lines its CU's vector L1 has to fetch, not by issue or latency (DESIGN 5.6), and more resident waves only thrash
-        // that cache: per 1 M reads of 100 / 150 / 300 bp 24 (20 at 300 bp) waves 3.85 / 6.23 / 13.29 ms, 16 waves 3.77 / 6.11 / 13.21.
-        // The counting form (rounds 2 - 4's kernel, issue bound): as many as fit, up to 24 (16 waves 6.77 ms, 20: 6.45, 24: 6.39).
-        int waves = 0, bpc = 1;
-        {
-            static const int shapes_q[][2] = {{8, 2}, {4, 4}, {16, 1}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
-            static const int shapes_c[][2] = {{12, 2}, {8, 3}, {4, 6}, {4, 5}, {16, 1}, {8, 2}, {4, 4}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
-            if (enq) { for (const auto &sh : shapes_q) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; } }
-            else for (const auto &sh : shapes_c) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; }
-        }
-        if (!waves) { g_err = "reads too long for the seed kernel's LDS layout"; return -1; }
-        if (const char *e = getenv("MC_EN_SHAPE")) { int a = 0, b = 0; if (sscanf(e, "%d,%d", &a, &b) == 2 && (a == 16 || a == 12 || a == 8 || a == 4) && b >= 1 && (size_t)b * (64 + a * per_wave) <= 160 * 1024) { waves = a; bpc = b; } }   // (experiments)
-        const size_t lds2 = 64 + waves * per_wave;
-#ifdef MC_EN_FRONT_ONLY   /* measurement build: the lists the front writes its wildcard asks to */
-        static uint32_t *fo_items = nullptr, *fo_cursor = nullptr;
-        const uint32_t fo_cap = 80u << 20;                          /* slots per list: 8 x 80 M x 12 B = 7.7 GB */
-        if (!fo_items) { HIPCK(hipMalloc((void **)&fo_items, (size_t)8 * fo_cap * 12)); HIPCK(hipMalloc((void **)&fo_cursor, 8 * 32 * 4)); }
-        HIPCK(hipMemsetAsync(fo_cursor, 0, 8 * 32 * 4, st));
-#define MC_FO_ARGS , fo_items, fo_cap, fo_cursor
-#else
-#define MC_FO_ARGS
-#endif
-#define MC_LAUNCH_EN(KERNEL, WV)                                                                                                                   \
-    do {                                                                                                                                           \
-        HIPCK(hipFuncSetAttribute((const void *)KERNEL<WV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));                               \
-        for (int p_ = 0; (int64_t)p_ * part_n < n; p_++) {                                                                                         \
-            const int64_t off_ = (int64_t)p_ * part_n, cnt_ = std::min(part_n, n - off_);                                                          \
-            const int blocks_ = (int)std::min<int64_t>((int64_t)256 * bpc, (cnt_ + WV - 1) / WV);                                                  \
-            if (in_parts) {                                                                                                                        \
-                const int64_t off2_ = off_ + part_n;                                                                                               \
-                if (off2_ < n) {                                                                                                                   \
-                    if (p_ >= 1) HIPCK(hipStreamWaitEvent(c.tr_stream, c.ev_en[p_ - 1], 0));                                                       \
-                    if (translate(c.tr_stream, off2_, std::min(part_n, n - off2_))) return -1;                                                     \
-                    HIPCK(hipEventRecord(c.ev_part[p_ + 1], c.tr_stream));                                                                         \
-                }                                                                                                                                  \
-                HIPCK(hipStreamWaitEvent(st, c.ev_part[p_], 0));                                                                                   \
-                if (p_) HIPCK(hipMemsetAsync(c.d_counters + C_ENCHUNK, 0, 4, st));                                                                 \
-            }                                                                                                                                      \
-            KERNEL<WV><<<dim3(blocks_), dim3(64 * WV), lds2, st>>>(h->d_T, X, h->d_bitmap, c.d_frames + off_ * 6 * FP, FP, L, cnt_, c.d_tasks, c.cap_tasks, c.d_counters, \
-                                                                   c.d_stats, (uint32_t)off_, en_prio MC_FO_ARGS);                               \
-            if (in_parts) HIPCK(hipEventRecord(c.ev_en[p_], st));                                                                                  \
-        }                                                                                                                                          \
-    } while (0)
-        if (enq) { if (waves == 16) MC_LAUNCH_EN(k_enumerate_q, 16); else if (waves == 12) MC_LAUNCH_EN(k_enumerate_q, 12); else if (waves == 8) MC_LAUNCH_EN(k_enumerate_q, 8); else MC_LAUNCH_EN(k_enumerate_q, 4); }
-        else { if (waves == 16) MC_LAUNCH_EN(k_enumerate_count, 16); else if (waves == 12) MC_LAUNCH_EN(k_enumerate_count, 12); else if (waves == 8) MC_LAUNCH_EN(k_enumerate_count, 8); else MC_LAUNCH_EN(k_enumerate_count, 4); }
-#undef MC_LAUNCH_EN
-    } else
-        k_enumerate<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(h->d_T, X, c.d_frames, FP, L, n, c.d_tasks, c.cap_tasks, c.d_counters, c.d_stats);
-    HIPCK(hipEventRecord(c.ev[2], st));
-    // the number of seed hits stays on the device: persistent workgroups walk the pool
-    const size_t lds_ev = (size_t)(MC_EV_BS / 64) * MC_EV_QCAP * 32;   // a queue of survivors per wave: 32 KB per workgroup
-    const bool ranges = h->fast_enum && !h->count_traffic;            // k_enumerate_q writes ranges of hits, the other two seed kernels single hits
-    HIPCK(hipFuncSetAttribute(ranges ? (const void *)k_eval_seeds<true> : (const void *)k_eval_seeds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ev));
-    static const unsigned ev_bpc = getenv("MC_EV_BPC") ? (unsigned)std::max(1, std::min(8, atoi(getenv("MC_EV_BPC")))) : (unsigned)MC_EV_BPC;   // (experiments)
-    if (ranges) k_eval_seeds<true><<<dim3(256u * ev_bpc), dim3(MC_EV_BS), lds_ev, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_tasks, c.d_counters + C_TASKS, c.cap_tasks, c.d_hsps, c.cap_hsps, c.d_gaps, c.cap_gaps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
-    else k_eval_seeds<false><<<dim3(256u * ev_bpc), dim3(MC_EV_BS), lds_ev, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_tasks, c.d_counters + C_TASKS, c.cap_tasks, c.d_hsps, c.cap_hsps, c.d_gaps, c.cap_gaps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
-    HIPCK(hipEventRecord(c.ev[3], st));
-    return counters_to_host(c);
-}
-
-// B: gapped extension
-static int stage_b(mc_handle *h, McCtx &c)
-{
-    const int L = h->read_len, FP = h->FP;
-    hipStream_t st = c.stream;
-    McIndex X = dev_index(h);
-    if (c.h_c[C_OVERFLOW]) { g_err = "seed task / HSP / gap task buffer overflow"; return -2; }
-    c.ntasks = c.h_c[C_TASKS];
-    const uint32_t ngaps = c.ngaps = c.h_c[C_GAPS];                 // (slots of the pool: the padding of the waves' last blocks included)
-    c.gpad = c.h_c[C_GPAD];
-    if (ngaps) {
-        // 1. group the tasks that extend the same ungapped segment and list the flanks of the distinct ones (k_gap_dedupe);
-        // 2. order the flanks by DP size (a counting sort, k_gap_sort_*; the ordering kernels' buffers are idle at this point); 3. extend them with the DP rows
-        // in LDS, those whose band leaves the window again with a wider one, the rest with full-size rows; 4. every task takes its
-        // HSP from its group's flank results.  The counts of 2. - 4. stay on the device.
-        static const int gap_refill = getenv("MC_GAP_REFILL") ? std::max(1, std::min(64, atoi(getenv("MC_GAP_REFILL")))) : MC_GAP_REFILL;   // (experiments)
-        static const unsigned gap_wpc = getenv("MC_GAP_WPC") ? (unsigned)std::max(1, atoi(getenv("MC_GAP_WPC"))) : 8u;                      // waves per CU of the launch
-        uint32_t slots = 1u << 16;
-        while (slots < 2 * ngaps) slots <<= 1;
-        if (slots > c.gtab_slots) { if (dalloc(&c.d_gtab, (size_t)slots)) return -1; c.gtab_slots = slots; }
-        // The flank sort borrows the buffers of the HSP ordering: 2 ngaps keys in d_k64 (8 cap_hsps bytes), 2 ngaps items in d_idx /
-        // d_idxo (4 cap_hsps bytes each).  The pools are sized so that ordinary batches fit (ensure_capacity); a batch
-        // dense in gap tasks that does not is an overflow like any other: the range is run again in halves.
-        if (2 * (uint64_t)ngaps > c.cap_hsps) { g_err = "gap task pool larger than the sort buffers"; return -2; }
-        uint32_t *gk = (uint32_t *)c.d_k64, *gi = c.d_idx, *gio = c.d_idxo;
-        HIPCK(hipMemsetAsync(c.d_gtab, 0, (size_t)slots * 8, st));
-        HIPCK(hipMemsetAsync(c.d_ghist, 0, MC_GS_BINS * sizeof(uint32_t), st));
-        k_gap_dedupe<<<dim3((ngaps + 255) / 256), dim3(256), 0, st>>>(X, L, c.d_gaps, ngaps, c.d_gtab, slots - 1, c.d_gleader, gk, gi, c.d_counters);
-        k_gap_sort_hist<<<dim3(512), dim3(256), 0, st>>>(gk, c.d_counters + C_ITEMS, 2 * ngaps, c.d_ghist);
-        k_gap_sort_scan<<<dim3(1), dim3(1024), 0, st>>>(c.d_ghist);
-        k_gap_sort_scatter<<<dim3(512), dim3(256), 0, st>>>(gk, gi, c.d_counters + C_ITEMS, 2 * ngaps, c.d_ghist, gio);
-        k_gapped_lds<MC_GAP_WIN, 64><<<dim3(std::min<uint32_t>((2 * ngaps + 63) / 64, 256u * gap_wpc)), dim3(64), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, gio, c.d_counters + C_ITEMS, c.d_fout,
-                                                                                                                 c.d_counters + C_RETRY, c.d_retry, gap_refill, c.d_counters + C_GTAKE);
-        k_gapped_lds<MC_GAP_WIN2, MC_GAP_LANES2><<<dim3(256u * 4u), dim3(64), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, c.d_retry, c.d_counters + C_RETRY, c.d_fout, c.d_counters + C_RETRY2, c.d_retry2, 1, c.d_counters + C_GTAKE2);
-        k_gapped<<<dim3(c.gap_threads_full / 128), dim3(128), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, c.d_retry2, c.d_counters + C_RETRY2, c.d_fout, c.d_counters, c.d_gws_full, MC_GAP_W);
-        k_gap_emit<<<dim3((ngaps + 255) / 256), dim3(256), 0, st>>>(h->d_T, X, L, c.d_gaps, ngaps, c.d_gleader, c.d_fout, c.d_hsps, c.cap_hsps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
-    }
-    HIPCK(hipEventRecord(c.ev[4], st));
-    return counters_to_host(c);
-}
-
-// C: HSPs into per-read segments ordered by (subject, hit order); the reads that can print anything (see k_bin_count)
-static int stage_c(mc_handle *h, McCtx &c)
-{
-    hipStream_t st = c.stream;
-    if (c.h_c[C_OVERFLOW]) { g_err = "HSP buffer overflow"; return -2; }
-    const uint32_t nslots = c.h_c[C_HSPS];                         // used slots of the pool, the padding of the waves' last blocks included
-    c.nh_all = nslots - c.h_c[C_HPAD];
-    c.nh = c.nh_all;                                               // (best hits only: the reads that can be classified are selected on the device - cand)
-    if (c.nh) {
-        const uint32_t n = (uint32_t)c.n;
-        const uint8_t *cand = h->best_only ? c.d_cand : nullptr;
-        uint32_t *cur = c.d_heads + 1;                             // heads[0] = 0; cur[r]: counts -> starts -> ends = heads[r + 1]
-        uint64_t *keys = c.d_k64;                                  // (the gapped stage's sort buffers: free again)
-        uint32_t *slots = c.d_idxo, *order = c.d_idx, *heavy = c.d_retry2, *heavy2 = c.d_retry2 + c.cap_gaps;   // (lists of at most n reads: cap_gaps >= 10 n)
-        static const unsigned bin_blocks = getenv("MC_BIN_BLOCKS") ? (unsigned)std::max(1, atoi(getenv("MC_BIN_BLOCKS"))) : 256u * 8u;   // (experiments)
-        static const bool order_serial = getenv("MC_ORDER_SERIAL") != nullptr;                                                              // (experiments: the three order kernels one after the other)
-        HIPCK(hipMemsetAsync(c.d_heads, 0, ((size_t)n + 2) * sizeof(uint32_t), st));
-        HIPCK(hipMemsetAsync(c.d_nrow, 0, ((size_t)n + 1) * sizeof(uint32_t), st));
-        HIPCK(hipMemsetAsync(order, 0xFF, (size_t)nslots * sizeof(uint32_t), st));
-        k_bin_count<<<dim3(bin_blocks), dim3(256), 0, st>>>(c.d_hkeys, c.d_counters, c.cap_hsps, cand, cur);
-        if (mc_scan_u32(cur, n, cur, c.d_scan, st)) return -1;
-        k_bin_scatter<<<dim3(bin_blocks), dim3(256), 0, st>>>(c.d_hkeys, c.d_counters, c.cap_hsps, cand, cur, c.d_hplace, keys, c.d_places, slots);
-        // the long segments beside the short ones (the few segments of more than 512 HSPs are a long tail on a nearly empty GPU)
-        uint32_t *heavy3 = heavy2 + c.cap_gaps / 2;
-        k_order_lists<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(c.d_heads, n, c.d_counters, heavy, heavy2, heavy3);
-        hipStream_t side = order_serial ? st : c.side, side2 = order_serial ? st : h->best_only ? c.side : c.side2;   // (best hits only: few reads are ordered at all - a third stream only costs)
-        if (!order_serial) { HIPCK(hipEventRecord(c.ev_fork, st)); HIPCK(hipStreamWaitEvent(c.side, c.ev_fork, 0)); HIPCK(hipStreamWaitEvent(c.side2, c.ev_fork, 0)); }
-        HIPCK(hipFuncSetAttribute((const void *)k_order_heavy<1024, MC_ORDER_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MC_ORDER_LDS * 18)));
-        k_order_heavy<1024, MC_ORDER_LDS><<<dim3(256u), dim3(1024), MC_ORDER_LDS * 18, side>>>(keys, c.d_places, slots, c.d_heads, heavy3, c.d_counters + C_ORDER3, c.d_counters + C_OTAKE3, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
-        k_order_heavy<256, MC_ORDER_MID><<<dim3(256u * 4u), dim3(256), MC_ORDER_MID * 18, side2>>>(keys, c.d_places, slots, c.d_heads, heavy2, c.d_counters + C_ORDER2, c.d_counters + C_OTAKE2, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
-        if (!order_serial) { HIPCK(hipEventRecord(c.ev_join, c.side)); HIPCK(hipEventRecord(c.ev_join2, c.side2)); }
-        k_order_light<<<dim3((n + MC_OL_READS - 1) / MC_OL_READS), dim3(256), 0, st>>>(keys, c.d_places, slots, c.d_heads, n, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow);
-        k_order_heavy<64, MC_ORDER_SMALL><<<dim3(256u * 16u), dim3(64), MC_ORDER_SMALL * 18, st>>>(keys, c.d_places, slots, c.d_heads, heavy, c.d_counters + C_ORDER, c.d_counters + C_OTAKE, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
-        if (!order_serial) { HIPCK(hipStreamWaitEvent(st, c.ev_join, 0)); HIPCK(hipStreamWaitEvent(st, c.ev_join2, 0)); }
-        k_order_copy<<<dim3(256u * 8u), dim3(256), 0, st>>>(order, c.d_gsz, c.d_hsps, c.d_heads, n, c.d_v);
-        if (getenv("MC_BIN_STATS")) {                                  // (development aid: the sizes of the segments)
-            std::vector<uint32_t> hh((size_t)n + 1);
-            HIPCK(hipStreamSynchronize(st));
-            HIPCK(hipMemcpy(hh.data(), c.d_heads, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
-            const uint32_t lim[9] = {16, 32, 64, 128, 512, 2048, 8192, 32768, 0xFFFFFFFFu};
-            uint64_t cnt[9] = {0}, sum[9] = {0};
-            std::vector<uint32_t> top;
-            for (uint32_t r = 0; r < n; r++) { const uint32_t k = hh[r + 1] - hh[r]; if (!k) continue; for (int b = 0; b < 9; b++) if (k <= lim[b]) { cnt[b]++; sum[b] += k; break; } if (k > 2048) top.push_back(k); }
-            std::sort(top.rbegin(), top.rend());
-            fprintf(stderr, "bin-stats segments <=16 32 64 128 512 2048 8192 32768 more: reads"); for (int b = 0; b < 9; b++) fprintf(stderr, " %llu", (unsigned long long)cnt[b]);
-            fprintf(stderr, "; HSPs"); for (int b = 0; b < 9; b++) fprintf(stderr, " %llu", (unsigned long long)sum[b]);
-            fprintf(stderr, "; largest:"); for (size_t i = 0; i < top.size() && i < 12; i++) fprintf(stderr, " %u", top[i]); fprintf(stderr, "\n");
-        }
-    }
-    HIPCK(hipEventRecord(c.ev[5], st));
-    return 0;
-}
-
-// D: per-read finishing (linking, ranking, cap, classification), rows into m8 order
-static int stage_d(mc_handle *h, McCtx &c)
-{
-    hipStream_t st = c.stream;
-    McIndex X = dev_index(h);
-    const uint32_t nh = c.nh, nheads = c.nheads = nh ? (uint32_t)c.n : 0u;   // (every read has a segment, most of them empty or unmarked)
-    if (nh) {
-        // the thread-per-read kernel (reads with few HSPs) on this stream, the wave-per-read kernels one after the other on a
-        // second one (each hands the reads its LDS arrays cannot hold to the next)
-        uint32_t *d_heavy = c.d_retry, *d_heavy2 = c.d_retry + c.cap_gaps / 2, *d_heavy3 = c.d_retry + c.cap_gaps;      // (d_retry is free again: the gap tasks are done)
-        uint32_t *d_light = c.d_retry + c.cap_gaps + c.cap_gaps / 2;
-        uint32_t *d_heavy1 = c.d_retry2, *d_heap_order = c.d_retry2 + c.cap_gaps;   // (the ordering kernels' lists: done)
-        const uint32_t light_pitch = (uint32_t)c.cap_reads + 1;
-        k_heavy_lists<<<dim3((nheads + 255) / 256), dim3(256), 0, st>>>(c.d_nv, nheads, c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_light, light_pitch, h->best_only ? MC_FH_MIN_BEST : MC_FH_MIN,
-                                                                         d_heavy1, d_heavy2, d_heavy3);
-        HIPCK(hipEventRecord(c.ev_fork, st));
-        {
-            const size_t l1 = (size_t)MC_FH_N1 * 16 + 3 * (size_t)(MC_FH_N1 + 2) * 2, l2 = (size_t)MC_FH_N2 * 16 + 3 * (size_t)(MC_FH_N2 + 2) * 2, l3 = (size_t)MC_FH_N3 * 16 + 3 * (size_t)(MC_FH_N3 + 2) * 2;
-            HIPCK(hipFuncSetAttribute((const void *)k_finish_heavy<MC_FH_N3, C_HEAVY3, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
-            HIPCK(hipStreamWaitEvent(c.side, c.ev_fork, 0));
-            HIPCK(hipStreamWaitEvent(c.side2, c.ev_fork, 0));
-            // the two kernels of the larger reads (few reads, long chains, a fraction of the GPU) beside the first one.  (Round 5, kernel trace:
-            // second + third, 0.84 ms per 1 M reads, is the longer chain in front of MergeRes' heap sort; the third in front of the thread-per-read
-            // kernels on this stream, or in front of the first on its stream, made the stage 0.1 - 0.2 ms LONGER - whatever runs behind the
-            // third waits for its few long reads, and they hold 135 KB of a CU's LDS each.)
-            const unsigned wpc2 = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (size_t)(158 * 1024) / (l2 + 1024)));   // waves per CU the LDS holds
-            // (the lists of the first two kernels with the longest stacks first - k_heavy_order; the third has a few dozen reads)
-            static const bool fh_sort = !(getenv("MC_FH_SORT") && atoi(getenv("MC_FH_SORT")) == 0);
-            uint32_t *d_sorted1 = c.d_retry2 + c.cap_gaps / 2, *d_sorted2 = c.d_retry2 + c.cap_gaps + c.cap_gaps / 2;      // (lists of at most n reads: cap_gaps >= 10 n)
-            if (fh_sort) k_heavy_order<<<dim3(1), dim3(1024), 0, c.side2>>>(d_heavy2, c.d_counters + C_HEAVY2, d_heavy, c.d_nv, 2, d_sorted2);
-            k_finish_heavy<MC_FH_N2, C_HEAVY2, -1><<<dim3(256 * wpc2), dim3(64), l2, c.side2>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
-                                                                                            c.d_nrow, c.d_bestof, c.d_counters, d_heavy, fh_sort ? d_sorted2 : d_heavy2, nullptr);
-            k_finish_heavy<MC_FH_N3, C_HEAVY3, -1><<<dim3(256), dim3(64), l3, c.side2>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
-                                                                                         c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_heavy3, nullptr);
-            HIPCK(hipEventRecord(c.ev_join2, c.side2));
-            if (fh_sort) k_heavy_order<<<dim3(1), dim3(1024), 0, c.side>>>(d_heavy1, c.d_counters + C_HEAVY1, d_heavy, c.d_nv, 0, d_sorted1);
-            k_finish_heavy<MC_FH_N1, C_HEAVY1, -1><<<dim3(256 * 12), dim3(64), l1, c.side>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
-                                                                                            c.d_nrow, c.d_bestof, c.d_counters, d_heavy, fh_sort ? d_sorted1 : d_heavy1, nullptr);
-            HIPCK(hipStreamWaitEvent(c.side, c.ev_join2, 0));
-            // MergeRes' heap sort of all of them (a lane per read), then their rows (a wave per read)
-            const size_t lh = (size_t)(MC_MAX_M8 + 2) * 64 * 4;
-            HIPCK(hipFuncSetAttribute((const void *)k_heap_lanes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lh));
-            k_heap_order<<<dim3(1), dim3(1024), 0, c.side>>>(d_heavy, c.d_nrow, c.d_counters, d_heap_order);
-            k_heap_lanes<<<dim3(256), dim3(64), lh, c.side>>>(c.d_heads, nheads, nh, c.d_tmp, c.d_nrow, c.d_counters, d_heavy, d_heap_order);
-            k_heavy_rows<<<dim3(256 * 12), dim3(64), 0, c.side>>>(h->d_T, X, h->d_P, h->d_fam, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id, c.d_nrow, c.d_bestof, c.d_counters, d_heavy);
-            HIPCK(hipEventRecord(c.ev_join, c.side));
-        }
-        // the light reads: the four size classes side by side (the counts stay on the device; blocks past a class' count leave at once)
-        {   // (size classes 2, 3 - up to 48 / MC_FH_MIN stacked HSPs - with MC_FH_MIN items of LDS per thread, classes 0, 1 - up to 4 / 16 - with 16; the
-            // items are reached through generic pointers - mc_finish_stacked is shared with the host - and a flat access to LDS must stay
-            // below 64 KB of the workgroup's allocation: 32 and 128 threads per workgroup)
-            const size_t lb = 32 * (MC_FH_MIN * 16 + 16), ls = 128 * (16 * 16 + 16);
-            static const int fin_lds = getenv("MC_FINISH_GLOBAL") ? 0 : 1;          // (experiments: the items in global scratch, as before round 4)
-            HIPCK(hipFuncSetAttribute((const void *)k_finish<32, MC_FH_MIN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-            k_finish<32, MC_FH_MIN, 2><<<dim3((nheads + 31) / 32, 2), dim3(32), lb, st>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp,
-                                                                                 c.first_read_id, c.d_nrow, c.d_bestof, d_light, light_pitch, c.d_counters + C_LIGHT0, fin_lds);
-            k_finish<128, 16, 0><<<dim3((nheads + 127) / 128, 2), dim3(128), ls, st>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp,
-                                                                                     c.first_read_id, c.d_nrow, c.d_bestof, d_light, light_pitch, c.d_counters + C_LIGHT0, fin_lds);
-        }
-        HIPCK(hipStreamWaitEvent(st, c.ev_join, 0));
-        if (mc_scan_u32(c.d_nrow, nheads, c.d_rowoff, c.d_scan, st)) return -1;
-        if (h->rows_ever) HIPCK(hipStreamWaitEvent(st, h->ev_rows, 0));   // (the rows of the run before may still be leaving d_rows)
-        k_emit_rows<<<dim3((nheads + 255) / 256), dim3(256), 0, st>>>(c.d_heads, nheads, c.d_nrow, c.d_rowoff, c.d_tmp, c.d_rows, c.cap_rows, c.d_bestof, c.d_best, c.d_counters, h->best_only ? 0 : 1);
-    }
-    HIPCK(hipEventRecord(c.ev[6], st));
-#ifdef MC_EXP_TIMING
-    {
-        HIPCK(hipStreamSynchronize(st)); HIPCK(hipStreamSynchronize(c.side));
+    } else {
+        HIPCK(hipStreamSynchronize(c.stream)); HIPCK(hipStreamSynchronize(c.side));
         unsigned long long acc[8], cnt[8];
         HIPCK(hipMemcpyFromSymbol(acc, HIP_SYMBOL(g_fh_acc), sizeof acc)); HIPCK(hipMemcpyFromSymbol(cnt, HIP_SYMBOL(g_fh_cnt), sizeof cnt));
         {
@@ -811,7 +521,223 @@ static int stage_d(mc_handle *h, McCtx &c)
         unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         HIPCK(hipMemcpyToSymbol(HIP_SYMBOL(g_fh_acc), z, sizeof z)); HIPCK(hipMemcpyToSymbol(HIP_SYMBOL(g_fh_cnt), z, sizeof z));
     }
+    return 0;
+}
+#else
+static int exp_timing_dump(McCtx &, char) { return 0; }
 #endif
+
+// A: translation + SEG, seed enumeration, seed evaluation (gate, growth, ungapped X-drop)
+static int stage_a(mc_handle *h, McCtx &c)
+{
+    const int64_t n = c.n;
+    const int L = h->read_len, FP = h->FP;
+    hipStream_t st = c.stream;
+    McIndex X = dev_index(h);
+    c.ntasks = c.ngaps = c.gpad = c.nh = c.nheads = c.nrows = c.nbest = c.nsegs = 0;
+    HIPCK(hipMemsetAsync(c.d_counters, 0, sizeof(uint32_t) * C_N, st));
+    HIPCK(hipMemsetAsync(c.d_stats, 0, sizeof(unsigned long long) * S_N, st));
+    if (h->best_only) HIPCK(hipMemsetAsync(c.d_cand, 0, (size_t)n, st));
+    HIPCK(hipMemsetAsync(c.d_low, 0, (size_t)n, st));
+    HIPCK(hipEventRecord(c.ev[0], st));
+    const int64_t threads = n * 6;
+    const size_t lds_rest = (size_t)MC_TS_NLNF(FP) * 8 + (size_t)MC_TS_THREADS * MC_TS_STRIDE(FP);
+    const size_t lds_staged = (size_t)MC_TS_STAGE(L) + lds_rest, lds_direct = (size_t)MC_TS_STAGE(0) + lds_rest;
+    static const int ts_force = getenv("MC_TS_STAGED") ? atoi(getenv("MC_TS_STAGED")) : -1;
+    const size_t cu_lds = 160 * 1024 - 1024;                      // (static LDS of the kernel and allocation granules)
+    const bool staged = ts_force >= 0 ? ts_force != 0 : cu_lds / lds_staged >= cu_lds / lds_direct;   // staging stays while it does not cost a resident workgroup
+    const size_t lds = staged ? lds_staged : lds_direct;
+    const unsigned ts_blocks = (unsigned)((n + MC_TS_READS - 1) / MC_TS_READS);
+    if (staged) {
+        if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_translate_seg<true><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, c.reads, L, n, c.d_frames, FP, h->d_segtab);
+    } else {
+        if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_translate_seg<false><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, c.reads, L, n, c.d_frames, FP, h->d_segtab);
+    }
+    HIPCK(hipEventRecord(c.ev[1], st));
+    if (exp_timing_dump(c, 'a')) return -1;
+    if (h->fast_enum) {
+        // k_enumerate_q (round 5: queues that persist across the reads of a chunk) is the kernel of the product path; the counting form
+        // (mc_set_counting: what the reference would read) is k_enumerate_count (rounds 2 - 4's one-wave-per-read kernel without filters).
+        const bool enq = !h->count_traffic;
+        const size_t per_wave = enq ? MC_ENQ_WAVE_LDS(FP, L) : sizeof(McEnWave) + MC_EN_WAVE_LDS(FP, L);
+        // Launch shape.  k_enumerate_q: SIXTEEN waves per CU (2 workgroups of 8) where the LDS holds them - the kernel is bound by the
+        // scattered lines its CU's vector L1 has to fetch, not by issue or latency (DESIGN 5.6), and more resident waves only thrash
+        // that cache: per 1 M reads of 100 / 150 / 300 bp 24 (20 at 300 bp) waves 3.85 / 6.23 / 13.29 ms, 16 waves 3.77 / 6.11 / 13.21.
+        // The counting form (rounds 2 - 4's kernel, issue bound): as many as fit, up to 24 (16 waves 6.77 ms, 20: 6.45, 24: 6.39).
+        int waves = 0, bpc = 1;
+        {
+            static const int shapes_q[][2] = {{8, 2}, {4, 4}, {16, 1}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
+            static const int shapes_c[][2] = {{12, 2}, {8, 3}, {4, 6}, {4, 5}, {16, 1}, {8, 2}, {4, 4}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
+            if (enq) { for (const auto &sh : shapes_q) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; } }
+            else for (const auto &sh : shapes_c) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; }
+        }
+        if (!waves) { g_err = "reads too long for the seed kernel's LDS layout"; return -1; }
+        const size_t lds2 = 64 + waves * per_wave;
+#define MC_LAUNCH_EN(KERNEL, WV)                                                                                                                   \
+    do {                                                                                                                                           \
+        HIPCK(hipFuncSetAttribute((const void *)KERNEL<WV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));                               \
+        const int blocks_ = (int)std::min<int64_t>((int64_t)256 * bpc, (n + WV - 1) / WV);                                                         \
+        KERNEL<WV><<<dim3(blocks_), dim3(64 * WV), lds2, st>>>(h->d_T, X, h->d_bitmap, c.d_frames, FP, L, n, c.d_tasks, c.cap_tasks, c.d_counters, c.d_stats); \
+    } while (0)
+        if (enq) { if (waves == 16) MC_LAUNCH_EN(k_enumerate_q, 16); else if (waves == 12) MC_LAUNCH_EN(k_enumerate_q, 12); else if (waves == 8) MC_LAUNCH_EN(k_enumerate_q, 8); else MC_LAUNCH_EN(k_enumerate_q, 4); }
+        else { if (waves == 16) MC_LAUNCH_EN(k_enumerate_count, 16); else if (waves == 12) MC_LAUNCH_EN(k_enumerate_count, 12); else if (waves == 8) MC_LAUNCH_EN(k_enumerate_count, 8); else MC_LAUNCH_EN(k_enumerate_count, 4); }
+#undef MC_LAUNCH_EN
+    } else
+        k_enumerate<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(h->d_T, X, c.d_frames, FP, L, n, c.d_tasks, c.cap_tasks, c.d_counters, c.d_stats);
+    HIPCK(hipEventRecord(c.ev[2], st));
+    // the number of seed hits stays on the device: persistent workgroups walk the pool
+    const size_t lds_ev = (size_t)(MC_EV_BS / 64) * MC_EV_QCAP * 32;   // a queue of survivors per wave: 32 KB per workgroup
+    const bool ranges = h->fast_enum && !h->count_traffic;            // k_enumerate_q writes ranges of hits, the other two seed kernels single hits
+    HIPCK(hipFuncSetAttribute(ranges ? (const void *)k_eval_seeds<true> : (const void *)k_eval_seeds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ev));
+    if (ranges) k_eval_seeds<true><<<dim3(256u * MC_EV_BPC), dim3(MC_EV_BS), lds_ev, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_tasks, c.d_counters + C_TASKS, c.cap_tasks, c.d_hsps, c.cap_hsps, c.d_gaps, c.cap_gaps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
+    else k_eval_seeds<false><<<dim3(256u * MC_EV_BPC), dim3(MC_EV_BS), lds_ev, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_tasks, c.d_counters + C_TASKS, c.cap_tasks, c.d_hsps, c.cap_hsps, c.d_gaps, c.cap_gaps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
+    HIPCK(hipEventRecord(c.ev[3], st));
+    return counters_to_host(c);
+}
+
+// B: gapped extension
+static int stage_b(mc_handle *h, McCtx &c)
+{
+    const int L = h->read_len, FP = h->FP;
+    hipStream_t st = c.stream;
+    McIndex X = dev_index(h);
+    if (c.h_c[C_OVERFLOW]) { g_err = "seed task / HSP / gap task buffer overflow"; return -2; }
+    c.ntasks = c.h_c[C_TASKS];
+    const uint32_t ngaps = c.ngaps = c.h_c[C_GAPS];                 // (slots of the pool: the padding of the waves' last blocks included)
+    c.gpad = c.h_c[C_GPAD];
+    if (ngaps) {
+        // 1. group the tasks that extend the same ungapped segment and list the flanks of the distinct ones (k_gap_dedupe);
+        // 2. order the flanks by DP size (a counting sort, k_gap_sort_*; the ordering kernels' buffers are idle at this point); 3. extend them with the DP rows
+        // in LDS, those whose band leaves the window again with a wider one, the rest with full-size rows; 4. every task takes its
+        // HSP from its group's flank results.  The counts of 2. - 4. stay on the device.
+        uint32_t slots = 1u << 16;
+        while (slots < 2 * ngaps) slots <<= 1;
+        if (slots > c.gtab_slots) { if (dalloc(&c.d_gtab, (size_t)slots)) return -1; c.gtab_slots = slots; }
+        // The flank sort borrows the buffers of the HSP ordering: 2 ngaps keys in d_k64 (8 cap_hsps bytes), 2 ngaps items in d_idx /
+        // d_idxo (4 cap_hsps bytes each).  The pools are sized so that ordinary batches fit (ensure_capacity); a batch
+        // dense in gap tasks that does not is an overflow like any other: the range is run again in halves.
+        if (2 * (uint64_t)ngaps > c.cap_hsps) { g_err = "gap task pool larger than the sort buffers"; return -2; }
+        uint32_t *gk = (uint32_t *)c.d_k64, *gi = c.d_idx, *gio = c.d_idxo;
+        HIPCK(hipMemsetAsync(c.d_gtab, 0, (size_t)slots * 8, st));
+        HIPCK(hipMemsetAsync(c.d_ghist, 0, MC_GS_BINS * sizeof(uint32_t), st));
+        k_gap_dedupe<<<dim3((ngaps + 255) / 256), dim3(256), 0, st>>>(X, L, c.d_gaps, ngaps, c.d_gtab, slots - 1, c.d_gleader, gk, gi, c.d_counters);
+        k_gap_sort_hist<<<dim3(512), dim3(256), 0, st>>>(gk, c.d_counters + C_ITEMS, 2 * ngaps, c.d_ghist);
+        k_gap_sort_scan<<<dim3(1), dim3(1024), 0, st>>>(c.d_ghist);
+        k_gap_sort_scatter<<<dim3(512), dim3(256), 0, st>>>(gk, gi, c.d_counters + C_ITEMS, 2 * ngaps, c.d_ghist, gio);
+        k_gapped_lds<MC_GAP_WIN, 64, MC_GAP_REFILL><<<dim3(std::min<uint32_t>((2 * ngaps + 63) / 64, 256u * 8u)), dim3(64), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, gio, c.d_counters + C_ITEMS, c.d_fout,
+                                                                                                                          c.d_counters + C_RETRY, c.d_retry, c.d_counters + C_GTAKE);   // (8 waves per CU)
+        k_gapped_lds<MC_GAP_WIN2, MC_GAP_LANES2, 1><<<dim3(256u * 4u), dim3(64), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, c.d_retry, c.d_counters + C_RETRY, c.d_fout, c.d_counters + C_RETRY2, c.d_retry2, c.d_counters + C_GTAKE2);
+        k_gapped<<<dim3(c.gap_threads_full / 128), dim3(128), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, c.d_retry2, c.d_counters + C_RETRY2, c.d_fout, c.d_counters, c.d_gws_full, MC_GAP_W);
+        k_gap_emit<<<dim3((ngaps + 255) / 256), dim3(256), 0, st>>>(h->d_T, X, L, c.d_gaps, ngaps, c.d_gleader, c.d_fout, c.d_hsps, c.cap_hsps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
+    }
+    HIPCK(hipEventRecord(c.ev[4], st));
+    return counters_to_host(c);
+}
+
+// C: HSPs into per-read segments ordered by (subject, hit order); the reads that can print anything (see k_bin_count)
+static int stage_c(mc_handle *h, McCtx &c)
+{
+    hipStream_t st = c.stream;
+    if (c.h_c[C_OVERFLOW]) { g_err = "HSP buffer overflow"; return -2; }
+    const uint32_t nslots = c.h_c[C_HSPS];                         // used slots of the pool, the padding of the waves' last blocks included
+    c.nh_all = nslots - c.h_c[C_HPAD];
+    c.nh = c.nh_all;                                               // (best hits only: the reads that can be classified are selected on the device - cand)
+    if (c.nh) {
+        const uint32_t n = (uint32_t)c.n;
+        const uint8_t *cand = h->best_only ? c.d_cand : nullptr;
+        uint32_t *cur = c.d_heads + 1;                             // heads[0] = 0; cur[r]: counts -> starts -> ends = heads[r + 1]
+        uint64_t *keys = c.d_k64;                                  // (the gapped stage's sort buffers: free again)
+        uint32_t *slots = c.d_idxo, *order = c.d_idx, *heavy = c.d_retry2, *heavy2 = c.d_retry2 + c.cap_gaps;   // (lists of at most n reads: cap_gaps >= 10 n)
+        HIPCK(hipMemsetAsync(c.d_heads, 0, ((size_t)n + 2) * sizeof(uint32_t), st));
+        HIPCK(hipMemsetAsync(c.d_nrow, 0, ((size_t)n + 1) * sizeof(uint32_t), st));
+        HIPCK(hipMemsetAsync(order, 0xFF, (size_t)nslots * sizeof(uint32_t), st));
+        k_bin_count<<<dim3(256u * 8u), dim3(256), 0, st>>>(c.d_hkeys, c.d_counters, c.cap_hsps, cand, cur);
+        if (mc_scan_u32(cur, n, cur, c.d_scan, st)) return -1;
+        k_bin_scatter<<<dim3(256u * 8u), dim3(256), 0, st>>>(c.d_hkeys, c.d_counters, c.cap_hsps, cand, cur, c.d_hplace, keys, c.d_places, slots);
+        // the long segments beside the short ones (the few segments of more than 512 HSPs are a long tail on a nearly empty GPU)
+        uint32_t *heavy3 = heavy2 + c.cap_gaps / 2;
+        k_order_lists<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(c.d_heads, n, c.d_counters, heavy, heavy2, heavy3);
+        hipStream_t side = c.side, side2 = h->best_only ? c.side : c.side2;   // (best hits only: few reads are ordered at all - a third stream only costs)
+        HIPCK(hipEventRecord(c.ev_fork, st)); HIPCK(hipStreamWaitEvent(c.side, c.ev_fork, 0)); HIPCK(hipStreamWaitEvent(c.side2, c.ev_fork, 0));
+        HIPCK(hipFuncSetAttribute((const void *)k_order_heavy<1024, MC_ORDER_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MC_ORDER_LDS * 18)));
+        k_order_heavy<1024, MC_ORDER_LDS><<<dim3(256u), dim3(1024), MC_ORDER_LDS * 18, side>>>(keys, c.d_places, slots, c.d_heads, heavy3, c.d_counters + C_ORDER3, c.d_counters + C_OTAKE3, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
+        k_order_heavy<256, MC_ORDER_MID><<<dim3(256u * 4u), dim3(256), MC_ORDER_MID * 18, side2>>>(keys, c.d_places, slots, c.d_heads, heavy2, c.d_counters + C_ORDER2, c.d_counters + C_OTAKE2, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
+        HIPCK(hipEventRecord(c.ev_join, c.side)); HIPCK(hipEventRecord(c.ev_join2, c.side2));
+        k_order_light<<<dim3((n + MC_OL_READS - 1) / MC_OL_READS), dim3(256), 0, st>>>(keys, c.d_places, slots, c.d_heads, n, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow);
+        k_order_heavy<64, MC_ORDER_SMALL><<<dim3(256u * 16u), dim3(64), MC_ORDER_SMALL * 18, st>>>(keys, c.d_places, slots, c.d_heads, heavy, c.d_counters + C_ORDER, c.d_counters + C_OTAKE, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
+        HIPCK(hipStreamWaitEvent(st, c.ev_join, 0)); HIPCK(hipStreamWaitEvent(st, c.ev_join2, 0));
+        k_order_copy<<<dim3(256u * 8u), dim3(256), 0, st>>>(order, c.d_gsz, c.d_hsps, c.d_heads, n, c.d_v);
+    }
+    HIPCK(hipEventRecord(c.ev[5], st));
+    return 0;
+}
+
+// D: per-read finishing (linking, ranking, cap, classification), rows into m8 order
+static int stage_d(mc_handle *h, McCtx &c)
+{
+    hipStream_t st = c.stream;
+    McIndex X = dev_index(h);
+    const uint32_t nh = c.nh, nheads = c.nheads = nh ? (uint32_t)c.n : 0u;   // (every read has a segment, most of them empty or unmarked)
+    if (nh) {
+        // the thread-per-read kernel (reads with few HSPs) on this stream, the wave-per-read kernels one after the other on a
+        // second one (each hands the reads its LDS arrays cannot hold to the next)
+        uint32_t *d_heavy = c.d_retry, *d_heavy2 = c.d_retry + c.cap_gaps / 2, *d_heavy3 = c.d_retry + c.cap_gaps;      // (d_retry is free again: the gap tasks are done)
+        uint32_t *d_light = c.d_retry + c.cap_gaps + c.cap_gaps / 2;
+        uint32_t *d_heavy1 = c.d_retry2, *d_heap_order = c.d_retry2 + c.cap_gaps;   // (the ordering kernels' lists: done)
+        const uint32_t light_pitch = (uint32_t)c.cap_reads + 1;
+        k_heavy_lists<<<dim3((nheads + 255) / 256), dim3(256), 0, st>>>(c.d_nv, nheads, c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_light, light_pitch, h->best_only ? MC_FH_MIN_BEST : MC_FH_MIN,
+                                                                         d_heavy1, d_heavy2, d_heavy3);
+        HIPCK(hipEventRecord(c.ev_fork, st));
+        {
+            const size_t l1 = (size_t)MC_FH_N1 * 16 + 3 * (size_t)(MC_FH_N1 + 2) * 2, l2 = (size_t)MC_FH_N2 * 16 + 3 * (size_t)(MC_FH_N2 + 2) * 2, l3 = (size_t)MC_FH_N3 * 16 + 3 * (size_t)(MC_FH_N3 + 2) * 2;
+            HIPCK(hipFuncSetAttribute((const void *)k_finish_heavy<MC_FH_N3, C_HEAVY3, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
+            HIPCK(hipStreamWaitEvent(c.side, c.ev_fork, 0));
+            HIPCK(hipStreamWaitEvent(c.side2, c.ev_fork, 0));
+            // the two kernels of the larger reads (few reads, long chains, a fraction of the GPU) beside the first one.  (Round 5, kernel trace:
+            // second + third, 0.84 ms per 1 M reads, is the longer chain in front of MergeRes' heap sort; the third in front of the thread-per-read
+            // kernels on this stream, or in front of the first on its stream, made the stage 0.1 - 0.2 ms LONGER - whatever runs behind the
+            // third waits for its few long reads, and they hold 135 KB of a CU's LDS each.)
+            const unsigned wpc2 = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (size_t)(158 * 1024) / (l2 + 1024)));   // waves per CU the LDS holds
+            // (the lists of the first two kernels with the longest stacks first - k_heavy_order; the third has a few dozen reads)
+            uint32_t *d_sorted1 = c.d_retry2 + c.cap_gaps / 2, *d_sorted2 = c.d_retry2 + c.cap_gaps + c.cap_gaps / 2;      // (lists of at most n reads: cap_gaps >= 10 n)
+            k_heavy_order<<<dim3(1), dim3(1024), 0, c.side2>>>(d_heavy2, c.d_counters + C_HEAVY2, d_heavy, c.d_nv, 2, d_sorted2);
+            k_finish_heavy<MC_FH_N2, C_HEAVY2, -1><<<dim3(256 * wpc2), dim3(64), l2, c.side2>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
+                                                                                            c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_sorted2, nullptr);
+            k_finish_heavy<MC_FH_N3, C_HEAVY3, -1><<<dim3(256), dim3(64), l3, c.side2>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
+                                                                                         c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_heavy3, nullptr);
+            HIPCK(hipEventRecord(c.ev_join2, c.side2));
+            k_heavy_order<<<dim3(1), dim3(1024), 0, c.side>>>(d_heavy1, c.d_counters + C_HEAVY1, d_heavy, c.d_nv, 0, d_sorted1);
+            k_finish_heavy<MC_FH_N1, C_HEAVY1, -1><<<dim3(256 * 12), dim3(64), l1, c.side>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
+                                                                                            c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_sorted1, nullptr);
+            HIPCK(hipStreamWaitEvent(c.side, c.ev_join2, 0));
+            // MergeRes' heap sort of all of them (a lane per read), then their rows (a wave per read)
+            const size_t lh = (size_t)(MC_MAX_M8 + 2) * 64 * 4;
+            HIPCK(hipFuncSetAttribute((const void *)k_heap_lanes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lh));
+            k_heap_order<<<dim3(1), dim3(1024), 0, c.side>>>(d_heavy, c.d_nrow, c.d_counters, d_heap_order);
+            k_heap_lanes<<<dim3(256), dim3(64), lh, c.side>>>(c.d_heads, nheads, nh, c.d_tmp, c.d_nrow, c.d_counters, d_heavy, d_heap_order);
+            k_heavy_rows<<<dim3(256 * 12), dim3(64), 0, c.side>>>(h->d_T, X, h->d_P, h->d_fam, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id, c.d_nrow, c.d_bestof, c.d_counters, d_heavy);
+            HIPCK(hipEventRecord(c.ev_join, c.side));
+        }
+        // the light reads: the four size classes side by side (the counts stay on the device; blocks past a class' count leave at once)
+        {   // (size classes 2, 3 - up to 48 / MC_FH_MIN stacked HSPs - with MC_FH_MIN items of LDS per thread, classes 0, 1 - up to 4 / 16 - with 16; the
+            // items are reached through generic pointers - mc_finish_stacked is shared with the host - and a flat access to LDS must stay
+            // below 64 KB of the workgroup's allocation: 32 and 128 threads per workgroup)
+            const size_t lb = 32 * (MC_FH_MIN * 16 + 16), ls = 128 * (16 * 16 + 16);
+            HIPCK(hipFuncSetAttribute((const void *)k_finish<32, MC_FH_MIN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
+            k_finish<32, MC_FH_MIN, 2><<<dim3((nheads + 31) / 32, 2), dim3(32), lb, st>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp,
+                                                                                 c.first_read_id, c.d_nrow, c.d_bestof, d_light, light_pitch, c.d_counters + C_LIGHT0);
+            k_finish<128, 16, 0><<<dim3((nheads + 127) / 128, 2), dim3(128), ls, st>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp,
+                                                                                     c.first_read_id, c.d_nrow, c.d_bestof, d_light, light_pitch, c.d_counters + C_LIGHT0);
+        }
+        HIPCK(hipStreamWaitEvent(st, c.ev_join, 0));
+        if (mc_scan_u32(c.d_nrow, nheads, c.d_rowoff, c.d_scan, st)) return -1;
+        if (h->rows_ever) HIPCK(hipStreamWaitEvent(st, h->ev_rows, 0));   // (the rows of the run before may still be leaving d_rows)
+        k_emit_rows<<<dim3((nheads + 255) / 256), dim3(256), 0, st>>>(c.d_heads, nheads, c.d_nrow, c.d_rowoff, c.d_tmp, c.d_rows, c.cap_rows, c.d_bestof, c.d_best, c.d_counters, h->best_only ? 0 : 1);
+    }
+    HIPCK(hipEventRecord(c.ev[6], st));
+    if (exp_timing_dump(c, 'd')) return -1;
     HIPCK(hipMemcpyAsync(c.h_stats, c.d_stats, sizeof(unsigned long long) * S_N, hipMemcpyDeviceToHost, st));
     return counters_to_host(c);
 }
@@ -962,7 +888,7 @@ static int run_range_once(mc_handle *h, int64_t first, int64_t count, int64_t fi
 {
     if (range_check(h, first, count)) return -1;
     if (count == 0) { memset(&h->stats, 0, sizeof h->stats); h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr; return 0; }
-    McCtx &c = h->ctx[0];
+    McCtx &c = h->ctx;
     const int rc = range_begin(h, c, first, count, first_read_id);
     if (rc) return rc;
     return range_end(h, c);
@@ -980,7 +906,7 @@ extern "C" int mc_range_begin(mc_handle *h, int64_t first, int64_t count, int64_
     if (range_check(h, first, count)) return -1;
     if (count <= 0) { g_err = "mc_range_begin: an empty range"; return -1; }
     if (h->pipe_nout) { g_err = "mc_range_begin: a range is in flight already (mc_range_end first)"; return -1; }
-    const int rc = range_begin(h, h->ctx[0], first, count, first_read_id);
+    const int rc = range_begin(h, h->ctx, first, count, first_read_id);
     if (rc) return rc;
     h->pipe_nout = 1;
     return 0;
@@ -992,7 +918,7 @@ extern "C" int mc_range_end(mc_handle *h)
     if (h->pipe_nout == 0) { g_err = "mc_range_end: no range in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     h->pipe_nout = 0;
-    return range_end(h, h->ctx[0]);
+    return range_end(h, h->ctx);
 }
 
 extern "C" int mc_ranges_in_flight(const mc_handle *h) { return h ? h->pipe_nout : 0; }
@@ -1007,7 +933,7 @@ extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap
     if (!h || !h->run_set || what < 0 || what > 3) { g_err = "mc_debug_stage: bad argument"; return -1; }
     if (h->pipe_nout) { g_err = "mc_debug_stage: ranges are in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    const McCtx &c = h->ctx[0];
+    const McCtx &c = h->ctx;
     const void *src = nullptr; int64_t bytes = 0; int32_t rec = 0;
     if (what == 0) { src = c.d_frames; rec = h->FP; bytes = c.n * 6 * (int64_t)h->FP; }
     else if (what == 1) { src = c.d_tasks; rec = (int32_t)sizeof(McSeedTask); bytes = (int64_t)c.ntasks * rec; }
@@ -1065,7 +991,7 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
         MC_OT("run_stream: staging buffers", t0);
     }
     if (!h->copy_stream) HIPCK(hipStreamCreate(&h->copy_stream));
-    if (expect_reads > 0 && ensure_capacity(h, h->ctx[0], std::min<int64_t>(bmax_run, expect_reads))) return -1;
+    if (expect_reads > 0 && ensure_capacity(h, h->ctx, std::min<int64_t>(bmax_run, expect_reads))) return -1;
     MC_OT("run_stream: pools", t0);
     McBatchSlot slot[2];
     for (int k = 0; k < 2; k++) { slot[k].pin = h->stage_pin[k]; slot[k].dev = h->stage_dev[k]; }
@@ -1278,14 +1204,14 @@ static void vl_pieces(const std::vector<uint32_t> &start, int64_t batch, std::ve
 // fixed-length run after this one then finds its pools in place)
 static int vl_pools(mc_handle *h, int Lmax, int64_t nmax)
 {
-    McCtx &c = h->ctx[0];
+    McCtx &c = h->ctx;
     h->read_len = Lmax; h->FP = ((Lmax / 3 + 2) + 3) & ~3;
     return ensure_capacity(h, c, std::min<int64_t>(std::max(c.cap_reads, nmax), (1 << 21) - 1));
 }
 
 static int search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offsets, int64_t nreads, int64_t first_read_id)
 {
-    McCtx &c = h->ctx[0];
+    McCtx &c = h->ctx;
     const int64_t total = offsets[nreads] - offsets[0];
     std::vector<int64_t> off((size_t)nreads + 1);
     for (int64_t i = 0; i <= nreads; i++) off[(size_t)i] = offsets[i] - offsets[0];
@@ -1431,7 +1357,7 @@ extern "C" int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_
     McRow *d_rows = nullptr; unsigned long long *d_bins = nullptr;
     HIPCK(hipMalloc((void **)&d_rows, (size_t)nrows * sizeof(McRow)));
     if (hipMalloc((void **)&d_bins, nbins * 24) != hipSuccess) { (void)hipFree(d_rows); g_err = "out of device memory"; return -1; }
-    hipStream_t st = h->ctx[0].stream;
+    hipStream_t st = h->ctx.stream;
     HIPCK(hipMemcpyAsync(d_rows, h->res_rows, (size_t)nrows * sizeof(McRow), hipMemcpyHostToDevice, st));
     HIPCK(hipMemsetAsync(d_bins, 0, nbins * 24, st));
     k_grid_classify<<<dim3((unsigned)((nrows + 127) / 128)), dim3(128), 0, st>>>(G, dev_index(h), h->d_fam, d_rows, nrows, d_bins, d_bins + nbins, (double *)(d_bins + 2 * nbins));
@@ -1684,7 +1610,7 @@ static int train_range(mc_handle *h, int64_t first, int64_t count, int64_t first
                        hipEvent_t e0, hipEvent_t e1, mc_stats &tot)
 {
     if (count <= 0) return 0;
-    McCtx &c = h->ctx[0];
+    McCtx &c = h->ctx;
     int rc = range_begin(h, c, first, count, first_read_id);
     if (rc == 0) rc = range_end(h, c);
     if (rc == -2 && count > 1) {
@@ -1731,7 +1657,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
         // the resident read buffer (mc_upload's) holds one range at a time: the simulator writes it, the search reads it
         const int64_t need = B * L + 16;
         if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
-        if (ensure_capacity(h, h->ctx[0], B)) return -1;
+        if (ensure_capacity(h, h->ctx, B)) return -1;
     }
     // the reference read-length mode: reads of L + ins - del bases (two passes), bucketed by length, each bucket searched at its length
     // and grid-classified into the same bins (a read lies in one bucket: its best survivor is the one of the whole library)
@@ -1742,7 +1668,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     if (hipMalloc((void **)&d_bins, nbins * 24) != hipSuccess) { g_err = "out of device memory"; return -1; }
     hipEvent_t ev[4] = {};
     for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { g_err = "hipEventCreate failed"; return -1; }
-    hipStream_t st = h->ctx[0].stream;
+    hipStream_t st = h->ctx.stream;
     const bool saved_best_only = h->best_only;
     h->best_only = false; h->rows_stay = true;                       // (the grid needs every row of a read)
     int rc = hipMemsetAsync(d_bins, 0, nbins * 24, st) == hipSuccess ? 0 : -1;

@@ -678,6 +678,9 @@ inline void mc_fill_tables(McTables &T, const McHostIndex &X, int read_len, doub
     // integer, where the reference's double arithmetic would decide - 8.94 and 26.98 are far from one; a change of the constants that
     // moves them there must fail loudly, not drift)
     for (double x : {T.xdrop_ungapped, T.xdrop_gapped}) if (fabs(x - nearbyint(x)) < 1e-6) { fprintf(stderr, "mc_fill_tables: an X-drop threshold on an integer (%.9f): the integer exit tests of the kernels are not exact there\n", x); abort(); }
+    // (k_eval_seeds' packed X-drop has no `run < -20` exit: the drop test fires first while floor(xdrop) + 1 <= MC_SEED_SCORE + 21 - best is
+    // at least the gated seed's score)
+    if (floor(T.xdrop_ungapped) + 1.0 > MC_SEED_SCORE + 21.0) { fprintf(stderr, "mc_fill_tables: ungapped X-drop threshold %.9f: the packed X-drop of the seed evaluation would miss the `run < -20` exit\n", T.xdrop_ungapped); abort(); }
     T.loge_thr = loge_thr;
     T.freq_thr = X.freq_thr;
     for (int g = 0; g < 10; g++) T.letter_p[g] = X.letter_p[g];

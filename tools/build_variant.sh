@@ -1,6 +1,6 @@
 #!/bin/bash
 # Development aid: an alternative build of the library with extra -D flags, for A/B runs on the GPU box through MCENSUS_LIB
-# (exp_libs/ is git-ignored but travels with gpurun):  tools/build_variant.sh <name> -DMC_BIN_LIGHT=64 ...
+# (exp_libs/ is git-ignored):  tools/build_variant.sh <name> -DMC_EV_GROUP=8 ...
 R=$(cd "$(dirname "$0")/.." && pwd)
 N=$1; shift
 mkdir -p $R/exp_libs

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Development aid (GPU box): the stage times of the timed steps with and without an environment switch of the library.
-#   tools/env_ab.sh "MC_ORDER_SERIAL=1" ["MC_OTHER=2" ...] [-- read-len batch]
+#   tools/env_ab.sh "MC_TS_STAGED=0" ["MC_OTHER=2" ...] [-- read-len batch]
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
 L=150; B=2000000
