@@ -164,6 +164,23 @@ int mc_write_m8_named(mc_handle *h, const char *path, int append, const char *co
 int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_cov, const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score,
                      int64_t *count_hits, int64_t *count_aln, double *count_cov);
 
+/* The uncertainty of an AGS estimate: the per-family sums of aggregate_hits (microbe_census.py:462-472) under B Poisson-bootstrap
+ * replicates of the sample, in one device pass.  Replicate b gives the read of best hit i the weight w(b, best[i].read) - Poisson(1),
+ * a pure function of (seed, b, read id): csrc/mc_boot.h states the formula and holds its threshold table - so the result does not
+ * depend on how the sample was split into batches, ranges or GPUs, nor on the order of best[].  best: n best hits as
+ * mc_result_best_hits() hands them out (of one run, of several gathered, or classified from a foreign m8).  family_stat[f]: the
+ * family's aln_stat as mc_set_run() numbers it (0 hits, 1 cov, 2 aln).  Outputs, zeroed first:
+ *   sums_i64 [B][nfam + 1]   hits family: sum of w; aln family: sum of w x aln; cov family: 0; column nfam: sum of w over all best
+ *                            hits (the classified reads the replicate drew).  Exact, whatever the launch geometry.
+ *   sums_f64 [B][nfam]       cov family: sum of w x (aln / target_len); others 0.  Each term rounded once, added in an order that
+ *                            depends on (n, B) alone: within (terms - 1) x 2^-53 of the exact sum, the same on every run.
+ * Refused: nfam outside 1 .. 32, B outside 1 .. 65536, a best hit whose family lies outside 0 .. nfam - 1, whose read id or alignment
+ * length is negative or whose target length is < 1.  Needs mc_open() only (no mc_set_run()). */
+int mc_bootstrap(mc_handle *h, const mc_best_hit *best, int64_t n, const int32_t *family_stat, int32_t nfam, int32_t B, uint64_t seed,
+                 int64_t *sums_i64, double *sums_f64);
+/* Milliseconds the last mc_bootstrap()'s kernels took (HIP events; the upload of the hits and the download of the sums not included). */
+float mc_bootstrap_ms(const mc_handle *h);
+
 /* ---- training (the reference's training/ workflow, TRAINING.txt steps 1 - 3, on the device) --------------------------------
  * A genome resident in HBM: bases = contig_off[ncontig] bytes, the contigs one after another as the FASTA holds them (line breaks
  * dropped, case kept); contig_off[0] = 0.  mc_simulate() writes reads [first, first + n) of library (seed, library_id) at

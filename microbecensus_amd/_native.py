@@ -173,6 +173,9 @@ def load_library():
     lib.mc_set_best_hits_only.argtypes = [C.c_void_p, C.c_int]
     lib.mc_grid_classify.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.c_int32,
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.mc_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.mc_bootstrap_ms.restype = C.c_float
+    lib.mc_bootstrap_ms.argtypes = [C.c_void_p]
     lib.mc_genome_open.restype = C.c_void_p
     lib.mc_genome_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     lib.mc_genome_close.restype = None
@@ -194,7 +197,7 @@ def load_library():
 EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "mc_set_index_cache", "mc_index_cache_check", "mc_open_rapdb", "mc_marker_count", "mc_marker_name", "mc_set_families", "mc_rapdb_verify", "mc_rapdb_write", "mc_index_view", "mc_set_run", "mc_search", "mc_search_varlen",
                     "mc_upload", "mc_attach", "mc_run", "mc_run_range", "mc_set_counting", "mc_debug_stage", "mc_range_begin", "mc_range_end", "mc_ranges_in_flight", "mc_result_rows", "mc_result_best_hits", "mc_result_stats", "mc_write_m8", "mc_write_m8_named",
                     "mc_reader_last_error", "mc_set_host_threads", "mc_reader_open", "mc_reader_open_range", "mc_reader_open_bz2_part", "mc_bz2_blocks", "mc_gz_chunks", "mc_reader_open_gz_part", "mc_reader_gz_provide", "mc_reader_gz_end_state", "mc_reader_gz_finish", "mc_reader_run", "mc_reader_reads", "mc_reader_get_stats", "mc_reader_times", "mc_reader_describe", "mc_dupset_open", "mc_dupset_close", "mc_dupset_walk", "mc_reader_take", "mc_reader_close", "mc_reader_trim", "mc_count_bases", "mc_quality_offset",
-                    "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify",
+                    "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify", "mc_bootstrap", "mc_bootstrap_ms",
                     "mc_genome_open", "mc_genome_close", "mc_genome_set_library", "mc_simulate", "mc_train_library", "mc_train_times",
                     "mc_genome_set_read_lengths", "mc_simulate_varlen", "mc_train_library_bases"]
 
@@ -792,6 +795,22 @@ class Engine:
                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), aln.ctypes.data_as(C.POINTER(C.c_int64)), cov.ctypes.data_as(C.POINTER(C.c_double))),
                     "mc_grid_classify")
         return hits, aln, cov
+
+    def bootstrap(self, best, stats, B, seed):
+        """The per-family sums of the best hits under B Poisson-bootstrap replicates (mc_bootstrap; csrc/mc_boot.h states the weights).
+        best: BEST_DTYPE array; stats: one aln_stat per family ('hits' / 'cov' / 'aln', or 0 / 1 / 2).  Returns (sums_i64 of shape
+        (B, nfam + 1): hits and aln families, last column the replicate's classified reads; sums_f64 of shape (B, nfam): cov families)."""
+        best = np.ascontiguousarray(best, dtype=BEST_DTYPE)
+        nfam, B = len(stats), int(B)
+        stat = (C.c_int32 * nfam)(*[ALN_STAT.get(s, s) for s in stats])
+        si = np.zeros((max(B, 0), nfam + 1), np.int64); sf = np.zeros((max(B, 0), nfam), np.float64)
+        self._check(self.lib.mc_bootstrap(self.h, best.ctypes.data_as(C.c_void_p), len(best), stat, nfam, B, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          si.ctypes.data_as(C.POINTER(C.c_int64)), sf.ctypes.data_as(C.POINTER(C.c_double))), "mc_bootstrap")
+        return si, sf
+
+    def bootstrap_ms(self):
+        """milliseconds the last bootstrap()'s kernels took (HIP events)"""
+        return float(self.lib.mc_bootstrap_ms(self.h))
 
     def simulate(self, genome, n, seed, library_id, first=0):
         """Reads [first, first + n) of library (seed, library_id) at this engine's read length: uint8 array (n, read_len)."""

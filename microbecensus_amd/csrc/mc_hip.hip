@@ -10,6 +10,7 @@
 //   k_grid.h               the training workflow's grid classification
 //   k_simulate.h           the training workflow's library simulator
 //   k_varlen.h             reads of mixed lengths bucketed by length (mc_search_varlen)
+//   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
 // ranges from a host-side source (mc_search, mc_search_files, mc_search_files_multi) with upload and search overlapped.
@@ -23,6 +24,7 @@
 #include "k_grid.h"
 #include "k_simulate.h"
 #include "k_varlen.h"
+#include "k_bootstrap.h"
 
 #include <map>
 
@@ -73,6 +75,7 @@ struct mc_handle {
     bool rows_stay = false;               // mc_train_library: the rows of a range stay in the context's d_rows (no copy to the host)
     float train_ms[3] = {0, 0, 0};        // mc_train_library: simulate, search, grid of the last library (HIP events)
     int64_t train_bases = 0;              // mc_train_library: the bases of the last library's reads (mc_train_library_bases)
+    float boot_ms = 0;                    // mc_bootstrap: the two kernels of the last call (HIP events)
     uint8_t *stage_pin[2] = {}, *stage_dev[2] = {}; size_t stage_bytes = 0; hipStream_t copy_stream = nullptr;   // run_stream
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -1368,6 +1371,67 @@ extern "C" int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_
     grid_counts(bins, nbins, n_cov * n_pid, n_score, nfam, order, count_hits, count_aln, count_cov);
     return 0;
 }
+
+// The hit tiles of mc_bootstrap(): about 4096 waves over the grid (hit tiles x replicate tiles of 64), at least 32 hits per tile, at
+// most 1024 tiles - a function of (n, B) alone, so a call's cov sums are the same on every run.
+static int boot_tiles(int64_t n, int32_t B)
+{
+    const int64_t rep_tiles = (B + MC_BOOT_LANES - 1) / MC_BOOT_LANES;
+    int64_t g = std::min<int64_t>(1024, std::max<int64_t>(32, 4096 / rep_tiles));
+    g = std::min<int64_t>(g, (n + 31) / 32);
+    return (int)std::max<int64_t>(1, g);
+}
+
+extern "C" int mc_bootstrap(mc_handle *h, const mc_best_hit *best, int64_t n, const int32_t *family_stat, int32_t nfam, int32_t B, uint64_t seed,
+                            int64_t *sums_i64, double *sums_f64)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!family_stat || !sums_i64 || !sums_f64 || (n > 0 && !best)) { g_err = "null argument"; return -1; }
+    if (nfam < 1 || nfam > 32) { g_err = "mc_bootstrap: 1 to 32 families"; return -1; }
+    if (B < 1 || B > (1 << 16)) { g_err = "mc_bootstrap: 1 to 65536 replicates"; return -1; }      // (the tiles' partial sums: at most 32 x 33 x B x 8 bytes there)
+    if (n < 0 || n > 0x7fffffffll) { g_err = "mc_bootstrap: bad number of best hits"; return -1; }
+    McBootPars P; memset(&P, 0, sizeof(P));
+    P.nfam = nfam; P.B = B; P.seed = seed;
+    for (int f = 0; f < nfam; f++) {
+        if (family_stat[f] != MC_BOOT_HITS && family_stat[f] != MC_BOOT_COV && family_stat[f] != MC_BOOT_ALN) { g_err = "mc_bootstrap: aln_stat must be 0 (hits), 1 (cov) or 2 (aln)"; return -1; }
+        P.stats |= (uint64_t)family_stat[f] << (2 * f);
+    }
+    for (int64_t i = 0; i < n; i++)      // (the family indexes the kernel's LDS array)
+        if (best[i].family < 0 || best[i].family >= nfam || best[i].read < 0 || best[i].aln < 0 || best[i].target_len < 1) { g_err = "mc_bootstrap: a best hit with a family outside 0 .. nfam - 1, a negative read id or alignment length, or no target length"; return -1; }
+    const size_t rows = (size_t)nfam + 1;
+    memset(sums_i64, 0, (size_t)B * rows * 8); memset(sums_f64, 0, (size_t)B * (size_t)nfam * 8);
+    h->boot_ms = 0;
+    if (n == 0) return 0;
+    HIPCK(hipSetDevice(h->device));
+    const int ntiles = boot_tiles(n, B);
+    const int64_t per_tile = (n + ntiles - 1) / ntiles;
+    mc_best_hit *d_hits = nullptr; unsigned long long *d_part = nullptr, *d_out = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto release = [&]() { if (d_hits) (void)hipFree(d_hits); if (d_part) (void)hipFree(d_part); if (d_out) (void)hipFree(d_out); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); };
+#define BOOTCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_err = std::string(#call) + ": " + hipGetErrorString(e_); release(); return -1; } } while (0)
+    const size_t nout = (size_t)B * (rows + (size_t)nfam);
+    BOOTCK(hipMalloc((void **)&d_hits, (size_t)n * sizeof(mc_best_hit)));
+    BOOTCK(hipMalloc((void **)&d_part, (size_t)ntiles * rows * (size_t)B * 8));
+    BOOTCK(hipMalloc((void **)&d_out, nout * 8));
+    BOOTCK(hipEventCreate(&e0)); BOOTCK(hipEventCreate(&e1));
+    hipStream_t st = h->ctx.stream;
+    BOOTCK(hipMemcpyAsync(d_hits, best, (size_t)n * sizeof(mc_best_hit), hipMemcpyHostToDevice, st));
+    BOOTCK(hipEventRecord(e0, st));
+    k_bootstrap<<<dim3((unsigned)ntiles, (unsigned)((B + MC_BOOT_LANES - 1) / MC_BOOT_LANES)), dim3(MC_BOOT_LANES), 0, st>>>(P, d_hits, n, per_tile, d_part);
+    long long *d_i64 = (long long *)d_out; double *d_f64 = (double *)(d_out + (size_t)B * rows);
+    k_bootstrap_reduce<<<dim3((unsigned)(((size_t)B * rows + 255) / 256)), dim3(256), 0, st>>>(P, ntiles, d_part, d_i64, d_f64);
+    BOOTCK(hipGetLastError());
+    BOOTCK(hipEventRecord(e1, st));
+    BOOTCK(hipMemcpyAsync(sums_i64, d_i64, (size_t)B * rows * 8, hipMemcpyDeviceToHost, st));
+    BOOTCK(hipMemcpyAsync(sums_f64, d_f64, (size_t)B * (size_t)nfam * 8, hipMemcpyDeviceToHost, st));
+    BOOTCK(hipStreamSynchronize(st));
+    BOOTCK(hipEventElapsedTime(&h->boot_ms, e0, e1));
+#undef BOOTCK
+    release();
+    return 0;
+}
+
+extern "C" float mc_bootstrap_ms(const mc_handle *h) { return h ? h->boot_ms : 0.0f; }
 
 extern "C" int mc_set_keep_rows(mc_handle *h, int keep)
 {

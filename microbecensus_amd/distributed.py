@@ -890,6 +890,9 @@ def run_pipeline_distributed(args, device=None):
     mc._cap_host_threads(threads)
     mc.impute_missing_args(args)
     mc.check_arguments(args)
+    if args.get("bootstrap") or args.get("curve"):
+        # the ranks reduce per-family counters; the bootstrap and the curve need the best hits themselves on one rank
+        sys.exit("--bootstrap and --curve are not available in a distributed run: use one process (args['devices'] spreads it over the GPUs of a node)")
     args["verbose"] = bool(args.get("verbose")) and rank == 0
     nccl = dist.is_initialized() and dist.get_backend() == "nccl"
     dev = torch.device("cuda", device) if nccl else None

@@ -29,6 +29,10 @@ What differs from the reference, on purpose:
     are dealt to them inside one process (mc_search_files_multi).  With neither, every visible GPU is used - as far as the run has
     batches for them (-n up to 2 M reads: one GPU).  Results do not depend on the number of GPUs.
   * args['threads'] (-t), when given, caps the worker threads of the native sampler (the reference forwards it to rapsearch -z).
+  * args['bootstrap'] = B (default 0: off) adds the sampling error of the estimate - B Poisson-bootstrap replicates of the sampled
+    reads, summed on the device (mc_bootstrap; csrc/mc_boot.h states the weights), args['bootstrap_seed'] their seed - and
+    args['curve'] = K (default 0) the AGS at K nested prefixes of the sample (what -n n_k would have returned).  run_pipeline
+    returns the same (est_ags, args); the figures land in args and report_results appends them.
 """
 import bz2
 import gzip
@@ -326,6 +330,9 @@ def check_arguments(args):
         sys.exit("Invalid number of threads: %s\nMust be a positive integer." % args["threads"])
     if args["nreads"] is not None and args["nreads"] < 1:
         sys.exit("Invalid number of reads: %s\nMust be a positive integer." % args["nreads"])
+    for key in ("bootstrap", "curve"):
+        if args.get(key) and (not isinstance(args[key], int) or isinstance(args[key], bool) or args[key] < 0):
+            sys.exit("Invalid %s: %s\nMust be a non-negative integer." % (key, args[key]))
     if args.get("model_dir") and args["read_length"] not in _valid_read_lengths(args["model_dir"]):
         sys.exit("Read length %s is not one the model in %s was trained for: %s" % (args["read_length"], args["model_dir"], _valid_read_lengths(args["model_dir"])))
 
@@ -636,13 +643,16 @@ def _classify_m8_file(args, paths):
     names, seqs = _native.load_markers(paths.get("db"))
     fam_of = {n: model["families"][f] for n, f in zip(names, model["marker_family"])}
     len_of = {n: float(len(s)) for n, s in zip(names, seqs)}
-    best = {}
+    best, tlen = {}, {}
     for r in parse_rapsearch(paths["tempfile"] + ".m8"):
         r["query_len"], r["target_fam"], r["target_len"] = args["read_length"], fam_of[r["target"]], len_of[r["target"]]
         if alignment_filter(r, optpars):
             continue
         if r["query"] not in best or best[r["query"]][-1] < r["score"]:
             best[r["query"]] = [r["target_fam"], r["aln"], r["aln"] / r["target_len"], r["score"]]
+            tlen[r["query"]] = r["target_len"]
+    if args.get("bootstrap") or args.get("curve"):       # (_best_array: the dict holds aln / target_len, the array both terms)
+        _run_cache.setdefault(paths["tempfile"], {})["m8_target_len"] = tlen
     return best
 
 
@@ -728,15 +738,13 @@ def aggregate_hits(args, paths, best_hits):
     return agg
 
 
-def estimate_average_genome_size(args, paths, agg_hits):
-    """AGS_j = coefficient_j / (hits_j / sampled bp); drop |AGS_j - median| >= 1.48 MAD; weighted mean."""
-    if args["verbose"]:
-        print("Computing average genome size...")
-    model = _model(args.get("model_dir"))
-    L = str(args["read_length"])
+def _ags_of_sums(model, read_length, agg_hits, bases):
+    """The arithmetic of estimate_average_genome_size (reference :474-512) on the per-family sums agg_hits of a sample of `bases`
+    sampled bases: the estimate itself, every bootstrap replicate and every point of the -n curve run these lines."""
+    L = str(read_length)
     estimates = {}
     for fam, hits in agg_hits.items():
-        rate = hits / (args["sampled_reads"] * args["read_length"])
+        rate = hits / bases
         if rate == 0:
             continue
         estimates[fam] = model["coefficients"]["_".join([L, fam])] / rate
@@ -749,10 +757,145 @@ def estimate_average_genome_size(args, paths, agg_hits):
         w = model["weights"]["_".join([L, fam])]
         total += est * w
         wsum += w
-    est_ags = total / wsum
+    return total / wsum
+
+
+def estimate_average_genome_size(args, paths, agg_hits):
+    """AGS_j = coefficient_j / (hits_j / sampled bp); drop |AGS_j - median| >= 1.48 MAD; weighted mean."""
+    if args["verbose"]:
+        print("Computing average genome size...")
+    est_ags = _ags_of_sums(_model(args.get("model_dir")), args["read_length"], agg_hits, args["sampled_reads"] * args["read_length"])
     if args["verbose"]:
         print("\t%s bp" % str(round(est_ags, 2)))
     return est_ags
+
+
+# ----------------------------------------------------------------------------------------------
+# how sure is the estimate: Poisson bootstrap over the sampled reads (device sums) and the -n curve
+# ----------------------------------------------------------------------------------------------
+def _ags_or_none(model, read_length, agg_hits, bases):
+    """_ags_of_sums, or None where it has no value: no family with a hit, or none that survives the outlier cut (wsum == 0)."""
+    if bases <= 0 or not any(v != 0 for v in agg_hits.values()):
+        return None
+    try:
+        return _ags_of_sums(model, read_length, agg_hits, bases)
+    except ZeroDivisionError:
+        return None
+
+
+def _best_array(args, paths, best_hits):
+    """The best hits of the run as a BEST_DTYPE array in ascending read id: the device's own, or (an m8 file classified by
+    _classify_m8_file: the -r route, a foreign file) rebuilt from the dict - process_seqfile names its reads 0, 1, ..."""
+    from . import _native
+    if isinstance(best_hits, _BestHits):
+        return best_hits._best, best_hits._fams
+    fams = _model(args.get("model_dir"))["families"]
+    tlen = _run_cache.get(paths["tempfile"], {}).get("m8_target_len")
+    if tlen is None:
+        raise Exception("bootstrap / curve: the best hits of this run carry no target lengths (classify_reads must run with the switch set)")
+    idx = {f: i for i, f in enumerate(fams)}
+    arr = np.zeros(len(best_hits), _native.BEST_DTYPE)
+    for i, (q, (fam, aln, cov, score)) in enumerate(best_hits.items()):
+        arr[i] = (int(q), idx[fam], int(aln), int(tlen[q]), score)
+    return arr[np.argsort(arr["read"], kind="stable")], fams
+
+
+def _family_order(best):
+    """family indices in the order of their first best hit: the order aggregate_hits' dict has"""
+    present, first = np.unique(best["family"], return_index=True)
+    return present[np.argsort(first)].tolist()
+
+
+BOOT_N0_DOMAIN = 0x6D635F626F6F74        # "mc_boot": the key domain of the host's draws for the reads without a best hit
+
+
+def bootstrap_unclassified(seed, B, n_unclassified):
+    """N0[b], b = 0 .. B-1: how many of the sample's reads WITHOUT a best hit replicate b drew - one Poisson(n_unclassified)
+    draw each (the sum of that many Poisson(1) weights), from numpy's Generator(PCG64(SeedSequence([BOOT_N0_DOMAIN, seed])))."""
+    rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([BOOT_N0_DOMAIN, int(seed) & 0xFFFFFFFFFFFFFFFF])))
+    return rng.poisson(float(max(0, int(n_unclassified))), size=int(B)).astype(np.int64)
+
+
+def bootstrap_replicates(args, best, fams, sums_i64, sums_f64, sampled_reads, seed):
+    """The replicate AGS values from the replicates' per-family sums (Engine.bootstrap's two arrays, or the host statement's):
+    replicate b sampled read_length x (W[b] + N0[b]) bases - W[b] the weights of its classified reads (last column of sums_i64) -
+    and its AGS is _ags_of_sums of its sums.  A list of B floats, None where a replicate has no value."""
+    model = _model(args.get("model_dir"))
+    optpars = find_opt_pars(args.get("model_dir"), args["read_length"])
+    L = args["read_length"]
+    order = _family_order(best)
+    is_cov = [optpars[fams[f]]["aln_stat"] == "cov" for f in order]
+    names = [fams[f] for f in order]
+    n0 = bootstrap_unclassified(seed, len(sums_i64), sampled_reads - len(best))
+    cols_i = sums_i64[:, order].tolist()
+    cols_f = sums_f64[:, order].tolist()
+    wtot = sums_i64[:, -1].tolist()
+    out = []
+    for b in range(len(sums_i64)):
+        agg = {nm: (cf if c else float(ci)) for nm, c, ci, cf in zip(names, is_cov, cols_i[b], cols_f[b])}
+        out.append(_ags_or_none(model, L, agg, L * (wtot[b] + int(n0[b]))))
+    return out
+
+
+def _boot_summary(values, asked):
+    used = np.array([v for v in values if v is not None], dtype=np.float64)
+    se = float(np.std(used, ddof=1)) if len(used) > 1 else float("nan")
+    lo, hi = (float(x) for x in np.percentile(used, [2.5, 97.5])) if len(used) else (float("nan"), float("nan"))
+    return {"se": se, "ci95": (lo, hi), "used": int(len(used)), "asked": int(asked), "values": values}
+
+
+def _boot_engine(args):
+    try:
+        return _engines_on(_devices_for(args)[:1], args.get("model_dir"))[0]
+    except RuntimeError as e:
+        raise Exception("--bootstrap sums its replicates on the GPU (mc_bootstrap) and there is no CPU fallback: %s" % e)
+
+
+def bootstrap_ags(args, best, fams, sampled_reads=None):
+    """B = args['bootstrap'] Poisson-bootstrap replicates of the sample whose best hits are `best` (the first sampled_reads reads;
+    default args['sampled_reads']): the per-family sums on the device, the replicate AGS values on the host.
+    {'se', 'ci95': (low, high), 'used', 'asked', 'values'}."""
+    B, seed = int(args["bootstrap"]), int(args.get("bootstrap_seed") or 0)
+    optpars = find_opt_pars(args.get("model_dir"), args["read_length"])
+    si, sf = _boot_engine(args).bootstrap(best, [optpars[f]["aln_stat"] for f in fams], B, seed)
+    n = args["sampled_reads"] if sampled_reads is None else sampled_reads
+    return _boot_summary(bootstrap_replicates(args, best, fams, si, sf, n, seed), B)
+
+
+def curve_points(sampled_reads, K):
+    """n_k = ceil(k x sampled_reads / K), k = 1 .. K"""
+    return [-(-k * int(sampled_reads) // int(K)) for k in range(1, int(K) + 1)]
+
+
+def ags_curve(args, paths, best, fams):
+    """The AGS of the first n_k sampled reads, k = 1 .. args['curve']: the sample is a head-take (process_seqfile), so that is what
+    a run with -n n_k returns.  [{'reads', 'ags' (None without a classified read)} (+ 'se' with args['bootstrap'])]."""
+    model = _model(args.get("model_dir"))
+    L = args["read_length"]
+    quiet = dict(args, verbose=False)
+    out = []
+    for n_k in curve_points(args["sampled_reads"], args["curve"]):
+        head = best[: int(np.searchsorted(best["read"], n_k, side="left"))]
+        agg = aggregate_hits(quiet, paths, _BestHits(head, fams)) if len(head) else {}
+        point = {"reads": n_k, "ags": _ags_or_none(model, L, agg, n_k * L)}
+        if args.get("bootstrap"):
+            point["se"] = bootstrap_ags(args, head, fams, n_k)["se"] if len(head) else float("nan")
+        out.append(point)
+    return out
+
+
+def _uncertainty(args, paths, best, fams):
+    """args['bootstrap'] / args['curve'] of run_pipeline: fills args['ags_boot_se'], ['ags_ci95'], ['ags_boot_replicates'] (used,
+    asked), ['ags_boot_values'] and args['ags_curve']."""
+    if args.get("bootstrap"):
+        if args["verbose"]:
+            print("Bootstrapping the estimate (%s replicates)..." % args["bootstrap"])
+        r = bootstrap_ags(args, best, fams)
+        args["ags_boot_se"], args["ags_ci95"], args["ags_boot_replicates"], args["ags_boot_values"] = r["se"], r["ci95"], (r["used"], r["asked"]), r["values"]
+        if args["verbose"]:
+            print("\tstandard error %s bp, 95%% interval %s - %s bp (%s of %s replicates)" % (round(r["se"], 2), round(r["ci95"][0], 2), round(r["ci95"][1], 2), r["used"], r["asked"]))
+    if args.get("curve"):
+        args["ags_curve"] = ags_curve(args, paths, best, fams)
 
 
 def report_results(args, est_ags, count_bases):
@@ -767,6 +910,15 @@ def report_results(args, est_ags, count_bases):
         if count_bases:
             out.write("%s:\t%s\n" % ("total_bases", count_bases))
             out.write("%s:\t%s\n" % ("genome_equivalents", count_bases / est_ags))
+        if args.get("bootstrap") and "ags_boot_se" in args:
+            for key, val in (("ags_boot_se", args["ags_boot_se"]), ("ags_ci95_low", args["ags_ci95"][0]), ("ags_ci95_high", args["ags_ci95"][1]),
+                             ("ags_boot_replicates", "%s/%s" % tuple(args["ags_boot_replicates"]))):
+                out.write("%s:\t%s\n" % (key, val))
+        if args.get("curve") and "ags_curve" in args:
+            out.write("curve_reads:\t%s\n" % "\t".join(str(p["reads"]) for p in args["ags_curve"]))
+            out.write("curve_ags:\t%s\n" % "\t".join(str(p["ags"]) for p in args["ags_curve"]))
+            if args.get("bootstrap"):
+                out.write("curve_se:\t%s\n" % "\t".join(str(p["se"]) for p in args["ags_curve"]))
 
 
 def clean_up(paths):
@@ -829,8 +981,11 @@ def run_pipeline(args):
             search_seqs(args, paths)
         best_hits = classify_reads(args, paths)
         agg_hits = aggregate_hits(args, paths, best_hits)
+        extras = _best_array(args, paths, best_hits) if args.get("bootstrap") or args.get("curve") else None
         clean_up(paths)
         est_ags = estimate_average_genome_size(args, paths, agg_hits)
+        if extras is not None:
+            _uncertainty(args, paths, *extras)
         return est_ags, args
     except Exception as error:     # the reference prints and swallows everything but SystemExit
         print(error)

@@ -36,6 +36,9 @@ def parse_arguments(argv=None):
     p.add_argument("-u", dest="max_unknown", type=int, default=100, help="max percent of unknown bases per read (default = 100)")
     p.add_argument("-g", dest="device", type=int, default=None, help="GPU index (default: every visible GPU the run has batches of 2 M reads for)")
     p.add_argument("--model", dest="model_dir", type=str, default=None, help="directory of a trained model (markers.faa.gz, model.json: scripts/train_microbe_census.py) to use instead of the packaged one")
+    p.add_argument("--bootstrap", dest="bootstrap", type=int, default=0, metavar="B", help="report the sampling error of the estimate from B Poisson-bootstrap replicates of the sampled reads (standard error and 95%% interval; default = 0: off)")
+    p.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=0, metavar="S", help="seed of the bootstrap (default = 0)")
+    p.add_argument("--curve", dest="curve", type=int, default=0, metavar="K", help="report the estimate at K nested prefixes of the sample: what -n n_k would have returned (default = 0: off)")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     if args["device"] is None:
