@@ -229,6 +229,38 @@ int64_t mc_train_library_bases(const mc_handle *h);
 /* Milliseconds of the last mc_train_library() from HIP events: [0] simulation (and, in the reference mode, bucketing), [1] search (the stages' own events), [2] grid. */
 int mc_train_times(const mc_handle *h, float *ms);
 
+/* ---- mock communities: how good is a model on a metagenome of known composition --------------------------------------------
+ * A community resident in HBM: M member genomes with copies[m] cells each (1 <= M <= 65,536; 1 <= copies <= 2^20).  bases and
+ * contig_off as for mc_genome_open(), the contigs of all members one after another; member m holds contigs
+ * member_first_contig[m] .. member_first_contig[m + 1] - 1 (member_first_contig[0] = 0, [M] = ncontig; every member has a contig).
+ * A community library is what shotgun sequencing of the mixture gives: a read comes from member m with probability proportional
+ * to copies[m] x (valid starts of m), and inside the member it is mc_simulate()'s read - csrc/mc_simlib.h states the draw.  A
+ * read is a pure function of (seed, library_id, read index); both mates of a fragment come from one member; a community of one
+ * member with one copy gives mc_simulate()'s library of that genome, byte for byte, for every library kind. */
+typedef struct mc_community mc_community;
+mc_community *mc_community_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, const int32_t *member_first_contig,
+                                const int64_t *copies, int32_t M, int32_t device);
+void mc_community_close(mc_community *c);
+/* The kind of library the community's calls make from now on: the kinds and refusals of mc_genome_set_library() (paired end: an
+ * insert longer than every contig of every member is refused).  NULL restores the default.  Reads always keep read_len bases
+ * (MC_READLEN_FIXED): a community has no reference read-length mode. */
+int mc_community_set_library(mc_community *c, const mc_library *lib);
+/* Reads [first, first + n) of library (seed, library_id) at read_len to dst_host (n x read_len bytes), as mc_simulate().  A member
+ * without a contig of the span (read_len, or the insert) is never drawn.  Refused: a community none of whose members has such a
+ * contig, one whose universe (the sum of copies x valid starts) reaches 2^62, insert < read_len. */
+int mc_community_simulate(mc_community *c, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host);
+/* One library pass, fused: reads [0, nreads) of library (seed, library_id) at mc_set_run()'s read length and settings, simulated
+ * straight into the handle's resident read buffer range by range (MC_STREAM_BATCH reads, global read ids) and searched from there.
+ * Afterwards mc_result_best_hits() / mc_result_stats() are those of mc_search() on the same reads with best hits only
+ * (mc_set_best_hits_only); mc_result_rows() is empty.  No read and no m8 row leaves the device.  The community must lie on the
+ * handle's device; a paired-end library has an even number of reads; at most 2^31 - 1 reads. */
+int mc_community_library(mc_handle *h, mc_community *c, int64_t nreads, uint64_t seed, uint64_t library_id);
+/* out[m], m < M: the reads of the last mc_community_simulate() / mc_community_library() that came from member m (counted on the
+ * device while they were made; a mate counts as a read). */
+int mc_community_member_reads(mc_community *c, int64_t *out);
+/* Milliseconds of the last mc_community_library() from HIP events: [0] simulation, [1] search (the stages' own events). */
+int mc_community_times(const mc_handle *h, float *ms);
+
 /* ---- host stage in front of the search: native read sampler (csrc/mc_reader.cpp; no GPU involved) ----------------
  * Replaces open_file / parse_seqs / quality_filter / process_seqfile (microbe_census.py:47-59, :294-325, :265-279,
  * :328-367) and count_bases (:573-584) with identical results, quirks included (see the header of mc_reader.cpp).

@@ -190,6 +190,15 @@ def load_library():
     lib.mc_simulate_varlen.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.mc_train_library_bases.restype = C.c_int64
     lib.mc_train_library_bases.argtypes = [C.c_void_p]
+    lib.mc_community_open.restype = C.c_void_p
+    lib.mc_community_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+    lib.mc_community_close.restype = None
+    lib.mc_community_close.argtypes = [C.c_void_p]
+    lib.mc_community_set_library.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mc_community_simulate.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]
+    lib.mc_community_library.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64]
+    lib.mc_community_member_reads.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mc_community_times.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     _lib = lib
     return lib
 
@@ -199,7 +208,9 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_reader_last_error", "mc_set_host_threads", "mc_reader_open", "mc_reader_open_range", "mc_reader_open_bz2_part", "mc_bz2_blocks", "mc_gz_chunks", "mc_reader_open_gz_part", "mc_reader_gz_provide", "mc_reader_gz_end_state", "mc_reader_gz_finish", "mc_reader_run", "mc_reader_reads", "mc_reader_get_stats", "mc_reader_times", "mc_reader_describe", "mc_dupset_open", "mc_dupset_close", "mc_dupset_walk", "mc_reader_take", "mc_reader_close", "mc_reader_trim", "mc_count_bases", "mc_quality_offset",
                     "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify", "mc_bootstrap", "mc_bootstrap_ms",
                     "mc_genome_open", "mc_genome_close", "mc_genome_set_library", "mc_simulate", "mc_train_library", "mc_train_times",
-                    "mc_genome_set_read_lengths", "mc_simulate_varlen", "mc_train_library_bases"]
+                    "mc_genome_set_read_lengths", "mc_simulate_varlen", "mc_train_library_bases",
+                    "mc_community_open", "mc_community_close", "mc_community_set_library", "mc_community_simulate", "mc_community_library", "mc_community_member_reads",
+                    "mc_community_times"]
 
 
 class DupSet:
@@ -579,6 +590,71 @@ class Genome:
             pass
 
 
+class Community:
+    """A mock community resident on one device (mc_community_open): members = [(bases, contig_off)] of the member genomes, copies = the
+    number of cells of each.  Its libraries draw a read from member m with probability proportional to copies[m] x (valid starts of
+    m); csrc/mc_simlib.h states the draw."""
+
+    def __init__(self, members, copies, device=0):
+        lib = load_library()
+        self.lib = lib
+        if len(members) < 1 or len(members) != len(copies):
+            raise ValueError("a community needs members and as many copies")
+        offs, first, at, nc = [np.zeros(1, np.int64)], [0], 0, 0
+        for bases, off in members:
+            off = np.asarray(off, dtype=np.int64)
+            assert off.ndim == 1 and len(off) >= 2 and off[0] == 0 and off[-1] == len(bases)
+            offs.append(off[1:] + at)
+            at += int(off[-1])
+            nc += len(off) - 1
+            first.append(nc)
+        self.bases = np.ascontiguousarray(np.concatenate([np.asarray(b, dtype=np.uint8) for b, _ in members]))
+        self.contig_off = np.ascontiguousarray(np.concatenate(offs))
+        self.member_first = np.array(first, dtype=np.int32)
+        self.copies = np.array([int(k) for k in copies], dtype=np.int64)
+        self.sizes = [int(len(b)) for b, _ in members]
+        self.device, self.M = device, len(members)
+        self.c = lib.mc_community_open(self.bases.ctypes.data_as(C.c_void_p), self.contig_off.ctypes.data_as(C.c_void_p), nc, self.member_first.ctypes.data_as(C.c_void_p),
+                                       self.copies.ctypes.data_as(C.c_void_p), self.M, device)
+        if not self.c:
+            raise RuntimeError("mc_community_open failed: %s" % lib.mc_last_error().decode())
+
+    def set_library(self, error_model=None, error_rate=None, paired_end=False, insert=None):
+        """The kind of library simulate() and Engine.community_library() make from now on (mc_community_set_library): as
+        Genome.set_library."""
+        if error_model not in ERROR_MODELS:
+            raise ValueError("unknown error model %r" % (error_model,))
+        lib = None
+        if error_model is not None or paired_end:
+            lib = C.byref(McLibrary(1 if paired_end else 0, int(insert or 0), ERROR_MODELS[error_model], float(error_rate or 0.0)))
+        if self.lib.mc_community_set_library(self.c, lib) != 0:
+            raise RuntimeError("mc_community_set_library failed: %s" % self.lib.mc_last_error().decode())
+
+    def simulate(self, read_len, n, seed, library_id, first=0):
+        out = np.empty((int(n), int(read_len)), dtype=np.uint8)
+        if self.lib.mc_community_simulate(self.c, int(read_len), int(first), int(n), int(seed), int(library_id), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("mc_community_simulate failed: %s" % self.lib.mc_last_error().decode())
+        return out
+
+    def member_reads(self):
+        """int64 (M,): the reads of the last simulate() / Engine.community_library() by the member they came from."""
+        out = np.zeros(self.M, np.int64)
+        if self.lib.mc_community_member_reads(self.c, out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("mc_community_member_reads failed: %s" % self.lib.mc_last_error().decode())
+        return out
+
+    def close(self):
+        if getattr(self, "c", None):
+            self.lib.mc_community_close(self.c)
+            self.c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _grid_pids(max_pids):
     """The grid's max_pids as the C ints the ABI takes.  A non-integral value is refused: the reference's pid_filter compares the
     printed identity with the float, and the kernel's integer test would not be that comparison."""
@@ -838,6 +914,19 @@ class Engine:
         ms = (C.c_float * 3)()
         self._check(self.lib.mc_train_times(self.h, ms), "mc_train_times")
         return {"simulate": ms[0], "search": ms[1], "grid": ms[2]}
+
+    def community_library(self, community, nreads, seed, library_id):
+        """One fused library pass of a community (mc_community_library): nreads reads simulated and searched on the device at this
+        engine's run settings.  Returns the best hits - those of search() on the same reads; stats() holds the search's totals,
+        community.member_reads() the reads per member."""
+        self._check(self.lib.mc_community_library(self.h, community.c, int(nreads), int(seed), int(library_id)), "mc_community_library")
+        return self.best_hits()
+
+    def community_times(self):
+        """{'simulate', 'search'}: milliseconds of the last community_library (HIP events)."""
+        ms = (C.c_float * 2)()
+        self._check(self.lib.mc_community_times(self.h, ms), "mc_community_times")
+        return {"simulate": ms[0], "search": ms[1]}
 
     def index_view(self):
         p = [C.c_void_p() for _ in range(5)]

@@ -9,6 +9,7 @@
 //   k_finish.h         D   sum statistics, std::sort / heap sort replayed, 500-row cap, classification; rows in m8 order
 //   k_grid.h               the training workflow's grid classification
 //   k_simulate.h           the training workflow's library simulator
+//   k_community.h          the library of a mock community of genomes (mc_community_*)
 //   k_varlen.h             reads of mixed lengths bucketed by length (mc_search_varlen)
 //   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
@@ -23,6 +24,7 @@
 #include "k_finish.h"
 #include "k_grid.h"
 #include "k_simulate.h"
+#include "k_community.h"
 #include "k_varlen.h"
 #include "k_bootstrap.h"
 
@@ -74,6 +76,7 @@ struct mc_handle {
     bool best_only = false;               // only the reads that can be classified are ranked; no rows (mc_set_best_hits_only)
     bool rows_stay = false;               // mc_train_library: the rows of a range stay in the context's d_rows (no copy to the host)
     float train_ms[3] = {0, 0, 0};        // mc_train_library: simulate, search, grid of the last library (HIP events)
+    float comm_ms[2] = {0, 0};            // mc_community_library: simulate, search of the last library (HIP events)
     int64_t train_bases = 0;              // mc_train_library: the bases of the last library's reads (mc_train_library_bases)
     float boot_ms = 0;                    // mc_bootstrap: the two kernels of the last call (HIP events)
     uint8_t *stage_pin[2] = {}, *stage_dev[2] = {}; size_t stage_bytes = 0; hipStream_t copy_stream = nullptr;   // run_stream
@@ -1793,5 +1796,215 @@ extern "C" int mc_train_times(const mc_handle *h, float *ms)
 {
     if (!h || !ms) { g_err = "null argument"; return -1; }
     for (int k = 0; k < 3; k++) ms[k] = h->train_ms[k];
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mock communities: M genomes with copies each, resident in HBM; their libraries (k_community.h), the fused library pass
+// ------------------------------------------------------------------------------------------------
+struct mc_community {
+    int device = 0, ncontig = 0, M = 0;
+    std::vector<int64_t> off, copies;                               // contig offsets, copies per member (host)
+    std::vector<int32_t> mfirst;                                    // member m holds contigs mfirst[m] .. mfirst[m + 1] - 1
+    uint8_t *d_bases = nullptr; int64_t *d_off = nullptr, *d_vstart = nullptr, *d_total = nullptr; uint64_t *d_cum = nullptr; int32_t *d_mfirst = nullptr;
+    unsigned long long *d_counts = nullptr;                         // reads per member of the pass under way
+    std::vector<int64_t> member_reads;                              // ... of the last simulate / library call
+    int span = 0;                                                   // the span (read length or insert) the member table was made for
+    mc_library lib = {0, 0, MC_ERR_NONE, 0.0};
+    uint64_t *d_thr = nullptr;
+};
+
+extern "C" void mc_community_close(mc_community *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    for (void *p : {(void *)c->d_bases, (void *)c->d_off, (void *)c->d_vstart, (void *)c->d_total, (void *)c->d_cum, (void *)c->d_mfirst, (void *)c->d_counts, (void *)c->d_thr})
+        if (p) (void)hipFree(p);
+    delete c;
+}
+
+extern "C" mc_community *mc_community_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, const int32_t *member_first_contig, const int64_t *copies,
+                                           int32_t M, int32_t device)
+{
+    if (!bases || !contig_off || ncontig < 1 || !member_first_contig || !copies) { g_err = "mc_community_open: bad argument"; return nullptr; }
+    if (M < 1 || M > MC_SIM_MAX_MEMBERS) { g_err = "mc_community_open: " + std::to_string(M) + " members (1 .. " + std::to_string(MC_SIM_MAX_MEMBERS) + ")"; return nullptr; }
+    if (contig_off[0] != 0) { g_err = "mc_community_open: contig_off[0] must be 0"; return nullptr; }
+    for (int i = 0; i < ncontig; i++) if (contig_off[i + 1] < contig_off[i]) { g_err = "mc_community_open: contig offsets must not decrease"; return nullptr; }
+    if (member_first_contig[0] != 0 || member_first_contig[M] != ncontig) { g_err = "mc_community_open: member_first_contig must run from 0 to ncontig"; return nullptr; }
+    for (int m = 0; m < M; m++) {
+        if (member_first_contig[m + 1] <= member_first_contig[m]) { g_err = "mc_community_open: member " + std::to_string(m) + " has no contig"; return nullptr; }
+        if (copies[m] < 1 || copies[m] > MC_SIM_MAX_COPIES) { g_err = "mc_community_open: member " + std::to_string(m) + " has " + std::to_string(copies[m]) + " copies (1 .. " + std::to_string(MC_SIM_MAX_COPIES) + ")"; return nullptr; }
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "no HIP device visible"; return nullptr; }
+    if (device < 0 || device >= ndev) { g_err = "mc_community_open: no such device"; return nullptr; }
+    if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return nullptr; }
+    mc_community *c = new mc_community();
+    c->device = device; c->ncontig = ncontig; c->M = M;
+    c->off.assign(contig_off, contig_off + ncontig + 1); c->copies.assign(copies, copies + M); c->mfirst.assign(member_first_contig, member_first_contig + M + 1);
+    c->member_reads.assign((size_t)M, 0);
+    const size_t nb = (size_t)contig_off[ncontig];
+    if (hipMalloc((void **)&c->d_bases, nb + 64) != hipSuccess || hipMalloc((void **)&c->d_off, sizeof(int64_t) * (ncontig + 1)) != hipSuccess ||
+        hipMalloc((void **)&c->d_vstart, sizeof(int64_t) * ncontig) != hipSuccess || hipMalloc((void **)&c->d_total, sizeof(int64_t) * M) != hipSuccess ||
+        hipMalloc((void **)&c->d_cum, sizeof(uint64_t) * (M + 1)) != hipSuccess || hipMalloc((void **)&c->d_mfirst, sizeof(int32_t) * (M + 1)) != hipSuccess ||
+        hipMalloc((void **)&c->d_counts, sizeof(unsigned long long) * M) != hipSuccess || hipMalloc((void **)&c->d_thr, sizeof(uint64_t) * MC_SIM_NTHR) != hipSuccess ||
+        hipMemcpy(c->d_bases, bases, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_off, contig_off, sizeof(int64_t) * (ncontig + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_mfirst, member_first_contig, sizeof(int32_t) * (M + 1), hipMemcpyHostToDevice) != hipSuccess) {
+        g_err = "mc_community_open: out of device memory";
+        mc_community_close(c);
+        return nullptr;
+    }
+    return c;
+}
+
+extern "C" int mc_community_set_library(mc_community *c, const mc_library *lib)
+{
+    if (!c) { g_err = "mc_community_set_library: bad argument"; return -1; }
+    const mc_library l = lib ? *lib : mc_library{0, 0, MC_ERR_NONE, 0.0};
+    if (l.error_model != MC_ERR_NONE && l.error_model != MC_ERR_UNIFORM && l.error_model != MC_ERR_ILLUMINA) { g_err = "unknown error model " + std::to_string(l.error_model); return -1; }
+    if (!(l.error_rate >= 0.0 && l.error_rate <= 1.0)) { g_err = "error rate " + std::to_string(l.error_rate) + " outside [0, 1]"; return -1; }
+    int64_t longest = 0;
+    for (int k = 0; k < c->ncontig; k++) longest = std::max(longest, c->off[(size_t)k + 1] - c->off[(size_t)k]);
+    if (l.paired_end && l.insert < 1) { g_err = "a paired-end library needs a positive insert"; return -1; }
+    if (l.paired_end && l.insert > longest) { g_err = "the community has no contig of at least the insert (" + std::to_string(l.insert) + " bp)"; return -1; }
+    uint64_t thr[MC_SIM_NTHR];
+    mc_sim_thresholds(l.error_model, l.error_rate, thr);
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipMemcpy(c->d_thr, thr, sizeof thr, hipMemcpyHostToDevice));
+    c->lib = l;
+    return 0;
+}
+
+// the member table for reads of L bases - fragments of `insert` bases for a paired-end library; refuses an insert shorter than the
+// read, a community none of whose members has a contig of that span, and a universe of 2^62 or more
+static int community_for_len(mc_community *c, int L)
+{
+    if (c->lib.paired_end && c->lib.insert < L) { g_err = "the insert (" + std::to_string(c->lib.insert) + ") is shorter than the read length (" + std::to_string(L) + ")"; return -1; }
+    const int span = c->lib.paired_end ? c->lib.insert : L;
+    if (c->span == span) return 0;
+    std::vector<int64_t> vs((size_t)c->ncontig), total((size_t)c->M);
+    std::vector<uint64_t> cum((size_t)c->M + 1);
+    const int bad = mc_sim_member_table(c->off.data(), c->mfirst.data(), c->copies.data(), c->M, span, vs.data(), total.data(), cum.data());
+    if (bad == 1) { g_err = "the community has no contig of at least the " + std::string(c->lib.paired_end ? "insert" : "read length") + " (" + std::to_string(span) + " bp)"; return -1; }
+    if (bad) { g_err = "the community's universe (the sum of copies x valid starts) does not stay below 2^62"; return -1; }
+    HIPCK(hipMemcpy(c->d_vstart, vs.data(), sizeof(int64_t) * vs.size(), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(c->d_total, total.data(), sizeof(int64_t) * total.size(), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(c->d_cum, cum.data(), sizeof(uint64_t) * cum.size(), hipMemcpyHostToDevice));
+    c->span = span;
+    return 0;
+}
+
+static int launch_community(const mc_community *c, int L, uint64_t key, int64_t first, int64_t n, uint8_t *dst, hipStream_t st)
+{
+    if (n <= 0) return 0;
+    const McCommTable T = {c->d_cum, c->d_total, c->d_mfirst, c->d_vstart, c->d_off, c->M, c->M <= MC_COMM_LDS_M ? 1 : 0};
+    if (default_library(c->lib)) {
+        k_community<<<dim3((unsigned)((n + 255) / 256)), dim3(256), comm_lds_bytes(c->M), st>>>(c->d_bases, T, L, key, first, n, dst, c->d_counts);
+    } else {
+        const McSimKind kind = {L, c->lib.paired_end ? 1 : 0, c->lib.paired_end ? c->lib.insert : L, c->lib.error_model != MC_ERR_NONE ? 1 : 0};
+        const size_t lds = (size_t)64 * L + sizeof(uint64_t) * MC_SIM_NTHR + comm_lds_bytes(c->M);
+        k_community_lib<<<dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st>>>(c->d_bases, T, kind, c->d_thr, key, mc_mix64(key ^ MC_SIM_EKEY), first, n, dst, c->d_counts);
+    }
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+// the counts of the pass that ended (everything on `st` waited for) to the host
+static int community_counts(mc_community *c, hipStream_t st)
+{
+    std::vector<unsigned long long> v((size_t)c->M);
+    HIPCK(hipMemcpyAsync(v.data(), c->d_counts, sizeof(unsigned long long) * v.size(), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    for (int m = 0; m < c->M; m++) c->member_reads[(size_t)m] = (int64_t)v[(size_t)m];
+    return 0;
+}
+
+extern "C" int mc_community_simulate(mc_community *c, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host)
+{
+    if (!c || first < 0 || n < 0 || (n > 0 && !dst_host)) { g_err = "mc_community_simulate: bad argument"; return -1; }
+    if (read_len < 18 || read_len > 3 * MC_MAXAA) { g_err = "read_len out of range (18..510)"; return -1; }
+    HIPCK(hipSetDevice(c->device));
+    if (community_for_len(c, read_len)) return -1;
+    std::fill(c->member_reads.begin(), c->member_reads.end(), 0);
+    if (n == 0) return 0;
+    const int64_t B = std::min<int64_t>(n, stream_batch());
+    uint8_t *d = nullptr;
+    HIPCK(hipMalloc((void **)&d, (size_t)(B * read_len)));
+    const uint64_t key = sim_key(seed, library_id);
+    int rc = hipMemset(c->d_counts, 0, sizeof(unsigned long long) * c->M) == hipSuccess ? 0 : -1;
+    if (rc) g_err = "mc_community_simulate: hipMemset failed";
+    for (int64_t at = 0; at < n && rc == 0; at += B) {               // ranges of the streaming batch size, as mc_community_library makes them
+        const int64_t cnt = std::min(B, n - at);
+        rc = launch_community(c, read_len, key, first + at, cnt, d, nullptr);
+        if (rc == 0 && hipMemcpy(dst_host + at * read_len, d, (size_t)(cnt * read_len), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "mc_community_simulate: copy failed"; rc = -1; }
+    }
+    if (rc == 0) rc = community_counts(c, nullptr);
+    (void)hipFree(d);
+    return rc;
+}
+
+extern "C" int mc_community_member_reads(mc_community *c, int64_t *out)
+{
+    if (!c || !out) { g_err = "mc_community_member_reads: bad argument"; return -1; }
+    memcpy(out, c->member_reads.data(), sizeof(int64_t) * (size_t)c->M);
+    return 0;
+}
+
+// The fused pass: every range is simulated into the resident read buffer and searched from there (mc_run_range: a range that
+// overflows a pool is run in smaller pieces) with best hits only; the best hits of the ranges are joined in read order - where
+// mc_search() on the same reads ends.
+extern "C" int mc_community_library(mc_handle *h, mc_community *c, int64_t nreads, uint64_t seed, uint64_t library_id)
+{
+    if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
+    if (!c || nreads < 0) { g_err = "mc_community_library: bad argument"; return -1; }
+    if (nreads > 0x7fffffff) { g_err = "mc_community_library: more than 2^31 - 1 reads"; return -1; }
+    if (c->lib.paired_end && (nreads & 1)) { g_err = "a paired-end library has an even number of reads (" + std::to_string(nreads) + " given)"; return -1; }
+    if (c->device != h->device) { g_err = "mc_community_library: the community lies on another device than the handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_community_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    const int L = h->read_len;
+    if (community_for_len(c, L)) return -1;
+    std::fill(c->member_reads.begin(), c->member_reads.end(), 0);
+    h->comm_ms[0] = h->comm_ms[1] = 0.f;
+    mc_stats tot; memset(&tot, 0, sizeof tot);
+    std::vector<mc_best_hit> all_best;
+    h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
+    if (nreads == 0) { h->stats = tot; return 0; }
+    const int64_t B = std::min<int64_t>(nreads, stream_batch());
+    const int64_t need = B * L + 16;                                 // the resident read buffer (mc_upload's) holds one range at a time
+    if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
+    if (ensure_capacity(h, h->ctx, B)) return -1;
+    hipEvent_t ev[2] = {};
+    for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { g_err = "hipEventCreate failed"; return -1; }
+    hipStream_t st = h->ctx.stream;
+    const bool saved_best_only = h->best_only;
+    h->best_only = true;
+    int rc = hipMemsetAsync(c->d_counts, 0, sizeof(unsigned long long) * c->M, st) == hipSuccess ? 0 : -1;
+    if (rc) g_err = "hipMemsetAsync failed";
+    const uint64_t key = sim_key(seed, library_id);
+    for (int64_t at = 0; at < nreads && rc == 0; at += B) {
+        const int64_t cnt = std::min(B, nreads - at);
+        if (hipEventRecord(ev[0], st) != hipSuccess || launch_community(c, L, key, at, cnt, h->d_reads, st) || hipEventRecord(ev[1], st) != hipSuccess) { rc = -1; break; }
+        h->reads_dev = h->d_reads; h->nreads = cnt;
+        if ((rc = mc_run_range(h, 0, cnt, at)) != 0) break;
+        h->comm_ms[0] += ev_ms(ev[0], ev[1]);
+        best_materialize(h);
+        all_best.insert(all_best.end(), h->best.begin(), h->best.end());
+        stats_add(tot, h->stats);
+    }
+    if (rc == 0) rc = community_counts(c, st); else (void)hipStreamSynchronize(st);
+    h->best_only = saved_best_only;
+    for (auto &e : ev) (void)hipEventDestroy(e);
+    if (rc) return rc;
+    h->res_rows = nullptr; h->n_res_rows = 0; h->best.swap(all_best); h->best_from = nullptr; h->stats = tot;
+    h->comm_ms[1] = tot.ms_total;
+    return 0;
+}
+
+extern "C" int mc_community_times(const mc_handle *h, float *ms)
+{
+    if (!h || !ms) { g_err = "null argument"; return -1; }
+    ms[0] = h->comm_ms[0]; ms[1] = h->comm_ms[1];
     return 0;
 }

@@ -84,6 +84,56 @@ MC_SIM_HD int mc_sim_contig(const int64_t *vstart, int ncontig, uint64_t u)
     return lo - 1;
 }
 
+// A community library (k_community.h; tests/emul/community.cpp): M member genomes with copies[m] cells each, their contigs one
+// after another (member m holds contigs mfirst[m] .. mfirst[m + 1] - 1).  key, ekey, span, frag, mate, the walk and the error stream
+// are those of a genome's library above; only the place of a fragment is drawn differently - a read comes from member m with
+// probability proportional to copies[m] x (valid starts of m):
+//     total[m] = valid starts of span bases in member m;  vstart[c] = valid starts of the member's contigs in front of contig c
+//     cum[m]   = sum over k < m of copies[k] x total[k];  universe = cum[M]  (0 < universe < 2^62)
+//     u        = mix(key + frag) % universe
+//     m        = the member with cum[m] <= u < cum[m + 1]            (a member without a contig of span bases is never drawn)
+//     v        = (u - cum[m]) % total[m];  c = the contig of m with vstart[c] <= v < vstart[c] + its valid starts;  s = off[c] + v - vstart[c]
+// One member with one copy: universe = total, u = v, and the library is the genome's, byte for byte.
+struct McSimPlace { int member, contig; int64_t start; };           // start: the fragment's first base in the concatenated bases
+
+MC_SIM_HD McSimPlace mc_sim_place(const uint64_t *cum, const int64_t *total, const int32_t *mfirst, const int64_t *vstart, const int64_t *off, int M, uint64_t x)
+{
+    const uint64_t u = x % cum[M];
+    int lo = 0, hi = M;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cum[mid] <= u) lo = mid + 1; else hi = mid; }
+    McSimPlace p;
+    p.member = lo - 1;
+    const uint64_t v = (u - cum[p.member]) % (uint64_t)total[p.member];
+    const int c0 = mfirst[p.member];
+    p.contig = c0 + mc_sim_contig(vstart + c0, mfirst[p.member + 1] - c0, v);
+    p.start = off[p.contig] + (int64_t)(v - (uint64_t)vstart[p.contig]);
+    return p;
+}
+
+// The member table of a community for fragments of span bases, on the host (mc_community_* and the g++ test build): vstart
+// (ncontig), total (M), cum (M + 1).  Returns 0, or 1 when the universe is 0 (no member has a contig of span bases) and 2 when it
+// does not stay below 2^62.
+#define MC_SIM_MAX_MEMBERS 65536
+#define MC_SIM_MAX_COPIES (1 << 20)
+#define MC_SIM_MAX_UNIVERSE (1ull << 62)
+inline int mc_sim_member_table(const int64_t *off, const int32_t *mfirst, const int64_t *copies, int M, int span, int64_t *vstart, int64_t *total, uint64_t *cum)
+{
+    cum[0] = 0;
+    for (int m = 0; m < M; m++) {
+        int64_t t = 0;
+        for (int c = mfirst[m]; c < mfirst[m + 1]; c++) {
+            vstart[c] = t;
+            const int64_t w = off[c + 1] - off[c] - span + 1;
+            if (w > 0) t += w;
+        }
+        total[m] = t;
+        const unsigned __int128 next = (unsigned __int128)cum[m] + (unsigned __int128)(uint64_t)copies[m] * (uint64_t)t;
+        if (next >= MC_SIM_MAX_UNIVERSE) return 2;
+        cum[m + 1] = (uint64_t)next;
+    }
+    return cum[M] == 0 ? 1 : 0;
+}
+
 // One read's walk.  base(p) returns the genome byte at absolute position p; emit(o, x) stores byte o of the read; event(j, e, x),
 // if the caller wants the log, sees every consumed base (e: 0 none, 1 substitution, 2 insertion, 3 deletion, 4 deletion refused).
 // [cs, ce) is the read's contig, p0 its first consumed base, dir +1 or -1.

@@ -268,14 +268,14 @@ def read_map(path, header=False):
 
 def write_reads(path, reads, paired_end=False):
     """A library in seq_sim.py's format: '>id\\nseq\\n', ids 0, 1, ...; paired end: '>k/1', '>k/2' for rows 2k, 2k + 1.  reads: an
-    (n, L) array, or (bases, offsets) of reads at their own lengths."""
+    (n, L) array, or (bases, offsets) of reads at their own lengths.  A path ending in .gz is written gzipped."""
     os.makedirs(os.path.dirname(path), exist_ok=True)
     if isinstance(reads, tuple):
         bases, off = reads
         rows = (bases[off[i]:off[i + 1]] for i in range(len(off) - 1))
     else:
         rows = (reads[i] for i in range(reads.shape[0]))
-    with open(path, "wb") as f:
+    with (gzip.open(path, "wb", compresslevel=1) if path.endswith(".gz") else open(path, "wb")) as f:
         for i, row in enumerate(rows):
             f.write(b">%d/%d\n" % (i >> 1, 1 + (i & 1)) if paired_end else b">%d\n" % i)
             f.write(row.tobytes())
