@@ -181,6 +181,28 @@ int mc_bootstrap(mc_handle *h, const mc_best_hit *best, int64_t n, const int32_t
 /* Milliseconds the last mc_bootstrap()'s kernels took (HIP events; the upload of the hits and the download of the sums not included). */
 float mc_bootstrap_ms(const mc_handle *h);
 
+/* Training step 5 (TRAINING.txt; the reference's optimize_weights.R): the per-family weights of one read length, fitted by the
+ * deterministic candidate search csrc/mc_wfit.h states - every generation C weight vectors around the best so far, made on the device
+ * from a hash of (seed, read_len, generation, candidate, family), each scored by mue = the median over the libraries of
+ * |truth - weighted mean of the kept predictions| / truth.  pred[N][F]: the predictions of training_preds.map, NaN for "NA";
+ * truth[N]: the true sizes.  Which predictions a library keeps is _ags_of_sums' cut (|pred - median| < 1.48 x MAD), made once.
+ * C = 0 and G = -1 select the header's defaults; G = 0 returns the start.  Outputs:
+ *   weights [F]          the fitted weights, each in [0, 1]; 1 / F for a family no library keeps
+ *   trace   [G + 1][3]   per generation: the best mue so far, the index of the generation's winning candidate (0: nothing was
+ *                        better; -1: the search had ended, sigma < 2^-20), sigma after it.  Row 0 is the start: mue(1 / F), 0, sigma.
+ * The result is the statement's bit for bit, whatever the launch geometry: the same bytes on every run.
+ * Refused: F outside 1 .. 32, N outside 1 .. 4096, C outside 0 .. 65536, G outside -1 .. 4096, a truth that is not a positive finite
+ * number, an infinite prediction.  Needs mc_open() only. */
+int mc_fit_weights(mc_handle *h, const double *pred, const double *truth, int32_t N, int32_t F, uint64_t seed, int32_t read_len, int32_t C, int32_t G,
+                   double *weights, double *trace);
+/* mue of K weight vectors of the caller's, w[K][F] -> out[K]: the mask and the kernel arithmetic of mc_fit_weights (+inf where
+ * more than half of the libraries keep no family of positive weight).  Refused as mc_fit_weights refuses, and a weight outside
+ * [0, 1] or NaN, K outside 0 .. 16777216.  Needs mc_open() only. */
+int mc_weights_mue(mc_handle *h, const double *pred, const double *truth, int32_t N, int32_t F, const double *w, int32_t K, double *out);
+/* Milliseconds the kernels of the last mc_fit_weights() / mc_weights_mue() took (HIP events; the table's upload and the results'
+ * download not included). */
+float mc_fit_weights_ms(const mc_handle *h);
+
 /* ---- training (the reference's training/ workflow, TRAINING.txt steps 1 - 3, on the device) --------------------------------
  * A genome resident in HBM: bases = contig_off[ncontig] bytes, the contigs one after another as the FASTA holds them (line breaks
  * dropped, case kept); contig_off[0] = 0.  mc_simulate() writes reads [first, first + n) of library (seed, library_id) at

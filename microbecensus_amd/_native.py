@@ -176,6 +176,10 @@ def load_library():
     lib.mc_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     lib.mc_bootstrap_ms.restype = C.c_float
     lib.mc_bootstrap_ms.argtypes = [C.c_void_p]
+    lib.mc_fit_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.mc_weights_mue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.mc_fit_weights_ms.restype = C.c_float
+    lib.mc_fit_weights_ms.argtypes = [C.c_void_p]
     lib.mc_genome_open.restype = C.c_void_p
     lib.mc_genome_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     lib.mc_genome_close.restype = None
@@ -207,6 +211,7 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_upload", "mc_attach", "mc_run", "mc_run_range", "mc_set_counting", "mc_debug_stage", "mc_range_begin", "mc_range_end", "mc_ranges_in_flight", "mc_result_rows", "mc_result_best_hits", "mc_result_stats", "mc_write_m8", "mc_write_m8_named",
                     "mc_reader_last_error", "mc_set_host_threads", "mc_reader_open", "mc_reader_open_range", "mc_reader_open_bz2_part", "mc_bz2_blocks", "mc_gz_chunks", "mc_reader_open_gz_part", "mc_reader_gz_provide", "mc_reader_gz_end_state", "mc_reader_gz_finish", "mc_reader_run", "mc_reader_reads", "mc_reader_get_stats", "mc_reader_times", "mc_reader_describe", "mc_dupset_open", "mc_dupset_close", "mc_dupset_walk", "mc_reader_take", "mc_reader_close", "mc_reader_trim", "mc_count_bases", "mc_quality_offset",
                     "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify", "mc_bootstrap", "mc_bootstrap_ms",
+                    "mc_fit_weights", "mc_weights_mue", "mc_fit_weights_ms",
                     "mc_genome_open", "mc_genome_close", "mc_genome_set_library", "mc_simulate", "mc_train_library", "mc_train_times",
                     "mc_genome_set_read_lengths", "mc_simulate_varlen", "mc_train_library_bases",
                     "mc_community_open", "mc_community_close", "mc_community_set_library", "mc_community_simulate", "mc_community_library", "mc_community_member_reads",
@@ -461,6 +466,16 @@ def load_model(path=None):
 
 
 ALN_STAT = {"hits": 0, "cov": 1, "aln": 2}
+
+
+def _wfit_default(name):
+    """a default of the weight fit, read out of csrc/mc_wfit.h (the one statement)"""
+    import re
+    with open(os.path.join(_HERE, "csrc", "mc_wfit.h")) as f:
+        return int(re.search(r"#define\s+%s\s+(\d+)" % name, f.read()).group(1))
+
+
+WFIT_DEFAULT_C, WFIT_DEFAULT_G = _wfit_default("MC_WFIT_C"), _wfit_default("MC_WFIT_G")
 
 
 def user_cache_dir():
@@ -887,6 +902,37 @@ class Engine:
     def bootstrap_ms(self):
         """milliseconds the last bootstrap()'s kernels took (HIP events)"""
         return float(self.lib.mc_bootstrap_ms(self.h))
+
+    def fit_weights(self, pred, truth, seed, read_len, candidates=None, generations=None):
+        """The per-family weights of one read length (mc_fit_weights; csrc/mc_wfit.h states the search).  pred: (N, F) float64, NaN
+        for NA; truth: (N,).  candidates / generations None: the header's defaults.  Returns (weights (F,), trace (G + 1, 3): best mue,
+        winning candidate, sigma per generation, row 0 the start)."""
+        pred = np.ascontiguousarray(pred, dtype=np.float64)
+        truth = np.ascontiguousarray(truth, dtype=np.float64)
+        if pred.ndim != 2 or truth.shape != (pred.shape[0],):
+            raise ValueError("fit_weights: pred (N, F) and truth (N,)")
+        Cn = 0 if candidates is None else int(candidates)
+        Gn = -1 if generations is None else int(generations)
+        rows = (WFIT_DEFAULT_G if Gn == -1 else max(Gn, 0)) + 1
+        w = np.zeros(pred.shape[1], np.float64); trace = np.zeros((rows, 3), np.float64)
+        self._check(self.lib.mc_fit_weights(self.h, pred.ctypes.data, truth.ctypes.data, pred.shape[0], pred.shape[1], int(seed) & 0xFFFFFFFFFFFFFFFF, int(read_len), Cn, Gn,
+                                            w.ctypes.data, trace.ctypes.data), "mc_fit_weights")
+        return w, trace
+
+    def weights_mue(self, pred, truth, w):
+        """mue of the weight vectors w (K, F) on the table (mc_weights_mue): (K,) float64"""
+        pred = np.ascontiguousarray(pred, dtype=np.float64)
+        truth = np.ascontiguousarray(truth, dtype=np.float64)
+        w = np.ascontiguousarray(np.atleast_2d(w), dtype=np.float64)
+        if pred.ndim != 2 or truth.shape != (pred.shape[0],) or w.shape[1] != pred.shape[1]:
+            raise ValueError("weights_mue: pred (N, F), truth (N,) and w (K, F)")
+        out = np.zeros(w.shape[0], np.float64)
+        self._check(self.lib.mc_weights_mue(self.h, pred.ctypes.data, truth.ctypes.data, pred.shape[0], pred.shape[1], w.ctypes.data, w.shape[0], out.ctypes.data), "mc_weights_mue")
+        return out
+
+    def fit_weights_ms(self):
+        """milliseconds the kernels of the last fit_weights() / weights_mue() took (HIP events)"""
+        return float(self.lib.mc_fit_weights_ms(self.h))
 
     def simulate(self, genome, n, seed, library_id, first=0):
         """Reads [first, first + n) of library (seed, library_id) at this engine's read length: uint8 array (n, read_len)."""

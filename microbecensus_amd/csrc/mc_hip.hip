@@ -12,6 +12,7 @@
 //   k_community.h          the library of a mock community of genomes (mc_community_*)
 //   k_varlen.h             reads of mixed lengths bucketed by length (mc_search_varlen)
 //   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
+//   k_wfit.h               the fit of the per-family weights, training step 5 (mc_fit_weights, mc_weights_mue)
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
 // ranges from a host-side source (mc_search, mc_search_files, mc_search_files_multi) with upload and search overlapped.
@@ -27,6 +28,7 @@
 #include "k_community.h"
 #include "k_varlen.h"
 #include "k_bootstrap.h"
+#include "k_wfit.h"
 
 #include <map>
 
@@ -79,6 +81,7 @@ struct mc_handle {
     float comm_ms[2] = {0, 0};            // mc_community_library: simulate, search of the last library (HIP events)
     int64_t train_bases = 0;              // mc_train_library: the bases of the last library's reads (mc_train_library_bases)
     float boot_ms = 0;                    // mc_bootstrap: the two kernels of the last call (HIP events)
+    float wfit_ms = 0;                    // mc_fit_weights / mc_weights_mue: the kernels of the last call (HIP events)
     uint8_t *stage_pin[2] = {}, *stage_dev[2] = {}; size_t stage_bytes = 0; hipStream_t copy_stream = nullptr;   // run_stream
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -1435,6 +1438,145 @@ extern "C" int mc_bootstrap(mc_handle *h, const mc_best_hit *best, int64_t n, co
 }
 
 extern "C" float mc_bootstrap_ms(const mc_handle *h) { return h ? h->boot_ms : 0.0f; }
+
+// ---- the fit of the per-family weights (k_wfit.h; csrc/mc_wfit.h states it) -------------------------------------------------------
+// The launch shape of k_wfit_eval for a table of N x F: whether the table is staged in LDS, the waves of a block, the words of LDS a
+// wave keeps its errors in, and the dynamic LDS of a block.
+struct WfitShape { bool tab_lds; int waves, err_words; size_t lds_bytes; };
+static WfitShape wfit_shape(int N, int F)
+{
+    WfitShape s;
+    const size_t tab = (size_t)(F + 2) * (size_t)N * 8;
+    s.err_words = (N + 63) / 64 > MC_WFIT_REG_ROUNDS ? N : 0;
+    const size_t per_wave = (size_t)s.err_words * 8 + 16;
+    s.tab_lds = tab <= MC_WFIT_TAB_LDS && tab + per_wave <= MC_WFIT_LDS_MAX;
+    const size_t room = MC_WFIT_LDS_MAX - (s.tab_lds ? tab : 0);
+    s.waves = (int)std::max<size_t>(1, std::min<size_t>(MC_WFIT_MAX_WAVES, room / per_wave));
+    s.lds_bytes = (s.tab_lds ? tab : 0) + (size_t)s.waves * per_wave;
+    return s;
+}
+
+// checks the table and makes the device layout of k_wfit.h from it: tab[F + 2][N], alive
+static int wfit_table(const char *who, const double *pred, const double *truth, int32_t N, int32_t F, std::vector<double> &tab, uint32_t &alive)
+{
+    if (F < 1 || F > MC_WFIT_MAX_F) { g_err = std::string(who) + ": 1 to 32 families"; return -1; }
+    if (N < 1 || N > MC_WFIT_MAX_N) { g_err = std::string(who) + ": 1 to " + std::to_string(MC_WFIT_MAX_N) + " libraries"; return -1; }
+    for (int n = 0; n < N; n++) if (!(truth[n] > 0.0) || std::isinf(truth[n])) { g_err = std::string(who) + ": a true size that is not a positive finite number"; return -1; }
+    for (size_t i = 0; i < (size_t)N * F; i++) if (std::isinf(pred[i])) { g_err = std::string(who) + ": an infinite prediction (NaN stands for NA)"; return -1; }
+    std::vector<double> pm((size_t)N * F);
+    std::vector<uint32_t> keep(N);
+    alive = mc_wfit_mask(pred, N, F, pm.data(), keep.data());
+    tab.assign((size_t)(F + 2) * N, 0.0);
+    for (int n = 0; n < N; n++) {
+        for (int f = 0; f < F; f++) tab[(size_t)f * N + n] = pm[(size_t)n * F + f];
+        tab[(size_t)F * N + n] = truth[n];
+        const uint64_t kb = keep[n];
+        memcpy(&tab[(size_t)(F + 1) * N + n], &kb, 8);
+    }
+    return 0;
+}
+
+static void wfit_launch_eval(const WfitShape &sh, int nblocks, hipStream_t st, const McWfitPars &P, const double *d_tab, const McWfitState *d_state, int32_t gen, const double *d_w,
+                             double *d_out, unsigned long long *d_best)
+{
+    if (sh.tab_lds) k_wfit_eval<true><<<dim3((unsigned)nblocks), dim3((unsigned)sh.waves * 64), sh.lds_bytes, st>>>(P, d_tab, d_state, gen, sh.err_words, d_w, d_out, d_best);
+    else k_wfit_eval<false><<<dim3((unsigned)nblocks), dim3((unsigned)sh.waves * 64), sh.lds_bytes, st>>>(P, d_tab, d_state, gen, sh.err_words, d_w, d_out, d_best);
+}
+
+extern "C" int mc_fit_weights(mc_handle *h, const double *pred, const double *truth, int32_t N, int32_t F, uint64_t seed, int32_t read_len, int32_t C, int32_t G,
+                              double *weights, double *trace)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!pred || !truth || !weights || !trace) { g_err = "null argument"; return -1; }
+    if (C < 0 || C > MC_WFIT_MAX_C) { g_err = "mc_fit_weights: 0 (the default) to 65536 candidates"; return -1; }
+    if (G < -1 || G > MC_WFIT_MAX_G) { g_err = "mc_fit_weights: -1 (the default) to 4096 generations"; return -1; }
+    if (C == 0) C = MC_WFIT_C;
+    if (G == -1) G = MC_WFIT_G;
+    std::vector<double> tab;
+    uint32_t alive = 0;
+    if (wfit_table("mc_fit_weights", pred, truth, N, F, tab, alive) != 0) return -1;
+    h->wfit_ms = 0;
+    HIPCK(hipSetDevice(h->device));
+    const WfitShape sh = wfit_shape(N, F);
+    const int nblocks = (int)std::min<int64_t>(2048, ((int64_t)C + sh.waves - 1) / sh.waves);
+    McWfitPars P; memset(&P, 0, sizeof(P));
+    P.N = N; P.F = F; P.C = C; P.alive = alive; P.seed = seed; P.L = (uint64_t)(int64_t)read_len;
+    McWfitState S0; memset(&S0, 0, sizeof(S0));
+    for (int f = 0; f < F; f++) S0.w[f] = 1.0 / (double)F;
+    S0.sigma = MC_WFIT_SIGMA0;
+    double *d_tab = nullptr, *d_trace = nullptr; McWfitState *d_state = nullptr; unsigned long long *d_best = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto release = [&]() { if (d_tab) (void)hipFree(d_tab); if (d_trace) (void)hipFree(d_trace); if (d_state) (void)hipFree(d_state); if (d_best) (void)hipFree(d_best); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); };
+#define WFITCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_err = std::string(#call) + ": " + hipGetErrorString(e_); release(); return -1; } } while (0)
+    const size_t trace_bytes = 3 * (size_t)(G + 1) * 8;
+    WFITCK(hipMalloc((void **)&d_tab, tab.size() * 8));
+    WFITCK(hipMalloc((void **)&d_trace, trace_bytes));
+    WFITCK(hipMalloc((void **)&d_state, sizeof(McWfitState)));
+    WFITCK(hipMalloc((void **)&d_best, (size_t)nblocks * 16));
+    WFITCK(hipEventCreate(&e0)); WFITCK(hipEventCreate(&e1));
+    hipStream_t st = h->ctx.stream;
+    WFITCK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+    WFITCK(hipMemcpyAsync(d_state, &S0, sizeof(S0), hipMemcpyHostToDevice, st));
+    WFITCK(hipMemsetAsync(d_trace, 0, trace_bytes, st));
+    WFITCK(hipEventRecord(e0, st));
+    McWfitPars P1 = P; P1.C = 1;                                   // the start: candidate 0 alone
+    wfit_launch_eval(sh, 1, st, P1, d_tab, d_state, -1, nullptr, nullptr, d_best);
+    k_wfit_update<<<dim3(1), dim3(256), 0, st>>>(P1, d_state, -1, 1, d_best, d_trace);
+    for (int g = 0; g < G; g++) {                                  // every generation enqueued; the host takes no part between them
+        wfit_launch_eval(sh, nblocks, st, P, d_tab, d_state, g, nullptr, nullptr, d_best);
+        k_wfit_update<<<dim3(1), dim3(256), 0, st>>>(P, d_state, g, nblocks, d_best, d_trace);
+    }
+    WFITCK(hipGetLastError());
+    WFITCK(hipEventRecord(e1, st));
+    McWfitState S1;
+    WFITCK(hipMemcpyAsync(&S1, d_state, sizeof(S1), hipMemcpyDeviceToHost, st));
+    WFITCK(hipMemcpyAsync(trace, d_trace, trace_bytes, hipMemcpyDeviceToHost, st));
+    WFITCK(hipStreamSynchronize(st));
+    WFITCK(hipEventElapsedTime(&h->wfit_ms, e0, e1));
+    for (int f = 0; f < F; f++) weights[f] = S1.w[f];
+    release();
+    return 0;
+}
+
+extern "C" int mc_weights_mue(mc_handle *h, const double *pred, const double *truth, int32_t N, int32_t F, const double *w, int32_t K, double *out)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!pred || !truth || (K > 0 && (!w || !out))) { g_err = "null argument"; return -1; }
+    if (K < 0 || K > (1 << 24)) { g_err = "mc_weights_mue: 0 to 16777216 weight vectors"; return -1; }
+    std::vector<double> tab;
+    uint32_t alive = 0;
+    if (wfit_table("mc_weights_mue", pred, truth, N, F, tab, alive) != 0) return -1;
+    for (size_t i = 0; i < (size_t)K * F; i++) if (!(w[i] >= 0.0 && w[i] <= 1.0)) { g_err = "mc_weights_mue: a weight outside [0, 1]"; return -1; }
+    h->wfit_ms = 0;
+    if (K == 0) return 0;
+    HIPCK(hipSetDevice(h->device));
+    const WfitShape sh = wfit_shape(N, F);
+    const int nblocks = (int)std::min<int64_t>(4096, ((int64_t)K + sh.waves - 1) / sh.waves);
+    McWfitPars P; memset(&P, 0, sizeof(P));
+    P.N = N; P.F = F; P.C = K; P.alive = alive;
+    double *d_tab = nullptr, *d_w = nullptr, *d_out = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto release = [&]() { if (d_tab) (void)hipFree(d_tab); if (d_w) (void)hipFree(d_w); if (d_out) (void)hipFree(d_out); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); };
+    WFITCK(hipMalloc((void **)&d_tab, tab.size() * 8));
+    WFITCK(hipMalloc((void **)&d_w, (size_t)K * F * 8));
+    WFITCK(hipMalloc((void **)&d_out, (size_t)K * 8));
+    WFITCK(hipEventCreate(&e0)); WFITCK(hipEventCreate(&e1));
+    hipStream_t st = h->ctx.stream;
+    WFITCK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+    WFITCK(hipMemcpyAsync(d_w, w, (size_t)K * F * 8, hipMemcpyHostToDevice, st));
+    WFITCK(hipEventRecord(e0, st));
+    wfit_launch_eval(sh, nblocks, st, P, d_tab, nullptr, 0, d_w, d_out, nullptr);
+    WFITCK(hipGetLastError());
+    WFITCK(hipEventRecord(e1, st));
+    WFITCK(hipMemcpyAsync(out, d_out, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    WFITCK(hipStreamSynchronize(st));
+    WFITCK(hipEventElapsedTime(&h->wfit_ms, e0, e1));
+#undef WFITCK
+    release();
+    return 0;
+}
+
+extern "C" float mc_fit_weights_ms(const mc_handle *h) { return h ? h->wfit_ms : 0.0f; }
 
 extern "C" int mc_set_keep_rows(mc_handle *h, int keep)
 {

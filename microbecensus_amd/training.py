@@ -7,8 +7,8 @@ classification on the GPU (mc_train_library) and the parameter fit of optimize_p
 Two orders the reference leaves to chance are fixed here: genomes are taken in sorted name order (the reference: os.listdir
 order, which decides the folds), and the candidates of one (read length, family) are enumerated min_score ascending, then
 max_pid ascending, then aln_cov ascending, then rate type hits / aln / cov - the FIRST strict minimum of the cross-validation
-error wins (the reference: whichever of its parallel processes finished first).  Weights are not fitted (optimize_weights.R):
-every (read length, family) gets weight 1.0.
+error wins (the reference: whichever of its parallel processes finished first).  Weights are 1.0 for every (read length, family)
+unless fit_weights is set: then step 5 (optimize_weights.R) runs as the device's candidate search (fit_weights(), csrc/mc_wfit.h).
 
 Libraries are single end without errors by default; error_model ('uniform' at error_rate, or 'illumina') and paired_end (with an
 insert) give seq_sim.py's other kinds (csrc/mc_simlib.h), with one deviation by default: every read keeps exactly L bases.
@@ -216,8 +216,100 @@ def fit(rates, sizes, xfolds):
     return k, float(err[k]), coeff, preds, err
 
 
+# ---- step 5: the per-family weights (optimize_weights.R as a device candidate search) -------------------------------------------
+def weight_tables(preds_rows, families, read_lengths):
+    """{L: (pred (N, F) float64 with NaN for NA, truth (N,), genome names)} from rows shaped as training_preds.map's: (read_length,
+    fam, genome_name, true_ags, est_ags), values as read from the file (strings, 'NA') or as train() holds them (numbers, None).
+    Libraries in the order of their first row, families in the order given."""
+    fidx = {f: i for i, f in enumerate(families)}
+    out = {}
+    for L in read_lengths:
+        rows = [r for r in preds_rows if int(r[0]) == int(L)]
+        genomes = list(dict.fromkeys(r[2] for r in rows))
+        gidx = {g: i for i, g in enumerate(genomes)}
+        pred = np.full((len(genomes), len(families)), np.nan)
+        truth = np.zeros(len(genomes))
+        for _, fam, g, true_ags, est in rows:
+            truth[gidx[g]] = float(true_ags)
+            if fam in fidx and est is not None and est != "NA":
+                pred[gidx[g], fidx[fam]] = float(est)
+        out[int(L)] = (pred, truth, genomes)
+    return out
+
+
+def fit_weights(preds_rows, families, read_lengths, engine, seed=0, candidates=None, generations=None):
+    """TRAINING.txt step 5 on the device, one call of mc_fit_weights per read length.  Returns ({"<L>_<fam>": weight}, {L: (mue at
+    1 / F, mue fitted)}).  engine: an open _native.Engine - there is no CPU fallback."""
+    if engine is None or not getattr(engine, "h", None):
+        raise RuntimeError("fit_weights searches its candidates on the GPU (mc_fit_weights) and there is no CPU fallback: no open engine given")
+    weights, mues = {}, {}
+    for L, (pred, truth, _) in weight_tables(preds_rows, families, read_lengths).items():
+        if not len(truth):
+            raise TrainingError("no training predictions for read length %d" % L)
+        w, trace = engine.fit_weights(pred, truth, seed, L, candidates, generations)
+        for fam, v in zip(families, w.tolist()):
+            weights["%d_%s" % (L, fam)] = v
+        mues[L] = (float(trace[0, 0]), float(trace[-1, 0]))
+    return weights, mues
+
+
+_fit_weights = fit_weights            # (train() has a switch of the same name)
+
+
+def weights_fit_record(seed, candidates, generations, mues):
+    """model.json's "weights_fit" record"""
+    from . import _native
+    return {"seed": int(seed), "candidates": int(candidates) if candidates else _native.WFIT_DEFAULT_C,
+            "generations": _native.WFIT_DEFAULT_G if generations is None or generations < 0 else int(generations),
+            "mue": {str(L): [m[0], m[1]] for L, m in sorted(mues.items())}}
+
+
+def _fit_engine(device, names, seqs, marker_family, nfam):
+    from . import _native
+    try:
+        return _native.Engine(device=device, names=names, seqs=seqs, marker_family=marker_family, nfam=nfam)
+    except RuntimeError as e:
+        raise RuntimeError("the weights are fitted on the GPU (mc_fit_weights) and there is no CPU fallback: %s" % e)
+
+
+def refit_model_dir(model_dir, device=0, seed=0, candidates=None, generations=None, log=print):
+    """Step 5 as a command of its own (scripts/optimize_weights.py): fits the weights on model_dir/training_preds.map and rewrites
+    weights.map and the weights (and "weights_fit") of model.json.  Returns the model."""
+    from . import _native
+    path = os.path.join(model_dir, "training_preds.map")
+    if not os.path.isfile(path):
+        raise TrainingError("%s does not exist (a model directory written by train_microbe_census.py holds it)" % path)
+    with open(os.path.join(model_dir, "model.json")) as f:
+        model = json.load(f)
+    names, seqs = _native.load_markers(os.path.join(model_dir, "markers.faa.gz"))
+    eng = _fit_engine(device, names, seqs, model["marker_family"], len(model["families"]))
+    try:
+        weights, mues = fit_weights(read_map(path, header=True), model["families"], model["read_lengths"], eng, seed, candidates, generations)
+    finally:
+        eng.close()
+    model["weights"] = weights
+    model["weights_fit"] = weights_fit_record(seed, candidates, generations, mues)
+    with open(os.path.join(model_dir, "model.json"), "w") as f:
+        json.dump(model, f, separators=(",", ":"), sort_keys=True)
+    write_weights_map(model_dir, weights)
+    log(fit_log_line(model["weights_fit"]))
+    return model
+
+
+def fit_log_line(rec):
+    return "Weights fitted on the GPU (seed %d, %d candidates x %d generations); median unsigned error per read length: %s" % (
+        rec["seed"], rec["candidates"], rec["generations"], ", ".join("%s: %.4g -> %.4g" % (L, m[0], m[1]) for L, m in sorted(rec["mue"].items(), key=lambda kv: int(kv[0]))))
+
+
+def write_weights_map(out_dir, weights):
+    with open(os.path.join(out_dir, "weights.map"), "w") as f:
+        for k in sorted(weights):
+            f.write("%s\t%r\n" % (k, weights[k]))
+
+
 # ---- outputs ------------------------------------------------------------------------------------------------------------------
-def write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, genome_sizes=None, preds=None, library=None):
+def write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, genome_sizes=None, preds=None, library=None,
+                weights_fit=None):
     """markers.faa.gz + model.json (the packaged schema, tools/build_data.py, plus the "library" record of a kind other than the
     default) and the reference's tables."""
     os.makedirs(out_dir, exist_ok=True)
@@ -228,6 +320,8 @@ def write_model(out_dir, names, seqs, marker_family, families, read_lengths, par
              "pars": pars, "coefficients": coefficients, "weights": weights}
     if library is not None:
         model["library"] = library
+    if weights_fit is not None:
+        model["weights_fit"] = weights_fit
     with open(os.path.join(out_dir, "model.json"), "w") as f:
         json.dump(model, f, separators=(",", ":"), sort_keys=True)
     with open(os.path.join(out_dir, "pars.map"), "w") as f:
@@ -239,9 +333,7 @@ def write_model(out_dir, names, seqs, marker_family, families, read_lengths, par
     with open(os.path.join(out_dir, "coefficients.map"), "w") as f:
         for k in sorted(coefficients):
             f.write("%s\t%r\n" % (k, coefficients[k]))
-    with open(os.path.join(out_dir, "weights.map"), "w") as f:
-        for k in sorted(weights):
-            f.write("%s\t%r\n" % (k, weights[k]))
+    write_weights_map(out_dir, weights)
     with open(os.path.join(out_dir, "read_len.map"), "w") as f:
         for L in sorted(int(L) for L in read_lengths):
             f.write("%d\n" % L)
@@ -295,8 +387,10 @@ def write_hits(path, families, hits, aln, cov):
 
 # ---- the run ------------------------------------------------------------------------------------------------------------------
 def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfolds=10, seed=0, device=0, write_reads_dir=None, log=print,
-          error_model=None, error_rate=None, paired_end=False, insert=None, reference_lengths=False):
-    """TRAINING.txt steps 1 - 4 in one call.  reference_lengths: seq_sim.py's read lengths (L + insertions - deletions), the library's
+          error_model=None, error_rate=None, paired_end=False, insert=None, reference_lengths=False, fit_weights=False, fit_seed=0, fit_candidates=None,
+          fit_generations=None):
+    """TRAINING.txt steps 1 - 4 in one call, and step 5 with fit_weights=True (the weights fitted on the device at fit_seed, with
+    fit_candidates x fit_generations candidates; None: the defaults of csrc/mc_wfit.h).  reference_lengths: seq_sim.py's read lengths (L + insertions - deletions), the library's
     bp their real total.  A paired-end library at coverage c holds library_reads(c, G, L) pairs (seq_sim.py's
     read_id counts pairs), so twice as many reads; a library's bp is its reads x L either way.  Returns the model dict written to
     out_dir/model.json, with the run's rates under '_rates' ({L: (genomes, families, candidates)}) and the genomes' sizes under
@@ -325,7 +419,7 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
         % (len(loaded), len(families), len(names), read_lengths, coverage, xfolds))
     if library is not None:
         log("Library: %s" % ", ".join("%s %s" % kv for kv in sorted(library.items()) if kv[1] not in (None, False)))
-    eng = _native.Engine(device=device, names=names, seqs=seqs, marker_family=marker_family, nfam=len(families))
+    eng = (_fit_engine if fit_weights else _native.Engine)(device, names, seqs, marker_family, len(families))
     gpu_genomes = [_native.Genome(bases, off, device) for _, bases, off in loaded]
     if library is not None:
         for g in gpu_genomes:
@@ -359,15 +453,22 @@ def train(genomes_dir, out_dir, read_lengths, coverage, gene_fams_dir=None, xfol
                 coefficients["%d_%s" % (L, fam)] = coeff
                 weights["%d_%s" % (L, fam)] = 1.0
                 preds.extend((L, fam, gname, est) for (gname, _, _), est in zip(loaded, pr))
+        fit_rec = None
+        if fit_weights:
+            weights, mues = _fit_weights([(L, fam, g, sizes[g], est) for L, fam, g, est in preds], families, read_lengths, eng, fit_seed, fit_candidates, fit_generations)
+            fit_rec = weights_fit_record(fit_seed, fit_candidates, fit_generations, mues)
     finally:
         for g in gpu_genomes:
             g.close()
         eng.close()
-    model = write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, sizes, preds, library)
+    model = write_model(out_dir, names, seqs, marker_family, families, read_lengths, pars, coefficients, weights, sizes, preds, library, fit_rec)
     zero = sorted(k for k, v in coefficients.items() if v == 0)
     if zero:
         log("Families no genome's reads were assigned to (coefficient 0): %s" % ", ".join(zero))
-    log("Weights are not fitted (optimize_weights.R is out of scope): every read length and family has weight 1.0")
+    if fit_rec is not None:
+        log(fit_log_line(fit_rec))
+    else:
+        log("Weights are not fitted (optimize_weights.R is out of scope): every read length and family has weight 1.0")
     log("Model written to %s" % out_dir)
     model["_rates"], model["_sizes"] = all_rates, sizes
     return model
