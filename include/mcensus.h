@@ -103,6 +103,35 @@ int mc_search(mc_handle *h, const uint8_t *reads, int64_t nreads, int64_t first_
  * (the message names the read), more than 2^31 - 1 reads. */
 int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offsets, int64_t nreads, int64_t first_read_id);
 
+/* ---- length classes: an estimate from reads of mixed lengths, each at the largest legal length it reaches (csrc/mc_classes.h states
+ * the rule).  mc_set_run_classes() replaces mc_set_run() for the class runs that follow: K ascending class lengths (1 <= K <= 32, each
+ * 18 .. 510) and the four parameter arrays as [K][nfam], row k = find_opt_pars(pars.map, class_len[k]).  The handle's single-length
+ * state (mc_search, mc_upload, ...) is the top class's; a later mc_set_run() restores the single-length run.
+ * mc_search_classes(): rows = nreads rows of stride = class_len[K - 1] bytes, a read's bases and then 0 bytes (a read longer than the
+ * stride cut to it).  The rows of a batch are sorted into their classes and trimmed on the device (csrc/k_classes.h) and the
+ * fixed-length pipeline runs once per non-empty class: that length's tables, that class's classification parameters and
+ * classification length.  Results: mc_result_best_hits() in ascending read id = first_read_id + row index, mc_result_best_classes()
+ * parallel to them (the class index of every best hit), mc_result_class_reads() (out[k]: the rows of class k; out[K]: the rows below
+ * class_len[0], which are skipped) and mc_result_stats() (totals).  mc_set_best_hits_only() is honoured.  A class run hands out NO m8
+ * rows: mc_result_rows() is empty and mc_write_m8() writes nothing.  Results do not depend on how the rows were cut into batches and
+ * ranges.  A run whose rows all fall in one class returns the best hits of mc_search() at that length on the cut reads, byte for byte.
+ * Refused, with a message naming the value: K outside 1 .. 32, a length outside 18 .. 510 or not ascending, a stride other than
+ * class_len[K - 1], a range in flight.  mc_search_files() on a reader of mc_reader_open_classes() is the same run from files; it is
+ * refused unless the handle's class list equals the reader's. */
+int mc_set_run_classes(mc_handle *h, const int32_t *class_len, int32_t K, double loge_thr, const double *min_cov, const double *min_score,
+                       const int32_t *max_aaid, const int32_t *aln_stat);
+int mc_search_classes(mc_handle *h, const uint8_t *rows, int64_t nreads, int32_t stride, int64_t first_read_id);
+int64_t mc_result_best_classes(mc_handle *h, const uint8_t **cls);
+int mc_result_class_reads(mc_handle *h, int64_t *out /* [K + 1] */);
+/* NOT part of the supported interface (like mc_debug_stage): a test and timing aid that may change or go.  The device prologue alone (row lengths, classes, scan, stable scatter, trimming gather) on nreads <= 2,097,151
+ * host rows under the class list of mc_set_run_classes().  Copied out where the pointer is not NULL: perm[nreads] (the row of every
+ * sorted position; rows without a class last), start[K + 2] (first sorted position of every class, of the rows without one, and
+ * nreads), word0[K + 1] (class k's reads lie back to back at pitch class_len[k] from byte 16 x word0[k] of the sorted bytes), the
+ * sorted bytes themselves when they fit sorted_cap, ms[2] (HIP events: [0] lengths, classes, scan and scatter, [1] the gather).
+ * Returns the number of sorted bytes, 16 x word0[K], or < 0. */
+int64_t mc_debug_classes_prologue(mc_handle *h, const uint8_t *rows, int64_t nreads, int32_t stride, uint32_t *perm, uint32_t *start, int64_t *word0,
+                                  uint8_t *sorted, int64_t sorted_cap, float *ms);
+
 /* Same pipeline on reads that are already resident in HBM (bench / streaming):
  * mc_upload() copies a batch to the device, mc_run() executes the kernels on it (no host transfers of reads). */
 int mc_upload(mc_handle *h, const uint8_t *reads, int64_t nreads);
@@ -305,6 +334,17 @@ void mc_set_host_threads(int32_t n);
  * fasta_out (may be NULL): the temp FASTA process_seqfile writes, ">{id}\n{seq[:L]}\n" per accepted read. */
 mc_reader *mc_reader_open(const char *const *paths, int32_t npaths, int32_t read_len, int64_t nreads, int32_t fastq, int32_t quality_offset,
                           double min_quality, double mean_quality, double max_unknown, int32_t filter_dups, const char *fasta_out);
+/* The same head-take under length classes (csrc/mc_classes.h): a record's L is its class length class_len[k], the largest one it
+ * reaches.  Too short: below class_len[0]; the N share and the quality mean and minimum run over the first L bases and qualities; the
+ * duplicate test on the full sequence, as ever; sampling stops at nreads accepted reads in all.  An accepted read is one row of
+ * mc_reader_stride() = class_len[K - 1] bytes - its first L bases, then 0 bytes - and the temp FASTA holds seq[:L].  mc_reader_stats is
+ * unchanged (the per-class counts come from the search: mc_result_class_reads).  mc_reader_run / _reads / _start / _fetch / _join and
+ * mc_search_files() work on such a reader; the window, part and slice readers below have no class form.  Refused as
+ * mc_set_run_classes() refuses a class list. */
+mc_reader *mc_reader_open_classes(const char *const *paths, int32_t npaths, const int32_t *class_len, int32_t K, int64_t nreads, int32_t fastq,
+                                  int32_t quality_offset, double min_quality, double mean_quality, double max_unknown, int32_t filter_dups, const char *fasta_out);
+/* bytes per row of mc_reader_reads() / mc_reader_fetch(): the read length, or the top class length */
+int32_t mc_reader_stride(const mc_reader *r);
 /* The same sampler on the byte window [byte_lo, byte_hi) of ONE plain (uncompressed, regular) file: the records that start in it.
  * Both ends are moved to the first record start behind them by one rule ('@' line whose second next line starts with '+' in a file
  * that starts with '@'; '>' line in one that starts with '>'), so consecutive windows cut a file into whole records whoever reads

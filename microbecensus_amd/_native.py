@@ -203,6 +203,17 @@ def load_library():
     lib.mc_community_library.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64]
     lib.mc_community_member_reads.argtypes = [C.c_void_p, C.c_void_p]
     lib.mc_community_times.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.mc_set_run_classes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mc_search_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]
+    lib.mc_result_best_classes.restype = C.c_int64
+    lib.mc_result_best_classes.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8))]
+    lib.mc_result_class_reads.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.mc_debug_classes_prologue.restype = C.c_int64
+    lib.mc_debug_classes_prologue.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
+    lib.mc_reader_open_classes.restype = C.c_void_p
+    lib.mc_reader_open_classes.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_char_p]
+    lib.mc_reader_stride.restype = C.c_int32
+    lib.mc_reader_stride.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 
@@ -215,7 +226,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_genome_open", "mc_genome_close", "mc_genome_set_library", "mc_simulate", "mc_train_library", "mc_train_times",
                     "mc_genome_set_read_lengths", "mc_simulate_varlen", "mc_train_library_bases",
                     "mc_community_open", "mc_community_close", "mc_community_set_library", "mc_community_simulate", "mc_community_library", "mc_community_member_reads",
-                    "mc_community_times"]
+                    "mc_community_times",
+                    "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride"]
 
 
 class DupSet:
@@ -264,6 +276,24 @@ class Reader:
                                     float(max_unknown), 1 if filter_dups else 0, fasta_out.encode() if fasta_out else None)
         if not self.r:
             raise RuntimeError(lib.mc_reader_last_error().decode())
+
+    @classmethod
+    def with_classes(cls, paths, class_len, nreads, fastq, quality_offset, min_quality, mean_quality, max_unknown, filter_dups, fasta_out=None):
+        """The sampler under length classes (mc_reader_open_classes): a record's L is the largest class length it reaches; rows of
+        class_len[-1] bytes, the read's first L bases and then 0 bytes.  read_len is the row stride."""
+        lib = load_library()
+        self = cls.__new__(cls)
+        if nreads is None:
+            nreads = (1 << 63) - 1
+        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+        cl = (C.c_int32 * len(class_len))(*[int(x) for x in class_len])
+        self.lib, self.class_len = lib, [int(x) for x in class_len]
+        self.r = lib.mc_reader_open_classes(arr, len(paths), cl, len(class_len), nreads, 1 if fastq else 0, int(quality_offset), float(min_quality), float(mean_quality),
+                                            float(max_unknown), 1 if filter_dups else 0, fasta_out.encode() if fasta_out else None)
+        if not self.r:
+            raise RuntimeError(lib.mc_reader_last_error().decode())
+        self.read_len = lib.mc_reader_stride(self.r)
+        return self
 
     @classmethod
     def on_range(cls, path, byte_lo, byte_hi, read_len, nreads, fastq, quality_offset, min_quality, mean_quality, max_unknown):
@@ -754,6 +784,56 @@ class Engine:
                 assert float(p[1]) == aaid[i]
         self._check(self.lib.mc_set_run(self.h, read_len, loge_thr, cov, score, aaid, stat), "mc_set_run")
         self.read_len = read_len
+
+    def set_run_classes(self, class_len, pars_by_len=None, families=None, loge_thr=1.0):
+        """Length classes (mc_set_run_classes): class_len ascending; pars_by_len[L] = find_opt_pars(pars.map, L) per class length."""
+        nf, K = self.nfam, len(class_len)
+        cov = (C.c_double * (nf * K))(*([0.0] * (nf * K))); score = (C.c_double * (nf * K))(*([0.0] * (nf * K)))
+        aaid = (C.c_int32 * (nf * K))(*([100] * (nf * K))); stat = (C.c_int32 * (nf * K))(*([0] * (nf * K)))
+        if pars_by_len is not None:
+            for k, L in enumerate(class_len):
+                for i, fam in enumerate(families):
+                    p = pars_by_len[L][fam]
+                    j = k * nf + i
+                    cov[j], aaid[j], score[j], stat[j] = float(p[0]), int(round(float(p[1]))), float(p[2]), ALN_STAT[p[3]]
+                    assert float(p[1]) == aaid[j]
+        cl = (C.c_int32 * max(K, 1))(*[int(x) for x in class_len])
+        self._check(self.lib.mc_set_run_classes(self.h, cl, K, loge_thr, cov, score, aaid, stat), "mc_set_run_classes")
+        self.class_len = [int(x) for x in class_len]
+        self.read_len = self.class_len[-1]
+
+    def search_classes(self, rows, first_read_id=0):
+        """rows: uint8 array (n, class_len[-1]), a read's bases then 0 bytes (mc_search_classes).  Returns (best_hits, classes, class_reads):
+        the best hits in ascending read id, the class index of each, and the rows per class (last entry: rows below the lowest class)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert rows.ndim == 2
+        self._check(self.lib.mc_search_classes(self.h, rows.ctypes.data_as(C.c_void_p), rows.shape[0], rows.shape[1], first_read_id), "mc_search_classes")
+        return self.class_results()
+
+    def class_results(self):
+        best = self.best_hits()
+        pc = C.POINTER(C.c_uint8)()
+        m = self.lib.mc_result_best_classes(self.h, C.byref(pc))
+        if m < 0:
+            raise RuntimeError("mc_result_best_classes failed: %s" % self.lib.mc_last_error().decode())
+        cls = np.ctypeslib.as_array(pc, shape=(m,)).copy() if m else np.zeros(0, np.uint8)
+        out = (C.c_int64 * (len(self.class_len) + 1))()
+        self._check(self.lib.mc_result_class_reads(self.h, out), "mc_result_class_reads")
+        return best, cls, np.array(list(out), np.int64)
+
+    def classes_prologue(self, rows, want_sorted=True):
+        """Test and timing aid (mc_debug_classes_prologue): perm, start, word0, the sorted bytes (or None) and the two kernel times."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        n, K = rows.shape[0], len(self.class_len)
+        perm = np.zeros(n, np.uint32); start = np.zeros(K + 2, np.uint32); word0 = np.zeros(K + 1, np.int64)
+        cap = n * rows.shape[1] + 16 * K + 16
+        srt = np.zeros(cap if want_sorted else 0, np.uint8)
+        ms = (C.c_float * 2)()
+        nb = self.lib.mc_debug_classes_prologue(self.h, rows.ctypes.data_as(C.c_void_p), n, rows.shape[1], perm.ctypes.data_as(C.c_void_p), start.ctypes.data_as(C.c_void_p),
+                                                word0.ctypes.data_as(C.c_void_p), srt.ctypes.data_as(C.c_void_p) if want_sorted else None, len(srt), ms)
+        if nb < 0:
+            raise RuntimeError("mc_debug_classes_prologue failed: %s" % self.lib.mc_last_error().decode())
+        return perm, start, word0, (srt[:nb] if want_sorted else None), (ms[0], ms[1])
 
     def search(self, reads, first_read_id=0):
         """reads: uint8 array (n, read_len) of bases.  Returns (rows, best_hits) as numpy structured arrays."""

@@ -11,6 +11,7 @@
 //   k_simulate.h           the training workflow's library simulator
 //   k_community.h          the library of a mock community of genomes (mc_community_*)
 //   k_varlen.h             reads of mixed lengths bucketed by length (mc_search_varlen)
+//   k_classes.h            padded read rows sorted into length classes and trimmed (mc_search_classes)
 //   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
 //   k_wfit.h               the fit of the per-family weights, training step 5 (mc_fit_weights, mc_weights_mue)
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
@@ -27,6 +28,7 @@
 #include "k_simulate.h"
 #include "k_community.h"
 #include "k_varlen.h"
+#include "k_classes.h"
 #include "k_bootstrap.h"
 #include "k_wfit.h"
 
@@ -100,6 +102,9 @@ struct mc_handle {
     std::vector<mc_best_hit> best; mc_stats stats;
     McCtx *best_from = nullptr; uint32_t best_count = 0;           // the context whose best hits (pinned, unordered) are those of the last range, and how many: best_materialize
     std::map<int, McTables> vl_tables; double vl_thr = 0;           // mc_search_varlen: mc_fill_tables() per bucket length, for the E-value threshold vl_thr
+    // length classes (mc_set_run_classes): the list, every class's classification parameters, and what the last class run left
+    McClasses cls = {}; bool cls_set = false, cls_results = false; std::vector<McClassPars> cls_pars;
+    std::vector<uint8_t> best_cls; int64_t cls_reads[MC_CL_BINS] = {};
 };
 
 static McIndex dev_index(const mc_handle *h)
@@ -403,6 +408,7 @@ extern "C" int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const
     const int newFP = ((read_len / 3 + 2) + 3) & ~3;
     if (newFP != h->FP || read_len != h->read_len) h->ctx.cap_reads = 0;   // pools are sized by read length and frame pitch
     h->read_len = read_len; h->FP = newFP; h->run_set = true;
+    h->cls_set = false;                                            // (mc_set_run_classes sets it again behind this)
     MC_OT("set_run: segtab, uploads", t0);
     return 0;
 }
@@ -838,6 +844,7 @@ static void best_materialize(mc_handle *h)
 static int range_end(mc_handle *h, McCtx &c)
 {
     c.busy = false;
+    h->cls_results = false;
     memset(&h->stats, 0, sizeof h->stats);
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
     h->stats.reads = c.n;
@@ -1082,6 +1089,7 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
 }
 
 void mc_host_copy(uint8_t *dst, const uint8_t *src, size_t bytes);   // (mc_reader.cpp: a batch copied by several threads)
+int32_t mc_reader_class_list(const mc_reader *r, int32_t *out);   // (mc_reader.cpp: the classes a reader was opened with; 0: a single-length reader)
 extern "C" int mc_search(mc_handle *h, const uint8_t *reads, int64_t nreads, int64_t first_read_id)
 {
     if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
@@ -1104,6 +1112,7 @@ extern "C" int mc_search(mc_handle *h, const uint8_t *reads, int64_t nreads, int
 extern "C" int mc_search_files_multi(mc_handle *const *handles, int32_t n_dev, mc_reader *r, int64_t first_read_id)
 {
     if (!handles || n_dev < 1 || !r) { g_err = "bad argument"; return -1; }
+    { int32_t cl[MC_CLS_MAX]; if (mc_reader_class_list(r, cl) > 0) { g_err = "mc_search_files_multi: a reader of length classes (one device: mc_search_files)"; return -1; } }
     for (int d = 0; d < n_dev; d++) {
         if (!handles[d] || !handles[d]->run_set) { g_err = "mc_set_run() must be called first on every handle"; return -1; }
         if (mc_reader_read_len(r) != handles[d]->read_len) { g_err = "the reader trims to another length than mc_set_run() was given"; return -1; }
@@ -1141,7 +1150,13 @@ extern "C" int mc_search_files_multi(mc_handle *const *handles, int32_t n_dev, m
     return 0;
 }
 
-extern "C" int mc_search_files(mc_handle *h, mc_reader *r, int64_t first_read_id) { return mc_search_files_multi(&h, 1, r, first_read_id); }
+static int search_files_classes(mc_handle *h, mc_reader *r, int64_t first_read_id);
+extern "C" int mc_search_files(mc_handle *h, mc_reader *r, int64_t first_read_id)
+{
+    int32_t cl[MC_CLS_MAX];
+    if (h && r && (h->cls_set || mc_reader_class_list(r, cl) > 0)) return search_files_classes(h, r, first_read_id);   // a class run: both sides must hold the same list
+    return mc_search_files_multi(&h, 1, r, first_read_id);
+}
 
 // ---- reads of mixed lengths (mc_search_varlen) ---------------------------------------------------------------------------------
 // The reads are bucketed by length on the device (k_varlen.h) and the fixed-length pipeline runs once per bucket, with the tables of
@@ -1309,6 +1324,289 @@ extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_
     if (one) return mc_search(h, nreads ? bases + offsets[0] : nullptr, nreads, first_read_id);   // every read of the run's length: the fixed path as it is
     HIPCK(hipSetDevice(h->device));
     return search_varlen(h, bases, offsets, nreads, first_read_id);
+}
+
+// ---- reads of mixed lengths, each at its length class (mc_set_run_classes, mc_search_classes) -------------------------------------
+// A batch of padded rows is sorted into its classes on the device (k_classes.h) and the fixed-length pipeline runs once per non-empty
+// class, cut into ranges as search_varlen cuts its buckets: with the tables of that length (vl_use_length) and - unlike there - the
+// classification parameters and length of that class.  No m8 rows: the best hits, their classes and the per-class counts.
+extern "C" int mc_set_run_classes(mc_handle *h, const int32_t *class_len, int32_t K, double loge_thr, const double *min_cov, const double *min_score,
+                                  const int32_t *max_aaid, const int32_t *aln_stat)
+{
+    if (!h || !class_len || !min_cov || !min_score || !max_aaid || !aln_stat) { g_err = "null argument"; return -1; }
+    int32_t bad = 0;
+    const int what = mc_classes_check(class_len, K, &bad);
+    if (what == 1) { g_err = "mc_set_run_classes: " + std::to_string(bad) + " length classes (1 .. 32 are supported)"; return -1; }
+    if (what == 2) { g_err = "mc_set_run_classes: class length " + std::to_string(bad) + " out of range (18 .. 510)"; return -1; }
+    if (what == 3) { g_err = "mc_set_run_classes: class length " + std::to_string(bad) + " does not ascend"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_run_classes: ranges begun with mc_range_begin() are still in flight"; return -1; }
+    const size_t F = (size_t)h->nfam, top = (size_t)(K - 1) * F;
+    // the handle's single-length state is the top class's: tables, pools and the run's E-value threshold come from mc_set_run
+    if (mc_set_run(h, class_len[K - 1], loge_thr, min_cov + top, min_score + top, max_aaid + top, aln_stat + top)) return -1;
+    h->cls.K = K;
+    h->cls_pars.assign((size_t)K, h->hP);
+    for (int k = 0; k < K; k++) {
+        h->cls.len[k] = class_len[k];
+        McClassPars &P = h->cls_pars[(size_t)k];
+        P.read_len = class_len[k];
+        for (size_t f = 0; f < F; f++) { P.min_cov[f] = min_cov[k * F + f]; P.min_score[f] = min_score[k * F + f]; P.max_aaid[f] = max_aaid[k * F + f]; P.aln_stat[f] = aln_stat[k * F + f]; }
+    }
+    h->cls_set = true;
+    return 0;
+}
+
+struct McClSorted { uint8_t *d_sorted = nullptr; uint32_t *d_perm = nullptr; std::vector<uint32_t> start; McClGather G; float ms[2] = {0, 0}; };
+
+// Sorts the n rows at d_rows (pitch stride, MC_CL_SLACK readable bytes behind them) into the classes of C: S.d_sorted receives every
+// class's trimmed reads back to back, class k from byte S.G.word0[k] * 16; S.start[k] is the class's first sorted position
+// (start[K]: the rows without a class, start[K + 1] = n), S.d_perm the row index of every sorted position.  ms (ev != nullptr: four
+// events): [0] lengths, classes, scan and scatter, [1] the gather.
+static int cl_prologue(McVlBuf &B, hipStream_t st, const uint8_t *d_rows, int64_t n, int stride, const McClasses &C, McClSorted &S, hipEvent_t *ev = nullptr)
+{
+    const uint32_t ntiles = (uint32_t)((n + MC_CL_TILE - 1) / MC_CL_TILE), nbins = (uint32_t)C.K + 1;
+    uint8_t *d_cls = nullptr; uint32_t *d_cnt = nullptr, *d_start = nullptr;
+    if (B.get(&d_cls, (size_t)n) || B.get(&d_cnt, (size_t)nbins * ntiles) || B.get(&d_start, nbins + 1) || B.get(&S.d_perm, (size_t)n)) return -1;
+    if (ev) HIPCK(hipEventRecord(ev[0], st));
+    k_cl_hist<<<dim3(ntiles), dim3(MC_CL_BS), 0, st>>>(d_rows, n, stride, C, mc_cl_lanes(stride), ntiles, d_cls, d_cnt);
+    HIPCK(hipGetLastError());
+    k_cl_scan<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, nbins * ntiles, ntiles, nbins, d_start);
+    HIPCK(hipGetLastError());
+    k_cl_scatter<<<dim3(ntiles), dim3(MC_CL_BS), 0, st>>>(d_cls, n, ntiles, nbins, d_cnt, S.d_perm);
+    HIPCK(hipGetLastError());
+    if (ev) HIPCK(hipEventRecord(ev[1], st));
+    S.start.assign(nbins + 1, 0);
+    HIPCK(hipMemcpyAsync(S.start.data(), d_start, S.start.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (S.start[nbins] != (uint32_t)n) { g_err = "internal: the length classes do not hold every row"; return -1; }
+    memset(&S.G, 0, sizeof S.G);
+    S.G.K = C.K;
+    for (int k = 0; k < C.K; k++) {
+        S.G.first[k] = S.start[(size_t)k]; S.G.cnt[k] = S.start[(size_t)k + 1] - S.start[(size_t)k];
+        S.G.word0[k + 1] = S.G.word0[k] + ((int64_t)S.G.cnt[k] * C.len[k] + 15) / 16;
+    }
+    const int64_t W = S.G.word0[C.K];
+    if (B.get(&S.d_sorted, (size_t)W * 16 + MC_CL_SLACK)) return -1;
+    HIPCK(hipMemsetAsync(S.d_sorted + W * 16, 0, MC_CL_SLACK, st));
+    if (ev) HIPCK(hipEventRecord(ev[2], st));
+    if (W) {
+        k_cl_gather<<<dim3((unsigned)std::min<int64_t>((W + MC_CL_BS - 1) / MC_CL_BS, MC_CL_GATHER_BLOCKS)), dim3(MC_CL_BS), 0, st>>>(d_rows, stride, S.d_perm, C, S.G, S.d_sorted);
+        HIPCK(hipGetLastError());
+    }
+    if (ev) {
+        HIPCK(hipEventRecord(ev[3], st));
+        HIPCK(hipEventSynchronize(ev[3]));
+        S.ms[0] = ev_ms(ev[0], ev[1]); S.ms[1] = ev_ms(ev[2], ev[3]);
+    }
+    return 0;
+}
+
+struct McClAcc { std::vector<mc_best_hit> best; std::vector<uint8_t> cls; mc_stats tot; int64_t reads[MC_CL_BINS]; };
+
+// one batch of rows, resident at d_rows: its best hits (global read ids) and counts are added to A
+static int classes_batch(mc_handle *h, const uint8_t *d_rows, int64_t n, int64_t first_read_id, McClAcc &A)
+{
+    McCtx &c = h->ctx;
+    const McClasses &C = h->cls;
+    hipStream_t st = c.stream;
+    McVlBuf B; McClSorted S;
+    if (cl_prologue(B, st, d_rows, n, mc_class_stride(C), C, S)) { (void)hipStreamSynchronize(st); return -1; }
+    const int64_t nclassed = (int64_t)S.start[(size_t)C.K];
+    std::vector<uint32_t> perm((size_t)nclassed);
+    if (nclassed) HIPCK(hipMemcpyAsync(perm.data(), S.d_perm, perm.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    struct Piece { int k; int64_t first, n; };
+    std::vector<Piece> pieces;
+    const int64_t batch = stream_batch();
+    int kmax = -1; int64_t nmax = 0;
+    for (int k = 0; k <= C.K; k++) A.reads[k] += (int64_t)(S.start[(size_t)k + 1] - S.start[(size_t)k]);
+    for (int k = 0; k < C.K; k++) {
+        const int64_t cnt = (int64_t)S.G.cnt[k];
+        if (!cnt) continue;
+        for (int64_t a = 0; a < cnt; a += batch) pieces.push_back({k, a, std::min(batch, cnt - a)});
+        kmax = k; nmax = std::max(nmax, std::min(batch, cnt));
+    }
+    A.tot.reads += n - nclassed;
+    if (pieces.empty()) return 0;
+    const size_t best0 = A.best.size();
+    const int L0 = h->read_len, FP0 = h->FP;
+    const uint8_t *saved_reads = h->reads_dev; const int64_t saved_n = h->nreads;
+    const bool saved_stay = h->rows_stay;
+    h->rows_stay = true;                                             // (a class run hands out no rows: they stay on the device)
+    int rc = vl_pools(h, C.len[kmax], nmax);
+    bool pending = false; int pending_k = 0;
+    auto collect = [&]() {
+        if (!pending) return;
+        pending = false;
+        best_materialize(h);
+        A.best.insert(A.best.end(), h->best.begin(), h->best.end());
+        A.cls.insert(A.cls.end(), h->best.size(), (uint8_t)pending_k);
+        stats_add(A.tot, h->stats);
+    };
+    auto begin = [&](const Piece &q) -> int {
+        if (vl_use_length(h, C.len[q.k])) return -1;
+        HIPCK(hipMemcpy(h->d_P, &h->cls_pars[(size_t)q.k], sizeof(McClassPars), hipMemcpyHostToDevice));
+        h->reads_dev = S.d_sorted + S.G.word0[q.k] * 16; h->nreads = (int64_t)S.G.cnt[q.k];
+        return mc_range_begin(h, q.first, q.n, (int64_t)S.G.first[q.k] + q.first);
+    };
+    // end(j), begin(j + 1), collect(j), as search_varlen: the front of the next piece runs while the host takes the results of this one
+    for (size_t j = 0; rc == 0 && j < pieces.size(); j++) {
+        if (j == 0 && (rc = begin(pieces[0])) != 0) break;
+        const Piece &q = pieces[j];
+        rc = mc_range_end(h);
+        if (rc == -2) rc = mc_run_range(h, q.first, q.n, (int64_t)S.G.first[q.k] + q.first);
+        if (rc) break;
+        pending = true; pending_k = q.k;
+        if (j + 1 < pieces.size() && (rc = begin(pieces[j + 1])) != 0) break;
+        collect();
+    }
+    if (rc == 0) collect();
+    if (h->pipe_nout) (void)mc_range_end(h);                         // (after an error: nothing stays in flight)
+    h->rows_stay = saved_stay;
+    h->read_len = L0; h->FP = FP0;
+    hipError_t e = hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice);   // the top class's tables and parameters back
+    if (e == hipSuccess) e = hipMemcpy(h->d_P, &h->hP, sizeof(McClassPars), hipMemcpyHostToDevice);
+    if (rc == 0 && e != hipSuccess) { g_err = std::string("restoring the run's tables: ") + hipGetErrorString(e); rc = -1; }
+    h->reads_dev = saved_reads; h->nreads = saved_n;
+    h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
+    if (rc) return rc;
+    // sorted positions -> global read ids, ascending (the batches follow each other in read order)
+    const size_t nb = A.best.size() - best0;
+    std::vector<std::pair<mc_best_hit, uint8_t>> tmp(nb);
+    for (size_t i = 0; i < nb; i++) {
+        tmp[i] = {A.best[best0 + i], A.cls[best0 + i]};
+        tmp[i].first.read = (int32_t)(first_read_id + perm[(size_t)tmp[i].first.read]);
+    }
+    std::sort(tmp.begin(), tmp.end(), [](const std::pair<mc_best_hit, uint8_t> &x, const std::pair<mc_best_hit, uint8_t> &y) { return x.first.read < y.first.read; });
+    for (size_t i = 0; i < nb; i++) { A.best[best0 + i] = tmp[i].first; A.cls[best0 + i] = tmp[i].second; }
+    return 0;
+}
+
+// fetch(dst, max, &first): as run_stream's, rows of the class stride.  The batches are uploaded and searched one after another (the
+// sampler of a class reader runs on its own thread beside them).
+static int classes_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64_t, int64_t *)> &fetch, int64_t first_read_id, int64_t expect_reads)
+{
+    HIPCK(hipSetDevice(h->device));
+    const int64_t B = std::max<int64_t>(1, expect_reads > 0 ? std::min(stream_batch(), expect_reads) : stream_batch()), stride = mc_class_stride(h->cls);   // (expect_reads: the most the source can deliver)
+    McVlBuf buf;
+    uint8_t *d_rows = nullptr, *pin = nullptr;
+    McClAcc A; memset(&A.tot, 0, sizeof A.tot); memset(A.reads, 0, sizeof A.reads);
+    int rc = 0;
+    int64_t cap = 0;
+    for (;;) {
+        int64_t at = 0;
+        if (!pin) { if (hipHostMalloc((void **)&pin, (size_t)(B * stride), hipHostMallocDefault) != hipSuccess) { g_err = "out of pinned host memory for the rows"; rc = -1; break; } }
+        const int64_t n = fetch(pin, B, &at);
+        if (n < 0) { rc = (int)n; break; }
+        if (n == 0) break;
+        if (n > cap) { if (buf.get(&d_rows, (size_t)(n * stride) + MC_CL_SLACK)) { rc = -1; break; } cap = n; }   // (the first batch is the largest)
+        if (hipMemcpyAsync(d_rows, pin, (size_t)(n * stride), hipMemcpyHostToDevice, h->ctx.stream) != hipSuccess ||
+            hipMemsetAsync(d_rows + n * stride, 0, MC_CL_SLACK, h->ctx.stream) != hipSuccess || hipStreamSynchronize(h->ctx.stream) != hipSuccess) { g_err = "upload of the rows failed"; rc = -1; break; }
+        if ((rc = classes_batch(h, d_rows, n, first_read_id + at, A)) != 0) break;
+        if (n < B) break;
+    }
+    if (pin) (void)hipHostFree(pin);
+    h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr; h->best_cls.clear();
+    if (rc) return rc;
+    h->best.swap(A.best); h->best_cls.swap(A.cls); h->stats = A.tot;
+    memcpy(h->cls_reads, A.reads, sizeof h->cls_reads);
+    h->cls_results = true;
+    return 0;
+}
+
+static int classes_ready(mc_handle *h, const char *who)
+{
+    if (!h || !h->run_set || !h->cls_set) { g_err = std::string(who) + ": mc_set_run_classes() must be called first"; return -1; }
+    if (h->pipe_nout) { g_err = std::string(who) + ": ranges begun with mc_range_begin() are still in flight"; return -1; }
+    return 0;
+}
+
+extern "C" int mc_search_classes(mc_handle *h, const uint8_t *rows, int64_t nreads, int32_t stride, int64_t first_read_id)
+{
+    if (classes_ready(h, "mc_search_classes")) return -1;
+    if (nreads < 0 || (nreads > 0 && !rows)) { g_err = "bad argument"; return -1; }
+    if (nreads > 0x7fffffff) { g_err = "more than 2^31 - 1 reads in one call"; return -1; }
+    if (stride != mc_class_stride(h->cls)) { g_err = "mc_search_classes: stride " + std::to_string(stride) + " is not the top class length " + std::to_string(mc_class_stride(h->cls)); return -1; }
+    int64_t at = 0;
+    return classes_stream(h, [&](uint8_t *dst, int64_t max_reads, int64_t *first) -> int64_t {
+        const int64_t n = std::max<int64_t>(0, std::min(max_reads, nreads - at));
+        if (n > 0) mc_host_copy(dst, rows + at * stride, (size_t)(n * stride));
+        *first = at; at += n;
+        return n;
+    }, first_read_id, nreads);
+}
+
+static int search_files_classes(mc_handle *h, mc_reader *r, int64_t first_read_id)
+{
+    if (classes_ready(h, "mc_search_files")) return -1;
+    int32_t rl[MC_CLS_MAX];
+    const int32_t rk = mc_reader_class_list(r, rl);
+    if (rk != h->cls.K || memcmp(rl, h->cls.len, sizeof(int32_t) * (size_t)rk) != 0) { g_err = "mc_search_files: the reader's length classes are not those of mc_set_run_classes()"; return -1; }
+    if (mc_reader_start(r) != 0) { g_err = mc_reader_last_error(); return -1; }
+    int64_t at = 0;
+    std::string ferr;
+    const int rc = classes_stream(h, [&](uint8_t *dst, int64_t max_reads, int64_t *first) -> int64_t {
+        const int64_t n = mc_reader_fetch(r, at, max_reads, dst);
+        if (n < 0) ferr = mc_reader_last_error();
+        *first = at; if (n > 0) at += n;
+        return n;
+    }, first_read_id, mc_reader_nreads(r));
+    const std::string err = !ferr.empty() ? ferr : std::string(rc ? mc_last_error() : "");
+    const int64_t sampled = mc_reader_join(r);
+    if (rc == -3) { g_err = err; return -3; }
+    if (sampled == -3) { g_err = mc_reader_last_error(); return -3; }
+    if (rc) { g_err = err; return rc; }
+    if (sampled < 0) { g_err = mc_reader_last_error(); return (int)sampled; }
+    return 0;
+}
+
+extern "C" int64_t mc_result_best_classes(mc_handle *h, const uint8_t **cls)
+{
+    if (!h || !cls) return -1;
+    if (!h->cls_results) { g_err = "mc_result_best_classes: the last run was not a class run"; return -1; }
+    *cls = h->best_cls.data();
+    return (int64_t)h->best_cls.size();
+}
+
+extern "C" int mc_result_class_reads(mc_handle *h, int64_t *out)
+{
+    if (!h || !out) { g_err = "null argument"; return -1; }
+    if (!h->cls_results) { g_err = "mc_result_class_reads: the last run was not a class run"; return -1; }
+    for (int k = 0; k <= h->cls.K; k++) out[k] = h->cls_reads[k];
+    return 0;
+}
+
+// Test and timing aid: the prologue alone on nreads host rows with the class list of mc_set_run_classes().  perm (nreads values),
+// start (K + 2), word0 (K + 1: each class's first 16-byte word of the sorted bytes) and, where they fit sorted_cap, the sorted bytes
+// (word0[K] * 16) are copied out; ms[0] lengths + classes + scan + scatter, ms[1] the gather (HIP events).  Returns word0[K] * 16.
+extern "C" int64_t mc_debug_classes_prologue(mc_handle *h, const uint8_t *rows, int64_t nreads, int32_t stride, uint32_t *perm, uint32_t *start, int64_t *word0,
+                                             uint8_t *sorted, int64_t sorted_cap, float *ms)
+{
+    if (classes_ready(h, "mc_debug_classes_prologue")) return -1;
+    if (nreads < 1 || nreads > (1 << 21) - 1 || !rows) { g_err = "mc_debug_classes_prologue: 1 .. 2097151 rows"; return -1; }
+    if (stride != mc_class_stride(h->cls)) { g_err = "mc_debug_classes_prologue: stride " + std::to_string(stride) + " is not the top class length"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    hipStream_t st = h->ctx.stream;
+    McVlBuf B; McClSorted S;
+    uint8_t *d_rows = nullptr;
+    const size_t bytes = (size_t)nreads * stride;
+    if (B.get(&d_rows, bytes + MC_CL_SLACK)) return -1;
+    HIPCK(hipMemcpyAsync(d_rows, rows, bytes, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(d_rows + bytes, 0, MC_CL_SLACK, st));
+    hipEvent_t ev[4] = {};
+    bool ev_ok = true;
+    for (auto &e : ev) ev_ok = ev_ok && hipEventCreate(&e) == hipSuccess;
+    const int rc = ev_ok ? cl_prologue(B, st, d_rows, nreads, stride, h->cls, S, ev) : -1;   // (cl_prologue may return early: the events go either way)
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+    if (!ev_ok) g_err = "mc_debug_classes_prologue: cannot create events";
+    if (rc) { (void)hipStreamSynchronize(st); return -1; }
+    const int64_t nbytes = S.G.word0[h->cls.K] * 16;
+    if (perm) HIPCK(hipMemcpyAsync(perm, S.d_perm, (size_t)nreads * 4, hipMemcpyDeviceToHost, st));
+    if (sorted && nbytes && nbytes <= sorted_cap) HIPCK(hipMemcpyAsync(sorted, S.d_sorted, (size_t)nbytes, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (start) memcpy(start, S.start.data(), S.start.size() * 4);
+    if (word0) memcpy(word0, S.G.word0, sizeof(int64_t) * (size_t)(h->cls.K + 1));
+    if (ms) { ms[0] = S.ms[0]; ms[1] = S.ms[1]; }
+    return nbytes;
 }
 
 // bin nk = reads whose best row passes exactly the first nk (ascending) cut-offs: cut-off j (ascending) counts the bins nk > j

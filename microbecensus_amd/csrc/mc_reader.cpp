@@ -60,6 +60,7 @@
 #include "../../include/mcensus.h"
 #include "mc_pgzip.h"
 #include "mc_pbzip2.h"
+#include "mc_classes.h"
 #if defined(__SSE2__)
 #include <emmintrin.h>
 #endif
@@ -680,6 +681,7 @@ struct Rec {
     uint32_t out;                                      // slot in the output of this region (or ~0)
     uint8_t flags;
     uint8_t shard;                                     // of the record's duplicate class: top bits of min(h1, h2) - a sequence and its reverse complement share it
+    uint16_t clen;                                     // the L of this record: Params::L, or its class length (Params::cls, mc_classes.h)
 };
 
 struct ShItem { uint64_t h1, h2; const uint8_t *seq; uint32_t len, idx; uint8_t q; };   // q: in - the quality filter's verdict (R_PASS / R_LOWQ / R_ERR) | R_STABLE; out - the sampler's (R_DUP or that verdict)
@@ -842,14 +844,22 @@ struct Params { size_t L = 0; int fastq = 0, qoff = 0, dups = 0; bool count_only
                 bool decide = false; double max_unknown = 0, mean_q = 0, min_q = 0;   // decide: the quality filter's verdict per record is given by the parser's threads (no -d: a record's fate depends on nothing but itself)
                 bool shards = false;
                 bool stable = false;
-                bool find_qoff = false; };                                            // find_qoff: mc_quality_offset - every piece looks for its first quality character that decides                                               // stable: the file is a mapping that stays until the sampler ends                                               // shards: -d - the parser's threads group their records by duplicate class, the classes' walkers give the verdicts
+                bool find_qoff = false;
+                McClasses cls = {}; };                                                 // cls.K > 0: mc_reader_open_classes - a record's L is its class length                                            // find_qoff: mc_quality_offset - every piece looks for its first quality character that decides                                               // stable: the file is a mapping that stays until the sampler ends                                               // shards: -d - the parser's threads group their records by duplicate class, the classes' walkers give the verdicts
 
 void evaluate(Rec &r, const Params &P)
 {
     r.flags = (r.qual ? R_QUAL : 0); r.out = ~0u; r.shard = 0;
     r.ncount = 0; r.nq = 0; r.qmin = 1 << 30; r.qsum = 0; r.h1 = r.h2 = 0;
     if (P.count_only) return;
-    if (r.len < P.L) { r.flags |= R_SHORT; return; }
+    size_t L = P.L;
+    if (P.cls.K > 0) {
+        const int k = mc_class_of(P.cls, (int)std::min<uint32_t>(r.len, MC_CLS_MAXLEN));
+        if (k == P.cls.K) { r.flags |= R_SHORT; return; }
+        L = (size_t)P.cls.len[k];
+    }
+    r.clen = (uint16_t)std::min<size_t>(L, 0xFFFF);
+    if (r.len < L) { r.flags |= R_SHORT; return; }
     // the first L bases: how many are 'N'; the first min(L, qlen) qualities: their sum and their minimum (as ord(c) - offset) - 16 bytes at
     // a time where SSE2 is there (byte sums by psadbw, the minimum by pminub: the offset comes off at the end), the plain loops elsewhere
     uint32_t nc = 0;
@@ -858,15 +868,15 @@ void evaluate(Rec &r, const Params &P)
     {
         const __m128i cN = _mm_set1_epi8('N'), zero = _mm_setzero_si128();
         __m128i acc = zero;
-        for (; i + 16 <= P.L; i += 16)
+        for (; i + 16 <= L; i += 16)
             acc = _mm_add_epi64(acc, _mm_sad_epu8(_mm_and_si128(_mm_cmpeq_epi8(_mm_loadu_si128((const __m128i *)(r.seq + i)), cN), _mm_set1_epi8(1)), zero));
         nc = (uint32_t)(_mm_cvtsi128_si64(acc) + _mm_cvtsi128_si64(_mm_unpackhi_epi64(acc, acc)));
     }
 #endif
-    for (; i < P.L; i++) nc += (r.seq[i] == 'N');
+    for (; i < L; i++) nc += (r.seq[i] == 'N');
     r.ncount = nc;
     if (P.fastq && r.qual) {
-        const size_t nq = r.qlen < P.L ? r.qlen : P.L;
+        const size_t nq = r.qlen < L ? r.qlen : L;
         int64_t sum = 0; int mn = 1 << 30;
         size_t k = 0;
 #if defined(__SSE2__)
@@ -893,7 +903,7 @@ void evaluate(Rec &r, const Params &P)
 // would raise at this record
 inline bool decide(Rec &r, const Params &P)
 {
-    bool fail = (double)(100 * (long long)r.ncount) / (double)P.L > P.max_unknown;
+    bool fail = (double)(100 * (long long)r.ncount) / (double)(P.cls.K > 0 ? (size_t)r.clen : P.L) > P.max_unknown;
     if (!fail && P.fastq) {
         if (!(r.flags & R_QUAL) || r.nq == 0) return false;
         if ((double)r.qsum / (double)r.nq < P.mean_q) fail = true;
@@ -1274,6 +1284,7 @@ int walk_file(const std::string &path, const Params &P0, Pool &pool, const std::
 struct mc_reader {
     std::vector<std::string> paths;
     int32_t L = 0, fastq = 0, qoff = 0, filter_dups = 0;
+    McClasses cls = {};                                            // mc_reader_open_classes (K > 0): L is the row stride, the top class length
     int64_t nreads = 0;
     int64_t range_lo = -1, range_hi = -1;                          // mc_reader_open_range
     int64_t bz_b0 = -1, bz_b1 = -1; int bz_kind = 0;               // mc_reader_open_bz2_part
@@ -1356,6 +1367,24 @@ extern "C" mc_reader *mc_reader_open(const char *const *paths, int32_t npaths, i
     r->L = read_len; r->nreads = nreads; r->fastq = fastq; r->qoff = quality_offset; r->filter_dups = filter_dups;
     r->min_q = min_quality; r->mean_q = mean_quality; r->max_unknown = max_unknown;
     if (fasta_out) r->fasta_out = fasta_out;
+    return r;
+}
+
+// The same head-take with length classes (mc_classes.h): a record's L is the largest class length it reaches - too short below
+// class_len[0]; the N share and the quality mean and minimum over its first L bases and qualities; the duplicate test on the full sequence,
+// as ever - and an accepted read is one row of class_len[K - 1] bytes, its first L bases and then 0 bytes (the temp FASTA holds seq[:L]).
+extern "C" mc_reader *mc_reader_open_classes(const char *const *paths, int32_t npaths, const int32_t *class_len, int32_t K, int64_t nreads, int32_t fastq,
+                                             int32_t quality_offset, double min_quality, double mean_quality, double max_unknown, int32_t filter_dups, const char *fasta_out)
+{
+    int32_t bad = 0;
+    const int what = class_len ? mc_classes_check(class_len, K, &bad) : 1;
+    if (what == 1) { r_err = "mc_reader_open_classes: " + std::to_string(class_len ? bad : 0) + " length classes (1 .. 32 are supported)"; return nullptr; }
+    if (what == 2) { r_err = "mc_reader_open_classes: class length " + std::to_string(bad) + " out of range (18 .. 510)"; return nullptr; }
+    if (what == 3) { r_err = "mc_reader_open_classes: class length " + std::to_string(bad) + " does not ascend"; return nullptr; }
+    mc_reader *r = mc_reader_open(paths, npaths, class_len[K - 1], nreads, fastq, quality_offset, min_quality, mean_quality, max_unknown, filter_dups, fasta_out);
+    if (!r) return nullptr;
+    r->cls.K = K;
+    for (int k = 0; k < K; k++) r->cls.len[k] = class_len[k];
     return r;
 }
 
@@ -1528,7 +1557,7 @@ static int64_t reader_run(mc_reader *r)
         if (packed) nparse = std::min(nparse, std::max(2, effective_cores() / 2));
     }
     Pool pool(nparse);
-    Params P; P.L = (size_t)r->L; P.fastq = r->fastq; P.qoff = r->qoff; P.dups = r->filter_dups;
+    Params P; P.L = (size_t)r->L; P.fastq = r->fastq; P.qoff = r->qoff; P.dups = r->filter_dups; P.cls = r->cls;
     const bool serial = getenv("MC_READER_SERIAL_SAMPLER") != nullptr;   // (tests compare the two forms)
     P.decide = !serial && !r->filter_dups;
     P.shards = !serial && r->filter_dups;
@@ -1537,6 +1566,12 @@ static int64_t reader_run(mc_reader *r)
     std::unique_ptr<SeqSet[]> seen_sh(P.shards ? new SeqSet[NSHARD] : nullptr);
     struct Maps { KeptMaps v; ~Maps() { for (auto &m : v) munmap((void *)m.first, m.second); } } maps;   // the plain files the sets point into             // the sets of the duplicate classes' walkers
     const size_t L = (size_t)r->L;
+    const bool classes = r->cls.K > 0;
+    // an accepted read -> its row: the first L bases; under length classes the first clen bases and 0 bytes up to the stride L
+    auto put_row = [L, classes](uint8_t *row, const Rec &rec) {
+        if (!classes) { memcpy(row, rec.seq, L); return; }
+        memcpy(row, rec.seq, rec.clen); memset(row + rec.clen, 0, L - rec.clen);
+    };
     int64_t kept = 0, rcode = 0;
     char idbuf[32];
     // what the reference raises at a record (R_ERR), in the order its sampler meets the causes: reverse_complement() of the duplicate
@@ -1621,12 +1656,13 @@ static int64_t reader_run(mc_reader *r)
                     uint8_t *dst = r->reads + (size_t)kept0 * L;
                     pool.run((int)np, [&](int k) {
                         int64_t j = base[k]; const int64_t stop = j + take[k];
-                        for (const Rec &rec : order[k]->recs) { if (j == stop) break; if (rec.flags & R_PASS) { memcpy(dst + (size_t)j * L, rec.seq, L); j++; } }
+                        for (const Rec &rec : order[k]->recs) { if (j == stop) break; if (rec.flags & R_PASS) { put_row(dst + (size_t)j * L, rec); j++; } }
                     });
                     if (out) {                                         // the FASTA copy of the sample (reference :352), in order
                         for (int64_t i = kept0; i < kept; i++) {
                             const int k = snprintf(idbuf, sizeof idbuf, ">%lld\n", (long long)i);
-                            fwrite(idbuf, 1, (size_t)k, out); fwrite(r->reads + (size_t)i * L, 1, L, out); fputc('\n', out);
+                            const uint8_t *row = r->reads + (size_t)i * L;
+                            fwrite(idbuf, 1, (size_t)k, out); fwrite(row, 1, classes ? (size_t)mc_class_row_len(row, (int)L) : L, out); fputc('\n', out);
                         }
                     }
                     r->publish(kept);
@@ -1645,7 +1681,7 @@ static int64_t reader_run(mc_reader *r)
                         if (rec.flags & R_RCBAD) { r_err = "KeyError: base outside ACGTN in reverse_complement"; rcode = -3; return false; }
                         if (seen.contains(rec.h2, rec.seq, rec.len, true)) { r->st.dups++; continue; }
                     }
-                    bool fail = (double)(100 * (long long)rec.ncount) / (double)L > r->max_unknown;
+                    bool fail = (double)(100 * (long long)rec.ncount) / (double)(classes ? (size_t)rec.clen : L) > r->max_unknown;
                     if (!fail && r->fastq) {
                         if (!(rec.flags & R_QUAL)) { r_err = "TypeError: record without qualities in a FASTQ run"; rcode = -3; return false; }
                         if (rec.nq == 0) { r_err = "ValueError: empty quality string"; rcode = -3; return false; }
@@ -1656,7 +1692,7 @@ static int64_t reader_run(mc_reader *r)
                     rec.out = (uint32_t)(kept - kept0);
                     if (out) {
                         const int k = snprintf(idbuf, sizeof idbuf, ">%lld\n", (long long)kept);
-                        fwrite(idbuf, 1, (size_t)k, out); fwrite(rec.seq, 1, L, out); fputc('\n', out);
+                        fwrite(idbuf, 1, (size_t)k, out); fwrite(rec.seq, 1, classes ? (size_t)rec.clen : L, out); fputc('\n', out);
                     }
                     kept++;
                     if (r->filter_dups && !seen.insert(rec.h1, rec.seq, rec.len, false)) { r_err = "out of memory for the set of accepted sequences"; rcode = -1; return false; }
@@ -1668,7 +1704,7 @@ static int64_t reader_run(mc_reader *r)
             if (kept > kept0) {
                 if (!r->reserve((size_t)kept * L)) { r_err = "out of memory for the sampled reads"; rcode = -1; return false; }
                 uint8_t *dst = r->reads + (size_t)kept0 * L;
-                pool.run((int)order.size(), [&](int k) { for (const Rec &rec : order[k]->recs) if (rec.out != ~0u) memcpy(dst + (size_t)rec.out * L, rec.seq, L); });
+                pool.run((int)order.size(), [&](int k) { for (const Rec &rec : order[k]->recs) if (rec.out != ~0u) put_row(dst + (size_t)rec.out * L, rec); });
                 r->publish(kept);
             }
             return !full;
@@ -1904,4 +1940,12 @@ extern "C" int32_t mc_reader_times(const mc_reader *r, double *out, int32_t n)
     return k;
 }
 extern "C" int32_t mc_reader_read_len(const mc_reader *r) { return r ? r->L : 0; }
+extern "C" int32_t mc_reader_stride(const mc_reader *r) { return r ? r->L : 0; }
+// library-internal (mc_hip.hip): the classes the reader was opened with -> out (up to MC_CLS_MAX values); returns K, 0 for a single-length reader
+int32_t mc_reader_class_list(const mc_reader *r, int32_t *out)
+{
+    if (!r) return 0;
+    for (int k = 0; k < r->cls.K; k++) out[k] = r->cls.len[k];
+    return r->cls.K;
+}
 extern "C" int64_t mc_reader_nreads(const mc_reader *r) { return r ? r->nreads : 0; }

@@ -869,6 +869,8 @@ def run_pipeline_distributed(args, device=None):
     import queue
     import sys
     import threading
+    if args.get("mixed_lengths") is not None and args.get("mixed_lengths") is not False:     # (before the process group or a device is touched)
+        sys.exit("--mixed-lengths runs on one GPU: run_pipeline_distributed has no class form")
     import torch
     import torch.distributed as dist
     from . import _native

@@ -305,6 +305,70 @@ def auto_detect_read_length(seqfile, file_type, valid=None):
     return best
 
 
+def class_of_length(class_len, n):
+    """The length class of a read of n bases (csrc/mc_classes.h): the index of the largest class_len[k] <= n, or None - too short."""
+    k = None
+    for j, L in enumerate(class_len):
+        if L <= n:
+            k = j
+    return k
+
+
+def auto_detect_length_classes(seqfile, valid=None):
+    """The default classes of args['mixed_lengths']: the 10,000 records auto_detect_read_length reads, classified over all of the
+    model's lengths; the lengths at least 1 % of them fall in are kept (that bounds the row stride and keeps stray long reads from
+    adding classes)."""
+    lengths = []
+    try:
+        with open_file(seqfile) as f_in:
+            for i, rec in enumerate(parse_seqs(f_in)):
+                if i == 10000:
+                    break
+                lengths.append(len(rec.seq))
+    except Exception:
+        sys.exit("Could not detect read length of: %s\nThis may be due to an invalid format\nTry specifying the classes with --mixed-lengths L1,L2,..." % seqfile)
+    valid = list(VALID_READ_LENGTHS if valid is None else valid)
+    counts = [0] * len(valid)
+    for n in lengths:
+        k = class_of_length(valid, n)
+        if k is not None:
+            counts[k] += 1
+    keep = [L for L, c in zip(valid, counts) if lengths and 100 * c >= len(lengths)]
+    if not keep:
+        sys.exit("Median read length is %s. Cannot compute AGS using reads shorter than %s bp." % (int(median(lengths)) if lengths else 0, valid[0]))
+    return keep
+
+
+def mixed_lengths_on(args):
+    """args['mixed_lengths'] is set: True or a list (an empty list is refused by check_mixed_lengths, not taken for "off")."""
+    return args.get("mixed_lengths") is not None and args.get("mixed_lengths") is not False
+
+
+def check_mixed_lengths(args, paths=None):
+    """args['mixed_lengths'] (True, or a list of class lengths): refuses what the switch does not combine with - before any GPU work -
+    and fills args['length_classes']."""
+    for key, flag in (("bootstrap", "--bootstrap"), ("curve", "--curve")):
+        if args.get(key):
+            sys.exit("--mixed-lengths cannot be combined with %s" % flag)
+    if args.get("rapsearch"):
+        sys.exit("--mixed-lengths cannot be combined with -r: an external search runs at one read length")
+    if args.get("keep_tmp"):
+        sys.exit("--mixed-lengths cannot be combined with keep_tmp: a class run leaves no m8 file")
+    if args.get("read_length") is not None:
+        sys.exit("--mixed-lengths cannot be combined with -l %s: every read is cut to its own length class" % args["read_length"])
+    valid = list(_valid_read_lengths(args.get("model_dir")))
+    want = args["mixed_lengths"]
+    if want is True:
+        classes = auto_detect_length_classes(args["seqfiles"][0], valid)
+    else:
+        classes = sorted(set(int(x) for x in want))
+        bad = [L for L in classes if L not in valid]
+        if bad or not classes:
+            sys.exit("Length classes %s are not lengths the model was trained for: %s" % (bad, valid))
+    args["length_classes"] = classes
+    args["read_length"] = "mixed"
+
+
 def impute_missing_args(args):
     for key, val in (("verbose", False), ("outfile", None), ("nreads", 1000000), ("threads", 1), ("filter_dups", False),
                      ("keep_tmp", False), ("mean_quality", -5), ("min_quality", -5), ("max_unknown", 100)):
@@ -333,7 +397,7 @@ def check_arguments(args):
     for key in ("bootstrap", "curve"):
         if args.get(key) and (not isinstance(args[key], int) or isinstance(args[key], bool) or args[key] < 0):
             sys.exit("Invalid %s: %s\nMust be a non-negative integer." % (key, args[key]))
-    if args.get("model_dir") and args["read_length"] not in _valid_read_lengths(args["model_dir"]):
+    if args.get("model_dir") and not mixed_lengths_on(args) and args["read_length"] not in _valid_read_lengths(args["model_dir"]):
         sys.exit("Read length %s is not one the model in %s was trained for: %s" % (args["read_length"], args["model_dir"], _valid_read_lengths(args["model_dir"])))
 
 
@@ -378,6 +442,8 @@ def quality_filter(rec, args):
 # ----------------------------------------------------------------------------------------------
 def _process_seqfile_py(args, paths):
     """The sampler in Python (bz2 inputs; also the readable statement of the rules the native reader follows)."""
+    if args.get("length_classes"):
+        return _process_seqfile_classes_py(args, paths)
     L, nreads = args["read_length"], args["nreads"]
     kept, seen = [], set()
     dups = too_short = low_qual = 0
@@ -402,6 +468,118 @@ def _process_seqfile_py(args, paths):
             if len(kept) == nreads:
                 break
     return (_pack_reads(kept, L) if kept else np.zeros((0, L), np.uint8)), {"sampled": len(kept), "too_short": too_short, "low_qual": low_qual, "dups": dups}
+
+
+def _process_seqfile_classes_py(args, paths):
+    """The same head-take under length classes (args['length_classes'], ascending): a record's L is the largest class length it
+    reaches; below the lowest class it is too short; the quality filter runs over its first L bases and qualities; the duplicate
+    test on the full sequence, as ever.  An accepted read is one row of length_classes[-1] bytes: seq[:L], then 0 bytes."""
+    classes, nreads = args["length_classes"], args["nreads"]
+    stride = classes[-1]
+    kept, seen = [], set()
+    dups = too_short = low_qual = 0
+    with open(paths["tempfile"], "w") as out:
+        for seqfile in args["seqfiles"]:
+            for rec in parse_seqs(open_file(seqfile)):
+                k = class_of_length(classes, len(rec.seq))
+                if k is None:
+                    too_short += 1
+                    continue
+                L = classes[k]
+                if args["filter_dups"] and (rec.seq in seen or rec.reverse_complement() in seen):
+                    dups += 1
+                    continue
+                if quality_filter(rec, dict(args, read_length=L)):
+                    low_qual += 1
+                    continue
+                out.write(">%d\n%s\n" % (len(kept), rec.seq[0:L]))
+                kept.append(rec.seq[0:L])
+                if args["filter_dups"]:
+                    seen.add(rec.seq)
+                if len(kept) == nreads:
+                    break
+            if len(kept) == nreads:
+                break
+    rows = np.zeros((len(kept), stride), np.uint8)
+    for i, s_ in enumerate(kept):
+        rows[i, :len(s_)] = np.frombuffer(s_.encode("latin-1"), np.uint8)
+    return rows, {"sampled": len(kept), "too_short": too_short, "low_qual": low_qual, "dups": dups}
+
+
+def _mixed_sample_search(args, paths):
+    """args['mixed_lengths']: sampler (native, or the Python statement under args['python_reader']) and the class run of the engine
+    (mc_search_files on a class reader / mc_search_classes).  Returns (best hits, their class indices, reads per class, families)."""
+    from . import _native
+    classes = args["length_classes"]
+    if args["verbose"]:
+        print("====Estimating Average Genome Size====")
+        print("Sampling & trimming reads...")
+    model = _model(args.get("model_dir"))
+    fams = model["families"]
+    try:
+        eng = _engines_on(_devices_for(args)[:1], args.get("model_dir"))[0]
+        eng.set_run_classes(classes, {L: model["pars"][str(L)] for L in classes}, fams)
+        eng.set_best_hits_only(not args["verbose"])
+        try:
+            if _native_reader_usable(args):
+                rd = _native.Reader.with_classes(args["seqfiles"], classes, args["nreads"], args["file_type"] == "fastq", args.get("quality_offset") or 0,
+                                                 args["min_quality"], args["mean_quality"], args["max_unknown"], args["filter_dups"])
+                try:
+                    eng.search_files(rd, keep_rows=False, best_only=not args["verbose"])
+                    best, cls, class_reads = eng.class_results()
+                    st = rd.stats()
+                finally:
+                    rd.close()
+            else:
+                rows, st = _process_seqfile_py(args, paths)
+                best, cls, class_reads = eng.search_classes(rows)
+            hit_reads = eng.stats()["reads_with_rows"]
+        finally:
+            eng.set_best_hits_only(False)
+    except _native.ReferenceError_ as e:           # the reference raises here; run_pipeline prints it and returns None
+        raise Exception(str(e))
+    except RuntimeError as error:
+        clean_up(paths)
+        sys.exit("\nDatabase search has exited with the following error:\n%s" % error)
+    if st.get("exhausted"):
+        _bases_cache[tuple(args["seqfiles"])] = st["bases"]
+    if st["sampled"] == 0:
+        clean_up(paths)
+        sys.exit("\nError! No reads remaining after filtering!")
+    args["sampled_reads"] = st["sampled"]
+    args["class_reads"] = [int(x) for x in class_reads[:len(classes)]]
+    if args["verbose"]:
+        print("\t%s reads shorter than %s bp and skipped" % (st["too_short"], classes[0]))
+        print("\t%s low quality reads found and skipped" % st["low_qual"])
+        print("\t%s duplicate reads found and skipped" % st["dups"])
+        print("\t%s reads sampled from seqfile" % st["sampled"])
+        for L, n in zip(classes, args["class_reads"]):
+            print("\t\t%s reads cut to %s bp" % (n, L))
+        print("Searching reads against marker proteins...")
+        print("\t%s reads hit marker proteins" % hit_reads)
+    return best, cls, fams
+
+
+def _run_mixed(args, paths):
+    """The estimate of args['mixed_lengths']: per class the sums of aggregate_hits over that class's best hits (its own aln_stat, in
+    read order), pooled by pooled_ags."""
+    best, cls, fams = _mixed_sample_search(args, paths)
+    if len(best) == 0:
+        clean_up(paths)
+        sys.exit("\nError: No hits to marker proteins - cannot estimate genome size! Rerun program with more reads.")
+    if args["verbose"]:
+        print("Filtering hits...")
+        print("\t%s reads assigned to a marker protein" % len(best))
+    classes = args["length_classes"]
+    sums = [aggregate_hits(dict(args, read_length=L), paths, _BestHits(best[cls == k], fams)) for k, L in enumerate(classes)]
+    args["class_sums"] = sums
+    clean_up(paths)
+    if args["verbose"]:
+        print("Computing average genome size...")
+    est_ags = pooled_ags(_model(args.get("model_dir")), classes, args["class_reads"], sums)
+    if args["verbose"]:
+        print("\t%s bp" % str(round(est_ags, 2)))
+    return est_ags
 
 
 def _native_reader_usable(args):
@@ -760,6 +938,61 @@ def _ags_of_sums(model, read_length, agg_hits, bases):
     return total / wsum
 
 
+def pooled_ags(model, class_len, class_reads, class_sums):
+    """One estimate from reads of several length classes.  Class k holds class_reads[k] sampled reads cut to class_len[k] bases:
+    bases_k = n_k x L_k, and class_sums[k][f] = S_kf is aggregate_hits' statistic of family f over the class's best hits.  With B the
+    sum of bases_k over the classes with n_k > 0, per family (every sum runs over k ASCENDING, the classes with n_k > 0 only):
+        x_f   = sum_k S_kf / coefficient[L_k, f]        (a class without a hit of f adds nothing); families with x_f = 0 are skipped
+        est_f = B / x_f                                 - the bases-weighted harmonic mean of the per-class estimates
+                                                          coefficient / (S_kf / bases_k): between the smallest and the largest of them
+        w_f   = sum_k bases_k x weight[L_k, f] / B
+    then _ags_of_sums' own cut (|est_f - median| < 1.48 MAD) and weighted mean, the families in the order of their first hit (k
+    ascending, then the class's own order).  With ONE class holding reads this is the reference's formula, and _ags_of_sums itself is
+    called: the number is run_pipeline -l L_k's bit for bit."""
+    live = [k for k in range(len(class_len)) if class_reads[k] > 0]
+    if len(live) == 1:
+        k = live[0]
+        return _ags_of_sums(model, class_len[k], class_sums[k], class_reads[k] * class_len[k])
+    estimates, weights = pooled_family_estimates(model, class_len, class_reads, class_sums)
+    spread = mad(list(estimates.values()))
+    centre = median(list(estimates.values()))
+    total = wsum = 0
+    for fam, est in estimates.items():
+        if abs(est - centre) >= spread:
+            continue
+        total += est * weights[fam]
+        wsum += weights[fam]
+    return total / wsum
+
+
+def pooled_family_estimates(model, class_len, class_reads, class_sums):
+    """The per-family part of pooled_ags, as its docstring states it: ({family: est_f}, {family: w_f}), the families in the order of
+    their first hit (k ascending, then the class's own order); families with x_f = 0 are left out."""
+    live = [k for k in range(len(class_len)) if class_reads[k] > 0]
+    bases = {k: class_reads[k] * class_len[k] for k in live}
+    B = 0
+    for k in live:
+        B += bases[k]
+    order = []
+    for k in live:
+        for fam in class_sums[k]:
+            if fam not in order:
+                order.append(fam)
+    estimates, weights = {}, {}
+    for fam in order:
+        x = 0.0
+        for k in live:
+            x += class_sums[k].get(fam, 0) / model["coefficients"]["_".join([str(class_len[k]), fam])]
+        if x == 0:
+            continue
+        estimates[fam] = B / x
+        w = 0.0
+        for k in live:
+            w += bases[k] * model["weights"]["_".join([str(class_len[k]), fam])]
+        weights[fam] = w / B
+    return estimates, weights
+
+
 def estimate_average_genome_size(args, paths, agg_hits):
     """AGS_j = coefficient_j / (hits_j / sampled bp); drop |AGS_j - median| >= 1.48 MAD; weighted mean."""
     if args["verbose"]:
@@ -905,8 +1138,12 @@ def report_results(args, est_ags, count_bases):
                          ("min_quality", args["min_quality"]), ("mean_quality", args["mean_quality"]), ("filter_dups", args["filter_dups"]),
                          ("max_unknown", args["max_unknown"])):
             out.write("%s:\t%s\n" % (key, val))
+        if mixed_lengths_on(args):
+            out.write("length_classes:\t%s\n" % "\t".join(str(L) for L in args["length_classes"]))
         out.write("\nResults\n")
         out.write("%s:\t%s\n" % ("average_genome_size", est_ags))
+        if mixed_lengths_on(args):
+            out.write("class_reads:\t%s\n" % "\t".join(str(n) for n in args["class_reads"]))
         if count_bases:
             out.write("%s:\t%s\n" % ("total_bases", count_bases))
             out.write("%s:\t%s\n" % ("genome_equivalents", count_bases / est_ags))
@@ -968,10 +1205,16 @@ def run_pipeline(args):
     try:
         check_input(args)
         _cap_host_threads(args.get("threads"))     # an explicit args['threads'] (-t) caps the sampler's worker threads
+        if mixed_lengths_on(args):              # every read at the largest legal length it reaches (check_mixed_lengths, pooled_ags)
+            check_mixed_lengths(args)
         impute_missing_args(args)
         check_arguments(args)
         if args["verbose"]:
             print_parameters(args)
+            if mixed_lengths_on(args):
+                print("Length classes: %s\n" % args["length_classes"])
+        if mixed_lengths_on(args):
+            return _run_mixed(args, paths), args
         if paths.get("rapsearch"):
             check_rapsearch(paths["rapsearch"])
         if _native_reader_usable(args) and not args.get("keep_tmp") and not paths.get("rapsearch"):

@@ -127,12 +127,38 @@ def random_community(genome_names, k, members, sigma, seed):
     return [genome_names[i] for i in pick.tolist()], [float(a) for a in abund.tolist()]
 
 
-def check_request(read_lengths, nreads, valid_lengths, where, error_model=None, error_rate=None, paired_end=False, insert=None, reference_lengths=False):
+def parse_length_mix(text):
+    """--length-mix 100:0.5,150:0.5 -> [(100, 0.5), (150, 0.5)], ascending: the length classes of a mixed library and the share of
+    its reads each holds.  Refused: anything else, a length twice, a share that is not positive, shares that do not add up to 1."""
+    mix = []
+    try:
+        for item in text.split(","):
+            L, share = item.split(":")
+            mix.append((int(L), float(share)))
+    except ValueError:
+        raise ValidationError("--length-mix %s: expected L1:share1,L2:share2,..." % text)
+    if len(set(L for L, _ in mix)) != len(mix):
+        raise ValidationError("--length-mix %s names a length twice" % text)
+    if any(not (s > 0 and math.isfinite(s)) for _, s in mix):
+        raise ValidationError("--length-mix %s: every share must be positive" % text)
+    if abs(sum(s for _, s in mix) - 1.0) > 1e-9:
+        raise ValidationError("--length-mix %s: the shares add up to %s, not 1" % (text, sum(s for _, s in mix)))
+    return sorted(mix)
+
+
+def mix_label(length_mix):
+    return "+".join(str(L) for L, _ in length_mix)
+
+
+def check_request(read_lengths, nreads, valid_lengths, where, error_model=None, error_rate=None, paired_end=False, insert=None, reference_lengths=False, length_mix=None):
     """Every refusal of a validation run that needs no genome, before any GPU work."""
     if reference_lengths:
         raise ValidationError("a community library has reads of one length: the reference read lengths (--reference-lengths) are not supported")
-    if not read_lengths:
+    if not read_lengths and not length_mix:
         raise ValidationError("no read length given (-l)")
+    read_lengths = list(read_lengths) + [L for L, _ in length_mix or []]
+    if length_mix and paired_end and any(round(s * nreads) % 2 for _, s in length_mix):
+        raise ValidationError("a paired-end library has an even number of reads: --length-mix gives a class an odd number of -n %d" % nreads)
     for L in read_lengths:
         if L not in valid_lengths:
             raise ValidationError("read length %s is not one the model %s was trained for: %s" % (L, where, list(valid_lengths)))
@@ -161,7 +187,7 @@ def check_request(read_lengths, nreads, valid_lengths, where, error_model=None, 
 def unsigned_error_summary(records):
     """{read length: (median, maximum) of |error|} over the records that have an estimate (optimize_weights.R: mue)."""
     out = {}
-    for L in sorted(set(r["read_length"] for r in records)):
+    for L in sorted(set(r["read_length"] for r in records), key=lambda L: (isinstance(L, str), L)):      # (a --length-mix row: "100+150")
         e = [abs(r["error"]) for r in records if r["read_length"] == L and r["error"] is not None]
         out[L] = (float(np.median(e)), float(max(e))) if e else (None, None)
     return out
@@ -179,8 +205,23 @@ def estimate_of_best_hits(model_dir, read_length, best, families, nreads):
     return mc._ags_or_none(mc._model(model_dir), read_length, agg, nreads * read_length)
 
 
+def estimate_of_mixed_passes(model_dir, length_mix, counts, bests, families):
+    """run_pipeline's mixed-lengths estimate of a library made of one pass per length class: per class aggregate_hits over its best
+    hits, pooled by pooled_ags.  None when no read was classified or no family survives."""
+    from . import microbe_census as mc
+    sums = [mc.aggregate_hits({"model_dir": model_dir, "read_length": L, "verbose": False}, {}, mc._BestHits(b, families)) if len(b) else {}
+            for (L, _), b in zip(length_mix, bests)]
+    # (_ags_or_none's conditions: no bases, no family with a hit, or none that survives the outlier cut)
+    if sum(n * L for n, (L, _) in zip(counts, length_mix)) <= 0 or not any(v != 0 for s in sums for v in s.values()):
+        return None
+    try:
+        return mc.pooled_ags(mc._model(model_dir), [L for L, _ in length_mix], counts, sums)
+    except ZeroDivisionError:
+        return None
+
+
 def validate(genomes_dir, out_dir, read_lengths, nreads, model_dir=None, communities=None, random=0, members=None, sigma=1.0, seed=0, device=0,
-             error_model=None, error_rate=None, paired_end=False, insert=None, write_reads_dir=None, reference_lengths=False, log=print):
+             error_model=None, error_rate=None, paired_end=False, insert=None, write_reads_dir=None, reference_lengths=False, log=print, length_mix=None):
     """Scores a model on mock communities.  communities: community files; random: how many random communities (of `members`
     genomes, log-normal(0, sigma) abundances).  Writes out_dir/validation.map and out_dir/communities/<name>.tsv and returns the
     records: dicts of community, read_length, members, reads, true_ags, est_ags (None without a classified read), error (signed,
@@ -191,7 +232,8 @@ def validate(genomes_dir, out_dir, read_lengths, nreads, model_dir=None, communi
     nreads = int(nreads)
     if model_dir:
         mc.check_model_dir(model_dir)
-    check_request(read_lengths, nreads, mc._valid_read_lengths(model_dir), model_dir or "(packaged)", error_model, error_rate, paired_end, insert, reference_lengths)
+    check_request(read_lengths, nreads, mc._valid_read_lengths(model_dir), model_dir or "(packaged)", error_model, error_rate, paired_end, insert, reference_lengths, length_mix)
+    label = mix_label(length_mix) if length_mix else None
     genomes = training.list_genomes(genomes_dir)
     names = [g for g, _ in genomes]
     if not communities and not random:
@@ -216,7 +258,7 @@ def validate(genomes_dir, out_dir, read_lengths, nreads, model_dir=None, communi
         for g in mem:
             if g not in loaded:
                 loaded[g] = _native.read_fasta_genome(path_of[g])
-    span = insert if paired_end else max(read_lengths)
+    span = insert if paired_end else max(read_lengths + [L for L, _ in length_mix or []])
     for cname, mem, _ in plan:
         if not any(len(loaded[g][1]) > 1 and int(np.max(np.diff(loaded[g][1]))) >= span for g in mem):
             raise ValidationError("community %s has no contig of at least %d bp" % (cname, span))
@@ -246,12 +288,35 @@ def validate(genomes_dir, out_dir, read_lengths, nreads, model_dir=None, communi
                                                                      "NA" if est is None else "%+.4f" % rec["error"]))
                 if write_reads_dir:
                     training.write_reads(os.path.join(write_reads_dir, "%s_%d.fa.gz" % (cname, L)), comm.simulate(L, nreads, seed, lid), paired_end)
+            if length_mix:
+                # a library of mixed lengths: one pass per class with round(share x n) reads and a library id of its own, the passes
+                # combined as run_pipeline's mixed_lengths combines the classes of a file
+                counts, bests = [], []
+                drawn[label] = np.zeros(len(mem), np.int64)
+                for L, share in length_mix:
+                    n_k = int(round(share * nreads))
+                    counts.append(n_k)
+                    if n_k == 0:
+                        bests.append(np.zeros(0, _native.BEST_DTYPE))
+                        continue
+                    eng.set_run(L, model["pars"][str(L)], fams)
+                    lid = training.library_id("%s|%s" % (cname, label), L)
+                    bests.append(eng.community_library(comm, n_k, seed, lid))
+                    drawn[label] += comm.member_reads()
+                    if write_reads_dir:                            # the mixed library, one file per class
+                        training.write_reads(os.path.join(write_reads_dir, "%s_%s_%d.fa.gz" % (cname, label, L)), comm.simulate(L, n_k, seed, lid), paired_end)
+                est = estimate_of_mixed_passes(model_dir, length_mix, counts, bests, fams)
+                rec = {"community": cname, "read_length": label, "members": len(mem), "reads": sum(counts), "true_ags": truth, "est_ags": est,
+                       "error": None if est is None else (est - truth) / truth, "member_reads": drawn[label].tolist(), "class_reads": counts}
+                records.append(rec)
+                log("  %s L=%s: true %.2f, estimated %s, error %s" % (cname, label, truth, "NA" if est is None else "%.2f" % est, "NA" if est is None else "%+.4f" % rec["error"]))
         finally:
             comm.close()
         with open(os.path.join(out_dir, "communities", cname + ".tsv"), "w") as f:
-            f.write("\t".join(["genome", "copies", "size"] + ["reads_%d" % L for L in read_lengths]) + "\n")
+            cols = read_lengths + ([label] if length_mix else [])
+            f.write("\t".join(["genome", "copies", "size"] + ["reads_%s" % L for L in cols]) + "\n")
             for i, g in enumerate(mem):
-                f.write("\t".join([g, str(copies[i]), str(sizes[i])] + [str(int(drawn[L][i])) for L in read_lengths]) + "\n")
+                f.write("\t".join([g, str(copies[i]), str(sizes[i])] + [str(int(drawn[L][i])) for L in cols]) + "\n")
     summary = unsigned_error_summary(records)
     with open(os.path.join(out_dir, "validation.map"), "w") as f:
         f.write("\t".join(["community", "read_length", "members", "reads", "true_ags", "est_ags", "error"]) + "\n")
@@ -259,7 +324,7 @@ def validate(genomes_dir, out_dir, read_lengths, nreads, model_dir=None, communi
             f.write("\t".join([r["community"], str(r["read_length"]), str(r["members"]), str(r["reads"]), repr(r["true_ags"]),
                                "NA" if r["est_ags"] is None else repr(r["est_ags"]), "NA" if r["error"] is None else repr(r["error"])]) + "\n")
         for L, (med, worst) in summary.items():
-            line = "read length %d: median unsigned error %s, maximum %s" % (L, "NA" if med is None else "%.4f" % med, "NA" if worst is None else "%.4f" % worst)
+            line = "read length %s: median unsigned error %s, maximum %s" % (L, "NA" if med is None else "%.4f" % med, "NA" if worst is None else "%.4f" % worst)
             f.write("# " + line + "\n")
             log(line)
     return records

@@ -38,6 +38,10 @@ def parse_arguments(argv=None):
     p.add_argument("--model", dest="model_dir", type=str, default=None, help="directory of a trained model (markers.faa.gz, model.json: scripts/train_microbe_census.py) to use instead of the packaged one")
     p.add_argument("--bootstrap", dest="bootstrap", type=int, default=0, metavar="B", help="report the sampling error of the estimate from B Poisson-bootstrap replicates of the sampled reads (standard error and 95%% interval; default = 0: off)")
     p.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=0, metavar="S", help="seed of the bootstrap (default = 0)")
+    p.add_argument("--mixed-lengths", dest="mixed_lengths", nargs="?", const=True, default=None, metavar="L1,L2,...",
+                   type=lambda v: [int(x) for x in v.split(",")],
+                   help="estimate from every read at the largest of the model's read lengths it reaches, instead of cutting all reads to one length and dropping the shorter ones; "
+                        "the optional list names the length classes (default: the model's lengths that at least 1%% of the first 10,000 reads fall in)")
     p.add_argument("--curve", dest="curve", type=int, default=0, metavar="K", help="report the estimate at K nested prefixes of the sample: what -n n_k would have returned (default = 0: off)")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")

@@ -28,7 +28,10 @@ def parse_arguments(argv=None):
     p.add_argument("--random", dest="random", type=int, default=0, help="number of random communities")
     p.add_argument("--members", dest="members", type=int, default=None, help="genomes per random community")
     p.add_argument("--sigma", dest="sigma", type=float, default=1.0, help="sigma of the random communities' log-normal abundances (default 1)")
-    p.add_argument("-l", dest="read_lengths", required=True, help="read lengths, comma separated (ones the model was trained for)")
+    p.add_argument("-l", dest="read_lengths", default="", help="read lengths, comma separated (ones the model was trained for)")
+    p.add_argument("--length-mix", dest="length_mix", default=None, metavar="L1:s1,L2:s2,...",
+                   help="also score libraries of mixed lengths, e.g. 100:0.5,150:0.5: per community one pass per length with round(share x n) reads, "
+                        "combined as run_microbe_census.py --mixed-lengths combines them (validation.map rows with read_length 100+150)")
     p.add_argument("-n", dest="nreads", type=int, required=True, help="reads per simulated metagenome")
     p.add_argument("--seed", dest="seed", type=int, default=0, help="seed of the communities and of the read simulator (default 0)")
     p.add_argument("-g", dest="device", type=int, default=0, help="GPU index (default 0)")
@@ -43,6 +46,13 @@ def parse_arguments(argv=None):
         args.read_lengths = [int(x) for x in args.read_lengths.split(",") if x.strip()]
     except ValueError:
         p.error("-l takes integers separated by commas")
+    if not args.read_lengths and not args.length_mix:
+        p.error("give -l, --length-mix or both")
+    if args.length_mix:
+        try:
+            args.length_mix = validation.parse_length_mix(args.length_mix)
+        except validation.ValidationError as e:
+            p.error(str(e))
     if args.communities and args.random:
         p.error("--communities and --random exclude each other")
     return args
@@ -53,7 +63,8 @@ def main(argv=None):
     try:
         validation.validate(a.genomes_dir, a.out_dir, a.read_lengths, a.nreads, model_dir=a.model_dir, communities=a.communities, random=a.random,
                             members=a.members, sigma=a.sigma, seed=a.seed, device=a.device, error_model=a.error_model, error_rate=a.error_rate,
-                            paired_end=a.paired_end, insert=a.insert, write_reads_dir=a.write_reads, reference_lengths=a.reference_lengths)
+                            paired_end=a.paired_end, insert=a.insert, write_reads_dir=a.write_reads, reference_lengths=a.reference_lengths,
+                            length_mix=a.length_mix)
     except (validation.ValidationError, training.TrainingError) as e:
         sys.exit("Error: %s" % e)
 
