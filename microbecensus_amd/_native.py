@@ -912,8 +912,8 @@ class Engine:
         self._check(self.lib.mc_run_range(self.h, first, count, first_read_id), "mc_run_range")
 
     def debug_stage(self, what):
-        """Test aid: what a stage of the last run_range() left on the device (0 frames, 1 seed hits, 2 gap tasks, 3 HSP pool) as a
-        (records, record_bytes) uint8 array."""
+        """Test aid: what a stage of the last run_range() left on the device (0 frames, 1 seed hits, 2 gap tasks, 3 HSP pool, 4 the
+        gapped chain's three counts: gap_counts()) as a (records, record_bytes) uint8 array."""
         rec = C.c_int32(0)
         n = self.lib.mc_debug_stage(self.h, what, None, 0, C.byref(rec))
         if n < 0:
@@ -922,6 +922,12 @@ class Engine:
         if n and self.lib.mc_debug_stage(self.h, what, buf.ctypes.data_as(C.c_void_p), n, C.byref(rec)) != n:
             raise RuntimeError("mc_debug_stage failed: %s" % self.lib.mc_last_error().decode())
         return buf.reshape(-1, rec.value) if rec.value else buf
+
+    def gap_counts(self):
+        """Test aid: the counts of the gapped extension's chain of kernels in the last run_range() (defined when it ran unsplit:
+        stats()["range_splits"] == 0) - the distinct flanks, those sent to the second window, those sent to full-size rows."""
+        v = self.debug_stage(4).reshape(-1).view("<u4")
+        return {"flanks": int(v[0]), "second_window": int(v[1]), "full_size": int(v[2])}
 
     def rows(self, copy=True):
         """m8 rows of the last run (structured array).  copy=False returns a view of the handle's buffer, valid until the next call."""

@@ -168,9 +168,14 @@ __global__ void __launch_bounds__(256) k_gap_emit(const McTables *__restrict__ T
 }
 
 #define MC_GAP_W 1200   // columns of the full-size DP workspace (markers are <= 1183 aa, checked in mc_open)
+#ifndef MC_GAP_WIN      // (a test builds the library with small windows so that ordinary flanks take the second launch and the full-size rows)
 #define MC_GAP_WIN 36   // columns of the LDS window of the first launch (18 KB per wave: eight waves per CU; per 1 M reads of 150 / 300 bp, first + second launch:
                         // 40 columns x 7 waves 2.00 + 0.41 / 9.49 + 1.05 ms, 36 x 8: 1.73 + 0.44 / 8.19 + 1.64, 32 x 9: 1.85 + 0.81 / 8.43 + 5.89)
+#endif
+#ifndef MC_GAP_WIN2     // (the same test)
 #define MC_GAP_WIN2 64  // ... of the second one, for the flanks whose band left the first (32 KB per wave)
+#endif
+static_assert(MC_GAP_WIN >= 16 && MC_GAP_WIN <= MC_GAP_WIN2, "row 0 of a flank has jEnd + 1 = 16 columns (xdrop_gapped 26.98: mc_gap_begin), and the second window is no narrower than the first");
 #define MC_GAP_LANES2 64 // lanes of a wave that take flanks in the second launch (per 1 M reads of 300 bp behind a 36-column first launch: 16 lanes 1.65 ms, 32: 1.43, 64: 0.93)
 
 __device__ __forceinline__ McFlankOut mc_flank_out(const McGapResult &R)

@@ -944,12 +944,23 @@ extern "C" int mc_ranges_in_flight(const mc_handle *h) { return h ? h->pipe_nout
 // hits (McSeedTask, 16 bytes; read = MC_TASK_NONE: padding of a block of the pool), 2 the gap tasks (McGapTask, 28 bytes), 3 the HSP
 // pool (McHsp, 48 bytes: the ungapped HSPs of k_eval_seeds and those of the gapped stage).  Returns the bytes there are (copied if
 // they fit cap_bytes), -1 on error.
+// 4: the counts of the gapped chain (stage B), three uint32 - the distinct flanks (C_ITEMS), those sent to the second window
+// (C_RETRY), those sent to full-size rows (C_RETRY2) - from the host copy of the counters that ended the range: only stage_b's
+// kernels touch these three, and the block is cleared by the next range's stage A.  Defined for a range that ran unsplit (after a
+// split they are the last piece's).
 extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap_bytes, int32_t *record_bytes)
 {
-    if (!h || !h->run_set || what < 0 || what > 3) { g_err = "mc_debug_stage: bad argument"; return -1; }
+    if (!h || !h->run_set || what < 0 || what > 4) { g_err = "mc_debug_stage: bad argument"; return -1; }
     if (h->pipe_nout) { g_err = "mc_debug_stage: ranges are in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     const McCtx &c = h->ctx;
+    if (what == 4) {
+        if (!c.h_c) { g_err = "mc_debug_stage: no range has run"; return -1; }
+        const uint32_t v[3] = {c.h_c[C_ITEMS], c.h_c[C_RETRY], c.h_c[C_RETRY2]};
+        if (record_bytes) *record_bytes = (int32_t)sizeof(uint32_t);
+        if (dst && (int64_t)sizeof v <= cap_bytes) memcpy(dst, v, sizeof v);
+        return (int64_t)sizeof v;
+    }
     const void *src = nullptr; int64_t bytes = 0; int32_t rec = 0;
     if (what == 0) { src = c.d_frames; rec = h->FP; bytes = c.n * 6 * (int64_t)h->FP; }
     else if (what == 1) { src = c.d_tasks; rec = (int32_t)sizeof(McSeedTask); bytes = (int64_t)c.ntasks * rec; }

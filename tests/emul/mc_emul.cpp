@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <fstream>
 #include <iostream>
+#include <tuple>
 
 static bool read_fasta(const char *path, std::vector<std::string> &names, std::vector<std::string> &seqs)
 {
@@ -356,6 +357,39 @@ int main(int argc, char **argv)
     }
     fprintf(stderr, "gapped window check (W = %d): %ld flanks, %ld leave the window, %ld differ from the full-size form\n", WIN, win_flanks, win_over, win_bad);
     if (win_bad) return 3;
+    {   // The device's unit of work and its chain of three kernels (k_gapped.h).  k_gap_dedupe extends ONE flank per distinct ungapped
+        // segment (mc_gap_same_segment: same read, subject, frame, segment start on both sequences, segment end - which member of a
+        // group leads does not matter: both flanks follow from those six numbers); k_gapped_lds runs the windowed form with W1 columns,
+        // and a flank whose band leaves the window or whose packed path statistics overflow (ws.ovf) again with W2; what fails there
+        // too is left to the full-size rows of k_gapped.  W1, W2: MC_GAP_W1, MC_GAP_W2 in the environment (the product's 36 and 64).
+        const int W1 = getenv("MC_GAP_W1") ? atoi(getenv("MC_GAP_W1")) : 36, W2 = getenv("MC_GAP_W2") ? atoi(getenv("MC_GAP_W2")) : 64;
+        if (W1 < 16 || W1 > W2) { fprintf(stderr, "gapped chain: 16 <= MC_GAP_W1 <= MC_GAP_W2\n"); return 2; }
+        struct Seg { uint32_t read, sidx; int frame, qs, ds, qe; };
+        std::vector<Seg> segs;
+        segs.reserve(gaps.size());
+        for (const McGapTask &g : gaps) segs.push_back(Seg{g.read, g.sidx, (int)(g.chrono >> 25), g.qp - g.qbwd, g.dp - g.qbwd, g.qp + g.L + g.qfwd});
+        auto less = [](const Seg &a, const Seg &b) { return std::tie(a.read, a.sidx, a.frame, a.qs, a.ds, a.qe) < std::tie(b.read, b.sidx, b.frame, b.qs, b.ds, b.qe); };
+        auto same = [](const Seg &a, const Seg &b) { return std::tie(a.read, a.sidx, a.frame, a.qs, a.ds, a.qe) == std::tie(b.read, b.sidx, b.frame, b.qs, b.ds, b.qe); };
+        std::sort(segs.begin(), segs.end(), less);
+        segs.erase(std::unique(segs.begin(), segs.end(), same), segs.end());
+        long ch_flanks = 0, ch_r1 = 0, ch_r2 = 0;
+        auto chain = [&](const uint8_t *s1, const uint8_t *s2, int st, int n1, int n2) {
+            ch_flanks++;
+            HostWin w1(W1);
+            if (!(mc_align_gapped_win(T, s1, st, s2, st, n1, n2, w1, W1).overflow || w1.ovf)) return;
+            ch_r1++;
+            HostWin w2(W2);
+            if (mc_align_gapped_win(T, s1, st, s2, st, n1, n2, w2, W2).overflow || w2.ovf) ch_r2++;
+        };
+        for (const Seg &s : segs) {
+            const uint8_t *q = &frames[((size_t)s.read * 6 + s.frame) * FP]; const int qlen = flen[(size_t)s.read * 6 + s.frame];
+            const uint8_t *d = X.res + X.off[s.sidx]; const int dlen = (int)(X.off[s.sidx + 1] - X.off[s.sidx]);
+            const int dend = s.ds + (s.qe - s.qs);                      // (an ungapped segment: as long on the subject as on the query)
+            if (qlen - s.qe > 2 && dlen - dend > 2) chain(q + s.qe, d + dend, 1, qlen - s.qe, dlen - dend);
+            if (s.qs > 2 && s.ds > 2) chain(q + s.qs - 1, d + s.ds - 1, -1, s.qs, s.ds);
+        }
+        fprintf(stderr, "gapped chain (%d, %d): %ld distinct flanks, %ld to the second window, %ld to full-size rows\n", W1, W2, ch_flanks, ch_r1, ch_r2);
+    }
     // stage 5: sort by (read, subject, chrono)
     std::sort(hsps.begin(), hsps.end(), [](const McHsp &a, const McHsp &b) { if (a.read != b.read) return a.read < b.read; if (a.sidx != b.sidx) return a.sidx < b.sidx; return a.chrono < b.chrono; });
     fprintf(stderr, "hsps kept: %zu\n", hsps.size());

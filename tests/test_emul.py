@@ -5,6 +5,7 @@ import gzip
 import hashlib
 import json
 import os
+import re
 import struct
 import subprocess
 
@@ -211,3 +212,68 @@ def test_heap_words_replay_equals_libstdcxx(tmp_path):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(REPO, "microbecensus_amd", "csrc"), "-o", exe, os.path.join(HERE, "emul", "heap_words_check.cpp")])
     out = subprocess.run([exe], stdout=subprocess.PIPE, check=True).stdout.decode()
     assert "arrays 200000 differ_from_plain 0 differ_from_libstdcxx 0" in out, out
+
+
+CHAIN_RE = re.compile(r"gapped chain \((\d+), (\d+)\): (\d+) distinct flanks, (\d+) to the second window, (\d+) to full-size rows")
+CHECK_RE = re.compile(r"gapped window check \(W = (\d+)\): (\d+) flanks, (\d+) leave the window, (\d+) differ from the full-size form")
+
+
+def run_gapped_chain(exe, faa, fa, out, w1, w2, win=None, dump=None):
+    """One run of the emulation with the chain's windows (w1, w2) and the window check at `win` (default w1).  Returns
+    ((D, R1, R2) of the "gapped chain" line, (flanks, leave, differ) of the "gapped window check" line)."""
+    env = dict(os.environ, MC_GAP_W1=str(w1), MC_GAP_W2=str(w2), MC_GAP_WIN=str(w1 if win is None else win))
+    if dump:
+        env["MC_DUMP_STAGES"] = dump
+    r = subprocess.run([exe, str(faa), str(fa), str(out)], env=env, stderr=subprocess.PIPE)
+    err = r.stderr.decode()
+    assert r.returncode == 0, err[-2000:]
+    m, c = CHAIN_RE.search(err), CHECK_RE.search(err)
+    assert m and c, err[-2000:]
+    assert (int(m.group(1)), int(m.group(2)), int(c.group(1))) == (w1, w2, w1 if win is None else win)
+    return tuple(int(m.group(k)) for k in (3, 4, 5)), tuple(int(c.group(k)) for k in (2, 3, 4))
+
+
+@pytest.fixture(scope="session")
+def chain_reads(tmp_path_factory):
+    d = tmp_path_factory.mktemp("chain")
+    out = {}
+    for case, src in (("config1_example_fq", "config1_example_fq.reads.fa.gz"), ("dirty_reads", "dirty_reads.fa.gz")):
+        out[case] = d / (case + ".fa")
+        out[case].write_bytes(gzip.open(os.path.join(GOLD, src), "rb").read())
+    return out
+
+
+@pytest.fixture(scope="session")
+def chain_counts(emul_bin, markers_faa, chain_reads, tmp_path_factory):
+    """(D, R1, R2) and the window check of both sets at the product's windows and at the small-window build's, computed once."""
+    d = tmp_path_factory.mktemp("chain_out")
+    return {(case, w): run_gapped_chain(emul_bin, markers_faa, fa, d / "o.m8", *w) for case, fa in chain_reads.items() for w in ((36, 64), (16, 24))}
+
+
+@pytest.mark.parametrize("case", ["config1_example_fq", "dirty_reads"])
+def test_gapped_chain_line_of_the_emulation(case, chain_counts):
+    """The device's unit of gapped work - one flank per distinct ungapped segment (`mc_gap_same_segment`) - and the chain of
+    k_gapped.h on it (window W1 with `ws.ovf`, then W2, then full-size rows), counted by the emulation: the numbers
+    tests/test_gpu_gapped_chain.py holds the device's counters against.  At the product's windows (36, 64) and at those of the
+    small-window build (16, 24), where both fallbacks must be busy."""
+    (d, r1, r2), (flanks, leave, differ) = chain_counts[case, (36, 64)]
+    (ds, r1s, r2s), (flanks_s, leave_s, differ_s) = chain_counts[case, (16, 24)]
+    print(case, chain_counts[case, (36, 64)], chain_counts[case, (16, 24)])
+    assert differ == 0 and differ_s == 0
+    assert d == ds and 100 < d <= flanks == flanks_s                  # the distinct flanks do not depend on the windows; every task's two flanks are more
+    assert r2 <= r1 <= min(d, leave) and r2s <= r1s <= min(ds, leave_s)   # (ws.ovf is counted by both lines; deduplicating can only lower a count)
+    assert r1s > 0 and r2s > 0
+    assert r1 <= r1s and r2 <= r2s                                    # a wider window never loses a flank the narrower one held
+
+
+@pytest.mark.parametrize("win", [16, 24, 36, 64])
+@pytest.mark.parametrize("case", ["config1_example_fq", "dirty_reads"])
+def test_windowed_gapped_form_equals_the_full_size_form(case, win, emul_bin, markers_faa, chain_reads, chain_counts, tmp_path):
+    """`mc_align_gapped_win` (what a lane of k_gapped_lds runs) == `mc_align_gapped` (what k_gapped runs) on every flank that stays
+    inside the window, at the four window sizes the two builds of the library use."""
+    if (case, (win, {36: 64, 16: 24}.get(win))) in chain_counts:
+        flanks, leave, differ = chain_counts[case, (win, {36: 64, 16: 24}[win])][1]
+    else:
+        flanks, leave, differ = run_gapped_chain(emul_bin, markers_faa, chain_reads[case], tmp_path / "o.m8", 36, 64, win=win)[1]
+    print(case, win, flanks, leave, differ)
+    assert flanks > 1000 and leave < flanks and differ == 0
