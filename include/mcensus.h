@@ -445,6 +445,35 @@ int mc_set_keep_rows(mc_handle *h, int keep);
  * "reads hit marker proteins" line (verbose). */
 int mc_set_best_hits_only(mc_handle *h, int on);
 
+/* ---- gene abundances: the numerator of RPKG ------------------------------------------------------------------------------------
+ * The reference's README gives the use of genome equivalents in its section "Normalization":
+ *     RPKG = (reads mapped to gene) / (gene length in kb) / (genome equivalents).
+ * The reference leaves "reads mapped to gene" to a search of the user's own; the engine is that search (any protein FASTA of up to
+ * 32,767 sequences of up to 2,047 residues), and these calls count its result per subject on the device, so that no m8 row has to
+ * reach the host.  csrc/k_abundance.h states the rule: a row passes when 100 x nmatch >= min_ident x alnlen, alnlen >= min_aln,
+ * bits >= min_bits and loge <= max_loge; a read's best row is the passing row of the highest bit score, the first on a tie
+ * (classify_reads' `best < score`, microbe_census.py:450); it adds 1 to reads[subject], alnlen to aligned[subject] and 1 to assigned.
+ * searched counts the reads of every range that completed.  All counters are 64-bit integers: exact, whatever the batches, ranges
+ * and launch geometry.
+ * mc_set_abundance(on != 0) zeroes the counters and sets the cut-offs; from then on every range that completes - mc_search,
+ * mc_search_varlen, mc_run / mc_run_range, mc_range_begin + mc_range_end, mc_search_files - adds to them until they are reset.  A
+ * range that overflowed a pool (mc_range_end's -2) adds nothing: the pieces mc_run_range runs it in do, each once.  With
+ * mc_set_keep_rows(h, 0) the rows of such a run stay on the device: mc_result_rows() is empty and nothing but the best hits is copied
+ * to the host.  on == 0 frees the counters and restores the path without them exactly.
+ * Refused, with a message naming the value: min_ident outside 0 .. 100, a negative min_aln, a NaN cut-off, a range in flight, best
+ * hits only switched on (the counts need every row of a read; mc_set_best_hits_only(h, 1) is refused in turn while they are on).
+ * While they are on, mc_search_classes, mc_search_files on a reader of length classes, mc_train_library and mc_community_library are
+ * refused.  mc_search_files_multi keeps one table per handle: the caller adds them (integers). */
+int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t min_aln, double min_bits, double max_loge);
+/* Zeroes the counters and mc_abundance_ms() (README "Normalization": one sample, one table).  Refused while the counts are off. */
+int mc_abundance_reset(mc_handle *h);
+/* The numerators of the README's "Normalization" formula as they stand: reads[s] and aligned[s] per subject s (arrays of
+ * mc_marker_count() values; either may be NULL), the reads searched and the reads assigned.  Refused while the counts are off. */
+int mc_abundance_read(mc_handle *h, int64_t *reads /* [nseq] */, int64_t *aligned /* [nseq] */, int64_t *searched, int64_t *assigned);
+/* Milliseconds the counting kernels took since the last reset (HIP events; one kernel per completed range) - the device cost of the
+ * README's "reads mapped to gene" beside mc_stats.ms_total of the same ranges. */
+float mc_abundance_ms(const mc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,11 @@ def load_library():
     lib.mc_reader_open_classes.argtypes = [C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_char_p]
     lib.mc_reader_stride.restype = C.c_int32
     lib.mc_reader_stride.argtypes = [C.c_void_p]
+    lib.mc_set_abundance.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_double, C.c_double]
+    lib.mc_abundance_reset.argtypes = [C.c_void_p]
+    lib.mc_abundance_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.mc_abundance_ms.restype = C.c_float
+    lib.mc_abundance_ms.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 
@@ -227,7 +232,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_genome_set_read_lengths", "mc_simulate_varlen", "mc_train_library_bases",
                     "mc_community_open", "mc_community_close", "mc_community_set_library", "mc_community_simulate", "mc_community_library", "mc_community_member_reads",
                     "mc_community_times",
-                    "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride"]
+                    "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride",
+                    "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms"]
 
 
 class DupSet:
@@ -879,6 +885,32 @@ class Engine:
             self.lib.mc_set_keep_rows(self.h, 1)
             self.lib.mc_set_best_hits_only(self.h, 0)
         return self.results()
+
+    def set_abundance(self, on=True, min_ident=0, min_aln=0, min_bits=0.0, max_loge=1.0):
+        """Per-gene read counts for RPKG (mc_set_abundance; csrc/k_abundance.h states the rule): from now on every read that is searched
+        adds its best row - among those with identity >= min_ident percent (an integer), alignment length >= min_aln, bit score >=
+        min_bits and log10 E <= max_loge - to the counters of that row's subject.  on=True zeroes the counters; on=False frees them.
+        With search_files(keep_rows=False) no m8 row reaches the host."""
+        if on and (isinstance(min_ident, float) and min_ident != int(min_ident)):
+            raise ValueError("min_ident must be an integer percent (%r given)" % (min_ident,))
+        self._check(self.lib.mc_set_abundance(self.h, 1 if on else 0, int(min_ident), int(min_aln), float(min_bits), float(max_loge)), "mc_set_abundance")
+
+    def abundance_reset(self):
+        """Zeroes the abundance counters and abundance_ms() (mc_abundance_reset)."""
+        self._check(self.lib.mc_abundance_reset(self.h), "mc_abundance_reset")
+
+    def abundance(self):
+        """The counters as they stand (mc_abundance_read): {"reads": int64[nseq], "aligned": int64[nseq], "searched": int, "assigned": int}."""
+        n = len(self.names)
+        reads = np.zeros(n, np.int64); aligned = np.zeros(n, np.int64)
+        searched, assigned = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.mc_abundance_read(self.h, reads.ctypes.data_as(C.c_void_p), aligned.ctypes.data_as(C.c_void_p), C.byref(searched), C.byref(assigned)),
+                    "mc_abundance_read")
+        return {"reads": reads, "aligned": aligned, "searched": int(searched.value), "assigned": int(assigned.value)}
+
+    def abundance_ms(self):
+        """milliseconds the abundance kernels took since the last reset (HIP events)"""
+        return float(self.lib.mc_abundance_ms(self.h))
 
     def upload(self, reads):
         reads = np.ascontiguousarray(reads, dtype=np.uint8)

@@ -1,0 +1,268 @@
+"""Gene abundances in RPKG - the use the reference's README gives for genome equivalents (section "Normalization"):
+
+    RPKG = (reads mapped to gene) / (gene length in kb) / (genome equivalents)
+
+The reads are sampled, filtered and trimmed exactly as run_pipeline does it (same reader, same -n -l -q -m -d -u), searched
+against the user's protein FASTA on the GPU, and counted per gene ON the device (Engine.set_abundance; csrc/k_abundance.h states
+the rule): no m8 row reaches the host.  Numerator and denominator come from the SAME sampled bases:
+
+    genome_equivalents_sampled = sampled_reads x trimmed_length / AGS          (the file's total bases are not used)
+    rpkg = reads / (3 x length_aa / 1000) / genome_equivalents_sampled
+
+The AGS is --ags VALUE, the average_genome_size line of a report (--ags-report FILE), or - by default - run_pipeline on the same
+files with the same options in the same process (the marker engine; the gene engine is a second Engine on the same device)."""
+import gzip
+import math
+import os
+
+import numpy as np
+
+from . import _native, microbe_census
+
+MAX_GENES = 32767         # MC_POST8 (csrc/mc_core.h): the engine's limits on a protein database
+MAX_GENE_LEN = 2047
+
+COLUMNS = ("gene", "length_aa", "reads", "aligned_aa", "rpkg")
+GROUP_COLUMNS = ("group", "genes", "reads", "rpkg")
+
+
+class AbundanceError(Exception):
+    """What run_abundance refuses - before any GPU work."""
+
+
+def read_genes(path):
+    """(names, seqs) of a protein FASTA (plain or .gz): a gene's name is the header's first token.  Refused: an empty FASTA, more than
+    32,767 sequences, a sequence of more than 2,047 residues or of none, duplicate names."""
+    if not os.path.isfile(path):
+        raise AbundanceError("Gene FASTA %s not found" % path)
+    names, seqs = _native.load_markers(path) if not _starts_headless(path) else ([], [])
+    if not names:
+        raise AbundanceError("Gene FASTA %s is empty: it holds no sequence" % path)
+    if len(names) > MAX_GENES:
+        raise AbundanceError("Gene FASTA %s holds %d sequences: more than %d" % (path, len(names), MAX_GENES))
+    seen = set()
+    for nm, sq in zip(names, seqs):
+        if nm in seen:
+            raise AbundanceError("Gene name %s occurs more than once in %s" % (nm, path))
+        seen.add(nm)
+        if len(sq) > MAX_GENE_LEN:
+            raise AbundanceError("Gene %s is %d residues long: longer than %d" % (nm, len(sq), MAX_GENE_LEN))
+        if len(sq) == 0:
+            raise AbundanceError("Gene %s has no residues" % nm)
+    return names, seqs
+
+
+def _starts_headless(path):
+    """True when the first non-empty line of the file is no FASTA header (load_markers would index a list that is not there)."""
+    opener = gzip.open if path.endswith(".gz") else open
+    with opener(path, "rt") as f:
+        for line in f:
+            if line.strip():
+                return not line.startswith(">")
+    return True
+
+
+def read_groups(path, names):
+    """{gene: group} of a TSV of gene and group (lines starting with # and empty lines skipped).  A gene that is not in the FASTA, or
+    that is given two groups, is refused."""
+    known = set(names)
+    out = {}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.rstrip("\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            cols = line.split("\t")
+            if len(cols) < 2 or not cols[0] or not cols[1]:
+                raise AbundanceError("%s line %d: expected gene<TAB>group, found %r" % (path, ln, line))
+            gene, group = cols[0], cols[1]
+            if gene not in known:
+                raise AbundanceError("%s line %d: gene %s is not in the gene FASTA" % (path, ln, gene))
+            if out.get(gene, group) != group:
+                raise AbundanceError("%s line %d: gene %s is given two groups, %s and %s" % (path, ln, gene, out[gene], group))
+            out[gene] = group
+    return out
+
+
+def read_ags_report(path):
+    """The average_genome_size of a report written by report_results (this project's or the reference's: `average_genome_size:\\t<v>`)."""
+    if not os.path.isfile(path):
+        raise AbundanceError("AGS report %s not found" % path)
+    with open(path) as f:
+        for line in f:
+            if line.startswith("average_genome_size:"):
+                txt = line.split(":", 1)[1].strip()
+                try:
+                    return float(txt)
+                except ValueError:
+                    raise AbundanceError("AGS report %s: average_genome_size %r is not a number" % (path, txt))
+    raise AbundanceError("AGS report %s has no average_genome_size line" % path)
+
+
+def check_ags(ags, source):
+    try:
+        v = float(ags)
+    except (TypeError, ValueError):
+        raise AbundanceError("The AGS %r (%s) is not a number" % (ags, source))
+    if not math.isfinite(v) or v <= 0:
+        raise AbundanceError("The AGS %r (%s) is not a positive finite number" % (ags, source))
+    return v
+
+
+def genome_equivalents(sampled_reads, read_length, ags):
+    return sampled_reads * read_length / ags
+
+
+def rpkg(reads, length_aa, ge):
+    """reads / (gene length in kb of nucleotides: 3 x length_aa / 1000) / genome equivalents - float64, one gene or arrays."""
+    return np.asarray(reads, dtype=np.float64) / (3.0 * np.asarray(length_aa, dtype=np.float64) / 1000.0) / float(ge)
+
+
+def group_table(names, reads, rpkgs, group_of):
+    """[(group, genes, reads, rpkg)] in the order the groups first appear in the FASTA; a gene missing from the map is a group of its own
+    name; a group's rpkg is the sum of its members' values, added in FASTA order."""
+    order, acc = [], {}
+    for nm, r, v in zip(names, reads, rpkgs):
+        g = group_of.get(nm, nm)
+        if g not in acc:
+            acc[g] = [0, 0, 0.0]
+            order.append(g)
+        a = acc[g]
+        a[0] += 1
+        a[1] += int(r)
+        a[2] += float(v)
+    return [(g, acc[g][0], acc[g][1], acc[g][2]) for g in order]
+
+
+def header_lines(args, table):
+    h = [("metagenome", ",".join(args["seqfiles"])), ("genes", args["genes"]), ("sampled_reads", table["sampled_reads"]),
+         ("trimmed_length", table["trimmed_length"]), ("min_ident", args["min_ident"]), ("min_aln", args["min_aln"]), ("min_bits", repr(float(args["min_bits"]))),
+         ("average_genome_size", repr(float(table["ags"]))), ("ags_source", table["ags_source"]),
+         ("genome_equivalents_sampled", repr(float(table["genome_equivalents_sampled"]))), ("reads_assigned", table["reads_assigned"])]
+    return ["# %s:\t%s\n" % kv for kv in h]
+
+
+def write_table(path, args, table):
+    with open(path, "w") as out:
+        out.writelines(header_lines(args, table))
+        out.write("\t".join(COLUMNS) + "\n")
+        for nm, ln, r, a, v in zip(table["gene"], table["length_aa"], table["reads"], table["aligned_aa"], table["rpkg"]):
+            out.write("%s\t%d\t%d\t%d\t%s\n" % (nm, ln, r, a, repr(float(v))))
+
+
+def write_groups(path, args, table):
+    with open(path, "w") as out:
+        out.writelines(header_lines(args, table))
+        out.write("# groups:\t%s\n" % args["groups"])
+        out.write("\t".join(GROUP_COLUMNS) + "\n")
+        for g, n, r, v in table["groups"]:
+            out.write("%s\t%d\t%d\t%s\n" % (g, n, r, repr(float(v))))
+
+
+def read_table(path):
+    """(header dict of strings, rows as lists of strings) of a table write_table / write_groups wrote."""
+    header, rows = {}, []
+    with open(path) as f:
+        for line in f:
+            if line.startswith("# "):
+                k, v = line[2:].rstrip("\n").split(":\t", 1)
+                header[k] = v
+            else:
+                rows.append(line.rstrip("\n").split("\t"))
+    return header, rows[1:]
+
+
+PIPELINE_KEYS = ("seqfiles", "nreads", "read_length", "min_quality", "mean_quality", "filter_dups", "max_unknown", "threads", "device", "model_dir", "verbose")
+
+
+def _pipeline_args(args):
+    # (nreads None is run_pipeline's "no cap" and is handed on; any other key that is None is left to impute_missing_args)
+    return {k: (list(args[k]) if k == "seqfiles" else args[k]) for k in PIPELINE_KEYS if k in args and (args[k] is not None or k == "nreads")}
+
+
+def check_request(args):
+    """Everything that can be refused before any GPU work; returns (names, seqs, group_of, ags or None, ags_source or None)."""
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.get("distributed"):
+        raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
+    for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None)):
+        args.setdefault(key, default)
+    if args["ags"] is not None and args["ags_report"] is not None:
+        raise AbundanceError("--ags %s and --ags-report %s cannot be combined: one AGS" % (args["ags"], args["ags_report"]))
+    mi = args["min_ident"]
+    if isinstance(mi, bool) or mi != int(mi) or not 0 <= int(mi) <= 100:
+        raise AbundanceError("--min-ident %s is not an integer percent from 0 to 100" % (mi,))
+    if isinstance(args["min_aln"], bool) or args["min_aln"] != int(args["min_aln"]) or int(args["min_aln"]) < 0:
+        raise AbundanceError("--min-aln %s is not a non-negative integer" % (args["min_aln"],))
+    if math.isnan(float(args["min_bits"])):
+        raise AbundanceError("--min-bits %s is not a number" % (args["min_bits"],))
+    args["min_ident"], args["min_aln"], args["min_bits"] = int(mi), int(args["min_aln"]), float(args["min_bits"])
+    ags = source = None
+    if args["ags"] is not None:
+        source = "--ags"
+        ags = check_ags(args["ags"], source)
+    names, seqs = read_genes(args["genes"])
+    group_of = read_groups(args["groups"], names) if args["groups"] else None
+    if args["ags_report"] is not None:
+        source = "report %s" % args["ags_report"]
+        ags = check_ags(read_ags_report(args["ags_report"]), source)
+    return names, seqs, group_of, ags, source
+
+
+def run_abundance(args):
+    """args: run_pipeline's keys (seqfiles, nreads, read_length, min_quality, mean_quality, filter_dups, max_unknown, device, model_dir,
+    verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report.  Writes args['outfile'] (and
+    <outfile>.groups.tsv with groups) when it is set; returns (table, args) - table: the columns as arrays (gene, length_aa, reads,
+    aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
+    names, seqs, group_of, ags, source = check_request(args)
+    microbe_census.check_input(args)
+    if ags is None:             # the estimate of the same sample: run_pipeline on the marker engine, same files, same options
+        est = microbe_census.run_pipeline(_pipeline_args(args))
+        if est is None:
+            raise AbundanceError("run_pipeline gave no AGS estimate for %s" % ",".join(args["seqfiles"]))
+        ags, pargs = est
+        source = "run_pipeline"
+        ags = check_ags(ags, source)
+    else:                       # the same imputation run_pipeline makes (file type, quality offset, read length), without a search
+        pargs = _pipeline_args(args)
+        microbe_census._cap_host_threads(pargs.get("threads"))
+        microbe_census.impute_missing_args(pargs)
+        microbe_census.check_arguments(pargs)
+    L = int(pargs["read_length"])
+    rd = _native.Reader(pargs["seqfiles"], L, pargs["nreads"], pargs["file_type"] == "fastq", pargs.get("quality_offset") or 0,
+                        pargs["min_quality"], pargs["mean_quality"], pargs["max_unknown"], pargs["filter_dups"])
+    eng = None
+    try:
+        eng = _native.Engine(device=int(args.get("device") or 0), names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
+        eng.set_run(L)
+        eng.set_abundance(True, min_ident=args["min_ident"], min_aln=args["min_aln"], min_bits=args["min_bits"])
+        try:
+            eng.search_files(rd, keep_rows=False)
+        except _native.ReferenceError_ as e:
+            raise AbundanceError(str(e))
+        ab = eng.abundance()
+        args["abundance_ms"], args["search_ms"] = eng.abundance_ms(), eng.stats()["ms_total"]
+        st = rd.stats()
+    finally:
+        rd.close()
+        if eng is not None:
+            eng.close()
+    sampled = int(st["sampled"])
+    if sampled == 0:
+        raise AbundanceError("No reads remaining after filtering")
+    if "sampled_reads" in pargs and int(pargs["sampled_reads"]) != sampled or ab["searched"] != sampled:
+        raise AbundanceError("the gene search saw %d reads (%d sampled), the AGS estimate %s" % (ab["searched"], sampled, pargs.get("sampled_reads")))
+    for k in ("file_type", "quality_offset", "read_length", "nreads", "min_quality", "mean_quality", "filter_dups", "max_unknown"):
+        if k in pargs:
+            args[k] = pargs[k]
+    args["sampled_reads"] = sampled
+    length_aa = np.array([len(s) for s in seqs], np.int64)
+    ge = genome_equivalents(sampled, L, ags)
+    table = {"gene": list(names), "length_aa": length_aa, "reads": ab["reads"], "aligned_aa": ab["aligned"], "rpkg": rpkg(ab["reads"], length_aa, ge),
+             "sampled_reads": sampled, "trimmed_length": L, "ags": ags, "ags_source": source, "genome_equivalents_sampled": ge, "reads_assigned": ab["assigned"]}
+    if group_of is not None:
+        table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of)
+    if args.get("outfile"):
+        write_table(args["outfile"], args, table)
+        if group_of is not None:
+            write_groups(args["outfile"] + ".groups.tsv", args, table)
+    return table, args

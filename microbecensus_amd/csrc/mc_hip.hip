@@ -14,6 +14,7 @@
 //   k_classes.h            padded read rows sorted into length classes and trimmed (mc_search_classes)
 //   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
 //   k_wfit.h               the fit of the per-family weights, training step 5 (mc_fit_weights, mc_weights_mue)
+//   k_abundance.h          per-gene read counts for RPKG, summed over the rows of every completed range (mc_set_abundance)
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
 // ranges from a host-side source (mc_search, mc_search_files, mc_search_files_multi) with upload and search overlapped.
@@ -31,6 +32,7 @@
 #include "k_classes.h"
 #include "k_bootstrap.h"
 #include "k_wfit.h"
+#include "k_abundance.h"
 
 #include <map>
 
@@ -84,6 +86,10 @@ struct mc_handle {
     int64_t train_bases = 0;              // mc_train_library: the bases of the last library's reads (mc_train_library_bases)
     float boot_ms = 0;                    // mc_bootstrap: the two kernels of the last call (HIP events)
     float wfit_ms = 0;                    // mc_fit_weights / mc_weights_mue: the kernels of the last call (HIP events)
+    // mc_set_abundance: the cut-offs, the (nseq + 1) x 2 device counters ([s]: reads, aligned of subject s; [nseq][0]: assigned), the reads
+    // of the completed ranges, the kernels' time since the last reset and the two events around the kernel of a range
+    bool abund = false; McAbundPars abund_pars = {}; unsigned long long *d_abund = nullptr; int64_t abund_searched = 0; float abund_ms = 0;
+    hipEvent_t ev_abund[2] = {nullptr, nullptr};
     uint8_t *stage_pin[2] = {}, *stage_dev[2] = {}; size_t stage_bytes = 0; hipStream_t copy_stream = nullptr;   // run_stream
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -151,6 +157,8 @@ extern "C" void mc_close(mc_handle *h)
     for (hipStream_t q : {h->side, h->side2}) if (q) (void)hipStreamDestroy(q);
     if (h->rows_stream) { (void)hipStreamSynchronize(h->rows_stream); (void)hipStreamDestroy(h->rows_stream); }
     if (h->ev_rows) (void)hipEventDestroy(h->ev_rows);
+    if (h->d_abund) (void)hipFree(h->d_abund);
+    for (hipEvent_t e : h->ev_abund) if (e) (void)hipEventDestroy(e);
     for (mc_row *p : h->pin_slot) if (p) (void)hipHostFree(p);
     delete h;
 }
@@ -757,11 +765,15 @@ static int stage_d(mc_handle *h, McCtx &c)
     return counters_to_host(c);
 }
 
+// the rows of a range stay on the device: mc_train_library and the class runs, and the abundance counts when nobody asked for the rows
+// (mc_set_abundance with mc_set_keep_rows(h, 0): the kernel has read them where they lie)
+static bool rows_stay(const mc_handle *h) { return h->rows_stay || (h->abund && !h->keep_rows); }
+
 // E: rows (final order and ABI layout: McRow == mc_row) and best hits into pinned host memory
 static int stage_e(mc_handle *h, McCtx &c)
 {
     hipStream_t st = c.stream;
-    if (c.nrows && !h->rows_stay) HIPCK(hipMemcpyAsync(h->pin_rows, c.d_rows, sizeof(McRow) * c.nrows, hipMemcpyDeviceToHost, h->rows_stream));   // (the range's stream has been waited for: d_rows is final)
+    if (c.nrows && !rows_stay(h)) HIPCK(hipMemcpyAsync(h->pin_rows, c.d_rows, sizeof(McRow) * c.nrows, hipMemcpyDeviceToHost, h->rows_stream));   // (the range's stream has been waited for: d_rows is final)
     if (c.nbest) HIPCK(hipMemcpyAsync(c.h_best, c.d_best, sizeof(McBestHit) * c.nbest, hipMemcpyDeviceToHost, st));
     return 0;
 }
@@ -856,7 +868,16 @@ static int range_end(mc_handle *h, McCtx &c)
     if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
     h->pin_cur ^= 1; h->pin_rows = h->pin_slot[h->pin_cur]; h->pin_cap = h->pin_slot_cap[h->pin_cur];   // (the other slot may still be receiving the rows of the run before)
     c.nrows = (c.nh && !h->best_only) ? c.h_c[C_ROWS] : 0u; c.nsegs = c.h_c[C_SEGS]; c.nbest = c.h_c[C_BEST];
-    if ((size_t)c.nrows > h->pin_cap && !h->rows_stay) {         // grow the pinned row buffer
+    // the abundance counts of the range: its rows are final and none of its pools overflowed - a range that did has returned above
+    // and counts nothing; the pieces mc_run_range cuts it into come through here one by one, each once
+    const bool abund = h->abund && !h->best_only;
+    if (abund) {
+        HIPCK(hipEventRecord(h->ev_abund[0], c.stream));
+        const uint32_t nr = std::min(c.nrows, c.cap_rows);
+        if (nr) k_abundance<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund);
+        HIPCK(hipEventRecord(h->ev_abund[1], c.stream));
+    }
+    if ((size_t)c.nrows > h->pin_cap && !rows_stay(h)) {         // grow the pinned row buffer
         (void)hipStreamSynchronize(h->rows_stream);                  // (the copy of the run before writes into the other buffer: let it finish before anything is freed)
         const size_t want = (size_t)c.nrows + c.nrows / 4 + 1024;
         mc_row *nb = nullptr;
@@ -874,9 +895,10 @@ static int range_end(mc_handle *h, McCtx &c)
     }
     rc = stage_e(h, c);
     if (rc) { (void)hipStreamSynchronize(c.stream); (void)hipStreamSynchronize(h->rows_stream); return rc; }
-    if (c.nrows && !h->rows_stay) { HIPCK(hipEventRecord(h->ev_rows, h->rows_stream)); h->rows_pending = true; h->rows_ever = true; }
+    if (c.nrows && !rows_stay(h)) { HIPCK(hipEventRecord(h->ev_rows, h->rows_stream)); h->rows_pending = true; h->rows_ever = true; }
     if ((rc = stage_wait(c)) != 0) return rc;
-    h->res_rows = h->rows_stay ? nullptr : h->pin_rows; h->n_res_rows = h->rows_stay ? 0 : (int64_t)c.nrows;
+    if (abund) { h->abund_searched += c.n; h->abund_ms += ev_ms(h->ev_abund[0], h->ev_abund[1]); }
+    h->res_rows = rows_stay(h) ? nullptr : h->pin_rows; h->n_res_rows = rows_stay(h) ? 0 : (int64_t)c.nrows;
     h->best_from = &c; h->best_count = c.nbest;                  // (mc_result_best_hits / whoever needs them: best_materialize)
 #ifdef MC_EXP_TIMING
     { const char *nm[6] = {"staging/other", "append", "lookup", "push", "setup", "expand"}; for (int k = 0; k < 6; k++) fprintf(stderr, "timing %-14s %8.3f Mcycles/wave-avg  %10llu entries\n", nm[k], (double)c.h_stats[4 + k] / 4096.0 / 1e6, c.h_stats[10 + k]); }
@@ -1315,6 +1337,7 @@ static int search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offs
     for (mc_best_hit &b : best) b.read = (int32_t)(first_read_id + perm[(size_t)b.read]);
     std::sort(best.begin(), best.end(), [](const mc_best_hit &x, const mc_best_hit &y) { return x.read < y.read; });
     tot.reads += nshort;
+    if (h->abund) h->abund_searched += nshort;                       // (reads too short to have a frame: searched, no rows - as mc_stats.reads counts them)
     h->res_rows = out.data(); h->n_res_rows = (int64_t)out.size(); h->best.swap(best); h->stats = tot;
     return 0;
 }
@@ -1528,6 +1551,7 @@ static int classes_ready(mc_handle *h, const char *who)
 {
     if (!h || !h->run_set || !h->cls_set) { g_err = std::string(who) + ": mc_set_run_classes() must be called first"; return -1; }
     if (h->pipe_nout) { g_err = std::string(who) + ": ranges begun with mc_range_begin() are still in flight"; return -1; }
+    if (h->abund) { g_err = std::string(who) + ": a class run is refused while abundance counting is on (mc_set_abundance)"; return -1; }
     return 0;
 }
 
@@ -1897,9 +1921,67 @@ extern "C" int mc_set_keep_rows(mc_handle *h, int keep)
 extern "C" int mc_set_best_hits_only(mc_handle *h, int on)
 {
     if (!h) { g_err = "null handle"; return -1; }
+    if (on && h->abund) { g_err = "mc_set_best_hits_only: refused while abundance counting is on - it needs every m8 row of a read (mc_set_abundance)"; return -1; }
     h->best_only = on != 0;
     return 0;
 }
+
+// ---- per-gene read counts for RPKG (the reference README, "Normalization"; csrc/k_abundance.h states the rule) ---------------------
+// The counters live in the handle and accumulate over every range that completes (range_end) until they are reset.
+static int abund_zero(mc_handle *h)
+{
+    HIPCK(hipSetDevice(h->device));
+    HIPCK(hipMemset(h->d_abund, 0, sizeof(unsigned long long) * 2 * ((size_t)h->H.nseq + 1)));
+    h->abund_searched = 0; h->abund_ms = 0.f;
+    return 0;
+}
+
+extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t min_aln, double min_bits, double max_loge)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_abundance: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (!on) {
+        if (h->d_abund) { (void)hipFree(h->d_abund); h->d_abund = nullptr; }
+        for (auto &e : h->ev_abund) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        h->abund = false; h->abund_searched = 0; h->abund_ms = 0.f;
+        return 0;
+    }
+    if (min_ident < 0 || min_ident > 100) { g_err = "mc_set_abundance: min_ident " + std::to_string(min_ident) + " is not a percent from 0 to 100"; return -1; }
+    if (min_aln < 0) { g_err = "mc_set_abundance: min_aln " + std::to_string(min_aln) + " is negative"; return -1; }
+    if (min_bits != min_bits) { g_err = "mc_set_abundance: min_bits is NaN"; return -1; }
+    if (max_loge != max_loge) { g_err = "mc_set_abundance: max_loge is NaN"; return -1; }
+    if (h->best_only) { g_err = "mc_set_abundance: best hits only is on (mc_set_best_hits_only) - abundance needs every m8 row of a read"; return -1; }
+    if (!h->d_abund && dalloc(&h->d_abund, 2 * ((size_t)h->H.nseq + 1))) return -1;
+    for (auto &e : h->ev_abund) if (!e) HIPCK(hipEventCreate(&e));
+    h->abund_pars.min_ident = min_ident; h->abund_pars.min_aln = min_aln; h->abund_pars.min_bits = min_bits; h->abund_pars.max_loge = max_loge;
+    h->abund = true;
+    return abund_zero(h);
+}
+
+extern "C" int mc_abundance_reset(mc_handle *h)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->abund) { g_err = "mc_abundance_reset: abundance counting is off (mc_set_abundance)"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_abundance_reset: a range begun with mc_range_begin() is still in flight"; return -1; }
+    return abund_zero(h);
+}
+
+extern "C" int mc_abundance_read(mc_handle *h, int64_t *reads, int64_t *aligned, int64_t *searched, int64_t *assigned)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->abund) { g_err = "mc_abundance_read: abundance counting is off (mc_set_abundance)"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    const size_t nseq = (size_t)h->H.nseq;
+    std::vector<unsigned long long> tab(2 * (nseq + 1));
+    HIPCK(hipMemcpy(tab.data(), h->d_abund, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // (the kernel of every completed range has been waited for: range_end)
+    for (size_t s = 0; s < nseq; s++) { if (reads) reads[s] = (int64_t)tab[2 * s]; if (aligned) aligned[s] = (int64_t)tab[2 * s + 1]; }
+    if (searched) *searched = h->abund_searched;
+    if (assigned) *assigned = (int64_t)tab[2 * nseq];
+    return 0;
+}
+
+extern "C" float mc_abundance_ms(const mc_handle *h) { return h ? h->abund_ms : 0.0f; }
 
 extern "C" int64_t mc_result_rows(mc_handle *h, const mc_row **rows) { if (!h) return -1; rows_wait(h); *rows = h->res_rows; return h->n_res_rows; }
 extern "C" int64_t mc_result_best_hits(mc_handle *h, const mc_best_hit **hits) { if (!h) return -1; best_materialize(h); *hits = h->best.data(); return (int64_t)h->best.size(); }
@@ -2156,6 +2238,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     if (g->lib.paired_end && (nreads & 1)) { g_err = "a paired-end library has an even number of reads (" + std::to_string(nreads) + " given)"; return -1; }
     if (g->device != h->device) { g_err = "mc_train_library: the genome lies on another device than the handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_train_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
+    if (h->abund) { g_err = "mc_train_library: refused while abundance counting is on (mc_set_abundance)"; return -1; }
     McGridPars G; std::vector<int> order;
     if (grid_pars(h, aln_covs, n_cov, max_pids, n_pid, min_scores, n_score, G, order)) return -1;
     HIPCK(hipSetDevice(h->device));
@@ -2413,6 +2496,7 @@ extern "C" int mc_community_library(mc_handle *h, mc_community *c, int64_t nread
     if (c->lib.paired_end && (nreads & 1)) { g_err = "a paired-end library has an even number of reads (" + std::to_string(nreads) + " given)"; return -1; }
     if (c->device != h->device) { g_err = "mc_community_library: the community lies on another device than the handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_community_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
+    if (h->abund) { g_err = "mc_community_library: refused while abundance counting is on (it runs best hits only; mc_set_abundance)"; return -1; }
     HIPCK(hipSetDevice(h->device));
     const int L = h->read_len;
     if (community_for_len(c, L)) return -1;

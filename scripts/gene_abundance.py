@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Gene abundances in RPKG (the reference README's "Normalization": reads mapped to gene / gene length in kb / genome equivalents)
+from a metagenome and a protein FASTA of the user's genes, counted on the GPU.  The reads are sampled, filtered and trimmed by the
+flags of scripts/run_microbe_census.py; the AGS is --ags, --ags-report, or the estimate of the same sample."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from microbecensus_amd import abundance, microbe_census  # noqa: E402
+
+
+def parse_arguments(argv=None):
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("--model", dest="model_dir", default=None)
+    model_dir = pre.parse_known_args(argv)[0].model_dir
+    if model_dir is not None:
+        microbe_census.check_model_dir(model_dir)
+    p = argparse.ArgumentParser(usage="%s [-options] <seqfiles> <genes.faa[.gz]> <out.tsv>" % os.path.basename(__file__),
+                                description="Per-gene read counts and RPKG of a metagenome against a protein FASTA (GPU search and counting).")
+    p.add_argument("seqfiles", type=str, help="path to input metagenome(s); comma separated; FASTA/FASTQ, optionally gz/bz2")
+    p.add_argument("genes", type=str, help="protein FASTA of the genes (plain or .gz): at most 32,767 sequences of at most 2,047 residues")
+    p.add_argument("outfile", type=str, help="path of the gene table (TSV)")
+    p.add_argument("-v", dest="verbose", action="store_true", default=False, help="print the AGS estimate's progress to stdout")
+    p.add_argument("-n", dest="nreads", type=int, default=2000000, help="number of reads to sample (default = 2000000)")
+    p.add_argument("-t", dest="threads", type=int, default=None, help="cap on the host threads of the read sampler")
+    p.add_argument("-l", dest="read_length", type=int, choices=microbe_census._valid_read_lengths(model_dir), help="trim all reads to this length")
+    p.add_argument("-q", dest="min_quality", type=int, default=-5, help="minimum base-level PHRED quality (default = -5; no filtering)")
+    p.add_argument("-m", dest="mean_quality", type=int, default=-5, help="minimum read-level PHRED quality (default = -5; no filtering)")
+    p.add_argument("-d", dest="filter_dups", action="store_true", default=False, help="filter duplicate reads")
+    p.add_argument("-u", dest="max_unknown", type=int, default=100, help="max percent of unknown bases per read (default = 100)")
+    p.add_argument("-g", dest="device", type=int, default=None, help="GPU index (default: 0)")
+    p.add_argument("--model", dest="model_dir", type=str, default=None, help="directory of a trained model for the AGS estimate instead of the packaged one")
+    p.add_argument("--min-ident", dest="min_ident", type=int, default=0, metavar="P", help="count a read's alignments of at least P percent identity (an integer, 0 - 100; default = 0)")
+    p.add_argument("--min-aln", dest="min_aln", type=int, default=0, metavar="A", help="... of at least A aligned residues (default = 0)")
+    p.add_argument("--min-bits", dest="min_bits", type=float, default=0.0, metavar="S", help="... of a bit score of at least S (default = 0)")
+    p.add_argument("--groups", dest="groups", type=str, default=None, metavar="map.tsv", help="TSV of gene and group: adds <out>.groups.tsv with the groups' sums")
+    p.add_argument("--ags", dest="ags", type=float, default=None, metavar="VALUE", help="average genome size in bp to normalise by")
+    p.add_argument("--ags-report", dest="ags_report", type=str, default=None, metavar="FILE", help="report of run_microbe_census.py (or of the reference) to take the average genome size from")
+    args = vars(p.parse_args(argv))
+    args["seqfiles"] = args["seqfiles"].split(",")
+    for k in ("device", "model_dir", "threads"):
+        if args[k] is None:
+            del args[k]
+    return args
+
+
+if __name__ == "__main__":
+    try:
+        table, args = abundance.run_abundance(parse_arguments())
+    except abundance.AbundanceError as e:
+        sys.exit("Error! %s" % e)
+    print("%d of %d sampled reads assigned to %d of %d genes; table: %s" % (table["reads_assigned"], table["sampled_reads"], int((table["reads"] > 0).sum()),
+                                                                           len(table["gene"]), args["outfile"]))

@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""The measurements of DESIGN.md 13 (GPU box), one process per mode, warm-up first, the two sides of a comparison alternating inside the
+repetition loop, median with min - max.  One JSON line per figure.
+
+    abundance_timing.py kernel               abundance_ms() against stats()["ms_total"] of the same ranges: 1 M reads of 150 bp of bench.py's
+                                             read recipe on the marker database (few hits), and the marker-dense library of
+                                             tests/test_gpu_abundance.py (about 100 rows per read) in ranges of 5,000 reads
+    abundance_timing.py files [--root TREE]  wall time of search_files(keep_rows=False) on a FASTA of the same reads with the counts on and
+                                             off, alternating; --root: the tree whose package and built library are measured - the parent
+                                             commit's has no switch and gives the off side alone
+    abundance_timing.py host                 what the kernel replaces: search_files(keep_rows=True) + numpy counting of the rows on the host,
+                                             against the counts on with keep_rows=False
+--reads (1,000,000), --dense-reads (100,000), --reps (7)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def spread(v):
+    return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "reps": len(v)}
+
+
+def numpy_counts(rows, nseq):
+    """the statement without cut-offs on an mc_row array: the first row of the highest bit score per read"""
+    import numpy as np
+    if len(rows) == 0:
+        return np.zeros(nseq, np.int64)
+    q = rows["query"]
+    first = np.flatnonzero(np.r_[True, q[1:] != q[:-1]])
+    top = np.maximum.reduceat(rows["bits"], first)
+    seg = np.repeat(np.arange(len(first)), np.diff(np.r_[first, len(rows)]))
+    is_top = rows["bits"] == top[seg]
+    pos = np.flatnonzero(is_top)
+    keep = pos[np.r_[True, seg[pos][1:] != seg[pos][:-1]]]
+    return np.bincount(rows["subject"][keep], minlength=nseq).astype(np.int64)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("what", choices=("kernel", "files", "host"))
+    p.add_argument("--root", default=os.path.dirname(HERE))
+    p.add_argument("--reads", type=int, default=1000000)
+    p.add_argument("--dense-reads", type=int, default=100000)
+    p.add_argument("--reps", type=int, default=7)
+    a = p.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
+    import numpy as np
+    from microbecensus_amd import _native, synth
+    L, n = 150, a.reads
+    model = _native.load_model()
+    eng = _native.Engine(device=0)
+    eng.set_run(L, model["pars"][str(L)], model["families"])
+    has_switch = hasattr(eng, "set_abundance")
+    reads = synth.GenomeReads(device="cpu", seed=20261001).single(n, L).numpy()
+    if a.what == "kernel":
+        names, seqs = _native.load_markers()
+        dense = synth.sample_reads(synth.build_genomes(seqs, total_bp=3_000_000, seed=404, marker_gene_fraction=1.0), a.dense_reads, L, seed=405)
+        for label, rd, piece in (("bench reads, marker database", reads, n), ("marker-dense library, ranges of 5,000", dense, 5000)):
+            eng.upload(rd)
+            eng.set_abundance(True)
+            ab, tot, rows = [], [], 0
+            for rep in range(a.reps + 1):
+                eng.abundance_reset()
+                t, rows = 0.0, 0
+                for lo in range(0, len(rd), piece):
+                    eng.run_range(lo, min(piece, len(rd) - lo), lo)
+                    st = eng.stats()
+                    t += st["ms_total"]; rows += st["rows"]
+                    assert st["range_splits"] == 0
+                ab.append(eng.abundance_ms() * 1e6 / len(rd)); tot.append(t * 1e6 / len(rd))
+            got = eng.abundance()
+            eng.set_abundance(False)
+            print(json.dumps({"what": "kernel", "library": label, "reads": len(rd), "rows_per_read": round(rows / len(rd), 2), "assigned": got["assigned"],
+                              "abundance_ms_per_1M_reads": spread(ab[1:]), "range_ms_total_per_1M_reads": spread(tot[1:]),
+                              "share": round(statistics.median(ab[1:]) / statistics.median(tot[1:]), 5)}), flush=True)
+    else:
+        with tempfile.TemporaryDirectory() as d:
+            fa = os.path.join(d, "reads.fa")
+            with open(fa, "wb") as f:
+                for s in range(0, n, 50000):
+                    f.write(b"".join(b">r%d\n%s\n" % (s + i, bytes(r)) for i, r in enumerate(reads[s:s + 50000])))
+
+            def run(on, keep_rows):
+                rd = _native.Reader([fa], L, 10 * n, False, 0, -5, -5, 100, False)
+                try:
+                    if has_switch:
+                        eng.set_abundance(on)
+                    t0 = time.perf_counter()
+                    rows, _ = eng.search_files(rd, keep_rows=keep_rows)
+                    if on:
+                        counts = eng.abundance()["reads"]
+                    elif keep_rows:
+                        counts = numpy_counts(rows, len(eng.names))
+                    else:
+                        counts = None
+                    return 1e3 * (time.perf_counter() - t0), counts
+                finally:
+                    rd.close()
+            if a.what == "files":
+                on, off = [], []
+                for rep in range(a.reps + 1):
+                    if has_switch:
+                        on.append(run(True, False)[0])
+                    off.append(run(False, False)[0])
+                out = {"what": "files", "root": os.path.abspath(a.root), "has_switch": has_switch, "reads": n, "off_wall_ms": spread(off[1:])}
+                if has_switch:
+                    out["on_wall_ms"] = spread(on[1:])
+                print(json.dumps(out), flush=True)
+            else:
+                dev, host = [], []
+                for rep in range(a.reps + 1):
+                    t1, c1 = run(True, False)
+                    t2, c2 = run(False, True)
+                    assert np.array_equal(c1, c2)
+                    dev.append(t1); host.append(t2)
+                print(json.dumps({"what": "host", "reads": n, "device_counts_wall_ms": spread(dev[1:]), "rows_to_host_and_numpy_wall_ms": spread(host[1:])}), flush=True)
+    if has_switch:
+        eng.set_abundance(False)
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
