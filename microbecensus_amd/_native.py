@@ -571,8 +571,46 @@ def read_fasta_genome(path):
     return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), np.array(off, dtype=np.int64)
 
 
-class Genome:
+class _SimSource:
+    """What Genome and Community share: a handle (attribute _HANDLE) on a device-resident source of reads, and the C functions
+    (_SET_LIBRARY, _SIMULATE, _CLOSE) that set its library kind, simulate (n, read_len) reads of it and close it."""
+
+    def set_library(self, error_model=None, error_rate=None, paired_end=False, insert=None):
+        """The kind of library simulate() and the engine's fused pass (Engine.train_library() of a genome, Engine.community_library()
+        of a community) make of this source from now on (mc_genome_set_library, mc_community_set_library): error_model None,
+        'uniform' (error_rate per base) or 'illumina'; paired_end with an insert of at least the read length (rows 2k, 2k + 1 are the
+        mates of fragment k).  No argument: the default, single end without errors."""
+        if error_model not in ERROR_MODELS:
+            raise ValueError("unknown error model %r" % (error_model,))
+        lib = None
+        if error_model is not None or paired_end:
+            lib = C.byref(McLibrary(1 if paired_end else 0, int(insert or 0), ERROR_MODELS[error_model], float(error_rate or 0.0)))
+        self._call(self._SET_LIBRARY, lib)
+
+    def simulate(self, read_len, n, seed, library_id, first=0):
+        out = np.empty((int(n), int(read_len)), dtype=np.uint8)
+        self._call(self._SIMULATE, int(read_len), int(first), int(n), int(seed), int(library_id), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def _call(self, fn, *args):
+        if getattr(self.lib, fn)(getattr(self, self._HANDLE), *args) != 0:
+            raise RuntimeError("%s failed: %s" % (fn, self.lib.mc_last_error().decode()))
+
+    def close(self):
+        if getattr(self, self._HANDLE, None):
+            getattr(self.lib, self._CLOSE)(getattr(self, self._HANDLE))
+            setattr(self, self._HANDLE, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Genome(_SimSource):
     """A genome resident on one device (mc_genome_open): Genome(bases, contig_off) or Genome.from_fasta(path)."""
+    _HANDLE, _SET_LIBRARY, _SIMULATE, _CLOSE = "g", "mc_genome_set_library", "mc_simulate", "mc_genome_close"
 
     def __init__(self, bases, contig_off, device=0):
         lib = load_library()
@@ -590,26 +628,13 @@ class Genome:
         bases, off = read_fasta_genome(path)
         return cls(bases, off, device)
 
-    def set_library(self, error_model=None, error_rate=None, paired_end=False, insert=None):
-        """The kind of library simulate() and Engine.train_library() make of this genome from now on (mc_genome_set_library):
-        error_model None, 'uniform' (error_rate per base) or 'illumina'; paired_end with an insert of at least the read length
-        (rows 2k, 2k + 1 are the mates of fragment k).  No argument: the default, single end without errors."""
-        if error_model not in ERROR_MODELS:
-            raise ValueError("unknown error model %r" % (error_model,))
-        lib = None
-        if error_model is not None or paired_end:
-            lib = C.byref(McLibrary(1 if paired_end else 0, int(insert or 0), ERROR_MODELS[error_model], float(error_rate or 0.0)))
-        if self.lib.mc_genome_set_library(self.g, lib) != 0:
-            raise RuntimeError("mc_genome_set_library failed: %s" % self.lib.mc_last_error().decode())
-
     def set_read_lengths(self, reference):
         """reference=True: the libraries of this genome have seq_sim.py's read lengths, read_len + insertions - deletions
         (mc_genome_set_read_lengths MC_READLEN_REFERENCE); False: every read keeps read_len bases (the default)."""
         self.set_read_length_mode(1 if reference else 0)
 
     def set_read_length_mode(self, mode):
-        if self.lib.mc_genome_set_read_lengths(self.g, int(mode)) != 0:
-            raise RuntimeError("mc_genome_set_read_lengths failed: %s" % self.lib.mc_last_error().decode())
+        self._call("mc_genome_set_read_lengths", int(mode))
 
     def simulate_varlen(self, read_len, n, seed, library_id, first=0):
         """Reads [first, first + n) in the reference read-length mode: (bases uint8, offsets int64 of n + 1)."""
@@ -623,28 +648,12 @@ class Genome:
             raise RuntimeError("mc_simulate_varlen failed: %s" % self.lib.mc_last_error().decode())
         return bases[:int(total)], offsets
 
-    def simulate(self, read_len, n, seed, library_id, first=0):
-        out = np.empty((int(n), int(read_len)), dtype=np.uint8)
-        if self.lib.mc_simulate(self.g, int(read_len), int(first), int(n), int(seed), int(library_id), out.ctypes.data_as(C.c_void_p)) != 0:
-            raise RuntimeError("mc_simulate failed: %s" % self.lib.mc_last_error().decode())
-        return out
 
-    def close(self):
-        if getattr(self, "g", None):
-            self.lib.mc_genome_close(self.g)
-            self.g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Community:
+class Community(_SimSource):
     """A mock community resident on one device (mc_community_open): members = [(bases, contig_off)] of the member genomes, copies = the
     number of cells of each.  Its libraries draw a read from member m with probability proportional to copies[m] x (valid starts of
     m); csrc/mc_simlib.h states the draw."""
+    _HANDLE, _SET_LIBRARY, _SIMULATE, _CLOSE = "c", "mc_community_set_library", "mc_community_simulate", "mc_community_close"
 
     def __init__(self, members, copies, device=0):
         lib = load_library()
@@ -670,40 +679,11 @@ class Community:
         if not self.c:
             raise RuntimeError("mc_community_open failed: %s" % lib.mc_last_error().decode())
 
-    def set_library(self, error_model=None, error_rate=None, paired_end=False, insert=None):
-        """The kind of library simulate() and Engine.community_library() make from now on (mc_community_set_library): as
-        Genome.set_library."""
-        if error_model not in ERROR_MODELS:
-            raise ValueError("unknown error model %r" % (error_model,))
-        lib = None
-        if error_model is not None or paired_end:
-            lib = C.byref(McLibrary(1 if paired_end else 0, int(insert or 0), ERROR_MODELS[error_model], float(error_rate or 0.0)))
-        if self.lib.mc_community_set_library(self.c, lib) != 0:
-            raise RuntimeError("mc_community_set_library failed: %s" % self.lib.mc_last_error().decode())
-
-    def simulate(self, read_len, n, seed, library_id, first=0):
-        out = np.empty((int(n), int(read_len)), dtype=np.uint8)
-        if self.lib.mc_community_simulate(self.c, int(read_len), int(first), int(n), int(seed), int(library_id), out.ctypes.data_as(C.c_void_p)) != 0:
-            raise RuntimeError("mc_community_simulate failed: %s" % self.lib.mc_last_error().decode())
-        return out
-
     def member_reads(self):
         """int64 (M,): the reads of the last simulate() / Engine.community_library() by the member they came from."""
         out = np.zeros(self.M, np.int64)
-        if self.lib.mc_community_member_reads(self.c, out.ctypes.data_as(C.c_void_p)) != 0:
-            raise RuntimeError("mc_community_member_reads failed: %s" % self.lib.mc_last_error().decode())
+        self._call("mc_community_member_reads", out.ctypes.data_as(C.c_void_p))
         return out
-
-    def close(self):
-        if getattr(self, "c", None):
-            self.lib.mc_community_close(self.c)
-            self.c = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _grid_pids(max_pids):

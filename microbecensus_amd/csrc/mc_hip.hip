@@ -8,8 +8,8 @@
 //   k_order.h          C   HSPs binned per read (no global sort), ordered and stacked for the reads that can print
 //   k_finish.h         D   sum statistics, std::sort / heap sort replayed, 500-row cap, classification; rows in m8 order
 //   k_grid.h               the training workflow's grid classification
-//   k_simulate.h           the training workflow's library simulator
-//   k_community.h          the library of a mock community of genomes (mc_community_*)
+//   k_simulate.h           the library simulator of the training workflow and of mock communities: the kernels, the genome's placer
+//   k_community.h          the placer of a mock community of genomes (mc_community_*)
 //   k_varlen.h             reads of mixed lengths bucketed by length (mc_search_varlen)
 //   k_classes.h            padded read rows sorted into length classes and trimmed (mc_search_classes)
 //   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
@@ -125,6 +125,24 @@ template <class Tp> static int dalloc(Tp **p, size_t n)
     HIPCK(hipMalloc((void **)p, n * sizeof(Tp)));
     return 0;
 }
+
+// Scoped owners of what a call makes on the device, so that no return path leaves any of it behind: buffers ...
+struct McDevBuf {
+    std::vector<void *> p;
+    template <class Tp> int get(Tp **x, size_t n) { HIPCK(hipMalloc((void **)x, std::max<size_t>(n, 1) * sizeof(Tp))); p.push_back(*x); return 0; }
+    McDevBuf() = default;
+    McDevBuf(const McDevBuf &) = delete;
+    ~McDevBuf() { for (void *q : p) (void)hipFree(q); }
+};
+// ... and events
+struct McEvents {
+    std::vector<hipEvent_t> e;
+    int make(int n) { for (int k = 0; k < n; k++) { hipEvent_t x; if (hipEventCreate(&x) != hipSuccess) { g_err = "hipEventCreate failed"; return -1; } e.push_back(x); } return 0; }
+    hipEvent_t operator[](int k) const { return e[(size_t)k]; }
+    McEvents() = default;
+    McEvents(const McEvents &) = delete;
+    ~McEvents() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
+};
 
 extern "C" int mc_device_count(void)
 {
@@ -460,12 +478,19 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
     return 0;
 }
 
+// the resident read buffer grown to hold nreads reads of the run's length (capacity in bytes: the read length may change between runs)
+static int reads_reserve(mc_handle *h, int64_t nreads)
+{
+    const int64_t need = nreads * (int64_t)h->read_len + 16;
+    if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
+    return 0;
+}
+
 extern "C" int mc_upload(mc_handle *h, const uint8_t *reads, int64_t nreads)
 {
     if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    const int64_t need = nreads * (int64_t)h->read_len + 16;       // capacity in bytes: the read length may change between runs
-    if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
+    if (reads_reserve(h, nreads)) return -1;
     if (nreads) HIPCK(hipMemcpyAsync(h->d_reads, reads, (size_t)nreads * h->read_len, hipMemcpyHostToDevice, h->ctx.stream));
     HIPCK(hipStreamSynchronize(h->ctx.stream));
     h->reads_dev = h->d_reads; h->nreads = nreads;
@@ -1195,11 +1220,6 @@ extern "C" int mc_search_files(mc_handle *h, mc_reader *r, int64_t first_read_id
 // The reads are bucketed by length on the device (k_varlen.h) and the fixed-length pipeline runs once per bucket, with the tables of
 // that length (mc_fill_tables: the query length enters the E-value through the length adjustment) and the classification length of
 // mc_set_run().  Ranges are numbered by sorted position (bucket start + rank): perm maps them back to the caller's reads.
-struct McVlBuf {
-    std::vector<void *> p;
-    template <class Tp> int get(Tp **x, size_t n) { HIPCK(hipMalloc((void **)x, std::max<size_t>(n, 1) * sizeof(Tp))); p.push_back(*x); return 0; }
-    ~McVlBuf() { for (void *q : p) (void)hipFree(q); }
-};
 
 // the handle runs bucket L from now on: its tables, read length and frame pitch (the pools were sized for the longest bucket)
 static int vl_use_length(mc_handle *h, int L)
@@ -1215,7 +1235,7 @@ static int vl_use_length(mc_handle *h, int L)
 // Buckets the nreads reads at d_bases / d_off (offsets from 0, on the device) by length: d_sorted receives every bucket's reads back to
 // back at its pitch, start[L] the bucket's first sorted position (start[MC_VL_BINS] = nreads), boff[L] its first byte, perm (device)
 // the read index of every sorted position.  Every length has been checked to lie in 1 .. 510 before.
-static int vl_bucket(McVlBuf &B, hipStream_t st, const uint8_t *d_bases, const int64_t *d_off, int64_t nreads, int64_t total, uint8_t **d_sorted,
+static int vl_bucket(McDevBuf &B, hipStream_t st, const uint8_t *d_bases, const int64_t *d_off, int64_t nreads, int64_t total, uint8_t **d_sorted,
                      uint32_t **d_perm, std::vector<uint32_t> &start, std::vector<int64_t> &boff)
 {
     const uint32_t ntiles = (uint32_t)((nreads + MC_VL_TILE - 1) / MC_VL_TILE);
@@ -1272,7 +1292,7 @@ static int search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offs
     const int64_t total = offsets[nreads] - offsets[0];
     std::vector<int64_t> off((size_t)nreads + 1);
     for (int64_t i = 0; i <= nreads; i++) off[(size_t)i] = offsets[i] - offsets[0];
-    McVlBuf B;
+    McDevBuf B;
     uint8_t *d_bases = nullptr, *d_sorted = nullptr; int64_t *d_off = nullptr; uint32_t *d_perm = nullptr;
     if (B.get(&d_bases, (size_t)total + 64) || B.get(&d_off, (size_t)nreads + 1)) return -1;
     hipStream_t st = c.stream;
@@ -1395,7 +1415,7 @@ struct McClSorted { uint8_t *d_sorted = nullptr; uint32_t *d_perm = nullptr; std
 // class's trimmed reads back to back, class k from byte S.G.word0[k] * 16; S.start[k] is the class's first sorted position
 // (start[K]: the rows without a class, start[K + 1] = n), S.d_perm the row index of every sorted position.  ms (ev != nullptr: four
 // events): [0] lengths, classes, scan and scatter, [1] the gather.
-static int cl_prologue(McVlBuf &B, hipStream_t st, const uint8_t *d_rows, int64_t n, int stride, const McClasses &C, McClSorted &S, hipEvent_t *ev = nullptr)
+static int cl_prologue(McDevBuf &B, hipStream_t st, const uint8_t *d_rows, int64_t n, int stride, const McClasses &C, McClSorted &S, hipEvent_t *ev = nullptr)
 {
     const uint32_t ntiles = (uint32_t)((n + MC_CL_TILE - 1) / MC_CL_TILE), nbins = (uint32_t)C.K + 1;
     uint8_t *d_cls = nullptr; uint32_t *d_cnt = nullptr, *d_start = nullptr;
@@ -1442,7 +1462,7 @@ static int classes_batch(mc_handle *h, const uint8_t *d_rows, int64_t n, int64_t
     McCtx &c = h->ctx;
     const McClasses &C = h->cls;
     hipStream_t st = c.stream;
-    McVlBuf B; McClSorted S;
+    McDevBuf B; McClSorted S;
     if (cl_prologue(B, st, d_rows, n, mc_class_stride(C), C, S)) { (void)hipStreamSynchronize(st); return -1; }
     const int64_t nclassed = (int64_t)S.start[(size_t)C.K];
     std::vector<uint32_t> perm((size_t)nclassed);
@@ -1521,7 +1541,7 @@ static int classes_stream(mc_handle *h, const std::function<int64_t(uint8_t *, i
 {
     HIPCK(hipSetDevice(h->device));
     const int64_t B = std::max<int64_t>(1, expect_reads > 0 ? std::min(stream_batch(), expect_reads) : stream_batch()), stride = mc_class_stride(h->cls);   // (expect_reads: the most the source can deliver)
-    McVlBuf buf;
+    McDevBuf buf;
     uint8_t *d_rows = nullptr, *pin = nullptr;
     McClAcc A; memset(&A.tot, 0, sizeof A.tot); memset(A.reads, 0, sizeof A.reads);
     int rc = 0;
@@ -1621,7 +1641,7 @@ extern "C" int64_t mc_debug_classes_prologue(mc_handle *h, const uint8_t *rows, 
     if (stride != mc_class_stride(h->cls)) { g_err = "mc_debug_classes_prologue: stride " + std::to_string(stride) + " is not the top class length"; return -1; }
     HIPCK(hipSetDevice(h->device));
     hipStream_t st = h->ctx.stream;
-    McVlBuf B; McClSorted S;
+    McDevBuf B; McClSorted S;
     uint8_t *d_rows = nullptr;
     const size_t bytes = (size_t)nreads * stride;
     if (B.get(&d_rows, bytes + MC_CL_SLACK)) return -1;
@@ -2015,101 +2035,176 @@ extern "C" int mc_write_m8_named(mc_handle *h, const char *path, int append, con
 }
 
 // ------------------------------------------------------------------------------------------------
-// training: device-resident genomes, simulated libraries, the fused library pass
+// training and mock communities: device-resident sources of reads, simulated libraries, the fused library passes
 // ------------------------------------------------------------------------------------------------
-struct mc_genome {
+// What a genome and a community share: the bases and contig offsets in HBM, the library kind with its error thresholds, and the
+// table of valid starts (made by either for the span at hand).  `noun` names the source in error messages.
+struct McSimSource {
+    const char *noun;
     int device = 0, ncontig = 0;
     std::vector<int64_t> off;                                       // contig offsets (host)
+    McDevBuf mem;                                                   // owns every device buffer of the source
     uint8_t *d_bases = nullptr; int64_t *d_off = nullptr, *d_vstart = nullptr;
-    int vstart_len = 0; int64_t total = 0;                          // the span (read length or insert) d_vstart was made for, and its valid starts
-    mc_library lib = {0, 0, MC_ERR_NONE, 0.0};                      // mc_genome_set_library's kind; d_thr: its error thresholds (mc_simlib.h)
+    int span = 0;                                                   // the span (read length or insert) the tables of valid starts were made for
+    mc_library lib = {0, 0, MC_ERR_NONE, 0.0};                      // mc_*_set_library's kind; d_thr: its error thresholds (mc_simlib.h)
     uint64_t *d_thr = nullptr;
+    explicit McSimSource(const char *n) : noun(n) {}
+    std::string fn(const char *what) const { return "mc_" + std::string(noun) + "_" + what; }
+};
+struct mc_genome : McSimSource {
     int read_lengths = MC_SIM_LEN_FIXED;                            // mc_genome_set_read_lengths
+    mc_genome() : McSimSource("genome") {}
+    McGenomePlacer placer() const { return {d_off, d_vstart, ncontig}; }
+};
+struct mc_community : McSimSource {
+    int M = 0;
+    std::vector<int64_t> copies;                                    // copies per member (host)
+    std::vector<int32_t> mfirst;                                    // member m holds contigs mfirst[m] .. mfirst[m + 1] - 1
+    int64_t *d_total = nullptr; uint64_t *d_cum = nullptr; int32_t *d_mfirst = nullptr;
+    unsigned long long *d_counts = nullptr;                         // reads per member of the pass under way
+    std::vector<int64_t> member_reads;                              // ... of the last simulate / library call
+    mc_community() : McSimSource("community") {}
+    McCommPlacer placer() const { return {d_cum, d_total, d_mfirst, d_vstart, d_off, M, M <= MC_COMM_LDS_M ? 1 : 0, d_counts, nullptr, nullptr, nullptr}; }
 };
 static_assert(MC_ERR_NONE == MC_SIM_ERR_NONE && MC_ERR_UNIFORM == MC_SIM_ERR_UNIFORM && MC_ERR_ILLUMINA == MC_SIM_ERR_ILLUMINA, "one numbering of the error models");
 static bool default_library(const mc_library &l) { return !l.paired_end && l.error_model == MC_ERR_NONE; }
 
-extern "C" mc_genome *mc_genome_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, int32_t device)
+// the checks of mc_*_open that need no device ...
+static int source_args(const McSimSource &s, const uint8_t *bases, const int64_t *contig_off, int32_t ncontig)
 {
-    if (!bases || !contig_off || ncontig < 1) { g_err = "mc_genome_open: bad argument"; return nullptr; }
-    if (contig_off[0] != 0) { g_err = "mc_genome_open: contig_off[0] must be 0"; return nullptr; }
-    for (int i = 0; i < ncontig; i++) if (contig_off[i + 1] < contig_off[i]) { g_err = "mc_genome_open: contig offsets must not decrease"; return nullptr; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "no HIP device visible"; return nullptr; }
-    if (device < 0 || device >= ndev) { g_err = "mc_genome_open: no such device"; return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return nullptr; }
-    mc_genome *g = new mc_genome();
-    g->device = device; g->ncontig = ncontig; g->off.assign(contig_off, contig_off + ncontig + 1);
-    const size_t nb = (size_t)contig_off[ncontig];
-    if (hipMalloc((void **)&g->d_bases, nb + 64) != hipSuccess || hipMalloc((void **)&g->d_off, sizeof(int64_t) * (ncontig + 1)) != hipSuccess ||
-        hipMalloc((void **)&g->d_vstart, sizeof(int64_t) * (ncontig + 1)) != hipSuccess || hipMalloc((void **)&g->d_thr, sizeof(uint64_t) * MC_SIM_NTHR) != hipSuccess ||
-        hipMemcpy(g->d_bases, bases, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(g->d_off, contig_off, sizeof(int64_t) * (ncontig + 1), hipMemcpyHostToDevice) != hipSuccess) {
-        g_err = "mc_genome_open: out of device memory";
-        mc_genome_close(g);
-        return nullptr;
-    }
-    return g;
-}
-
-extern "C" void mc_genome_close(mc_genome *g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    for (void *p : {(void *)g->d_bases, (void *)g->d_off, (void *)g->d_vstart, (void *)g->d_thr}) if (p) (void)hipFree(p);
-    delete g;
-}
-
-// the valid starts of every contig for reads of L bases - fragments of `insert` bases for a paired-end library (prefix sums on
-// the device); refuses a genome without a contig of that span, and an insert shorter than the read
-static int genome_for_len(mc_genome *g, int L)
-{
-    if (g->lib.paired_end && g->lib.insert < L) { g_err = "the insert (" + std::to_string(g->lib.insert) + ") is shorter than the read length (" + std::to_string(L) + ")"; return -1; }
-    const int span = g->lib.paired_end ? g->lib.insert : L;
-    if (g->vstart_len == span) return 0;
-    std::vector<int64_t> vs((size_t)g->ncontig + 1, 0);
-    for (int c = 0; c < g->ncontig; c++) vs[(size_t)c + 1] = vs[(size_t)c] + std::max<int64_t>(0, g->off[(size_t)c + 1] - g->off[(size_t)c] - span + 1);
-    if (vs.back() == 0) {
-        g_err = "the genome has no contig of at least the " + std::string(g->lib.paired_end ? "insert" : "read length") + " (" + std::to_string(span) + " bp)";
-        return -1;
-    }
-    HIPCK(hipMemcpy(g->d_vstart, vs.data(), sizeof(int64_t) * vs.size(), hipMemcpyHostToDevice));
-    g->vstart_len = span; g->total = vs.back();
+    if (!bases || !contig_off || ncontig < 1) { g_err = s.fn("open") + ": bad argument"; return -1; }
+    if (contig_off[0] != 0) { g_err = s.fn("open") + ": contig_off[0] must be 0"; return -1; }
+    for (int i = 0; i < ncontig; i++) if (contig_off[i + 1] < contig_off[i]) { g_err = s.fn("open") + ": contig offsets must not decrease"; return -1; }
     return 0;
 }
-
-extern "C" int mc_genome_set_library(mc_genome *g, const mc_library *lib)
+// ... and the device's: the bases (64 bytes of slack behind them) and the offsets to it, room for the valid starts and the thresholds
+static int source_open(McSimSource &s, const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, int32_t device)
 {
-    if (!g) { g_err = "mc_genome_set_library: bad argument"; return -1; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "no HIP device visible"; return -1; }
+    if (device < 0 || device >= ndev) { g_err = s.fn("open") + ": no such device"; return -1; }
+    if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return -1; }
+    s.device = device; s.ncontig = ncontig; s.off.assign(contig_off, contig_off + ncontig + 1);
+    const size_t nb = (size_t)contig_off[ncontig];
+    if (s.mem.get(&s.d_bases, nb + 64) || s.mem.get(&s.d_off, (size_t)ncontig + 1) || s.mem.get(&s.d_vstart, (size_t)ncontig + 1) || s.mem.get(&s.d_thr, MC_SIM_NTHR) ||
+        hipMemcpy(s.d_bases, bases, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(s.d_off, contig_off, sizeof(int64_t) * (ncontig + 1), hipMemcpyHostToDevice) != hipSuccess) {
+        g_err = s.fn("open") + ": out of device memory";
+        return -1;
+    }
+    return 0;
+}
+template <class S> static void source_close(S *s) { if (s) { (void)hipSetDevice(s->device); delete s; } }
+
+extern "C" mc_genome *mc_genome_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, int32_t device)
+{
+    mc_genome *g = new mc_genome();
+    if (source_args(*g, bases, contig_off, ncontig) || source_open(*g, bases, contig_off, ncontig, device)) { mc_genome_close(g); return nullptr; }
+    return g;
+}
+extern "C" void mc_genome_close(mc_genome *g) { source_close(g); }
+
+static int set_library(McSimSource *s, const char *fn, const mc_library *lib)
+{
+    if (!s) { g_err = std::string(fn) + ": bad argument"; return -1; }
     const mc_library l = lib ? *lib : mc_library{0, 0, MC_ERR_NONE, 0.0};
     if (l.error_model != MC_ERR_NONE && l.error_model != MC_ERR_UNIFORM && l.error_model != MC_ERR_ILLUMINA) { g_err = "unknown error model " + std::to_string(l.error_model); return -1; }
     if (!(l.error_rate >= 0.0 && l.error_rate <= 1.0)) { g_err = "error rate " + std::to_string(l.error_rate) + " outside [0, 1]"; return -1; }
     int64_t longest = 0;
-    for (int c = 0; c < g->ncontig; c++) longest = std::max(longest, g->off[(size_t)c + 1] - g->off[(size_t)c]);
+    for (int c = 0; c < s->ncontig; c++) longest = std::max(longest, s->off[(size_t)c + 1] - s->off[(size_t)c]);
     if (l.paired_end && l.insert < 1) { g_err = "a paired-end library needs a positive insert"; return -1; }
-    if (l.paired_end && l.insert > longest) { g_err = "the genome has no contig of at least the insert (" + std::to_string(l.insert) + " bp)"; return -1; }
+    if (l.paired_end && l.insert > longest) { g_err = "the " + std::string(s->noun) + " has no contig of at least the insert (" + std::to_string(l.insert) + " bp)"; return -1; }
     uint64_t thr[MC_SIM_NTHR];
     mc_sim_thresholds(l.error_model, l.error_rate, thr);
-    HIPCK(hipSetDevice(g->device));
-    HIPCK(hipMemcpy(g->d_thr, thr, sizeof thr, hipMemcpyHostToDevice));
-    g->lib = l;
+    HIPCK(hipSetDevice(s->device));
+    HIPCK(hipMemcpy(s->d_thr, thr, sizeof thr, hipMemcpyHostToDevice));
+    s->lib = l;
+    return 0;
+}
+extern "C" int mc_genome_set_library(mc_genome *g, const mc_library *lib) { return set_library(g, "mc_genome_set_library", lib); }
+extern "C" int mc_community_set_library(mc_community *c, const mc_library *lib) { return set_library(c, "mc_community_set_library", lib); }
+
+// The span of a fragment for reads of L bases: the insert of a paired-end library, else L.  Returns it when the source's tables have to
+// be made for it, 0 when they stand, -1 for an insert shorter than the read.  no_contig(): what a source without a start of that span says.
+static int span_to_make(const McSimSource &s, int L)
+{
+    if (s.lib.paired_end && s.lib.insert < L) { g_err = "the insert (" + std::to_string(s.lib.insert) + ") is shorter than the read length (" + std::to_string(L) + ")"; return -1; }
+    const int span = s.lib.paired_end ? s.lib.insert : L;
+    return s.span == span ? 0 : span;
+}
+static int no_contig(const McSimSource &s, int span)
+{
+    g_err = "the " + std::string(s.noun) + " has no contig of at least the " + std::string(s.lib.paired_end ? "insert" : "read length") + " (" + std::to_string(span) + " bp)";
+    return -1;
+}
+
+// the valid starts of every contig for reads of L bases (prefix sums); refuses a genome without a contig of the span
+static int source_for_len(mc_genome *g, int L)
+{
+    const int span = span_to_make(*g, L);
+    if (span <= 0) return span;
+    std::vector<int64_t> vs((size_t)g->ncontig + 1, 0);
+    for (int c = 0; c < g->ncontig; c++) vs[(size_t)c + 1] = vs[(size_t)c] + std::max<int64_t>(0, g->off[(size_t)c + 1] - g->off[(size_t)c] - span + 1);
+    if (vs.back() == 0) return no_contig(*g, span);
+    HIPCK(hipMemcpy(g->d_vstart, vs.data(), sizeof(int64_t) * vs.size(), hipMemcpyHostToDevice));
+    g->span = span;
+    return 0;
+}
+// the member table for reads of L bases; refuses a community none of whose members has a contig of the span, and a universe of 2^62 or more
+static int source_for_len(mc_community *c, int L)
+{
+    const int span = span_to_make(*c, L);
+    if (span <= 0) return span;
+    std::vector<int64_t> vs((size_t)c->ncontig), total((size_t)c->M);
+    std::vector<uint64_t> cum((size_t)c->M + 1);
+    const int bad = mc_sim_member_table(c->off.data(), c->mfirst.data(), c->copies.data(), c->M, span, vs.data(), total.data(), cum.data());
+    if (bad == 1) return no_contig(*c, span);
+    if (bad) { g_err = "the community's universe (the sum of copies x valid starts) does not stay below 2^62"; return -1; }
+    HIPCK(hipMemcpy(c->d_vstart, vs.data(), sizeof(int64_t) * vs.size(), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(c->d_total, total.data(), sizeof(int64_t) * total.size(), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(c->d_cum, cum.data(), sizeof(uint64_t) * cum.size(), hipMemcpyHostToDevice));
+    c->span = span;
     return 0;
 }
 
-static uint64_t sim_key(uint64_t seed, uint64_t library_id) { return mc_mix64(seed ^ mc_mix64(library_id)); }
+// what the simulate entry points do first: the read length's range, the source's device, its tables for that length
+template <class S> static int simulate_begin(S *s, int read_len)
+{
+    if (read_len < 18 || read_len > 3 * MC_MAXAA) { g_err = "read_len out of range (18..510)"; return -1; }
+    HIPCK(hipSetDevice(s->device));
+    return source_for_len(s, read_len);
+}
 
-static int launch_simulate(const mc_genome *g, int L, uint64_t key, int64_t first, int64_t n, uint8_t *dst, hipStream_t st)
+static uint64_t sim_key(uint64_t seed, uint64_t library_id) { return mc_mix64(seed ^ mc_mix64(library_id)); }
+static McSimKind sim_kind(const McSimSource &s, int L) { return McSimKind{L, s.lib.paired_end ? 1 : 0, s.lib.paired_end ? s.lib.insert : L, s.lib.error_model != MC_ERR_NONE ? 1 : 0}; }
+
+// reads [first, first + n) of the source's library into dst (device), on st
+template <class S> static int launch_simulate(const S *s, int L, uint64_t key, int64_t first, int64_t n, uint8_t *dst, hipStream_t st)
 {
     if (n <= 0) return 0;
-    if (default_library(g->lib)) {
-        k_simulate<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, L, key, first, n, dst);
+    const auto place = s->placer();
+    if (default_library(s->lib)) {
+        k_sim_copy<<<dim3((unsigned)((n + 255) / 256)), dim3(256), place.lds_bytes(), st>>>(s->d_bases, place, L, key, first, n, dst);
     } else {
-        const McSimKind kind = {L, g->lib.paired_end ? 1 : 0, g->lib.paired_end ? g->lib.insert : L, g->lib.error_model != MC_ERR_NONE ? 1 : 0};
-        const size_t lds = (size_t)64 * L + sizeof(uint64_t) * MC_SIM_NTHR;
-        k_simulate_lib<<<dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, kind, g->d_thr, key,
-                                                                           mc_mix64(key ^ MC_SIM_EKEY), first, n, dst);
+        const size_t lds = (size_t)64 * L + sizeof(uint64_t) * MC_SIM_NTHR + place.lds_bytes();
+        k_sim_walk<<<dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st>>>(s->d_bases, place, sim_kind(*s, L), s->d_thr, key, mc_mix64(key ^ MC_SIM_EKEY), first, n, dst);
     }
     HIPCK(hipGetLastError());
+    return 0;
+}
+
+// reads [first, first + n) to the host, in ranges of the streaming batch size, as the fused passes make them
+template <class S> static int simulate_to_host(const S *s, int L, int64_t first, int64_t n, uint64_t key, uint8_t *dst_host, const char *fn)
+{
+    const int64_t B = std::min<int64_t>(n, stream_batch());
+    McDevBuf buf;
+    uint8_t *d = nullptr;
+    if (buf.get(&d, (size_t)(B * L))) return -1;
+    for (int64_t at = 0; at < n; at += B) {
+        const int64_t cnt = std::min(B, n - at);
+        if (launch_simulate(s, L, key, first + at, cnt, d, nullptr)) return -1;
+        if (hipMemcpy(dst_host + at * L, d, (size_t)(cnt * L), hipMemcpyDeviceToHost) != hipSuccess) { g_err = std::string(fn) + ": copy failed"; return -1; }
+    }
     return 0;
 }
 
@@ -2130,10 +2225,11 @@ static int simulate_var(const mc_genome *g, int L, uint64_t key, int64_t first, 
 {
     *total = 0;
     if (n <= 0) return 0;
-    const McSimKind kind = {L, g->lib.paired_end ? 1 : 0, g->lib.paired_end ? g->lib.insert : L, g->lib.error_model != MC_ERR_NONE ? 1 : 0};
+    const McSimKind kind = sim_kind(*g, L);
+    const McGenomePlacer place = g->placer();
     const uint64_t ekey = mc_mix64(key ^ MC_SIM_EKEY);
     const dim3 grid((unsigned)((n + 63) / 64));
-    k_simulate_var<<<grid, dim3(64), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, kind, g->d_thr, key, ekey, first, n, d_lens, nullptr, nullptr);
+    k_simulate_var<<<grid, dim3(64), 0, st>>>(g->d_bases, place, kind, g->d_thr, key, ekey, first, n, d_lens, nullptr, nullptr);
     HIPCK(hipGetLastError());
     std::vector<uint32_t> lens((size_t)n);
     HIPCK(hipMemcpyAsync(lens.data(), d_lens, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -2149,7 +2245,7 @@ static int simulate_var(const mc_genome *g, int L, uint64_t key, int64_t first, 
     }
     k_sim_scan<<<dim3(1), dim3(1024), 0, st>>>(d_lens, n, d_roff);
     HIPCK(hipGetLastError());
-    k_simulate_var<<<grid, dim3(64), 0, st>>>(g->d_bases, g->d_off, g->d_vstart, g->ncontig, kind, g->d_thr, key, ekey, first, n, nullptr, d_roff, d_dst);
+    k_simulate_var<<<grid, dim3(64), 0, st>>>(g->d_bases, place, kind, g->d_thr, key, ekey, first, n, nullptr, d_roff, d_dst);
     HIPCK(hipGetLastError());
     *total = sum;
     return 0;
@@ -2159,13 +2255,11 @@ extern "C" int64_t mc_simulate_varlen(mc_genome *g, int32_t read_len, int64_t fi
                                       int64_t dst_cap, int64_t *offsets)
 {
     if (!g || first < 0 || n < 0 || !offsets) { g_err = "mc_simulate_varlen: bad argument"; return -1; }
-    if (read_len < 18 || read_len > 3 * MC_MAXAA) { g_err = "read_len out of range (18..510)"; return -1; }
-    HIPCK(hipSetDevice(g->device));
-    if (genome_for_len(g, read_len)) return -1;
+    if (simulate_begin(g, read_len)) return -1;
     offsets[0] = 0;
     if (n == 0) return 0;
     const int64_t B = std::min<int64_t>(n, stream_batch()), W = std::min(2 * read_len, 3 * MC_MAXAA);
-    McVlBuf buf;
+    McDevBuf buf;
     uint8_t *d = nullptr; uint32_t *d_lens = nullptr; int64_t *d_roff = nullptr;
     if (buf.get(&d, (size_t)(B * W + 64)) || buf.get(&d_lens, (size_t)B) || buf.get(&d_roff, (size_t)B + 1)) return -1;
     const uint64_t key = sim_key(seed, library_id);
@@ -2186,22 +2280,9 @@ extern "C" int64_t mc_simulate_varlen(mc_genome *g, int32_t read_len, int64_t fi
 extern "C" int mc_simulate(mc_genome *g, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host)
 {
     if (!g || first < 0 || n < 0 || (n > 0 && !dst_host)) { g_err = "mc_simulate: bad argument"; return -1; }
-    if (read_len < 18 || read_len > 3 * MC_MAXAA) { g_err = "read_len out of range (18..510)"; return -1; }
-    HIPCK(hipSetDevice(g->device));
-    if (genome_for_len(g, read_len)) return -1;
-    const int64_t B = std::min<int64_t>(n, stream_batch());
+    if (simulate_begin(g, read_len)) return -1;
     if (n == 0) return 0;
-    uint8_t *d = nullptr;
-    HIPCK(hipMalloc((void **)&d, (size_t)(B * read_len)));
-    const uint64_t key = sim_key(seed, library_id);
-    int rc = 0;
-    for (int64_t at = 0; at < n && rc == 0; at += B) {               // ranges of the streaming batch size, as mc_train_library makes them
-        const int64_t cnt = std::min(B, n - at);
-        rc = launch_simulate(g, read_len, key, first + at, cnt, d, nullptr);
-        if (rc == 0 && hipMemcpy(dst_host + at * read_len, d, (size_t)(cnt * read_len), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "mc_simulate: copy failed"; rc = -1; }
-    }
-    (void)hipFree(d);
-    return rc;
+    return simulate_to_host(g, read_len, first, n, sim_key(seed, library_id), dst_host, "mc_simulate");
 }
 
 // one range of the resident reads through the pipeline with its rows left on the device, then the grid over those rows into the
@@ -2230,6 +2311,24 @@ static int train_range(mc_handle *h, int64_t first, int64_t count, int64_t first
     return 0;
 }
 
+// mc_train_library and mc_community_library run the handle in a mode of their own (best hits only or not, rows left on the device or
+// not); however they return, the caller's mode comes back
+struct McModeGuard {
+    mc_handle *h; bool best_only, rows_stay;
+    McModeGuard(mc_handle *h_, bool best, bool stay) : h(h_), best_only(h_->best_only), rows_stay(h_->rows_stay) { h->best_only = best; h->rows_stay = stay; }
+    McModeGuard(const McModeGuard &) = delete;
+    ~McModeGuard() { h->best_only = best_only; h->rows_stay = rows_stay; }
+};
+
+// one range of a library into the resident read buffer, between the events ev[0] and ev[1] on the handle's stream
+template <class S> static int simulate_resident(mc_handle *h, const S *s, uint64_t key, int64_t at, int64_t cnt, const McEvents &ev)
+{
+    hipStream_t st = h->ctx.stream;
+    if (hipEventRecord(ev[0], st) != hipSuccess || launch_simulate(s, h->read_len, key, at, cnt, h->d_reads, st) || hipEventRecord(ev[1], st) != hipSuccess) return -1;
+    h->reads_dev = h->d_reads; h->nreads = cnt;
+    return 0;
+}
+
 extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint64_t seed, uint64_t library_id, const double *aln_covs, int32_t n_cov,
                                 const int32_t *max_pids, int32_t n_pid, const double *min_scores, int32_t n_score, int64_t *count_hits, int64_t *count_aln, double *count_cov)
 {
@@ -2243,7 +2342,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     if (grid_pars(h, aln_covs, n_cov, max_pids, n_pid, min_scores, n_score, G, order)) return -1;
     HIPCK(hipSetDevice(h->device));
     const int L = h->read_len;
-    if (genome_for_len(g, L)) return -1;
+    if (source_for_len(g, L)) return -1;
     const int nfam = h->nfam;
     const size_t nbins = (size_t)n_cov * n_pid * (MC_GRID_MAXS + 1) * nfam;
     const size_t nout = (size_t)n_cov * n_pid * n_score * nfam;
@@ -2254,31 +2353,25 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     const int64_t B = std::min<int64_t>(nreads, stream_batch());
     const bool ref = g->read_lengths == MC_SIM_LEN_REFERENCE;
     h->train_bases = 0;
-    if (!ref) {
-        // the resident read buffer (mc_upload's) holds one range at a time: the simulator writes it, the search reads it
-        const int64_t need = B * L + 16;
-        if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
-        if (ensure_capacity(h, h->ctx, B)) return -1;
-    }
+    // the resident read buffer (mc_upload's) holds one range at a time: the simulator writes it, the search reads it
+    if (!ref && (reads_reserve(h, B) || ensure_capacity(h, h->ctx, B))) return -1;
     // the reference read-length mode: reads of L + ins - del bases (two passes), bucketed by length, each bucket searched at its length
     // and grid-classified into the same bins (a read lies in one bucket: its best survivor is the one of the whole library)
-    McVlBuf vb;
+    McDevBuf vb;
     uint8_t *d_sim = nullptr; uint32_t *d_lens = nullptr; int64_t *d_roff = nullptr;
     if (ref && (vb.get(&d_sim, (size_t)(B * std::min(2 * L, 3 * MC_MAXAA) + 64)) || vb.get(&d_lens, (size_t)B) || vb.get(&d_roff, (size_t)B + 1))) return -1;
     unsigned long long *d_bins = nullptr;
-    if (hipMalloc((void **)&d_bins, nbins * 24) != hipSuccess) { g_err = "out of device memory"; return -1; }
-    hipEvent_t ev[4] = {};
-    for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { g_err = "hipEventCreate failed"; return -1; }
+    if (vb.get(&d_bins, nbins * 3)) { g_err = "out of device memory"; return -1; }
+    McEvents ev;
+    if (ev.make(4)) return -1;
     hipStream_t st = h->ctx.stream;
-    const bool saved_best_only = h->best_only;
-    h->best_only = false; h->rows_stay = true;                       // (the grid needs every row of a read)
+    McModeGuard mode(h, false, true);                                // (the grid needs every row of a read)
     int rc = hipMemsetAsync(d_bins, 0, nbins * 24, st) == hipSuccess ? 0 : -1;
     if (rc) g_err = "hipMemsetAsync failed";
     const uint64_t key = sim_key(seed, library_id);
     for (int64_t at = 0; at < nreads && rc == 0 && !ref; at += B) {
         const int64_t cnt = std::min(B, nreads - at);
-        if (hipEventRecord(ev[0], st) != hipSuccess || launch_simulate(g, L, key, at, cnt, h->d_reads, st) || hipEventRecord(ev[1], st) != hipSuccess) { rc = -1; break; }
-        h->reads_dev = h->d_reads; h->nreads = cnt;
+        if (simulate_resident(h, g, key, at, cnt, ev)) { rc = -1; break; }
         rc = train_range(h, 0, cnt, at, G, d_bins, nbins, ev[2], ev[3], tot);
         if (rc) break;
         h->train_ms[0] += ev_ms(ev[0], ev[1]);
@@ -2289,7 +2382,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
         const int64_t cnt = std::min(B, nreads - at);
         int64_t bases = 0;
         if (hipEventRecord(ev[0], st) != hipSuccess || simulate_var(g, L, key, at, cnt, d_lens, d_roff, d_sim, st, &bases)) { rc = -1; break; }
-        McVlBuf bb;
+        McDevBuf bb;
         uint8_t *d_sorted = nullptr; uint32_t *d_perm = nullptr;
         std::vector<uint32_t> start; std::vector<int64_t> boff;
         if (vl_bucket(bb, st, d_sim, d_roff, cnt, bases, &d_sorted, &d_perm, start, boff) || hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess) { rc = -1; break; }
@@ -2311,14 +2404,10 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
         h->read_len = L; h->FP = FP0; h->reads_dev = nullptr; h->nreads = 0;
         if (hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice) != hipSuccess && rc == 0) { g_err = "restoring the run's tables failed"; rc = -1; }
     }
-    h->best_only = saved_best_only; h->rows_stay = false;
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
     std::vector<unsigned long long> bins(nbins * 3);
     if (rc == 0 && (hipMemcpyAsync(bins.data(), d_bins, nbins * 24, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { g_err = "mc_train_library: copy of the bins failed"; rc = -1; }
-    if (rc) (void)hipStreamSynchronize(st);
-    (void)hipFree(d_bins);
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    if (rc) return rc;
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
     grid_counts(bins, nbins, n_cov * n_pid, n_score, nfam, order, count_hits, count_aln, count_cov);
     h->stats = tot; h->train_ms[1] = tot.ms_total;
     return 0;
@@ -2334,117 +2423,40 @@ extern "C" int mc_train_times(const mc_handle *h, float *ms)
 }
 
 // ------------------------------------------------------------------------------------------------
-// mock communities: M genomes with copies each, resident in HBM; their libraries (k_community.h), the fused library pass
+// mock communities: M genomes with copies each, resident in HBM; their libraries (k_community.h's placer), the fused library pass
 // ------------------------------------------------------------------------------------------------
-struct mc_community {
-    int device = 0, ncontig = 0, M = 0;
-    std::vector<int64_t> off, copies;                               // contig offsets, copies per member (host)
-    std::vector<int32_t> mfirst;                                    // member m holds contigs mfirst[m] .. mfirst[m + 1] - 1
-    uint8_t *d_bases = nullptr; int64_t *d_off = nullptr, *d_vstart = nullptr, *d_total = nullptr; uint64_t *d_cum = nullptr; int32_t *d_mfirst = nullptr;
-    unsigned long long *d_counts = nullptr;                         // reads per member of the pass under way
-    std::vector<int64_t> member_reads;                              // ... of the last simulate / library call
-    int span = 0;                                                   // the span (read length or insert) the member table was made for
-    mc_library lib = {0, 0, MC_ERR_NONE, 0.0};
-    uint64_t *d_thr = nullptr;
-};
-
-extern "C" void mc_community_close(mc_community *c)
+static int community_open(mc_community *c, const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, const int32_t *member_first_contig, const int64_t *copies,
+                          int32_t M, int32_t device)
 {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    for (void *p : {(void *)c->d_bases, (void *)c->d_off, (void *)c->d_vstart, (void *)c->d_total, (void *)c->d_cum, (void *)c->d_mfirst, (void *)c->d_counts, (void *)c->d_thr})
-        if (p) (void)hipFree(p);
-    delete c;
+    if (!bases || !contig_off || ncontig < 1 || !member_first_contig || !copies) { g_err = "mc_community_open: bad argument"; return -1; }
+    if (M < 1 || M > MC_SIM_MAX_MEMBERS) { g_err = "mc_community_open: " + std::to_string(M) + " members (1 .. " + std::to_string(MC_SIM_MAX_MEMBERS) + ")"; return -1; }
+    if (source_args(*c, bases, contig_off, ncontig)) return -1;
+    if (member_first_contig[0] != 0 || member_first_contig[M] != ncontig) { g_err = "mc_community_open: member_first_contig must run from 0 to ncontig"; return -1; }
+    for (int m = 0; m < M; m++) {
+        if (member_first_contig[m + 1] <= member_first_contig[m]) { g_err = "mc_community_open: member " + std::to_string(m) + " has no contig"; return -1; }
+        if (copies[m] < 1 || copies[m] > MC_SIM_MAX_COPIES) { g_err = "mc_community_open: member " + std::to_string(m) + " has " + std::to_string(copies[m]) + " copies (1 .. " + std::to_string(MC_SIM_MAX_COPIES) + ")"; return -1; }
+    }
+    if (source_open(*c, bases, contig_off, ncontig, device)) return -1;
+    c->M = M; c->copies.assign(copies, copies + M); c->mfirst.assign(member_first_contig, member_first_contig + M + 1);
+    c->member_reads.assign((size_t)M, 0);
+    if (c->mem.get(&c->d_total, (size_t)M) || c->mem.get(&c->d_cum, (size_t)M + 1) || c->mem.get(&c->d_mfirst, (size_t)M + 1) || c->mem.get(&c->d_counts, (size_t)M) ||
+        hipMemcpy(c->d_mfirst, member_first_contig, sizeof(int32_t) * (M + 1), hipMemcpyHostToDevice) != hipSuccess) {
+        g_err = "mc_community_open: out of device memory";
+        return -1;
+    }
+    return 0;
 }
-
 extern "C" mc_community *mc_community_open(const uint8_t *bases, const int64_t *contig_off, int32_t ncontig, const int32_t *member_first_contig, const int64_t *copies,
                                            int32_t M, int32_t device)
 {
-    if (!bases || !contig_off || ncontig < 1 || !member_first_contig || !copies) { g_err = "mc_community_open: bad argument"; return nullptr; }
-    if (M < 1 || M > MC_SIM_MAX_MEMBERS) { g_err = "mc_community_open: " + std::to_string(M) + " members (1 .. " + std::to_string(MC_SIM_MAX_MEMBERS) + ")"; return nullptr; }
-    if (contig_off[0] != 0) { g_err = "mc_community_open: contig_off[0] must be 0"; return nullptr; }
-    for (int i = 0; i < ncontig; i++) if (contig_off[i + 1] < contig_off[i]) { g_err = "mc_community_open: contig offsets must not decrease"; return nullptr; }
-    if (member_first_contig[0] != 0 || member_first_contig[M] != ncontig) { g_err = "mc_community_open: member_first_contig must run from 0 to ncontig"; return nullptr; }
-    for (int m = 0; m < M; m++) {
-        if (member_first_contig[m + 1] <= member_first_contig[m]) { g_err = "mc_community_open: member " + std::to_string(m) + " has no contig"; return nullptr; }
-        if (copies[m] < 1 || copies[m] > MC_SIM_MAX_COPIES) { g_err = "mc_community_open: member " + std::to_string(m) + " has " + std::to_string(copies[m]) + " copies (1 .. " + std::to_string(MC_SIM_MAX_COPIES) + ")"; return nullptr; }
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_err = "no HIP device visible"; return nullptr; }
-    if (device < 0 || device >= ndev) { g_err = "mc_community_open: no such device"; return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return nullptr; }
     mc_community *c = new mc_community();
-    c->device = device; c->ncontig = ncontig; c->M = M;
-    c->off.assign(contig_off, contig_off + ncontig + 1); c->copies.assign(copies, copies + M); c->mfirst.assign(member_first_contig, member_first_contig + M + 1);
-    c->member_reads.assign((size_t)M, 0);
-    const size_t nb = (size_t)contig_off[ncontig];
-    if (hipMalloc((void **)&c->d_bases, nb + 64) != hipSuccess || hipMalloc((void **)&c->d_off, sizeof(int64_t) * (ncontig + 1)) != hipSuccess ||
-        hipMalloc((void **)&c->d_vstart, sizeof(int64_t) * ncontig) != hipSuccess || hipMalloc((void **)&c->d_total, sizeof(int64_t) * M) != hipSuccess ||
-        hipMalloc((void **)&c->d_cum, sizeof(uint64_t) * (M + 1)) != hipSuccess || hipMalloc((void **)&c->d_mfirst, sizeof(int32_t) * (M + 1)) != hipSuccess ||
-        hipMalloc((void **)&c->d_counts, sizeof(unsigned long long) * M) != hipSuccess || hipMalloc((void **)&c->d_thr, sizeof(uint64_t) * MC_SIM_NTHR) != hipSuccess ||
-        hipMemcpy(c->d_bases, bases, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_off, contig_off, sizeof(int64_t) * (ncontig + 1), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_mfirst, member_first_contig, sizeof(int32_t) * (M + 1), hipMemcpyHostToDevice) != hipSuccess) {
-        g_err = "mc_community_open: out of device memory";
-        mc_community_close(c);
-        return nullptr;
-    }
+    if (community_open(c, bases, contig_off, ncontig, member_first_contig, copies, M, device)) { mc_community_close(c); return nullptr; }
     return c;
 }
+extern "C" void mc_community_close(mc_community *c) { source_close(c); }
 
-extern "C" int mc_community_set_library(mc_community *c, const mc_library *lib)
-{
-    if (!c) { g_err = "mc_community_set_library: bad argument"; return -1; }
-    const mc_library l = lib ? *lib : mc_library{0, 0, MC_ERR_NONE, 0.0};
-    if (l.error_model != MC_ERR_NONE && l.error_model != MC_ERR_UNIFORM && l.error_model != MC_ERR_ILLUMINA) { g_err = "unknown error model " + std::to_string(l.error_model); return -1; }
-    if (!(l.error_rate >= 0.0 && l.error_rate <= 1.0)) { g_err = "error rate " + std::to_string(l.error_rate) + " outside [0, 1]"; return -1; }
-    int64_t longest = 0;
-    for (int k = 0; k < c->ncontig; k++) longest = std::max(longest, c->off[(size_t)k + 1] - c->off[(size_t)k]);
-    if (l.paired_end && l.insert < 1) { g_err = "a paired-end library needs a positive insert"; return -1; }
-    if (l.paired_end && l.insert > longest) { g_err = "the community has no contig of at least the insert (" + std::to_string(l.insert) + " bp)"; return -1; }
-    uint64_t thr[MC_SIM_NTHR];
-    mc_sim_thresholds(l.error_model, l.error_rate, thr);
-    HIPCK(hipSetDevice(c->device));
-    HIPCK(hipMemcpy(c->d_thr, thr, sizeof thr, hipMemcpyHostToDevice));
-    c->lib = l;
-    return 0;
-}
-
-// the member table for reads of L bases - fragments of `insert` bases for a paired-end library; refuses an insert shorter than the
-// read, a community none of whose members has a contig of that span, and a universe of 2^62 or more
-static int community_for_len(mc_community *c, int L)
-{
-    if (c->lib.paired_end && c->lib.insert < L) { g_err = "the insert (" + std::to_string(c->lib.insert) + ") is shorter than the read length (" + std::to_string(L) + ")"; return -1; }
-    const int span = c->lib.paired_end ? c->lib.insert : L;
-    if (c->span == span) return 0;
-    std::vector<int64_t> vs((size_t)c->ncontig), total((size_t)c->M);
-    std::vector<uint64_t> cum((size_t)c->M + 1);
-    const int bad = mc_sim_member_table(c->off.data(), c->mfirst.data(), c->copies.data(), c->M, span, vs.data(), total.data(), cum.data());
-    if (bad == 1) { g_err = "the community has no contig of at least the " + std::string(c->lib.paired_end ? "insert" : "read length") + " (" + std::to_string(span) + " bp)"; return -1; }
-    if (bad) { g_err = "the community's universe (the sum of copies x valid starts) does not stay below 2^62"; return -1; }
-    HIPCK(hipMemcpy(c->d_vstart, vs.data(), sizeof(int64_t) * vs.size(), hipMemcpyHostToDevice));
-    HIPCK(hipMemcpy(c->d_total, total.data(), sizeof(int64_t) * total.size(), hipMemcpyHostToDevice));
-    HIPCK(hipMemcpy(c->d_cum, cum.data(), sizeof(uint64_t) * cum.size(), hipMemcpyHostToDevice));
-    c->span = span;
-    return 0;
-}
-
-static int launch_community(const mc_community *c, int L, uint64_t key, int64_t first, int64_t n, uint8_t *dst, hipStream_t st)
-{
-    if (n <= 0) return 0;
-    const McCommTable T = {c->d_cum, c->d_total, c->d_mfirst, c->d_vstart, c->d_off, c->M, c->M <= MC_COMM_LDS_M ? 1 : 0};
-    if (default_library(c->lib)) {
-        k_community<<<dim3((unsigned)((n + 255) / 256)), dim3(256), comm_lds_bytes(c->M), st>>>(c->d_bases, T, L, key, first, n, dst, c->d_counts);
-    } else {
-        const McSimKind kind = {L, c->lib.paired_end ? 1 : 0, c->lib.paired_end ? c->lib.insert : L, c->lib.error_model != MC_ERR_NONE ? 1 : 0};
-        const size_t lds = (size_t)64 * L + sizeof(uint64_t) * MC_SIM_NTHR + comm_lds_bytes(c->M);
-        k_community_lib<<<dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st>>>(c->d_bases, T, kind, c->d_thr, key, mc_mix64(key ^ MC_SIM_EKEY), first, n, dst, c->d_counts);
-    }
-    HIPCK(hipGetLastError());
-    return 0;
-}
-
-// the counts of the pass that ended (everything on `st` waited for) to the host
+// the device's counts cleared before a pass (on st), and to the host when it has ended (everything on `st` waited for)
+static int community_counts_reset(mc_community *c, hipStream_t st) { HIPCK(hipMemsetAsync(c->d_counts, 0, sizeof(unsigned long long) * c->M, st)); return 0; }
 static int community_counts(mc_community *c, hipStream_t st)
 {
     std::vector<unsigned long long> v((size_t)c->M);
@@ -2457,25 +2469,11 @@ static int community_counts(mc_community *c, hipStream_t st)
 extern "C" int mc_community_simulate(mc_community *c, int32_t read_len, int64_t first, int64_t n, uint64_t seed, uint64_t library_id, uint8_t *dst_host)
 {
     if (!c || first < 0 || n < 0 || (n > 0 && !dst_host)) { g_err = "mc_community_simulate: bad argument"; return -1; }
-    if (read_len < 18 || read_len > 3 * MC_MAXAA) { g_err = "read_len out of range (18..510)"; return -1; }
-    HIPCK(hipSetDevice(c->device));
-    if (community_for_len(c, read_len)) return -1;
+    if (simulate_begin(c, read_len)) return -1;
     std::fill(c->member_reads.begin(), c->member_reads.end(), 0);
     if (n == 0) return 0;
-    const int64_t B = std::min<int64_t>(n, stream_batch());
-    uint8_t *d = nullptr;
-    HIPCK(hipMalloc((void **)&d, (size_t)(B * read_len)));
-    const uint64_t key = sim_key(seed, library_id);
-    int rc = hipMemset(c->d_counts, 0, sizeof(unsigned long long) * c->M) == hipSuccess ? 0 : -1;
-    if (rc) g_err = "mc_community_simulate: hipMemset failed";
-    for (int64_t at = 0; at < n && rc == 0; at += B) {               // ranges of the streaming batch size, as mc_community_library makes them
-        const int64_t cnt = std::min(B, n - at);
-        rc = launch_community(c, read_len, key, first + at, cnt, d, nullptr);
-        if (rc == 0 && hipMemcpy(dst_host + at * read_len, d, (size_t)(cnt * read_len), hipMemcpyDeviceToHost) != hipSuccess) { g_err = "mc_community_simulate: copy failed"; rc = -1; }
-    }
-    if (rc == 0) rc = community_counts(c, nullptr);
-    (void)hipFree(d);
-    return rc;
+    if (community_counts_reset(c, nullptr) || simulate_to_host(c, read_len, first, n, sim_key(seed, library_id), dst_host, "mc_community_simulate")) return -1;
+    return community_counts(c, nullptr);
 }
 
 extern "C" int mc_community_member_reads(mc_community *c, int64_t *out)
@@ -2498,8 +2496,7 @@ extern "C" int mc_community_library(mc_handle *h, mc_community *c, int64_t nread
     if (h->pipe_nout) { g_err = "mc_community_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
     if (h->abund) { g_err = "mc_community_library: refused while abundance counting is on (it runs best hits only; mc_set_abundance)"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    const int L = h->read_len;
-    if (community_for_len(c, L)) return -1;
+    if (source_for_len(c, h->read_len)) return -1;
     std::fill(c->member_reads.begin(), c->member_reads.end(), 0);
     h->comm_ms[0] = h->comm_ms[1] = 0.f;
     mc_stats tot; memset(&tot, 0, sizeof tot);
@@ -2507,21 +2504,16 @@ extern "C" int mc_community_library(mc_handle *h, mc_community *c, int64_t nread
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
     if (nreads == 0) { h->stats = tot; return 0; }
     const int64_t B = std::min<int64_t>(nreads, stream_batch());
-    const int64_t need = B * L + 16;                                 // the resident read buffer (mc_upload's) holds one range at a time
-    if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
-    if (ensure_capacity(h, h->ctx, B)) return -1;
-    hipEvent_t ev[2] = {};
-    for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { g_err = "hipEventCreate failed"; return -1; }
+    if (reads_reserve(h, B) || ensure_capacity(h, h->ctx, B)) return -1;   // the resident read buffer (mc_upload's) holds one range at a time
+    McEvents ev;
+    if (ev.make(2)) return -1;
     hipStream_t st = h->ctx.stream;
-    const bool saved_best_only = h->best_only;
-    h->best_only = true;
-    int rc = hipMemsetAsync(c->d_counts, 0, sizeof(unsigned long long) * c->M, st) == hipSuccess ? 0 : -1;
-    if (rc) g_err = "hipMemsetAsync failed";
+    McModeGuard mode(h, true, h->rows_stay);
+    int rc = community_counts_reset(c, st);
     const uint64_t key = sim_key(seed, library_id);
     for (int64_t at = 0; at < nreads && rc == 0; at += B) {
         const int64_t cnt = std::min(B, nreads - at);
-        if (hipEventRecord(ev[0], st) != hipSuccess || launch_community(c, L, key, at, cnt, h->d_reads, st) || hipEventRecord(ev[1], st) != hipSuccess) { rc = -1; break; }
-        h->reads_dev = h->d_reads; h->nreads = cnt;
+        if (simulate_resident(h, c, key, at, cnt, ev)) { rc = -1; break; }
         if ((rc = mc_run_range(h, 0, cnt, at)) != 0) break;
         h->comm_ms[0] += ev_ms(ev[0], ev[1]);
         best_materialize(h);
@@ -2529,8 +2521,6 @@ extern "C" int mc_community_library(mc_handle *h, mc_community *c, int64_t nread
         stats_add(tot, h->stats);
     }
     if (rc == 0) rc = community_counts(c, st); else (void)hipStreamSynchronize(st);
-    h->best_only = saved_best_only;
-    for (auto &e : ev) (void)hipEventDestroy(e);
     if (rc) return rc;
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.swap(all_best); h->best_from = nullptr; h->stats = tot;
     h->comm_ms[1] = tot.ms_total;

@@ -3,8 +3,8 @@
 makes of the oracle's m8 of a simulated library, one file per case (tests/golden/training_library_<case>.json.gz).
 
 For each case:
-  1. the library's reads are made on the CPU by tests/simlib_restated.simulate (the numpy restatement the GPU tests pin k_simulate /
-     k_simulate_lib to, byte for byte), from one genome of tests/golden/genomes/genomes30.npz, with the (seed, library id, kind)
+  1. the library's reads are made on the CPU by tests/simlib_restated.simulate (the numpy restatement the GPU tests pin k_sim_copy /
+     k_sim_walk to, byte for byte), from one genome of tests/golden/genomes/genomes30.npz, with the (seed, library id, kind)
      recorded in the golden;
   2. the reads, named by their index (">%d", mates included, as Engine.write_m8 names them), are searched by oracle/rs_port on
      oracle/_ref/rapdb_2.15: one slice per core (at most 16 processes), the outputs joined in read order; the md5 of that m8 is

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import community_restated as cr
+import simlib_restated as sr
 from microbecensus_amd import _native, training, validation
 from microbecensus_amd import microbe_census as mc
 
@@ -103,6 +104,49 @@ def test_one_member_one_copy_is_mc_simulate(genomes):
         finally:
             comm.close()
             g.close()
+
+
+# ---- 6b. the edges of the simulator both sources share ---------------------------------------------------------------------
+EDGE_LS, EDGE_NS, EDGE_FIRST = (18, 101, 510), (1, 63, 65, 257), 1235       # the read-length limits and an odd one; one row, a row less / more than a wave, a row more than a block; mate 1 first
+
+
+def edge_kind(kind, L):
+    return dict(kind, insert=max(400, L + 7)) if kind.get("paired_end") else kind
+
+
+def edge_references(genomes, kind, L):
+    """The restatements' rows [EDGE_FIRST, EDGE_FIRST + 257) of a three-member community and of one genome: every shorter range is a prefix."""
+    members, copies = [(b, o) for _, b, o in genomes[:3]], [3, 1, 70000]
+    bases, off, mfirst = cr.join_members(members)
+    n, lid, k = max(EDGE_NS), training.library_id("edges", L), edge_kind(kind, L)
+    want_c, m, _, _ = cr.simulate(bases, off, mfirst, copies, L, EDGE_FIRST, n, 9, lid, **k)
+    want_g = sr.simulate(genomes[4][1], genomes[4][2], L, EDGE_FIRST, n, 9, lid, **k)
+    return members, copies, lid, k, want_c, m, want_g
+
+
+def test_edges_of_the_shared_simulator(genomes):
+    """Shapes the other tests never reach: L at both limits and L = 101 (a last block whose rows x L bytes are no multiple of 4), libraries
+    of 1, 63, 65 and 257 reads, a range that begins on mate 1, an insert of max(400, L + 7) - for every kind, a community and a genome
+    against their restatements, and the community of that genome alone against the genome."""
+    members, copies = edge_references(genomes, {}, 18)[:2]
+    _, gb, goff = genomes[4]
+    comm, one, g = _native.Community(members, copies, 0), _native.Community([(gb, goff)], [1], 0), _native.Genome(gb, goff, 0)
+    try:
+        for kind in KINDS:
+            for L in EDGE_LS:
+                _, _, lid, k, want_c, m, want_g = edge_references(genomes, kind, L)
+                for src in (comm, one, g):
+                    src.set_library(**k)
+                for n in EDGE_NS:
+                    assert np.array_equal(comm.simulate(L, n, 9, lid, first=EDGE_FIRST), want_c[:n]), (kind, L, n)
+                    assert np.array_equal(comm.member_reads(), np.bincount(m[:n], minlength=3)), (kind, L, n)
+                    got = g.simulate(L, n, 9, lid, first=EDGE_FIRST)
+                    assert np.array_equal(got, want_g[:n]), (kind, L, n)
+                    assert one.simulate(L, n, 9, lid, first=EDGE_FIRST).tobytes() == got.tobytes(), (kind, L, n)
+                    assert one.member_reads().tolist() == [n]
+    finally:
+        for src in (comm, one, g):
+            src.close()
 
 
 # ---- 7. fused == staged ---------------------------------------------------------------------------------------------------

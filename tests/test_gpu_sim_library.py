@@ -1,4 +1,4 @@
-"""GPU tests of the simulator's library kinds (mc_genome_set_library, csrc/k_simulate.h k_simulate_lib): device bytes against the
+"""GPU tests of the simulator's library kinds (mc_genome_set_library, csrc/k_simulate.h k_sim_walk): device bytes against the
 numpy restatement, the exact invariants, the fused library pass against the pinned path, the ABI's refusals, and training end to
 end with Illumina errors and with mate pairs."""
 import ctypes as C
