@@ -3,8 +3,8 @@
 // with at most MC_CL_BINS = 33 bins (the K classes and "no class"), which fit in LDS and registers, and a gather that trims.
 //   k_cl_hist     per tile of MC_CL_TILE rows: the length of every row (P lanes per row, one aligned 16-byte load each, a min over the
 //                 P lanes), its class (cls[row]; K = none), and how many rows of each class; counts[bin * ntiles + tile]
-//   k_cl_scan     one workgroup: exclusive scan of counts in that (bin-major) order -> where each tile's rows of each class go;
-//                 start[bin] = first sorted position of the class, start[nbins] = n
+//   k_bin_scan    (k_varlen.h's, with nbins = K + 1) exclusive scan of counts in that (bin-major) order -> where each tile's rows of
+//                 each class go; start[bin] = first sorted position of the class, start[nbins] = n
 //   k_cl_scatter  perm[sorted position] = row index; stable: within a class the row indices ascend.  Ranks come from wave ballots
 //                 (one round per class present in the wave), not from a scan over the workgroup's rows
 //   k_cl_gather   the first class_len[k] bytes of every row of class k to that class's block of dst (16-byte aligned), a thread per
@@ -14,6 +14,7 @@
 // The rows buffer is 16-byte aligned and has MC_CL_SLACK readable bytes behind its last row; dst has them behind its last block.
 #pragma once
 #include "mc_classes.h"
+#include "k_varlen.h"                                                // (k_bin_scan)
 
 #define MC_CL_BINS (MC_CLS_MAX + 1)
 #define MC_CL_TILE 4096
@@ -61,32 +62,6 @@ __global__ void __launch_bounds__(MC_CL_BS) k_cl_hist(const uint8_t *__restrict_
     }
     __syncthreads();
     if (threadIdx.x <= (unsigned)C.K) counts[(size_t)threadIdx.x * ntiles + blockIdx.x] = hist[threadIdx.x];
-}
-
-// one workgroup of 1024 threads; m = nbins * ntiles entries, total n < 2^31
-__global__ void __launch_bounds__(1024) k_cl_scan(uint32_t *__restrict__ counts, uint32_t m, uint32_t ntiles, uint32_t nbins, uint32_t *__restrict__ start)
-{
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, chunk = (m + 1023) / 1024;
-    const uint32_t lo = min(m, t * chunk), hi = min(m, lo + chunk);
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < hi; i++) s += counts[i];
-    part[t] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {                        // inclusive scan of the chunk sums (Hillis - Steele)
-        const uint32_t v = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - s;
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint32_t v = counts[i];
-        if (i % ntiles == 0) start[i / ntiles] = run;
-        counts[i] = run;
-        run += v;
-    }
-    if (t == 1023) start[nbins] = part[1023];
 }
 
 __global__ void __launch_bounds__(MC_CL_BS) k_cl_scatter(const uint8_t *__restrict__ cls, int64_t n, uint32_t ntiles, uint32_t nbins, const uint32_t *__restrict__ tile_off,

@@ -1,8 +1,9 @@
 // k_varlen.h - a batch of reads of mixed lengths bucketed by length on the device (mc_search_varlen): the fixed-length pipeline
 // then runs once per bucket, each bucket's reads back to back at that bucket's pitch.
 //   k_vl_hist     per tile of MC_VL_TILE reads: how many reads of each length; counts[len * ntiles + tile]
-//   k_vl_scan     one workgroup: exclusive scan of counts in that (length-major) order -> where each tile's reads of each length go;
-//                 start[len] = first sorted position of the bucket of length len, start[MC_VL_BINS] = n
+//   k_bin_scan    one workgroup: exclusive scan of counts in that (length-major) order -> where each tile's reads of each length go;
+//                 start[len] = first sorted position of the bucket of length len, start[nbins] = n.  The one scan of every (bin, tile)
+//                 count table: k_classes.h launches it with its own number of bins
 //   k_vl_scatter  perm[sorted position] = read index; stable: within a bucket the read indices ascend
 //   k_vl_gather   each read's bases to its bucket's block of dst (byte_off[len] + rank in the bucket * len)
 // The host has checked every length (1 .. MC_MAXAA * 3) before these run: off[i + 1] - off[i] is always a valid bin.
@@ -26,8 +27,8 @@ __global__ void __launch_bounds__(MC_VL_BS) k_vl_hist(const int64_t *__restrict_
     for (int l = threadIdx.x; l < MC_VL_BINS; l += MC_VL_BS) counts[(size_t)l * ntiles + blockIdx.x] = hist[l];
 }
 
-// one workgroup of 1024 threads; m = MC_VL_BINS * ntiles entries, total n < 2^31
-__global__ void __launch_bounds__(1024) k_vl_scan(uint32_t *__restrict__ counts, uint32_t m, uint32_t ntiles, uint32_t *__restrict__ start)
+// one workgroup of 1024 threads; m = nbins * ntiles entries, total n < 2^31
+__global__ void __launch_bounds__(1024) k_bin_scan(uint32_t *__restrict__ counts, uint32_t m, uint32_t ntiles, uint32_t nbins, uint32_t *__restrict__ start)
 {
     __shared__ uint32_t part[1024];
     const uint32_t t = threadIdx.x, chunk = (m + 1023) / 1024;
@@ -49,7 +50,7 @@ __global__ void __launch_bounds__(1024) k_vl_scan(uint32_t *__restrict__ counts,
         counts[i] = run;
         run += v;
     }
-    if (t == 1023) start[MC_VL_BINS] = part[1023];
+    if (t == 1023) start[nbins] = part[1023];
 }
 
 __global__ void __launch_bounds__(MC_VL_BS) k_vl_scatter(const int64_t *__restrict__ off, int64_t n, uint32_t ntiles, const uint32_t *__restrict__ tile_off, uint32_t *__restrict__ perm)

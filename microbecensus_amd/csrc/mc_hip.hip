@@ -15,6 +15,7 @@
 //   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
 //   k_wfit.h               the fit of the per-family weights, training step 5 (mc_fit_weights, mc_weights_mue)
 //   k_abundance.h          per-gene read counts for RPKG, summed over the rows of every completed range (mc_set_abundance)
+//   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
 // ranges from a host-side source (mc_search, mc_search_files, mc_search_files_multi) with upload and search overlapped.
@@ -33,6 +34,7 @@
 #include "k_bootstrap.h"
 #include "k_wfit.h"
 #include "k_abundance.h"
+#include "mc_pieces.h"
 
 #include <map>
 
@@ -410,6 +412,9 @@ extern "C" int mc_index_view(const mc_handle *h, const uint8_t **res_codes, cons
     return 0;
 }
 
+// the run's own tables (mc_set_run's) to the device: when they are made, and when a borrowed length has ended (McLenBorrow)
+static hipError_t run_tables_up(mc_handle *h) { return hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice); }
+
 extern "C" int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const double *min_cov, const double *min_score, const int32_t *max_aaid, const int32_t *aln_stat)
 {
     if (!h) { g_err = "null handle"; return -1; }
@@ -423,7 +428,7 @@ extern "C" int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const
     memset(&h->hP, 0, sizeof h->hP);
     h->hP.nfam = h->nfam; h->hP.read_len = read_len;
     for (int f = 0; f < h->nfam; f++) { h->hP.min_cov[f] = min_cov[f]; h->hP.min_score[f] = min_score[f]; h->hP.max_aaid[f] = max_aaid[f]; h->hP.aln_stat[f] = aln_stat[f]; }
-    HIPCK(hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice));
+    HIPCK(run_tables_up(h));
     if (!h->d_segtab) {   // Seg::getprob of every short window, tabulated once (ln n! does not depend on the run)
         std::vector<uint64_t> tab;
         mc_build_segtab(h->hT.lnfac, tab);
@@ -821,6 +826,25 @@ static void stats_add(mc_stats &tot, const mc_stats &s)
 static int run_range_once(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id);
 static void best_materialize(mc_handle *h);
 
+// The results of a run that is made of several ranges: rows (its own vector, or one of the handle's), best hits, for a class run the
+// class of every best hit, and the statistics.  take() adds those of the range that ended last; the front of the next range may be
+// running meanwhile (range_begin).
+struct McResults {
+    std::vector<mc_row> own_rows, &rows;                             // (own_rows first: rows may be bound to it)
+    std::vector<mc_best_hit> best; std::vector<uint8_t> tag; mc_stats tot;
+    bool want_rows, tagged;
+    McResults(bool want_rows_, std::vector<mc_row> *rows_ = nullptr, bool tagged_ = false) : rows(rows_ ? *rows_ : own_rows), want_rows(want_rows_), tagged(tagged_) { memset(&tot, 0, sizeof tot); }
+    McResults(const McResults &) = delete;
+    void take(mc_handle *h, int tag_ = 0)
+    {
+        if (want_rows) { rows_wait(h); rows.insert(rows.end(), h->res_rows, h->res_rows + h->n_res_rows); }
+        best_materialize(h);
+        best.insert(best.end(), h->best.begin(), h->best.end());
+        if (tagged) tag.insert(tag.end(), h->best.size(), (uint8_t)tag_);
+        stats_add(tot, h->stats);
+    }
+};
+
 // A range whose seed hits / HSPs / rows overflow the pools sized for ordinary shotgun reads (-2 from the pipeline) is run again in
 // halves, and their results joined: the caller sees one range either way.
 extern "C" int mc_run_range(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id)
@@ -828,23 +852,19 @@ extern "C" int mc_run_range(mc_handle *h, int64_t first, int64_t count, int64_t 
     if (h && h->pipe_nout) { g_err = "mc_run_range: ranges begun with mc_range_begin() are still in flight"; return -1; }
     int rc = run_range_once(h, first, count, first_read_id);
     if (rc != -2 || count <= 1) return rc;
-    std::vector<mc_row> &rows = h->split_rows; rows.clear();
-    std::vector<mc_best_hit> best; mc_stats tot; memset(&tot, 0, sizeof tot);
-    tot.range_splits = 1;
+    h->split_rows.clear();
+    McResults R(true, &h->split_rows);
+    R.tot.range_splits = 1;
     int64_t off = 0, step = std::max<int64_t>(1, count / 2);
     while (off < count) {
         const int64_t nb = std::min<int64_t>(step, count - off);
         rc = run_range_once(h, first + off, nb, first_read_id + off);
-        if (rc == -2 && nb > 1) { step = std::max<int64_t>(1, nb / 2); tot.range_splits++; continue; }
+        if (rc == -2 && nb > 1) { step = std::max<int64_t>(1, nb / 2); R.tot.range_splits++; continue; }
         if (rc) return rc;
-        rows_wait(h);
-        rows.insert(rows.end(), h->res_rows, h->res_rows + h->n_res_rows);
-        best_materialize(h);
-        best.insert(best.end(), h->best.begin(), h->best.end());
-        stats_add(tot, h->stats);
+        R.take(h);
         off += nb;
     }
-    h->res_rows = rows.data(); h->n_res_rows = (int64_t)rows.size(); h->best.swap(best); h->best_from = nullptr; h->stats = tot;
+    h->res_rows = R.rows.data(); h->n_res_rows = (int64_t)R.rows.size(); h->best.swap(R.best); h->best_from = nullptr; h->stats = R.tot;
     return 0;
 }
 
@@ -1096,20 +1116,13 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
             if (rc <= 0) return;
         }
     });
-    std::vector<mc_row> &all_rows = h->all_rows; all_rows.clear();
-    if (h->keep_rows && expect_reads > 0) all_rows.reserve((size_t)expect_reads * 2 + 1024);   // (shotgun reads of real genomes: 1.9 rows per read; untouched pages cost nothing)
-    std::vector<mc_best_hit> all_best; mc_stats tot; memset(&tot, 0, sizeof tot);
+    h->all_rows.clear();
+    if (h->keep_rows && expect_reads > 0) h->all_rows.reserve((size_t)expect_reads * 2 + 1024);   // (shotgun reads of real genomes: 1.9 rows per read; untouched pages cost nothing)
+    McResults R(h->keep_rows, &h->all_rows);
     const uint8_t *saved_reads = h->reads_dev; const int64_t saved_n = h->nreads;
     // the results of the range that ended last -> those of the stream (called while the front of the next batch runs)
     bool pending = false;
-    auto collect = [&]() {
-        if (!pending) return;
-        pending = false;
-        if (h->keep_rows) { rows_wait(h); all_rows.insert(all_rows.end(), h->res_rows, h->res_rows + h->n_res_rows); }
-        best_materialize(h);
-        all_best.insert(all_best.end(), h->best.begin(), h->best.end());
-        stats_add(tot, h->stats);
-    };
+    auto collect = [&]() { if (pending) { pending = false; R.take(h); } };
     auto release = [&](int k) { std::unique_lock<std::mutex> lk(mu); slot[k].state = 0; cv.notify_all(); };
     // batch `k` is in flight: its range ends (a pool overflow is answered by mc_run_range: smaller ranges); its results are pending
     auto end_batch = [&](int k) -> int {
@@ -1142,7 +1155,7 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
     uploader.join();
     h->reads_dev = saved_reads; h->nreads = saved_n;
     if (rc) return rc;
-    h->res_rows = all_rows.data(); h->n_res_rows = (int64_t)all_rows.size(); h->best.swap(all_best); h->best_from = nullptr; h->stats = tot;
+    h->res_rows = R.rows.data(); h->n_res_rows = (int64_t)R.rows.size(); h->best.swap(R.best); h->best_from = nullptr; h->stats = R.tot;
     return 0;
 }
 
@@ -1216,21 +1229,86 @@ extern "C" int mc_search_files(mc_handle *h, mc_reader *r, int64_t first_read_id
     return mc_search_files_multi(&h, 1, r, first_read_id);
 }
 
+// ---- the handle borrowed for other read lengths: mc_search_varlen, the class runs, mc_train_library's reference read lengths ---------
+// mc_train_library, mc_community_library and the class runs put the handle in a mode of their own (best hits only or not, rows left
+// on the device or not); however they return, the caller's mode comes back
+struct McModeGuard {
+    mc_handle *h; bool best_only, rows_stay;
+    McModeGuard(mc_handle *h_, bool best, bool stay) : h(h_), best_only(h_->best_only), rows_stay(h_->rows_stay) { h->best_only = best; h->rows_stay = stay; }
+    McModeGuard(const McModeGuard &) = delete;
+    ~McModeGuard() { h->best_only = best_only; h->rows_stay = rows_stay; }
+};
+
+// The handle borrowed for other read lengths than the run's (and, in a class run, other classification parameters): its read length,
+// frame pitch and resident reads are noted here and come back with close(), and so do the run's tables and parameters on the device
+// where use() has replaced them - however the borrower returns.
+struct McLenBorrow {
+    mc_handle *h; int read_len, FP; const uint8_t *reads_dev; int64_t nreads; bool tables = false, pars = false, open = true;
+    explicit McLenBorrow(mc_handle *h_) : h(h_), read_len(h_->read_len), FP(h_->FP), reads_dev(h_->reads_dev), nreads(h_->nreads) {}
+    McLenBorrow(const McLenBorrow &) = delete;
+    ~McLenBorrow() { (void)close(-1); }
+    void set_len(int L) { h->read_len = L; h->FP = ((L / 3 + 2) + 3) & ~3; }
+    // the pools for the pieces: sized once, for the longest length, and for the larger of the largest piece and what they held before (a
+    // fixed-length run after this one then finds its pools in place)
+    int pools(int Lmax, int64_t nmax)
+    {
+        set_len(Lmax);
+        return ensure_capacity(h, h->ctx, std::min<int64_t>(std::max(h->ctx.cap_reads, nmax), (1 << 21) - 1));
+    }
+    // the handle runs reads of L bases from now on: their tables (mc_fill_tables: the query length enters the E-value), read length and
+    // frame pitch (the pools were sized for the longest length), and the classification parameters P where some are given
+    int use(int L, const McClassPars *P = nullptr)
+    {
+        if (h->vl_thr != h->hT.loge_thr) { h->vl_tables.clear(); h->vl_thr = h->hT.loge_thr; }
+        auto it = h->vl_tables.find(L);
+        if (it == h->vl_tables.end()) { it = h->vl_tables.emplace(L, McTables()).first; mc_fill_tables(it->second, h->H, L, h->vl_thr); }
+        tables = true;
+        HIPCK(hipMemcpy(h->d_T, &it->second, sizeof(McTables), hipMemcpyHostToDevice));
+        if (P) { pars = true; HIPCK(hipMemcpy(h->d_P, P, sizeof(McClassPars), hipMemcpyHostToDevice)); }
+        set_len(L);
+        return 0;
+    }
+    // rc is what the borrower has come to: it is returned, or - where it is 0 and the run's tables cannot be put back - that error
+    int close(int rc = 0)
+    {
+        if (!open) return rc;
+        open = false;
+        h->read_len = read_len; h->FP = FP; h->reads_dev = reads_dev; h->nreads = nreads;
+        hipError_t e = tables ? run_tables_up(h) : hipSuccess;
+        if (e == hipSuccess && pars) e = hipMemcpy(h->d_P, &h->hP, sizeof(McClassPars), hipMemcpyHostToDevice);
+        if (rc == 0 && e != hipSuccess) { g_err = std::string("restoring the run's tables: ") + hipGetErrorString(e); rc = -1; }
+        return rc;
+    }
+};
+
+// The pieces of a sorted batch through the pipeline, each at its length (and, pars != nullptr, with the parameters pars[tag] of its bin),
+// its reads at block_of(piece); results into R, a piece's best hits tagged with its bin.  end(j), begin(j + 1), take(j): the front of
+// the next piece runs while the host takes the results of this one.  A piece that overflowed a pool is run again in smaller ranges
+// while its length is still the handle's.
+template <class BlockOf> static int run_pieces(mc_handle *h, McLenBorrow &len, const std::vector<McPiece> &pieces, BlockOf block_of, const McClassPars *pars, McResults &R)
+{
+    auto begin = [&](const McPiece &q) -> int {
+        if (len.use(q.L, pars ? pars + q.tag : nullptr)) return -1;
+        h->reads_dev = block_of(q); h->nreads = q.bin_n;
+        return mc_range_begin(h, q.first, q.n, q.bin_first + q.first);
+    };
+    int rc = pieces.empty() ? 0 : begin(pieces[0]);
+    for (size_t j = 0; rc == 0 && j < pieces.size(); j++) {
+        const McPiece &q = pieces[j];
+        rc = mc_range_end(h);
+        if (rc == -2) rc = mc_run_range(h, q.first, q.n, q.bin_first + q.first);
+        if (rc) break;
+        if (j + 1 < pieces.size() && (rc = begin(pieces[j + 1])) != 0) break;
+        R.take(h, q.tag);
+    }
+    if (h->pipe_nout) (void)mc_range_end(h);                         // (after an error: nothing stays in flight)
+    return rc;
+}
+
 // ---- reads of mixed lengths (mc_search_varlen) ---------------------------------------------------------------------------------
 // The reads are bucketed by length on the device (k_varlen.h) and the fixed-length pipeline runs once per bucket, with the tables of
 // that length (mc_fill_tables: the query length enters the E-value through the length adjustment) and the classification length of
 // mc_set_run().  Ranges are numbered by sorted position (bucket start + rank): perm maps them back to the caller's reads.
-
-// the handle runs bucket L from now on: its tables, read length and frame pitch (the pools were sized for the longest bucket)
-static int vl_use_length(mc_handle *h, int L)
-{
-    if (h->vl_thr != h->hT.loge_thr) { h->vl_tables.clear(); h->vl_thr = h->hT.loge_thr; }
-    auto it = h->vl_tables.find(L);
-    if (it == h->vl_tables.end()) { it = h->vl_tables.emplace(L, McTables()).first; mc_fill_tables(it->second, h->H, L, h->vl_thr); }
-    HIPCK(hipMemcpy(h->d_T, &it->second, sizeof(McTables), hipMemcpyHostToDevice));
-    h->read_len = L; h->FP = ((L / 3 + 2) + 3) & ~3;
-    return 0;
-}
 
 // Buckets the nreads reads at d_bases / d_off (offsets from 0, on the device) by length: d_sorted receives every bucket's reads back to
 // back at its pitch, start[L] the bucket's first sorted position (start[MC_VL_BINS] = nreads), boff[L] its first byte, perm (device)
@@ -1245,7 +1323,7 @@ static int vl_bucket(McDevBuf &B, hipStream_t st, const uint8_t *d_bases, const 
     HIPCK(hipMemsetAsync(*d_sorted + total, 0, 64, st));
     k_vl_hist<<<dim3(ntiles), dim3(MC_VL_BS), 0, st>>>(d_off, nreads, ntiles, d_cnt);
     HIPCK(hipGetLastError());
-    k_vl_scan<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, (uint32_t)MC_VL_BINS * ntiles, ntiles, d_start);
+    k_bin_scan<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, (uint32_t)MC_VL_BINS * ntiles, ntiles, MC_VL_BINS, d_start);
     HIPCK(hipGetLastError());
     k_vl_scatter<<<dim3(ntiles), dim3(MC_VL_BS), 0, st>>>(d_off, nreads, ntiles, d_cnt, *d_perm);
     HIPCK(hipGetLastError());
@@ -1262,28 +1340,12 @@ static int vl_bucket(McDevBuf &B, hipStream_t st, const uint8_t *d_bases, const 
     return 0;
 }
 
-// the buckets' pieces: lengths of 18 bases and more (a shorter read has no frame of more than 5 residues, which RAPsearch2 skips:
-// hitless), each cut into ranges of at most `batch` reads; Lmax / nmax: the longest bucket's length and the largest piece
-struct McVlPiece { int L; int64_t first, n; };
-static void vl_pieces(const std::vector<uint32_t> &start, int64_t batch, std::vector<McVlPiece> &pieces, int &Lmax, int64_t &nmax, int64_t &nshort)
+// the buckets as the piece cutter takes them (mc_pieces.h): bin L - 1 holds the reads of L bases
+static std::vector<McBin> vl_bins(const std::vector<uint32_t> &start)
 {
-    pieces.clear(); Lmax = 0; nmax = 0; nshort = 0;
-    for (int L = 1; L < MC_VL_BINS; L++) {
-        const int64_t cnt = (int64_t)(start[(size_t)L + 1] - start[(size_t)L]);
-        if (!cnt) continue;
-        if (L < 18) { nshort += cnt; continue; }
-        for (int64_t a = 0; a < cnt; a += batch) pieces.push_back({L, a, std::min(batch, cnt - a)});
-        Lmax = L; nmax = std::max(nmax, std::min(batch, cnt));
-    }
-}
-
-// the pools for the pieces: sized once, for the longest bucket, and for the larger of the largest piece and what they held before (a
-// fixed-length run after this one then finds its pools in place)
-static int vl_pools(mc_handle *h, int Lmax, int64_t nmax)
-{
-    McCtx &c = h->ctx;
-    h->read_len = Lmax; h->FP = ((Lmax / 3 + 2) + 3) & ~3;
-    return ensure_capacity(h, c, std::min<int64_t>(std::max(c.cap_reads, nmax), (1 << 21) - 1));
+    std::vector<McBin> bins;
+    for (int L = 1; L < MC_VL_BINS; L++) bins.push_back({L, (int64_t)(start[(size_t)L + 1] - start[(size_t)L]), (int64_t)start[(size_t)L]});
+    return bins;
 }
 
 static int search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offsets, int64_t nreads, int64_t first_read_id)
@@ -1303,62 +1365,28 @@ static int search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offs
     std::vector<uint32_t> perm((size_t)nreads);
     HIPCK(hipMemcpyAsync(perm.data(), d_perm, perm.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
-    std::vector<McVlPiece> pieces;
-    int Lmax = 0; int64_t nmax = 0, nshort = 0;
-    vl_pieces(start, stream_batch(), pieces, Lmax, nmax, nshort);
-    std::vector<mc_row> rows; std::vector<mc_best_hit> best; mc_stats tot; memset(&tot, 0, sizeof tot);
-    const int L0 = h->read_len, FP0 = h->FP;
-    const uint8_t *saved_reads = h->reads_dev; const int64_t saved_n = h->nreads;
+    const McPieces P = mc_cut_pieces(vl_bins(start), stream_batch());
+    McResults R(h->keep_rows);
     int rc = 0;
-    if (!pieces.empty()) {
-        rc = vl_pools(h, Lmax, nmax);
-        bool pending = false;
-        auto collect = [&]() {
-            if (!pending) return;
-            pending = false;
-            if (h->keep_rows) { rows_wait(h); rows.insert(rows.end(), h->res_rows, h->res_rows + h->n_res_rows); }
-            best_materialize(h);
-            best.insert(best.end(), h->best.begin(), h->best.end());
-            stats_add(tot, h->stats);
-        };
-        auto begin = [&](const McVlPiece &q) -> int {
-            if (vl_use_length(h, q.L)) return -1;
-            h->reads_dev = d_sorted + boff[(size_t)q.L]; h->nreads = (int64_t)(start[(size_t)q.L + 1] - start[(size_t)q.L]);
-            return mc_range_begin(h, q.first, q.n, (int64_t)start[(size_t)q.L] + q.first);
-        };
-        // end(k), begin(k + 1), collect(k): the front of the next piece runs while the host takes the results of this one.  A piece
-        // that overflowed a pool is run again in smaller ranges while its length is still the handle's.
-        for (size_t k = 0; rc == 0 && k < pieces.size(); k++) {
-            if (k == 0 && (rc = begin(pieces[0])) != 0) break;
-            const McVlPiece &q = pieces[k];
-            rc = mc_range_end(h);
-            if (rc == -2) rc = mc_run_range(h, q.first, q.n, (int64_t)start[(size_t)q.L] + q.first);
-            if (rc) break;
-            pending = true;
-            if (k + 1 < pieces.size() && (rc = begin(pieces[k + 1])) != 0) break;
-            collect();
-        }
-        if (rc == 0) collect();
-        if (h->pipe_nout) (void)mc_range_end(h);                     // (after an error: nothing stays in flight)
+    if (!P.v.empty()) {
+        McLenBorrow len(h);
+        if ((rc = len.pools(P.Lmax, P.nmax)) == 0) rc = run_pieces(h, len, P.v, [&](const McPiece &q) { return d_sorted + boff[(size_t)q.L]; }, nullptr, R);
         rows_wait(h);
-        h->read_len = L0; h->FP = FP0;
-        const hipError_t e = hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice);   // the run's own tables back
-        if (rc == 0 && e != hipSuccess) { g_err = std::string("restoring the run's tables: ") + hipGetErrorString(e); rc = -1; }
+        rc = len.close(rc);                                          // the run's own tables back
     }
-    h->reads_dev = saved_reads; h->nreads = saved_n;
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
     if (rc) return rc;
     // results in the caller's order: rows grouped by original read (stable: a read's rows keep RAPsearch2's order), best hits sorted
     std::vector<int64_t> at((size_t)nreads + 1, 0);
-    for (const mc_row &r : rows) at[(size_t)perm[(size_t)r.query] + 1]++;
+    for (const mc_row &r : R.rows) at[(size_t)perm[(size_t)r.query] + 1]++;
     for (int64_t i = 0; i < nreads; i++) at[(size_t)i + 1] += at[(size_t)i];
-    std::vector<mc_row> &out = h->all_rows; out.resize(rows.size());
-    for (const mc_row &r : rows) { const uint32_t o = perm[(size_t)r.query]; mc_row &d = out[(size_t)at[o]++]; d = r; d.query = (int32_t)(first_read_id + o); }
-    for (mc_best_hit &b : best) b.read = (int32_t)(first_read_id + perm[(size_t)b.read]);
-    std::sort(best.begin(), best.end(), [](const mc_best_hit &x, const mc_best_hit &y) { return x.read < y.read; });
-    tot.reads += nshort;
-    if (h->abund) h->abund_searched += nshort;                       // (reads too short to have a frame: searched, no rows - as mc_stats.reads counts them)
-    h->res_rows = out.data(); h->n_res_rows = (int64_t)out.size(); h->best.swap(best); h->stats = tot;
+    std::vector<mc_row> &out = h->all_rows; out.resize(R.rows.size());
+    for (const mc_row &r : R.rows) { const uint32_t o = perm[(size_t)r.query]; mc_row &d = out[(size_t)at[o]++]; d = r; d.query = (int32_t)(first_read_id + o); }
+    for (mc_best_hit &b : R.best) b.read = (int32_t)(first_read_id + perm[(size_t)b.read]);
+    std::sort(R.best.begin(), R.best.end(), [](const mc_best_hit &x, const mc_best_hit &y) { return x.read < y.read; });
+    R.tot.reads += P.nshort;
+    if (h->abund) h->abund_searched += P.nshort;                       // (reads too short to have a frame: searched, no rows - as mc_stats.reads counts them)
+    h->res_rows = out.data(); h->n_res_rows = (int64_t)out.size(); h->best.swap(R.best); h->stats = R.tot;
     return 0;
 }
 
@@ -1382,7 +1410,7 @@ extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_
 
 // ---- reads of mixed lengths, each at its length class (mc_set_run_classes, mc_search_classes) -------------------------------------
 // A batch of padded rows is sorted into its classes on the device (k_classes.h) and the fixed-length pipeline runs once per non-empty
-// class, cut into ranges as search_varlen cuts its buckets: with the tables of that length (vl_use_length) and - unlike there - the
+// class, cut into ranges as search_varlen cuts its buckets: with the tables of that length (McLenBorrow::use) and - unlike there - the
 // classification parameters and length of that class.  No m8 rows: the best hits, their classes and the per-class counts.
 extern "C" int mc_set_run_classes(mc_handle *h, const int32_t *class_len, int32_t K, double loge_thr, const double *min_cov, const double *min_score,
                                   const int32_t *max_aaid, const int32_t *aln_stat)
@@ -1423,7 +1451,7 @@ static int cl_prologue(McDevBuf &B, hipStream_t st, const uint8_t *d_rows, int64
     if (ev) HIPCK(hipEventRecord(ev[0], st));
     k_cl_hist<<<dim3(ntiles), dim3(MC_CL_BS), 0, st>>>(d_rows, n, stride, C, mc_cl_lanes(stride), ntiles, d_cls, d_cnt);
     HIPCK(hipGetLastError());
-    k_cl_scan<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, nbins * ntiles, ntiles, nbins, d_start);
+    k_bin_scan<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, nbins * ntiles, ntiles, nbins, d_start);
     HIPCK(hipGetLastError());
     k_cl_scatter<<<dim3(ntiles), dim3(MC_CL_BS), 0, st>>>(d_cls, n, ntiles, nbins, d_cnt, S.d_perm);
     HIPCK(hipGetLastError());
@@ -1454,10 +1482,8 @@ static int cl_prologue(McDevBuf &B, hipStream_t st, const uint8_t *d_rows, int64
     return 0;
 }
 
-struct McClAcc { std::vector<mc_best_hit> best; std::vector<uint8_t> cls; mc_stats tot; int64_t reads[MC_CL_BINS]; };
-
-// one batch of rows, resident at d_rows: its best hits (global read ids) and counts are added to A
-static int classes_batch(mc_handle *h, const uint8_t *d_rows, int64_t n, int64_t first_read_id, McClAcc &A)
+// one batch of rows, resident at d_rows: its best hits (global read ids, tagged with their class) are added to R, its counts to reads
+static int classes_batch(mc_handle *h, const uint8_t *d_rows, int64_t n, int64_t first_read_id, McResults &R, int64_t *reads)
 {
     McCtx &c = h->ctx;
     const McClasses &C = h->cls;
@@ -1468,70 +1494,33 @@ static int classes_batch(mc_handle *h, const uint8_t *d_rows, int64_t n, int64_t
     std::vector<uint32_t> perm((size_t)nclassed);
     if (nclassed) HIPCK(hipMemcpyAsync(perm.data(), S.d_perm, perm.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
-    struct Piece { int k; int64_t first, n; };
-    std::vector<Piece> pieces;
-    const int64_t batch = stream_batch();
-    int kmax = -1; int64_t nmax = 0;
-    for (int k = 0; k <= C.K; k++) A.reads[k] += (int64_t)(S.start[(size_t)k + 1] - S.start[(size_t)k]);
-    for (int k = 0; k < C.K; k++) {
-        const int64_t cnt = (int64_t)S.G.cnt[k];
-        if (!cnt) continue;
-        for (int64_t a = 0; a < cnt; a += batch) pieces.push_back({k, a, std::min(batch, cnt - a)});
-        kmax = k; nmax = std::max(nmax, std::min(batch, cnt));
+    std::vector<McBin> bins;
+    for (int k = 0; k < C.K; k++) bins.push_back({C.len[k], (int64_t)S.G.cnt[k], (int64_t)S.G.first[k]});
+    const McPieces P = mc_cut_pieces(bins, stream_batch());            // (P.nshort is 0 here: mc_classes_check admits no class under 18 bases)
+    for (int k = 0; k <= C.K; k++) reads[k] += (int64_t)(S.start[(size_t)k + 1] - S.start[(size_t)k]);
+    R.tot.reads += n - nclassed;
+    if (P.v.empty()) return 0;
+    const size_t best0 = R.best.size();
+    int rc;
+    {
+        McModeGuard mode(h, h->best_only, true);                     // (a class run hands out no rows: they stay on the device)
+        McLenBorrow len(h);
+        if ((rc = len.pools(P.Lmax, P.nmax)) == 0)
+            rc = run_pieces(h, len, P.v, [&](const McPiece &q) { return S.d_sorted + S.G.word0[q.tag] * 16; }, h->cls_pars.data(), R);
+        rc = len.close(rc);                                          // the top class's tables and parameters back
     }
-    A.tot.reads += n - nclassed;
-    if (pieces.empty()) return 0;
-    const size_t best0 = A.best.size();
-    const int L0 = h->read_len, FP0 = h->FP;
-    const uint8_t *saved_reads = h->reads_dev; const int64_t saved_n = h->nreads;
-    const bool saved_stay = h->rows_stay;
-    h->rows_stay = true;                                             // (a class run hands out no rows: they stay on the device)
-    int rc = vl_pools(h, C.len[kmax], nmax);
-    bool pending = false; int pending_k = 0;
-    auto collect = [&]() {
-        if (!pending) return;
-        pending = false;
-        best_materialize(h);
-        A.best.insert(A.best.end(), h->best.begin(), h->best.end());
-        A.cls.insert(A.cls.end(), h->best.size(), (uint8_t)pending_k);
-        stats_add(A.tot, h->stats);
-    };
-    auto begin = [&](const Piece &q) -> int {
-        if (vl_use_length(h, C.len[q.k])) return -1;
-        HIPCK(hipMemcpy(h->d_P, &h->cls_pars[(size_t)q.k], sizeof(McClassPars), hipMemcpyHostToDevice));
-        h->reads_dev = S.d_sorted + S.G.word0[q.k] * 16; h->nreads = (int64_t)S.G.cnt[q.k];
-        return mc_range_begin(h, q.first, q.n, (int64_t)S.G.first[q.k] + q.first);
-    };
-    // end(j), begin(j + 1), collect(j), as search_varlen: the front of the next piece runs while the host takes the results of this one
-    for (size_t j = 0; rc == 0 && j < pieces.size(); j++) {
-        if (j == 0 && (rc = begin(pieces[0])) != 0) break;
-        const Piece &q = pieces[j];
-        rc = mc_range_end(h);
-        if (rc == -2) rc = mc_run_range(h, q.first, q.n, (int64_t)S.G.first[q.k] + q.first);
-        if (rc) break;
-        pending = true; pending_k = q.k;
-        if (j + 1 < pieces.size() && (rc = begin(pieces[j + 1])) != 0) break;
-        collect();
-    }
-    if (rc == 0) collect();
-    if (h->pipe_nout) (void)mc_range_end(h);                         // (after an error: nothing stays in flight)
-    h->rows_stay = saved_stay;
-    h->read_len = L0; h->FP = FP0;
-    hipError_t e = hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice);   // the top class's tables and parameters back
-    if (e == hipSuccess) e = hipMemcpy(h->d_P, &h->hP, sizeof(McClassPars), hipMemcpyHostToDevice);
-    if (rc == 0 && e != hipSuccess) { g_err = std::string("restoring the run's tables: ") + hipGetErrorString(e); rc = -1; }
-    h->reads_dev = saved_reads; h->nreads = saved_n;
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
     if (rc) return rc;
     // sorted positions -> global read ids, ascending (the batches follow each other in read order)
-    const size_t nb = A.best.size() - best0;
+    std::vector<mc_best_hit> &best = R.best; std::vector<uint8_t> &cls = R.tag;
+    const size_t nb = best.size() - best0;
     std::vector<std::pair<mc_best_hit, uint8_t>> tmp(nb);
     for (size_t i = 0; i < nb; i++) {
-        tmp[i] = {A.best[best0 + i], A.cls[best0 + i]};
+        tmp[i] = {best[best0 + i], cls[best0 + i]};
         tmp[i].first.read = (int32_t)(first_read_id + perm[(size_t)tmp[i].first.read]);
     }
     std::sort(tmp.begin(), tmp.end(), [](const std::pair<mc_best_hit, uint8_t> &x, const std::pair<mc_best_hit, uint8_t> &y) { return x.first.read < y.first.read; });
-    for (size_t i = 0; i < nb; i++) { A.best[best0 + i] = tmp[i].first; A.cls[best0 + i] = tmp[i].second; }
+    for (size_t i = 0; i < nb; i++) { best[best0 + i] = tmp[i].first; cls[best0 + i] = tmp[i].second; }
     return 0;
 }
 
@@ -1543,7 +1532,8 @@ static int classes_stream(mc_handle *h, const std::function<int64_t(uint8_t *, i
     const int64_t B = std::max<int64_t>(1, expect_reads > 0 ? std::min(stream_batch(), expect_reads) : stream_batch()), stride = mc_class_stride(h->cls);   // (expect_reads: the most the source can deliver)
     McDevBuf buf;
     uint8_t *d_rows = nullptr, *pin = nullptr;
-    McClAcc A; memset(&A.tot, 0, sizeof A.tot); memset(A.reads, 0, sizeof A.reads);
+    McResults R(false, nullptr, true);                               // (no rows; every best hit tagged with its class)
+    int64_t reads[MC_CL_BINS] = {};
     int rc = 0;
     int64_t cap = 0;
     for (;;) {
@@ -1555,14 +1545,14 @@ static int classes_stream(mc_handle *h, const std::function<int64_t(uint8_t *, i
         if (n > cap) { if (buf.get(&d_rows, (size_t)(n * stride) + MC_CL_SLACK)) { rc = -1; break; } cap = n; }   // (the first batch is the largest)
         if (hipMemcpyAsync(d_rows, pin, (size_t)(n * stride), hipMemcpyHostToDevice, h->ctx.stream) != hipSuccess ||
             hipMemsetAsync(d_rows + n * stride, 0, MC_CL_SLACK, h->ctx.stream) != hipSuccess || hipStreamSynchronize(h->ctx.stream) != hipSuccess) { g_err = "upload of the rows failed"; rc = -1; break; }
-        if ((rc = classes_batch(h, d_rows, n, first_read_id + at, A)) != 0) break;
+        if ((rc = classes_batch(h, d_rows, n, first_read_id + at, R, reads)) != 0) break;
         if (n < B) break;
     }
     if (pin) (void)hipHostFree(pin);
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr; h->best_cls.clear();
     if (rc) return rc;
-    h->best.swap(A.best); h->best_cls.swap(A.cls); h->stats = A.tot;
-    memcpy(h->cls_reads, A.reads, sizeof h->cls_reads);
+    h->best.swap(R.best); h->best_cls.swap(R.tag); h->stats = R.tot;
+    memcpy(h->cls_reads, reads, sizeof h->cls_reads);
     h->cls_results = true;
     return 0;
 }
@@ -2311,15 +2301,6 @@ static int train_range(mc_handle *h, int64_t first, int64_t count, int64_t first
     return 0;
 }
 
-// mc_train_library and mc_community_library run the handle in a mode of their own (best hits only or not, rows left on the device or
-// not); however they return, the caller's mode comes back
-struct McModeGuard {
-    mc_handle *h; bool best_only, rows_stay;
-    McModeGuard(mc_handle *h_, bool best, bool stay) : h(h_), best_only(h_->best_only), rows_stay(h_->rows_stay) { h->best_only = best; h->rows_stay = stay; }
-    McModeGuard(const McModeGuard &) = delete;
-    ~McModeGuard() { h->best_only = best_only; h->rows_stay = rows_stay; }
-};
-
 // one range of a library into the resident read buffer, between the events ev[0] and ev[1] on the handle's stream
 template <class S> static int simulate_resident(mc_handle *h, const S *s, uint64_t key, int64_t at, int64_t cnt, const McEvents &ev)
 {
@@ -2377,32 +2358,31 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
         h->train_ms[0] += ev_ms(ev[0], ev[1]);
         h->train_bases += cnt * L;
     }
-    const int FP0 = h->FP;
-    for (int64_t at = 0; at < nreads && rc == 0 && ref; at += B) {
-        const int64_t cnt = std::min(B, nreads - at);
-        int64_t bases = 0;
-        if (hipEventRecord(ev[0], st) != hipSuccess || simulate_var(g, L, key, at, cnt, d_lens, d_roff, d_sim, st, &bases)) { rc = -1; break; }
-        McDevBuf bb;
-        uint8_t *d_sorted = nullptr; uint32_t *d_perm = nullptr;
-        std::vector<uint32_t> start; std::vector<int64_t> boff;
-        if (vl_bucket(bb, st, d_sim, d_roff, cnt, bases, &d_sorted, &d_perm, start, boff) || hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess) { rc = -1; break; }
-        h->train_ms[0] += ev_ms(ev[0], ev[1]);
-        h->train_bases += bases;
-        std::vector<McVlPiece> pieces;
-        int Lmax = 0; int64_t nmax = 0, nshort = 0;
-        vl_pieces(start, B, pieces, Lmax, nmax, nshort);
-        tot.reads += nshort;
-        if (!pieces.empty() && (rc = vl_pools(h, Lmax, nmax)) != 0) break;
-        for (const McVlPiece &q : pieces) {
-            if ((rc = vl_use_length(h, q.L)) != 0) break;
-            h->reads_dev = d_sorted + boff[(size_t)q.L]; h->nreads = (int64_t)(start[(size_t)q.L + 1] - start[(size_t)q.L]);
-            if ((rc = train_range(h, q.first, q.n, at + (int64_t)start[(size_t)q.L] + q.first, G, d_bins, nbins, ev[2], ev[3], tot)) != 0) break;
+    if (ref) {
+        McLenBorrow len(h);
+        for (int64_t at = 0; at < nreads && rc == 0; at += B) {
+            const int64_t cnt = std::min(B, nreads - at);
+            int64_t bases = 0;
+            if (hipEventRecord(ev[0], st) != hipSuccess || simulate_var(g, L, key, at, cnt, d_lens, d_roff, d_sim, st, &bases)) { rc = -1; break; }
+            McDevBuf bb;
+            uint8_t *d_sorted = nullptr; uint32_t *d_perm = nullptr;
+            std::vector<uint32_t> start; std::vector<int64_t> boff;
+            if (vl_bucket(bb, st, d_sim, d_roff, cnt, bases, &d_sorted, &d_perm, start, boff) || hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess) { rc = -1; break; }
+            h->train_ms[0] += ev_ms(ev[0], ev[1]);
+            h->train_bases += bases;
+            const McPieces P = mc_cut_pieces(vl_bins(start), B);
+            tot.reads += P.nshort;
+            if (!P.v.empty() && (rc = len.pools(P.Lmax, P.nmax)) != 0) break;
+            // a plain loop, not run_pieces: the grid reads a piece's rows where they lie, before the next front may overwrite them
+            for (const McPiece &q : P.v) {
+                if ((rc = len.use(q.L)) != 0) break;
+                h->reads_dev = d_sorted + boff[(size_t)q.L]; h->nreads = q.bin_n;
+                if ((rc = train_range(h, q.first, q.n, at + q.bin_first + q.first, G, d_bins, nbins, ev[2], ev[3], tot)) != 0) break;
+            }
+            (void)hipStreamSynchronize(st);                          // (the bucket buffers are freed at the end of the range)
         }
-        (void)hipStreamSynchronize(st);                              // (the bucket buffers are freed at the end of the range)
-    }
-    if (ref) {                                                       // the run's own length and tables back
-        h->read_len = L; h->FP = FP0; h->reads_dev = nullptr; h->nreads = 0;
-        if (hipMemcpy(h->d_T, &h->hT, sizeof(McTables), hipMemcpyHostToDevice) != hipSuccess && rc == 0) { g_err = "restoring the run's tables failed"; rc = -1; }
+        rc = len.close(rc);                                          // the run's own length and tables back
+        h->reads_dev = nullptr; h->nreads = 0;                       // (the buckets the handle read from are gone)
     }
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
     std::vector<unsigned long long> bins(nbins * 3);

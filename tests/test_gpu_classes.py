@@ -235,3 +235,57 @@ def test_validate_length_mix_pools_its_passes(tmp_path):
     assert rows[1][:4] == ["random000", "100+150", "4", "50001"] and float(rows[1][5]) == r["est_ags"]
     tsv = training.read_map(str(tmp_path / "out" / "communities" / "random000.tsv"), header=True)
     assert [int(x[4]) for x in tsv] == r["member_reads"]
+
+
+def _same_rows(a, b):
+    """m8 rows equal field by field (the record has padding bytes, which nobody writes)"""
+    return len(a) == len(b) and all((a[f] == b[f]).all() for f in a.dtype.names)
+
+
+def test_class_piece_boundaries_and_handle_back(engine, mixed, monkeypatch):
+    """1,000, 1,001 and 1 rows of three classes beside 3 rows too short, interleaved, at the smallest batch: the rows arrive in batches of
+    1,000, 1,000 and 5, each cut into one piece per class present (a class never exceeds its batch, so no class is cut in two here;
+    test_every_class_equals_its_single_length_run does that).  Best hits and classes are those of the per-class single-length runs,
+    and a second class run straight after is byte-identical.
+    The handle comes back: a fixed-length search at the top class's length and a run over resident reads, taken after
+    mc_set_run_classes, are repeated after the class runs with NO mc_set_run or mc_set_run_classes between, the last of them a run
+    whose last piece is of 100 bp - so length, frame pitch, tables, parameters (d_P) and the resident reads were all another
+    class's when it ended, and only the restore makes them the top class's again."""
+    seqs, lens = mixed
+    classes, counts = [50, 100, 150], [1000, 1001, 1, 3]
+    all_cls = cr.class_of(np.minimum(lens, classes[-1]), classes)
+    pick = np.concatenate([np.flatnonzero(all_cls == k)[:c] for k, c in enumerate(counts)])
+    np.random.default_rng(5).shuffle(pick)                                       # the classes interleaved: every batch of rows holds several
+    rows = cr.make_rows([seqs[i] for i in pick], classes[-1])
+    want_cls = all_cls[pick]
+    r150 = np.stack([np.frombuffer(s[:150], np.uint8) for s, n in zip(seqs, lens) if n >= 150][:2000])
+    monkeypatch.setenv("MC_STREAM_BATCH", "1000")
+    _set_classes(engine, classes)
+    rows0, best0 = engine.search(r150)                                           # the handle's single-length state: the top class's
+    engine.upload(r150[:700])
+    engine.run(first_read_id=5)
+    res0 = engine.results()
+    assert len(rows0) > 0 and len(best0) > 0 and len(res0[1]) > 0
+    best, cls, class_reads = engine.search_classes(rows, first_read_id=7)
+    assert engine.stats()["reads"] == len(rows) == 2005 and len(engine.rows()) == 0
+    best2, cls2, class_reads2 = engine.search_classes(rows, first_read_id=7)
+    assert len(best) > 0 and best2.tobytes() == best.tobytes() and cls2.tobytes() == cls.tobytes()
+    assert class_reads.tolist() == counts == class_reads2.tolist()
+    assert (np.diff(best["read"]) > 0).all() and (cls == want_cls[best["read"] - 7]).all()
+    _, cls3, class_reads3 = engine.search_classes(rows[want_cls < 2][:1500])     # batches of 1,000 and 500: the last piece is of class 0 or 1
+    assert class_reads3[2:].tolist() == [0, 0] and len(cls3) > 0
+    engine.run(first_read_id=5)                                                  # the resident reads are still the uploaded ones
+    res1 = engine.results()
+    assert _same_rows(res1[0], res0[0]) and res1[1].tobytes() == res0[1].tobytes()
+    rows1, best1 = engine.search(r150)
+    assert _same_rows(rows1, rows0) and best1.tobytes() == best0.tobytes()
+    with_hits = 0
+    for k, L in enumerate(classes):
+        idx = np.flatnonzero(want_cls == k)
+        got = best[cls == k].copy()
+        got["read"] = np.searchsorted(idx, got["read"] - 7)                      # renumbered by rank inside the class
+        engine.set_run(L, MODEL["pars"][str(L)], FAMS)
+        _, want = engine.search(rows[idx, :L])
+        assert _same(got, want), "class %d (%d bp)" % (k, L)
+        with_hits += len(want) > 0
+    assert with_hits >= 1 and len(best[cls == 1]) > 0

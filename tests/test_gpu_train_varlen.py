@@ -197,3 +197,35 @@ def test_training_rates_use_the_real_bp(tmp_path):
     assert np.allclose(got["_rates"][150], rates, rtol=1e-12, atol=0)
     rates_nominal = training.rates_by_candidate([c[0] for c in counts], [c[1] for c in counts], [c[2] for c in counts], nominal)
     assert not np.allclose(got["_rates"][150], rates_nominal, rtol=1e-9, atol=0)
+
+
+def test_handle_comes_back_after_reference_length_training(monkeypatch):
+    """A fixed-length search, one reference-length library of three ranges, the same search again WITHOUT another set_run: identical
+    rows and best hits - the run's length, frame pitch and tables are the handle's again, and the resident reads hold no range."""
+    from microbecensus_amd import synth
+    monkeypatch.setenv("MC_STREAM_BATCH", "1000")
+    name, bases, off = mk.load_genome(3)
+    _, mseqs = _native.load_markers()
+    reads = synth.sample_reads(synth.build_genomes(mseqs, total_bp=400_000, seed=7, marker_gene_fraction=0.2), 2000, 150, seed=3)
+    g = _native.Genome(bases, off, 0)
+    eng = _native.Engine(device=0)
+    try:
+        eng.set_run(150)
+        rows0, best0 = eng.search(reads)
+        g.set_library("uniform", 0.05)
+        g.set_read_lengths(True)
+        eng.train_library(g, 3000, 5, training.library_id(name, 150), *GRID)
+        assert eng.stats()["reads"] == 3000 and eng.train_library_bases() != 3000 * 150      # reads of several lengths: the tables were switched
+        with pytest.raises(RuntimeError, match="range outside the resident read set"):
+            eng.run_range(0, 1)                                                # (training leaves no resident reads behind)
+        rows1, best1 = eng.search(reads)
+        eng.upload(reads)
+        eng.run()
+        rows2, best2 = eng.results()
+    finally:
+        eng.close()
+        g.close()
+    assert len(rows0) > 0 and len(best0) > 0
+    for rows, best in ((rows1, best1), (rows2, best2)):
+        assert len(rows) == len(rows0) and all((rows[f] == rows0[f]).all() for f in rows.dtype.names)
+        assert best.tobytes() == best0.tobytes()

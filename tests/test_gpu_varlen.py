@@ -168,3 +168,78 @@ def test_search_varlen_refusals(eng):
             eng.search_varlen(seqs)
     rows, best = eng.search_varlen([b"ACGTACGTAC", b"ACGTAC"])             # reads under 18 bases: no rows, nothing searched
     assert len(rows) == 0 and len(best) == 0 and eng.stats()["reads"] == 2
+
+
+# ---- piece boundaries, and the handle after a borrowed-length run -------------------------------------------------------------------
+BOUNDARY_COUNTS = [(17, 5), (18, 1), (150, 1000), (151, 1001), (200, 2096)]       # 4,103 reads: more than one 4,096-read tile of the bucketing kernels
+
+
+@pytest.fixture(scope="module")
+def boundary(eng):
+    """(reads2d, lens, rows of the per-length yardstick, best hits of the 150 bp reads at set_run(150)): the lengths interleaved; under a
+    batch of 1,000 the buckets are one piece of 1 read, one of exactly the batch, batch + 1 and 2 x batch + 96."""
+    names, mseqs = _native.load_markers()
+    genome = synth.build_genomes(mseqs, total_bp=400_000, seed=7, marker_gene_fraction=0.2)
+    lens = np.repeat([L for L, _ in BOUNDARY_COUNTS], [c for _, c in BOUNDARY_COUNTS]).astype(np.int64)
+    np.random.RandomState(12).shuffle(lens)
+    reads = synth.sample_reads(genome, len(lens), 200, seed=13)
+    assert "MC_STREAM_BATCH" not in os.environ
+    want = _per_length(eng, reads, lens)
+    idx = np.nonzero(lens == 150)[0]
+    eng.set_run(150)
+    _, b150 = eng.search(reads[idx, :150])
+    b150["read"] = idx[b150["read"]]
+    assert len(want) > 500 and len(b150) > 0 and len(set(lens[want["query"]].tolist())) >= 3
+    return reads, lens, want, b150
+
+
+@pytest.mark.parametrize("batch", ["1000", None], ids=["batch-1000", "one-piece-per-length"])
+def test_varlen_piece_boundaries(eng, boundary, batch, monkeypatch):
+    """Buckets of 1, batch, batch + 1 and 2 x batch + 96 reads beside reads too short to search: the rows are those of per-length
+    mc_search runs, the best hits of the run's own length those of mc_search, however the buckets are cut into pieces.
+    _per_length yields rows only, and a per-length mc_search cannot restate the best hits of the other lengths: a mixed run classifies
+    every read at mc_set_run()'s length (150), mc_search at the length it was set up for.  So only the 150 bp bucket's best hits have
+    an independent yardstick; for the other lengths the test asks that they are best hits of reads with rows, ascending, and the
+    same under both cuts - which compares the code with itself."""
+    reads, lens, want, b150 = boundary
+    if batch:
+        monkeypatch.setenv("MC_STREAM_BATCH", batch)
+    eng.set_run(150)
+    rows, best = eng.search_varlen(_as_varlen(reads, lens))
+    st = eng.stats()
+    assert st["reads"] == len(lens) == 4103 and st["rows"] == len(rows)
+    assert len(rows) == len(want) and _same(rows, want)
+    assert _same(best[lens[best["read"]] == 150], b150)
+    assert (np.diff(best["read"]) > 0).all() and set(best["read"].tolist()) <= set(rows["query"].tolist())
+    if batch:                                                          # the best hits of every length do not depend on the cut either
+        monkeypatch.delenv("MC_STREAM_BATCH")
+        _, best_whole = eng.search_varlen(_as_varlen(reads, lens))
+        assert _same(best, best_whole)
+
+
+@pytest.mark.parametrize("case", ["pieces", "all-short"])
+def test_handle_comes_back_after_search_varlen(eng, boundary, case, monkeypatch):
+    """A fixed-length search, a varlen call, the same search again WITHOUT another set_run: identical (rows field by field: their padding bytes are nobody's; best hits byte for byte), equal counts - the run's
+    length, frame pitch, tables and resident reads are the handle's again.  all-short: no piece, the tables were never switched."""
+    reads, lens, _, _ = boundary
+    r150 = np.ascontiguousarray(reads[lens == 150, :150])
+    monkeypatch.setenv("MC_STREAM_BATCH", "1000")
+    eng.set_run(150)
+    rows0, best0 = eng.search(r150)
+    st0 = eng.stats()
+    eng.upload(r150[:700])
+    eng.run(first_read_id=5)
+    res0 = eng.results()
+    if case == "pieces":
+        rows, _ = eng.search_varlen(_as_varlen(reads, lens))
+        assert len(rows) > 0 and eng.stats()["reads"] == len(lens)
+    else:
+        rows, best = eng.search_varlen([b"ACGTACGTACGTACGTA", b"ACGTAC", b"A"])
+        assert len(rows) == 0 and len(best) == 0 and eng.stats()["reads"] == 3
+    eng.run(first_read_id=5)                                           # the resident reads are still the uploaded ones
+    res1 = eng.results()
+    assert len(res0[0]) > 0 and _same(res1[0], res0[0]) and res1[1].tobytes() == res0[1].tobytes()
+    rows1, best1 = eng.search(r150)
+    st1 = eng.stats()
+    assert len(rows0) > 0 and len(best0) > 0 and _same(rows1, rows0) and best1.tobytes() == best0.tobytes()
+    assert {k: st0[k] for k in STAT_COUNTS} == {k: st1[k] for k in STAT_COUNTS}
