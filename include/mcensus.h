@@ -162,6 +162,9 @@ int mc_ranges_in_flight(const mc_handle *h);
  * window, those it sent on to full-size rows (AlignGapped@0x40a550); defined for a range that ran unsplit (mc_stats.range_splits
  * == 0).  Returns the number of bytes (copied to dst when they fit cap_bytes; dst may be NULL to ask for the size), -1 on error. */
 int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap_bytes, int32_t *record_bytes);
+/* Test aid (tests/test_gpu_owned.py): what the library holds of the HIP runtime in this process, over all handles - out[0] device
+ * buffers, [1] pinned host buffers, [2] streams, [3] events.  Counted where each is made and destroyed (csrc/mc_owned.h). */
+void mc_debug_live(int64_t out[4]);
 
 /* The seed kernel can count the index reads of the reference's algorithm for the batch (mc_stats.bucket_lookups /
  * key_probes: what CHashSearch::Searching@0x415050 / ExtendSeq2Set@0x413b90 would read - bench.py reports the rate at which

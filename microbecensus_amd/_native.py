@@ -219,6 +219,8 @@ def load_library():
     lib.mc_abundance_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.mc_abundance_ms.restype = C.c_float
     lib.mc_abundance_ms.argtypes = [C.c_void_p]
+    lib.mc_debug_live.restype = None
+    lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -233,7 +235,7 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_community_open", "mc_community_close", "mc_community_set_library", "mc_community_simulate", "mc_community_library", "mc_community_member_reads",
                     "mc_community_times",
                     "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride",
-                    "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms"]
+                    "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms", "mc_debug_live"]
 
 
 class DupSet:
@@ -461,6 +463,13 @@ def quality_offset(path):
     qualities, an unreadable file: it then fails the way the reference does)."""
     v = load_library().mc_quality_offset(path.encode())
     return v if v in (32, 64) else None
+
+
+def debug_live():
+    """Test aid (mc_debug_live): the device buffers, pinned host buffers, streams and events the library holds in this process."""
+    out = (C.c_int64 * 4)()
+    load_library().mc_debug_live(out)
+    return tuple(out)
 
 
 def rapdb_verify(rapdb_path, names, seqs):

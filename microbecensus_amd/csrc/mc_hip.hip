@@ -35,6 +35,7 @@
 #include "k_wfit.h"
 #include "k_abundance.h"
 #include "mc_pieces.h"
+#include "mc_owned.h"
 
 #include <map>
 
@@ -45,20 +46,20 @@
 // handle: what overlaps is the host's work on the results of one range with the front of the next, and that needs no second set of
 // pools - range_begin.
 struct McCtx {
-    hipStream_t stream = nullptr, side = nullptr, side2 = nullptr;   // the pipeline of a range, and two side streams of the ordering / finishing kernels
-    hipEvent_t ev[8] = {}, ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
+    McStream stream; hipStream_t side = nullptr, side2 = nullptr;   // the pipeline of a range, and two side streams of the ordering / finishing kernels (borrowed: the handle's)
+    McEvent ev[8], ev_fork, ev_join, ev_join2;
     int64_t cap_reads = 0; int pool_len = 0;                       // the pools hold cap_reads reads of up to pool_len bases
     uint32_t cap_tasks = 0, cap_gaps = 0, cap_hsps = 0, cap_rows = 0;
-    uint8_t *d_frames = nullptr, *d_frames_base = nullptr;   // (64 bytes of room in front: k_eval_seeds reads 8 bytes at a time backwards from a seed)
-    unsigned long long *d_stats = nullptr;
-    McSeedTask *d_tasks = nullptr; McGapTask *d_gaps = nullptr; McHsp *d_hsps = nullptr, *d_v = nullptr, *d_tmp = nullptr;
-    uint64_t *d_k64 = nullptr, *d_hkeys = nullptr, *d_hplace = nullptr, *d_places = nullptr; uint32_t *d_idx = nullptr, *d_idxo = nullptr, *d_heads = nullptr, *d_scan = nullptr, *d_gsz = nullptr, *d_nv = nullptr; uint32_t *d_ghist = nullptr;
-    uint32_t *d_counters = nullptr;
-    McRow *d_rows = nullptr; uint32_t *d_nrow = nullptr, *d_rowoff = nullptr; McBestHit *d_best = nullptr, *d_bestof = nullptr; uint8_t *d_low = nullptr, *d_cand = nullptr;
-    McGapCell *d_gws_full = nullptr; uint32_t *d_retry = nullptr, *d_retry2 = nullptr; int gap_threads_full = 0;
-    unsigned long long *d_gtab = nullptr; uint32_t gtab_slots = 0; uint32_t *d_gleader = nullptr; McFlankOut *d_fout = nullptr;
+    McDev<uint8_t> d_frames_base; uint8_t *d_frames = nullptr;   // (a view 64 bytes in: k_eval_seeds reads 8 bytes at a time backwards from a seed)
+    McDev<unsigned long long> d_stats;
+    McDev<McSeedTask> d_tasks; McDev<McGapTask> d_gaps; McDev<McHsp> d_hsps, d_v, d_tmp;
+    McDev<uint64_t> d_k64, d_hkeys, d_hplace, d_places; McDev<uint32_t> d_idx, d_idxo, d_heads, d_scan, d_gsz, d_nv, d_ghist;
+    McDev<uint32_t> d_counters;
+    McDev<McRow> d_rows; McDev<uint32_t> d_nrow, d_rowoff; McDev<McBestHit> d_best, d_bestof; McDev<uint8_t> d_low, d_cand;
+    McDev<McGapCell> d_gws_full; McDev<uint32_t> d_retry, d_retry2; int gap_threads_full = 0;
+    McDev<unsigned long long> d_gtab; uint32_t gtab_slots = 0; McDev<uint32_t> d_gleader; McDev<McFlankOut> d_fout;
     // pinned host mirrors
-    uint32_t *h_c = nullptr; unsigned long long *h_stats = nullptr; McBestHit *h_best = nullptr; size_t h_best_cap = 0;
+    McPin<uint32_t> h_c; McPin<unsigned long long> h_stats; McPin<McBestHit> h_best; size_t h_best_cap = 0;
     // the range being processed
     const uint8_t *reads = nullptr; int64_t n = 0, first_read_id = 0;
     uint32_t ntasks = 0, ngaps = 0, gpad = 0, nh = 0, nh_all = 0, nheads = 0, nrows = 0, nbest = 0, nsegs = 0;
@@ -70,13 +71,13 @@ struct mc_handle {
     std::vector<int32_t> fam;
     int nfam = 0, device = 0;
     // device index + tables
-    uint8_t *d_res = nullptr, *d_res_base = nullptr; uint32_t *d_off = nullptr, *d_bstart = nullptr, *d_post = nullptr; unsigned long long *d_post8 = nullptr; uint16_t *d_keys = nullptr; int32_t *d_fam = nullptr;
-    McTables *d_T = nullptr; McClassPars *d_P = nullptr;
+    McDev<uint8_t> d_res_base; uint8_t *d_res = nullptr; McDev<uint32_t> d_off, d_bstart, d_post; McDev<unsigned long long> d_post8; McDev<uint16_t> d_keys; McDev<int32_t> d_fam;   // (d_res: a view 64 bytes in)
+    McDev<McTables> d_T; McDev<McClassPars> d_P;
     McTables hT; McClassPars hP;
     int read_len = 0, FP = 0; bool run_set = false;
-    uint32_t *d_bitmap = nullptr;
-    McBucketRec *d_rec = nullptr;
-    uint32_t *d_filt = nullptr, *d_wild = nullptr, *d_pair = nullptr; uint64_t *d_segtab = nullptr; unsigned long long *d_rt = nullptr;
+    McDev<uint32_t> d_bitmap;
+    McDev<McBucketRec> d_rec;
+    McDev<uint32_t> d_filt, d_wild, d_pair; McDev<uint64_t> d_segtab; McDev<unsigned long long> d_rt;
     bool fast_enum = false;
     bool count_traffic = false;
     int pipe_nout = 0;                    // mc_range_begin / mc_range_end: 1 while a range has been begun and not ended
@@ -90,21 +91,20 @@ struct mc_handle {
     float wfit_ms = 0;                    // mc_fit_weights / mc_weights_mue: the kernels of the last call (HIP events)
     // mc_set_abundance: the cut-offs, the (nseq + 1) x 2 device counters ([s]: reads, aligned of subject s; [nseq][0]: assigned), the reads
     // of the completed ranges, the kernels' time since the last reset and the two events around the kernel of a range
-    bool abund = false; McAbundPars abund_pars = {}; unsigned long long *d_abund = nullptr; int64_t abund_searched = 0; float abund_ms = 0;
-    hipEvent_t ev_abund[2] = {nullptr, nullptr};
-    uint8_t *stage_pin[2] = {}, *stage_dev[2] = {}; size_t stage_bytes = 0; hipStream_t copy_stream = nullptr;   // run_stream
+    bool abund = false; McAbundPars abund_pars = {}; McDev<unsigned long long> d_abund; int64_t abund_searched = 0; float abund_ms = 0;
+    McEvent ev_abund[2];
+    McPin<uint8_t> stage_pin[2]; McDev<uint8_t> stage_dev[2]; size_t stage_bytes = 0; McStream copy_stream;   // run_stream (stage_bytes: what all four hold, 0 until they do)
     // resident reads
     int64_t nreads = 0, cap_own = 0;
-    uint8_t *d_reads = nullptr;
+    McDev<uint8_t> d_reads;
     const uint8_t *reads_dev = nullptr;   // resident read set (own buffer or attached caller memory)
     McCtx ctx;
     // host results: rows of the last run land in pinned memory; mc_search() accumulates its batches in all_rows
     // The rows travel to the host while the caller goes on (two pinned buffers in turn, a stream and an event of their own):
     // mc_run_range() returns when the best hits are there; whoever looks at the rows waits for their copy (rows_wait).
-    mc_row *pin_slot[2] = {nullptr, nullptr}; size_t pin_slot_cap[2] = {0, 0}; int pin_cur = 0;
-    mc_row *pin_rows = nullptr; size_t pin_cap = 0;                // the slot of the current run
-    hipStream_t side = nullptr, side2 = nullptr;                    // (McCtx::side, side2)
-    hipStream_t rows_stream = nullptr; hipEvent_t ev_rows = nullptr; bool rows_pending = false, rows_ever = false;
+    McPin<mc_row> pin_slot[2]; size_t pin_slot_cap[2] = {0, 0}; int pin_cur = 0;   // (pin_cur: the slot of the current run)
+    McStream side, side2;                                           // (McCtx::side, side2)
+    McStream rows_stream; McEvent ev_rows; bool rows_pending = false, rows_ever = false;
     std::vector<mc_row> all_rows, split_rows;                       // accumulated over the batches of a stream / over the halves of a range that overflowed
     const mc_row *res_rows = nullptr; int64_t n_res_rows = 0;
     std::vector<mc_best_hit> best; mc_stats stats;
@@ -121,30 +121,7 @@ static McIndex dev_index(const mc_handle *h)
     return X;
 }
 
-template <class Tp> static int dalloc(Tp **p, size_t n)
-{
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    HIPCK(hipMalloc((void **)p, n * sizeof(Tp)));
-    return 0;
-}
-
-// Scoped owners of what a call makes on the device, so that no return path leaves any of it behind: buffers ...
-struct McDevBuf {
-    std::vector<void *> p;
-    template <class Tp> int get(Tp **x, size_t n) { HIPCK(hipMalloc((void **)x, std::max<size_t>(n, 1) * sizeof(Tp))); p.push_back(*x); return 0; }
-    McDevBuf() = default;
-    McDevBuf(const McDevBuf &) = delete;
-    ~McDevBuf() { for (void *q : p) (void)hipFree(q); }
-};
-// ... and events
-struct McEvents {
-    std::vector<hipEvent_t> e;
-    int make(int n) { for (int k = 0; k < n; k++) { hipEvent_t x; if (hipEventCreate(&x) != hipSuccess) { g_err = "hipEventCreate failed"; return -1; } e.push_back(x); } return 0; }
-    hipEvent_t operator[](int k) const { return e[(size_t)k]; }
-    McEvents() = default;
-    McEvents(const McEvents &) = delete;
-    ~McEvents() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-};
+extern "C" void mc_debug_live(int64_t out[4]) { for (int k = 0; k < MC_LIVE_N; k++) out[k] = mc_live[k].load(); }
 
 extern "C" int mc_device_count(void)
 {
@@ -153,33 +130,13 @@ extern "C" int mc_device_count(void)
     return n;
 }
 
-static void ctx_free(McCtx &c)
-{
-    void *ptrs[] = {c.d_frames_base, c.d_tasks, c.d_gaps, c.d_hsps, c.d_v, c.d_tmp, c.d_k64, c.d_hkeys, c.d_hplace, c.d_places, c.d_idx, c.d_idxo, c.d_heads, c.d_scan, c.d_gsz, c.d_nv, c.d_ghist, c.d_counters, c.d_rows,
-                    c.d_nrow, c.d_rowoff, c.d_best, c.d_bestof, c.d_low, c.d_cand, c.d_gws_full, c.d_retry, c.d_retry2, c.d_gtab, c.d_gleader, c.d_fout, c.d_stats};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (void *p : {(void *)c.h_c, (void *)c.h_stats, (void *)c.h_best}) if (p) (void)hipHostFree(p);
-    for (auto &e : c.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {c.ev_fork, c.ev_join, c.ev_join2}) if (e) (void)hipEventDestroy(e);
-    if (c.stream) (void)hipStreamDestroy(c.stream);                // (side, side2: the handle's)
-    c = McCtx();
-}
-
+// Every resource of the handle is a member that frees itself (mc_owned.h).  What is left is order: the rows of the last run may
+// still be on their way into a pinned slot, and that copy has to end before the slot does.
 extern "C" void mc_close(mc_handle *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    void *ptrs[] = {h->d_res_base, h->d_off, h->d_bstart, h->d_post, h->d_post8, h->d_keys, h->d_fam, h->d_T, h->d_P, h->d_reads, h->d_bitmap, h->d_rec, h->d_filt, h->d_wild, h->d_pair, h->d_rt, h->d_segtab};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    ctx_free(h->ctx);
-    for (int k = 0; k < 2; k++) { if (h->stage_pin[k]) (void)hipHostFree(h->stage_pin[k]); if (h->stage_dev[k]) (void)hipFree(h->stage_dev[k]); }
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    for (hipStream_t q : {h->side, h->side2}) if (q) (void)hipStreamDestroy(q);
-    if (h->rows_stream) { (void)hipStreamSynchronize(h->rows_stream); (void)hipStreamDestroy(h->rows_stream); }
-    if (h->ev_rows) (void)hipEventDestroy(h->ev_rows);
-    if (h->d_abund) (void)hipFree(h->d_abund);
-    for (hipEvent_t e : h->ev_abund) if (e) (void)hipEventDestroy(e);
-    for (mc_row *p : h->pin_slot) if (p) (void)hipHostFree(p);
+    if (h->rows_stream) (void)hipStreamSynchronize(h->rows_stream);
     delete h;
 }
 
@@ -188,11 +145,11 @@ extern "C" void mc_close(mc_handle *h)
 // open that way (the reference's default use is ONE run per process: microbe_census.py:375) - this takes ~25.
 struct McUploader {
     static constexpr size_t CH = (size_t)8 << 20;
-    uint8_t *pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; hipStream_t st = nullptr; int k = 0; bool used[2] = {false, false};
+    McPin<uint8_t> pin[2]; McEvent ev[2]; McStream st; int k = 0; bool used[2] = {false, false};
     int init()
     {
-        HIPCK(hipStreamCreate(&st));
-        for (int i = 0; i < 2; i++) { HIPCK(hipHostMalloc((void **)&pin[i], CH, hipHostMallocDefault)); HIPCK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
+        if (st.create()) return -1;
+        for (int i = 0; i < 2; i++) if (pin[i].alloc(CH) || ev[i].create(false)) return -1;
         return 0;
     }
     int put(void *dst, const void *src, size_t bytes)
@@ -208,11 +165,7 @@ struct McUploader {
         return 0;
     }
     int finish() { if (st) HIPCK(hipStreamSynchronize(st)); return 0; }
-    ~McUploader()
-    {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (int i = 0; i < 2; i++) { if (pin[i]) (void)hipHostFree(pin[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); }
-    }
+    ~McUploader() { if (st) (void)hipStreamSynchronize(st); }       // (a copy may still read a bounce buffer)
 };
 
 // h->H holds the host index (built from FASTA or loaded from a rapdb): everything device side
@@ -237,26 +190,25 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
     // says otherwise) and streams that share one wait for each other: with nine streams the front of a range could land behind the
     // 5 ms copy of the rows of the range before (measured: 51.2 instead of 53.6 M reads/s) - hence few streams.  The queue count is
     // the environment's: neither this library nor the package's entry points set it.
-    HIPCK(hipStreamCreate(&h->side)); HIPCK(hipStreamCreate(&h->side2));
+    if (h->side.create() || h->side2.create()) return -1;
     {
         McCtx &c = h->ctx;
-        HIPCK(hipStreamCreate(&c.stream)); c.side = h->side; c.side2 = h->side2;
-        for (auto &e : c.ev) HIPCK(hipEventCreate(&e));
-        HIPCK(hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming)); HIPCK(hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&c.ev_join2, hipEventDisableTiming));
-        if (dalloc(&c.d_counters, C_N) || dalloc(&c.d_stats, S_N) || dalloc(&c.d_ghist, (size_t)MC_GS_BINS)) return -1;
-        HIPCK(hipHostMalloc((void **)&c.h_c, sizeof(uint32_t) * C_N, hipHostMallocDefault));
-        HIPCK(hipHostMalloc((void **)&c.h_stats, sizeof(unsigned long long) * S_N, hipHostMallocDefault));
+        if (c.stream.create()) return -1;
+        c.side = h->side; c.side2 = h->side2;
+        for (auto &e : c.ev) if (e.create()) return -1;
+        if (c.ev_fork.create(false) || c.ev_join.create(false) || c.ev_join2.create(false)) return -1;
+        if (c.d_counters.alloc(C_N) || c.d_stats.alloc(S_N) || c.d_ghist.alloc((size_t)MC_GS_BINS)) return -1;
+        if (c.h_c.alloc(C_N) || c.h_stats.alloc(S_N)) return -1;
     }
-    HIPCK(hipStreamCreate(&h->rows_stream)); HIPCK(hipEventCreateWithFlags(&h->ev_rows, hipEventDisableTiming));
+    if (h->rows_stream.create() || h->ev_rows.create(false)) return -1;
     const McHostIndex &H = h->H;
     if (H.res.size() >= MC_TASK_ABS_LIMIT) { g_err = "marker database too large: more than 16 M residues (MC_TASK_W3)"; return -1; }
-    if (dalloc(&h->d_res_base, H.res.size() + 128) || dalloc(&h->d_off, H.off.size()) || dalloc(&h->d_bstart, H.bstart.size()) || dalloc(&h->d_post, H.post.size() + 1) || dalloc(&h->d_post8, (H.post.size() + 1) * MC_POST_WORDS) ||
-        dalloc(&h->d_keys, H.keys.size()) || dalloc(&h->d_fam, (size_t)nseq) || dalloc(&h->d_T, 1) || dalloc(&h->d_P, 1)) return -1;
+    if (h->d_res_base.alloc(H.res.size() + 128) || h->d_off.alloc(H.off.size()) || h->d_bstart.alloc(H.bstart.size()) || h->d_post.alloc(H.post.size() + 1) || h->d_post8.alloc((H.post.size() + 1) * MC_POST_WORDS) ||
+        h->d_keys.alloc(H.keys.size()) || h->d_fam.alloc((size_t)nseq) || h->d_T.alloc(1) || h->d_P.alloc(1)) return -1;
     HIPCK(hipMemset(h->d_res_base, MC_INV, H.res.size() + 128));
     h->d_res = h->d_res_base + 64;                                 // (k_gapped_lds reads 16 bytes at a time around a flank's first residues)
-    if (dalloc(&h->d_bitmap, H.bitmap.size()) || dalloc(&h->d_filt, H.filt.size()) || dalloc(&h->d_wild, H.wild.size()) || dalloc(&h->d_pair, H.pair.size()) || dalloc(&h->d_rt, H.rt.size())) return -1;
-    if (!H.rec.empty() && dalloc(&h->d_rec, H.rec.size())) return -1;
+    if (h->d_bitmap.alloc(H.bitmap.size()) || h->d_filt.alloc(H.filt.size()) || h->d_wild.alloc(H.wild.size()) || h->d_pair.alloc(H.pair.size()) || h->d_rt.alloc(H.rt.size())) return -1;
+    if (!H.rec.empty() && h->d_rec.alloc(H.rec.size())) return -1;
     {
         McUploader up;
         if (up.init() || up.put(h->d_res, H.res.data(), H.res.size()) || up.put(h->d_off, H.off.data(), H.off.size() * 4) || up.put(h->d_bstart, H.bstart.data(), H.bstart.size() * 4) ||
@@ -432,7 +384,7 @@ extern "C" int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const
     if (!h->d_segtab) {   // Seg::getprob of every short window, tabulated once (ln n! does not depend on the run)
         std::vector<uint64_t> tab;
         mc_build_segtab(h->hT.lnfac, tab);
-        if (dalloc(&h->d_segtab, tab.size())) return -1;
+        if (h->d_segtab.alloc(tab.size())) return -1;
         HIPCK(hipMemcpy(h->d_segtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
     }
     HIPCK(hipMemcpy(h->d_P, &h->hP, sizeof(McClassPars), hipMemcpyHostToDevice));
@@ -464,18 +416,17 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
     c.cap_hsps = (uint32_t)std::min<int64_t>(cap * (L / 3 + 8) + (1 << 20) + ev_pad, 0x7fffffff);
     c.cap_rows = (uint32_t)std::min<int64_t>(cap * 16 + (1 << 20), 0x7fffffff);
     c.gap_threads_full = 16 * 1024;                                 // full-size DP rows for the last-resort launch (460 MB)
-    if (dalloc(&c.d_frames_base, (size_t)cap * 6 * h->FP + 128) || dalloc(&c.d_tasks, c.cap_tasks) ||
-        dalloc(&c.d_gaps, c.cap_gaps) || dalloc(&c.d_hsps, c.cap_hsps) || dalloc(&c.d_v, c.cap_hsps) ||
-        dalloc(&c.d_tmp, (size_t)c.cap_hsps * 2) || dalloc(&c.d_k64, c.cap_hsps) || dalloc(&c.d_hkeys, c.cap_hsps) || dalloc(&c.d_hplace, c.cap_hsps) || dalloc(&c.d_places, c.cap_hsps) || dalloc(&c.d_idx, c.cap_hsps) ||
-        dalloc(&c.d_idxo, c.cap_hsps) || dalloc(&c.d_heads, (size_t)cap + 2) || dalloc(&c.d_scan, (size_t)4100) || dalloc(&c.d_gsz, c.cap_hsps) || dalloc(&c.d_nv, (size_t)cap + 1) || dalloc(&c.d_rows, c.cap_rows) ||
-        dalloc(&c.d_low, (size_t)cap + 64) || dalloc(&c.d_cand, (size_t)cap + 64) || dalloc(&c.d_nrow, (size_t)cap + 1) || dalloc(&c.d_rowoff, (size_t)cap + 1) || dalloc(&c.d_best, (size_t)cap + 1) || dalloc(&c.d_bestof, (size_t)cap + 1) ||
-        dalloc(&c.d_gws_full, (size_t)c.gap_threads_full * MC_GAP_W) || dalloc(&c.d_retry, (size_t)c.cap_gaps * 2 + (size_t)cap + 1) || dalloc(&c.d_retry2, (size_t)c.cap_gaps * 2) || dalloc(&c.d_gleader, (size_t)c.cap_gaps) ||
-        dalloc(&c.d_fout, (size_t)c.cap_gaps * 2))
+    if (c.d_frames_base.alloc((size_t)cap * 6 * h->FP + 128) || c.d_tasks.alloc(c.cap_tasks) ||
+        c.d_gaps.alloc(c.cap_gaps) || c.d_hsps.alloc(c.cap_hsps) || c.d_v.alloc(c.cap_hsps) ||
+        c.d_tmp.alloc((size_t)c.cap_hsps * 2) || c.d_k64.alloc(c.cap_hsps) || c.d_hkeys.alloc(c.cap_hsps) || c.d_hplace.alloc(c.cap_hsps) || c.d_places.alloc(c.cap_hsps) || c.d_idx.alloc(c.cap_hsps) ||
+        c.d_idxo.alloc(c.cap_hsps) || c.d_heads.alloc((size_t)cap + 2) || c.d_scan.alloc((size_t)4100) || c.d_gsz.alloc(c.cap_hsps) || c.d_nv.alloc((size_t)cap + 1) || c.d_rows.alloc(c.cap_rows) ||
+        c.d_low.alloc((size_t)cap + 64) || c.d_cand.alloc((size_t)cap + 64) || c.d_nrow.alloc((size_t)cap + 1) || c.d_rowoff.alloc((size_t)cap + 1) || c.d_best.alloc((size_t)cap + 1) || c.d_bestof.alloc((size_t)cap + 1) ||
+        c.d_gws_full.alloc((size_t)c.gap_threads_full * MC_GAP_W) || c.d_retry.alloc((size_t)c.cap_gaps * 2 + (size_t)cap + 1) || c.d_retry2.alloc((size_t)c.cap_gaps * 2) || c.d_gleader.alloc((size_t)c.cap_gaps) ||
+        c.d_fout.alloc((size_t)c.cap_gaps * 2))
         return -1;
     c.d_frames = c.d_frames_base + 64;
     HIPCK(hipMemsetAsync(c.d_frames_base, MC_INV, 64, c.stream));
-    if (c.h_best) { (void)hipHostFree(c.h_best); c.h_best = nullptr; }
-    HIPCK(hipHostMalloc((void **)&c.h_best, sizeof(McBestHit) * ((size_t)cap + 1), hipHostMallocDefault));
+    if (c.h_best.alloc((size_t)cap + 1)) return -1;
     c.h_best_cap = (size_t)cap + 1;
     c.cap_reads = cap; c.pool_len = (int)L;
     HIPCK(hipStreamSynchronize(c.stream));
@@ -487,7 +438,7 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
 static int reads_reserve(mc_handle *h, int64_t nreads)
 {
     const int64_t need = nreads * (int64_t)h->read_len + 16;
-    if (need > h->cap_own) { if (dalloc(&h->d_reads, (size_t)need)) return -1; h->cap_own = need; }
+    if (need > h->cap_own) { if (h->d_reads.alloc((size_t)need)) return -1; h->cap_own = need; }
     return 0;
 }
 
@@ -667,12 +618,12 @@ static int stage_b(mc_handle *h, McCtx &c)
         // HSP from its group's flank results.  The counts of 2. - 4. stay on the device.
         uint32_t slots = 1u << 16;
         while (slots < 2 * ngaps) slots <<= 1;
-        if (slots > c.gtab_slots) { if (dalloc(&c.d_gtab, (size_t)slots)) return -1; c.gtab_slots = slots; }
+        if (slots > c.gtab_slots) { if (c.d_gtab.alloc((size_t)slots)) return -1; c.gtab_slots = slots; }
         // The flank sort borrows the buffers of the HSP ordering: 2 ngaps keys in d_k64 (8 cap_hsps bytes), 2 ngaps items in d_idx /
         // d_idxo (4 cap_hsps bytes each).  The pools are sized so that ordinary batches fit (ensure_capacity); a batch
         // dense in gap tasks that does not is an overflow like any other: the range is run again in halves.
         if (2 * (uint64_t)ngaps > c.cap_hsps) { g_err = "gap task pool larger than the sort buffers"; return -2; }
-        uint32_t *gk = (uint32_t *)c.d_k64, *gi = c.d_idx, *gio = c.d_idxo;
+        uint32_t *gk = (uint32_t *)c.d_k64.get(), *gi = c.d_idx, *gio = c.d_idxo;
         HIPCK(hipMemsetAsync(c.d_gtab, 0, (size_t)slots * 8, st));
         HIPCK(hipMemsetAsync(c.d_ghist, 0, MC_GS_BINS * sizeof(uint32_t), st));
         k_gap_dedupe<<<dim3((ngaps + 255) / 256), dim3(256), 0, st>>>(X, L, c.d_gaps, ngaps, c.d_gtab, slots - 1, c.d_gleader, gk, gi, c.d_counters);
@@ -715,11 +666,11 @@ static int stage_c(mc_handle *h, McCtx &c)
         hipStream_t side = c.side, side2 = h->best_only ? c.side : c.side2;   // (best hits only: few reads are ordered at all - a third stream only costs)
         HIPCK(hipEventRecord(c.ev_fork, st)); HIPCK(hipStreamWaitEvent(c.side, c.ev_fork, 0)); HIPCK(hipStreamWaitEvent(c.side2, c.ev_fork, 0));
         HIPCK(hipFuncSetAttribute((const void *)k_order_heavy<1024, MC_ORDER_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MC_ORDER_LDS * 18)));
-        k_order_heavy<1024, MC_ORDER_LDS><<<dim3(256u), dim3(1024), MC_ORDER_LDS * 18, side>>>(keys, c.d_places, slots, c.d_heads, heavy3, c.d_counters + C_ORDER3, c.d_counters + C_OTAKE3, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
-        k_order_heavy<256, MC_ORDER_MID><<<dim3(256u * 4u), dim3(256), MC_ORDER_MID * 18, side2>>>(keys, c.d_places, slots, c.d_heads, heavy2, c.d_counters + C_ORDER2, c.d_counters + C_OTAKE2, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
+        k_order_heavy<1024, MC_ORDER_LDS><<<dim3(256u), dim3(1024), MC_ORDER_LDS * 18, side>>>(keys, c.d_places, slots, c.d_heads, heavy3, c.d_counters + C_ORDER3, c.d_counters + C_OTAKE3, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp.get());
+        k_order_heavy<256, MC_ORDER_MID><<<dim3(256u * 4u), dim3(256), MC_ORDER_MID * 18, side2>>>(keys, c.d_places, slots, c.d_heads, heavy2, c.d_counters + C_ORDER2, c.d_counters + C_OTAKE2, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp.get());
         HIPCK(hipEventRecord(c.ev_join, c.side)); HIPCK(hipEventRecord(c.ev_join2, c.side2));
         k_order_light<<<dim3((n + MC_OL_READS - 1) / MC_OL_READS), dim3(256), 0, st>>>(keys, c.d_places, slots, c.d_heads, n, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow);
-        k_order_heavy<64, MC_ORDER_SMALL><<<dim3(256u * 16u), dim3(64), MC_ORDER_SMALL * 18, st>>>(keys, c.d_places, slots, c.d_heads, heavy, c.d_counters + C_ORDER, c.d_counters + C_OTAKE, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp);
+        k_order_heavy<64, MC_ORDER_SMALL><<<dim3(256u * 16u), dim3(64), MC_ORDER_SMALL * 18, st>>>(keys, c.d_places, slots, c.d_heads, heavy, c.d_counters + C_ORDER, c.d_counters + C_OTAKE, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp.get());
         HIPCK(hipStreamWaitEvent(st, c.ev_join, 0)); HIPCK(hipStreamWaitEvent(st, c.ev_join2, 0));
         k_order_copy<<<dim3(256u * 8u), dim3(256), 0, st>>>(order, c.d_gsz, c.d_hsps, c.d_heads, n, c.d_v);
     }
@@ -803,7 +754,7 @@ static bool rows_stay(const mc_handle *h) { return h->rows_stay || (h->abund && 
 static int stage_e(mc_handle *h, McCtx &c)
 {
     hipStream_t st = c.stream;
-    if (c.nrows && !rows_stay(h)) HIPCK(hipMemcpyAsync(h->pin_rows, c.d_rows, sizeof(McRow) * c.nrows, hipMemcpyDeviceToHost, h->rows_stream));   // (the range's stream has been waited for: d_rows is final)
+    if (c.nrows && !rows_stay(h)) HIPCK(hipMemcpyAsync(h->pin_slot[h->pin_cur], c.d_rows, sizeof(McRow) * c.nrows, hipMemcpyDeviceToHost, h->rows_stream));   // (the range's stream has been waited for: d_rows is final)
     if (c.nbest) HIPCK(hipMemcpyAsync(c.h_best, c.d_best, sizeof(McBestHit) * c.nbest, hipMemcpyDeviceToHost, st));
     return 0;
 }
@@ -893,7 +844,7 @@ static void best_materialize(mc_handle *h)
     if (!c) return;
     h->best_from = nullptr;
     const uint32_t nb = h->best_count;                             // (taken at range_end: the front of the next range has reset the context's counts since)
-    std::sort(c->h_best, c->h_best + nb, [](const McBestHit &x, const McBestHit &y) { return x.read < y.read; });
+    std::sort(c->h_best.get(), c->h_best + nb, [](const McBestHit &x, const McBestHit &y) { return x.read < y.read; });
     h->best.resize(nb);
     for (uint32_t i = 0; i < nb; i++) { const McBestHit &x = c->h_best[i]; mc_best_hit &o = h->best[i]; o.read = x.read; o.family = x.family; o.aln = x.aln; o.target_len = x.target_len; o.bits = x.bits; }
 }
@@ -911,7 +862,7 @@ static int range_end(mc_handle *h, McCtx &c)
     if (rc == 0) rc = stage_wait(c);
     if (rc == 0 && c.h_c[C_OVERFLOW]) { g_err = "row buffer overflow"; rc = -2; }
     if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
-    h->pin_cur ^= 1; h->pin_rows = h->pin_slot[h->pin_cur]; h->pin_cap = h->pin_slot_cap[h->pin_cur];   // (the other slot may still be receiving the rows of the run before)
+    h->pin_cur ^= 1;                                                // (the other slot may still be receiving the rows of the run before)
     c.nrows = (c.nh && !h->best_only) ? c.h_c[C_ROWS] : 0u; c.nsegs = c.h_c[C_SEGS]; c.nbest = c.h_c[C_BEST];
     // the abundance counts of the range: its rows are final and none of its pools overflowed - a range that did has returned above
     // and counts nothing; the pieces mc_run_range cuts it into come through here one by one, each once
@@ -922,28 +873,21 @@ static int range_end(mc_handle *h, McCtx &c)
         if (nr) k_abundance<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund);
         HIPCK(hipEventRecord(h->ev_abund[1], c.stream));
     }
-    if ((size_t)c.nrows > h->pin_cap && !rows_stay(h)) {         // grow the pinned row buffer
+    if ((size_t)c.nrows > h->pin_slot_cap[h->pin_cur] && !rows_stay(h)) {   // grow the pinned row buffer
         (void)hipStreamSynchronize(h->rows_stream);                  // (the copy of the run before writes into the other buffer: let it finish before anything is freed)
         const size_t want = (size_t)c.nrows + c.nrows / 4 + 1024;
-        mc_row *nb = nullptr;
-        if (hipHostMalloc((void **)&nb, want * sizeof(mc_row), hipHostMallocDefault) != hipSuccess) { g_err = "out of pinned host memory for the rows"; return -1; }
-        if (h->pin_rows) (void)hipHostFree(h->pin_rows);
-        h->pin_rows = nb; h->pin_cap = want; h->pin_slot[h->pin_cur] = nb; h->pin_slot_cap[h->pin_cur] = want;
+        McPin<mc_row> nb, ob;                                      // (made before the old one goes, which the move-assignment frees)
+        if (nb.alloc(want)) { g_err = "out of pinned host memory for the rows"; return -1; }
+        h->pin_slot[h->pin_cur] = std::move(nb); h->pin_slot_cap[h->pin_cur] = want;
         const int other = h->pin_cur ^ 1;                        // the other slot grows with it (pinning 300 MB takes 40 ms: not in the middle of a later run)
-        if (h->pin_slot_cap[other] < want) {
-            mc_row *ob = nullptr;
-            if (hipHostMalloc((void **)&ob, want * sizeof(mc_row), hipHostMallocDefault) == hipSuccess) {
-                if (h->pin_slot[other]) (void)hipHostFree(h->pin_slot[other]);
-                h->pin_slot[other] = ob; h->pin_slot_cap[other] = want;
-            }
-        }
+        if (h->pin_slot_cap[other] < want && ob.alloc(want) == 0) { h->pin_slot[other] = std::move(ob); h->pin_slot_cap[other] = want; }
     }
     rc = stage_e(h, c);
     if (rc) { (void)hipStreamSynchronize(c.stream); (void)hipStreamSynchronize(h->rows_stream); return rc; }
     if (c.nrows && !rows_stay(h)) { HIPCK(hipEventRecord(h->ev_rows, h->rows_stream)); h->rows_pending = true; h->rows_ever = true; }
     if ((rc = stage_wait(c)) != 0) return rc;
     if (abund) { h->abund_searched += c.n; h->abund_ms += ev_ms(h->ev_abund[0], h->ev_abund[1]); }
-    h->res_rows = rows_stay(h) ? nullptr : h->pin_rows; h->n_res_rows = rows_stay(h) ? 0 : (int64_t)c.nrows;
+    h->res_rows = rows_stay(h) ? nullptr : (const mc_row *)h->pin_slot[h->pin_cur]; h->n_res_rows = rows_stay(h) ? 0 : (int64_t)c.nrows;
     h->best_from = &c; h->best_count = c.nbest;                  // (mc_result_best_hits / whoever needs them: best_materialize)
 #ifdef MC_EXP_TIMING
     { const char *nm[6] = {"staging/other", "append", "lookup", "push", "setup", "expand"}; for (int k = 0; k < 6; k++) fprintf(stderr, "timing %-14s %8.3f Mcycles/wave-avg  %10llu entries\n", nm[k], (double)c.h_stats[4 + k] / 4096.0 / 1e6, c.h_stats[10 + k]); }
@@ -1074,17 +1018,13 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
     int64_t bmax_run = B;
     if (B == BMAX && expect_reads > 0) { bmax_run = 262144; while (bmax_run < BMAX && bmax_run * 4 < expect_reads) bmax_run <<= 1; bmax_run = std::min(bmax_run, BMAX); }
     const size_t stage_bytes = (size_t)(bmax_run * L + 64);
-    if (!h->stage_pin[0] || h->stage_bytes < stage_bytes) {
-        for (int k = 0; k < 2; k++) {
-            if (h->stage_pin[k]) { (void)hipHostFree(h->stage_pin[k]); h->stage_pin[k] = nullptr; }
-            if (h->stage_dev[k]) { (void)hipFree(h->stage_dev[k]); h->stage_dev[k] = nullptr; }
-            HIPCK(hipHostMalloc((void **)&h->stage_pin[k], stage_bytes, hipHostMallocDefault));
-            HIPCK(hipMalloc((void **)&h->stage_dev[k], stage_bytes));
-        }
+    if (h->stage_bytes < stage_bytes) {
+        h->stage_bytes = 0;                                          // (a failure below leaves no size behind that a later, smaller run could trust)
+        for (int k = 0; k < 2; k++) if (h->stage_pin[k].alloc(stage_bytes) || h->stage_dev[k].alloc(stage_bytes)) return -1;
         h->stage_bytes = stage_bytes;
         MC_OT("run_stream: staging buffers", t0);
     }
-    if (!h->copy_stream) HIPCK(hipStreamCreate(&h->copy_stream));
+    if (!h->copy_stream && h->copy_stream.create()) return -1;
     if (expect_reads > 0 && ensure_capacity(h, h->ctx, std::min<int64_t>(bmax_run, expect_reads))) return -1;
     MC_OT("run_stream: pools", t0);
     McBatchSlot slot[2];
@@ -1531,14 +1471,14 @@ static int classes_stream(mc_handle *h, const std::function<int64_t(uint8_t *, i
     HIPCK(hipSetDevice(h->device));
     const int64_t B = std::max<int64_t>(1, expect_reads > 0 ? std::min(stream_batch(), expect_reads) : stream_batch()), stride = mc_class_stride(h->cls);   // (expect_reads: the most the source can deliver)
     McDevBuf buf;
-    uint8_t *d_rows = nullptr, *pin = nullptr;
+    uint8_t *d_rows = nullptr; McPin<uint8_t> pin;
     McResults R(false, nullptr, true);                               // (no rows; every best hit tagged with its class)
     int64_t reads[MC_CL_BINS] = {};
     int rc = 0;
     int64_t cap = 0;
     for (;;) {
         int64_t at = 0;
-        if (!pin) { if (hipHostMalloc((void **)&pin, (size_t)(B * stride), hipHostMallocDefault) != hipSuccess) { g_err = "out of pinned host memory for the rows"; rc = -1; break; } }
+        if (!pin && pin.alloc((size_t)(B * stride))) { g_err = "out of pinned host memory for the rows"; rc = -1; break; }
         const int64_t n = fetch(pin, B, &at);
         if (n < 0) { rc = (int)n; break; }
         if (n == 0) break;
@@ -1548,7 +1488,7 @@ static int classes_stream(mc_handle *h, const std::function<int64_t(uint8_t *, i
         if ((rc = classes_batch(h, d_rows, n, first_read_id + at, R, reads)) != 0) break;
         if (n < B) break;
     }
-    if (pin) (void)hipHostFree(pin);
+    pin.reset();
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr; h->best_cls.clear();
     if (rc) return rc;
     h->best.swap(R.best); h->best_cls.swap(R.tag); h->stats = R.tot;
@@ -1637,13 +1577,9 @@ extern "C" int64_t mc_debug_classes_prologue(mc_handle *h, const uint8_t *rows, 
     if (B.get(&d_rows, bytes + MC_CL_SLACK)) return -1;
     HIPCK(hipMemcpyAsync(d_rows, rows, bytes, hipMemcpyHostToDevice, st));
     HIPCK(hipMemsetAsync(d_rows + bytes, 0, MC_CL_SLACK, st));
-    hipEvent_t ev[4] = {};
-    bool ev_ok = true;
-    for (auto &e : ev) ev_ok = ev_ok && hipEventCreate(&e) == hipSuccess;
-    const int rc = ev_ok ? cl_prologue(B, st, d_rows, nreads, stride, h->cls, S, ev) : -1;   // (cl_prologue may return early: the events go either way)
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-    if (!ev_ok) g_err = "mc_debug_classes_prologue: cannot create events";
-    if (rc) { (void)hipStreamSynchronize(st); return -1; }
+    McEvents ev;
+    if (ev.make(4)) { g_err = "mc_debug_classes_prologue: cannot create events"; (void)hipStreamSynchronize(st); return -1; }
+    if (cl_prologue(B, st, d_rows, nreads, stride, h->cls, S, ev.e.data())) { (void)hipStreamSynchronize(st); return -1; }
     const int64_t nbytes = S.G.word0[h->cls.K] * 16;
     if (perm) HIPCK(hipMemcpyAsync(perm, S.d_perm, (size_t)nreads * 4, hipMemcpyDeviceToHost, st));
     if (sorted && nbytes && nbytes <= sorted_cap) HIPCK(hipMemcpyAsync(sorted, S.d_sorted, (size_t)nbytes, hipMemcpyDeviceToHost, st));
@@ -1706,9 +1642,9 @@ extern "C" int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_
     const int64_t nrows = h->n_res_rows;
     if (nrows == 0) return 0;
     rows_wait(h);
+    McDevBuf buf;
     McRow *d_rows = nullptr; unsigned long long *d_bins = nullptr;
-    HIPCK(hipMalloc((void **)&d_rows, (size_t)nrows * sizeof(McRow)));
-    if (hipMalloc((void **)&d_bins, nbins * 24) != hipSuccess) { (void)hipFree(d_rows); g_err = "out of device memory"; return -1; }
+    if (buf.get(&d_rows, (size_t)nrows) || buf.get(&d_bins, nbins * 3)) return -1;
     hipStream_t st = h->ctx.stream;
     HIPCK(hipMemcpyAsync(d_rows, h->res_rows, (size_t)nrows * sizeof(McRow), hipMemcpyHostToDevice, st));
     HIPCK(hipMemsetAsync(d_bins, 0, nbins * 24, st));
@@ -1716,7 +1652,6 @@ extern "C" int mc_grid_classify(mc_handle *h, const double *aln_covs, int32_t n_
     std::vector<unsigned long long> bins(nbins * 3);
     HIPCK(hipMemcpyAsync(bins.data(), d_bins, nbins * 24, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
-    (void)hipFree(d_rows); (void)hipFree(d_bins);
     grid_counts(bins, nbins, n_cov * n_pid, n_score, nfam, order, count_hits, count_aln, count_cov);
     return 0;
 }
@@ -1755,28 +1690,22 @@ extern "C" int mc_bootstrap(mc_handle *h, const mc_best_hit *best, int64_t n, co
     const int ntiles = boot_tiles(n, B);
     const int64_t per_tile = (n + ntiles - 1) / ntiles;
     mc_best_hit *d_hits = nullptr; unsigned long long *d_part = nullptr, *d_out = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto release = [&]() { if (d_hits) (void)hipFree(d_hits); if (d_part) (void)hipFree(d_part); if (d_out) (void)hipFree(d_out); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); };
-#define BOOTCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_err = std::string(#call) + ": " + hipGetErrorString(e_); release(); return -1; } } while (0)
+    McDevBuf buf; McEvents ev;
     const size_t nout = (size_t)B * (rows + (size_t)nfam);
-    BOOTCK(hipMalloc((void **)&d_hits, (size_t)n * sizeof(mc_best_hit)));
-    BOOTCK(hipMalloc((void **)&d_part, (size_t)ntiles * rows * (size_t)B * 8));
-    BOOTCK(hipMalloc((void **)&d_out, nout * 8));
-    BOOTCK(hipEventCreate(&e0)); BOOTCK(hipEventCreate(&e1));
+    if (buf.get(&d_hits, (size_t)n) || buf.get(&d_part, (size_t)ntiles * rows * (size_t)B) || buf.get(&d_out, nout) || ev.make(2)) return -1;
+    hipEvent_t e0 = ev[0], e1 = ev[1];
     hipStream_t st = h->ctx.stream;
-    BOOTCK(hipMemcpyAsync(d_hits, best, (size_t)n * sizeof(mc_best_hit), hipMemcpyHostToDevice, st));
-    BOOTCK(hipEventRecord(e0, st));
+    HIPCK(hipMemcpyAsync(d_hits, best, (size_t)n * sizeof(mc_best_hit), hipMemcpyHostToDevice, st));
+    HIPCK(hipEventRecord(e0, st));
     k_bootstrap<<<dim3((unsigned)ntiles, (unsigned)((B + MC_BOOT_LANES - 1) / MC_BOOT_LANES)), dim3(MC_BOOT_LANES), 0, st>>>(P, d_hits, n, per_tile, d_part);
     long long *d_i64 = (long long *)d_out; double *d_f64 = (double *)(d_out + (size_t)B * rows);
     k_bootstrap_reduce<<<dim3((unsigned)(((size_t)B * rows + 255) / 256)), dim3(256), 0, st>>>(P, ntiles, d_part, d_i64, d_f64);
-    BOOTCK(hipGetLastError());
-    BOOTCK(hipEventRecord(e1, st));
-    BOOTCK(hipMemcpyAsync(sums_i64, d_i64, (size_t)B * rows * 8, hipMemcpyDeviceToHost, st));
-    BOOTCK(hipMemcpyAsync(sums_f64, d_f64, (size_t)B * (size_t)nfam * 8, hipMemcpyDeviceToHost, st));
-    BOOTCK(hipStreamSynchronize(st));
-    BOOTCK(hipEventElapsedTime(&h->boot_ms, e0, e1));
-#undef BOOTCK
-    release();
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(e1, st));
+    HIPCK(hipMemcpyAsync(sums_i64, d_i64, (size_t)B * rows * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(sums_f64, d_f64, (size_t)B * (size_t)nfam * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    HIPCK(hipEventElapsedTime(&h->boot_ms, e0, e1));
     return 0;
 }
 
@@ -1848,20 +1777,15 @@ extern "C" int mc_fit_weights(mc_handle *h, const double *pred, const double *tr
     for (int f = 0; f < F; f++) S0.w[f] = 1.0 / (double)F;
     S0.sigma = MC_WFIT_SIGMA0;
     double *d_tab = nullptr, *d_trace = nullptr; McWfitState *d_state = nullptr; unsigned long long *d_best = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto release = [&]() { if (d_tab) (void)hipFree(d_tab); if (d_trace) (void)hipFree(d_trace); if (d_state) (void)hipFree(d_state); if (d_best) (void)hipFree(d_best); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); };
-#define WFITCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_err = std::string(#call) + ": " + hipGetErrorString(e_); release(); return -1; } } while (0)
+    McDevBuf buf; McEvents ev;
     const size_t trace_bytes = 3 * (size_t)(G + 1) * 8;
-    WFITCK(hipMalloc((void **)&d_tab, tab.size() * 8));
-    WFITCK(hipMalloc((void **)&d_trace, trace_bytes));
-    WFITCK(hipMalloc((void **)&d_state, sizeof(McWfitState)));
-    WFITCK(hipMalloc((void **)&d_best, (size_t)nblocks * 16));
-    WFITCK(hipEventCreate(&e0)); WFITCK(hipEventCreate(&e1));
+    if (buf.get(&d_tab, tab.size()) || buf.get(&d_trace, trace_bytes / 8) || buf.get(&d_state, 1) || buf.get(&d_best, (size_t)nblocks * 2) || ev.make(2)) return -1;
+    hipEvent_t e0 = ev[0], e1 = ev[1];
     hipStream_t st = h->ctx.stream;
-    WFITCK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
-    WFITCK(hipMemcpyAsync(d_state, &S0, sizeof(S0), hipMemcpyHostToDevice, st));
-    WFITCK(hipMemsetAsync(d_trace, 0, trace_bytes, st));
-    WFITCK(hipEventRecord(e0, st));
+    HIPCK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(d_state, &S0, sizeof(S0), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(d_trace, 0, trace_bytes, st));
+    HIPCK(hipEventRecord(e0, st));
     McWfitPars P1 = P; P1.C = 1;                                   // the start: candidate 0 alone
     wfit_launch_eval(sh, 1, st, P1, d_tab, d_state, -1, nullptr, nullptr, d_best);
     k_wfit_update<<<dim3(1), dim3(256), 0, st>>>(P1, d_state, -1, 1, d_best, d_trace);
@@ -1869,15 +1793,14 @@ extern "C" int mc_fit_weights(mc_handle *h, const double *pred, const double *tr
         wfit_launch_eval(sh, nblocks, st, P, d_tab, d_state, g, nullptr, nullptr, d_best);
         k_wfit_update<<<dim3(1), dim3(256), 0, st>>>(P, d_state, g, nblocks, d_best, d_trace);
     }
-    WFITCK(hipGetLastError());
-    WFITCK(hipEventRecord(e1, st));
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(e1, st));
     McWfitState S1;
-    WFITCK(hipMemcpyAsync(&S1, d_state, sizeof(S1), hipMemcpyDeviceToHost, st));
-    WFITCK(hipMemcpyAsync(trace, d_trace, trace_bytes, hipMemcpyDeviceToHost, st));
-    WFITCK(hipStreamSynchronize(st));
-    WFITCK(hipEventElapsedTime(&h->wfit_ms, e0, e1));
+    HIPCK(hipMemcpyAsync(&S1, d_state, sizeof(S1), hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(trace, d_trace, trace_bytes, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    HIPCK(hipEventElapsedTime(&h->wfit_ms, e0, e1));
     for (int f = 0; f < F; f++) weights[f] = S1.w[f];
-    release();
     return 0;
 }
 
@@ -1898,24 +1821,19 @@ extern "C" int mc_weights_mue(mc_handle *h, const double *pred, const double *tr
     McWfitPars P; memset(&P, 0, sizeof(P));
     P.N = N; P.F = F; P.C = K; P.alive = alive;
     double *d_tab = nullptr, *d_w = nullptr, *d_out = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto release = [&]() { if (d_tab) (void)hipFree(d_tab); if (d_w) (void)hipFree(d_w); if (d_out) (void)hipFree(d_out); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); };
-    WFITCK(hipMalloc((void **)&d_tab, tab.size() * 8));
-    WFITCK(hipMalloc((void **)&d_w, (size_t)K * F * 8));
-    WFITCK(hipMalloc((void **)&d_out, (size_t)K * 8));
-    WFITCK(hipEventCreate(&e0)); WFITCK(hipEventCreate(&e1));
+    McDevBuf buf; McEvents ev;
+    if (buf.get(&d_tab, tab.size()) || buf.get(&d_w, (size_t)K * F) || buf.get(&d_out, (size_t)K) || ev.make(2)) return -1;
+    hipEvent_t e0 = ev[0], e1 = ev[1];
     hipStream_t st = h->ctx.stream;
-    WFITCK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
-    WFITCK(hipMemcpyAsync(d_w, w, (size_t)K * F * 8, hipMemcpyHostToDevice, st));
-    WFITCK(hipEventRecord(e0, st));
+    HIPCK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(d_w, w, (size_t)K * F * 8, hipMemcpyHostToDevice, st));
+    HIPCK(hipEventRecord(e0, st));
     wfit_launch_eval(sh, nblocks, st, P, d_tab, nullptr, 0, d_w, d_out, nullptr);
-    WFITCK(hipGetLastError());
-    WFITCK(hipEventRecord(e1, st));
-    WFITCK(hipMemcpyAsync(out, d_out, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    WFITCK(hipStreamSynchronize(st));
-    WFITCK(hipEventElapsedTime(&h->wfit_ms, e0, e1));
-#undef WFITCK
-    release();
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(e1, st));
+    HIPCK(hipMemcpyAsync(out, d_out, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    HIPCK(hipEventElapsedTime(&h->wfit_ms, e0, e1));
     return 0;
 }
 
@@ -1952,8 +1870,8 @@ extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t
     if (h->pipe_nout) { g_err = "mc_set_abundance: a range begun with mc_range_begin() is still in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     if (!on) {
-        if (h->d_abund) { (void)hipFree(h->d_abund); h->d_abund = nullptr; }
-        for (auto &e : h->ev_abund) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        h->d_abund.reset();
+        for (auto &e : h->ev_abund) e.reset();
         h->abund = false; h->abund_searched = 0; h->abund_ms = 0.f;
         return 0;
     }
@@ -1962,8 +1880,8 @@ extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t
     if (min_bits != min_bits) { g_err = "mc_set_abundance: min_bits is NaN"; return -1; }
     if (max_loge != max_loge) { g_err = "mc_set_abundance: max_loge is NaN"; return -1; }
     if (h->best_only) { g_err = "mc_set_abundance: best hits only is on (mc_set_best_hits_only) - abundance needs every m8 row of a read"; return -1; }
-    if (!h->d_abund && dalloc(&h->d_abund, 2 * ((size_t)h->H.nseq + 1))) return -1;
-    for (auto &e : h->ev_abund) if (!e) HIPCK(hipEventCreate(&e));
+    if (!h->d_abund && h->d_abund.alloc(2 * ((size_t)h->H.nseq + 1))) return -1;
+    for (auto &e : h->ev_abund) if (!e && e.create()) return -1;
     h->abund_pars.min_ident = min_ident; h->abund_pars.min_aln = min_aln; h->abund_pars.min_bits = min_bits; h->abund_pars.max_loge = max_loge;
     h->abund = true;
     return abund_zero(h);
