@@ -114,7 +114,9 @@ __global__ void __launch_bounds__(TPB) k_finish(const McTables *__restrict__ T, 
 //  * __final_insertion_sort is a stable sort of an array in which no element is further than 15 positions from its place
 //    (ranges of <= 16 between ordered neighbours): place = position - (larger keys among the 15 before) + (smaller keys among
 //    the 15 behind).
-// Checked against mc_std_sort on 200,000 random arrays (ties, sorted, reversed; tests/test_emul.py runs the same formulation).
+// tests/emul/wave_sort_form.h restates this formulation with the lanes flattened: tests/test_order_host.py holds it to mc_std_sort on
+// 200,000 generated arrays (ties, sorted, reversed, organ pipe) and on McIlroy's adversary, which reaches the depth-0 fallback;
+// tests/test_gpu_order_units.py holds this function itself to mc_std_sort on such arrays, at k_finish_heavy's LDS layout.
 __device__ __forceinline__ void mc_wave_std_sort(McSortItem *items, int n, uint16_t *posA, uint16_t *posB, uint16_t *npos, int *stk, int lane)
 {
     if (n <= 1) return;
