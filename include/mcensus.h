@@ -477,6 +477,33 @@ int mc_abundance_read(mc_handle *h, int64_t *reads /* [nseq] */, int64_t *aligne
  * README's "reads mapped to gene" beside mc_stats.ms_total of the same ranges. */
 float mc_abundance_ms(const mc_handle *h);
 
+/* ---- coverage breadth and depth of the genes, beside the counts -----------------------------------------------------------------
+ * A high RPKG (README "Normalization") may be a few hundred reads piled on one conserved domain; whether the gene is there shows in
+ * the fraction of its residues that a read covers.  csrc/k_coverage.h states the rule: the subject span of a row is the residues
+ * sstart .. send, 0-BASED AND INCLUSIVE (mc_row.sstart / send; columns 9 and 10 of RAPsearch2's m8); a read's best row - the very row
+ * that mc_set_abundance counts - adds 1 to the depth of each of them.  Per subject: covered = residues of depth > 0, spanned = the sum
+ * of the depths = the sum of send - sstart + 1 over the best rows, max_depth = the largest depth.  Exact integers, whatever the
+ * batches, ranges and launch geometry; the depth is 32-bit (2^32 reads on one residue wrap), spanned 64-bit.
+ * mc_set_coverage(on != 0) allocates and zeroes the depth's difference array (residues + subjects 32-bit slots) and ALSO zeroes the
+ * abundance counters of the README's "Normalization" numerators: counts and depth describe the same reads.  From then on every
+ * range that adds to the counts marks its best rows' spans, in the same kernel; a range that overflowed a pool marks nothing, its
+ * pieces once.  on == 0 frees the array and restores the path without it exactly.  mc_set_abundance(h, 0, ...) also turns coverage
+ * off; mc_abundance_reset() also zeroes the depth and mc_coverage_ms().
+ * Refused, with a message naming the cause: abundance counting off (README "Normalization": mc_set_abundance first), a range in flight.
+ * mc_search_files_multi keeps one array per handle: DEPTH adds across handles (mc_coverage_depth, spanned), covered and max_depth do
+ * not - the caller recomputes them from the summed depth. */
+int mc_set_coverage(mc_handle *h, int on);
+/* covered[s], spanned[s] and max_depth[s] per subject s as they stand (arrays of mc_marker_count() values; any may be NULL) - the
+ * breadth and depth that qualify the README's "Normalization" numerators: one scan kernel per call.  Refused while coverage is off. */
+int mc_coverage_read(mc_handle *h, int64_t *covered /* [nseq] */, int64_t *spanned /* [nseq] */, int64_t *max_depth /* [nseq] */);
+/* The depth of every residue, the subjects one after the other in FASTA order (no sentinels): the per-residue picture behind the
+ * README's "Normalization" counts.  n must equal the database's residue total (the sum of the sequence lengths); otherwise, and
+ * while coverage is off, refused - with both numbers in the message. */
+int mc_coverage_depth(mc_handle *h, uint32_t *depth /* [n] */, int64_t n);
+/* Milliseconds the scan kernels of mc_coverage_read / mc_coverage_depth took since the last reset (HIP events).  The marks ride in
+ * the counting kernel: their time is part of mc_abundance_ms() (README "Normalization": the device cost of "reads mapped to gene"). */
+float mc_coverage_ms(const mc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,11 @@ def load_library():
     lib.mc_abundance_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.mc_abundance_ms.restype = C.c_float
     lib.mc_abundance_ms.argtypes = [C.c_void_p]
+    lib.mc_set_coverage.argtypes = [C.c_void_p, C.c_int]
+    lib.mc_coverage_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mc_coverage_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.mc_coverage_ms.restype = C.c_float
+    lib.mc_coverage_ms.argtypes = [C.c_void_p]
     lib.mc_debug_live.restype = None
     lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
@@ -235,7 +240,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_community_open", "mc_community_close", "mc_community_set_library", "mc_community_simulate", "mc_community_library", "mc_community_member_reads",
                     "mc_community_times",
                     "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride",
-                    "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms", "mc_debug_live"]
+                    "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms",
+                    "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms", "mc_debug_live"]
 
 
 class DupSet:
@@ -900,6 +906,33 @@ class Engine:
     def abundance_ms(self):
         """milliseconds the abundance kernels took since the last reset (HIP events)"""
         return float(self.lib.mc_abundance_ms(self.h))
+
+    def set_coverage(self, on=True):
+        """Coverage breadth and depth of the genes beside the counts (mc_set_coverage; csrc/k_coverage.h states the rule): from now on
+        a read's best row - the one set_abundance counts - adds 1 to the depth of the subject residues sstart .. send (0-based, inclusive).
+        on=True zeroes the depth AND the abundance counters; on=False frees it.  Refused while set_abundance is off."""
+        self._check(self.lib.mc_set_coverage(self.h, 1 if on else 0), "mc_set_coverage")
+
+    def coverage(self):
+        """The per-gene figures as they stand (mc_coverage_read): {"covered", "spanned", "max_depth"}, int64[nseq] each."""
+        n = len(self.names)
+        out = {k: np.zeros(n, np.int64) for k in ("covered", "spanned", "max_depth")}
+        self._check(self.lib.mc_coverage_read(self.h, *(out[k].ctypes.data_as(C.c_void_p) for k in ("covered", "spanned", "max_depth"))), "mc_coverage_read")
+        return out
+
+    def coverage_depth(self):
+        """The depth of every residue (mc_coverage_depth): one uint32 array, the genes one after the other in FASTA order - the caller
+        splits it by the genes' lengths."""
+        p = [C.c_void_p() for _ in range(5)]
+        nres, npost, thr, lp = C.c_int64(), C.c_int64(), C.c_uint32(), (C.c_double * 10)()
+        self._check(self.lib.mc_index_view(self.h, *[C.byref(x) for x in p], C.byref(nres), C.byref(npost), C.byref(thr), lp), "mc_index_view")
+        depth = np.zeros(int(nres.value), np.uint32)
+        self._check(self.lib.mc_coverage_depth(self.h, depth.ctypes.data_as(C.c_void_p), depth.size), "mc_coverage_depth")
+        return depth
+
+    def coverage_ms(self):
+        """milliseconds the coverage scan kernels took since the last reset (HIP events); the marks are part of abundance_ms()"""
+        return float(self.lib.mc_coverage_ms(self.h))
 
     def upload(self, reads):
         reads = np.ascontiguousarray(reads, dtype=np.uint8)

@@ -10,7 +10,17 @@ the rule): no m8 row reaches the host.  Numerator and denominator come from the 
     rpkg = reads / (3 x length_aa / 1000) / genome_equivalents_sampled
 
 The AGS is --ags VALUE, the average_genome_size line of a report (--ags-report FILE), or - by default - run_pipeline on the same
-files with the same options in the same process (the marker engine; the gene engine is a second Engine on the same device)."""
+files with the same options in the same process (the marker engine; the gene engine is a second Engine on the same device).
+
+A high RPKG alone does not say that a gene is there: a few hundred reads piled on one conserved domain give one.  With coverage
+(Engine.set_coverage; csrc/k_coverage.h states the rule) the table also says which part of the gene the assigned reads cover: a best
+row covers the subject residues sstart .. send of RAPsearch2's m8 - 0-based and inclusive - and per gene
+
+    covered_aa = residues covered by at least one read      breadth = covered_aa / length_aa
+    mean_depth = (sum of the depths) / length_aa            max_depth = the largest depth
+
+min_breadth F adds the column detected (reads > 0 and covered_aa >= F x length_aa); depth_out writes the depth itself, run-length
+encoded (gene, start, end, depth: 0-based start, exclusive end)."""
 import gzip
 import math
 import os
@@ -24,6 +34,8 @@ MAX_GENE_LEN = 2047
 
 COLUMNS = ("gene", "length_aa", "reads", "aligned_aa", "rpkg")
 GROUP_COLUMNS = ("group", "genes", "reads", "rpkg")
+COVERAGE_COLUMNS = ("covered_aa", "breadth", "mean_depth", "max_depth")     # behind COLUMNS with coverage; "detected" behind them with min_breadth
+DEPTH_COLUMNS = ("gene", "start", "end", "depth")
 
 
 class AbundanceError(Exception):
@@ -118,20 +130,79 @@ def rpkg(reads, length_aa, ge):
     return np.asarray(reads, dtype=np.float64) / (3.0 * np.asarray(length_aa, dtype=np.float64) / 1000.0) / float(ge)
 
 
-def group_table(names, reads, rpkgs, group_of):
+def group_table(names, reads, rpkgs, group_of, detected=None):
     """[(group, genes, reads, rpkg)] in the order the groups first appear in the FASTA; a gene missing from the map is a group of its own
-    name; a group's rpkg is the sum of its members' values, added in FASTA order."""
+    name; a group's rpkg is the sum of its members' values, added in FASTA order.  With detected (0 / 1 per gene) every tuple ends with
+    the group's genes_detected."""
     order, acc = [], {}
-    for nm, r, v in zip(names, reads, rpkgs):
+    for k, (nm, r, v) in enumerate(zip(names, reads, rpkgs)):
         g = group_of.get(nm, nm)
         if g not in acc:
-            acc[g] = [0, 0, 0.0]
+            acc[g] = [0, 0, 0.0, 0]
             order.append(g)
         a = acc[g]
         a[0] += 1
         a[1] += int(r)
         a[2] += float(v)
-    return [(g, acc[g][0], acc[g][1], acc[g][2]) for g in order]
+        if detected is not None:
+            a[3] += int(detected[k])
+    return [(g,) + tuple(acc[g][:4 if detected is not None else 3]) for g in order]
+
+
+def coverage_columns(length_aa, covered, spanned):
+    """(breadth, mean_depth) in float64: covered_aa / length_aa and spanned / length_aa."""
+    ln = np.asarray(length_aa, dtype=np.float64)
+    return np.asarray(covered, dtype=np.float64) / ln, np.asarray(spanned, dtype=np.float64) / ln
+
+
+def detect(reads, covered, length_aa, min_breadth):
+    """1 where reads > 0 and covered_aa >= F x length_aa (covered_aa x 1 >= F x length_aa, compared in float64), otherwise 0."""
+    f = np.float64(min_breadth)
+    return ((np.asarray(reads) > 0) & (np.asarray(covered, dtype=np.float64) * 1 >= f * np.asarray(length_aa, dtype=np.float64))).astype(np.int64)
+
+
+def depth_runs(depth, length_aa):
+    """The maximal runs of equal non-zero depth, gene by gene: (gene index, start, end, depth) as arrays - start 0-based within the gene,
+    end exclusive.  depth: every residue's depth, the genes one after the other (Engine.coverage_depth).  A run never crosses from one
+    gene into the next, whatever the depths on either side."""
+    depth = np.asarray(depth)
+    length_aa = np.asarray(length_aa, dtype=np.int64)
+    first = np.cumsum(length_aa) - length_aa
+    if depth.size != int(length_aa.sum()):
+        raise ValueError("%d depths for genes of %d residues" % (depth.size, int(length_aa.sum())))
+    if depth.size == 0:
+        z = np.zeros(0, np.int64)
+        return z, z, z, z
+    gene = np.repeat(np.arange(len(length_aa), dtype=np.int64), length_aa)
+    starts = np.flatnonzero(np.r_[True, (depth[1:] != depth[:-1]) | (gene[1:] != gene[:-1])])
+    ends = np.r_[starts[1:], depth.size]
+    keep = depth[starts] > 0
+    starts, ends = starts[keep], ends[keep]
+    g = gene[starts]
+    return g, starts - first[g], ends - first[g], depth[starts].astype(np.int64)
+
+
+def write_depth(path, names, length_aa, depth):
+    """bedGraph-style TSV of depth_runs: gene, start, end, depth - genes in FASTA order, only the genes that reads cover."""
+    g, a, b, d = depth_runs(depth, length_aa)
+    with open(path, "w") as out:
+        out.write("#" + "\t".join(DEPTH_COLUMNS) + "\n")
+        out.writelines("%s\t%d\t%d\t%d\n" % (names[k], x, y, v) for k, x, y, v in zip(g.tolist(), a.tolist(), b.tolist(), d.tolist()))
+
+
+def read_depth(path, names, length_aa):
+    """The public inverse of write_depth, for whoever reads the file back (a plot, a test): the depth of every residue, the genes one after
+    the other as in Engine.coverage_depth() - zeros where the file has no run.  names and length_aa: the gene FASTA's, in its order."""
+    length_aa = np.asarray(length_aa, dtype=np.int64)
+    first = dict(zip(names, (np.cumsum(length_aa) - length_aa).tolist()))
+    depth = np.zeros(int(length_aa.sum()), np.uint32)
+    with open(path) as f:
+        for line in f:
+            if line.startswith("#"):
+                continue
+            nm, a, b, d = line.rstrip("\n").split("\t")
+            depth[first[nm] + int(a):first[nm] + int(b)] = int(d)
+    return depth
 
 
 def header_lines(args, table):
@@ -139,24 +210,36 @@ def header_lines(args, table):
          ("trimmed_length", table["trimmed_length"]), ("min_ident", args["min_ident"]), ("min_aln", args["min_aln"]), ("min_bits", repr(float(args["min_bits"]))),
          ("average_genome_size", repr(float(table["ags"]))), ("ags_source", table["ags_source"]),
          ("genome_equivalents_sampled", repr(float(table["genome_equivalents_sampled"]))), ("reads_assigned", table["reads_assigned"])]
+    if table.get("covered_aa") is not None:
+        h.append(("coverage", "on"))
+    if table.get("detected") is not None:
+        h += [("min_breadth", repr(float(table["min_breadth"]))), ("genes_detected", int(np.sum(table["detected"])))]
     return ["# %s:\t%s\n" % kv for kv in h]
 
 
 def write_table(path, args, table):
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
-        out.write("\t".join(COLUMNS) + "\n")
-        for nm, ln, r, a, v in zip(table["gene"], table["length_aa"], table["reads"], table["aligned_aa"], table["rpkg"]):
-            out.write("%s\t%d\t%d\t%d\t%s\n" % (nm, ln, r, a, repr(float(v))))
+        cov, det = table.get("covered_aa") is not None, table.get("detected") is not None
+        out.write("\t".join(COLUMNS + (COVERAGE_COLUMNS if cov else ()) + (("detected",) if det else ())) + "\n")
+        for k, (nm, ln, r, a, v) in enumerate(zip(table["gene"], table["length_aa"], table["reads"], table["aligned_aa"], table["rpkg"])):
+            line = "%s\t%d\t%d\t%d\t%s" % (nm, ln, r, a, repr(float(v)))
+            if cov:
+                line += "\t%d\t%s\t%s\t%d" % (table["covered_aa"][k], repr(float(table["breadth"][k])), repr(float(table["mean_depth"][k])), table["max_depth"][k])
+            if det:
+                line += "\t%d" % table["detected"][k]
+            out.write(line + "\n")
 
 
 def write_groups(path, args, table):
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
         out.write("# groups:\t%s\n" % args["groups"])
-        out.write("\t".join(GROUP_COLUMNS) + "\n")
-        for g, n, r, v in table["groups"]:
-            out.write("%s\t%d\t%d\t%s\n" % (g, n, r, repr(float(v))))
+        det = table.get("detected") is not None
+        out.write("\t".join(GROUP_COLUMNS + (("genes_detected",) if det else ())) + "\n")
+        for row in table["groups"]:
+            g, n, r, v = row[:4]
+            out.write("%s\t%d\t%d\t%s%s\n" % (g, n, r, repr(float(v)), "\t%d" % row[4] if det else ""))
 
 
 def read_table(path):
@@ -184,8 +267,27 @@ def check_request(args):
     """Everything that can be refused before any GPU work; returns (names, seqs, group_of, ags or None, ags_source or None)."""
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.get("distributed"):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
-    for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None)):
+    for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
+                         ("coverage", False), ("min_breadth", None), ("depth_out", None)):
         args.setdefault(key, default)
+    if args["min_breadth"] is not None:
+        f = args["min_breadth"]
+        try:
+            f = float("nan") if isinstance(f, bool) else float(f)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if not 0.0 < f <= 1.0:                                   # (NaN compares false)
+            raise AbundanceError("--min-breadth %s is not a fraction in (0, 1]" % (args["min_breadth"],))
+        args["min_breadth"] = f
+    if args["depth_out"] is not None:
+        if not args["depth_out"]:
+            raise AbundanceError("--depth-out %r is an empty path" % (args["depth_out"],))
+        where = os.path.abspath(args["depth_out"])
+        if args.get("outfile") and where == os.path.abspath(args["outfile"]):
+            raise AbundanceError("--depth-out %s is the path of the gene table itself: two files" % (args["depth_out"],))
+        if args.get("outfile") and args["groups"] and where == os.path.abspath(args["outfile"] + ".groups.tsv"):
+            raise AbundanceError("--depth-out %s is the path of the groups table (<outfile>.groups.tsv): two files" % (args["depth_out"],))
+    args["coverage"] = bool(args["coverage"]) or args["min_breadth"] is not None or args["depth_out"] is not None
     if args["ags"] is not None and args["ags_report"] is not None:
         raise AbundanceError("--ags %s and --ags-report %s cannot be combined: one AGS" % (args["ags"], args["ags_report"]))
     mi = args["min_ident"]
@@ -210,7 +312,8 @@ def check_request(args):
 
 def run_abundance(args):
     """args: run_pipeline's keys (seqfiles, nreads, read_length, min_quality, mean_quality, filter_dups, max_unknown, device, model_dir,
-    verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report.  Writes args['outfile'] (and
+    verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and - all off by default - coverage, min_breadth
+    (implies coverage), depth_out (a path; implies coverage).  Writes args['outfile'] (and
     <outfile>.groups.tsv with groups) when it is set; returns (table, args) - table: the columns as arrays (gene, length_aa, reads,
     aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
     names, seqs, group_of, ags, source = check_request(args)
@@ -235,12 +338,18 @@ def run_abundance(args):
         eng = _native.Engine(device=int(args.get("device") or 0), names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
         eng.set_run(L)
         eng.set_abundance(True, min_ident=args["min_ident"], min_aln=args["min_aln"], min_bits=args["min_bits"])
+        if args["coverage"]:
+            eng.set_coverage(True)
         try:
             eng.search_files(rd, keep_rows=False)
         except _native.ReferenceError_ as e:
             raise AbundanceError(str(e))
         ab = eng.abundance()
+        cov = eng.coverage() if args["coverage"] else None
+        depth = eng.coverage_depth() if args["depth_out"] is not None else None
         args["abundance_ms"], args["search_ms"] = eng.abundance_ms(), eng.stats()["ms_total"]
+        if args["coverage"]:
+            args["coverage_ms"] = eng.coverage_ms()
         st = rd.stats()
     finally:
         rd.close()
@@ -259,8 +368,17 @@ def run_abundance(args):
     ge = genome_equivalents(sampled, L, ags)
     table = {"gene": list(names), "length_aa": length_aa, "reads": ab["reads"], "aligned_aa": ab["aligned"], "rpkg": rpkg(ab["reads"], length_aa, ge),
              "sampled_reads": sampled, "trimmed_length": L, "ags": ags, "ags_source": source, "genome_equivalents_sampled": ge, "reads_assigned": ab["assigned"]}
+    if cov is not None:
+        breadth, mean_depth = coverage_columns(length_aa, cov["covered"], cov["spanned"])
+        table.update({"covered_aa": cov["covered"], "breadth": breadth, "mean_depth": mean_depth, "max_depth": cov["max_depth"], "spanned_aa": cov["spanned"]})
+        if args["min_breadth"] is not None:
+            table["min_breadth"] = args["min_breadth"]
+            table["detected"] = detect(ab["reads"], cov["covered"], length_aa, args["min_breadth"])
+        if depth is not None:
+            table["depth"] = depth
+            write_depth(args["depth_out"], names, length_aa, depth)
     if group_of is not None:
-        table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of)
+        table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of, table.get("detected"))
     if args.get("outfile"):
         write_table(args["outfile"], args, table)
         if group_of is not None:

@@ -15,6 +15,7 @@
 //   k_bootstrap.h          the Poisson bootstrap of the per-family sums (mc_bootstrap)
 //   k_wfit.h               the fit of the per-family weights, training step 5 (mc_fit_weights, mc_weights_mue)
 //   k_abundance.h          per-gene read counts for RPKG, summed over the rows of every completed range (mc_set_abundance)
+//   k_coverage.h           per-gene coverage breadth and depth beside them: marks in the counting kernel, a scan at read time (mc_set_coverage)
 //   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
@@ -34,6 +35,7 @@
 #include "k_bootstrap.h"
 #include "k_wfit.h"
 #include "k_abundance.h"
+#include "k_coverage.h"
 #include "mc_pieces.h"
 #include "mc_owned.h"
 
@@ -93,6 +95,10 @@ struct mc_handle {
     // of the completed ranges, the kernels' time since the last reset and the two events around the kernel of a range
     bool abund = false; McAbundPars abund_pars = {}; McDev<unsigned long long> d_abund; int64_t abund_searched = 0; float abund_ms = 0;
     McEvent ev_abund[2];
+    // mc_set_coverage: the difference array of the depth (nres + nseq slots: k_coverage.h, "Layout"), the scan's 3 x nseq results, the
+    // scan kernels' time since the last reset and the two events around a scan
+    bool cov = false; McDev<uint32_t> d_cov; McDev<unsigned long long> d_covout; float cov_ms = 0;
+    McEvent ev_cov[2];
     McPin<uint8_t> stage_pin[2]; McDev<uint8_t> stage_dev[2]; size_t stage_bytes = 0; McStream copy_stream;   // run_stream (stage_bytes: what all four hold, 0 until they do)
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -870,7 +876,8 @@ static int range_end(mc_handle *h, McCtx &c)
     if (abund) {
         HIPCK(hipEventRecord(h->ev_abund[0], c.stream));
         const uint32_t nr = std::min(c.nrows, c.cap_rows);
-        if (nr) k_abundance<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund);
+        if (nr && h->cov) k_abundance_cov<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund, h->d_off, h->d_cov);   // (the marks ride with the counts: k_coverage.h)
+        else if (nr) k_abundance<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund);
         HIPCK(hipEventRecord(h->ev_abund[1], c.stream));
     }
     if ((size_t)c.nrows > h->pin_slot_cap[h->pin_cur] && !rows_stay(h)) {   // grow the pinned row buffer
@@ -1856,12 +1863,22 @@ extern "C" int mc_set_best_hits_only(mc_handle *h, int on)
 
 // ---- per-gene read counts for RPKG (the reference README, "Normalization"; csrc/k_abundance.h states the rule) ---------------------
 // The counters live in the handle and accumulate over every range that completes (range_end) until they are reset.
+static size_t cov_slots(const mc_handle *h) { return (size_t)h->H.nres + (size_t)h->H.nseq; }   // (every gene's residues and its sentinel)
 static int abund_zero(mc_handle *h)
 {
     HIPCK(hipSetDevice(h->device));
     HIPCK(hipMemset(h->d_abund, 0, sizeof(unsigned long long) * 2 * ((size_t)h->H.nseq + 1)));
     h->abund_searched = 0; h->abund_ms = 0.f;
+    if (h->cov) HIPCK(hipMemset(h->d_cov, 0, sizeof(uint32_t) * cov_slots(h)));   // (counts and depth describe the same reads)
+    h->cov_ms = 0.f;
     return 0;
+}
+
+static void cov_off(mc_handle *h)
+{
+    h->d_cov.reset(); h->d_covout.reset();
+    for (auto &e : h->ev_cov) e.reset();
+    h->cov = false; h->cov_ms = 0.f;
 }
 
 extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t min_aln, double min_bits, double max_loge)
@@ -1873,6 +1890,7 @@ extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t
         h->d_abund.reset();
         for (auto &e : h->ev_abund) e.reset();
         h->abund = false; h->abund_searched = 0; h->abund_ms = 0.f;
+        cov_off(h);
         return 0;
     }
     if (min_ident < 0 || min_ident > 100) { g_err = "mc_set_abundance: min_ident " + std::to_string(min_ident) + " is not a percent from 0 to 100"; return -1; }
@@ -1910,6 +1928,67 @@ extern "C" int mc_abundance_read(mc_handle *h, int64_t *reads, int64_t *aligned,
 }
 
 extern "C" float mc_abundance_ms(const mc_handle *h) { return h ? h->abund_ms : 0.0f; }
+
+// ---- per-gene coverage breadth and depth beside the counts (csrc/k_coverage.h states the rule and the layout) -------------------------
+extern "C" int mc_set_coverage(mc_handle *h, int on)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_coverage: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (!on) { cov_off(h); return 0; }
+    if (!h->abund) { g_err = "mc_set_coverage: abundance counting is off (mc_set_abundance) - coverage is that of the reads it counts"; return -1; }
+    if (!h->d_cov && h->d_cov.alloc(cov_slots(h))) return -1;
+    if (!h->d_covout && h->d_covout.alloc(3 * (size_t)h->H.nseq)) { cov_off(h); return -1; }
+    for (auto &e : h->ev_cov) if (!e && e.create()) { cov_off(h); return -1; }
+    h->cov = true;
+    return abund_zero(h);
+}
+
+// the scan of the difference array as it stands, into d_covout and (when given) depth: device memory of nres values
+static int cov_scan(mc_handle *h, uint32_t *d_depth)
+{
+    const int32_t nseq = (int32_t)h->H.nseq;
+    if (d_depth) HIPCK(hipMemsetAsync(d_depth, 0, sizeof(uint32_t) * (size_t)h->H.nres, 0));
+    HIPCK(hipEventRecord(h->ev_cov[0], 0));
+    k_coverage_scan<<<dim3(((unsigned)nseq + 3) / 4), dim3(256), 0, 0>>>(h->d_abund, h->d_off, h->d_cov, nseq, h->d_covout, d_depth);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(h->ev_cov[1], 0));
+    HIPCK(hipEventSynchronize(h->ev_cov[1]));
+    h->cov_ms += ev_ms(h->ev_cov[0], h->ev_cov[1]);
+    return 0;
+}
+
+extern "C" int mc_coverage_read(mc_handle *h, int64_t *covered, int64_t *spanned, int64_t *max_depth)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->cov) { g_err = "mc_coverage_read: coverage is off (mc_set_coverage)"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (cov_scan(h, nullptr)) return -1;
+    const size_t nseq = (size_t)h->H.nseq;
+    std::vector<unsigned long long> out(3 * nseq);
+    HIPCK(hipMemcpy(out.data(), h->d_covout, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < nseq; s++) {
+        if (covered) covered[s] = (int64_t)out[3 * s];
+        if (spanned) spanned[s] = (int64_t)out[3 * s + 1];
+        if (max_depth) max_depth[s] = (int64_t)out[3 * s + 2];
+    }
+    return 0;
+}
+
+extern "C" int mc_coverage_depth(mc_handle *h, uint32_t *depth, int64_t n)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->cov) { g_err = "mc_coverage_depth: coverage is off (mc_set_coverage)"; return -1; }
+    if (n != h->H.nres || !depth) { g_err = "mc_coverage_depth: the array holds " + std::to_string(n) + " values, the database " + std::to_string(h->H.nres) + " residues"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    McDevBuf buf; uint32_t *d_depth = nullptr;
+    if (buf.get(&d_depth, (size_t)n)) return -1;
+    if (cov_scan(h, d_depth)) return -1;
+    HIPCK(hipMemcpy(depth, d_depth, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" float mc_coverage_ms(const mc_handle *h) { return h ? h->cov_ms : 0.0f; }
 
 extern "C" int64_t mc_result_rows(mc_handle *h, const mc_row **rows) { if (!h) return -1; rows_wait(h); *rows = h->res_rows; return h->n_res_rows; }
 extern "C" int64_t mc_result_best_hits(mc_handle *h, const mc_best_hit **hits) { if (!h) return -1; best_materialize(h); *hits = h->best.data(); return (int64_t)h->best.size(); }

@@ -37,6 +37,9 @@ def parse_arguments(argv=None):
     p.add_argument("--groups", dest="groups", type=str, default=None, metavar="map.tsv", help="TSV of gene and group: adds <out>.groups.tsv with the groups' sums")
     p.add_argument("--ags", dest="ags", type=float, default=None, metavar="VALUE", help="average genome size in bp to normalise by")
     p.add_argument("--ags-report", dest="ags_report", type=str, default=None, metavar="FILE", help="report of run_microbe_census.py (or of the reference) to take the average genome size from")
+    p.add_argument("--coverage", dest="coverage", action="store_true", default=False, help="add covered_aa, breadth (covered_aa / length_aa), mean_depth and max_depth: which part of a gene its reads cover")
+    p.add_argument("--min-breadth", dest="min_breadth", type=float, default=None, metavar="F", help="add the column detected: reads > 0 and breadth >= F (0 < F <= 1); implies --coverage")
+    p.add_argument("--depth-out", dest="depth_out", type=str, default=None, metavar="FILE", help="write the per-residue depth as gene, start, end, depth (0-based start, exclusive end); implies --coverage")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):

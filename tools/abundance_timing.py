@@ -10,7 +10,11 @@ repetition loop, median with min - max.  One JSON line per figure.
                                              commit's has no switch and gives the off side alone
     abundance_timing.py host                 what the kernel replaces: search_files(keep_rows=True) + numpy counting of the rows on the host,
                                              against the counts on with keep_rows=False
---reads (1,000,000), --dense-reads (100,000), --reps (7)."""
+--reads (1,000,000), --dense-reads (100,000), --reps (7).
+--coverage (kernel, files): coverage breadth and depth beside the counts (Engine.set_coverage; csrc/k_coverage.h), the two sides alternating
+inside the repetition loop: `kernel` adds abundance_ms() with the marks riding in the counting kernel and coverage_ms() of one
+coverage() read (the scan); `files` adds the wall time of file -> counts + coverage() with the switch on.  A tree without the switch
+(the parent commit's) gives the off sides alone."""
 import argparse
 import json
 import os
@@ -48,6 +52,7 @@ def main():
     p.add_argument("--reads", type=int, default=1000000)
     p.add_argument("--dense-reads", type=int, default=100000)
     p.add_argument("--reps", type=int, default=7)
+    p.add_argument("--coverage", action="store_true")
     a = p.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     import numpy as np
@@ -57,6 +62,7 @@ def main():
     eng = _native.Engine(device=0)
     eng.set_run(L, model["pars"][str(L)], model["families"])
     has_switch = hasattr(eng, "set_abundance")
+    cov = a.coverage and hasattr(eng, "set_coverage")
     reads = synth.GenomeReads(device="cpu", seed=20261001).single(n, L).numpy()
     if a.what == "kernel":
         names, seqs = _native.load_markers()
@@ -65,20 +71,32 @@ def main():
             eng.upload(rd)
             eng.set_abundance(True)
             ab, tot, rows = [], [], 0
+            ab_cov, tot_cov, scan, figures = [], [], [], None
             for rep in range(a.reps + 1):
-                eng.abundance_reset()
-                t, rows = 0.0, 0
-                for lo in range(0, len(rd), piece):
-                    eng.run_range(lo, min(piece, len(rd) - lo), lo)
-                    st = eng.stats()
-                    t += st["ms_total"]; rows += st["rows"]
-                    assert st["range_splits"] == 0
-                ab.append(eng.abundance_ms() * 1e6 / len(rd)); tot.append(t * 1e6 / len(rd))
+                for marks in ((False, True) if cov else (False,)):
+                    if cov:
+                        eng.set_coverage(marks)
+                    eng.abundance_reset()
+                    t, rows = 0.0, 0
+                    for lo in range(0, len(rd), piece):
+                        eng.run_range(lo, min(piece, len(rd) - lo), lo)
+                        st = eng.stats()
+                        t += st["ms_total"]; rows += st["rows"]
+                        assert st["range_splits"] == 0
+                    (ab_cov if marks else ab).append(eng.abundance_ms() * 1e6 / len(rd)); (tot_cov if marks else tot).append(t * 1e6 / len(rd))
+                    if marks:
+                        figures = eng.coverage()
+                        scan.append(eng.coverage_ms())
             got = eng.abundance()
             eng.set_abundance(False)
-            print(json.dumps({"what": "kernel", "library": label, "reads": len(rd), "rows_per_read": round(rows / len(rd), 2), "assigned": got["assigned"],
-                              "abundance_ms_per_1M_reads": spread(ab[1:]), "range_ms_total_per_1M_reads": spread(tot[1:]),
-                              "share": round(statistics.median(ab[1:]) / statistics.median(tot[1:]), 5)}), flush=True)
+            out = {"what": "kernel", "library": label, "reads": len(rd), "rows_per_read": round(rows / len(rd), 2), "assigned": got["assigned"],
+                   "abundance_ms_per_1M_reads": spread(ab[1:]), "range_ms_total_per_1M_reads": spread(tot[1:]),
+                   "share": round(statistics.median(ab[1:]) / statistics.median(tot[1:]), 5)}
+            if cov:
+                out.update({"coverage": True, "abundance_ms_per_1M_reads_with_marks": spread(ab_cov[1:]), "range_ms_total_per_1M_reads_with_marks": spread(tot_cov[1:]),
+                            "coverage_ms_per_read_of_the_figures": spread(scan[1:]), "genes": len(eng.names), "genes_covered": int((figures["covered"] > 0).sum()),
+                            "max_depth": int(figures["max_depth"].max())})
+            print(json.dumps(out), flush=True)
     else:
         with tempfile.TemporaryDirectory() as d:
             fa = os.path.join(d, "reads.fa")
@@ -86,15 +104,19 @@ def main():
                 for s in range(0, n, 50000):
                     f.write(b"".join(b">r%d\n%s\n" % (s + i, bytes(r)) for i, r in enumerate(reads[s:s + 50000])))
 
-            def run(on, keep_rows):
+            def run(on, keep_rows, marks=False):
                 rd = _native.Reader([fa], L, 10 * n, False, 0, -5, -5, 100, False)
                 try:
                     if has_switch:
                         eng.set_abundance(on)
+                    if cov and on:
+                        eng.set_coverage(marks)                      # (explicitly on both sides: set_abundance(True) leaves coverage as it was)
                     t0 = time.perf_counter()
                     rows, _ = eng.search_files(rd, keep_rows=keep_rows)
                     if on:
                         counts = eng.abundance()["reads"]
+                        if marks:
+                            eng.coverage()
                     elif keep_rows:
                         counts = numpy_counts(rows, len(eng.names))
                     else:
@@ -103,14 +125,18 @@ def main():
                 finally:
                     rd.close()
             if a.what == "files":
-                on, off = [], []
+                on, off, on_cov = [], [], []
                 for rep in range(a.reps + 1):
+                    if cov:
+                        on_cov.append(run(True, False, True)[0])
                     if has_switch:
                         on.append(run(True, False)[0])
                     off.append(run(False, False)[0])
                 out = {"what": "files", "root": os.path.abspath(a.root), "has_switch": has_switch, "reads": n, "off_wall_ms": spread(off[1:])}
                 if has_switch:
                     out["on_wall_ms"] = spread(on[1:])
+                if cov:
+                    out["on_with_coverage_wall_ms"] = spread(on_cov[1:])
                 print(json.dumps(out), flush=True)
             else:
                 dev, host = [], []
