@@ -160,7 +160,8 @@ int mc_ranges_in_flight(const mc_handle *h);
  * (28 bytes; ExtendSeq2Set@0x413b90), 3: the HSP pool (48 bytes; CalRes@0x4077a0), 4: the counts of the gapped extension's chain
  * of kernels (tests/test_gpu_gapped_chain.py), three uint32 - the distinct flanks it extended, those it sent to the second, wider
  * window, those it sent on to full-size rows (AlignGapped@0x40a550); defined for a range that ran unsplit (mc_stats.range_splits
- * == 0).  Returns the number of bytes (copied to dst when they fit cap_bytes; dst may be NULL to ask for the size), -1 on error. */
+ * == 0), 5: one uint32, the form of k_translate_seg the last range launched - 1: the block's reads staged in LDS, 0: read from global
+ * memory (tests/test_gpu_translate_seg.py).  Returns the number of bytes (copied to dst when they fit cap_bytes; dst may be NULL to ask for the size), -1 on error. */
 int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap_bytes, int32_t *record_bytes);
 /* Test aid (tests/test_gpu_owned.py): what the library holds of the HIP runtime in this process, over all handles - out[0] device
  * buffers, [1] pinned host buffers, [2] streams, [3] events.  Counted where each is made and destroyed (csrc/mc_owned.h). */

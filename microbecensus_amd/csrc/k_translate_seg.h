@@ -66,7 +66,7 @@ __device__ __forceinline__ void mc_seg_wave(const double *lnf, const int32_t *fx
     }
     int sp = 1, base = 0, m = 0, i = 0, lowlim = 0, loi = 0, hii = 0;
     bool any = false;
-    if (st != DONE) { ws.stk[0] = 0; ws.stk[1] = (int16_t)n; }
+    if (st != DONE) ws.stk[0] = (int16_t)(uint16_t)(n << 8);
     const unsigned long long ltmask = (1ull << lane) - 1;
     for (;;) {
         MC_TS_TICK(1);
@@ -75,7 +75,7 @@ __device__ __forceinline__ void mc_seg_wave(const double *lnf, const int32_t *fx
             if (st == POP) {
                 if (sp == 0) { st = DONE; break; }
                 sp--;
-                base = ws.stk[2 * sp]; m = ws.stk[2 * sp + 1];
+                base = MC_SEG_START(ws.stk[sp]); m = MC_SEG_LEN(ws.stk[sp]);
                 if (W > m) continue;
                 lo = mc_seg_flags_of(Flo, base, m, W);
                 i = mc_bits_next(lo, 0);
@@ -229,7 +229,7 @@ __device__ __forceinline__ void mc_seg_wave(const double *lnf, const int32_t *fx
             const int leftend = loi + lend, rightend = hii - (myn - rend - 1);
             if (i < leftend) {
                 const int l2 = loi, r2 = leftend - 1;
-                if (sp < 8) { ws.stk[2 * sp] = (int16_t)(base + l2); ws.stk[2 * sp + 1] = (int16_t)(r2 - l2 + 1); sp++; }
+                sp = mc_seg_push(ws.stk, sp, W, base + l2, r2 - l2 + 1);   // (never full: the bound at MC_SEG_STK, mc_core.h)
             }
             mk = mc_bits_or(mk, mc_bits_range(base + leftend, base + rightend));
             any = true;

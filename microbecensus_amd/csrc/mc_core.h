@@ -269,18 +269,49 @@ MC_HD void mc_seg_trim(const McTables &T, const uint8_t *s, int n, int *leftend,
     *leftend = *leftend + lend;
     *rightend = *rightend - (n - rend - 1);
 }
+// ---- the work list that stands in for Seg::segseq's recursion --------------------------------------------------------------
+// Seg::segseq scans a segment and, for every low-complexity stretch whose trimmed window starts right of the stretch's first
+// low window, calls itself on the remainder [loi, leftend) left of the masked block [leftend, rightend].  Here the remainder
+// goes onto a list and is scanned later (the result is a set of positions: the order does not matter).  A remainder shorter
+// than the window W is never scanned (`if (W > m) continue`), so it is not listed either.  MC_SEG_STK entries are enough:
+//   * call an entry's footprint the entry plus the residue behind it, leftend: the first residue of the masked block that
+//     followed it.  leftend <= rightend <= hii <= m - 1, so a footprint lies inside the segment whose scan listed it, and it
+//     has at least W + 1 residues;
+//   * two entries of one scan have disjoint footprints: after a stretch the scan goes on at lowlim = min(hii, rightend) + 1
+//     > leftend, and the next remainder starts at loi >= lowlim;
+//   * a segment is taken off the list BEFORE its scan lists anything, and all it lists lies inside it, hence inside its own
+//     footprint, which was disjoint from every other footprint on the list.  By induction the footprints on the list are
+//     pairwise disjoint at all times, and all lie in [0, n);
+//   * so the list never holds more than n / (W + 1) entries: 170 / 13 = 13 for W = 12, 11 / 9 = 1 for W = 8.
+// An entry is start | length << 8 (both <= MC_MAXAA; the 16 bits are kept in the int16_t the workspace has always been made of):
+// 16 entries are the 32 bytes the kernel's LDS row has for them - and the int16_t[16] every caller of McSegWS passes.
+// A push onto a full list cannot happen; a build that wants to see one anyway defines MC_SEG_ON_FULL (tests/emul/seg_forms.cpp).
+#define MC_SEG_STK 16
+static_assert(MC_MAXAA / 13 < MC_SEG_STK && MC_MAXAA <= 255, "the SEG work list: n / (W + 1) entries of 8 + 8 bits");
+#ifndef MC_SEG_ON_FULL
+#define MC_SEG_ON_FULL() ((void)0)
+#endif
+#define MC_SEG_START(e) ((int)((uint16_t)(e) & 255))
+#define MC_SEG_LEN(e) ((int)((uint16_t)(e) >> 8))
+MC_HD int mc_seg_push(int16_t *stk, int sp, int W, int start, int len)
+{ // returns the new number of entries
+    if (len < W) return sp;
+    if (sp >= MC_SEG_STK) { MC_SEG_ON_FULL(); return sp; }
+    stk[sp] = (int16_t)(uint16_t)(start | (len << 8));
+    return sp + 1;
+}
 // Seg::segseq@0x43a9e0 with the recursion turned into a work list (the result is a set of positions,
 // so the order in which sub-ranges are handled does not matter).  H must hold n doubles.
 MC_HDN void mc_seg_mask(const McTables &T, const uint8_t *prot, int n, uint8_t *maskbits /* (MC_MAXAA+7)/8 */, double *H)
 {
     int W = (n <= 11) ? 8 : 12;
-    int16_t stk_s[16], stk_n[16];
+    int16_t stk[MC_SEG_STK];
     int sp = 0;
     for (int i = 0; i < (MC_MAXAA + 7) / 8; i++) maskbits[i] = 0;
-    stk_s[0] = 0; stk_n[0] = (int16_t)n; sp = 1;
+    stk[0] = (int16_t)(uint16_t)(n << 8); sp = 1;
     while (sp > 0) {
         sp--;
-        int base = stk_s[sp], m = stk_n[sp];
+        int base = MC_SEG_START(stk[sp]), m = MC_SEG_LEN(stk[sp]);
         const uint8_t *s = prot + base;
         if (W > m) continue;
         // Seg::seqent@0x43a2e0
@@ -313,7 +344,7 @@ MC_HDN void mc_seg_mask(const McTables &T, const uint8_t *prot, int n, uint8_t *
                 mc_seg_trim(T, s + leftend, rightend - leftend + 1, &leftend, &rightend);
                 if (i < leftend) {
                     int lend = loi, rend = leftend - 1;
-                    if (sp < 16) { stk_s[sp] = (int16_t)(base + lend); stk_n[sp] = (int16_t)(rend - lend + 1); sp++; }
+                    sp = mc_seg_push(stk, sp, W, base + lend, rend - lend + 1);
                 }
                 for (j = leftend; j <= rightend; j++) maskbits[(base + j) >> 3] |= (uint8_t)(1u << ((base + j) & 7));
                 i = (hii < rightend) ? hii : rightend;
@@ -328,9 +359,9 @@ MC_HDN void mc_seg_mask(const McTables &T, const uint8_t *prot, int n, uint8_t *
 //   * the per-window entropies are reduced to the two facts SEG ever uses (H <= 2.2, H <= 2.5), kept as bit sets;
 //   * the sorted state vector is maintained incrementally (Seg::decrementsv/incrementsv@0x438d30/0x438d70)
 //     instead of being re-sorted for every window;
-//   * all arrays live in a caller-provided workspace (LDS on the device): comp[20], sv[24], stack[16] (int16 pairs).
+//   * all arrays live in a caller-provided workspace (LDS on the device): comp[20], sv[24], the work list (MC_SEG_STK entries of 16 bits).
 // ---------------------------------------------------------------------------------------------
-struct McSegWS { uint8_t *comp; uint8_t *sv; int16_t *stk; };   // 20 B, 24 B, 32 B
+struct McSegWS { uint8_t *comp; uint8_t *sv; int16_t *stk; };   // 20 B, 24 B, 32 B (MC_SEG_STK entries)
 
 MC_HD void mc_sv_dec(uint8_t *sv, int x)
 { // a class with count x loses one member: the LAST entry equal to x becomes x-1 (keeps the vector sorted)
@@ -522,11 +553,11 @@ MC_HDN void mc_seg_mask_ws(const McTables &T, uint8_t *prot, int n, const McSegW
     mc_bits_clear(mk);
     if (W > n) return;
     int sp = 1;
-    ws.stk[0] = 0; ws.stk[1] = (int16_t)n;
+    ws.stk[0] = (int16_t)(uint16_t)(n << 8);
     bool any = false;
     while (sp > 0) {
         sp--;
-        int base = ws.stk[2 * sp], m = ws.stk[2 * sp + 1];
+        int base = MC_SEG_START(ws.stk[sp]), m = MC_SEG_LEN(ws.stk[sp]);
         const uint8_t *s = prot + base;
         if (W > m) continue;
         mc_bits_clear(lo); mc_bits_clear(hi);
@@ -559,7 +590,7 @@ MC_HDN void mc_seg_mask_ws(const McTables &T, uint8_t *prot, int n, const McSegW
                 mc_seg_trim_ws(T.lnfac, s + leftend, rightend - leftend + 1, &leftend, &rightend, ws);
                 if (i < leftend) {
                     int lend = loi, rend = leftend - 1;
-                    if (sp < 8) { ws.stk[2 * sp] = (int16_t)(base + lend); ws.stk[2 * sp + 1] = (int16_t)(rend - lend + 1); sp++; }
+                    sp = mc_seg_push(ws.stk, sp, W, base + lend, rend - lend + 1);
                 }
                 for (j = leftend; j <= rightend; j++) mc_bits_set(mk, base + j);
                 any = true;
@@ -590,11 +621,11 @@ MC_HDN void mc_seg_mask_fx(const double *lnfac /* McTables::lnfac */, const int3
     mc_bits_clear(mk);
     if (W > n) return;
     int sp = 1;
-    ws.stk[0] = 0; ws.stk[1] = (int16_t)n;
+    ws.stk[0] = (int16_t)(uint16_t)(n << 8);
     bool any = false;
     while (sp > 0) {
         sp--;
-        const int base = ws.stk[2 * sp], m = ws.stk[2 * sp + 1];
+        const int base = MC_SEG_START(ws.stk[sp]), m = MC_SEG_LEN(ws.stk[sp]);
         const uint8_t *s = prot + base;
         if (W > m) continue;
         mc_bits_clear(lo); mc_bits_clear(hi);
@@ -631,7 +662,7 @@ MC_HDN void mc_seg_mask_fx(const double *lnfac /* McTables::lnfac */, const int3
                 else mc_seg_trim_ws(lnfac, s + leftend, rightend - leftend + 1, &leftend, &rightend, ws);
                 if (i < leftend) {
                     int lend = loi, rend = leftend - 1;
-                    if (sp < 8) { ws.stk[2 * sp] = (int16_t)(base + lend); ws.stk[2 * sp + 1] = (int16_t)(rend - lend + 1); sp++; }
+                    sp = mc_seg_push(ws.stk, sp, W, base + lend, rend - lend + 1);
                 }
                 for (j = leftend; j <= rightend; j++) mc_bits_set(mk, base + j);
                 any = true;
@@ -773,11 +804,11 @@ MC_HDN void mc_seg_mask_fx2(const double *lnfac, const int32_t *fx, uint8_t *pro
     mc_seg_window_flags(fx, prot, n, W, ws.comp, Flo, Fhi);
     if (!(Flo.a | Flo.b | Flo.c)) return;
     int sp = 1;
-    ws.stk[0] = 0; ws.stk[1] = (int16_t)n;
+    ws.stk[0] = (int16_t)(uint16_t)(n << 8);
     bool any = false;
     while (sp > 0) {
         sp--;
-        const int base = ws.stk[2 * sp], m = ws.stk[2 * sp + 1];
+        const int base = MC_SEG_START(ws.stk[sp]), m = MC_SEG_LEN(ws.stk[sp]);
         const uint8_t *s = prot + base;
         if (W > m) continue;
         const McBits192 lo = mc_seg_flags_of(Flo, base, m, W), hi = mc_seg_flags_of(Fhi, base, m, W);
@@ -791,7 +822,7 @@ MC_HDN void mc_seg_mask_fx2(const double *lnfac, const int32_t *fx, uint8_t *pro
             else mc_seg_trim_ws(lnfac, s + leftend, rightend - leftend + 1, &leftend, &rightend, ws);
             if (i < leftend) {
                 const int lend = loi, rend = leftend - 1;
-                if (sp < 8) { ws.stk[2 * sp] = (int16_t)(base + lend); ws.stk[2 * sp + 1] = (int16_t)(rend - lend + 1); sp++; }
+                sp = mc_seg_push(ws.stk, sp, W, base + lend, rend - lend + 1);
             }
             mk = mc_bits_or(mk, mc_bits_range(base + leftend, base + rightend));
             any = true;

@@ -51,6 +51,7 @@ struct McCtx {
     McStream stream; hipStream_t side = nullptr, side2 = nullptr;   // the pipeline of a range, and two side streams of the ordering / finishing kernels (borrowed: the handle's)
     McEvent ev[8], ev_fork, ev_join, ev_join2;
     int64_t cap_reads = 0; int pool_len = 0;                       // the pools hold cap_reads reads of up to pool_len bases
+    int ts_staged = -1;                                            // the form of k_translate_seg the last range launched (mc_debug_stage 5)
     uint32_t cap_tasks = 0, cap_gaps = 0, cap_hsps = 0, cap_rows = 0;
     McDev<uint8_t> d_frames_base; uint8_t *d_frames = nullptr;   // (a view 64 bytes in: k_eval_seeds reads 8 bytes at a time backwards from a seed)
     McDev<unsigned long long> d_stats;
@@ -557,6 +558,7 @@ static int stage_a(mc_handle *h, McCtx &c)
     const size_t cu_lds = 160 * 1024 - 1024;                      // (static LDS of the kernel and allocation granules)
     const bool staged = ts_force >= 0 ? ts_force != 0 : cu_lds / lds_staged >= cu_lds / lds_direct;   // staging stays while it does not cost a resident workgroup
     const size_t lds = staged ? lds_staged : lds_direct;
+    c.ts_staged = staged ? 1 : 0;
     const unsigned ts_blocks = (unsigned)((n + MC_TS_READS - 1) / MC_TS_READS);
     if (staged) {
         if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -968,7 +970,7 @@ extern "C" int mc_ranges_in_flight(const mc_handle *h) { return h ? h->pipe_nout
 // split they are the last piece's).
 extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap_bytes, int32_t *record_bytes)
 {
-    if (!h || !h->run_set || what < 0 || what > 4) { g_err = "mc_debug_stage: bad argument"; return -1; }
+    if (!h || !h->run_set || what < 0 || what > 5) { g_err = "mc_debug_stage: bad argument"; return -1; }
     if (h->pipe_nout) { g_err = "mc_debug_stage: ranges are in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     const McCtx &c = h->ctx;
@@ -977,6 +979,13 @@ extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap
         const uint32_t v[3] = {c.h_c[C_ITEMS], c.h_c[C_RETRY], c.h_c[C_RETRY2]};
         if (record_bytes) *record_bytes = (int32_t)sizeof(uint32_t);
         if (dst && (int64_t)sizeof v <= cap_bytes) memcpy(dst, v, sizeof v);
+        return (int64_t)sizeof v;
+    }
+    if (what == 5) {
+        if (c.ts_staged < 0) { g_err = "mc_debug_stage: no range has run"; return -1; }
+        const uint32_t v = (uint32_t)c.ts_staged;
+        if (record_bytes) *record_bytes = (int32_t)sizeof v;
+        if (dst && (int64_t)sizeof v <= cap_bytes) memcpy(dst, &v, sizeof v);
         return (int64_t)sizeof v;
     }
     const void *src = nullptr; int64_t bytes = 0; int32_t rec = 0;

@@ -143,8 +143,8 @@ def test_gpu_index_structures_agree_with_the_binary_searches(emul_bin, markers_f
 
 
 def test_seg_variants_agree_frame_by_frame(emul_bin, markers_faa, tmp_path):
-    """The fixed-point / register SEG the kernel runs against the plain restatement, on every frame of the config-1 reads;
-    the emulation also proves the integer entropy tests over every possible window composition (mc_seg_fx_verify)."""
+    """The fixed-point / register SEG the kernel runs against the plain restatement, on every frame of the config-1 reads and of a
+    generated 510-bp set; the emulation also proves the integer entropy tests over every possible window composition (mc_seg_fx_verify)."""
     import gzip
     fa = tmp_path / "c1.fa"
     fa.write_bytes(gzip.open(os.path.join(GOLD, "config1_example_fq.reads.fa.gz")).read())
@@ -155,6 +155,16 @@ def test_seg_variants_agree_frame_by_frame(emul_bin, markers_faa, tmp_path):
     assert "0 disagreements over all window compositions" in err
     assert ", 0 differ from the plain restatement" in err
     assert "base codes: 0 of 512 differ" in err
+    # ... and on 500 reads of 510 bp built for SEG's corners (tests/seg_cases.py: many stretches per frame, stretches over 100
+    # residues, remainders that fill the work list): the register forms of the flags and compositions on that content
+    import seg_cases
+    gen = seg_cases.make_reads(510, 500, seed=1)
+    fa2 = tmp_path / "seg510.fa"
+    fa2.write_bytes(b"".join(b">%d\n%s\n" % (i, bytes(r)) for i, r in enumerate(gen)))
+    r = subprocess.run([emul_bin, markers_faa, str(fa2), str(tmp_path / "o2.m8")], env=env, stderr=subprocess.PIPE)
+    err = r.stderr.decode()
+    assert r.returncode == 0, err
+    assert "seg check: 3000 frames, 0 differ from the plain restatement" in err
 
 
 def test_shared_algorithms_and_reader_under_sanitizers(markers_faa, tmp_path):
