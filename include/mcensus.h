@@ -38,6 +38,9 @@ typedef struct mc_best_hit {
 typedef struct mc_stats {
     int64_t reads, seed_tasks, gap_tasks, hsps, rows, reads_with_rows, classified;
     int64_t bucket_lookups, key_probes;   /* algorithmic traffic of the seed kernel: 8 B and 2 B reads */
+    /* HIP event intervals of the six stages.  ms_translate is the translation kernel's own interval wherever it ran: where it was
+     * issued ahead (mc_range_end) it shared the device with the ordering and finishing kernels of the range before and took longer
+     * than alone.  ms_total is the SUM of the six: it can exceed the wall time of a step, in which stages of two ranges overlap. */
     float ms_translate, ms_seed, ms_eval, ms_gapped, ms_sort, ms_finish, ms_total;
     /* what the seed kernel itself asked its structures (timed form): 9-mer filter words (4 B), wildcard filter lines (32 B),
      * pair filter blocks (16 B), bucket records + key groups searched (32 B + 16 B); seed_tasks postings (4 B) came out */
@@ -149,10 +152,20 @@ int mc_run_range(mc_handle *h, int64_t first, int64_t count, int64_t first_read_
  * device: a second mc_range_begin() before mc_range_end() is refused.  mc_search() / mc_search_files() run their batches this
  * way, bench.py its steps.  mc_range_end() returns -2 when the range overflowed a pool: it is then no longer in flight - give
  * it to mc_run_range(), which runs it in smaller pieces.  mc_run_range() and mc_search*() refuse to run while a range is in
- * flight.  Results never depend on any of this. */
+ * flight.  Results never depend on any of this.
+ * Looking ahead: the ordering and finishing kernels of a range leave the device nearly empty, and the translation of the NEXT range
+ * needs nothing of this one.  mc_range_end() therefore issues, behind the range's gapped stage and on a stream of its own, the
+ * translation of the range it expects next: the one that follows contiguously in the same resident read set - first + count, up to
+ * count reads, clipped to the set, nothing at its end - which is how mc_search(), mc_search_files() and bench.py walk a set.  An
+ * mc_range_begin() / mc_run_range() of that range, or of fewer reads from the same first read, with the same resident reads, read
+ * length and tables, finds its frames there and starts with the seed kernel; any other range waits for the lookahead's kernel and
+ * translates itself.  A wrong guess costs one translation beside work the device was waiting through anyway and never changes a
+ * result; whatever replaces reads, tables or pools, mc_debug_stage() and mc_close() wait for a lookahead and discard it.
+ * mc_run_range() issues none.  mc_ranges_translated_ahead(): the ranges begun since mc_open() that used a lookahead. */
 int mc_range_begin(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id);
 int mc_range_end(mc_handle *h);
 int mc_ranges_in_flight(const mc_handle *h);
+int64_t mc_ranges_translated_ahead(const mc_handle *h);
 
 /* Test aid (tests/test_gpu_parity.py, per-stage parity with the CPU emulation of the kernels' per-thread code): what the stages of
  * the last mc_run_range() left on the device - what = 0: the six translated, SEG-masked frames of every read (rows of

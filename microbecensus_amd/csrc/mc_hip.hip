@@ -37,6 +37,7 @@
 #include "k_abundance.h"
 #include "k_coverage.h"
 #include "mc_pieces.h"
+#include "mc_ahead.h"
 #include "mc_owned.h"
 
 #include <map>
@@ -64,7 +65,9 @@ struct McCtx {
     // pinned host mirrors
     McPin<uint32_t> h_c; McPin<unsigned long long> h_stats; McPin<McBestHit> h_best; size_t h_best_cap = 0;
     // the range being processed
-    const uint8_t *reads = nullptr; int64_t n = 0, first_read_id = 0;
+    const uint8_t *reads = nullptr; int64_t n = 0, first_read_id = 0, first = 0;   // (first: the range's first read in the resident set)
+    int ahead_from = -1;                                           // the pair of the handle's ahead_ev around the lookahead this range used; -1: none
+    bool own_a0 = true;                                            // ev[0], ev[1] are around a translation of the range's own (all of it, or the reads behind the lookahead's)
     uint32_t ntasks = 0, ngaps = 0, gpad = 0, nh = 0, nh_all = 0, nheads = 0, nrows = 0, nbest = 0, nsegs = 0;
     bool busy = false;                                             // a range has been begun and not ended
 };
@@ -106,6 +109,12 @@ struct mc_handle {
     McDev<uint8_t> d_reads;
     const uint8_t *reads_dev = nullptr;   // resident read set (own buffer or attached caller memory)
     McCtx ctx;
+    // the lookahead (mc_ahead.h): the translation of the range expected next, on a stream of its own beside the ordering and finishing
+    // kernels of the running range.  ahead_ev[p]: the events around the kernel of lookahead p (two pairs in turn: the range that used
+    // lookahead p reads its translation time at ITS range_end, after the lookahead for the range behind it has been issued);
+    // ahead_wait: the kernel of ahead_ev[ahead_p] may still be running and nothing has been made to wait for it yet.
+    McStream ahead_stream; McEvent ahead_ev[2][2]; int ahead_p = 0; bool ahead_wait = false;
+    McAhead ahead; uint64_t reads_gen = 0, tables_gen = 0; int64_t ahead_used = 0;
     // host results: rows of the last run land in pinned memory; mc_search() accumulates its batches in all_rows
     // The rows travel to the host while the caller goes on (two pinned buffers in turn, a stream and an event of their own):
     // mc_run_range() returns when the best hits are there; whoever looks at the rows waits for their copy (rows_wait).
@@ -121,6 +130,19 @@ struct mc_handle {
     McClasses cls = {}; bool cls_set = false, cls_results = false; std::vector<McClassPars> cls_pars;
     std::vector<uint8_t> best_cls; int64_t cls_reads[MC_CL_BINS] = {};
 };
+
+// The lookahead is given up: its kernel is waited for (after its event it is harmless) and its frames are nobody's.  Before anything
+// that assumes a quiet device once no range is in flight - new reads, new tables, new pools, a look at d_frames, the end of the handle.
+static void ahead_drop(mc_handle *h)
+{
+    if (h->ahead_wait) { (void)hipStreamSynchronize(h->ahead_stream); h->ahead_wait = false; }   // (nothing but lookaheads runs in that stream)
+    mc_ahead_drop(h->ahead);
+}
+static constexpr bool MC_AHEAD_ON = true;                          // range_end issues lookaheads (off: every range translates in its own range_begin, as before)
+static McAheadKey ahead_key(const mc_handle *h, int64_t first, int64_t count) { return {h->reads_gen, first, count, h->read_len, h->FP, h->tables_gen}; }
+// the resident reads are about to change (the buffer, or what it holds) / the run's tables on the device are
+static void reads_change(mc_handle *h) { ahead_drop(h); h->reads_gen++; }
+static void tables_change(mc_handle *h) { ahead_drop(h); h->tables_gen++; }
 
 static McIndex dev_index(const mc_handle *h)
 {
@@ -143,6 +165,7 @@ extern "C" void mc_close(mc_handle *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
+    ahead_drop(h);                                                  // (a lookahead may still be writing d_frames)
     if (h->rows_stream) (void)hipStreamSynchronize(h->rows_stream);
     delete h;
 }
@@ -208,6 +231,8 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
         if (c.h_c.alloc(C_N) || c.h_stats.alloc(S_N)) return -1;
     }
     if (h->rows_stream.create() || h->ev_rows.create(false)) return -1;
+    if (h->ahead_stream.create()) return -1;                       // (an ordinary stream: one of the lowest priority measured no better - DESIGN.md 5.5)
+    for (auto &pair : h->ahead_ev) for (auto &e : pair) if (e.create()) return -1;
     const McHostIndex &H = h->H;
     if (H.res.size() >= MC_TASK_ABS_LIMIT) { g_err = "marker database too large: more than 16 M residues (MC_TASK_W3)"; return -1; }
     if (h->d_res_base.alloc(H.res.size() + 128) || h->d_off.alloc(H.off.size()) || h->d_bstart.alloc(H.bstart.size()) || h->d_post.alloc(H.post.size() + 1) || h->d_post8.alloc((H.post.size() + 1) * MC_POST_WORDS) ||
@@ -384,6 +409,7 @@ extern "C" int mc_set_run(mc_handle *h, int32_t read_len, double loge_thr, const
     MC_OT("set_run: tables", t0);
     if (mc_seg_fx_verify(h->hT, nullptr) != 0) { g_err = "internal: the fixed-point SEG tests disagree with the reference arithmetic"; return -1; }
     MC_OT("set_run: seg_fx_verify", t0);
+    tables_change(h);                                              // (a lookahead reads d_T, and its frames have this run's pitch)
     memset(&h->hP, 0, sizeof h->hP);
     h->hP.nfam = h->nfam; h->hP.read_len = read_len;
     for (int f = 0; f < h->nfam; f++) { h->hP.min_cov[f] = min_cov[f]; h->hP.min_score[f] = min_score[f]; h->hP.max_aaid[f] = max_aaid[f]; h->hP.aln_stat[f] = aln_stat[f]; }
@@ -408,6 +434,7 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
 {
     if (nreads <= c.cap_reads && h->read_len <= c.pool_len) return 0;   // (pools sized for longer reads fit shorter ones: mc_search_varlen)
     if (h->best_from == &c) best_materialize(h);                   // (the best hits of the range before still lie in the pinned buffer that is about to be replaced)
+    ahead_drop(h);                                                  // (d_frames_base is about to be freed)
     double t0 = mc_now();
     int64_t cap = nreads;
     if (cap > (1 << 21) - 1) { g_err = "batch larger than 2097151 reads"; return -1; }
@@ -445,7 +472,7 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
 static int reads_reserve(mc_handle *h, int64_t nreads)
 {
     const int64_t need = nreads * (int64_t)h->read_len + 16;
-    if (need > h->cap_own) { if (h->d_reads.alloc((size_t)need)) return -1; h->cap_own = need; }
+    if (need > h->cap_own) { reads_change(h); if (h->d_reads.alloc((size_t)need)) return -1; h->cap_own = need; }
     return 0;
 }
 
@@ -453,6 +480,7 @@ extern "C" int mc_upload(mc_handle *h, const uint8_t *reads, int64_t nreads)
 {
     if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
     HIPCK(hipSetDevice(h->device));
+    reads_change(h);
     if (reads_reserve(h, nreads)) return -1;
     if (nreads) HIPCK(hipMemcpyAsync(h->d_reads, reads, (size_t)nreads * h->read_len, hipMemcpyHostToDevice, h->ctx.stream));
     HIPCK(hipStreamSynchronize(h->ctx.stream));
@@ -463,6 +491,7 @@ extern "C" int mc_upload(mc_handle *h, const uint8_t *reads, int64_t nreads)
 extern "C" int mc_attach(mc_handle *h, const void *device_reads, int64_t nreads)
 {
     if (!h || !h->run_set) { g_err = "mc_set_run() must be called first"; return -1; }
+    reads_change(h);
     h->reads_dev = (const uint8_t *)device_reads; h->nreads = nreads;
     return 0;
 }
@@ -478,8 +507,9 @@ static int counters_to_host(McCtx &c) { HIPCK(hipMemcpyAsync(c.h_c, c.d_counters
 // The cycle counters of the MC_EXP_TIMING build (DESIGN's cycle tables), printed to stderr and cleared: at the end of the translation
 // (stage 'a') and of the finishing (stage 'd').  Without that build: nothing.
 #ifdef MC_EXP_TIMING
-static int exp_timing_dump(McCtx &c, char stage)
+static int exp_timing_dump(mc_handle *h, McCtx &c, char stage)
 {
+    ahead_drop(h);                                                  // (a lookahead's kernel adds to the same counters)
     if (stage == 'a') {
         HIPCK(hipStreamSynchronize(c.stream));
         unsigned long long acc[12], cnt[12];
@@ -535,23 +565,17 @@ static int exp_timing_dump(McCtx &c, char stage)
     return 0;
 }
 #else
-static int exp_timing_dump(McCtx &, char) { return 0; }
+static int exp_timing_dump(mc_handle *, McCtx &, char) { return 0; }
 #endif
 
-// A: translation + SEG, seed enumeration, seed evaluation (gate, growth, ungapped X-drop)
-static int stage_a(mc_handle *h, McCtx &c)
+// A0: translation + SEG of the n reads at `reads` into the frames of reads at .. at + n - 1 of d_frames, on stream st between the
+// events e0 and e1.  It reads the reads, d_T and d_segtab and writes nothing but those frames: stage C of a running range still reads
+// d_low and the counters, and A0 may run beside it (range_end).
+static int stage_a0(mc_handle *h, McCtx &c, hipStream_t st, const uint8_t *reads, int64_t at, int64_t n, hipEvent_t e0, hipEvent_t e1)
 {
-    const int64_t n = c.n;
     const int L = h->read_len, FP = h->FP;
-    hipStream_t st = c.stream;
-    McIndex X = dev_index(h);
-    c.ntasks = c.ngaps = c.gpad = c.nh = c.nheads = c.nrows = c.nbest = c.nsegs = 0;
-    HIPCK(hipMemsetAsync(c.d_counters, 0, sizeof(uint32_t) * C_N, st));
-    HIPCK(hipMemsetAsync(c.d_stats, 0, sizeof(unsigned long long) * S_N, st));
-    if (h->best_only) HIPCK(hipMemsetAsync(c.d_cand, 0, (size_t)n, st));
-    HIPCK(hipMemsetAsync(c.d_low, 0, (size_t)n, st));
-    HIPCK(hipEventRecord(c.ev[0], st));
-    const int64_t threads = n * 6;
+    uint8_t *frames = c.d_frames + at * 6 * FP;                   // (FP is a multiple of 4: the kernel's word stores stay aligned)
+    HIPCK(hipEventRecord(e0, st));
     const size_t lds_rest = (size_t)MC_TS_NLNF(FP) * 8 + (size_t)MC_TS_THREADS * MC_TS_STRIDE(FP);
     const size_t lds_staged = (size_t)MC_TS_STAGE(L) + lds_rest, lds_direct = (size_t)MC_TS_STAGE(0) + lds_rest;
     static const int ts_force = getenv("MC_TS_STAGED") ? atoi(getenv("MC_TS_STAGED")) : -1;
@@ -562,13 +586,33 @@ static int stage_a(mc_handle *h, McCtx &c)
     const unsigned ts_blocks = (unsigned)((n + MC_TS_READS - 1) / MC_TS_READS);
     if (staged) {
         if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_translate_seg<true><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, c.reads, L, n, c.d_frames, FP, h->d_segtab);
+        k_translate_seg<true><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, reads, L, n, frames, FP, h->d_segtab);
     } else {
         if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_translate_seg<false><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, c.reads, L, n, c.d_frames, FP, h->d_segtab);
+        k_translate_seg<false><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, reads, L, n, frames, FP, h->d_segtab);
     }
-    HIPCK(hipEventRecord(c.ev[1], st));
-    if (exp_timing_dump(c, 'a')) return -1;
+    HIPCK(hipEventRecord(e1, st));
+    return 0;
+}
+
+// A: the counters cleared, then A0 of the reads no lookahead has translated (range_begin: `covered` of them it has, from the range's
+// first), then A1: seed enumeration, seed evaluation (gate, growth, ungapped X-drop)
+static int stage_a(mc_handle *h, McCtx &c, int64_t covered)
+{
+    const int64_t n = c.n;
+    const int L = h->read_len, FP = h->FP;
+    hipStream_t st = c.stream;
+    McIndex X = dev_index(h);
+    c.ntasks = c.ngaps = c.gpad = c.nh = c.nheads = c.nrows = c.nbest = c.nsegs = 0;
+    HIPCK(hipMemsetAsync(c.d_counters, 0, sizeof(uint32_t) * C_N, st));
+    HIPCK(hipMemsetAsync(c.d_stats, 0, sizeof(unsigned long long) * S_N, st));
+    if (h->best_only) HIPCK(hipMemsetAsync(c.d_cand, 0, (size_t)n, st));
+    HIPCK(hipMemsetAsync(c.d_low, 0, (size_t)n, st));
+    c.own_a0 = covered < n;
+    if (!c.own_a0) HIPCK(hipEventRecord(c.ev[1], st));             // (the seed kernel's interval starts here: the stream has waited for the lookahead)
+    else if (stage_a0(h, c, st, c.reads + covered * L, covered, n - covered, c.ev[0], c.ev[1])) return -1;
+    if (exp_timing_dump(h, c, 'a')) return -1;
+    const int64_t threads = n * 6;
     if (h->fast_enum) {
         // k_enumerate_q (round 5: queues that persist across the reads of a chunk) is the kernel of the product path; the counting form
         // (mc_set_counting: what the reference would read) is k_enumerate_count (rounds 2 - 4's one-wave-per-read kernel without filters).
@@ -749,7 +793,7 @@ static int stage_d(mc_handle *h, McCtx &c)
         k_emit_rows<<<dim3((nheads + 255) / 256), dim3(256), 0, st>>>(c.d_heads, nheads, c.d_nrow, c.d_rowoff, c.d_tmp, c.d_rows, c.cap_rows, c.d_bestof, c.d_best, c.d_counters, h->best_only ? 0 : 1);
     }
     HIPCK(hipEventRecord(c.ev[6], st));
-    if (exp_timing_dump(c, 'd')) return -1;
+    if (exp_timing_dump(h, c, 'd')) return -1;
     HIPCK(hipMemcpyAsync(c.h_stats, c.d_stats, sizeof(unsigned long long) * S_N, hipMemcpyDeviceToHost, st));
     return counters_to_host(c);
 }
@@ -838,10 +882,29 @@ extern "C" int mc_run_range(mc_handle *h, int64_t first, int64_t count, int64_t 
 static int range_begin(mc_handle *h, McCtx &c, int64_t first, int64_t count, int64_t first_read_id)
 {
     if (ensure_capacity(h, c, count)) return -1;
-    c.reads = h->reads_dev + first * h->read_len; c.n = count; c.first_read_id = first_read_id;
-    const int rc = stage_a(h, c);
+    c.reads = h->reads_dev + first * h->read_len; c.n = count; c.first_read_id = first_read_id; c.first = first;
+    // A lookahead that covers the range has written its frames already; one that does not is over.  Either way the range's stream
+    // waits for the lookahead's kernel before A1 reads d_frames or A0 writes them.
+    const int64_t covered = mc_ahead_take(h->ahead, ahead_key(h, first, count));   // (reads of the range, from its first; a longer range translates the rest itself)
+    if (h->ahead_wait) { HIPCK(hipStreamWaitEvent(c.stream, h->ahead_ev[h->ahead_p][1], 0)); h->ahead_wait = false; }
+    c.ahead_from = covered ? h->ahead_p : -1;
+    if (covered) { h->ahead_used++; h->ahead_p ^= 1; }              // (the lookahead behind this range takes the other pair of events)
+    const int rc = stage_a(h, c, covered);
     if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
     c.busy = true;
+    return 0;
+}
+
+// The translation of the range expected next - reads [first, first + count) of the resident set as it is now - beside what is left of
+// the running range: issued behind the event that ends its gapped stage, the last reader of d_frames.  No range larger than the pools.
+static int ahead_issue(mc_handle *h, McCtx &c, int64_t first, int64_t count)
+{
+    if (count <= 0 || count > c.cap_reads || h->read_len > c.pool_len || first < 0 || first + count > h->nreads || !h->reads_dev) return 0;
+    ahead_drop(h);
+    HIPCK(hipStreamWaitEvent(h->ahead_stream, c.ev[4], 0));
+    h->ahead_wait = true;                                           // (from here on something may be in the stream)
+    if (stage_a0(h, c, h->ahead_stream, h->reads_dev + first * h->read_len, 0, count, h->ahead_ev[h->ahead_p][0], h->ahead_ev[h->ahead_p][1])) { ahead_drop(h); return -1; }
+    mc_ahead_offer(h->ahead, ahead_key(h, first, count));
     return 0;
 }
 
@@ -857,7 +920,7 @@ static void best_materialize(mc_handle *h)
     for (uint32_t i = 0; i < nb; i++) { const McBestHit &x = c->h_best[i]; mc_best_hit &o = h->best[i]; o.read = x.read; o.family = x.family; o.aln = x.aln; o.target_len = x.target_len; o.bits = x.bits; }
 }
 
-static int range_end(mc_handle *h, McCtx &c)
+static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t next_count = 0)
 {
     c.busy = false;
     h->cls_results = false;
@@ -866,10 +929,11 @@ static int range_end(mc_handle *h, McCtx &c)
     h->stats.reads = c.n;
     int rc = stage_wait(c);
     if (rc == 0) rc = stage_b(h, c);
+    if (rc == 0 && MC_AHEAD_ON) rc = ahead_issue(h, c, next_first, next_count);   // (B's kernels are issued: d_frames is free behind ev[4])
     if (rc == 0 && (rc = stage_wait(c)) == 0 && (rc = stage_c(h, c)) == 0) rc = stage_d(h, c);   // (C leaves its counts on the device: D is issued behind it)
     if (rc == 0) rc = stage_wait(c);
     if (rc == 0 && c.h_c[C_OVERFLOW]) { g_err = "row buffer overflow"; rc = -2; }
-    if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
+    if (rc) { (void)hipStreamSynchronize(c.stream); ahead_drop(h); return rc; }   // (-2: the caller answers with mc_run_range on this range, whose A0 writes d_frames)
     h->pin_cur ^= 1;                                                // (the other slot may still be receiving the rows of the run before)
     c.nrows = (c.nh && !h->best_only) ? c.h_c[C_ROWS] : 0u; c.nsegs = c.h_c[C_SEGS]; c.nbest = c.h_c[C_BEST];
     // the abundance counts of the range: its rows are final and none of its pools overflowed - a range that did has returned above
@@ -905,8 +969,9 @@ static int range_end(mc_handle *h, McCtx &c)
     h->stats.seed_exact_asks += (int64_t)c.h_stats[S_EXACT]; h->stats.seed_wild_asks += (int64_t)c.h_stats[S_WILD]; h->stats.seed_pair_asks += (int64_t)c.h_stats[S_PAIRS]; h->stats.seed_probes += (int64_t)c.h_stats[S_PROBES];
     h->stats.gap_tasks += c.ngaps - c.gpad; h->stats.hsps += c.nh_all; h->stats.rows += c.nrows; h->stats.reads_with_rows += c.nsegs;
     // kernel times: HIP events around the stages
-    h->stats.ms_translate += ev_ms(c.ev[0], c.ev[1]); h->stats.ms_seed += ev_ms(c.ev[1], c.ev[2]); h->stats.ms_eval += ev_ms(c.ev[2], c.ev[3]);
-    h->stats.ms_gapped += ev_ms(c.ev[3], c.ev[4]); h->stats.ms_sort += ev_ms(c.ev[4], c.ev[5]); h->stats.ms_finish += ev_ms(c.ev[5], c.ev[6]); h->stats.ms_total += ev_ms(c.ev[0], c.ev[6]);
+    const float ms_tr = (c.own_a0 ? ev_ms(c.ev[0], c.ev[1]) : 0.0f) + (c.ahead_from >= 0 ? ev_ms(h->ahead_ev[c.ahead_from][0], h->ahead_ev[c.ahead_from][1]) : 0.0f);   // (the kernel's own interval, wherever it ran)
+    h->stats.ms_translate += ms_tr; h->stats.ms_seed += ev_ms(c.ev[1], c.ev[2]); h->stats.ms_eval += ev_ms(c.ev[2], c.ev[3]);
+    h->stats.ms_gapped += ev_ms(c.ev[3], c.ev[4]); h->stats.ms_sort += ev_ms(c.ev[4], c.ev[5]); h->stats.ms_finish += ev_ms(c.ev[5], c.ev[6]); h->stats.ms_total += ms_tr + ev_ms(c.ev[1], c.ev[6]);
     h->stats.classified = (int64_t)c.nbest;
     return 0;
 }
@@ -935,8 +1000,13 @@ static int run_range_once(mc_handle *h, int64_t first, int64_t count, int64_t fi
 // end(i), begin(i + 1), results of i, end(i + 1), ... keeps the device busy while the host works on the results.  One range at a
 // time is on the device: a second mc_range_begin() before mc_range_end() is refused.  A range that overflows a pool comes back with
 // -2 from mc_range_end: it is no longer in flight; run it with mc_run_range (which splits it).
-// (Round 4 also measured the TAIL of a range - ordering, finishing - running beside the front of the next, on ordinary streams, on
-// streams of their own priority and on streams with CU masks: it does not pay)
+// mc_range_end() also LOOKS AHEAD: behind the range's gapped stage - the last reader of d_frames - it issues the translation of the range
+// it expects next (the one that follows contiguously in the resident set: mc_ahead_predict; run_stream and run_pieces name theirs) on
+// a stream of its own, beside the ordering and finishing kernels; an mc_range_begin() of that range (or of a prefix of it, or of a
+// longer one, which translates the rest on top) starts with the seed kernel, any other waits for the lookahead's kernel and translates
+// itself (range_begin, mc_ahead.h).  mc_run_range() issues none.  2.8 % of a step: DESIGN.md 5.5, where the reason it is not more stands.
+// (Round 4 also measured the whole TAIL of a range - ordering, finishing - running beside the whole front of the next, on ordinary
+// streams, on streams of their own priority and on streams with CU masks: it does not pay)
 extern "C" int mc_range_begin(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id)
 {
     if (range_check(h, first, count)) return -1;
@@ -948,13 +1018,23 @@ extern "C" int mc_range_begin(mc_handle *h, int64_t first, int64_t count, int64_
     return 0;
 }
 
+// The end of the range in flight, with a lookahead for the range the caller will begin next (count reads from first of the resident
+// set as it is NOW; count 0: none), or - predict - for the range that follows the running one contiguously in its set.
+static int range_end_next(mc_handle *h, int64_t first, int64_t count, bool predict)
+{
+    if (predict) count = mc_ahead_predict(h->ctx.first, h->ctx.n, h->nreads, &first);
+    return range_end(h, h->ctx, first, count);
+}
+
+extern "C" int64_t mc_ranges_translated_ahead(const mc_handle *h) { return h ? h->ahead_used : 0; }
+
 extern "C" int mc_range_end(mc_handle *h)
 {
     if (!h) { g_err = "null handle"; return -1; }
     if (h->pipe_nout == 0) { g_err = "mc_range_end: no range in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     h->pipe_nout = 0;
-    return range_end(h, h->ctx);
+    return range_end_next(h, 0, 0, true);
 }
 
 extern "C" int mc_ranges_in_flight(const mc_handle *h) { return h ? h->pipe_nout : 0; }
@@ -973,6 +1053,7 @@ extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap
     if (!h || !h->run_set || what < 0 || what > 5) { g_err = "mc_debug_stage: bad argument"; return -1; }
     if (h->pipe_nout) { g_err = "mc_debug_stage: ranges are in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
+    ahead_drop(h);
     const McCtx &c = h->ctx;
     if (what == 4) {
         if (!c.h_c) { g_err = "mc_debug_stage: no range has run"; return -1; }
@@ -1001,6 +1082,7 @@ extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap
 extern "C" int mc_set_counting(mc_handle *h, int on)
 {
     if (!h) { g_err = "null handle"; return -1; }
+    ahead_drop(h);
     h->count_traffic = on != 0;
     return 0;
 }
@@ -1025,6 +1107,7 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
 {
     HIPCK(hipSetDevice(h->device));
     if (h->pipe_nout) { g_err = "ranges begun with mc_range_begin() are still in flight"; return -1; }
+    ahead_drop(h);                                                  // (a lookahead of the caller's ranges: the pools may be replaced, and the resident set is another from here on)
     const int64_t BMAX = MC_STREAM_BATCH, B = stream_batch(), L = h->read_len;
     double t0 = mc_now();
     // The largest batch of this run: a quarter of the reads the caller expects (a power of two between 256 k and 2 M; 2 M when it
@@ -1080,10 +1163,15 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
     bool pending = false;
     auto collect = [&]() { if (pending) { pending = false; R.take(h); } };
     auto release = [&](int k) { std::unique_lock<std::mutex> lk(mu); slot[k].state = 0; cv.notify_all(); };
-    // batch `k` is in flight: its range ends (a pool overflow is answered by mc_run_range: smaller ranges); its results are pending
-    auto end_batch = [&](int k) -> int {
-        int r = mc_range_end(h);
-        if (r == -2) { h->reads_dev = slot[k].dev; h->nreads = slot[k].n; r = mc_run_range(h, 0, slot[k].n, first_read_id + slot[k].first); }
+    auto reads_at = [&](int k) { reads_change(h); h->reads_dev = slot[k].dev; h->nreads = slot[k].n; };
+    // batch `k` is in flight: its range ends (a pool overflow is answered by mc_run_range: smaller ranges); its results are pending.
+    // next >= 0: batch `next` is ready and is begun behind this one - the resident set is ITS slot already (the running range took its
+    // reads' address at range_begin), and its translation is issued ahead.
+    auto end_batch = [&](int k, int next) -> int {
+        if (next >= 0) reads_at(next);
+        h->pipe_nout = 0;                                            // (mc_range_end, told the next range)
+        int r = range_end_next(h, 0, next >= 0 ? slot[next].n : 0, false);
+        if (r == -2) { reads_at(k); r = mc_run_range(h, 0, slot[k].n, first_read_id + slot[k].first); if (next >= 0) reads_at(next); }
         if (r) return r;
         pending = true;
         release(k);                                                  // (the reads of the batch are no longer needed: the uploader may fill the slot)
@@ -1094,21 +1182,23 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
         {   // the next batch is not there yet (the source is the slower side): nothing to overlap with - finish the range in flight now
             bool ready;
             { std::unique_lock<std::mutex> lk(mu); ready = slot[k].state != 0; }
-            if (!ready && flying >= 0) { if ((rc = end_batch(flying)) != 0) break; flying = -1; collect(); }
+            if (!ready && flying >= 0) { if ((rc = end_batch(flying, -1)) != 0) break; flying = -1; collect(); }
         }
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return slot[k].state != 0; }); }
         if (slot[k].state == 2) { if (slot[k].rc < 0) { rc = (int)slot[k].rc; if (!up_err.empty()) g_err = up_err; } break; }
-        if (flying >= 0) { if ((rc = end_batch(flying)) != 0) break; flying = -1; }
-        h->reads_dev = slot[k].dev; h->nreads = slot[k].n;
+        if (flying >= 0) { if ((rc = end_batch(flying, k)) != 0) break; flying = -1; }
+        else reads_at(k);
         if ((rc = mc_range_begin(h, 0, slot[k].n, first_read_id + slot[k].first)) != 0) break;
         flying = k;
         collect();                                                   // the batch before, while the front of this one runs
     }
-    if (rc == 0 && flying >= 0) { rc = end_batch(flying); flying = -1; }
+    if (rc == 0 && flying >= 0) { rc = end_batch(flying, -1); flying = -1; }
     if (rc == 0) collect();
-    if (h->pipe_nout) (void)mc_range_end(h);                         // (after an error: nothing stays in flight)
+    if (h->pipe_nout) { h->pipe_nout = 0; (void)range_end(h, h->ctx); }   // (after an error: nothing stays in flight)
+    ahead_drop(h);                                                   // (nor a lookahead that reads a slot: the uploader may be filling it, and the slots outlive this call only as memory)
     { std::unique_lock<std::mutex> lk(mu); abort_up = true; cv.notify_all(); }
     uploader.join();
+    reads_change(h);
     h->reads_dev = saved_reads; h->nreads = saved_n;
     if (rc) return rc;
     h->res_rows = R.rows.data(); h->n_res_rows = (int64_t)R.rows.size(); h->best.swap(R.best); h->best_from = nullptr; h->stats = R.tot;
@@ -1200,7 +1290,7 @@ struct McModeGuard {
 // where use() has replaced them - however the borrower returns.
 struct McLenBorrow {
     mc_handle *h; int read_len, FP; const uint8_t *reads_dev; int64_t nreads; bool tables = false, pars = false, open = true;
-    explicit McLenBorrow(mc_handle *h_) : h(h_), read_len(h_->read_len), FP(h_->FP), reads_dev(h_->reads_dev), nreads(h_->nreads) {}
+    explicit McLenBorrow(mc_handle *h_) : h(h_), read_len(h_->read_len), FP(h_->FP), reads_dev(h_->reads_dev), nreads(h_->nreads) { ahead_drop(h); }
     McLenBorrow(const McLenBorrow &) = delete;
     ~McLenBorrow() { (void)close(-1); }
     void set_len(int L) { h->read_len = L; h->FP = ((L / 3 + 2) + 3) & ~3; }
@@ -1219,6 +1309,7 @@ struct McLenBorrow {
         auto it = h->vl_tables.find(L);
         if (it == h->vl_tables.end()) { it = h->vl_tables.emplace(L, McTables()).first; mc_fill_tables(it->second, h->H, L, h->vl_thr); }
         tables = true;
+        tables_change(h);
         HIPCK(hipMemcpy(h->d_T, &it->second, sizeof(McTables), hipMemcpyHostToDevice));
         if (P) { pars = true; HIPCK(hipMemcpy(h->d_P, P, sizeof(McClassPars), hipMemcpyHostToDevice)); }
         set_len(L);
@@ -1229,6 +1320,7 @@ struct McLenBorrow {
     {
         if (!open) return rc;
         open = false;
+        tables_change(h); reads_change(h);
         h->read_len = read_len; h->FP = FP; h->reads_dev = reads_dev; h->nreads = nreads;
         hipError_t e = tables ? run_tables_up(h) : hipSuccess;
         if (e == hipSuccess && pars) e = hipMemcpy(h->d_P, &h->hP, sizeof(McClassPars), hipMemcpyHostToDevice);
@@ -1243,21 +1335,31 @@ struct McLenBorrow {
 // while its length is still the handle's.
 template <class BlockOf> static int run_pieces(mc_handle *h, McLenBorrow &len, const std::vector<McPiece> &pieces, BlockOf block_of, const McClassPars *pars, McResults &R)
 {
-    auto begin = [&](const McPiece &q) -> int {
-        if (len.use(q.L, pars ? pars + q.tag : nullptr)) return -1;
-        h->reads_dev = block_of(q); h->nreads = q.bin_n;
+    // (a piece of the same bin as the one before it: same length, tables, parameters and reads - the handle stays as it is, and the
+    // piece's translation could be issued ahead)
+    auto same_bin = [](const McPiece &a, const McPiece &b) { return a.tag == b.tag && a.L == b.L && a.bin_first == b.bin_first && a.bin_n == b.bin_n; };
+    auto begin = [&](const McPiece &q, const McPiece *before) -> int {
+        if (!before || !same_bin(*before, q)) {
+            if (len.use(q.L, pars ? pars + q.tag : nullptr)) return -1;
+            reads_change(h);
+            h->reads_dev = block_of(q); h->nreads = q.bin_n;
+        }
         return mc_range_begin(h, q.first, q.n, q.bin_first + q.first);
     };
-    int rc = pieces.empty() ? 0 : begin(pieces[0]);
+    int rc = pieces.empty() ? 0 : begin(pieces[0], nullptr);
     for (size_t j = 0; rc == 0 && j < pieces.size(); j++) {
         const McPiece &q = pieces[j];
-        rc = mc_range_end(h);
+        const McPiece *nx = j + 1 < pieces.size() ? &pieces[j + 1] : nullptr;
+        const bool ahead = nx && same_bin(q, *nx);
+        h->pipe_nout = 0;                                            // (mc_range_end, told the next range: the next piece where it is of this bin, else none)
+        rc = range_end_next(h, ahead ? nx->first : 0, ahead ? nx->n : 0, false);
         if (rc == -2) rc = mc_run_range(h, q.first, q.n, q.bin_first + q.first);
         if (rc) break;
-        if (j + 1 < pieces.size() && (rc = begin(pieces[j + 1])) != 0) break;
+        if (nx && (rc = begin(*nx, &q)) != 0) break;
         R.take(h, q.tag);
     }
-    if (h->pipe_nout) (void)mc_range_end(h);                         // (after an error: nothing stays in flight)
+    if (h->pipe_nout) { h->pipe_nout = 0; (void)range_end(h, h->ctx); }   // (after an error: nothing stays in flight)
+    ahead_drop(h);                                                   // (the blocks the pieces were read from are the caller's)
     return rc;
 }
 
@@ -2311,6 +2413,7 @@ static int train_range(mc_handle *h, int64_t first, int64_t count, int64_t first
 template <class S> static int simulate_resident(mc_handle *h, const S *s, uint64_t key, int64_t at, int64_t cnt, const McEvents &ev)
 {
     hipStream_t st = h->ctx.stream;
+    reads_change(h);
     if (hipEventRecord(ev[0], st) != hipSuccess || launch_simulate(s, h->read_len, key, at, cnt, h->d_reads, st) || hipEventRecord(ev[1], st) != hipSuccess) return -1;
     h->reads_dev = h->d_reads; h->nreads = cnt;
     return 0;
@@ -2324,6 +2427,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     if (g->lib.paired_end && (nreads & 1)) { g_err = "a paired-end library has an even number of reads (" + std::to_string(nreads) + " given)"; return -1; }
     if (g->device != h->device) { g_err = "mc_train_library: the genome lies on another device than the handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_train_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
+    ahead_drop(h);                                                  // (the resident reads are about to be simulated over)
     if (h->abund) { g_err = "mc_train_library: refused while abundance counting is on (mc_set_abundance)"; return -1; }
     McGridPars G; std::vector<int> order;
     if (grid_pars(h, aln_covs, n_cov, max_pids, n_pid, min_scores, n_score, G, order)) return -1;
@@ -2382,12 +2486,14 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
             // a plain loop, not run_pieces: the grid reads a piece's rows where they lie, before the next front may overwrite them
             for (const McPiece &q : P.v) {
                 if ((rc = len.use(q.L)) != 0) break;
+                reads_change(h);
                 h->reads_dev = d_sorted + boff[(size_t)q.L]; h->nreads = q.bin_n;
                 if ((rc = train_range(h, q.first, q.n, at + q.bin_first + q.first, G, d_bins, nbins, ev[2], ev[3], tot)) != 0) break;
             }
             (void)hipStreamSynchronize(st);                          // (the bucket buffers are freed at the end of the range)
         }
         rc = len.close(rc);                                          // the run's own length and tables back
+        reads_change(h);
         h->reads_dev = nullptr; h->nreads = 0;                       // (the buckets the handle read from are gone)
     }
     h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr;
@@ -2480,6 +2586,7 @@ extern "C" int mc_community_library(mc_handle *h, mc_community *c, int64_t nread
     if (c->lib.paired_end && (nreads & 1)) { g_err = "a paired-end library has an even number of reads (" + std::to_string(nreads) + " given)"; return -1; }
     if (c->device != h->device) { g_err = "mc_community_library: the community lies on another device than the handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_community_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
+    ahead_drop(h);                                                  // (the resident reads are about to be simulated over)
     if (h->abund) { g_err = "mc_community_library: refused while abundance counting is on (it runs best hits only; mc_set_abundance)"; return -1; }
     HIPCK(hipSetDevice(h->device));
     if (source_for_len(c, h->read_len)) return -1;
