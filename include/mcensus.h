@@ -518,6 +518,40 @@ int mc_coverage_depth(mc_handle *h, uint32_t *depth /* [n] */, int64_t n);
  * the counting kernel: their time is part of mc_abundance_ms() (README "Normalization": the device cost of "reads mapped to gene"). */
 float mc_coverage_ms(const mc_handle *h);
 
+/* ---- the genes that tie for a read's best hit, beside the counts ------------------------------------------------------------------
+ * "Reads mapped to gene" (README "Normalization") gives a read to the FIRST row of the highest bit score, and among near-identical
+ * sequences - alleles, variants, families - most reads tie: the first of them gets every count, its siblings none.  csrc/k_ties.h
+ * states the rule: T is the highest bit score among a read's passing rows; the read's tied set is the DISTINCT subjects that have a
+ * passing row with bits == T (exact double equality; any row order; a subject that ties twice is in it once), k its size.  A read
+ * that mc_set_abundance does not assign adds nothing.  Per subject: candidates = reads whose tied set holds it, unique = reads whose
+ * tied set is it alone, share = in units of 2^-32, floor(2^32 / k) per read to every tied subject and the remainder to the first
+ * tied one - the subject the read is assigned to - so that the shares sum to assigned x 2^32.  Scalars: ambiguous = reads with
+ * k > 1; with a group map, group_ambiguous = reads whose tied set spans two groups and group_unique[g] = reads whose whole tied set
+ * lies in group g.  With coverage on, the first tied row of EVERY tied subject marks its span in a second depth (the "any" depth).
+ * All are 64-bit integers: exact, whatever the batches, ranges and launch geometry.
+ * mc_set_ties(on != 0) takes the map group_of[nseq] with values in 0 .. ngroups - 1 (or NULL and 0: no groups), and zeroes the tie
+ * counters AND the abundance counters and depth of the README's "Normalization" numerators: all describe the same reads.  From then
+ * on every range that adds to the counts runs one more kernel behind the counting kernel, on the same rows where they lie (also with
+ * mc_set_keep_rows(h, 0)); a range that overflowed a pool adds nothing, its pieces once.  The any-depth exists exactly while ties and
+ * coverage are both on, whichever was set second.  on == 0 frees everything and restores the path without it exactly.
+ * mc_set_abundance(h, 0, ...) also turns ties off; mc_abundance_reset() also zeroes the tie counters, the any-depth and mc_ties_ms().
+ * Refused, with a message naming the cause: abundance counting off (README "Normalization": mc_set_abundance first), a range in flight,
+ * a group_of entry outside 0 .. ngroups - 1, ngroups < 0, ngroups > 0 with a NULL map.
+ * mc_search_files_multi keeps one set of counters per handle: every counter adds across handles; covered_any and max_depth_any do not. */
+int mc_set_ties(mc_handle *h, int on, const int32_t *group_of /* [nseq] or NULL */, int32_t ngroups);
+/* The tie counters as they stand, beside the README's "Normalization" numerators of mc_abundance_read: per subject candidates, unique
+ * and share (arrays of mc_marker_count() values), group_unique per group (zero values without a map), and the two scalars
+ * (group_ambiguous is 0 without a map).  Any pointer may be NULL.  Refused while ties are off. */
+int mc_ties_read(mc_handle *h, int64_t *candidates /* [nseq] */, int64_t *unique /* [nseq] */, uint64_t *share /* [nseq] */, int64_t *group_unique /* [ngroups] */,
+                 int64_t *ambiguous, int64_t *group_ambiguous);
+/* covered_any[s], spanned_any[s] and max_depth_any[s] per subject s: mc_coverage_read's figures of the any-depth - the breadth a gene
+ * of the README's "Normalization" table would have if every tied read were its own.  Any pointer may be NULL; one scan kernel per call
+ * (its time is part of mc_coverage_ms()).  Refused while coverage or ties is off. */
+int mc_ties_coverage_read(mc_handle *h, int64_t *covered_any /* [nseq] */, int64_t *spanned_any /* [nseq] */, int64_t *max_depth_any /* [nseq] */);
+/* Milliseconds the tie kernels took since the last reset (HIP events; one kernel per completed range) - beside mc_abundance_ms(), the
+ * device cost of the README's "reads mapped to gene". */
+float mc_ties_ms(const mc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -226,6 +226,11 @@ def load_library():
     lib.mc_coverage_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.mc_coverage_ms.restype = C.c_float
     lib.mc_coverage_ms.argtypes = [C.c_void_p]
+    lib.mc_set_ties.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32]
+    lib.mc_ties_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.mc_ties_coverage_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mc_ties_ms.restype = C.c_float
+    lib.mc_ties_ms.argtypes = [C.c_void_p]
     lib.mc_debug_live.restype = None
     lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
@@ -243,7 +248,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_community_times",
                     "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride",
                     "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms",
-                    "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms", "mc_debug_live"]
+                    "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms",
+                    "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms", "mc_debug_live"]
 
 
 class DupSet:
@@ -935,6 +941,44 @@ class Engine:
     def coverage_ms(self):
         """milliseconds the coverage scan kernels took since the last reset (HIP events); the marks are part of abundance_ms()"""
         return float(self.lib.mc_coverage_ms(self.h))
+
+    def set_ties(self, on=True, group_of=None, ngroups=0):
+        """The tie accounting beside the counts (mc_set_ties; csrc/k_ties.h states the rule): from now on every read that set_abundance
+        counts also adds to candidates, unique and share of the DISTINCT subjects that tie for its highest bit score.  group_of: one
+        group number in 0 .. ngroups - 1 per subject, or None.  on=True zeroes the tie counters AND the abundance counters and depth;
+        on=False frees them.  Refused while set_abundance is off."""
+        if on and group_of is not None:
+            g = np.ascontiguousarray(group_of, dtype=np.int32)
+            if g.shape != (len(self.names),):
+                raise ValueError("group_of holds %d values, the database %d sequences" % (g.size, len(self.names)))
+            rc = self.lib.mc_set_ties(self.h, 1, g.ctypes.data_as(C.c_void_p), int(ngroups))
+        else:
+            rc = self.lib.mc_set_ties(self.h, 1 if on else 0, None, int(ngroups) if on else 0)
+        self._check(rc, "mc_set_ties")
+        self._ties_ngroups = int(ngroups) if on else 0
+
+    def ties(self):
+        """The tie counters as they stand (mc_ties_read): {"candidates", "unique": int64[nseq], "share": uint64[nseq] in units of 2^-32,
+        "group_unique": int64[ngroups], "ambiguous", "group_ambiguous": int}."""
+        n = len(self.names)
+        out = {"candidates": np.zeros(n, np.int64), "unique": np.zeros(n, np.int64), "share": np.zeros(n, np.uint64),
+               "group_unique": np.zeros(getattr(self, "_ties_ngroups", 0), np.int64)}
+        amb, gamb = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.mc_ties_read(self.h, *(out[k].ctypes.data_as(C.c_void_p) for k in ("candidates", "unique", "share", "group_unique")), C.byref(amb), C.byref(gamb)),
+                    "mc_ties_read")
+        out["ambiguous"], out["group_ambiguous"] = int(amb.value), int(gamb.value)
+        return out
+
+    def ties_coverage(self):
+        """The per-gene figures of the any-depth (mc_ties_coverage_read): {"covered_any", "spanned_any", "max_depth_any"}, int64[nseq] each."""
+        n = len(self.names)
+        out = {k: np.zeros(n, np.int64) for k in ("covered_any", "spanned_any", "max_depth_any")}
+        self._check(self.lib.mc_ties_coverage_read(self.h, *(out[k].ctypes.data_as(C.c_void_p) for k in ("covered_any", "spanned_any", "max_depth_any"))), "mc_ties_coverage_read")
+        return out
+
+    def ties_ms(self):
+        """milliseconds the tie kernels took since the last reset (HIP events)"""
+        return float(self.lib.mc_ties_ms(self.h))
 
     def upload(self, reads):
         reads = np.ascontiguousarray(reads, dtype=np.uint8)

@@ -20,7 +20,17 @@ row covers the subject residues sstart .. send of RAPsearch2's m8 - 0-based and 
     mean_depth = (sum of the depths) / length_aa            max_depth = the largest depth
 
 min_breadth F adds the column detected (reads > 0 and covered_aa >= F x length_aa); depth_out writes the depth itself, run-length
-encoded (gene, start, end, depth: 0-based start, exclusive end)."""
+encoded (gene, start, end, depth: 0-based start, exclusive end).
+
+The counts give a read to ONE gene: the first row of its highest bit score.  Among near-identical genes - alleles, variants, families -
+most reads tie, and the first of the tied genes gets them all.  With ties (Engine.set_ties; csrc/k_ties.h states the rule) the table
+also says, per gene, how many of its reads were its alone, how many it tied for, and what an even split gives it:
+
+    unique_reads    = reads whose highest bit score only this gene has      candidate_reads = reads that have it on this gene
+    shared_reads    = the sum over those reads of 1 / k, k the genes tied   rpkg_shared     = the rpkg formula on shared_reads
+
+and with coverage covered_any_aa / breadth_any (the residues that a tied read covers, whichever gene it was given to) and, with
+min_breadth, detected_any (candidate_reads > 0 and covered_any_aa >= F x length_aa).  The existing columns keep their values."""
 import gzip
 import math
 import os
@@ -36,6 +46,10 @@ COLUMNS = ("gene", "length_aa", "reads", "aligned_aa", "rpkg")
 GROUP_COLUMNS = ("group", "genes", "reads", "rpkg")
 COVERAGE_COLUMNS = ("covered_aa", "breadth", "mean_depth", "max_depth")     # behind COLUMNS with coverage; "detected" behind them with min_breadth
 DEPTH_COLUMNS = ("gene", "start", "end", "depth")
+TIES_COLUMNS = ("unique_reads", "candidate_reads", "shared_reads", "rpkg_shared")    # behind all of them with ties ...
+TIES_COVERAGE_COLUMNS = ("covered_any_aa", "breadth_any")                            # ... these behind them with coverage, "detected_any" last with min_breadth
+GROUP_TIES_COLUMNS = ("unique_reads", "shared_reads", "rpkg_shared")                 # behind the groups table's columns; "genes_detected_any" last with min_breadth
+SHARE_ONE = 4294967296.0                                                             # share[] counts in units of 2^-32 (csrc/k_ties.h)
 
 
 class AbundanceError(Exception):
@@ -149,6 +163,35 @@ def group_table(names, reads, rpkgs, group_of, detected=None):
     return [(g,) + tuple(acc[g][:4 if detected is not None else 3]) for g in order]
 
 
+def group_ids(names, group_of):
+    """(ids, groups): every gene's group number and the groups' names, numbered in the order group_table lists them - the map that
+    goes to the device (Engine.set_ties)."""
+    index, ids = {}, np.zeros(len(names), np.int32)
+    for k, nm in enumerate(names):
+        ids[k] = index.setdefault(group_of.get(nm, nm), len(index))
+    return ids, list(index)
+
+
+def shared_reads(share):
+    """share[] of the device (units of 2^-32) as reads: np.float64(share) / 4294967296.0"""
+    return np.asarray(share, dtype=np.uint64).astype(np.float64) / SHARE_ONE
+
+
+def group_ties_table(ids, ngroups, group_unique, share, rpkg_shared, detected_any=None):
+    """[(unique_reads, shared_reads, rpkg_shared)] per group, in group_ids' numbering.  unique_reads is the device's group_unique - the
+    reads whose whole tied set lies in the group - and NOT the sum of the members' unique_reads; shared_reads is the members' shares
+    added as integers and then divided by 2^32; rpkg_shared the sum of the members' values, added in FASTA order.  With detected_any every
+    tuple ends with the group's genes_detected_any."""
+    acc = [[0, 0.0, 0] for _ in range(ngroups)]
+    for k, g in enumerate(np.asarray(ids).tolist()):
+        a = acc[g]
+        a[0] += int(share[k])
+        a[1] += float(rpkg_shared[k])
+        if detected_any is not None:
+            a[2] += int(detected_any[k])
+    return [(int(group_unique[g]), float(np.float64(np.uint64(a[0])) / SHARE_ONE), a[1]) + ((a[2],) if detected_any is not None else ()) for g, a in enumerate(acc)]
+
+
 def coverage_columns(length_aa, covered, spanned):
     """(breadth, mean_depth) in float64: covered_aa / length_aa and spanned / length_aa."""
     ln = np.asarray(length_aa, dtype=np.float64)
@@ -214,6 +257,10 @@ def header_lines(args, table):
         h.append(("coverage", "on"))
     if table.get("detected") is not None:
         h += [("min_breadth", repr(float(table["min_breadth"]))), ("genes_detected", int(np.sum(table["detected"])))]
+    if table.get("unique_reads") is not None:
+        h += [("ties", "on"), ("reads_ambiguous", table["reads_ambiguous"])]
+        if table.get("reads_ambiguous_across_groups") is not None:
+            h.append(("reads_ambiguous_across_groups", table["reads_ambiguous_across_groups"]))
     return ["# %s:\t%s\n" % kv for kv in h]
 
 
@@ -221,13 +268,21 @@ def write_table(path, args, table):
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
         cov, det = table.get("covered_aa") is not None, table.get("detected") is not None
-        out.write("\t".join(COLUMNS + (COVERAGE_COLUMNS if cov else ()) + (("detected",) if det else ())) + "\n")
+        ties, tcov, tdet = table.get("unique_reads") is not None, table.get("covered_any_aa") is not None, table.get("detected_any") is not None
+        out.write("\t".join(COLUMNS + (COVERAGE_COLUMNS if cov else ()) + (("detected",) if det else ()) + (TIES_COLUMNS if ties else ())
+                            + (TIES_COVERAGE_COLUMNS if tcov else ()) + (("detected_any",) if tdet else ())) + "\n")
         for k, (nm, ln, r, a, v) in enumerate(zip(table["gene"], table["length_aa"], table["reads"], table["aligned_aa"], table["rpkg"])):
             line = "%s\t%d\t%d\t%d\t%s" % (nm, ln, r, a, repr(float(v)))
             if cov:
                 line += "\t%d\t%s\t%s\t%d" % (table["covered_aa"][k], repr(float(table["breadth"][k])), repr(float(table["mean_depth"][k])), table["max_depth"][k])
             if det:
                 line += "\t%d" % table["detected"][k]
+            if ties:
+                line += "\t%d\t%d\t%s\t%s" % (table["unique_reads"][k], table["candidate_reads"][k], repr(float(table["shared_reads"][k])), repr(float(table["rpkg_shared"][k])))
+            if tcov:
+                line += "\t%d\t%s" % (table["covered_any_aa"][k], repr(float(table["breadth_any"][k])))
+            if tdet:
+                line += "\t%d" % table["detected_any"][k]
             out.write(line + "\n")
 
 
@@ -236,10 +291,15 @@ def write_groups(path, args, table):
         out.writelines(header_lines(args, table))
         out.write("# groups:\t%s\n" % args["groups"])
         det = table.get("detected") is not None
-        out.write("\t".join(GROUP_COLUMNS + (("genes_detected",) if det else ())) + "\n")
-        for row in table["groups"]:
+        gt = table.get("groups_ties")
+        tdet = gt is not None and table.get("detected_any") is not None
+        out.write("\t".join(GROUP_COLUMNS + (("genes_detected",) if det else ()) + (GROUP_TIES_COLUMNS if gt is not None else ()) + (("genes_detected_any",) if tdet else ())) + "\n")
+        for k, row in enumerate(table["groups"]):
             g, n, r, v = row[:4]
-            out.write("%s\t%d\t%d\t%s%s\n" % (g, n, r, repr(float(v)), "\t%d" % row[4] if det else ""))
+            more = ""
+            if gt is not None:
+                more = "\t%d\t%s\t%s" % (gt[k][0], repr(float(gt[k][1])), repr(float(gt[k][2]))) + ("\t%d" % gt[k][3] if tdet else "")
+            out.write("%s\t%d\t%d\t%s%s%s\n" % (g, n, r, repr(float(v)), "\t%d" % row[4] if det else "", more))
 
 
 def read_table(path):
@@ -268,7 +328,7 @@ def check_request(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.get("distributed"):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
-                         ("coverage", False), ("min_breadth", None), ("depth_out", None)):
+                         ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False)):
         args.setdefault(key, default)
     if args["min_breadth"] is not None:
         f = args["min_breadth"]
@@ -287,6 +347,9 @@ def check_request(args):
             raise AbundanceError("--depth-out %s is the path of the gene table itself: two files" % (args["depth_out"],))
         if args.get("outfile") and args["groups"] and where == os.path.abspath(args["outfile"] + ".groups.tsv"):
             raise AbundanceError("--depth-out %s is the path of the groups table (<outfile>.groups.tsv): two files" % (args["depth_out"],))
+    if not isinstance(args["ties"], (bool, int)) or args["ties"] not in (0, 1):
+        raise AbundanceError("ties %r is not a switch: True or False" % (args["ties"],))
+    args["ties"] = bool(args["ties"])
     args["coverage"] = bool(args["coverage"]) or args["min_breadth"] is not None or args["depth_out"] is not None
     if args["ags"] is not None and args["ags_report"] is not None:
         raise AbundanceError("--ags %s and --ags-report %s cannot be combined: one AGS" % (args["ags"], args["ags_report"]))
@@ -313,7 +376,8 @@ def check_request(args):
 def run_abundance(args):
     """args: run_pipeline's keys (seqfiles, nreads, read_length, min_quality, mean_quality, filter_dups, max_unknown, device, model_dir,
     verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and - all off by default - coverage, min_breadth
-    (implies coverage), depth_out (a path; implies coverage).  Writes args['outfile'] (and
+    (implies coverage), depth_out (a path; implies coverage), ties (the genes that tie for a read's best hit: unique, candidate and
+    shared reads beside the counts; sets args['ties_ms']).  Writes args['outfile'] (and
     <outfile>.groups.tsv with groups) when it is set; returns (table, args) - table: the columns as arrays (gene, length_aa, reads,
     aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
     names, seqs, group_of, ags, source = check_request(args)
@@ -340,6 +404,13 @@ def run_abundance(args):
         eng.set_abundance(True, min_ident=args["min_ident"], min_aln=args["min_aln"], min_bits=args["min_bits"])
         if args["coverage"]:
             eng.set_coverage(True)
+        gids = None
+        if args["ties"]:
+            if group_of is not None:
+                gids, gnames = group_ids(names, group_of)
+                eng.set_ties(True, gids, len(gnames))
+            else:
+                eng.set_ties(True)
         try:
             eng.search_files(rd, keep_rows=False)
         except _native.ReferenceError_ as e:
@@ -348,8 +419,12 @@ def run_abundance(args):
         cov = eng.coverage() if args["coverage"] else None
         depth = eng.coverage_depth() if args["depth_out"] is not None else None
         args["abundance_ms"], args["search_ms"] = eng.abundance_ms(), eng.stats()["ms_total"]
+        ti = eng.ties() if args["ties"] else None
+        tcov = eng.ties_coverage() if args["ties"] and args["coverage"] else None
         if args["coverage"]:
             args["coverage_ms"] = eng.coverage_ms()
+        if args["ties"]:
+            args["ties_ms"] = eng.ties_ms()
         st = rd.stats()
     finally:
         rd.close()
@@ -377,6 +452,18 @@ def run_abundance(args):
         if depth is not None:
             table["depth"] = depth
             write_depth(args["depth_out"], names, length_aa, depth)
+    if ti is not None:
+        sh = shared_reads(ti["share"])
+        table.update({"unique_reads": ti["unique"], "candidate_reads": ti["candidates"], "shared_reads": sh, "rpkg_shared": rpkg(sh, length_aa, ge), "share": ti["share"],
+                      "reads_ambiguous": ti["ambiguous"]})
+        if tcov is not None:
+            table.update({"covered_any_aa": tcov["covered_any"], "breadth_any": coverage_columns(length_aa, tcov["covered_any"], tcov["spanned_any"])[0]})
+            if args["min_breadth"] is not None:
+                table["detected_any"] = detect(ti["candidates"], tcov["covered_any"], length_aa, args["min_breadth"])
+        if group_of is not None:
+            table["reads_ambiguous_across_groups"] = ti["group_ambiguous"]
+            table["group_unique"] = ti["group_unique"]
+            table["groups_ties"] = group_ties_table(gids, len(gnames), ti["group_unique"], ti["share"], table["rpkg_shared"], table.get("detected_any"))
     if group_of is not None:
         table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of, table.get("detected"))
     if args.get("outfile"):

@@ -16,6 +16,7 @@
 //   k_wfit.h               the fit of the per-family weights, training step 5 (mc_fit_weights, mc_weights_mue)
 //   k_abundance.h          per-gene read counts for RPKG, summed over the rows of every completed range (mc_set_abundance)
 //   k_coverage.h           per-gene coverage breadth and depth beside them: marks in the counting kernel, a scan at read time (mc_set_coverage)
+//   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
 //   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
@@ -36,6 +37,7 @@
 #include "k_wfit.h"
 #include "k_abundance.h"
 #include "k_coverage.h"
+#include "k_ties.h"
 #include "mc_pieces.h"
 #include "mc_ahead.h"
 #include "mc_owned.h"
@@ -103,6 +105,11 @@ struct mc_handle {
     // scan kernels' time since the last reset and the two events around a scan
     bool cov = false; McDev<uint32_t> d_cov; McDev<unsigned long long> d_covout; float cov_ms = 0;
     McEvent ev_cov[2];
+    // mc_set_ties: the tie counters of k_ties.h in ONE buffer ((nseq + 1) x 2: candidates, unique of subject s, [nseq]: ambiguous,
+    // group_ambiguous; then nseq shares; then ngroups group_unique), the group map, the any-depth's difference array (it exists
+    // exactly while ties and coverage are both on), the kernels' time since the last reset and the event behind the kernel of a range
+    bool ties = false; int32_t ties_ngroups = 0; McDev<unsigned long long> d_ties; McDev<int32_t> d_tgroup; McDev<uint32_t> d_cov_any; float ties_ms = 0;
+    McEvent ev_ties;
     McPin<uint8_t> stage_pin[2]; McDev<uint8_t> stage_dev[2]; size_t stage_bytes = 0; McStream copy_stream;   // run_stream (stage_bytes: what all four hold, 0 until they do)
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -945,6 +952,12 @@ static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t nex
         if (nr && h->cov) k_abundance_cov<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund, h->d_off, h->d_cov);   // (the marks ride with the counts: k_coverage.h)
         else if (nr) k_abundance<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund);
         HIPCK(hipEventRecord(h->ev_abund[1], c.stream));
+        if (h->ties) {                                              // (behind the counting kernel, on the same final rows where they lie: k_ties.h)
+            const size_t ns = (size_t)h->H.nseq;
+            if (nr) k_ties<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)ns, h->d_ties, h->d_ties + 2 * (ns + 1), h->d_tgroup,
+                                                                                 h->d_tgroup ? h->d_ties + 3 * ns + 2 : nullptr, h->d_cov_any ? h->d_off.get() : nullptr, h->d_cov_any);
+            HIPCK(hipEventRecord(h->ev_ties, c.stream));
+        }
     }
     if ((size_t)c.nrows > h->pin_slot_cap[h->pin_cur] && !rows_stay(h)) {   // grow the pinned row buffer
         (void)hipStreamSynchronize(h->rows_stream);                  // (the copy of the run before writes into the other buffer: let it finish before anything is freed)
@@ -960,6 +973,7 @@ static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t nex
     if (c.nrows && !rows_stay(h)) { HIPCK(hipEventRecord(h->ev_rows, h->rows_stream)); h->rows_pending = true; h->rows_ever = true; }
     if ((rc = stage_wait(c)) != 0) return rc;
     if (abund) { h->abund_searched += c.n; h->abund_ms += ev_ms(h->ev_abund[0], h->ev_abund[1]); }
+    if (abund && h->ties) h->ties_ms += ev_ms(h->ev_abund[1], h->ev_ties);
     h->res_rows = rows_stay(h) ? nullptr : (const mc_row *)h->pin_slot[h->pin_cur]; h->n_res_rows = rows_stay(h) ? 0 : (int64_t)c.nrows;
     h->best_from = &c; h->best_count = c.nbest;                  // (mc_result_best_hits / whoever needs them: best_materialize)
 #ifdef MC_EXP_TIMING
@@ -1975,6 +1989,7 @@ extern "C" int mc_set_best_hits_only(mc_handle *h, int on)
 // ---- per-gene read counts for RPKG (the reference README, "Normalization"; csrc/k_abundance.h states the rule) ---------------------
 // The counters live in the handle and accumulate over every range that completes (range_end) until they are reset.
 static size_t cov_slots(const mc_handle *h) { return (size_t)h->H.nres + (size_t)h->H.nseq; }   // (every gene's residues and its sentinel)
+static size_t ties_slots(const mc_handle *h) { return 3 * (size_t)h->H.nseq + 2 + (size_t)h->ties_ngroups; }   // (k_ties.h, "Layout": the pair table, the shares, group_unique)
 static int abund_zero(mc_handle *h)
 {
     HIPCK(hipSetDevice(h->device));
@@ -1982,14 +1997,23 @@ static int abund_zero(mc_handle *h)
     h->abund_searched = 0; h->abund_ms = 0.f;
     if (h->cov) HIPCK(hipMemset(h->d_cov, 0, sizeof(uint32_t) * cov_slots(h)));   // (counts and depth describe the same reads)
     h->cov_ms = 0.f;
+    if (h->ties) HIPCK(hipMemset(h->d_ties, 0, sizeof(unsigned long long) * ties_slots(h)));   // (... and so do the tie counters)
+    if (h->d_cov_any) HIPCK(hipMemset(h->d_cov_any, 0, sizeof(uint32_t) * cov_slots(h)));
+    h->ties_ms = 0.f;
     return 0;
 }
 
 static void cov_off(mc_handle *h)
 {
-    h->d_cov.reset(); h->d_covout.reset();
+    h->d_cov.reset(); h->d_covout.reset(); h->d_cov_any.reset();
     for (auto &e : h->ev_cov) e.reset();
     h->cov = false; h->cov_ms = 0.f;
+}
+
+static void ties_off(mc_handle *h)
+{
+    h->d_ties.reset(); h->d_tgroup.reset(); h->d_cov_any.reset(); h->ev_ties.reset();
+    h->ties = false; h->ties_ngroups = 0; h->ties_ms = 0.f;
 }
 
 extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t min_aln, double min_bits, double max_loge)
@@ -2002,6 +2026,7 @@ extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t
         for (auto &e : h->ev_abund) e.reset();
         h->abund = false; h->abund_searched = 0; h->abund_ms = 0.f;
         cov_off(h);
+        ties_off(h);
         return 0;
     }
     if (min_ident < 0 || min_ident > 100) { g_err = "mc_set_abundance: min_ident " + std::to_string(min_ident) + " is not a percent from 0 to 100"; return -1; }
@@ -2051,17 +2076,19 @@ extern "C" int mc_set_coverage(mc_handle *h, int on)
     if (!h->d_cov && h->d_cov.alloc(cov_slots(h))) return -1;
     if (!h->d_covout && h->d_covout.alloc(3 * (size_t)h->H.nseq)) { cov_off(h); return -1; }
     for (auto &e : h->ev_cov) if (!e && e.create()) { cov_off(h); return -1; }
+    if (h->ties && !h->d_cov_any && h->d_cov_any.alloc(cov_slots(h))) { cov_off(h); return -1; }   // (the any-depth: while ties and coverage are both on, whichever was set second)
     h->cov = true;
     return abund_zero(h);
 }
 
 // the scan of the difference array as it stands, into d_covout and (when given) depth: device memory of nres values
-static int cov_scan(mc_handle *h, uint32_t *d_depth)
+static int cov_scan(mc_handle *h, uint32_t *d_depth, const unsigned long long *d_tab = nullptr, const uint32_t *d_diff = nullptr)
 {
+    if (!d_tab) { d_tab = h->d_abund; d_diff = h->d_cov; }          // (mc_ties_coverage_read hands in the tie table and the any-depth: the same scan)
     const int32_t nseq = (int32_t)h->H.nseq;
     if (d_depth) HIPCK(hipMemsetAsync(d_depth, 0, sizeof(uint32_t) * (size_t)h->H.nres, 0));
     HIPCK(hipEventRecord(h->ev_cov[0], 0));
-    k_coverage_scan<<<dim3(((unsigned)nseq + 3) / 4), dim3(256), 0, 0>>>(h->d_abund, h->d_off, h->d_cov, nseq, h->d_covout, d_depth);
+    k_coverage_scan<<<dim3(((unsigned)nseq + 3) / 4), dim3(256), 0, 0>>>(d_tab, h->d_off, d_diff, nseq, h->d_covout, d_depth);
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(h->ev_cov[1], 0));
     HIPCK(hipEventSynchronize(h->ev_cov[1]));
@@ -2100,6 +2127,71 @@ extern "C" int mc_coverage_depth(mc_handle *h, uint32_t *depth, int64_t n)
 }
 
 extern "C" float mc_coverage_ms(const mc_handle *h) { return h ? h->cov_ms : 0.0f; }
+
+// ---- the tie accounting beside the counts (csrc/k_ties.h states the rule and the layout) ----------------------------------------------
+extern "C" int mc_set_ties(mc_handle *h, int on, const int32_t *group_of, int32_t ngroups)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_ties: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (!on) { ties_off(h); return 0; }
+    if (!h->abund) { g_err = "mc_set_ties: abundance counting is off (mc_set_abundance) - the ties are those of the reads it counts"; return -1; }
+    if (ngroups < 0) { g_err = "mc_set_ties: ngroups " + std::to_string(ngroups) + " is negative"; return -1; }
+    if (ngroups > 0 && !group_of) { g_err = "mc_set_ties: " + std::to_string(ngroups) + " groups and a NULL group map"; return -1; }
+    const size_t nseq = (size_t)h->H.nseq;
+    if (ngroups == 0) group_of = nullptr;
+    for (size_t s = 0; group_of && s < nseq; s++)
+        if (group_of[s] < 0 || group_of[s] >= ngroups) { g_err = "mc_set_ties: group_of[" + std::to_string(s) + "] = " + std::to_string(group_of[s]) + " lies outside 0 .. " + std::to_string(ngroups - 1); return -1; }
+    ties_off(h);                                                    // (a map of another size: everything anew)
+    h->ties_ngroups = ngroups;
+    if (h->d_ties.alloc(ties_slots(h)) || (!h->ev_ties && h->ev_ties.create())) { ties_off(h); return -1; }
+    if (group_of) {
+        if (h->d_tgroup.alloc(nseq)) { ties_off(h); return -1; }
+        if (mc_owned_ck(hipMemcpy(h->d_tgroup, group_of, sizeof(int32_t) * nseq, hipMemcpyHostToDevice), "hipMemcpy(d_tgroup, group_of)")) { ties_off(h); return -1; }
+    }
+    if (h->cov && h->d_cov_any.alloc(cov_slots(h))) { ties_off(h); return -1; }
+    h->ties = true;
+    return abund_zero(h);
+}
+
+extern "C" int mc_ties_read(mc_handle *h, int64_t *candidates, int64_t *unique, uint64_t *share, int64_t *group_unique, int64_t *ambiguous, int64_t *group_ambiguous)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ties) { g_err = "mc_ties_read: ties are off (mc_set_ties)"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    const size_t nseq = (size_t)h->H.nseq;
+    std::vector<unsigned long long> tab(ties_slots(h));
+    HIPCK(hipMemcpy(tab.data(), h->d_ties, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // (the kernel of every completed range has been waited for: range_end)
+    for (size_t s = 0; s < nseq; s++) {
+        if (candidates) candidates[s] = (int64_t)tab[2 * s];
+        if (unique) unique[s] = (int64_t)tab[2 * s + 1];
+        if (share) share[s] = (uint64_t)tab[2 * (nseq + 1) + s];
+    }
+    for (int32_t g = 0; group_unique && g < h->ties_ngroups; g++) group_unique[g] = (int64_t)tab[3 * nseq + 2 + (size_t)g];
+    if (ambiguous) *ambiguous = (int64_t)tab[2 * nseq];
+    if (group_ambiguous) *group_ambiguous = (int64_t)tab[2 * nseq + 1];
+    return 0;
+}
+
+extern "C" int mc_ties_coverage_read(mc_handle *h, int64_t *covered_any, int64_t *spanned_any, int64_t *max_depth_any)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ties) { g_err = "mc_ties_coverage_read: ties are off (mc_set_ties)"; return -1; }
+    if (!h->cov) { g_err = "mc_ties_coverage_read: coverage is off (mc_set_coverage)"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (cov_scan(h, nullptr, h->d_ties, h->d_cov_any)) return -1;
+    const size_t nseq = (size_t)h->H.nseq;
+    std::vector<unsigned long long> out(3 * nseq);
+    HIPCK(hipMemcpy(out.data(), h->d_covout, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < nseq; s++) {
+        if (covered_any) covered_any[s] = (int64_t)out[3 * s];
+        if (spanned_any) spanned_any[s] = (int64_t)out[3 * s + 1];
+        if (max_depth_any) max_depth_any[s] = (int64_t)out[3 * s + 2];
+    }
+    return 0;
+}
+
+extern "C" float mc_ties_ms(const mc_handle *h) { return h ? h->ties_ms : 0.0f; }
 
 extern "C" int64_t mc_result_rows(mc_handle *h, const mc_row **rows) { if (!h) return -1; rows_wait(h); *rows = h->res_rows; return h->n_res_rows; }
 extern "C" int64_t mc_result_best_hits(mc_handle *h, const mc_best_hit **hits) { if (!h) return -1; best_materialize(h); *hits = h->best.data(); return (int64_t)h->best.size(); }

@@ -40,6 +40,8 @@ def parse_arguments(argv=None):
     p.add_argument("--coverage", dest="coverage", action="store_true", default=False, help="add covered_aa, breadth (covered_aa / length_aa), mean_depth and max_depth: which part of a gene its reads cover")
     p.add_argument("--min-breadth", dest="min_breadth", type=float, default=None, metavar="F", help="add the column detected: reads > 0 and breadth >= F (0 < F <= 1); implies --coverage")
     p.add_argument("--depth-out", dest="depth_out", type=str, default=None, metavar="FILE", help="write the per-residue depth as gene, start, end, depth (0-based start, exclusive end); implies --coverage")
+    p.add_argument("--ties", dest="ties", action="store_true", default=False, help="add unique_reads, candidate_reads, shared_reads and rpkg_shared: the genes that tie for a read's highest bit score share the read "
+                   "(with --coverage also covered_any_aa and breadth_any, with --min-breadth detected_any, with --groups the groups' unique and shared reads)")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):

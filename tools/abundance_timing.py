@@ -14,7 +14,11 @@ repetition loop, median with min - max.  One JSON line per figure.
 --coverage (kernel, files): coverage breadth and depth beside the counts (Engine.set_coverage; csrc/k_coverage.h), the two sides alternating
 inside the repetition loop: `kernel` adds abundance_ms() with the marks riding in the counting kernel and coverage_ms() of one
 coverage() read (the scan); `files` adds the wall time of file -> counts + coverage() with the switch on.  A tree without the switch
-(the parent commit's) gives the off sides alone."""
+(the parent commit's) gives the off sides alone.
+    abundance_timing.py ties                 the tie accounting beside the counts (Engine.set_ties; csrc/k_ties.h), three legs alternating inside
+                                             the repetition loop on both libraries of `kernel`: counts alone, counts + ties, counts + coverage +
+                                             ties - abundance_ms() and ties_ms() of each, against ms_total of the same ranges; then the wall
+                                             time of file -> counts (+ ties()) with the switch off and on, as `files` measures it"""
 import argparse
 import json
 import os
@@ -45,9 +49,65 @@ def numpy_counts(rows, nseq):
     return np.bincount(rows["subject"][keep], minlength=nseq).astype(np.int64)
 
 
+def ties_legs(a, eng, reads, _native, synth):
+    L, n = 150, len(reads)
+    names, seqs = _native.load_markers()
+    dense = synth.sample_reads(synth.build_genomes(seqs, total_bp=3_000_000, seed=404, marker_gene_fraction=1.0), a.dense_reads, L, seed=405)
+    legs = (("counts", False, False), ("counts_ties", False, True), ("counts_coverage_ties", True, True))
+    for label, rd, piece in (("bench reads, marker database", reads, n), ("marker-dense library, ranges of 5,000", dense, 5000)):
+        eng.upload(rd)
+        eng.set_abundance(True)
+        ms = {leg[0]: {"abundance": [], "ties": [], "total": []} for leg in legs}
+        rows, t = 0, None
+        for rep in range(a.reps + 1):
+            for name, marks, ties in legs:
+                eng.set_coverage(marks)
+                eng.set_ties(ties)
+                eng.abundance_reset()
+                tot, rows = 0.0, 0
+                for lo in range(0, len(rd), piece):
+                    eng.run_range(lo, min(piece, len(rd) - lo), lo)
+                    st = eng.stats()
+                    tot += st["ms_total"]; rows += st["rows"]
+                    assert st["range_splits"] == 0
+                ms[name]["abundance"].append(eng.abundance_ms() * 1e6 / len(rd)); ms[name]["total"].append(tot * 1e6 / len(rd))
+                ms[name]["ties"].append(eng.ties_ms() * 1e6 / len(rd) if ties else 0.0)
+                if ties:
+                    t = eng.ties()
+        got = eng.abundance()
+        eng.set_abundance(False)
+        out = {"what": "ties", "library": label, "reads": len(rd), "rows_per_read": round(rows / len(rd), 2), "assigned": got["assigned"], "ambiguous": t["ambiguous"],
+               "candidates": int(t["candidates"].sum())}
+        for name in ms:
+            out[name] = {"abundance_ms_per_1M_reads": spread(ms[name]["abundance"][1:]), "ties_ms_per_1M_reads": spread(ms[name]["ties"][1:]),
+                         "range_ms_total_per_1M_reads": spread(ms[name]["total"][1:])}
+        print(json.dumps(out), flush=True)
+    with tempfile.TemporaryDirectory() as d:
+        fa = os.path.join(d, "reads.fa")
+        with open(fa, "wb") as f:
+            for s in range(0, n, 50000):
+                f.write(b"".join(b">r%d\n%s\n" % (s + i, bytes(r)) for i, r in enumerate(reads[s:s + 50000])))
+        wall = {"counts": [], "counts_ties": []}
+        for rep in range(a.reps + 1):
+            for name, ties in (("counts_ties", True), ("counts", False)):
+                rd = _native.Reader([fa], L, 10 * n, False, 0, -5, -5, 100, False)
+                try:
+                    eng.set_abundance(True)
+                    eng.set_ties(ties)
+                    t0 = time.perf_counter()
+                    eng.search_files(rd, keep_rows=False)
+                    eng.abundance()
+                    if ties:
+                        eng.ties()
+                    wall[name].append(1e3 * (time.perf_counter() - t0))
+                finally:
+                    rd.close()
+        print(json.dumps({"what": "ties files", "reads": n, "counts_wall_ms": spread(wall["counts"][1:]), "counts_ties_wall_ms": spread(wall["counts_ties"][1:])}), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("what", choices=("kernel", "files", "host"))
+    p.add_argument("what", choices=("kernel", "files", "host", "ties"))
     p.add_argument("--root", default=os.path.dirname(HERE))
     p.add_argument("--reads", type=int, default=1000000)
     p.add_argument("--dense-reads", type=int, default=100000)
@@ -64,7 +124,9 @@ def main():
     has_switch = hasattr(eng, "set_abundance")
     cov = a.coverage and hasattr(eng, "set_coverage")
     reads = synth.GenomeReads(device="cpu", seed=20261001).single(n, L).numpy()
-    if a.what == "kernel":
+    if a.what == "ties":
+        ties_legs(a, eng, reads, _native, synth)
+    elif a.what == "kernel":
         names, seqs = _native.load_markers()
         dense = synth.sample_reads(synth.build_genomes(seqs, total_bp=3_000_000, seed=404, marker_gene_fraction=1.0), a.dense_reads, L, seed=405)
         for label, rd, piece in (("bench reads, marker database", reads, n), ("marker-dense library, ranges of 5,000", dense, 5000)):
