@@ -26,7 +26,9 @@ MC_HD bool mc_abund_passes(const McAbundPars &A, int nmatch, int alnlen, double 
 // first, one atomic on tab[nseq][0] per workgroup that assigned any - a device-scope atomic on ONE address runs at the memory
 // side (mc_block_alloc).  32,767 x 16 bytes does not fit an LDS histogram; the hits of a range are spread over the subjects.
 // rows: the nrows final rows of a completed range (c.d_rows), ascending read id.  tab: (nseq + 1) x 2 counters.
-// (k_coverage.h holds a SECOND COPY of this walk, k_abundance_cov, which also marks the best row's span: whoever edits one edits both.)
+// (k_coverage.h holds a SECOND COPY of this walk, k_abundance_cov, which also marks the best row's span: whoever edits one edits both.
+// One walk under both kernels compiled to other code and measured about 1 % slower on five of six legs: DESIGN.md 13.3.  Both are
+// launched by mc_abund_launch, mc_abund.h, which also owns the table.)
 __global__ void __launch_bounds__(256) k_abundance(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, unsigned long long *tab)
 {
     __shared__ uint32_t wcnt[4];

@@ -21,7 +21,8 @@
 //
 // ---- Layout -------------------------------------------------------------------------------------------------------------------
 // The depth is kept as a difference array of uint32_t: gene s owns len_s + 1 slots from covoff[s] = sum over t < s of (len_t + 1)
-// = off[s] + s (off: the index's residue offsets, nseq + 1 of them, on the device anyway - covoff is computed, not stored).  At most
+// = off[s] + s (off: the index's residue offsets, nseq + 1 of them, on the device anyway - covoff is computed, not stored; the array's
+// size: mc_diff_slots, mc_abund.h).  At most
 // 32,767 x 2,048 slots: 32 bits hold every offset.  The last slot of a gene is a sentinel: the -1 of a span that ends at len - 1
 // lands there and not in the next gene.
 // Mark (k_abundance_cov): the best row adds +1 at covoff[s] + sstart and -1 (wrapping) at covoff[s] + send + 1.  depth[p] is the
@@ -29,10 +30,9 @@
 //
 // k_abundance_cov is k_abundance (k_abundance.h: the same walk, the same mc_abund_passes, the same tie rule, the same counters) with
 // the best row's span kept and two 32-bit atomics issued beside the two 64-bit ones: the walk over a read's rows happens once, and
-// range_end launches this kernel INSTEAD of k_abundance while coverage is on.  It is a kernel of its own and not an instantiation of
-// a template both share: every shared form that was tried changed the code the compiler makes for k_abundance itself,
-// and the path without coverage is to stay the kernel it was, instruction for instruction.  tests/test_gpu_coverage_units.py holds
-// the counters of THIS kernel to tests/abundance_restated.py, so the two walks cannot drift apart unseen.
+// mc_abund_launch (mc_abund.h) launches this kernel INSTEAD of k_abundance while coverage is on.  A kernel of its own, not an instantiation
+// of a template both share: DESIGN.md 13.3 has why.  tests/test_gpu_coverage_units.py holds the counters of BOTH kernels to
+// tests/abundance_restated.py, so the two walks cannot drift apart unseen.
 __global__ void __launch_bounds__(256) k_abundance_cov(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, unsigned long long *tab,
                                                        const uint32_t *__restrict__ off, uint32_t *diff)
 {

@@ -35,7 +35,8 @@
 // ---- Layout -------------------------------------------------------------------------------------------------------------------
 // tab: (nseq + 1) x 2 counters, the shape of k_abundance's table: [s] = candidates, unique of subject s; [nseq] = ambiguous,
 // group_ambiguous.  share: nseq counters.  group_unique: ngroups counters.  diff_any: nres + nseq slots (k_coverage.h, "Layout"), or
-// null while coverage is off.
+// null while coverage is off.  The three counter arrays are ONE buffer; where each begins and how large it is: mc_tie_share_at,
+// mc_tie_group_at, mc_tie_slots in mc_abund.h - the only other place that knows these numbers.
 
 // the device's sink of mc_ties_read: plain vector atomics
 struct McTiesDev {
@@ -63,7 +64,7 @@ struct McTiesPass {
 
 // The shape of k_abundance: the thread at a read's first row walks the read's rows (mc_ties_read: up to three walks, and a duplicate
 // check among the tied rows only); ambiguous and group_ambiguous are summed over the workgroup first, one atomic each per workgroup
-// that has any.  Launched behind the counting kernel on the same rows (range_end), it reads them where they lie.
+// that has any.  Launched behind the counting kernel on the same rows (mc_abund_launch, mc_abund.h), it reads them where they lie.
 // group_of / group_unique: null without a group map.  off / diff_any: null while coverage is off.
 __global__ void __launch_bounds__(256) k_ties(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, unsigned long long *tab, unsigned long long *share,
                                               const int32_t *__restrict__ group_of, unsigned long long *group_unique, const uint32_t *__restrict__ off, uint32_t *diff_any)

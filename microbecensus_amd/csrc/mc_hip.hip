@@ -17,6 +17,7 @@
 //   k_abundance.h          per-gene read counts for RPKG, summed over the rows of every completed range (mc_set_abundance)
 //   k_coverage.h           per-gene coverage breadth and depth beside them: marks in the counting kernel, a scan at read time (mc_set_coverage)
 //   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
+//   mc_abund.h             (host) the owner of those three: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
 //   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
@@ -35,12 +36,10 @@
 #include "k_classes.h"
 #include "k_bootstrap.h"
 #include "k_wfit.h"
-#include "k_abundance.h"
-#include "k_coverage.h"
-#include "k_ties.h"
 #include "mc_pieces.h"
 #include "mc_ahead.h"
 #include "mc_owned.h"
+#include "mc_abund.h"
 
 #include <map>
 
@@ -97,19 +96,7 @@ struct mc_handle {
     int64_t train_bases = 0;              // mc_train_library: the bases of the last library's reads (mc_train_library_bases)
     float boot_ms = 0;                    // mc_bootstrap: the two kernels of the last call (HIP events)
     float wfit_ms = 0;                    // mc_fit_weights / mc_weights_mue: the kernels of the last call (HIP events)
-    // mc_set_abundance: the cut-offs, the (nseq + 1) x 2 device counters ([s]: reads, aligned of subject s; [nseq][0]: assigned), the reads
-    // of the completed ranges, the kernels' time since the last reset and the two events around the kernel of a range
-    bool abund = false; McAbundPars abund_pars = {}; McDev<unsigned long long> d_abund; int64_t abund_searched = 0; float abund_ms = 0;
-    McEvent ev_abund[2];
-    // mc_set_coverage: the difference array of the depth (nres + nseq slots: k_coverage.h, "Layout"), the scan's 3 x nseq results, the
-    // scan kernels' time since the last reset and the two events around a scan
-    bool cov = false; McDev<uint32_t> d_cov; McDev<unsigned long long> d_covout; float cov_ms = 0;
-    McEvent ev_cov[2];
-    // mc_set_ties: the tie counters of k_ties.h in ONE buffer ((nseq + 1) x 2: candidates, unique of subject s, [nseq]: ambiguous,
-    // group_ambiguous; then nseq shares; then ngroups group_unique), the group map, the any-depth's difference array (it exists
-    // exactly while ties and coverage are both on), the kernels' time since the last reset and the event behind the kernel of a range
-    bool ties = false; int32_t ties_ngroups = 0; McDev<unsigned long long> d_ties; McDev<int32_t> d_tgroup; McDev<uint32_t> d_cov_any; float ties_ms = 0;
-    McEvent ev_ties;
+    McAbundance ab;                       // mc_set_abundance, mc_set_coverage, mc_set_ties: the switches and all that hangs on them (mc_abund.h)
     McPin<uint8_t> stage_pin[2]; McDev<uint8_t> stage_dev[2]; size_t stage_bytes = 0; McStream copy_stream;   // run_stream (stage_bytes: what all four hold, 0 until they do)
     // resident reads
     int64_t nreads = 0, cap_own = 0;
@@ -246,6 +233,7 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
         h->d_keys.alloc(H.keys.size()) || h->d_fam.alloc((size_t)nseq) || h->d_T.alloc(1) || h->d_P.alloc(1)) return -1;
     HIPCK(hipMemset(h->d_res_base, MC_INV, H.res.size() + 128));
     h->d_res = h->d_res_base + 64;                                 // (k_gapped_lds reads 16 bytes at a time around a flank's first residues)
+    h->ab.bind(nseq, (size_t)H.nres, h->d_off);
     if (h->d_bitmap.alloc(H.bitmap.size()) || h->d_filt.alloc(H.filt.size()) || h->d_wild.alloc(H.wild.size()) || h->d_pair.alloc(H.pair.size()) || h->d_rt.alloc(H.rt.size())) return -1;
     if (!H.rec.empty() && h->d_rec.alloc(H.rec.size())) return -1;
     {
@@ -502,8 +490,6 @@ extern "C" int mc_attach(mc_handle *h, const void *device_reads, int64_t nreads)
     h->reads_dev = (const uint8_t *)device_reads; h->nreads = nreads;
     return 0;
 }
-
-static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; (void)hipEventElapsedTime(&ms, a, b); return ms; }
 
 // The pipeline of a range, in five stages.  Each stage only ISSUES work on the range's stream and ends with an asynchronous copy
 // of the device counters into pinned host memory; the next stage starts by waiting for that copy (stage_wait) and sizes its
@@ -807,7 +793,7 @@ static int stage_d(mc_handle *h, McCtx &c)
 
 // the rows of a range stay on the device: mc_train_library and the class runs, and the abundance counts when nobody asked for the rows
 // (mc_set_abundance with mc_set_keep_rows(h, 0): the kernel has read them where they lie)
-static bool rows_stay(const mc_handle *h) { return h->rows_stay || (h->abund && !h->keep_rows); }
+static bool rows_stay(const mc_handle *h) { return h->rows_stay || (h->ab.active() && !h->keep_rows); }
 
 // E: rows (final order and ABI layout: McRow == mc_row) and best hits into pinned host memory
 static int stage_e(mc_handle *h, McCtx &c)
@@ -945,20 +931,8 @@ static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t nex
     c.nrows = (c.nh && !h->best_only) ? c.h_c[C_ROWS] : 0u; c.nsegs = c.h_c[C_SEGS]; c.nbest = c.h_c[C_BEST];
     // the abundance counts of the range: its rows are final and none of its pools overflowed - a range that did has returned above
     // and counts nothing; the pieces mc_run_range cuts it into come through here one by one, each once
-    const bool abund = h->abund && !h->best_only;
-    if (abund) {
-        HIPCK(hipEventRecord(h->ev_abund[0], c.stream));
-        const uint32_t nr = std::min(c.nrows, c.cap_rows);
-        if (nr && h->cov) k_abundance_cov<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund, h->d_off, h->d_cov);   // (the marks ride with the counts: k_coverage.h)
-        else if (nr) k_abundance<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)h->H.nseq, h->d_abund);
-        HIPCK(hipEventRecord(h->ev_abund[1], c.stream));
-        if (h->ties) {                                              // (behind the counting kernel, on the same final rows where they lie: k_ties.h)
-            const size_t ns = (size_t)h->H.nseq;
-            if (nr) k_ties<<<dim3((nr + 255) / 256), dim3(256), 0, c.stream>>>(h->abund_pars, c.d_rows, nr, (int32_t)ns, h->d_ties, h->d_ties + 2 * (ns + 1), h->d_tgroup,
-                                                                                 h->d_tgroup ? h->d_ties + 3 * ns + 2 : nullptr, h->d_cov_any ? h->d_off.get() : nullptr, h->d_cov_any);
-            HIPCK(hipEventRecord(h->ev_ties, c.stream));
-        }
-    }
+    const bool abund = h->ab.active() && !h->best_only;
+    if (abund && h->ab.launch(c.d_rows, std::min(c.nrows, c.cap_rows), c.stream)) return -1;
     if ((size_t)c.nrows > h->pin_slot_cap[h->pin_cur] && !rows_stay(h)) {   // grow the pinned row buffer
         (void)hipStreamSynchronize(h->rows_stream);                  // (the copy of the run before writes into the other buffer: let it finish before anything is freed)
         const size_t want = (size_t)c.nrows + c.nrows / 4 + 1024;
@@ -972,8 +946,7 @@ static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t nex
     if (rc) { (void)hipStreamSynchronize(c.stream); (void)hipStreamSynchronize(h->rows_stream); return rc; }
     if (c.nrows && !rows_stay(h)) { HIPCK(hipEventRecord(h->ev_rows, h->rows_stream)); h->rows_pending = true; h->rows_ever = true; }
     if ((rc = stage_wait(c)) != 0) return rc;
-    if (abund) { h->abund_searched += c.n; h->abund_ms += ev_ms(h->ev_abund[0], h->ev_abund[1]); }
-    if (abund && h->ties) h->ties_ms += ev_ms(h->ev_abund[1], h->ev_ties);
+    if (abund) h->ab.range_done(c.n);
     h->res_rows = rows_stay(h) ? nullptr : (const mc_row *)h->pin_slot[h->pin_cur]; h->n_res_rows = rows_stay(h) ? 0 : (int64_t)c.nrows;
     h->best_from = &c; h->best_count = c.nbest;                  // (mc_result_best_hits / whoever needs them: best_materialize)
 #ifdef MC_EXP_TIMING
@@ -1457,7 +1430,7 @@ static int search_varlen(mc_handle *h, const uint8_t *bases, const int64_t *offs
     for (mc_best_hit &b : R.best) b.read = (int32_t)(first_read_id + perm[(size_t)b.read]);
     std::sort(R.best.begin(), R.best.end(), [](const mc_best_hit &x, const mc_best_hit &y) { return x.read < y.read; });
     R.tot.reads += P.nshort;
-    if (h->abund) h->abund_searched += P.nshort;                       // (reads too short to have a frame: searched, no rows - as mc_stats.reads counts them)
+    h->ab.add_searched(P.nshort);                                    // (reads too short to have a frame: searched, no rows - as mc_stats.reads counts them)
     h->res_rows = out.data(); h->n_res_rows = (int64_t)out.size(); h->best.swap(R.best); h->stats = R.tot;
     return 0;
 }
@@ -1633,7 +1606,7 @@ static int classes_ready(mc_handle *h, const char *who)
 {
     if (!h || !h->run_set || !h->cls_set) { g_err = std::string(who) + ": mc_set_run_classes() must be called first"; return -1; }
     if (h->pipe_nout) { g_err = std::string(who) + ": ranges begun with mc_range_begin() are still in flight"; return -1; }
-    if (h->abund) { g_err = std::string(who) + ": a class run is refused while abundance counting is on (mc_set_abundance)"; return -1; }
+    if (h->ab.active()) { g_err = std::string(who) + ": a class run is refused while abundance counting is on (mc_set_abundance)"; return -1; }
     return 0;
 }
 
@@ -1981,217 +1954,107 @@ extern "C" int mc_set_keep_rows(mc_handle *h, int keep)
 extern "C" int mc_set_best_hits_only(mc_handle *h, int on)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (on && h->abund) { g_err = "mc_set_best_hits_only: refused while abundance counting is on - it needs every m8 row of a read (mc_set_abundance)"; return -1; }
+    if (on && h->ab.active()) { g_err = "mc_set_best_hits_only: refused while abundance counting is on - it needs every m8 row of a read (mc_set_abundance)"; return -1; }
     h->best_only = on != 0;
     return 0;
 }
 
-// ---- per-gene read counts for RPKG (the reference README, "Normalization"; csrc/k_abundance.h states the rule) ---------------------
-// The counters live in the handle and accumulate over every range that completes (range_end) until they are reset.
-static size_t cov_slots(const mc_handle *h) { return (size_t)h->H.nres + (size_t)h->H.nseq; }   // (every gene's residues and its sentinel)
-static size_t ties_slots(const mc_handle *h) { return 3 * (size_t)h->H.nseq + 2 + (size_t)h->ties_ngroups; }   // (k_ties.h, "Layout": the pair table, the shares, group_unique)
-static int abund_zero(mc_handle *h)
-{
-    HIPCK(hipSetDevice(h->device));
-    HIPCK(hipMemset(h->d_abund, 0, sizeof(unsigned long long) * 2 * ((size_t)h->H.nseq + 1)));
-    h->abund_searched = 0; h->abund_ms = 0.f;
-    if (h->cov) HIPCK(hipMemset(h->d_cov, 0, sizeof(uint32_t) * cov_slots(h)));   // (counts and depth describe the same reads)
-    h->cov_ms = 0.f;
-    if (h->ties) HIPCK(hipMemset(h->d_ties, 0, sizeof(unsigned long long) * ties_slots(h)));   // (... and so do the tie counters)
-    if (h->d_cov_any) HIPCK(hipMemset(h->d_cov_any, 0, sizeof(uint32_t) * cov_slots(h)));
-    h->ties_ms = 0.f;
-    return 0;
-}
-
-static void cov_off(mc_handle *h)
-{
-    h->d_cov.reset(); h->d_covout.reset(); h->d_cov_any.reset();
-    for (auto &e : h->ev_cov) e.reset();
-    h->cov = false; h->cov_ms = 0.f;
-}
-
-static void ties_off(mc_handle *h)
-{
-    h->d_ties.reset(); h->d_tgroup.reset(); h->d_cov_any.reset(); h->ev_ties.reset();
-    h->ties = false; h->ties_ngroups = 0; h->ties_ms = 0.f;
-}
-
+// ---- per-gene read counts for RPKG, coverage breadth and depth, the tie accounting (k_abundance.h, k_coverage.h and k_ties.h state the
+// rules) - the counters live in the handle's McAbundance (mc_abund.h) and accumulate over every range that completes (range_end) until
+// they are reset.  Here: the arguments are checked, the device is set, the owner is called.
 extern "C" int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t min_aln, double min_bits, double max_loge)
 {
     if (!h) { g_err = "null handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_set_abundance: a range begun with mc_range_begin() is still in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    if (!on) {
-        h->d_abund.reset();
-        for (auto &e : h->ev_abund) e.reset();
-        h->abund = false; h->abund_searched = 0; h->abund_ms = 0.f;
-        cov_off(h);
-        ties_off(h);
-        return 0;
-    }
+    if (!on) return h->ab.set_counts(false, McAbundPars());
     if (min_ident < 0 || min_ident > 100) { g_err = "mc_set_abundance: min_ident " + std::to_string(min_ident) + " is not a percent from 0 to 100"; return -1; }
     if (min_aln < 0) { g_err = "mc_set_abundance: min_aln " + std::to_string(min_aln) + " is negative"; return -1; }
     if (min_bits != min_bits) { g_err = "mc_set_abundance: min_bits is NaN"; return -1; }
     if (max_loge != max_loge) { g_err = "mc_set_abundance: max_loge is NaN"; return -1; }
     if (h->best_only) { g_err = "mc_set_abundance: best hits only is on (mc_set_best_hits_only) - abundance needs every m8 row of a read"; return -1; }
-    if (!h->d_abund && h->d_abund.alloc(2 * ((size_t)h->H.nseq + 1))) return -1;
-    for (auto &e : h->ev_abund) if (!e && e.create()) return -1;
-    h->abund_pars.min_ident = min_ident; h->abund_pars.min_aln = min_aln; h->abund_pars.min_bits = min_bits; h->abund_pars.max_loge = max_loge;
-    h->abund = true;
-    return abund_zero(h);
+    McAbundPars A; A.min_ident = min_ident; A.min_aln = min_aln; A.min_bits = min_bits; A.max_loge = max_loge;
+    return h->ab.set_counts(true, A);
 }
 
 extern "C" int mc_abundance_reset(mc_handle *h)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->abund) { g_err = "mc_abundance_reset: abundance counting is off (mc_set_abundance)"; return -1; }
+    if (!h->ab.on) { g_err = "mc_abundance_reset: abundance counting is off (mc_set_abundance)"; return -1; }
     if (h->pipe_nout) { g_err = "mc_abundance_reset: a range begun with mc_range_begin() is still in flight"; return -1; }
-    return abund_zero(h);
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.reset();
 }
 
 extern "C" int mc_abundance_read(mc_handle *h, int64_t *reads, int64_t *aligned, int64_t *searched, int64_t *assigned)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->abund) { g_err = "mc_abundance_read: abundance counting is off (mc_set_abundance)"; return -1; }
+    if (!h->ab.on) { g_err = "mc_abundance_read: abundance counting is off (mc_set_abundance)"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    const size_t nseq = (size_t)h->H.nseq;
-    std::vector<unsigned long long> tab(2 * (nseq + 1));
-    HIPCK(hipMemcpy(tab.data(), h->d_abund, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // (the kernel of every completed range has been waited for: range_end)
-    for (size_t s = 0; s < nseq; s++) { if (reads) reads[s] = (int64_t)tab[2 * s]; if (aligned) aligned[s] = (int64_t)tab[2 * s + 1]; }
-    if (searched) *searched = h->abund_searched;
-    if (assigned) *assigned = (int64_t)tab[2 * nseq];
-    return 0;
+    return h->ab.read_counts(reads, aligned, searched, assigned);
 }
 
-extern "C" float mc_abundance_ms(const mc_handle *h) { return h ? h->abund_ms : 0.0f; }
-
-// ---- per-gene coverage breadth and depth beside the counts (csrc/k_coverage.h states the rule and the layout) -------------------------
 extern "C" int mc_set_coverage(mc_handle *h, int on)
 {
     if (!h) { g_err = "null handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_set_coverage: a range begun with mc_range_begin() is still in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    if (!on) { cov_off(h); return 0; }
-    if (!h->abund) { g_err = "mc_set_coverage: abundance counting is off (mc_set_abundance) - coverage is that of the reads it counts"; return -1; }
-    if (!h->d_cov && h->d_cov.alloc(cov_slots(h))) return -1;
-    if (!h->d_covout && h->d_covout.alloc(3 * (size_t)h->H.nseq)) { cov_off(h); return -1; }
-    for (auto &e : h->ev_cov) if (!e && e.create()) { cov_off(h); return -1; }
-    if (h->ties && !h->d_cov_any && h->d_cov_any.alloc(cov_slots(h))) { cov_off(h); return -1; }   // (the any-depth: while ties and coverage are both on, whichever was set second)
-    h->cov = true;
-    return abund_zero(h);
-}
-
-// the scan of the difference array as it stands, into d_covout and (when given) depth: device memory of nres values
-static int cov_scan(mc_handle *h, uint32_t *d_depth, const unsigned long long *d_tab = nullptr, const uint32_t *d_diff = nullptr)
-{
-    if (!d_tab) { d_tab = h->d_abund; d_diff = h->d_cov; }          // (mc_ties_coverage_read hands in the tie table and the any-depth: the same scan)
-    const int32_t nseq = (int32_t)h->H.nseq;
-    if (d_depth) HIPCK(hipMemsetAsync(d_depth, 0, sizeof(uint32_t) * (size_t)h->H.nres, 0));
-    HIPCK(hipEventRecord(h->ev_cov[0], 0));
-    k_coverage_scan<<<dim3(((unsigned)nseq + 3) / 4), dim3(256), 0, 0>>>(d_tab, h->d_off, d_diff, nseq, h->d_covout, d_depth);
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(h->ev_cov[1], 0));
-    HIPCK(hipEventSynchronize(h->ev_cov[1]));
-    h->cov_ms += ev_ms(h->ev_cov[0], h->ev_cov[1]);
-    return 0;
+    if (on && !h->ab.on) { g_err = "mc_set_coverage: abundance counting is off (mc_set_abundance) - coverage is that of the reads it counts"; return -1; }
+    return h->ab.set_coverage(on != 0);
 }
 
 extern "C" int mc_coverage_read(mc_handle *h, int64_t *covered, int64_t *spanned, int64_t *max_depth)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->cov) { g_err = "mc_coverage_read: coverage is off (mc_set_coverage)"; return -1; }
+    if (!h->ab.cov) { g_err = "mc_coverage_read: coverage is off (mc_set_coverage)"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    if (cov_scan(h, nullptr)) return -1;
-    const size_t nseq = (size_t)h->H.nseq;
-    std::vector<unsigned long long> out(3 * nseq);
-    HIPCK(hipMemcpy(out.data(), h->d_covout, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (size_t s = 0; s < nseq; s++) {
-        if (covered) covered[s] = (int64_t)out[3 * s];
-        if (spanned) spanned[s] = (int64_t)out[3 * s + 1];
-        if (max_depth) max_depth[s] = (int64_t)out[3 * s + 2];
-    }
-    return 0;
+    return h->ab.read_figures(false, covered, spanned, max_depth);
 }
 
 extern "C" int mc_coverage_depth(mc_handle *h, uint32_t *depth, int64_t n)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->cov) { g_err = "mc_coverage_depth: coverage is off (mc_set_coverage)"; return -1; }
+    if (!h->ab.cov) { g_err = "mc_coverage_depth: coverage is off (mc_set_coverage)"; return -1; }
     if (n != h->H.nres || !depth) { g_err = "mc_coverage_depth: the array holds " + std::to_string(n) + " values, the database " + std::to_string(h->H.nres) + " residues"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    McDevBuf buf; uint32_t *d_depth = nullptr;
-    if (buf.get(&d_depth, (size_t)n)) return -1;
-    if (cov_scan(h, d_depth)) return -1;
-    HIPCK(hipMemcpy(depth, d_depth, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
+    return h->ab.read_depth(depth);
 }
 
-extern "C" float mc_coverage_ms(const mc_handle *h) { return h ? h->cov_ms : 0.0f; }
-
-// ---- the tie accounting beside the counts (csrc/k_ties.h states the rule and the layout) ----------------------------------------------
 extern "C" int mc_set_ties(mc_handle *h, int on, const int32_t *group_of, int32_t ngroups)
 {
     if (!h) { g_err = "null handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_set_ties: a range begun with mc_range_begin() is still in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    if (!on) { ties_off(h); return 0; }
-    if (!h->abund) { g_err = "mc_set_ties: abundance counting is off (mc_set_abundance) - the ties are those of the reads it counts"; return -1; }
+    if (!on) return h->ab.set_ties(false, nullptr, 0);
+    if (!h->ab.on) { g_err = "mc_set_ties: abundance counting is off (mc_set_abundance) - the ties are those of the reads it counts"; return -1; }
     if (ngroups < 0) { g_err = "mc_set_ties: ngroups " + std::to_string(ngroups) + " is negative"; return -1; }
     if (ngroups > 0 && !group_of) { g_err = "mc_set_ties: " + std::to_string(ngroups) + " groups and a NULL group map"; return -1; }
-    const size_t nseq = (size_t)h->H.nseq;
     if (ngroups == 0) group_of = nullptr;
-    for (size_t s = 0; group_of && s < nseq; s++)
+    for (size_t s = 0; group_of && s < (size_t)h->H.nseq; s++)
         if (group_of[s] < 0 || group_of[s] >= ngroups) { g_err = "mc_set_ties: group_of[" + std::to_string(s) + "] = " + std::to_string(group_of[s]) + " lies outside 0 .. " + std::to_string(ngroups - 1); return -1; }
-    ties_off(h);                                                    // (a map of another size: everything anew)
-    h->ties_ngroups = ngroups;
-    if (h->d_ties.alloc(ties_slots(h)) || (!h->ev_ties && h->ev_ties.create())) { ties_off(h); return -1; }
-    if (group_of) {
-        if (h->d_tgroup.alloc(nseq)) { ties_off(h); return -1; }
-        if (mc_owned_ck(hipMemcpy(h->d_tgroup, group_of, sizeof(int32_t) * nseq, hipMemcpyHostToDevice), "hipMemcpy(d_tgroup, group_of)")) { ties_off(h); return -1; }
-    }
-    if (h->cov && h->d_cov_any.alloc(cov_slots(h))) { ties_off(h); return -1; }
-    h->ties = true;
-    return abund_zero(h);
+    return h->ab.set_ties(true, group_of, ngroups);
 }
 
 extern "C" int mc_ties_read(mc_handle *h, int64_t *candidates, int64_t *unique, uint64_t *share, int64_t *group_unique, int64_t *ambiguous, int64_t *group_ambiguous)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->ties) { g_err = "mc_ties_read: ties are off (mc_set_ties)"; return -1; }
+    if (!h->ab.ties) { g_err = "mc_ties_read: ties are off (mc_set_ties)"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    const size_t nseq = (size_t)h->H.nseq;
-    std::vector<unsigned long long> tab(ties_slots(h));
-    HIPCK(hipMemcpy(tab.data(), h->d_ties, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));   // (the kernel of every completed range has been waited for: range_end)
-    for (size_t s = 0; s < nseq; s++) {
-        if (candidates) candidates[s] = (int64_t)tab[2 * s];
-        if (unique) unique[s] = (int64_t)tab[2 * s + 1];
-        if (share) share[s] = (uint64_t)tab[2 * (nseq + 1) + s];
-    }
-    for (int32_t g = 0; group_unique && g < h->ties_ngroups; g++) group_unique[g] = (int64_t)tab[3 * nseq + 2 + (size_t)g];
-    if (ambiguous) *ambiguous = (int64_t)tab[2 * nseq];
-    if (group_ambiguous) *group_ambiguous = (int64_t)tab[2 * nseq + 1];
-    return 0;
+    return h->ab.read_ties(candidates, unique, share, group_unique, ambiguous, group_ambiguous);
 }
 
 extern "C" int mc_ties_coverage_read(mc_handle *h, int64_t *covered_any, int64_t *spanned_any, int64_t *max_depth_any)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->ties) { g_err = "mc_ties_coverage_read: ties are off (mc_set_ties)"; return -1; }
-    if (!h->cov) { g_err = "mc_ties_coverage_read: coverage is off (mc_set_coverage)"; return -1; }
+    if (!h->ab.ties) { g_err = "mc_ties_coverage_read: ties are off (mc_set_ties)"; return -1; }
+    if (!h->ab.cov) { g_err = "mc_ties_coverage_read: coverage is off (mc_set_coverage)"; return -1; }
     HIPCK(hipSetDevice(h->device));
-    if (cov_scan(h, nullptr, h->d_ties, h->d_cov_any)) return -1;
-    const size_t nseq = (size_t)h->H.nseq;
-    std::vector<unsigned long long> out(3 * nseq);
-    HIPCK(hipMemcpy(out.data(), h->d_covout, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (size_t s = 0; s < nseq; s++) {
-        if (covered_any) covered_any[s] = (int64_t)out[3 * s];
-        if (spanned_any) spanned_any[s] = (int64_t)out[3 * s + 1];
-        if (max_depth_any) max_depth_any[s] = (int64_t)out[3 * s + 2];
-    }
-    return 0;
+    return h->ab.read_figures(true, covered_any, spanned_any, max_depth_any);
 }
 
-extern "C" float mc_ties_ms(const mc_handle *h) { return h ? h->ties_ms : 0.0f; }
+extern "C" float mc_abundance_ms(const mc_handle *h) { return h ? h->ab.ms : 0.0f; }
+extern "C" float mc_coverage_ms(const mc_handle *h) { return h ? h->ab.cov_ms : 0.0f; }
+extern "C" float mc_ties_ms(const mc_handle *h) { return h ? h->ab.ties_ms : 0.0f; }
 
 extern "C" int64_t mc_result_rows(mc_handle *h, const mc_row **rows) { if (!h) return -1; rows_wait(h); *rows = h->res_rows; return h->n_res_rows; }
 extern "C" int64_t mc_result_best_hits(mc_handle *h, const mc_best_hit **hits) { if (!h) return -1; best_materialize(h); *hits = h->best.data(); return (int64_t)h->best.size(); }
@@ -2520,7 +2383,7 @@ extern "C" int mc_train_library(mc_handle *h, mc_genome *g, int64_t nreads, uint
     if (g->device != h->device) { g_err = "mc_train_library: the genome lies on another device than the handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_train_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
     ahead_drop(h);                                                  // (the resident reads are about to be simulated over)
-    if (h->abund) { g_err = "mc_train_library: refused while abundance counting is on (mc_set_abundance)"; return -1; }
+    if (h->ab.active()) { g_err = "mc_train_library: refused while abundance counting is on (mc_set_abundance)"; return -1; }
     McGridPars G; std::vector<int> order;
     if (grid_pars(h, aln_covs, n_cov, max_pids, n_pid, min_scores, n_score, G, order)) return -1;
     HIPCK(hipSetDevice(h->device));
@@ -2679,7 +2542,7 @@ extern "C" int mc_community_library(mc_handle *h, mc_community *c, int64_t nread
     if (c->device != h->device) { g_err = "mc_community_library: the community lies on another device than the handle"; return -1; }
     if (h->pipe_nout) { g_err = "mc_community_library: ranges begun with mc_range_begin() are still in flight"; return -1; }
     ahead_drop(h);                                                  // (the resident reads are about to be simulated over)
-    if (h->abund) { g_err = "mc_community_library: refused while abundance counting is on (it runs best hits only; mc_set_abundance)"; return -1; }
+    if (h->ab.active()) { g_err = "mc_community_library: refused while abundance counting is on (it runs best hits only; mc_set_abundance)"; return -1; }
     HIPCK(hipSetDevice(h->device));
     if (source_for_len(c, h->read_len)) return -1;
     std::fill(c->member_reads.begin(), c->member_reads.end(), 0);

@@ -18,24 +18,7 @@
 #include "order_io.h"
 #include "wave_sort_form.h"
 #include "order_expect.h"
-
-#define CK(call)                                                                                                            \
-    do {                                                                                                                    \
-        hipError_t e_ = (call);                                                                                             \
-        if (e_ != hipSuccess) { fprintf(stderr, "HIP error: %s: %s (line %d)\n", #call, hipGetErrorString(e_), __LINE__); fflush(stderr); exit(3); } \
-    } while (0)
-#define CK_LAUNCH() do { CK(hipGetLastError()); CK(hipDeviceSynchronize()); } while (0)
-
-// a device array: uploaded or filled with one byte, read back whole, freed with the object
-template <class T> struct Dev {
-    T *p = nullptr; size_t n = 0;
-    Dev(size_t count, int fill = 0) : n(count) { CK(hipMalloc((void **)&p, (n + 16) * sizeof(T))); CK(hipMemset(p, fill, (n + 16) * sizeof(T))); }
-    Dev(const T *h, size_t count) : Dev(count) { if (n) CK(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice)); }
-    Dev(const Dev &) = delete;
-    ~Dev() { (void)hipFree(p); }
-    std::vector<T> host() const { std::vector<T> h(n); if (n) CK(hipMemcpy(h.data(), p, n * sizeof(T), hipMemcpyDeviceToHost)); return h; }
-    operator T *() const { return p; }
-};
+#include "device_ck.h"                                              // CK, CK_LAUNCH, Dev<T>
 
 // ---- a. mc_wave_std_sort: a wave per array, the items and the three index arrays in LDS as k_finish_heavy<MAXN> lays them out -----
 template <int MAXN>

@@ -4,39 +4,20 @@
 //   device_ties run IN OUT      (files of sections: order_io.h; tests/ties_cases.py writes IN and reads OUT)
 // IN:  the cut-offs (McAbundPars), off (nseq + 1 residue offsets), the rows (McRow), ascending read id, group_of (nseq groups, or an
 //      empty section: no map), and two int32: ngroups, coverage (0 / 1).
-// OUT: 0 the counting kernel's tab ((nseq + 1) x 2), 1 the tie tab ((nseq + 1) x 2), 2 share (nseq), 3 group_unique (ngroups); with
-//      coverage 4 the scan's 3 x nseq figures of the any-depth, 5 the any-depth of every residue, 6 the depth of every residue (the
-//      counting kernel's marks), without it three empty sections; then the 16 elements of padding behind 7 the counting tab, 8 the tie
-//      tab, 9 share, 10 group_unique, 11 the two difference arrays (zeros all), which no kernel may touch.
-// The kernels are launched as range_end launches them: k_abundance (k_abundance_cov with coverage), then k_ties on the same rows with
-// the same grid; null pointers where range_end hands in null pointers.  The input is checked before anything is launched (exit status
-// 2); every HIP call is checked: an error is printed and ends the program with status 3 at once.
+// OUT: 0 the counting kernel's tab ((nseq + 1) x 2), 1 the tie tab ((nseq + 1) x 2), 2 share (nseq), 3 group_unique (ngroups) - the three
+//      parts of the ONE tie table, cut where csrc/mc_abund.h's layout cuts it; with coverage 4 the scan's 3 x nseq figures of the
+//      any-depth, 5 the any-depth of every residue, 6 the depth of every residue (the counting kernel's marks), without it three empty
+//      sections; then the 16 elements of padding behind 7 the counting tab, 8 the tie table, 9 the two difference arrays (zeros all),
+//      which no kernel may touch.
+// The kernels are launched by mc_abund_launch (csrc/mc_abund.h), the function range_end launches them through: k_abundance
+// (k_abundance_cov with coverage), then k_ties on the same rows with the same grid; null pointers where range_end hands in null
+// pointers.  The input is checked before anything is launched (exit status 2); every HIP call is checked: an error is printed and ends
+// the program with status 3 at once.
 #include "mc_hip_common.h"
-#include "k_abundance.h"
-#include "k_coverage.h"
-#include "k_ties.h"
+#include "mc_abund.h"
 
 #include "order_io.h"
-
-#define CK(call)                                                                                                            \
-    do {                                                                                                                    \
-        hipError_t e_ = (call);                                                                                             \
-        if (e_ != hipSuccess) { fprintf(stderr, "HIP error: %s: %s (line %d)\n", #call, hipGetErrorString(e_), __LINE__); fflush(stderr); exit(3); } \
-    } while (0)
-#define CK_LAUNCH() do { CK(hipGetLastError()); CK(hipDeviceSynchronize()); } while (0)
-
-// a device array: uploaded or zeroed, read back whole, freed with the object.  16 elements of zeroed padding lie behind it: pad() reads
-// them back, and the test asserts that no kernel wrote there
-template <class T> struct Dev {
-    T *p = nullptr; size_t n = 0;
-    Dev(size_t count) : n(count) { CK(hipMalloc((void **)&p, (n + 16) * sizeof(T))); CK(hipMemset(p, 0, (n + 16) * sizeof(T))); }
-    Dev(const T *h, size_t count) : Dev(count) { if (n) CK(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice)); }
-    Dev(const Dev &) = delete;
-    ~Dev() { (void)hipFree(p); }
-    std::vector<T> host() const { std::vector<T> h(n); if (n) CK(hipMemcpy(h.data(), p, n * sizeof(T), hipMemcpyDeviceToHost)); return h; }
-    std::vector<T> pad() const { std::vector<T> h(16); CK(hipMemcpy(h.data(), p + n, 16 * sizeof(T), hipMemcpyDeviceToHost)); return h; }
-    operator T *() const { return p; }
-};
+#include "device_ck.h"                                              // CK, CK_LAUNCH, Dev<T>
 
 int main(int argc, char **argv)
 {
@@ -58,30 +39,28 @@ int main(int argc, char **argv)
     for (size_t s = 0; s < ngo; s++) if (group_of[s] < 0 || group_of[s] >= ngroups) { fprintf(stderr, "input: group_of[%zu] = %d\n", s, group_of[s]); return 2; }
     if (nrows > (1u << 24)) { fprintf(stderr, "input: %zu rows\n", nrows); return 2; }
     for (size_t i = 1; i < nrows; i++) if (rows[i].query < rows[i - 1].query) { fprintf(stderr, "input: row %zu: read ids descend\n", i); return 2; }
-    const size_t nres = off[nseq], slots = nres + (size_t)nseq;
+    const size_t nres = off[nseq], ns = (size_t)nseq, slots = mc_diff_slots(nres, ns);
 
     Dev<uint32_t> d_off(off, noff), d_diff(cov ? slots : 0), d_any(cov ? slots : 0), d_depth(cov ? nres : 0), d_depth_any(cov ? nres : 0);
     Dev<McRow> d_rows(rows, nrows);
     Dev<int32_t> d_group(group_of, ngo);
-    Dev<unsigned long long> d_tab(2 * ((size_t)nseq + 1)), d_ttab(2 * ((size_t)nseq + 1)), d_share((size_t)nseq), d_gu((size_t)ngroups), d_out(3 * (size_t)nseq), d_out_any(3 * (size_t)nseq);
-    const uint32_t nr = (uint32_t)nrows;
-    if (nr) {
-        if (cov) k_abundance_cov<<<dim3((nr + 255) / 256), dim3(256)>>>(*A, d_rows, nr, nseq, d_tab, d_off, d_diff);
-        else k_abundance<<<dim3((nr + 255) / 256), dim3(256)>>>(*A, d_rows, nr, nseq, d_tab);
-        CK_LAUNCH();
-        k_ties<<<dim3((nr + 255) / 256), dim3(256)>>>(*A, d_rows, nr, nseq, d_ttab, d_share, ngo ? (const int32_t *)d_group : nullptr, ngo ? (unsigned long long *)d_gu : nullptr,
-                                                      cov ? (const uint32_t *)d_off : nullptr, cov ? (uint32_t *)d_any : nullptr);
-        CK_LAUNCH();
-    }
-    out.put(d_tab.host()); out.put(d_ttab.host()); out.put(d_share.host()); out.put(d_gu.host());
+    Dev<unsigned long long> d_tab(mc_pair_slots(ns)), d_ties(mc_tie_slots(ns, (size_t)ngroups)), d_out(3 * ns), d_out_any(3 * ns);
+    McEvent own[3];
+    for (McEvent &e : own) if (e.create()) { fprintf(stderr, "HIP error: %s\n", g_err.c_str()); return 3; }
+    const hipEvent_t ev[3] = {own[0], own[1], own[2]};
+    const McAbundBufs B = {nseq, d_off, d_tab, cov ? (uint32_t *)d_diff : nullptr, d_ties, ngo ? (const int32_t *)d_group : nullptr, cov ? (uint32_t *)d_any : nullptr};
+    if (mc_abund_launch(*A, B, d_rows, (uint32_t)nrows, nullptr, ev)) { fprintf(stderr, "HIP error: %s\n", g_err.c_str()); return 3; }
+    CK_LAUNCH();
+    const std::vector<unsigned long long> ties = d_ties.host();
+    out.put(d_tab.host()); out.put(ties.data(), mc_tie_share_at(ns)); out.put(ties.data() + mc_tie_share_at(ns), ns); out.put(ties.data() + mc_tie_group_at(ns), (size_t)ngroups);
     if (cov) {
-        k_coverage_scan<<<dim3(((unsigned)nseq + 3) / 4), dim3(256)>>>(d_ttab, d_off, d_any, nseq, d_out_any, d_depth_any); CK_LAUNCH();
+        k_coverage_scan<<<dim3(((unsigned)nseq + 3) / 4), dim3(256)>>>(d_ties, d_off, d_any, nseq, d_out_any, d_depth_any); CK_LAUNCH();
         k_coverage_scan<<<dim3(((unsigned)nseq + 3) / 4), dim3(256)>>>(d_tab, d_off, d_diff, nseq, d_out, d_depth); CK_LAUNCH();
         out.put(d_out_any.host()); out.put(d_depth_any.host()); out.put(d_depth.host());
     } else {
         for (int k = 0; k < 3; k++) out.put((const uint32_t *)nullptr, 0);
     }
-    out.put(d_tab.pad()); out.put(d_ttab.pad()); out.put(d_share.pad()); out.put(d_gu.pad());
+    out.put(d_tab.pad()); out.put(d_ties.pad());
     { std::vector<uint32_t> p = d_diff.pad(), p2 = d_any.pad(); p.insert(p.end(), p2.begin(), p2.end()); out.put(p); }
     sections_write(argv[3], out);
     return 0;

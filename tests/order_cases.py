@@ -4,8 +4,10 @@ Every input is a legal state of the pipeline - sizes within the kernels' capacit
 before anything is launched."""
 import os
 import re
+import subprocess
 
 import numpy as np
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "microbecensus_amd", "csrc")
@@ -51,6 +53,37 @@ def read_sections(path):
         at += 8 + nb
     assert at == len(raw)
     return out
+
+
+# ---- the device harnesses (tests/emul/device_*.hip): one build, one child process per case ---------------------------------------------
+_ABNORMAL = []          # the cases whose child ended abnormally, in any module: nothing more is started on the GPU behind them
+
+
+def harness(name, tmp_path_factory):
+    """tests/emul/<name>.hip built with the library's flags (a module-scoped fixture calls this: once per module)."""
+    exe = str(tmp_path_factory.mktemp(name) / name)
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", CSRC, "-o", exe, os.path.join(EMUL, name + ".hip")])
+    return exe
+
+
+def run_child(exe, case, arrays, tmp, limit, verb=None):
+    """One child process `exe <verb or case> IN OUT` under a time limit of its own; returns the sections it wrote.  A child that ends by a
+    signal, at its time limit or with a HIP error fails its test with its output, and every later call - of any module - fails at once
+    without starting anything.  Exit status 2, the harness refusing its input before anything was launched, is no such end."""
+    if _ABNORMAL:
+        pytest.fail("not started: the child of case %s ended abnormally earlier in this run" % _ABNORMAL[0], pytrace=False)
+    write_sections(tmp / (case + ".in"), arrays)
+    cmd = ["timeout", "-k", "10", str(limit), exe, verb or case, str(tmp / (case + ".in")), str(tmp / (case + ".out"))]
+    try:
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=limit + 30)
+    except subprocess.TimeoutExpired as e:
+        _ABNORMAL.append(case)
+        pytest.fail("%s: no end after %d s\n%s" % (case, limit + 30, e.stdout), pytrace=False)
+    if p.returncode != 0:
+        if p.returncode != 2:
+            _ABNORMAL.append(case)
+        pytest.fail("%s: exit status %d\n%s" % (case, p.returncode, p.stdout), pytrace=False)
+    return read_sections(tmp / (case + ".out"))
 
 
 def pack(arrays, dtype):

@@ -5,11 +5,11 @@ import gzip
 import hashlib
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
+import abund_inputs as I
 import abundance_restated as R
 
 pytestmark = pytest.mark.gpu
@@ -29,18 +29,12 @@ def _same(got, want):
 
 @pytest.fixture(scope="module")
 def engine():
-    from microbecensus_amd import _native
-    e = _native.Engine(device=0)
-    model = _native.load_model()
-    e.set_run(100, model["pars"]["100"], model["families"])
-    yield e
-    e.close()
+    yield from I.marker_engine()
 
 
 @pytest.fixture(scope="module")
 def reads():
-    seqs = [l.rstrip(b"\r\n") for l in gzip.open(os.path.join(GOLD, CASE + ".reads.fa.gz"), "rb") if not l.startswith(b">")]
-    return np.frombuffer(b"".join(seqs), dtype=np.uint8).reshape(len(seqs), len(seqs[0]))
+    return I.example_reads()
 
 
 @pytest.fixture(scope="module")
@@ -72,18 +66,10 @@ def test_marker_database_equals_the_restatement_of_the_reference_m8(engine, read
 
 def test_generic_database_equals_the_restatement_of_the_reference_m8():
     """18,553 sequences, 20,000 reads, the generic seed path: subject indices up to 18,552."""
-    sys.path.insert(0, GOLD)
-    import make_generic_db_golden as G
-    from microbecensus_amd import _native
-    meta = json.load(open(os.path.join(GOLD, "generic_db.json")))
-    names, seqs, rd = G.case_inputs()
-    assert hashlib.md5(b"".join(b">%d\n%s\n" % (i, bytes(r)) for i, r in enumerate(rd))).hexdigest() == meta["reads_md5"]
-    rows = R.rows_from_m8(os.path.join(GOLD, "generic_db.m8.gz"), names)
-    assert len(rows) == meta["m8_rows"] and max(r[1] for r in rows) > 18000
     mixed = dict(min_ident=50, min_aln=25, min_bits=40.5, max_loge=-2.5)
-    eng = _native.Engine(device=0, names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
-    try:
-        eng.set_run(meta["read_length"])
+    with I.generic_case() as (eng, names, seqs, rd, meta, m8):
+        rows = R.rows_from_m8(m8, names)
+        assert len(rows) == meta["m8_rows"] and max(r[1] for r in rows) > 18000
         for cut in (dict(), mixed):
             assert R.cutoffs_clear_of_printed_values(rows, cut.get("min_bits", 0.0), cut.get("max_loge", 1.0))
             want = R.abundance(rows, len(names), **cut)
@@ -93,8 +79,6 @@ def test_generic_database_equals_the_restatement_of_the_reference_m8():
             print(cut, "assigned", got["assigned"], "genes hit", int((got["reads"] > 0).sum()), "abundance ms", eng.abundance_ms(), "of", eng.stats()["ms_total"])
             assert got["searched"] == len(rd) and _same(got, want)
         assert want["assigned"] not in (0, meta["reads_with_rows"])          # (the mixed set cuts)
-    finally:
-        eng.close()
 
 
 def test_counters_do_not_depend_on_batches_ranges_or_entry_point(engine, reads, golden_rows, tmp_path, monkeypatch):
@@ -163,43 +147,16 @@ def test_counters_do_not_depend_on_batches_ranges_or_entry_point(engine, reads, 
 
 
 def test_a_range_that_overflows_its_pools_counts_once(monkeypatch):
-    """The marker-dense library of tests/test_gpu_blindspots.py's recipe (~290 HSPs and ~100 m8 rows per read).  The size: the pools of
-    a run of n reads of 150 bp hold 16 n + 2^20 rows and 58 n + 3 x 2^20 HSPs (ensure_capacity), so ~100 rows per read overflow the row
-    pool from n = 12,500 on and ~290 HSPs per read the HSP pool from 13,600 on: 24,000 reads on an engine of their own (pools only
-    grow) is a small size that takes the halving path with a margin, and the test asserts that it does.  The counters must be those of 5,000-read batches (which fit: no split), and the
-    restatement's on that run's own host rows - the one place the code's rows are the yardstick; tests/test_gpu_blindspots.py pins them
-    to the oracle."""
-    from microbecensus_amd import _native, synth
-    names, seqs = _native.load_markers()
-    genome = synth.build_genomes(seqs, total_bp=3_000_000, seed=404, marker_gene_fraction=1.0)
-    rd = synth.sample_reads(genome, 24_000, 150, seed=405)
-    cut = dict(min_ident=40, min_aln=30)
-    eng = _native.Engine(device=0)
-    try:
-        eng.set_run(150)
-        eng.set_abundance(True, **cut)
-        eng.search(rd)
-        st = eng.stats()
-        one = eng.abundance()
-        print("one call:", st["range_splits"], "splits,", st["rows"], "rows; abundance ms", eng.abundance_ms(), "of", st["ms_total"])
-        assert st["range_splits"] > 0, "the batch did not overflow: the test no longer exercises the halving path"
-        eng.abundance_reset()
-        monkeypatch.setenv("MC_STREAM_BATCH", "5000")
-        rows5, _ = eng.search(rd)
-        monkeypatch.delenv("MC_STREAM_BATCH")
-        st5 = eng.stats()
-        five = eng.abundance()
-        assert st5["range_splits"] == 0 and st5["rows"] == st["rows"] == len(rows5)
-        eng.abundance_reset()
-        monkeypatch.setenv("MC_STREAM_BATCH", "1000000")                  # the same through mc_range_end's -2 and mc_run_range with the rows staying on the device
-        eng.lib.mc_set_keep_rows(eng.h, 0)
-        eng.search(rd)
-        eng.lib.mc_set_keep_rows(eng.h, 1)
-        monkeypatch.delenv("MC_STREAM_BATCH")
-        stay = eng.abundance()
-        assert len(eng.rows()) == 0
-    finally:
-        eng.close()
+    """The marker-dense library (abund_inputs.dense_runs says why 24,000 reads), and the test asserts that it takes the halving path.  The
+    counters must be those of 5,000-read batches (which fit: no split), and the restatement's on that run's own host rows - the one place
+    the code's rows are the yardstick; tests/test_gpu_blindspots.py pins them to the oracle."""
+    cut = I.DENSE_CUT
+    runs = I.dense_runs(monkeypatch, lambda eng: eng.set_abundance(True, **cut), lambda eng: (eng.abundance(), eng.abundance_ms()), stay=True)
+    names, rd, (st, (one, ms)), (st5, (five, _), rows5), ((stay, _), stay_rows) = runs["names"], runs["reads"], runs["one"], runs["five"], runs["stay"]
+    print("one call:", st["range_splits"], "splits,", st["rows"], "rows; abundance ms", ms, "of", st["ms_total"])
+    assert st["range_splits"] > 0, "the batch did not overflow: the test no longer exercises the halving path"
+    assert st5["range_splits"] == 0 and st5["rows"] == st["rows"] == len(rows5)
+    assert stay_rows == 0
     want = R.abundance(R.rows_from_array(rows5), len(names), **cut)
     assert want["assigned"] > 10_000 and one["searched"] == five["searched"] == stay["searched"] == len(rd)
     assert _same(five, want) and _same(one, want) and _same(stay, want)

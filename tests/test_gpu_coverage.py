@@ -6,11 +6,11 @@ import gzip
 import hashlib
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
+import abund_inputs as I
 import abundance_restated as R
 import coverage_restated as V
 
@@ -31,18 +31,12 @@ def _same_counts(got, want):
 
 @pytest.fixture(scope="module")
 def engine():
-    from microbecensus_amd import _native
-    e = _native.Engine(device=0)
-    model = _native.load_model()
-    e.set_run(100, model["pars"]["100"], model["families"])
-    yield e
-    e.close()
+    yield from I.marker_engine()
 
 
 @pytest.fixture(scope="module")
 def reads():
-    seqs = [l.rstrip(b"\r\n") for l in gzip.open(os.path.join(GOLD, CASE + ".reads.fa.gz"), "rb") if not l.startswith(b">")]
-    return np.frombuffer(b"".join(seqs), dtype=np.uint8).reshape(len(seqs), len(seqs[0]))
+    return I.example_reads()
 
 
 @pytest.fixture(scope="module")
@@ -79,19 +73,11 @@ def test_marker_database_equals_the_restatement_of_the_reference_m8(engine, read
 
 def test_generic_database_equals_the_restatement_of_the_reference_m8():
     """18,553 sequences, 20,000 reads, the generic seed path: depths up to 10, subject indices up to 18,552."""
-    sys.path.insert(0, GOLD)
-    import make_generic_db_golden as G
-    from microbecensus_amd import _native
-    meta = json.load(open(os.path.join(GOLD, "generic_db.json")))
-    names, seqs, rd = G.case_inputs()
-    assert hashlib.md5(b"".join(b">%d\n%s\n" % (i, bytes(r)) for i, r in enumerate(rd))).hexdigest() == meta["reads_md5"]
-    lengths = [len(s) for s in seqs]
-    rows = V.rows_from_m8(os.path.join(GOLD, "generic_db.m8.gz"), names)
-    assert len(rows) == meta["m8_rows"]
     mixed = dict(min_ident=50, min_aln=25, min_bits=40.5, max_loge=-2.5)
-    eng = _native.Engine(device=0, names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
-    try:
-        eng.set_run(meta["read_length"])
+    with I.generic_case() as (eng, names, seqs, rd, meta, m8):
+        lengths = [len(s) for s in seqs]
+        rows = V.rows_from_m8(m8, names)
+        assert len(rows) == meta["m8_rows"]
         for cut in (dict(), mixed):
             assert R.cutoffs_clear_of_printed_values(rows, cut.get("min_bits", 0.0), cut.get("max_loge", 1.0))
             want, want_ab = V.coverage(rows, lengths, **cut), R.abundance([r[:6] for r in rows], len(names), **cut)
@@ -104,8 +90,6 @@ def test_generic_database_equals_the_restatement_of_the_reference_m8():
             assert ab["searched"] == len(rd) and _same_counts(ab, want_ab) and _same(got, depth, want)
             assert V.invariants(got, ab["reads"], lengths) == []
         assert want_ab["assigned"] not in (0, meta["reads_with_rows"])                   # (the mixed set cuts)
-    finally:
-        eng.close()
 
 
 def test_coverage_does_not_depend_on_batches_ranges_or_entry_point(engine, reads, golden, tmp_path, monkeypatch):
@@ -186,31 +170,18 @@ def test_a_range_that_overflows_its_pools_marks_once(monkeypatch):
     """The recipe and size of test_gpu_abundance.py's test_a_range_that_overflows_its_pools_counts_once: 24,000 marker-dense reads on an
     engine of their own take the halving path (asserted).  The coverage of the one call must be that of 5,000-read batches (which fit:
     no split) and the restatement's on that run's own host rows."""
-    from microbecensus_amd import _native, synth
-    names, seqs = _native.load_markers()
-    lengths = [len(s) for s in seqs]
-    genome = synth.build_genomes(seqs, total_bp=3_000_000, seed=404, marker_gene_fraction=1.0)
-    rd = synth.sample_reads(genome, 24_000, 150, seed=405)
-    cut = dict(min_ident=40, min_aln=30)
-    eng = _native.Engine(device=0)
-    try:
-        eng.set_run(150)
+    cut = I.DENSE_CUT
+
+    def switches(eng):
         eng.set_abundance(True, **cut)
         eng.set_coverage(True)
-        eng.search(rd)
-        st = eng.stats()
-        one = (eng.coverage(), eng.coverage_depth(), eng.abundance())
-        print("one call:", st["range_splits"], "splits,", st["rows"], "rows; abundance ms", eng.abundance_ms(), "scan ms", eng.coverage_ms(), "of", st["ms_total"])
-        assert st["range_splits"] > 0, "the batch did not overflow: the test no longer exercises the halving path"
-        eng.abundance_reset()
-        monkeypatch.setenv("MC_STREAM_BATCH", "5000")
-        rows5, _ = eng.search(rd)
-        monkeypatch.delenv("MC_STREAM_BATCH")
-        st5 = eng.stats()
-        five = (eng.coverage(), eng.coverage_depth(), eng.abundance())
-        assert st5["range_splits"] == 0 and st5["rows"] == st["rows"] == len(rows5)
-    finally:
-        eng.close()
+    runs = I.dense_runs(monkeypatch, switches, lambda eng: (eng.coverage(), eng.coverage_depth(), eng.abundance(), eng.abundance_ms(), eng.coverage_ms()))
+    names, rd, lengths = runs["names"], runs["reads"], [len(s) for s in runs["seqs"]]
+    (st, one), (st5, five, rows5) = runs["one"], runs["five"]
+    print("one call:", st["range_splits"], "splits,", st["rows"], "rows; abundance ms", one[3], "scan ms", one[4], "of", st["ms_total"])
+    assert st["range_splits"] > 0, "the batch did not overflow: the test no longer exercises the halving path"
+    assert st5["range_splits"] == 0 and st5["rows"] == st["rows"] == len(rows5)
+    one, five = one[:3], five[:3]
     want = V.coverage(V.rows_from_array(rows5), lengths, **cut)
     reads_want = np.bincount([s for s, _, _ in want["best"]], minlength=len(names))
     assert len(want["best"]) > 10_000 and int(want["max_depth"].max()) > 2

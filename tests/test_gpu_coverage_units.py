@@ -1,14 +1,12 @@
 """The coverage kernels (csrc/k_coverage.h) on synthetic rows at the smallest shapes that can go wrong: k_abundance_cov (the counting
-kernel that also marks) and k_coverage_scan, launched by tests/emul/device_coverage.hip with the library's grids - test_gpu_order_units.py's
+kernel that also marks) and k_coverage_scan - and, the small cases once more with coverage off, k_abundance (csrc/k_abundance.h) -,
+launched by tests/emul/device_coverage.hip through the library's launch function (csrc/mc_abund.h) - test_gpu_order_units.py's
 idiom: the harness includes the library's headers and is built here with the library's flags, every case is one child process under a
 time limit of its own, and every comparison is exact, against tests/coverage_restated.py (covered, spanned, max_depth and the depth of
 every residue) and tests/abundance_restated.py (the reads / aligned / assigned counters of the same launch).
 
 A child that ends by a signal, at its time limit or with a HIP error fails its test with its output, and every later test of the
-module then fails at once without starting anything on the GPU."""
-import os
-import subprocess
-
+three unit modules then fails at once without starting anything on the GPU (order_cases.run_child)."""
 import numpy as np
 import pytest
 
@@ -19,35 +17,17 @@ from microbecensus_amd._native import ROW_DTYPE
 
 pytestmark = pytest.mark.gpu
 
-_ABNORMAL = []          # the cases whose child ended abnormally: nothing more is started behind them
 PARS = np.dtype([("min_ident", "<i4"), ("min_aln", "<i4"), ("min_bits", "<f8"), ("max_loge", "<f8")])   # McAbundPars
 assert ROW_DTYPE.itemsize == 72 and PARS.itemsize == 24
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("device_coverage") / "device_coverage")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", oc.CSRC, "-o", exe,
-                           os.path.join(oc.EMUL, "device_coverage.hip")])
-    return exe
+    return oc.harness("device_coverage", tmp_path_factory)
 
 
 def _run(exe, case, arrays, tmp, limit):
-    """One child process under a time limit of its own; returns the sections it wrote."""
-    if _ABNORMAL:
-        pytest.fail("not started: the child of case %s ended abnormally earlier in this module" % _ABNORMAL[0], pytrace=False)
-    oc.write_sections(tmp / (case + ".in"), arrays)
-    cmd = ["timeout", "-k", "10", str(limit), exe, "run", str(tmp / (case + ".in")), str(tmp / (case + ".out"))]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=limit + 30)
-    except subprocess.TimeoutExpired as e:
-        _ABNORMAL.append(case)
-        pytest.fail("%s: no end after %d s\n%s" % (case, limit + 30, e.stdout), pytrace=False)
-    if p.returncode != 0:
-        if p.returncode != 2:                                     # (2: the harness refused its input before anything was launched)
-            _ABNORMAL.append(case)
-        pytest.fail("%s: exit status %d\n%s" % (case, p.returncode, p.stdout), pytrace=False)
-    return oc.read_sections(tmp / (case + ".out"))
+    return oc.run_child(exe, case, arrays, tmp, limit, "run")
 
 
 def _rows(spec):
@@ -61,28 +41,39 @@ def _rows(spec):
     return arr
 
 
-def _check(exe, case, tmp, lengths, rows, cut=None):
-    """Runs the case and compares everything with the restatements; returns the restated coverage (for the case's own conditions)."""
+def _padding_untouched(out):
+    """nothing was written behind any array: tab's and the difference array's padding still zero, the figures' and the depth's still 0xFF"""
+    assert len(out) == 11 and len(out[8]) == len(out[9]) == 64
+    assert not np.frombuffer(out[5], "<u8").any() and not np.frombuffer(out[10], "<u4").any(), "a write behind tab or the difference array"
+    assert all(np.all(np.frombuffer(out[k], "u1") == 0xFF) for k in (6, 7, 8, 9)), "a write behind the figures or the depth"
+
+
+def _counters(tab, ab, nseq, assigned):
+    assert np.array_equal(tab[0:2 * nseq:2], ab["reads"][:nseq].astype(np.uint64)) and np.array_equal(tab[1:2 * nseq:2], ab["aligned"][:nseq].astype(np.uint64)), "reads / aligned"
+    assert int(tab[2 * nseq]) == int(ab["reads"][:nseq].sum()) == assigned and int(tab[2 * nseq + 1]) == 0, "assigned"
+
+
+def _check(exe, case, tmp, lengths, rows, cut=None, without=True):
+    """Runs the case and compares everything with the restatements; returns the restated coverage (for the case's own conditions).
+    without: the case once more with the harness's coverage switch off - k_abundance instead of k_abundance_cov through the same launch
+    function: the counters are abundance_restated's, the padding is untouched and the difference array, which no kernel was handed,
+    holds nothing."""
     cut = cut or {}
     pars = np.zeros(1, PARS)
     pars[0] = (cut.get("min_ident", 0), cut.get("min_aln", 0), cut.get("min_bits", 0.0), cut.get("max_loge", 1.0))
     off = np.zeros(len(lengths) + 1, np.uint32)
     off[1:] = np.cumsum(lengths)
-    out = _run(exe, case, [pars, off, rows], tmp, 60)
+    out = _run(exe, case, [pars, off, rows, np.int32([1])], tmp, 60)
     nseq = len(lengths)
     tab, fig, depth, fig2, diff = (np.frombuffer(out[0], "<u8"), np.frombuffer(out[1], "<u8").reshape(nseq, 3), np.frombuffer(out[2], "<u4"),
                                    np.frombuffer(out[3], "<u8").reshape(nseq, 3), np.frombuffer(out[4], "<u4"))
-    # nothing was written behind any array: tab's and the difference array's padding still zero, the figures' and the depth's still 0xFF
-    assert not np.frombuffer(out[5], "<u8").any() and not np.frombuffer(out[10], "<u4").any(), "a write behind tab or the difference array"
-    assert all(np.all(np.frombuffer(out[k], "u1") == 0xFF) for k in (6, 7, 8, 9)), "a write behind the figures or the depth"
-    assert len(out[8]) == len(out[9]) == 64 and len(out) == 11
+    _padding_untouched(out)
     inside = rows[(rows["subject"] >= 0) & (rows["subject"] < nseq)]     # (the restatements index by subject: what the kernel ignores is left out below)
     want = V.coverage(V.rows_from_array(rows), lengths, **cut)
     ab = R.abundance([r for r in R.rows_from_array(rows)], nseq + int(max(0, rows["subject"].max() - nseq + 1)) if len(rows) else nseq, **cut)
     print("%s: %d genes, %d rows (%d with a subject of the database), %d best rows, covered %d, spanned %d, max depth %d" % (
         case, nseq, len(rows), len(inside), len(want["best"]), int(want["covered"].sum()), int(want["spanned"].sum()), int(want["max_depth"].max())))
-    assert np.array_equal(tab[0:2 * nseq:2], ab["reads"][:nseq].astype(np.uint64)) and np.array_equal(tab[1:2 * nseq:2], ab["aligned"][:nseq].astype(np.uint64)), "reads / aligned"
-    assert int(tab[2 * nseq]) == int(ab["reads"][:nseq].sum()) == len(want["best"]) and int(tab[2 * nseq + 1]) == 0, "assigned"
+    _counters(tab, ab, nseq, len(want["best"]))
     assert np.array_equal(depth, want["depth"]), "depth: first difference at residue %d" % int(np.flatnonzero(depth != want["depth"])[0])
     for k, name in enumerate(("covered", "spanned", "max_depth")):
         assert np.array_equal(fig[:, k], want[name].astype(np.uint64)), name
@@ -92,6 +83,11 @@ def _check(exe, case, tmp, lengths, rows, cut=None):
     ends_at_last = np.bincount([s for s, a, b in want["best"] if b == lengths[s] - 1], minlength=nseq)
     assert np.array_equal(diff[first + np.asarray(lengths)], (-ends_at_last).astype(np.uint32)), "sentinels"
     assert V.invariants(want, ab["reads"][:nseq], lengths) == []
+    if without:
+        out = _run(exe, case + "_without", [pars, off, rows, np.int32([0])], tmp, 60)
+        _padding_untouched(out)
+        _counters(np.frombuffer(out[0], "<u8"), ab, nseq, len(want["best"]))
+        assert len(out[1]) == len(out[2]) == len(out[3]) == 0 and len(out[4]) == 4 * (sum(lengths) + nseq) and not np.frombuffer(out[4], "<u4").any(), "the difference array"
     return want
 
 
@@ -125,6 +121,14 @@ def test_gene_counts(harness, tmp_path, nseq):
     assert (want["covered"] > 0).all()
 
 
+@pytest.mark.parametrize("nrows", [1, 256, 257])
+def test_row_counts(harness, tmp_path, nrows):
+    """1, 256 and 257 rows, one read each: one thread, exactly one workgroup, one row into the second.  Time limit 60 s."""
+    lengths = [40, 64, 9]
+    want = _check(harness, "rows%d" % nrows, tmp_path, lengths, _rows([(q, q % 3, q % 9, q % 9) for q in range(nrows)]))
+    assert len(want["best"]) == nrows and int(want["spanned"].sum()) == nrows
+
+
 def test_sentinel_isolation(harness, tmp_path):
     """A gene whose only span ends at len - 1, directly followed by a gene whose only span starts at 0 - and the same at a chunk's
     end (64 residues).  Time limit 60 s."""
@@ -140,7 +144,7 @@ def test_depth_past_16_bits(harness, tmp_path):
     rows[:] = _rows([(0, 1, 3, 70)])[0]
     rows["query"] = np.arange(n + 2)
     rows["subject"][n:] = (0, 2)
-    want = _check(harness, "deep", tmp_path, [80, 100, 90], rows)
+    want = _check(harness, "deep", tmp_path, [80, 100, 90], rows, without=False)
     assert want["max_depth"].tolist() == [1, n, 1] and want["spanned"].tolist() == [68, 68 * n, 68] and want["covered"].tolist() == [68, 68, 68]
 
 

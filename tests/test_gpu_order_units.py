@@ -5,10 +5,7 @@ depth limit.  tests/emul/device_order.hip includes the library's kernel headers 
 case is one child process, and every comparison is exact (the outputs are permutations, counts and copied records).
 
 A child that ends by a signal, at its time limit or with a HIP error fails its test with its output, and every later test of the
-module then fails at once without starting anything on the GPU."""
-import os
-import subprocess
-
+three unit modules then fails at once without starting anything on the GPU (order_cases.run_child)."""
 import numpy as np
 import pytest
 
@@ -16,33 +13,14 @@ import order_cases as oc
 
 pytestmark = pytest.mark.gpu
 
-_ABNORMAL = []          # the cases whose child ended abnormally: nothing more is started behind them
-
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("device_order") / "device_order")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", oc.CSRC, "-o", exe,
-                           os.path.join(oc.EMUL, "device_order.hip")])
-    return exe
+    return oc.harness("device_order", tmp_path_factory)
 
 
 def _run(exe, case, arrays, tmp, limit):
-    """One child process under a time limit of its own; returns the sections it wrote."""
-    if _ABNORMAL:
-        pytest.fail("not started: the child of case %s ended abnormally earlier in this module" % _ABNORMAL[0], pytrace=False)
-    oc.write_sections(tmp / (case + ".in"), arrays)
-    cmd = ["timeout", "-k", "10", str(limit), exe, case, str(tmp / (case + ".in")), str(tmp / (case + ".out"))]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=limit + 30)
-    except subprocess.TimeoutExpired as e:
-        _ABNORMAL.append(case)
-        pytest.fail("%s: no end after %d s\n%s" % (case, limit + 30, e.stdout), pytrace=False)
-    if p.returncode != 0:
-        if p.returncode != 2:                                     # (2: the harness refused its input before anything was launched)
-            _ABNORMAL.append(case)
-        pytest.fail("%s: exit status %d\n%s" % (case, p.returncode, p.stdout), pytrace=False)
-    return oc.read_sections(tmp / (case + ".out"))
+    return oc.run_child(exe, case, arrays, tmp, limit)
 
 
 @pytest.fixture(scope="module")

@@ -8,11 +8,11 @@ import gzip
 import hashlib
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
+import abund_inputs as I
 import abundance_restated as R
 import coverage_restated as V
 import ties_restated as T
@@ -34,18 +34,12 @@ def _same_any(got, want):
 
 @pytest.fixture(scope="module")
 def engine():
-    from microbecensus_amd import _native
-    e = _native.Engine(device=0)
-    model = _native.load_model()
-    e.set_run(100, model["pars"]["100"], model["families"])
-    yield e
-    e.close()
+    yield from I.marker_engine()
 
 
 @pytest.fixture(scope="module")
 def reads():
-    seqs = [l.rstrip(b"\r\n") for l in gzip.open(os.path.join(GOLD, CASE + ".reads.fa.gz"), "rb") if not l.startswith(b">")]
-    return np.frombuffer(b"".join(seqs), dtype=np.uint8).reshape(len(seqs), len(seqs[0]))
+    return I.example_reads()
 
 
 @pytest.fixture(scope="module")
@@ -90,20 +84,12 @@ def test_marker_database_equals_the_restatement_of_the_reference_m8(engine, read
 def test_generic_database_equals_the_restatement_of_the_reference_m8():
     """18,553 sequences, 20,000 reads, the generic seed path: 22 ambiguous reads, four reads that tie with the same subject twice, 316
     reads whose top score is not in their first row."""
-    sys.path.insert(0, GOLD)
-    import make_generic_db_golden as G
-    from microbecensus_amd import _native
-    meta = json.load(open(os.path.join(GOLD, "generic_db.json")))
-    names, seqs, rd = G.case_inputs()
-    assert hashlib.md5(b"".join(b">%d\n%s\n" % (i, bytes(r)) for i, r in enumerate(rd))).hexdigest() == meta["reads_md5"]
-    lengths = [len(s) for s in seqs]
-    rows = V.rows_from_m8(os.path.join(GOLD, "generic_db.m8.gz"), names)
-    assert len(rows) == meta["m8_rows"]
-    group_of = (np.arange(len(names)) // 50).astype(np.int32)
-    ngroups = int(group_of.max()) + 1
-    eng = _native.Engine(device=0, names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
-    try:
-        eng.set_run(meta["read_length"])
+    with I.generic_case() as (eng, names, seqs, rd, meta, m8):
+        lengths = [len(s) for s in seqs]
+        rows = V.rows_from_m8(m8, names)
+        assert len(rows) == meta["m8_rows"]
+        group_of = (np.arange(len(names)) // 50).astype(np.int32)
+        ngroups = int(group_of.max()) + 1
         for cut in CUTS:
             assert R.cutoffs_clear_of_printed_values(rows, cut.get("min_bits", 0.0), cut.get("max_loge", 1.0))
             want, want_ab = T.ties(rows, lengths, group_of, ngroups, **cut), R.abundance([r[:6] for r in rows], len(names), **cut)
@@ -119,8 +105,6 @@ def test_generic_database_equals_the_restatement_of_the_reference_m8():
             assert T.invariants(got, ab["reads"], ab["assigned"], group_of) == []
             if not cut:
                 assert got["ambiguous"] == 22
-    finally:
-        eng.close()
 
 
 def test_counters_do_not_depend_on_ranges_or_entry_point(engine, reads, golden, tmp_path):
@@ -229,42 +213,24 @@ def test_a_range_that_overflows_its_pools_adds_once(monkeypatch):
     """The recipe and size of test_gpu_abundance.py's test_a_range_that_overflows_its_pools_counts_once: 24,000 marker-dense reads on an
     engine of their own take the halving path (asserted) - also with the rows staying on the device.  The tie counters of the one call
     must be those of 5,000-read batches (which fit: no split) and the restatement's on that run's own host rows."""
-    from microbecensus_amd import _native, abundance, synth
+    from microbecensus_amd import _native, abundance
     names, seqs = _native.load_markers()
     lengths = [len(s) for s in seqs]
     group_of, gnames = abundance.group_ids(names, {n: n.split("_")[0] for n in names})     # every gene in its family's group
     ngroups = len(gnames)
-    genome = synth.build_genomes(seqs, total_bp=3_000_000, seed=404, marker_gene_fraction=1.0)
-    rd = synth.sample_reads(genome, 24_000, 150, seed=405)
-    cut = dict(min_ident=40, min_aln=30)
-    eng = _native.Engine(device=0)
-    try:
-        eng.set_run(150)
+    cut = I.DENSE_CUT
+
+    def switches(eng):
         eng.set_abundance(True, **cut)
         eng.set_coverage(True)
         eng.set_ties(True, group_of, ngroups)
-        eng.search(rd)
-        st = eng.stats()
-        one = (eng.ties(), eng.ties_coverage(), eng.abundance())
-        print("one call:", st["range_splits"], "splits,", st["rows"], "rows; abundance ms", eng.abundance_ms(), "ties ms", eng.ties_ms(), "of", st["ms_total"])
-        assert st["range_splits"] > 0, "the batch did not overflow: the test no longer exercises the halving path"
-        eng.abundance_reset()
-        monkeypatch.setenv("MC_STREAM_BATCH", "5000")
-        rows5, _ = eng.search(rd)
-        monkeypatch.delenv("MC_STREAM_BATCH")
-        st5 = eng.stats()
-        five = (eng.ties(), eng.ties_coverage(), eng.abundance())
-        assert st5["range_splits"] == 0 and st5["rows"] == st["rows"] == len(rows5)
-        eng.abundance_reset()
-        monkeypatch.setenv("MC_STREAM_BATCH", "1000000")                  # the same through mc_range_end's -2 and mc_run_range with the rows staying on the device
-        eng.lib.mc_set_keep_rows(eng.h, 0)
-        eng.search(rd)
-        eng.lib.mc_set_keep_rows(eng.h, 1)
-        monkeypatch.delenv("MC_STREAM_BATCH")
-        stay = (eng.ties(), eng.ties_coverage(), eng.abundance())
-        assert len(eng.rows()) == 0
-    finally:
-        eng.close()
+    runs = I.dense_runs(monkeypatch, switches, lambda eng: (eng.ties(), eng.ties_coverage(), eng.abundance(), eng.abundance_ms(), eng.ties_ms()), stay=True)
+    rd, (st, one), (st5, five, rows5), (stay, stay_rows) = runs["reads"], runs["one"], runs["five"], runs["stay"]
+    print("one call:", st["range_splits"], "splits,", st["rows"], "rows; abundance ms", one[3], "ties ms", one[4], "of", st["ms_total"])
+    assert st["range_splits"] > 0, "the batch did not overflow: the test no longer exercises the halving path"
+    assert st5["range_splits"] == 0 and st5["rows"] == st["rows"] == len(rows5)
+    assert stay_rows == 0
+    one, five, stay = one[:3], five[:3], stay[:3]
     want = T.ties(V.rows_from_array(rows5), lengths, group_of, ngroups, **cut)
     print("restated:", len(want["k"]), "reads,", want["ambiguous"], "ambiguous, largest tied set", max(want["k"]))
     assert len(want["k"]) > 10_000 and want["ambiguous"] > 100

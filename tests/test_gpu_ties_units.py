@@ -6,10 +6,7 @@ against tests/ties_restated.py (every counter, the any-depth of every residue an
 are those of tests/ties_cases.py, which test_ties_host.py runs through the same walk on the CPU.
 
 A child that ends by a signal, at its time limit or with a HIP error fails its test with its output, and every later test of the
-module then fails at once without starting anything on the GPU."""
-import os
-import subprocess
-
+three unit modules then fails at once without starting anything on the GPU (order_cases.run_child)."""
 import numpy as np
 import pytest
 
@@ -18,34 +15,16 @@ import ties_cases as tc
 
 pytestmark = pytest.mark.gpu
 
-_ABNORMAL = []          # the cases whose child ended abnormally: nothing more is started behind them
 ONE = 1 << 32
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("device_ties") / "device_ties")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", oc.CSRC, "-o", exe,
-                           os.path.join(oc.EMUL, "device_ties.hip")])
-    return exe
+    return oc.harness("device_ties", tmp_path_factory)
 
 
 def _run(exe, case, arrays, tmp, limit):
-    """One child process under a time limit of its own; returns the sections it wrote."""
-    if _ABNORMAL:
-        pytest.fail("not started: the child of case %s ended abnormally earlier in this module" % _ABNORMAL[0], pytrace=False)
-    oc.write_sections(tmp / (case + ".in"), arrays)
-    cmd = ["timeout", "-k", "10", str(limit), exe, "run", str(tmp / (case + ".in")), str(tmp / (case + ".out"))]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=limit + 30)
-    except subprocess.TimeoutExpired as e:
-        _ABNORMAL.append(case)
-        pytest.fail("%s: no end after %d s\n%s" % (case, limit + 30, e.stdout), pytrace=False)
-    if p.returncode != 0:
-        if p.returncode != 2:                                     # (2: the harness refused its input before anything was launched)
-            _ABNORMAL.append(case)
-        pytest.fail("%s: exit status %d\n%s" % (case, p.returncode, p.stdout), pytrace=False)
-    return oc.read_sections(tmp / (case + ".out"))
+    return oc.run_child(exe, case, arrays, tmp, limit, "run")
 
 
 def _check(exe, name, c, tmp):
@@ -53,10 +32,10 @@ def _check(exe, name, c, tmp):
     want = tc.expected(name, c)
     t, ab, cv = want
     out = _run(exe, name, tc.sections_in(c), tmp, 60)
-    assert len(out) == 12
+    assert len(out) == 10
     nseq, nres = len(c["lengths"]), sum(c["lengths"])
-    # nothing was written behind any array
-    assert all(not np.frombuffer(out[k], "u1").any() for k in (7, 8, 9, 10, 11)), "a write behind a table, the shares, group_unique or a difference array"
+    # nothing was written behind any array (the tie table is ONE array, as in the library: its parts are compared counter by counter below)
+    assert all(len(out[k]) >= 128 and not np.frombuffer(out[k], "u1").any() for k in (7, 8, 9)), "a write behind the count table, the tie table or a difference array"
     tab = np.frombuffer(out[0], "<u8")
     reads = ab["reads"][:nseq]
     print("%s: %d genes, %d rows, %d reads assigned, %d ambiguous, %d across groups, largest tied set %d, sum of candidates %d" % (
