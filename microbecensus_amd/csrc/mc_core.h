@@ -1443,7 +1443,10 @@ MC_HDN McGapResult mc_align_gapped(const TT &T, const uint8_t *s1, int st1, cons
 //   plane of a cell written by row 0 or by the right growth, whose "D path" is the cell's E path (PD = PH there): only the left
 //   border of a later row can continue such a cell (an in-band cell over it has main - first = D - ext: a tie, which opens), so
 //   those cells carry a flag (MC_PD_GROW) that the border looks at.
-// * Scores in 16 bits: |score| <= 11 * 170 + 64.
+// * Scores in a signed 12-bit field (mc_gap_pack; the H word of a cell is sign-extended from 12 bits by mc_gap_unpack and by the
+//   accessors' loadH): a flank has at most MC_MAXAA - 1 = 169 residues and a substitution gains at most 11, so H <= 11 * 169 = 1859,
+//   and 11 * 169 + 64 < 2048; from below, a cell that is written lies at most one step (open + ext + the worst substitution, under
+//   64 together) under a cell within xdrop_gapped of best >= 0, and row 0 ends at -open - jEnd * ext = -26: H > -2048.
 // * The subject residue of a column travels with the column's cell (read from memory once, when the column enters the band):
 //   bits 24..28 of the PD word.
 // WS: load(slot, H, D, PH, PD) / store(slot, H, D, PH, PD) / loadH(slot), slot = 0 .. W-1 (the accessor owns the layout).
@@ -1451,6 +1454,7 @@ MC_HDN McGapResult mc_align_gapped(const TT &T, const uint8_t *s1, int st1, cons
 // The extension is a state machine - mc_gap_begin (row 0), mc_gap_row (one DP row), mc_gap_result - so that a GPU lane can take
 // the next flank the moment its own ends (k_gapped_lds); mc_align_gapped_win runs it to the end for one flank.
 // ---------------------------------------------------------------------------------------------
+static_assert(11 * (MC_MAXAA - 1) + 64 < 2048, "a cell's score must fit the signed 12-bit field of mc_gap_pack");
 #define MC_PP_RUN 0x10000u
 #define MC_PD_GROW 0x80000000u
 #define MC_PD_YMASK 0x1F000000u

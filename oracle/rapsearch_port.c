@@ -640,8 +640,9 @@ static void tr_push(trace_t *t, char mode)
 }
 
 static int align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2,
-                        int *c1, int *c2, int *ident, trace_t *tr)
-{
+                        int *c1, int *c2, int *ident, trace_t *tr, int *width)
+{ /* width (optional, two ints): [0] the widest live band, the largest j - (jStart - 1) over the cells written (row 0: jStart = 1);
+   * [1] the DP rows that were run */
     const int open = GAP_OPEN, ext = GAP_EXT, first = GAP_OPEN + GAP_EXT;
     int *H = (int *)malloc(sizeof(int) * (size_t)(n2 + 2)), *D = (int *)malloc(sizeof(int) * (size_t)(n2 + 2));
     size_t W = (size_t)n2 + 2;
@@ -652,12 +653,14 @@ static int align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2
 #define PE(i, j) pe[(size_t)(i) * W + (size_t)(j)]
 #define PD(i, j) pd[(size_t)(i) * W + (size_t)(j)]
     *c1 = *c2 = *ident = 0; tr->n = 0;
+    if (width) width[0] = width[1] = 0;
+#define WIDE(j) do { if (width && (j) - (jStart - 1) > *width) *width = (j) - (jStart - 1); } while (0)
     H[0] = 0; D[0] = -open;
     PM(0, 0) = '0';
     if (n2 > 0 && jEnd > 0) { /* 0x40a6c1-0x40a770 */
         r = -open;
         for (j = 1;; ) {
-            r -= ext; H[j] = r; D[j] = r - open;
+            r -= ext; H[j] = r; D[j] = r - open; WIDE(j);
             if (j == 1) { PM(0, j) = 'E'; PE(0, j) = 'E'; } else { PM(0, j) = 'e'; PE(0, j) = 'e'; }
             PD(0, j) = 'D';
             j++;
@@ -686,7 +689,7 @@ static int align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2
                 if (E > h) { PM(i, j) = te; h = E; }
                 if (h < Dn) { PM(i, j) = td; h = Dn; }
                 PE(i, j) = te; PD(i, j) = td;
-                diag = H[j]; H[j] = h; D[j] = Dn;
+                diag = H[j]; H[j] = h; D[j] = Dn; WIDE(j);
                 hprev = h;
                 if (h > best) { best = h; bestI = i; bestJ = j; }
                 else if ((double)best - T_XGAP > (double)h && j > bestJ) {
@@ -704,7 +707,7 @@ static int align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2
                 int a = hprev - first, b = E - ext;
                 if (a > b) { E = a; te = 'E'; } else { E = b; te = 'e'; }
                 PM(i, j) = te; PE(i, j) = te;
-                H[j] = E; D[j] = E - open;
+                H[j] = E; D[j] = E - open; WIDE(j);
                 if (E > best) { best = E; bestI = i; bestJ = j; }
                 else if ((double)best - T_XGAP > (double)E) { jEnd = j; break; }
                 hprev = E;
@@ -718,6 +721,7 @@ static int align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2
                 for (;;) { k--; if (jStart > k) break; if (lim > (double)H[k]) { jStart = k; break; } }
             }
         }
+        if (width) width[1] = i;
         i++; /* 0x40a9fa-0x40aa1b */
         if (n1 < i) break;
         if (!(jStart < jEnd)) break;
@@ -742,6 +746,22 @@ done:
 #undef PM
 #undef PE
 #undef PD
+#undef WIDE
+}
+
+/* AlignGapped on one pair of flanks, for the unit tests of the gapped kernels: returns the gain; out = c1, c2, ident, steps (the sum
+ * of the trace's run lengths), runs (the non-'s' runs), gapcols (their summed lengths) - as align_and_record derives them - width,
+ * and the number of DP rows that were run. */
+int rs_align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2, int out[8])
+{
+    trace_t tr = {NULL, NULL, 0, 0};
+    int g, i;
+    init_tables();
+    for (i = 0; i < 8; i++) out[i] = 0;
+    g = align_gapped(seq1, seq2, n1, n2, &out[0], &out[1], &out[2], &tr, &out[6]);
+    for (i = 0; i < tr.n; i++) { out[3] += tr.l[i]; if (tr.m[i] != 's') { out[4]++; out[5] += tr.l[i]; } }
+    free(tr.m); free(tr.l);
+    return g;
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -854,7 +874,7 @@ static void align_and_record(qstate *qs, int frame, const uint8_t *q, int qlen, 
         int qend = qfwd + qpos + L, dend = dfwd + dpos + L;
         int dright = dlen - dend, qright = qlen - qend, c1, c2, id, g;
         if (dright > 2 && qright > 2) {
-            g = align_gapped(q + qend, d + dend, qright, dright, &c1, &c2, &id, &qs->tr_r);
+            g = align_gapped(q + qend, d + dend, qright, dright, &c1, &c2, &id, &qs->tr_r, NULL);
             if (g > 0) { score += g; nmatch += id; qfwd += c1; dfwd += c2; nr = qs->tr_r.n; }
         }
         {
@@ -864,7 +884,7 @@ static void align_and_record(qstate *qs, int frame, const uint8_t *q, int qlen, 
                 if (need > qs->revcap) { qs->revcap = need * 2; qs->rev1 = (uint8_t *)realloc(qs->rev1, (size_t)qs->revcap); qs->rev2 = (uint8_t *)realloc(qs->rev2, (size_t)qs->revcap); }
                 for (i = 0; i < qleft; i++) qs->rev1[i] = q[qleft - 1 - i];
                 for (i = 0; i < dleft; i++) qs->rev2[i] = d[dleft - 1 - i];
-                g = align_gapped(qs->rev1, qs->rev2, qleft, dleft, &c1, &c2, &id, &qs->tr_l);
+                g = align_gapped(qs->rev1, qs->rev2, qleft, dleft, &c1, &c2, &id, &qs->tr_l, NULL);
                 if (g > 0) { score += g; nmatch += id; qbwd += c1; dbwd += c2; nl = qs->tr_l.n; }
             }
         }

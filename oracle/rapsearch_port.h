@@ -55,6 +55,11 @@ int rs_search_read(const rs_db *db, int query_index, const char *seq, int len,
  * length.  out[f] must hold len/3+1 bytes. (BuildQHash@0x40b530, Seg::maskseq@0x43ade0) */
 void rs_translate6(const char *seq, int len, uint8_t *out[6], int lens[6]);
 
+/* AlignGapped@0x40a550 on one pair of flanks (residue codes as rs_translate6 writes them; a left flank is passed reversed).
+ * Returns the gain; out = c1, c2, ident, steps, runs, gapcols, width (the widest live band: the largest j - (jStart - 1) over
+ * the cells written), the DP rows that were run. */
+int rs_align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2, int out[8]);
+
 /* Format one row the way the binary does (ostream default %g precision, tab separated). */
 int rs_format_row(const rs_db *db, const rs_row *r, const char *qname, char *buf, int buflen);
 

@@ -154,6 +154,40 @@ def test_a_flank_with_32_gap_runs_reaches_full_size_rows_in_the_product_library(
     assert max(r[4] for r in rows) >= 32
 
 
+def test_flanks_wider_than_64_columns_reach_full_size_rows_in_the_product_library(sets, tmp_path):
+    """The product's own windows, the route by width: six reads against a database of six synthetic subjects
+    (gapped_cases.wide_witness - 30 shared residues, then flanks whose band is 70 columns wide or wider by the oracle's AlignGapped;
+    high-complexity residues, SEG masks none of them).  The emulation counts 6 distinct flanks, all 6 through the second window
+    to full-size rows; the device counts the same, and the rows are the oracle's on a database prerapsearch-formatted from the same
+    subjects.  With the read above this is all the work k_gapped gets in the product build: that one by run count, these by width.
+    (Measured on the MI355X: 1.2 s.)"""
+    import gapped_cases as gc
+    from microbecensus_amd import _native
+    names, seqs, reads = gc.wide_witness()
+    faa, fa = tmp_path / "wide.faa", tmp_path / "wide.fa"
+    faa.write_text("".join(">%s\n%s\n" % ns for ns in zip(names, seqs)))
+    fa.write_bytes(b"".join(b">%d\n%s\n" % (i, bytes(r)) for i, r in enumerate(reads)))
+    (d, r1, r2), (_, _, differ) = run_gapped_chain(sets.exe, faa, fa, tmp_path / "e.m8", 36, 64)
+    want = {"flanks": d, "second_window": r1, "full_size": r2}
+    assert differ == 0 and r2 >= len(reads)
+    _native.rapdb_write(names, seqs, str(tmp_path / "rapdb_2.15"))
+    oracle = _oracle_rows(reads, ref_dir=str(tmp_path))
+    assert len(oracle) >= len(reads)
+    eng = _native.Engine(device=0, names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
+    try:
+        eng.set_run(reads.shape[1])
+        eng.upload(reads)
+        eng.run_range(0, len(reads))
+        st, got = eng.stats(), eng.gap_counts()
+        rows = _rows(eng.rows())
+    finally:
+        eng.close()
+    print("device", got, "emulation", want)
+    assert st["range_splits"] == 0
+    assert_rows_equal(rows, oracle)
+    assert got == want and got["full_size"] > 0
+
+
 _SMALL_WORKER = r"""
 import hashlib, json, os, sys
 sys.path.insert(0, sys.argv[1])
