@@ -153,19 +153,27 @@ int mc_run_range(mc_handle *h, int64_t first, int64_t count, int64_t first_read_
  * way, bench.py its steps.  mc_range_end() returns -2 when the range overflowed a pool: it is then no longer in flight - give
  * it to mc_run_range(), which runs it in smaller pieces.  mc_run_range() and mc_search*() refuse to run while a range is in
  * flight.  Results never depend on any of this.
- * Looking ahead: the ordering and finishing kernels of a range leave the device nearly empty, and the translation of the NEXT range
- * needs nothing of this one.  mc_range_end() therefore issues, behind the range's gapped stage and on a stream of its own, the
- * translation of the range it expects next: the one that follows contiguously in the same resident read set - first + count, up to
- * count reads, clipped to the set, nothing at its end - which is how mc_search(), mc_search_files() and bench.py walk a set.  An
+ * Looking ahead: the translation of the NEXT range needs nothing of this one, and it needs the vector ALUs where the seed search and
+ * the seed evaluation wait for memory.  mc_range_begin() therefore issues, on a stream of its own and into the second of two frame
+ * buffers, the translation of the range it expects next, which runs beside the front of its own range: the one that follows
+ * contiguously in the same resident read set - first + count, up to
+ * count reads, clipped to the set, nothing at its end - which is how bench.py and a caller's own stream of ranges walk a set.
+ * (mc_search(), mc_search_files() and the calls on reads of mixed lengths know their next range only when the running one ends:
+ * theirs is issued by that end, behind the gapped stage, beside the ordering and finishing kernels.)  An
  * mc_range_begin() / mc_run_range() of that range, or of fewer reads from the same first read, with the same resident reads, read
  * length and tables, finds its frames there and starts with the seed kernel; any other range waits for the lookahead's kernel and
  * translates itself.  A wrong guess costs one translation beside work the device was waiting through anyway and never changes a
  * result; whatever replaces reads, tables or pools, mc_debug_stage() and mc_close() wait for a lookahead and discard it.
- * mc_run_range() issues none.  mc_ranges_translated_ahead(): the ranges begun since mc_open() that used a lookahead. */
+ * mc_run_range() issues none.  mc_ranges_translated_ahead(): the ranges begun since mc_open() that used a lookahead.
+ * mc_stats.ms_translate is a figure of the range's own stream: its own translation (all of it, or the reads behind a lookahead's) plus
+ * the time its stream waited for a lookahead's kernel to end, so that the six ms_* stages add up to ms_total.  mc_ahead_kernel_ms():
+ * the interval of the lookahead's kernel that the range which ended last used, between its own two events, in the background of the
+ * range before it - 0 where the range used none (tools/ahead_trace.py). */
 int mc_range_begin(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id);
 int mc_range_end(mc_handle *h);
 int mc_ranges_in_flight(const mc_handle *h);
 int64_t mc_ranges_translated_ahead(const mc_handle *h);
+float mc_ahead_kernel_ms(const mc_handle *h);
 
 /* Test aid (tests/test_gpu_parity.py, per-stage parity with the CPU emulation of the kernels' per-thread code): what the stages of
  * the last mc_run_range() left on the device - what = 0: the six translated, SEG-masked frames of every read (rows of

@@ -113,6 +113,8 @@ def load_library():
     lib.mc_ranges_in_flight.argtypes = [C.c_void_p]
     lib.mc_ranges_translated_ahead.restype = C.c_int64
     lib.mc_ranges_translated_ahead.argtypes = [C.c_void_p]
+    lib.mc_ahead_kernel_ms.restype = C.c_float
+    lib.mc_ahead_kernel_ms.argtypes = [C.c_void_p]
     lib.mc_result_rows.restype = C.c_int64
     lib.mc_result_rows.argtypes = [C.c_void_p, C.POINTER(C.POINTER(McRow))]
     lib.mc_result_best_hits.restype = C.c_int64
@@ -238,7 +240,7 @@ def load_library():
 
 
 EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "mc_set_index_cache", "mc_index_cache_check", "mc_open_rapdb", "mc_marker_count", "mc_marker_name", "mc_set_families", "mc_rapdb_verify", "mc_rapdb_write", "mc_index_view", "mc_set_run", "mc_search", "mc_search_varlen",
-                    "mc_upload", "mc_attach", "mc_run", "mc_run_range", "mc_set_counting", "mc_debug_stage", "mc_range_begin", "mc_range_end", "mc_ranges_in_flight", "mc_ranges_translated_ahead", "mc_result_rows", "mc_result_best_hits", "mc_result_stats", "mc_write_m8", "mc_write_m8_named",
+                    "mc_upload", "mc_attach", "mc_run", "mc_run_range", "mc_set_counting", "mc_debug_stage", "mc_range_begin", "mc_range_end", "mc_ranges_in_flight", "mc_ranges_translated_ahead", "mc_ahead_kernel_ms", "mc_result_rows", "mc_result_best_hits", "mc_result_stats", "mc_write_m8", "mc_write_m8_named",
                     "mc_reader_last_error", "mc_set_host_threads", "mc_reader_open", "mc_reader_open_range", "mc_reader_open_bz2_part", "mc_bz2_blocks", "mc_gz_chunks", "mc_reader_open_gz_part", "mc_reader_gz_provide", "mc_reader_gz_end_state", "mc_reader_gz_finish", "mc_reader_run", "mc_reader_reads", "mc_reader_get_stats", "mc_reader_times", "mc_reader_describe", "mc_dupset_open", "mc_dupset_close", "mc_dupset_walk", "mc_reader_take", "mc_reader_close", "mc_reader_trim", "mc_count_bases", "mc_quality_offset",
                     "mc_reader_start", "mc_reader_fetch", "mc_reader_join", "mc_reader_read_len", "mc_reader_nreads", "mc_search_files", "mc_search_files_multi", "mc_set_keep_rows", "mc_set_best_hits_only", "mc_grid_classify", "mc_bootstrap", "mc_bootstrap_ms",
                     "mc_fit_weights", "mc_weights_mue", "mc_fit_weights_ms",
@@ -1009,8 +1011,12 @@ class Engine:
         return self.lib.mc_ranges_in_flight(self.h)
 
     def ranges_translated_ahead(self):
-        """The ranges begun since the engine was opened whose translation range_end() of the range before had issued ahead."""
+        """The ranges begun since the engine was opened whose translation had been issued ahead, in the background of the range before."""
         return int(self.lib.mc_ranges_translated_ahead(self.h))
+
+    def ahead_kernel_ms(self):
+        """The interval (ms) of the lookahead's kernel that the range which ended last used; 0 where it used none."""
+        return float(self.lib.mc_ahead_kernel_ms(self.h))
 
     def run_range(self, first, count, first_read_id=0):
         self._check(self.lib.mc_run_range(self.h, first, count, first_read_id), "mc_run_range")

@@ -52,10 +52,16 @@
 struct McCtx {
     McStream stream; hipStream_t side = nullptr, side2 = nullptr;   // the pipeline of a range, and two side streams of the ordering / finishing kernels (borrowed: the handle's)
     McEvent ev[8], ev_fork, ev_join, ev_join2;
+    McEvent ev_wait[2]; bool waited = false;                       // around the stream's wait for a lookahead's kernel (range_begin); waited: this range's stream had one
     int64_t cap_reads = 0; int pool_len = 0;                       // the pools hold cap_reads reads of up to pool_len bases
     int ts_staged = -1;                                            // the form of k_translate_seg the last range launched (mc_debug_stage 5)
     uint32_t cap_tasks = 0, cap_gaps = 0, cap_hsps = 0, cap_rows = 0;
-    McDev<uint8_t> d_frames_base; uint8_t *d_frames = nullptr;   // (a view 64 bytes in: k_eval_seeds reads 8 bytes at a time backwards from a seed)
+    // Two frame buffers (mc_ahead.h): d_frames is the RUNNING range's - the one every reader means - and a lookahead writes the other;
+    // a range_begin that takes a lookahead makes that buffer the current one (frames_use).  Views 64 bytes in, behind an apron of MC_INV:
+    // k_eval_seeds reads 8 bytes at a time backwards from a seed.
+    McDev<uint8_t> d_frames_base[2]; uint8_t *d_frames = nullptr;
+    uint8_t *frames_of(int b) const { return d_frames_base[b] + 64; }
+    void frames_use(int b) { d_frames = frames_of(b); }
     McDev<unsigned long long> d_stats;
     McDev<McSeedTask> d_tasks; McDev<McGapTask> d_gaps; McDev<McHsp> d_hsps, d_v, d_tmp;
     McDev<uint64_t> d_k64, d_hkeys, d_hplace, d_places; McDev<uint32_t> d_idx, d_idxo, d_heads, d_scan, d_gsz, d_nv, d_ghist;
@@ -68,6 +74,7 @@ struct McCtx {
     // the range being processed
     const uint8_t *reads = nullptr; int64_t n = 0, first_read_id = 0, first = 0;   // (first: the range's first read in the resident set)
     int ahead_from = -1;                                           // the pair of the handle's ahead_ev around the lookahead this range used; -1: none
+    bool predicts = false;                                         // the range issues the lookahead for the range behind it itself, at its begin (mc_range_begin); otherwise range_end is told
     bool own_a0 = true;                                            // ev[0], ev[1] are around a translation of the range's own (all of it, or the reads behind the lookahead's)
     uint32_t ntasks = 0, ngaps = 0, gpad = 0, nh = 0, nh_all = 0, nheads = 0, nrows = 0, nbest = 0, nsegs = 0;
     bool busy = false;                                             // a range has been begun and not ended
@@ -103,12 +110,13 @@ struct mc_handle {
     McDev<uint8_t> d_reads;
     const uint8_t *reads_dev = nullptr;   // resident read set (own buffer or attached caller memory)
     McCtx ctx;
-    // the lookahead (mc_ahead.h): the translation of the range expected next, on a stream of its own beside the ordering and finishing
-    // kernels of the running range.  ahead_ev[p]: the events around the kernel of lookahead p (two pairs in turn: the range that used
-    // lookahead p reads its translation time at ITS range_end, after the lookahead for the range behind it has been issued);
+    // the lookahead (mc_ahead.h): the translation of the range expected next, on a stream of its own beside the front of the
+    // running range, into the frame buffer that range does not use.  ahead_ev[p]: the events around the kernel of lookahead p (two
+    // pairs in turn: the range that used lookahead p reads its interval at ITS range_end, after the lookahead for the range behind it has been issued);
     // ahead_wait: the kernel of ahead_ev[ahead_p] may still be running and nothing has been made to wait for it yet.
     McStream ahead_stream; McEvent ahead_ev[2][2]; int ahead_p = 0; bool ahead_wait = false;
     McAhead ahead; uint64_t reads_gen = 0, tables_gen = 0; int64_t ahead_used = 0;
+    float ahead_ms = 0;                                            // the interval of the lookahead's kernel the range that ended last used (mc_ahead_kernel_ms); 0: it used none
     // host results: rows of the last run land in pinned memory; mc_search() accumulates its batches in all_rows
     // The rows travel to the host while the caller goes on (two pinned buffers in turn, a stream and an event of their own):
     // mc_run_range() returns when the best hits are there; whoever looks at the rows waits for their copy (rows_wait).
@@ -132,7 +140,7 @@ static void ahead_drop(mc_handle *h)
     if (h->ahead_wait) { (void)hipStreamSynchronize(h->ahead_stream); h->ahead_wait = false; }   // (nothing but lookaheads runs in that stream)
     mc_ahead_drop(h->ahead);
 }
-static constexpr bool MC_AHEAD_ON = true;                          // range_end issues lookaheads (off: every range translates in its own range_begin, as before)
+static constexpr bool MC_AHEAD_ON = true;                          // lookaheads are issued (off: every range translates in its own range_begin, as before)
 static McAheadKey ahead_key(const mc_handle *h, int64_t first, int64_t count) { return {h->reads_gen, first, count, h->read_len, h->FP, h->tables_gen}; }
 // the resident reads are about to change (the buffer, or what it holds) / the run's tables on the device are
 static void reads_change(mc_handle *h) { ahead_drop(h); h->reads_gen++; }
@@ -214,18 +222,26 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
     // says otherwise) and streams that share one wait for each other: with nine streams the front of a range could land behind the
     // 5 ms copy of the rows of the range before (measured: 51.2 instead of 53.6 M reads/s) - hence few streams.  The queue count is
     // the environment's: neither this library nor the package's entry points set it.
+    // The ORDER of creation decides who shares: the runtime gives the first four streams a hardware queue each and every later one the
+    // LAST-made queue among those with the fewest streams (read off the Queue_Id column of kernel traces).  The lookahead's
+    // kernel lives for most of a range, and whatever shares its queue waits behind it - as the rows' copy did (a blit kernel), and
+    // stage D behind that.  So: the range's stream, the lookahead's, side, side2 - four queues - then the rows' stream, which lands on
+    // side2's queue (its copy of range i has long left when range i + 1 reaches its finishing kernels); the null stream comes to lie on
+    // side's, and run_stream's copy stream, made last, on the lookahead's.  That policy is observed, not documented, and the layout
+    // holds for the FIRST handle of a process whose caller has made no streams before mc_open: a second handle's streams, or a handle
+    // behind a caller's own, join queues that are taken, wherever the fewest streams are.  Only speed depends on it, never a result.
+    if (h->ctx.stream.create() || h->ahead_stream.create()) return -1;
     if (h->side.create() || h->side2.create()) return -1;
     {
         McCtx &c = h->ctx;
-        if (c.stream.create()) return -1;
         c.side = h->side; c.side2 = h->side2;
         for (auto &e : c.ev) if (e.create()) return -1;
         if (c.ev_fork.create(false) || c.ev_join.create(false) || c.ev_join2.create(false)) return -1;
+        for (auto &e : c.ev_wait) if (e.create()) return -1;
         if (c.d_counters.alloc(C_N) || c.d_stats.alloc(S_N) || c.d_ghist.alloc((size_t)MC_GS_BINS)) return -1;
         if (c.h_c.alloc(C_N) || c.h_stats.alloc(S_N)) return -1;
     }
     if (h->rows_stream.create() || h->ev_rows.create(false)) return -1;
-    if (h->ahead_stream.create()) return -1;                       // (an ordinary stream: one of the lowest priority measured no better - DESIGN.md 5.5)
     for (auto &pair : h->ahead_ev) for (auto &e : pair) if (e.create()) return -1;
     const McHostIndex &H = h->H;
     if (H.res.size() >= MC_TASK_ABS_LIMIT) { g_err = "marker database too large: more than 16 M residues (MC_TASK_W3)"; return -1; }
@@ -429,7 +445,7 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
 {
     if (nreads <= c.cap_reads && h->read_len <= c.pool_len) return 0;   // (pools sized for longer reads fit shorter ones: mc_search_varlen)
     if (h->best_from == &c) best_materialize(h);                   // (the best hits of the range before still lie in the pinned buffer that is about to be replaced)
-    ahead_drop(h);                                                  // (d_frames_base is about to be freed)
+    ahead_drop(h);                                                  // (both frame buffers are about to be freed)
     double t0 = mc_now();
     int64_t cap = nreads;
     if (cap > (1 << 21) - 1) { g_err = "batch larger than 2097151 reads"; return -1; }
@@ -445,7 +461,7 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
     c.cap_hsps = (uint32_t)std::min<int64_t>(cap * (L / 3 + 8) + (1 << 20) + ev_pad, 0x7fffffff);
     c.cap_rows = (uint32_t)std::min<int64_t>(cap * 16 + (1 << 20), 0x7fffffff);
     c.gap_threads_full = 16 * 1024;                                 // full-size DP rows for the last-resort launch (460 MB)
-    if (c.d_frames_base.alloc((size_t)cap * 6 * h->FP + 128) || c.d_tasks.alloc(c.cap_tasks) ||
+    if (c.d_frames_base[0].alloc((size_t)cap * 6 * h->FP + 128) || c.d_frames_base[1].alloc((size_t)cap * 6 * h->FP + 128) || c.d_tasks.alloc(c.cap_tasks) ||
         c.d_gaps.alloc(c.cap_gaps) || c.d_hsps.alloc(c.cap_hsps) || c.d_v.alloc(c.cap_hsps) ||
         c.d_tmp.alloc((size_t)c.cap_hsps * 2) || c.d_k64.alloc(c.cap_hsps) || c.d_hkeys.alloc(c.cap_hsps) || c.d_hplace.alloc(c.cap_hsps) || c.d_places.alloc(c.cap_hsps) || c.d_idx.alloc(c.cap_hsps) ||
         c.d_idxo.alloc(c.cap_hsps) || c.d_heads.alloc((size_t)cap + 2) || c.d_scan.alloc((size_t)4100) || c.d_gsz.alloc(c.cap_hsps) || c.d_nv.alloc((size_t)cap + 1) || c.d_rows.alloc(c.cap_rows) ||
@@ -453,8 +469,8 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
         c.d_gws_full.alloc((size_t)c.gap_threads_full * MC_GAP_W) || c.d_retry.alloc((size_t)c.cap_gaps * 2 + (size_t)cap + 1) || c.d_retry2.alloc((size_t)c.cap_gaps * 2) || c.d_gleader.alloc((size_t)c.cap_gaps) ||
         c.d_fout.alloc((size_t)c.cap_gaps * 2))
         return -1;
-    c.d_frames = c.d_frames_base + 64;
-    HIPCK(hipMemsetAsync(c.d_frames_base, MC_INV, 64, c.stream));
+    c.frames_use(h->ahead.cur);
+    for (auto &b : c.d_frames_base) HIPCK(hipMemsetAsync(b, MC_INV, 64, c.stream));
     if (c.h_best.alloc((size_t)cap + 1)) return -1;
     c.h_best_cap = (size_t)cap + 1;
     c.cap_reads = cap; c.pool_len = (int)L;
@@ -561,13 +577,13 @@ static int exp_timing_dump(mc_handle *h, McCtx &c, char stage)
 static int exp_timing_dump(mc_handle *, McCtx &, char) { return 0; }
 #endif
 
-// A0: translation + SEG of the n reads at `reads` into the frames of reads at .. at + n - 1 of d_frames, on stream st between the
-// events e0 and e1.  It reads the reads, d_T and d_segtab and writes nothing but those frames: stage C of a running range still reads
-// d_low and the counters, and A0 may run beside it (range_end).
-static int stage_a0(mc_handle *h, McCtx &c, hipStream_t st, const uint8_t *reads, int64_t at, int64_t n, hipEvent_t e0, hipEvent_t e1)
+// A0: translation + SEG of the n reads at `reads` into the frames of reads at .. at + n - 1 of the frame buffer `into`, on stream st
+// between the events e0 and e1.  It reads the reads, d_T and d_segtab and writes nothing but those frames: a running range reads the
+// other buffer, d_low and the counters, and A0 may run beside all of it (ahead_issue).
+static int stage_a0(mc_handle *h, McCtx &c, hipStream_t st, const uint8_t *reads, uint8_t *into, int64_t at, int64_t n, hipEvent_t e0, hipEvent_t e1)
 {
     const int L = h->read_len, FP = h->FP;
-    uint8_t *frames = c.d_frames + at * 6 * FP;                   // (FP is a multiple of 4: the kernel's word stores stay aligned)
+    uint8_t *frames = into + at * 6 * FP;                         // (FP is a multiple of 4: the kernel's word stores stay aligned)
     HIPCK(hipEventRecord(e0, st));
     const size_t lds_rest = (size_t)MC_TS_NLNF(FP) * 8 + (size_t)MC_TS_THREADS * MC_TS_STRIDE(FP);
     const size_t lds_staged = (size_t)MC_TS_STAGE(L) + lds_rest, lds_direct = (size_t)MC_TS_STAGE(0) + lds_rest;
@@ -603,7 +619,7 @@ static int stage_a(mc_handle *h, McCtx &c, int64_t covered)
     HIPCK(hipMemsetAsync(c.d_low, 0, (size_t)n, st));
     c.own_a0 = covered < n;
     if (!c.own_a0) HIPCK(hipEventRecord(c.ev[1], st));             // (the seed kernel's interval starts here: the stream has waited for the lookahead)
-    else if (stage_a0(h, c, st, c.reads + covered * L, covered, n - covered, c.ev[0], c.ev[1])) return -1;
+    else if (stage_a0(h, c, st, c.reads + covered * L, c.d_frames, covered, n - covered, c.ev[0], c.ev[1])) return -1;
     if (exp_timing_dump(h, c, 'a')) return -1;
     const int64_t threads = n * 6;
     if (h->fast_enum) {
@@ -872,31 +888,54 @@ extern "C" int mc_run_range(mc_handle *h, int64_t first, int64_t count, int64_t 
 // mc_search with rows - the 270 MB of rows to copy out of the pinned buffer).  The next front may overwrite every pool of the
 // range before: what the host still reads of it lies in pinned host memory (rows: two buffers in turn; best hits; the counters
 // were taken at range_end), and the rows still leaving the device are waited for by stage D (ev_rows).
-static int range_begin(mc_handle *h, McCtx &c, int64_t first, int64_t count, int64_t first_read_id)
+static int ahead_issue(mc_handle *h, McCtx &c, int64_t first, int64_t count, hipEvent_t behind);
+// predicts: the range issues the lookahead for the range that follows it contiguously in its set (mc_ahead_predict) itself, behind its
+// own A1 launches; otherwise its range_end is told the next range, or there is none (mc_run_range).
+static int range_begin(mc_handle *h, McCtx &c, int64_t first, int64_t count, int64_t first_read_id, bool predicts)
 {
     if (ensure_capacity(h, c, count)) return -1;
-    c.reads = h->reads_dev + first * h->read_len; c.n = count; c.first_read_id = first_read_id; c.first = first;
-    // A lookahead that covers the range has written its frames already; one that does not is over.  Either way the range's stream
-    // waits for the lookahead's kernel before A1 reads d_frames or A0 writes them.
+    c.reads = h->reads_dev + first * h->read_len; c.n = count; c.first_read_id = first_read_id; c.first = first; c.predicts = predicts;
+    // A lookahead that covers the range has written its frames into the other buffer, which becomes the range's; one that does not is
+    // over and the current buffer stays.  Either way the range's stream waits for the lookahead's kernel - one lookahead at most is on
+    // the device - between two events: the time of that wait is the range's own, the kernel's interval is not (range_end).
     const int64_t covered = mc_ahead_take(h->ahead, ahead_key(h, first, count));   // (reads of the range, from its first; a longer range translates the rest itself)
-    if (h->ahead_wait) { HIPCK(hipStreamWaitEvent(c.stream, h->ahead_ev[h->ahead_p][1], 0)); h->ahead_wait = false; }
+    c.frames_use(h->ahead.cur);
+    c.waited = h->ahead_wait && hipEventQuery(h->ahead_ev[h->ahead_p][1]) != hipSuccess;   // (a kernel that has ended is not waited for: two events on an idle stream would time the host's pause)
+    if (c.waited) {
+        HIPCK(hipEventRecord(c.ev_wait[0], c.stream));
+        HIPCK(hipStreamWaitEvent(c.stream, h->ahead_ev[h->ahead_p][1], 0));
+        HIPCK(hipEventRecord(c.ev_wait[1], c.stream));
+    }
+    h->ahead_wait = false;
     c.ahead_from = covered ? h->ahead_p : -1;
     if (covered) { h->ahead_used++; h->ahead_p ^= 1; }              // (the lookahead behind this range takes the other pair of events)
-    const int rc = stage_a(h, c, covered);
+    int rc = stage_a(h, c, covered);
     if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
     c.busy = true;
+    if (predicts && MC_AHEAD_ON) {
+        int64_t next_first = 0;
+        const int64_t next_count = mc_ahead_predict(first, count, h->nreads, &next_first);
+        if ((rc = ahead_issue(h, c, next_first, next_count, c.ev[1])) != 0) { (void)hipStreamSynchronize(c.stream); c.busy = false; return rc; }
+    }
     return 0;
 }
 
-// The translation of the range expected next - reads [first, first + count) of the resident set as it is now - beside what is left of
-// the running range: issued behind the event that ends its gapped stage, the last reader of d_frames.  No range larger than the pools.
-static int ahead_issue(mc_handle *h, McCtx &c, int64_t first, int64_t count)
+// The translation of the range expected next - reads [first, first + count) of the resident set as it is now - beside the running
+// range, into the frame buffer that range does not use: no reader of d_frames has to be waited for.  behind: an event of the running
+// range's stream the kernel starts behind, or none.  range_begin gives ev[1], the event in front of its seed kernel: the seed kernel,
+// launched right behind it on its own queue, is resident first - 16 waves per CU, the LDS nearly full - so the translation gets what
+// is left of the CUs beside it and floods them when the seed kernel's grid runs out, beside k_eval_seeds.  Without the event the two
+// race for the CUs and the step has two speeds; behind the seed kernel's END it finds k_eval_seeds resident, waits for that and runs
+// beside the gapped stage, which then takes as much longer as the translation lasts.  A grid BOUNDED to 256 x G one-wave workgroups
+// that loop over the blocks was built and measured too, and lost: a wave takes 110 us per block of ten reads however empty its CU is.
+// All of it: DESIGN.md 5.5.  No range larger than the pools.
+static int ahead_issue(mc_handle *h, McCtx &c, int64_t first, int64_t count, hipEvent_t behind)
 {
     if (count <= 0 || count > c.cap_reads || h->read_len > c.pool_len || first < 0 || first + count > h->nreads || !h->reads_dev) return 0;
-    ahead_drop(h);
-    HIPCK(hipStreamWaitEvent(h->ahead_stream, c.ev[4], 0));
+    ahead_drop(h);                                                  // (nothing to wait for: range_begin has made the range's stream wait for the lookahead before this one)
+    if (behind) HIPCK(hipStreamWaitEvent(h->ahead_stream, behind, 0));
     h->ahead_wait = true;                                           // (from here on something may be in the stream)
-    if (stage_a0(h, c, h->ahead_stream, h->reads_dev + first * h->read_len, 0, count, h->ahead_ev[h->ahead_p][0], h->ahead_ev[h->ahead_p][1])) { ahead_drop(h); return -1; }
+    if (stage_a0(h, c, h->ahead_stream, h->reads_dev + first * h->read_len, c.frames_of(mc_ahead_target(h->ahead)), 0, count, h->ahead_ev[h->ahead_p][0], h->ahead_ev[h->ahead_p][1])) { ahead_drop(h); return -1; }
     mc_ahead_offer(h->ahead, ahead_key(h, first, count));
     return 0;
 }
@@ -922,7 +961,9 @@ static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t nex
     h->stats.reads = c.n;
     int rc = stage_wait(c);
     if (rc == 0) rc = stage_b(h, c);
-    if (rc == 0 && MC_AHEAD_ON) rc = ahead_issue(h, c, next_first, next_count);   // (B's kernels are issued: d_frames is free behind ev[4])
+    // the next range a caller names (run_stream, run_pieces: it is known only here): behind the gapped stage, beside C + D, where it
+    // has been since it exists - beside the gapped kernels it costs them what it takes
+    if (rc == 0 && MC_AHEAD_ON && !c.predicts) rc = ahead_issue(h, c, next_first, next_count, c.ev[4]);
     if (rc == 0 && (rc = stage_wait(c)) == 0 && (rc = stage_c(h, c)) == 0) rc = stage_d(h, c);   // (C leaves its counts on the device: D is issued behind it)
     if (rc == 0) rc = stage_wait(c);
     if (rc == 0 && c.h_c[C_OVERFLOW]) { g_err = "row buffer overflow"; rc = -2; }
@@ -956,7 +997,10 @@ static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t nex
     h->stats.seed_exact_asks += (int64_t)c.h_stats[S_EXACT]; h->stats.seed_wild_asks += (int64_t)c.h_stats[S_WILD]; h->stats.seed_pair_asks += (int64_t)c.h_stats[S_PAIRS]; h->stats.seed_probes += (int64_t)c.h_stats[S_PROBES];
     h->stats.gap_tasks += c.ngaps - c.gpad; h->stats.hsps += c.nh_all; h->stats.rows += c.nrows; h->stats.reads_with_rows += c.nsegs;
     // kernel times: HIP events around the stages
-    const float ms_tr = (c.own_a0 ? ev_ms(c.ev[0], c.ev[1]) : 0.0f) + (c.ahead_from >= 0 ? ev_ms(h->ahead_ev[c.ahead_from][0], h->ahead_ev[c.ahead_from][1]) : 0.0f);   // (the kernel's own interval, wherever it ran)
+    // ms_translate is the range's own stream's: its A0, where it had one, and the time it waited for a lookahead's kernel - so the six
+    // stage times add up to the range.  The lookahead's kernel ran in the background of the range before: mc_ahead_kernel_ms.
+    const float ms_tr = (c.own_a0 ? ev_ms(c.ev[0], c.ev[1]) : 0.0f) + (c.waited ? ev_ms(c.ev_wait[0], c.ev_wait[1]) : 0.0f);
+    h->ahead_ms = c.ahead_from >= 0 ? ev_ms(h->ahead_ev[c.ahead_from][0], h->ahead_ev[c.ahead_from][1]) : 0.0f;
     h->stats.ms_translate += ms_tr; h->stats.ms_seed += ev_ms(c.ev[1], c.ev[2]); h->stats.ms_eval += ev_ms(c.ev[2], c.ev[3]);
     h->stats.ms_gapped += ev_ms(c.ev[3], c.ev[4]); h->stats.ms_sort += ev_ms(c.ev[4], c.ev[5]); h->stats.ms_finish += ev_ms(c.ev[5], c.ev[6]); h->stats.ms_total += ms_tr + ev_ms(c.ev[1], c.ev[6]);
     h->stats.classified = (int64_t)c.nbest;
@@ -977,7 +1021,7 @@ static int run_range_once(mc_handle *h, int64_t first, int64_t count, int64_t fi
     if (range_check(h, first, count)) return -1;
     if (count == 0) { memset(&h->stats, 0, sizeof h->stats); h->res_rows = nullptr; h->n_res_rows = 0; h->best.clear(); h->best_from = nullptr; return 0; }
     McCtx &c = h->ctx;
-    const int rc = range_begin(h, c, first, count, first_read_id);
+    const int rc = range_begin(h, c, first, count, first_read_id, false);
     if (rc) return rc;
     return range_end(h, c);
 }
@@ -987,33 +1031,33 @@ static int run_range_once(mc_handle *h, int64_t first, int64_t count, int64_t fi
 // end(i), begin(i + 1), results of i, end(i + 1), ... keeps the device busy while the host works on the results.  One range at a
 // time is on the device: a second mc_range_begin() before mc_range_end() is refused.  A range that overflows a pool comes back with
 // -2 from mc_range_end: it is no longer in flight; run it with mc_run_range (which splits it).
-// mc_range_end() also LOOKS AHEAD: behind the range's gapped stage - the last reader of d_frames - it issues the translation of the range
-// it expects next (the one that follows contiguously in the resident set: mc_ahead_predict; run_stream and run_pieces name theirs) on
-// a stream of its own, beside the ordering and finishing kernels; an mc_range_begin() of that range (or of a prefix of it, or of a
-// longer one, which translates the rest on top) starts with the seed kernel, any other waits for the lookahead's kernel and translates
-// itself (range_begin, mc_ahead.h).  mc_run_range() issues none.  2.8 % of a step: DESIGN.md 5.5, where the reason it is not more stands.
+// mc_range_begin() also LOOKS AHEAD: behind the front of its own range it issues the translation of the range it expects next (the one
+// that follows contiguously in the resident set: mc_ahead_predict) on a stream of its own, into the frame buffer its own range does
+// not use, beside its seed kernel and seed evaluation; run_stream and run_pieces name their next range at its end, and theirs runs
+// behind the gapped stage.  An mc_range_begin() of that range (or of a prefix of it, or of a longer one, which translates the rest on
+// top) starts with the seed kernel in that buffer, any other waits for the lookahead's kernel and translates itself (range_begin,
+// mc_ahead.h).  mc_run_range() issues none.  4.5 % of a step on top of the 2.8 % of the lookahead behind the gapped stage: DESIGN.md 5.5.
 // (Round 4 also measured the whole TAIL of a range - ordering, finishing - running beside the whole front of the next, on ordinary
 // streams, on streams of their own priority and on streams with CU masks: it does not pay)
-extern "C" int mc_range_begin(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id)
+// predicts: mc_range_begin itself; run_stream and run_pieces tell range_end their next range instead (range_end_next)
+static int range_begin_checked(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id, bool predicts)
 {
     if (range_check(h, first, count)) return -1;
     if (count <= 0) { g_err = "mc_range_begin: an empty range"; return -1; }
     if (h->pipe_nout) { g_err = "mc_range_begin: a range is in flight already (mc_range_end first)"; return -1; }
-    const int rc = range_begin(h, h->ctx, first, count, first_read_id);
+    const int rc = range_begin(h, h->ctx, first, count, first_read_id, predicts);
     if (rc) return rc;
     h->pipe_nout = 1;
     return 0;
 }
+extern "C" int mc_range_begin(mc_handle *h, int64_t first, int64_t count, int64_t first_read_id) { return range_begin_checked(h, first, count, first_read_id, true); }
 
 // The end of the range in flight, with a lookahead for the range the caller will begin next (count reads from first of the resident
-// set as it is NOW; count 0: none), or - predict - for the range that follows the running one contiguously in its set.
-static int range_end_next(mc_handle *h, int64_t first, int64_t count, bool predict)
-{
-    if (predict) count = mc_ahead_predict(h->ctx.first, h->ctx.n, h->nreads, &first);
-    return range_end(h, h->ctx, first, count);
-}
+// set as it is NOW; count 0: none).
+static int range_end_next(mc_handle *h, int64_t first, int64_t count) { return range_end(h, h->ctx, first, count); }
 
 extern "C" int64_t mc_ranges_translated_ahead(const mc_handle *h) { return h ? h->ahead_used : 0; }
+extern "C" float mc_ahead_kernel_ms(const mc_handle *h) { return h ? h->ahead_ms : 0.0f; }
 
 extern "C" int mc_range_end(mc_handle *h)
 {
@@ -1021,7 +1065,7 @@ extern "C" int mc_range_end(mc_handle *h)
     if (h->pipe_nout == 0) { g_err = "mc_range_end: no range in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     h->pipe_nout = 0;
-    return range_end_next(h, 0, 0, true);
+    return range_end(h, h->ctx);                                   // (its mc_range_begin has issued the lookahead)
 }
 
 extern "C" int mc_ranges_in_flight(const mc_handle *h) { return h ? h->pipe_nout : 0; }
@@ -1157,7 +1201,7 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
     auto end_batch = [&](int k, int next) -> int {
         if (next >= 0) reads_at(next);
         h->pipe_nout = 0;                                            // (mc_range_end, told the next range)
-        int r = range_end_next(h, 0, next >= 0 ? slot[next].n : 0, false);
+        int r = range_end_next(h, 0, next >= 0 ? slot[next].n : 0);
         if (r == -2) { reads_at(k); r = mc_run_range(h, 0, slot[k].n, first_read_id + slot[k].first); if (next >= 0) reads_at(next); }
         if (r) return r;
         pending = true;
@@ -1175,7 +1219,7 @@ static int run_stream(mc_handle *h, const std::function<int64_t(uint8_t *, int64
         if (slot[k].state == 2) { if (slot[k].rc < 0) { rc = (int)slot[k].rc; if (!up_err.empty()) g_err = up_err; } break; }
         if (flying >= 0) { if ((rc = end_batch(flying, k)) != 0) break; flying = -1; }
         else reads_at(k);
-        if ((rc = mc_range_begin(h, 0, slot[k].n, first_read_id + slot[k].first)) != 0) break;
+        if ((rc = range_begin_checked(h, 0, slot[k].n, first_read_id + slot[k].first, false)) != 0) break;
         flying = k;
         collect();                                                   // the batch before, while the front of this one runs
     }
@@ -1331,7 +1375,7 @@ template <class BlockOf> static int run_pieces(mc_handle *h, McLenBorrow &len, c
             reads_change(h);
             h->reads_dev = block_of(q); h->nreads = q.bin_n;
         }
-        return mc_range_begin(h, q.first, q.n, q.bin_first + q.first);
+        return range_begin_checked(h, q.first, q.n, q.bin_first + q.first, false);
     };
     int rc = pieces.empty() ? 0 : begin(pieces[0], nullptr);
     for (size_t j = 0; rc == 0 && j < pieces.size(); j++) {
@@ -1339,7 +1383,7 @@ template <class BlockOf> static int run_pieces(mc_handle *h, McLenBorrow &len, c
         const McPiece *nx = j + 1 < pieces.size() ? &pieces[j + 1] : nullptr;
         const bool ahead = nx && same_bin(q, *nx);
         h->pipe_nout = 0;                                            // (mc_range_end, told the next range: the next piece where it is of this bin, else none)
-        rc = range_end_next(h, ahead ? nx->first : 0, ahead ? nx->n : 0, false);
+        rc = range_end_next(h, ahead ? nx->first : 0, ahead ? nx->n : 0);
         if (rc == -2) rc = mc_run_range(h, q.first, q.n, q.bin_first + q.first);
         if (rc) break;
         if (nx && (rc = begin(*nx, &q)) != 0) break;
@@ -2345,7 +2389,7 @@ static int train_range(mc_handle *h, int64_t first, int64_t count, int64_t first
 {
     if (count <= 0) return 0;
     McCtx &c = h->ctx;
-    int rc = range_begin(h, c, first, count, first_read_id);
+    int rc = range_begin(h, c, first, count, first_read_id, false);
     if (rc == 0) rc = range_end(h, c);
     if (rc == -2 && count > 1) {
         tot.range_splits++;
