@@ -560,6 +560,34 @@ int mc_ties_coverage_read(mc_handle *h, int64_t *covered_any /* [nseq] */, int64
  * device cost of the README's "reads mapped to gene". */
 float mc_ties_ms(const mc_handle *h);
 
+/* ---- a rarefaction curve beside the counts: the gene table's figures at K nested prefixes of the sample ---------------------------
+ * Was the sample sequenced deeply enough, or would twice the reads have found more genes?  csrc/k_curve.h states the rule: with K
+ * points n_0 <= ... <= n_{K-1} (64-bit, each >= 1, repeats allowed; 1 <= K <= 64) a read with a best row - the one mc_set_abundance
+ * counts - and global id q (first_read_id plus its index) falls into bin b(q) = the number of k with n_k <= q and adds 1 and its
+ * alignment length to that bin of its subject; with coverage on it also lowers the "first id" of every residue of its span to
+ * min(first, q).  At read time point k is, per subject: reads and aligned summed over the bins 0 .. k, covered = the residues whose
+ * first id is below n_k - exactly what mc_abundance_read and mc_coverage_read return after a run on the first n_k reads alone.
+ * All are 64-bit integers: exact, whatever the batches, ranges and launch geometry; a range that overflowed a pool adds nothing, its
+ * pieces once.
+ * mc_set_curve(h, K, points) copies the points and zeroes the curve AND the abundance counters, depth and ties: all describe the
+ * same reads; K == 0 frees everything and restores the path without it exactly.  From then on every range that adds to the counts
+ * runs one more kernel behind the counting kernel (and the tie kernel), on the same rows where they lie.  mc_set_abundance(h, 0, ...)
+ * also turns the curve off; mc_abundance_reset() also zeroes it and mc_curve_ms(); mc_set_coverage in either direction keeps the
+ * curve on (going on zeroes everything, as always).
+ * Refused, with a message naming the value: K < 0 or K > 64, a point < 1 or below the one before it, abundance counting off, a range
+ * in flight.  While the curve is on mc_search_varlen is refused: its rows carry the sorted position, not the caller's read id. */
+int mc_set_curve(mc_handle *h, int32_t K, const int64_t *points /* [K] */);
+/* The curve as it stands: reads, aligned and covered are K x nseq values, point k of subject s at [k * nseq + s]; assigned: K values,
+ * the reads assigned among the first n_k; beyond: the assigned reads with an id >= n_{K-1} - they are in no point.  Any pointer may
+ * be NULL; one scan kernel per call.  Refused while the curve is off, and when covered is asked for with coverage off. */
+int mc_curve_read(mc_handle *h, int64_t *reads /* [K * nseq] */, int64_t *aligned /* [K * nseq] */, int64_t *covered /* [K * nseq] or NULL */, int64_t *assigned /* [K] */,
+                  int64_t *beyond);
+/* The number of points the curve is on with - the K that sizes mc_curve_read's arrays; 0 while it is off. */
+int32_t mc_curve_k(const mc_handle *h);
+/* Milliseconds the curve's kernels took since the last reset (HIP events): one kernel per completed range plus one scan per
+ * mc_curve_read. */
+float mc_curve_ms(const mc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

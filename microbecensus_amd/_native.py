@@ -233,6 +233,12 @@ def load_library():
     lib.mc_ties_coverage_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mc_ties_ms.restype = C.c_float
     lib.mc_ties_ms.argtypes = [C.c_void_p]
+    lib.mc_set_curve.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.mc_curve_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.mc_curve_k.restype = C.c_int32
+    lib.mc_curve_k.argtypes = [C.c_void_p]
+    lib.mc_curve_ms.restype = C.c_float
+    lib.mc_curve_ms.argtypes = [C.c_void_p]
     lib.mc_debug_live.restype = None
     lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
@@ -251,7 +257,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride",
                     "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms",
                     "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms",
-                    "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms", "mc_debug_live"]
+                    "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms",
+                    "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms", "mc_debug_live"]
 
 
 class DupSet:
@@ -977,6 +984,32 @@ class Engine:
         out = {k: np.zeros(n, np.int64) for k in ("covered_any", "spanned_any", "max_depth_any")}
         self._check(self.lib.mc_ties_coverage_read(self.h, *(out[k].ctypes.data_as(C.c_void_p) for k in ("covered_any", "spanned_any", "max_depth_any"))), "mc_ties_coverage_read")
         return out
+
+    def set_curve(self, points):
+        """A rarefaction curve beside the counts (mc_set_curve; csrc/k_curve.h states the rule): points - ascending read counts n_k, each
+        >= 1, at most 64, repeats allowed - or None / an empty list to turn it off.  From now on every read that set_abundance assigns is
+        also counted by the prefix of the sample it belongs to (its global id: first_read_id plus its index).  Turning it on zeroes the
+        curve AND the abundance counters, depth and ties.  Refused while set_abundance is off; search_varlen is refused while it is on."""
+        pts = [] if points is None else [int(x) for x in points]
+        arr = np.array(pts, dtype=np.int64)
+        self._check(self.lib.mc_set_curve(self.h, len(pts), arr.ctypes.data_as(C.c_void_p) if len(pts) else None), "mc_set_curve")
+
+    def curve(self, covered=True):
+        """The curve as it stands (mc_curve_read): {"reads", "aligned": int64[K, nseq], "covered": int64[K, nseq] (with covered=True:
+        coverage must be on), "assigned": int64[K], "beyond": int} - row k is what abundance() and coverage()["covered"] return after
+        a run on the first n_k reads alone; beyond counts the assigned reads behind the last point."""
+        K, n = int(self.lib.mc_curve_k(self.h)), len(self.names)                  # (the library's K sizes the arrays, however the curve was set)
+        out = {k: np.zeros((K, n), np.int64) for k in (("reads", "aligned", "covered") if covered else ("reads", "aligned"))}
+        out["assigned"] = np.zeros(K, np.int64)
+        beyond = C.c_int64(0)
+        self._check(self.lib.mc_curve_read(self.h, out["reads"].ctypes.data_as(C.c_void_p), out["aligned"].ctypes.data_as(C.c_void_p),
+                                           out["covered"].ctypes.data_as(C.c_void_p) if covered else None, out["assigned"].ctypes.data_as(C.c_void_p), C.byref(beyond)), "mc_curve_read")
+        out["beyond"] = int(beyond.value)
+        return out
+
+    def curve_ms(self):
+        """milliseconds the curve's kernels took since the last reset (HIP events): k_curve per range and one scan per curve()"""
+        return float(self.lib.mc_curve_ms(self.h))
 
     def ties_ms(self):
         """milliseconds the tie kernels took since the last reset (HIP events)"""

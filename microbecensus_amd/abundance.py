@@ -30,7 +30,14 @@ also says, per gene, how many of its reads were its alone, how many it tied for,
     shared_reads    = the sum over those reads of 1 / k, k the genes tied   rpkg_shared     = the rpkg formula on shared_reads
 
 and with coverage covered_any_aa / breadth_any (the residues that a tied read covers, whichever gene it was given to) and, with
-min_breadth, detected_any (candidate_reads > 0 and covered_any_aa >= F x length_aa).  The existing columns keep their values."""
+min_breadth, detected_any (candidate_reads > 0 and covered_any_aa >= F x length_aa).  The existing columns keep their values.
+
+Was the sample sequenced deeply enough?  With curve K (Engine.set_curve; csrc/k_curve.h states the rule) the same run also gives every
+figure the table is built from at K nested prefixes of the sample, n_k = microbe_census.curve_points(sampled_reads, K) - the points of
+run_pipeline's AGS curve: reads, aligned_aa and covered_aa per gene and, from them by the lines above, RPKG, reads_assigned, the genes
+with reads, the genes detected and the groups with reads.  The sampler is a head-take, so point k is, integer for integer, the table
+of a run with -n n_k, and the last point is the run's own table.  The tie columns stay whole-sample figures: the curve does not
+rarefy them."""
 import gzip
 import math
 import os
@@ -49,6 +56,8 @@ DEPTH_COLUMNS = ("gene", "start", "end", "depth")
 TIES_COLUMNS = ("unique_reads", "candidate_reads", "shared_reads", "rpkg_shared")    # behind all of them with ties ...
 TIES_COVERAGE_COLUMNS = ("covered_any_aa", "breadth_any")                            # ... these behind them with coverage, "detected_any" last with min_breadth
 GROUP_TIES_COLUMNS = ("unique_reads", "shared_reads", "rpkg_shared")                 # behind the groups table's columns; "genes_detected_any" last with min_breadth
+CURVE_COLUMNS = ("sampled_reads", "average_genome_size", "genome_equivalents_sampled", "reads_assigned", "genes_with_reads")   # "genes_detected" behind them with min_breadth, "groups_with_reads" with groups
+MAX_CURVE = 64                                                                       # MC_CURVE_MAXK (csrc/mc_curve.h)
 SHARE_ONE = 4294967296.0                                                             # share[] counts in units of 2^-32 (csrc/k_ties.h)
 
 
@@ -261,6 +270,8 @@ def header_lines(args, table):
         h += [("ties", "on"), ("reads_ambiguous", table["reads_ambiguous"])]
         if table.get("reads_ambiguous_across_groups") is not None:
             h.append(("reads_ambiguous_across_groups", table["reads_ambiguous_across_groups"]))
+    if table.get("curve") is not None:
+        h.append(("curve", len(table["curve"]["points"])))
     return ["# %s:\t%s\n" % kv for kv in h]
 
 
@@ -302,6 +313,57 @@ def write_groups(path, args, table):
             out.write("%s\t%d\t%d\t%s%s%s\n" % (g, n, r, repr(float(v)), "\t%d" % row[4] if det else "", more))
 
 
+def _na(v, fmt=repr):
+    return "NA" if v is None else fmt(v)
+
+
+def curve_figures(names, length_aa, read_length, points, reads, aligned, covered, ags, min_breadth=None, group_of=None):
+    """table['curve'] from the device's arrays: points n_k, reads / aligned / covered (or None) as [K, genes], ags: one value per point
+    (None: no estimate at that point - its AGS, genome equivalents and RPKG are None / NaN).  Every figure comes from the lines the
+    gene table is made with: genome_equivalents, rpkg, detect, group_table."""
+    K = len(points)
+    cu = {"points": [int(n) for n in points], "reads": reads, "aligned_aa": aligned, "ags": [None if a is None else float(a) for a in ags],
+          "genome_equivalents_sampled": [], "rpkg": np.full((K, len(names)), np.nan), "reads_assigned": [int(x) for x in reads.sum(axis=1)],
+          "genes_with_reads": [int(x) for x in (reads > 0).sum(axis=1)]}
+    for k, n_k in enumerate(cu["points"]):
+        ge = None if cu["ags"][k] is None else genome_equivalents(n_k, read_length, cu["ags"][k])
+        cu["genome_equivalents_sampled"].append(ge)
+        if ge is not None:
+            cu["rpkg"][k] = rpkg(reads[k], length_aa, ge)
+    if covered is not None:
+        cu["covered_aa"] = covered
+        if min_breadth is not None:
+            cu["detected"] = np.stack([detect(reads[k], covered[k], length_aa, min_breadth) for k in range(K)])
+            cu["genes_detected"] = [int(x) for x in cu["detected"].sum(axis=1)]
+    if group_of is not None:
+        cu["groups"] = [group_table(names, reads[k], cu["rpkg"][k], group_of, cu["detected"][k] if "detected" in cu else None) for k in range(K)]
+        cu["groups_with_reads"] = [sum(1 for g in gt if g[2] > 0) for gt in cu["groups"]]
+    return cu
+
+
+def write_curve(path, args, table):
+    """<outfile>.curve.tsv: the gene table's header lines, then one row per point"""
+    cu = table["curve"]
+    det, grp = "genes_detected" in cu, "groups_with_reads" in cu
+    with open(path, "w") as out:
+        out.writelines(header_lines(args, table))
+        out.write("\t".join(CURVE_COLUMNS + (("genes_detected",) if det else ()) + (("groups_with_reads",) if grp else ())) + "\n")
+        for k, n_k in enumerate(cu["points"]):
+            line = "%d\t%s\t%s\t%d\t%d" % (n_k, _na(cu["ags"][k]), _na(cu["genome_equivalents_sampled"][k]), cu["reads_assigned"][k], cu["genes_with_reads"][k])
+            out.write(line + ("\t%d" % cu["genes_detected"][k] if det else "") + ("\t%d" % cu["groups_with_reads"][k] if grp else "") + "\n")
+
+
+def write_curve_genes(path, table):
+    """--curve-genes: gene, reads_1 .. reads_K and with coverage covered_aa_1 .. covered_aa_K - genes in FASTA order"""
+    cu = table["curve"]
+    K, cov = len(cu["points"]), cu.get("covered_aa")
+    with open(path, "w") as out:
+        out.write("# curve_points:\t%s\n" % "\t".join(str(n) for n in cu["points"]))
+        out.write("\t".join(["gene"] + ["reads_%d" % (k + 1) for k in range(K)] + (["covered_aa_%d" % (k + 1) for k in range(K)] if cov is not None else [])) + "\n")
+        for g, nm in enumerate(table["gene"]):
+            out.write("\t".join([nm] + [str(int(cu["reads"][k, g])) for k in range(K)] + ([str(int(cov[k, g])) for k in range(K)] if cov is not None else [])) + "\n")
+
+
 def read_table(path):
     """(header dict of strings, rows as lists of strings) of a table write_table / write_groups wrote."""
     header, rows = {}, []
@@ -328,8 +390,25 @@ def check_request(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.get("distributed"):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
-                         ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False)):
+                         ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None)):
         args.setdefault(key, default)
+    if args["curve"] is not None:
+        K = args["curve"]
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= MAX_CURVE:
+            raise AbundanceError("--curve %s is not an integer from 1 to %d" % (K, MAX_CURVE))
+        args["curve"] = int(K)
+    if args["curve_genes"] is not None:
+        if not args["curve_genes"]:
+            raise AbundanceError("--curve-genes %r is an empty path" % (args["curve_genes"],))
+        if args["curve"] is None:
+            raise AbundanceError("--curve-genes %s needs --curve K: it writes the curve's per-gene matrix" % (args["curve_genes"],))
+        where = os.path.abspath(args["curve_genes"])
+        others = [(args.get("outfile"), "the gene table itself"), (args["outfile"] + ".curve.tsv" if args.get("outfile") else None, "the curve table (<outfile>.curve.tsv)"),
+                  (args["outfile"] + ".groups.tsv" if args.get("outfile") and args["groups"] else None, "the groups table (<outfile>.groups.tsv)"),
+                  (args["depth_out"] or None, "the depth file (--depth-out)")]
+        for other, what in others:
+            if other and where == os.path.abspath(other):
+                raise AbundanceError("--curve-genes %s is the path of %s: two files" % (args["curve_genes"], what))
     if args["min_breadth"] is not None:
         f = args["min_breadth"]
         try:
@@ -377,13 +456,15 @@ def run_abundance(args):
     """args: run_pipeline's keys (seqfiles, nreads, read_length, min_quality, mean_quality, filter_dups, max_unknown, device, model_dir,
     verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and - all off by default - coverage, min_breadth
     (implies coverage), depth_out (a path; implies coverage), ties (the genes that tie for a read's best hit: unique, candidate and
-    shared reads beside the counts; sets args['ties_ms']).  Writes args['outfile'] (and
+    shared reads beside the counts; sets args['ties_ms']), curve (K, 1 .. 64: table['curve'], the table's figures at K prefixes of the sample
+    - the sampler then runs to its end before the search starts; sets args['curve_ms']; writes <outfile>.curve.tsv) and curve_genes (a path:
+    the curve's per-gene matrix).  Writes args['outfile'] (and
     <outfile>.groups.tsv with groups) when it is set; returns (table, args) - table: the columns as arrays (gene, length_aa, reads,
     aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
     names, seqs, group_of, ags, source = check_request(args)
     microbe_census.check_input(args)
     if ags is None:             # the estimate of the same sample: run_pipeline on the marker engine, same files, same options
-        est = microbe_census.run_pipeline(_pipeline_args(args))
+        est = microbe_census.run_pipeline(dict(_pipeline_args(args), curve=args["curve"]) if args["curve"] else _pipeline_args(args))
         if est is None:
             raise AbundanceError("run_pipeline gave no AGS estimate for %s" % ",".join(args["seqfiles"]))
         ags, pargs = est
@@ -411,8 +492,22 @@ def run_abundance(args):
                 eng.set_ties(True, gids, len(gnames))
             else:
                 eng.set_ties(True)
+        cu = points = None
         try:
-            eng.search_files(rd, keep_rows=False)
+            if args["curve"]:       # the points depend on how many reads the sampler takes: it runs to its end first, then one search
+                n = rd.run()
+                if n:               # (no read taken: nothing is searched, and the run ends below with "No reads remaining after filtering" as without the switch)
+                    points = microbe_census.curve_points(n, args["curve"])
+                    eng.set_curve(points)
+                    eng.lib.mc_set_keep_rows(eng.h, 0)
+                    try:
+                        eng.search(rd.reads(n))
+                    finally:
+                        eng.lib.mc_set_keep_rows(eng.h, 1)
+                    cu = eng.curve(covered=bool(args["coverage"]))
+                    args["curve_ms"] = eng.curve_ms()
+            else:
+                eng.search_files(rd, keep_rows=False)
         except _native.ReferenceError_ as e:
             raise AbundanceError(str(e))
         ab = eng.abundance()
@@ -466,8 +561,23 @@ def run_abundance(args):
             table["groups_ties"] = group_ties_table(gids, len(gnames), ti["group_unique"], ti["share"], table["rpkg_shared"], table.get("detected_any"))
     if group_of is not None:
         table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of, table.get("detected"))
+    if cu is not None:
+        if cu["beyond"] != 0:
+            raise AbundanceError("the curve: %d assigned reads lie behind the last point %d (%d sampled)" % (cu["beyond"], points[-1], sampled))
+        if source == "run_pipeline":
+            est_curve = pargs.get("ags_curve") or []
+            if [p["reads"] for p in est_curve] != points:
+                raise AbundanceError("the AGS curve's points %s are not the gene curve's %s" % ([p["reads"] for p in est_curve], points))
+            ags_k = [p["ags"] for p in est_curve]
+        else:
+            ags_k = [ags] * len(points)
+        table["curve"] = curve_figures(names, length_aa, L, points, cu["reads"], cu["aligned"], cu.get("covered"), ags_k, args["min_breadth"], group_of)
     if args.get("outfile"):
         write_table(args["outfile"], args, table)
         if group_of is not None:
             write_groups(args["outfile"] + ".groups.tsv", args, table)
+        if cu is not None:
+            write_curve(args["outfile"] + ".curve.tsv", args, table)
+    if cu is not None and args["curve_genes"] is not None:
+        write_curve_genes(args["curve_genes"], table)
     return table, args

@@ -17,7 +17,8 @@
 //   k_abundance.h          per-gene read counts for RPKG, summed over the rows of every completed range (mc_set_abundance)
 //   k_coverage.h           per-gene coverage breadth and depth beside them: marks in the counting kernel, a scan at read time (mc_set_coverage)
 //   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
-//   mc_abund.h             (host) the owner of those three: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
+//   k_curve.h              the rarefaction curve beside them: per-gene counts per prefix of the sample, every residue's first read, a scan at read time (mc_set_curve)
+//   mc_abund.h             (host) the owner of those four: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
 //   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
@@ -1485,6 +1486,7 @@ extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_
     if (nreads < 0 || !offsets || (nreads > 0 && !bases)) { g_err = "bad argument"; return -1; }
     if (nreads > 0x7fffffff) { g_err = "more than 2^31 - 1 reads in one call"; return -1; }
     if (h->pipe_nout) { g_err = "ranges begun with mc_range_begin() are still in flight"; return -1; }
+    if (h->ab.curve) { g_err = "mc_search_varlen: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     bool one = true;
     for (int64_t i = 0; i < nreads; i++) {
         const int64_t len = offsets[i + 1] - offsets[i];
@@ -2096,6 +2098,40 @@ extern "C" int mc_ties_coverage_read(mc_handle *h, int64_t *covered_any, int64_t
     return h->ab.read_figures(true, covered_any, spanned_any, max_depth_any);
 }
 
+// the rarefaction curve: K points (ascending, each >= 1) turn it on and zero every counter; K == 0 turns it off
+extern "C" int mc_set_curve(mc_handle *h, int32_t K, const int64_t *points)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_curve: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (K == 0) return h->ab.set_curve(0, nullptr);
+    if (K < 0 || K > MC_CURVE_MAXK) { g_err = "mc_set_curve: K " + std::to_string(K) + " is not a number of points from 0 to " + std::to_string(MC_CURVE_MAXK); return -1; }
+    if (!points) { g_err = "mc_set_curve: " + std::to_string(K) + " points and a NULL array"; return -1; }
+    if (!h->ab.on) { g_err = "mc_set_curve: abundance counting is off (mc_set_abundance) - the curve is that of the reads it counts (K = " + std::to_string(K) + ")"; return -1; }
+    unsigned long long pts[MC_CURVE_MAXK];
+    for (int32_t k = 0; k < K; k++) {
+        if (points[k] < 1) { g_err = "mc_set_curve: point " + std::to_string(k) + " is " + std::to_string(points[k]) + ": below 1"; return -1; }
+        if (k && points[k] < points[k - 1]) { g_err = "mc_set_curve: point " + std::to_string(k) + " is " + std::to_string(points[k]) + ": below the point before it, " + std::to_string(points[k - 1]); return -1; }
+        pts[k] = (unsigned long long)points[k];
+    }
+    return h->ab.set_curve(K, pts);
+}
+
+// reads, aligned, covered (or NULL): K x nseq values, point by point; assigned: K values; beyond: the reads behind the last point
+extern "C" int mc_curve_read(mc_handle *h, int64_t *reads, int64_t *aligned, int64_t *covered, int64_t *assigned, int64_t *beyond)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.curve) { g_err = "mc_curve_read: the curve is off (mc_set_curve)"; return -1; }
+    if (covered && !h->ab.cov) { g_err = "mc_curve_read: covered asked for with coverage off (mc_set_coverage; K = " + std::to_string(h->ab.K) + ")"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_curve(reads, aligned, covered, assigned, beyond);
+}
+
+// the number of points the curve is on with; 0: off
+extern "C" int32_t mc_curve_k(const mc_handle *h) { return h && h->ab.curve ? h->ab.K : 0; }
+
+// k_curve's time over the completed ranges plus the scans' at the reads, since the last zeroing
+extern "C" float mc_curve_ms(const mc_handle *h) { return h ? h->ab.curve_ms + h->ab.cscan_ms : 0.0f; }
 extern "C" float mc_abundance_ms(const mc_handle *h) { return h ? h->ab.ms : 0.0f; }
 extern "C" float mc_coverage_ms(const mc_handle *h) { return h ? h->ab.cov_ms : 0.0f; }
 extern "C" float mc_ties_ms(const mc_handle *h) { return h ? h->ab.ties_ms : 0.0f; }

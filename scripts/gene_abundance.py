@@ -42,6 +42,9 @@ def parse_arguments(argv=None):
     p.add_argument("--depth-out", dest="depth_out", type=str, default=None, metavar="FILE", help="write the per-residue depth as gene, start, end, depth (0-based start, exclusive end); implies --coverage")
     p.add_argument("--ties", dest="ties", action="store_true", default=False, help="add unique_reads, candidate_reads, shared_reads and rpkg_shared: the genes that tie for a read's highest bit score share the read "
                    "(with --coverage also covered_any_aa and breadth_any, with --min-breadth detected_any, with --groups the groups' unique and shared reads)")
+    p.add_argument("--curve", dest="curve", type=int, default=None, metavar="K", help="a rarefaction curve: the table's figures at K nested prefixes of the sample (1 - 64), as runs with -n n_k would give them; "
+                   "writes <out>.curve.tsv.  The reads are sampled to the end before the search starts; the tie columns are not rarefied")
+    p.add_argument("--curve-genes", dest="curve_genes", type=str, default=None, metavar="FILE", help="with --curve: write the per-gene matrix, gene, reads_1 .. reads_K (and covered_aa_1 .. covered_aa_K with coverage)")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):
