@@ -242,7 +242,11 @@ __device__ unsigned long long g_fh_worst[12];   // the slowest read of the launc
 // the heap words of a heavy read: in its own scratch, behind the place of its rows (at most n rows of 72 bytes; the area holds 96 n
 // bytes and the words need 4 n + 8)
 static_assert(sizeof(McRow) == 72 && sizeof(McHsp) == 48, "mc_heavy_words: rows of 72 bytes in an area of 2 x 48 bytes per HSP");
-__device__ __forceinline__ uint32_t *mc_heavy_words(McHsp *tmp, uint32_t a, int n) { return (uint32_t *)((uint8_t *)(tmp + 2 * (size_t)a) + (size_t)sizeof(McRow) * n); }
+// (where they lie from `base` for a read whose segment of n HSPs starts at a - the kernels' bytes of tmp; from 0, for a host that
+// places or reads them, the byte offset)
+template <class B> __host__ __device__ __forceinline__ B mc_heavy_words_from(B base, uint32_t a, int n) { return base + 2 * (size_t)a * sizeof(McHsp) + (size_t)sizeof(McRow) * n; }
+static inline size_t mc_heavy_words_at(uint32_t a, int n) { return mc_heavy_words_from<size_t>(0, a, n); }
+__device__ __forceinline__ uint32_t *mc_heavy_words(McHsp *tmp, uint32_t a, int n) { return (uint32_t *)mc_heavy_words_from((uint8_t *)tmp, a, n); }
 
 // MergeRes' heap sort for the heavy reads, ONE LANE PER READ: the sort replays libstdc++'s exact sequence of moves and is a chain
 // of dependent LDS accesses - as lane 0 of the read's own wave it was half of the heavy kernels' time (cycle counters), with 63

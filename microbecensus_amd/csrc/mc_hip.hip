@@ -7,6 +7,7 @@
 //   k_gapped.h         B   gapped X-drop: one DP per distinct segment, a lane per flank, DP rows packed in LDS
 //   k_order.h          C   HSPs binned per read (no global sort), ordered and stacked for the reads that can print
 //   k_finish.h         D   sum statistics, std::sort / heap sort replayed, 500-row cap, classification; rows in m8 order
+//   mc_stages.h            (host) the launches of A - D: grids, LDS sizes, forks and joins, over raw pointers; the stages below sequence them, the unit tests' harnesses share them
 //   k_grid.h               the training workflow's grid classification
 //   k_simulate.h           the library simulator of the training workflow and of mock communities: the kernels, the genome's placer
 //   k_community.h          the placer of a mock community of genomes (mc_community_*)
@@ -30,6 +31,7 @@
 #include "k_gapped.h"
 #include "k_order.h"
 #include "k_finish.h"
+#include "mc_stages.h"
 #include "k_grid.h"
 #include "k_simulate.h"
 #include "k_community.h"
@@ -68,7 +70,7 @@ struct McCtx {
     McDev<uint64_t> d_k64, d_hkeys, d_hplace, d_places; McDev<uint32_t> d_idx, d_idxo, d_heads, d_scan, d_gsz, d_nv, d_ghist;
     McDev<uint32_t> d_counters;
     McDev<McRow> d_rows; McDev<uint32_t> d_nrow, d_rowoff; McDev<McBestHit> d_best, d_bestof; McDev<uint8_t> d_low, d_cand;
-    McDev<McGapCell> d_gws_full; McDev<uint32_t> d_retry, d_retry2; int gap_threads_full = 0;
+    McDev<McGapCell> d_gws_full; McDev<uint32_t> d_retry, d_retry2;
     McDev<unsigned long long> d_gtab; uint32_t gtab_slots = 0; McDev<uint32_t> d_gleader; McDev<McFlankOut> d_fout;
     // pinned host mirrors
     McPin<uint32_t> h_c; McPin<unsigned long long> h_stats; McPin<McBestHit> h_best; size_t h_best_cap = 0;
@@ -152,6 +154,67 @@ static McIndex dev_index(const mc_handle *h)
     McIndex X; X.res = h->d_res; X.off = h->d_off; X.bstart = h->d_bstart; X.post = h->d_post; X.post8 = h->d_post8; X.keys = h->d_keys; X.rec = h->d_rec; X.filt = h->d_filt; X.wild = h->d_wild; X.pair = h->d_pair; X.rt = h->d_rt; X.rt_mask = h->H.rt_mask; X.nseq = h->H.nseq;
     return X;
 }
+
+static McRun run_of(const mc_handle *h) { return {h->d_T, dev_index(h), h->d_P, h->d_fam, h->read_len, h->FP}; }
+static McFork fork_of(const McCtx &c) { return {c.side, c.side2, c.ev_fork, c.ev_join, c.ev_join2}; }
+
+// ---- The carving of the pools: what each stage's launch function (mc_stages.h) is given of them ---------------------------------
+// The ONLY place that writes an offset into d_retry, d_retry2, d_k64, d_idx, d_idxo or d_tmp.  A stage borrows what another has
+// finished with; beside every borrowed region stands what is written there and the condition under which that fits.  The conditions
+// in the capacities alone are checked where the pools are sized (carve_fits, ensure_capacity); DESIGN.md 5.9 has the table.
+// With cap = cap_reads and G = cap_gaps:  d_retry has 2 G + cap + 1 words, d_retry2 2 G, d_k64 cap_hsps of 8 bytes, d_idx and d_idxo
+// cap_hsps of 4, d_tmp 2 cap_hsps McHsp.  G / 2 rounds down, so [0, G / 2) and [G / 2, G) hold G / 2 and G - G / 2 >= G / 2 words.
+
+// A1: every array is its own pool
+static McSeedBufs carve_seed(const mc_handle *h, const McCtx &c)
+{
+    return {c.d_frames, h->d_bitmap, c.d_tasks, c.cap_tasks, c.d_counters, c.d_stats, c.d_hsps, c.cap_hsps, c.d_gaps, c.cap_gaps, h->best_only ? c.d_cand.get() : nullptr, c.d_hkeys, c.d_low, c.d_hplace};
+}
+// B.  Borrowed from the HSP ordering, idle until stage C: the flanks' 2 ngaps sort keys of 4 bytes in d_k64 (8 cap_hsps bytes), the
+// 2 ngaps flanks in d_idx, their sorted list in d_idxo (4 cap_hsps bytes each): 2 ngaps <= cap_hsps, which depends on the range and
+// is checked per range (stage_b).  Its own: retry, retry2 - flanks that leave a window, at most 2 ngaps <= 2 G of 2 G words.
+static McGapBufs carve_gap(const mc_handle *h, const McCtx &c, uint32_t slots)
+{
+    McGapBufs B = {};
+    B.frames = c.d_frames; B.gaps = c.d_gaps; B.counters = c.d_counters;
+    B.tab = c.d_gtab; B.slots = slots; B.leader = c.d_gleader; B.hist = c.d_ghist;
+    B.key = (uint32_t *)c.d_k64.get(); B.item = c.d_idx; B.list = c.d_idxo;
+    B.fout = c.d_fout; B.retry = c.d_retry; B.retry2 = c.d_retry2; B.ws_full = c.d_gws_full;
+    B.hsps = c.d_hsps; B.cap_hsps = c.cap_hsps; B.cand = h->best_only ? c.d_cand.get() : nullptr; B.hkeys = c.d_hkeys; B.low = c.d_low; B.hplace = c.d_hplace;
+    return B;
+}
+// C.  keys, slots, order in d_k64, d_idxo, d_idx (the gapped stage's sort buffers: free again) - one entry per binned HSP of at most
+// cap_hsps, their own size.  Borrowed from the gapped stage, whose retry lists are done: the three lists of k_order_lists in d_retry2
+// at 0, G and G + G / 2 - each lists a read at most once, n <= cap entries, in regions of G, G / 2 and G - G / 2 words: cap <= G / 2.
+// scratch: all of d_tmp, 12 words of 8 bytes per HSP of a segment at 12 x its first slot - the two McHsp of 48 bytes d_tmp has per slot.
+static McOrderBufs carve_order(const mc_handle *h, const McCtx &c)
+{
+    const size_t G = c.cap_gaps;
+    McOrderBufs B = {};
+    B.hkeys = c.d_hkeys; B.hplace = c.d_hplace; B.cap_hsps = c.cap_hsps; B.cand = h->best_only ? c.d_cand.get() : nullptr; B.counters = c.d_counters;
+    B.heads = c.d_heads; B.scan = c.d_scan; B.keys = c.d_k64; B.places = c.d_places; B.slots = c.d_idxo; B.order = c.d_idx;
+    B.heavy = c.d_retry2; B.heavy2 = c.d_retry2 + G; B.heavy3 = c.d_retry2 + G + G / 2;
+    B.low = c.d_low; B.gsz = c.d_gsz; B.nv = c.d_nv; B.nrow = c.d_nrow; B.scratch = (uint64_t *)c.d_tmp.get(); B.hsps = c.d_hsps; B.v = c.d_v;
+    return B;
+}
+// D.  All eight lists are borrowed: d_retry is free again (the gap tasks are done), and so is d_retry2 (the ordering kernels' lists:
+// done).  Each of heavy .. heap_order holds a read, or an entry of heavy, at most once: nheads <= cap entries in a region of at least
+// G / 2 words - cap <= G / 2 again.  The four light lists lie at pitch cap + 1 behind d_retry + G + G / 2 and end at
+// G + G / 2 + 4 (cap + 1) of the array's 2 G + cap + 1 words: 3 (cap + 1) <= G - G / 2.
+static McFinishBufs carve_finish(const McCtx &c)
+{
+    const size_t G = c.cap_gaps;
+    McFinishBufs B = {};
+    B.nv = c.d_nv; B.heads = c.d_heads; B.v = c.d_v; B.tmp = c.d_tmp; B.nrow = c.d_nrow; B.rowoff = c.d_rowoff; B.scan = c.d_scan;
+    B.best_of = c.d_bestof; B.best = c.d_best; B.counters = c.d_counters; B.rows = c.d_rows; B.cap_rows = c.cap_rows;
+    B.heavy = c.d_retry; B.heavy2 = c.d_retry + G / 2; B.heavy3 = c.d_retry + G; B.light = c.d_retry + G + G / 2; B.light_pitch = (uint32_t)c.cap_reads + 1;
+    B.heavy1 = c.d_retry2; B.sorted1 = c.d_retry2 + G / 2; B.heap_order = c.d_retry2 + G; B.sorted2 = c.d_retry2 + G + G / 2;
+    return B;
+}
+// The conditions above that depend on the capacities alone.  They hold for every batch the library accepts: cap <= 2^21 - 1, and
+// G = min(cap (L / 8 + 8) + 2^18 + ev_pad, 2^27 - 2) with L >= 18 is at least 10 cap + 2^18 unclipped - 3 (cap + 1) <= 5 cap + 2^17 -
+// and 2^27 - 2 clipped, where G - G / 2 = 2^26 - 1 >= 3 x 2^21.  The stronger one implies the other.
+static bool carve_fits(int64_t cap, int64_t G) { return cap <= G / 2 && 3 * (cap + 1) <= G - G / 2; }
 
 extern "C" void mc_debug_live(int64_t out[4]) { for (int k = 0; k < MC_LIVE_N; k++) out[k] = mc_live[k].load(); }
 
@@ -262,7 +325,7 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
             (!H.rec.empty() && up.put(h->d_rec, H.rec.data(), H.rec.size() * sizeof(McBucketRec))) || up.finish()) return -1;
     }
     if (H.nseq > 32767) { g_err = "marker database too large: more than 32,767 sequences (MC_POST8)"; return -1; }
-    k_post8<<<dim3((unsigned)((H.post.size() + 255) / 256)), dim3(256)>>>(h->d_post, h->d_off, h->d_res, (uint32_t)H.post.size(), h->d_post8);
+    if (mc_post8_launch(h->d_post, h->d_off, h->d_res, (uint32_t)H.post.size(), h->d_post8, nullptr)) return -1;
     HIPCK(hipDeviceSynchronize());
     MC_OT("  index upload", t0);
     if (H.max_bucket > 2047) { g_err = "a seed bucket holds more than 2047 postings: the hit-order key cannot index it"; return -1; }
@@ -461,13 +524,13 @@ static int ensure_capacity(mc_handle *h, McCtx &c, int64_t nreads)
     // allocating the pools of a 1 M-read batch took 0.8 s, most of the wall time of the reference's default run; a denser batch is split)
     c.cap_hsps = (uint32_t)std::min<int64_t>(cap * (L / 3 + 8) + (1 << 20) + ev_pad, 0x7fffffff);
     c.cap_rows = (uint32_t)std::min<int64_t>(cap * 16 + (1 << 20), 0x7fffffff);
-    c.gap_threads_full = 16 * 1024;                                 // full-size DP rows for the last-resort launch (460 MB)
+    if (!carve_fits(cap, c.cap_gaps)) { g_err = "internal: the gap task pool is too small for the lists the ordering and finishing stages keep in it"; return -1; }   // (never, for a batch the library accepts: carve_fits)
     if (c.d_frames_base[0].alloc((size_t)cap * 6 * h->FP + 128) || c.d_frames_base[1].alloc((size_t)cap * 6 * h->FP + 128) || c.d_tasks.alloc(c.cap_tasks) ||
         c.d_gaps.alloc(c.cap_gaps) || c.d_hsps.alloc(c.cap_hsps) || c.d_v.alloc(c.cap_hsps) ||
         c.d_tmp.alloc((size_t)c.cap_hsps * 2) || c.d_k64.alloc(c.cap_hsps) || c.d_hkeys.alloc(c.cap_hsps) || c.d_hplace.alloc(c.cap_hsps) || c.d_places.alloc(c.cap_hsps) || c.d_idx.alloc(c.cap_hsps) ||
         c.d_idxo.alloc(c.cap_hsps) || c.d_heads.alloc((size_t)cap + 2) || c.d_scan.alloc((size_t)4100) || c.d_gsz.alloc(c.cap_hsps) || c.d_nv.alloc((size_t)cap + 1) || c.d_rows.alloc(c.cap_rows) ||
         c.d_low.alloc((size_t)cap + 64) || c.d_cand.alloc((size_t)cap + 64) || c.d_nrow.alloc((size_t)cap + 1) || c.d_rowoff.alloc((size_t)cap + 1) || c.d_best.alloc((size_t)cap + 1) || c.d_bestof.alloc((size_t)cap + 1) ||
-        c.d_gws_full.alloc((size_t)c.gap_threads_full * MC_GAP_W) || c.d_retry.alloc((size_t)c.cap_gaps * 2 + (size_t)cap + 1) || c.d_retry2.alloc((size_t)c.cap_gaps * 2) || c.d_gleader.alloc((size_t)c.cap_gaps) ||
+        c.d_gws_full.alloc((size_t)MC_GAP_THREADS_FULL * MC_GAP_W) || c.d_retry.alloc((size_t)c.cap_gaps * 2 + (size_t)cap + 1) || c.d_retry2.alloc((size_t)c.cap_gaps * 2) || c.d_gleader.alloc((size_t)c.cap_gaps) ||
         c.d_fout.alloc((size_t)c.cap_gaps * 2))
         return -1;
     c.frames_use(h->ahead.cur);
@@ -583,24 +646,9 @@ static int exp_timing_dump(mc_handle *, McCtx &, char) { return 0; }
 // other buffer, d_low and the counters, and A0 may run beside all of it (ahead_issue).
 static int stage_a0(mc_handle *h, McCtx &c, hipStream_t st, const uint8_t *reads, uint8_t *into, int64_t at, int64_t n, hipEvent_t e0, hipEvent_t e1)
 {
-    const int L = h->read_len, FP = h->FP;
-    uint8_t *frames = into + at * 6 * FP;                         // (FP is a multiple of 4: the kernel's word stores stay aligned)
+    uint8_t *frames = into + at * 6 * h->FP;                      // (FP is a multiple of 4: the kernel's word stores stay aligned)
     HIPCK(hipEventRecord(e0, st));
-    const size_t lds_rest = (size_t)MC_TS_NLNF(FP) * 8 + (size_t)MC_TS_THREADS * MC_TS_STRIDE(FP);
-    const size_t lds_staged = (size_t)MC_TS_STAGE(L) + lds_rest, lds_direct = (size_t)MC_TS_STAGE(0) + lds_rest;
-    static const int ts_force = getenv("MC_TS_STAGED") ? atoi(getenv("MC_TS_STAGED")) : -1;
-    const size_t cu_lds = 160 * 1024 - 1024;                      // (static LDS of the kernel and allocation granules)
-    const bool staged = ts_force >= 0 ? ts_force != 0 : cu_lds / lds_staged >= cu_lds / lds_direct;   // staging stays while it does not cost a resident workgroup
-    const size_t lds = staged ? lds_staged : lds_direct;
-    c.ts_staged = staged ? 1 : 0;
-    const unsigned ts_blocks = (unsigned)((n + MC_TS_READS - 1) / MC_TS_READS);
-    if (staged) {
-        if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_translate_seg<true><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, reads, L, n, frames, FP, h->d_segtab);
-    } else {
-        if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_translate_seg<false><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(h->d_T, reads, L, n, frames, FP, h->d_segtab);
-    }
+    if (mc_translate_launch(h->d_T, h->d_segtab, reads, h->read_len, h->FP, n, frames, st, &c.ts_staged)) return -1;
     HIPCK(hipEventRecord(e1, st));
     return 0;
 }
@@ -610,9 +658,7 @@ static int stage_a0(mc_handle *h, McCtx &c, hipStream_t st, const uint8_t *reads
 static int stage_a(mc_handle *h, McCtx &c, int64_t covered)
 {
     const int64_t n = c.n;
-    const int L = h->read_len, FP = h->FP;
     hipStream_t st = c.stream;
-    McIndex X = dev_index(h);
     c.ntasks = c.ngaps = c.gpad = c.nh = c.nheads = c.nrows = c.nbest = c.nsegs = 0;
     HIPCK(hipMemsetAsync(c.d_counters, 0, sizeof(uint32_t) * C_N, st));
     HIPCK(hipMemsetAsync(c.d_stats, 0, sizeof(unsigned long long) * S_N, st));
@@ -620,83 +666,34 @@ static int stage_a(mc_handle *h, McCtx &c, int64_t covered)
     HIPCK(hipMemsetAsync(c.d_low, 0, (size_t)n, st));
     c.own_a0 = covered < n;
     if (!c.own_a0) HIPCK(hipEventRecord(c.ev[1], st));             // (the seed kernel's interval starts here: the stream has waited for the lookahead)
-    else if (stage_a0(h, c, st, c.reads + covered * L, c.d_frames, covered, n - covered, c.ev[0], c.ev[1])) return -1;
+    else if (stage_a0(h, c, st, c.reads + covered * h->read_len, c.d_frames, covered, n - covered, c.ev[0], c.ev[1])) return -1;
     if (exp_timing_dump(h, c, 'a')) return -1;
-    const int64_t threads = n * 6;
-    if (h->fast_enum) {
-        // k_enumerate_q (round 5: queues that persist across the reads of a chunk) is the kernel of the product path; the counting form
-        // (mc_set_counting: what the reference would read) is k_enumerate_count (rounds 2 - 4's one-wave-per-read kernel without filters).
-        const bool enq = !h->count_traffic;
-        const size_t per_wave = enq ? MC_ENQ_WAVE_LDS(FP, L) : sizeof(McEnWave) + MC_EN_WAVE_LDS(FP, L);
-        // Launch shape.  k_enumerate_q: SIXTEEN waves per CU (2 workgroups of 8) where the LDS holds them - the kernel is bound by the
-        // scattered lines its CU's vector L1 has to fetch, not by issue or latency, and more resident waves only thrash
-        // that cache: per 1 M reads of 100 / 150 / 300 bp 24 (20 at 300 bp) waves 3.85 / 6.23 / 13.29 ms, 16 waves 3.77 / 6.11 / 13.21.
-        // The counting form (rounds 2 - 4's kernel, issue bound): as many as fit, up to 24 (16 waves 6.77 ms, 20: 6.45, 24: 6.39).
-        int waves = 0, bpc = 1;
-        {
-            static const int shapes_q[][2] = {{8, 2}, {4, 4}, {16, 1}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
-            static const int shapes_c[][2] = {{12, 2}, {8, 3}, {4, 6}, {4, 5}, {16, 1}, {8, 2}, {4, 4}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
-            if (enq) { for (const auto &sh : shapes_q) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; } }
-            else for (const auto &sh : shapes_c) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; }
-        }
-        if (!waves) { g_err = "reads too long for the seed kernel's LDS layout"; return -1; }
-        const size_t lds2 = 64 + waves * per_wave;
-#define MC_LAUNCH_EN(KERNEL, WV)                                                                                                                   \
-    do {                                                                                                                                           \
-        HIPCK(hipFuncSetAttribute((const void *)KERNEL<WV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));                               \
-        const int blocks_ = (int)std::min<int64_t>((int64_t)256 * bpc, (n + WV - 1) / WV);                                                         \
-        KERNEL<WV><<<dim3(blocks_), dim3(64 * WV), lds2, st>>>(h->d_T, X, h->d_bitmap, c.d_frames, FP, L, n, c.d_tasks, c.cap_tasks, c.d_counters, c.d_stats); \
-    } while (0)
-        if (enq) { if (waves == 16) MC_LAUNCH_EN(k_enumerate_q, 16); else if (waves == 12) MC_LAUNCH_EN(k_enumerate_q, 12); else if (waves == 8) MC_LAUNCH_EN(k_enumerate_q, 8); else MC_LAUNCH_EN(k_enumerate_q, 4); }
-        else { if (waves == 16) MC_LAUNCH_EN(k_enumerate_count, 16); else if (waves == 12) MC_LAUNCH_EN(k_enumerate_count, 12); else if (waves == 8) MC_LAUNCH_EN(k_enumerate_count, 8); else MC_LAUNCH_EN(k_enumerate_count, 4); }
-#undef MC_LAUNCH_EN
-    } else
-        k_enumerate<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(h->d_T, X, c.d_frames, FP, L, n, c.d_tasks, c.cap_tasks, c.d_counters, c.d_stats);
+    const McRun R = run_of(h);
+    const McSeedBufs B = carve_seed(h, c);
+    const McSeedKernel kind = !h->fast_enum ? MC_SEED_PLAIN : h->count_traffic ? MC_SEED_COUNTING : MC_SEED_QUEUES;
+    if (mc_enumerate_launch(R, B, n, kind, st)) return -1;
     HIPCK(hipEventRecord(c.ev[2], st));
-    // the number of seed hits stays on the device: persistent workgroups walk the pool
-    const size_t lds_ev = (size_t)(MC_EV_BS / 64) * MC_EV_QCAP * 32;   // a queue of survivors per wave: 32 KB per workgroup
-    const bool ranges = h->fast_enum && !h->count_traffic;            // k_enumerate_q writes ranges of hits, the other two seed kernels single hits
-    HIPCK(hipFuncSetAttribute(ranges ? (const void *)k_eval_seeds<true> : (const void *)k_eval_seeds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ev));
-    if (ranges) k_eval_seeds<true><<<dim3(256u * MC_EV_BPC), dim3(MC_EV_BS), lds_ev, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_tasks, c.d_counters + C_TASKS, c.cap_tasks, c.d_hsps, c.cap_hsps, c.d_gaps, c.cap_gaps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
-    else k_eval_seeds<false><<<dim3(256u * MC_EV_BPC), dim3(MC_EV_BS), lds_ev, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_tasks, c.d_counters + C_TASKS, c.cap_tasks, c.d_hsps, c.cap_hsps, c.d_gaps, c.cap_gaps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
+    if (mc_eval_seeds_launch(R, B, kind == MC_SEED_QUEUES, st)) return -1;
     HIPCK(hipEventRecord(c.ev[3], st));
     return counters_to_host(c);
 }
 
-// B: gapped extension
+// B: gapped extension (mc_gap_launch)
 static int stage_b(mc_handle *h, McCtx &c)
 {
-    const int L = h->read_len, FP = h->FP;
     hipStream_t st = c.stream;
-    McIndex X = dev_index(h);
     if (c.h_c[C_OVERFLOW]) { g_err = "seed task / HSP / gap task buffer overflow"; return -2; }
     c.ntasks = c.h_c[C_TASKS];
     const uint32_t ngaps = c.ngaps = c.h_c[C_GAPS];                 // (slots of the pool: the padding of the waves' last blocks included)
     c.gpad = c.h_c[C_GPAD];
     if (ngaps) {
-        // 1. group the tasks that extend the same ungapped segment and list the flanks of the distinct ones (k_gap_dedupe);
-        // 2. order the flanks by DP size (a counting sort, k_gap_sort_*; the ordering kernels' buffers are idle at this point); 3. extend them with the DP rows
-        // in LDS, those whose band leaves the window again with a wider one, the rest with full-size rows; 4. every task takes its
-        // HSP from its group's flank results.  The counts of 2. - 4. stay on the device.
         uint32_t slots = 1u << 16;
         while (slots < 2 * ngaps) slots <<= 1;
         if (slots > c.gtab_slots) { if (c.d_gtab.alloc((size_t)slots)) return -1; c.gtab_slots = slots; }
-        // The flank sort borrows the buffers of the HSP ordering: 2 ngaps keys in d_k64 (8 cap_hsps bytes), 2 ngaps items in d_idx /
-        // d_idxo (4 cap_hsps bytes each).  The pools are sized so that ordinary batches fit (ensure_capacity); a batch
-        // dense in gap tasks that does not is an overflow like any other: the range is run again in halves.
+        // The flank sort borrows the buffers of the HSP ordering (carve_gap).  The pools are sized so that ordinary batches fit
+        // (ensure_capacity); a batch dense in gap tasks that does not is an overflow like any other: the range is run again in halves.
         if (2 * (uint64_t)ngaps > c.cap_hsps) { g_err = "gap task pool larger than the sort buffers"; return -2; }
-        uint32_t *gk = (uint32_t *)c.d_k64.get(), *gi = c.d_idx, *gio = c.d_idxo;
-        HIPCK(hipMemsetAsync(c.d_gtab, 0, (size_t)slots * 8, st));
-        HIPCK(hipMemsetAsync(c.d_ghist, 0, MC_GS_BINS * sizeof(uint32_t), st));
-        k_gap_dedupe<<<dim3((ngaps + 255) / 256), dim3(256), 0, st>>>(X, L, c.d_gaps, ngaps, c.d_gtab, slots - 1, c.d_gleader, gk, gi, c.d_counters);
-        k_gap_sort_hist<<<dim3(512), dim3(256), 0, st>>>(gk, c.d_counters + C_ITEMS, 2 * ngaps, c.d_ghist);
-        k_gap_sort_scan<<<dim3(1), dim3(1024), 0, st>>>(c.d_ghist);
-        k_gap_sort_scatter<<<dim3(512), dim3(256), 0, st>>>(gk, gi, c.d_counters + C_ITEMS, 2 * ngaps, c.d_ghist, gio);
-        k_gapped_lds<MC_GAP_WIN, 64, MC_GAP_REFILL><<<dim3(std::min<uint32_t>((2 * ngaps + 63) / 64, 256u * 8u)), dim3(64), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, gio, c.d_counters + C_ITEMS, c.d_fout,
-                                                                                                                          c.d_counters + C_RETRY, c.d_retry, c.d_counters + C_GTAKE);   // (8 waves per CU)
-        k_gapped_lds<MC_GAP_WIN2, MC_GAP_LANES2, 1><<<dim3(256u * 4u), dim3(64), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, c.d_retry, c.d_counters + C_RETRY, c.d_fout, c.d_counters + C_RETRY2, c.d_retry2, c.d_counters + C_GTAKE2);
-        k_gapped<<<dim3(c.gap_threads_full / 128), dim3(128), 0, st>>>(h->d_T, X, c.d_frames, FP, L, c.d_gaps, c.d_retry2, c.d_counters + C_RETRY2, c.d_fout, c.d_counters, c.d_gws_full, MC_GAP_W);
-        k_gap_emit<<<dim3((ngaps + 255) / 256), dim3(256), 0, st>>>(h->d_T, X, L, c.d_gaps, ngaps, c.d_gleader, c.d_fout, c.d_hsps, c.cap_hsps, c.d_counters, h->d_P, h->d_fam, h->best_only ? c.d_cand : nullptr, c.d_hkeys, c.d_low, c.d_hplace);
+        if (mc_gap_launch(run_of(h), carve_gap(h, c, slots), ngaps, st)) return -1;
     }
     HIPCK(hipEventRecord(c.ev[4], st));
     return counters_to_host(c);
@@ -710,32 +707,7 @@ static int stage_c(mc_handle *h, McCtx &c)
     const uint32_t nslots = c.h_c[C_HSPS];                         // used slots of the pool, the padding of the waves' last blocks included
     c.nh_all = nslots - c.h_c[C_HPAD];
     c.nh = c.nh_all;                                               // (best hits only: the reads that can be classified are selected on the device - cand)
-    if (c.nh) {
-        const uint32_t n = (uint32_t)c.n;
-        const uint8_t *cand = h->best_only ? c.d_cand : nullptr;
-        uint32_t *cur = c.d_heads + 1;                             // heads[0] = 0; cur[r]: counts -> starts -> ends = heads[r + 1]
-        uint64_t *keys = c.d_k64;                                  // (the gapped stage's sort buffers: free again)
-        uint32_t *slots = c.d_idxo, *order = c.d_idx, *heavy = c.d_retry2, *heavy2 = c.d_retry2 + c.cap_gaps;   // (lists of at most n reads: cap_gaps >= 10 n)
-        HIPCK(hipMemsetAsync(c.d_heads, 0, ((size_t)n + 2) * sizeof(uint32_t), st));
-        HIPCK(hipMemsetAsync(c.d_nrow, 0, ((size_t)n + 1) * sizeof(uint32_t), st));
-        HIPCK(hipMemsetAsync(order, 0xFF, (size_t)nslots * sizeof(uint32_t), st));
-        k_bin_count<<<dim3(256u * 8u), dim3(256), 0, st>>>(c.d_hkeys, c.d_counters, c.cap_hsps, cand, cur);
-        if (mc_scan_u32(cur, n, cur, c.d_scan, st)) return -1;
-        k_bin_scatter<<<dim3(256u * 8u), dim3(256), 0, st>>>(c.d_hkeys, c.d_counters, c.cap_hsps, cand, cur, c.d_hplace, keys, c.d_places, slots);
-        // the long segments beside the short ones (the few segments of more than 512 HSPs are a long tail on a nearly empty GPU)
-        uint32_t *heavy3 = heavy2 + c.cap_gaps / 2;
-        k_order_lists<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(c.d_heads, n, c.d_counters, heavy, heavy2, heavy3);
-        hipStream_t side = c.side, side2 = h->best_only ? c.side : c.side2;   // (best hits only: few reads are ordered at all - a third stream only costs)
-        HIPCK(hipEventRecord(c.ev_fork, st)); HIPCK(hipStreamWaitEvent(c.side, c.ev_fork, 0)); HIPCK(hipStreamWaitEvent(c.side2, c.ev_fork, 0));
-        HIPCK(hipFuncSetAttribute((const void *)k_order_heavy<1024, MC_ORDER_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MC_ORDER_LDS * 18)));
-        k_order_heavy<1024, MC_ORDER_LDS><<<dim3(256u), dim3(1024), MC_ORDER_LDS * 18, side>>>(keys, c.d_places, slots, c.d_heads, heavy3, c.d_counters + C_ORDER3, c.d_counters + C_OTAKE3, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp.get());
-        k_order_heavy<256, MC_ORDER_MID><<<dim3(256u * 4u), dim3(256), MC_ORDER_MID * 18, side2>>>(keys, c.d_places, slots, c.d_heads, heavy2, c.d_counters + C_ORDER2, c.d_counters + C_OTAKE2, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp.get());
-        HIPCK(hipEventRecord(c.ev_join, c.side)); HIPCK(hipEventRecord(c.ev_join2, c.side2));
-        k_order_light<<<dim3((n + MC_OL_READS - 1) / MC_OL_READS), dim3(256), 0, st>>>(keys, c.d_places, slots, c.d_heads, n, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow);
-        k_order_heavy<64, MC_ORDER_SMALL><<<dim3(256u * 16u), dim3(64), MC_ORDER_SMALL * 18, st>>>(keys, c.d_places, slots, c.d_heads, heavy, c.d_counters + C_ORDER, c.d_counters + C_OTAKE, c.d_low, order, c.d_gsz, c.d_nv, c.d_nrow, (uint64_t *)c.d_tmp.get());
-        HIPCK(hipStreamWaitEvent(st, c.ev_join, 0)); HIPCK(hipStreamWaitEvent(st, c.ev_join2, 0));
-        k_order_copy<<<dim3(256u * 8u), dim3(256), 0, st>>>(order, c.d_gsz, c.d_hsps, c.d_heads, n, c.d_v);
-    }
+    if (c.nh && mc_order_stage_launch(carve_order(h, c), (uint32_t)c.n, nslots, st, fork_of(c), h->best_only)) return -1;
     HIPCK(hipEventRecord(c.ev[5], st));
     return 0;
 }
@@ -744,64 +716,8 @@ static int stage_c(mc_handle *h, McCtx &c)
 static int stage_d(mc_handle *h, McCtx &c)
 {
     hipStream_t st = c.stream;
-    McIndex X = dev_index(h);
     const uint32_t nh = c.nh, nheads = c.nheads = nh ? (uint32_t)c.n : 0u;   // (every read has a segment, most of them empty or unmarked)
-    if (nh) {
-        // the thread-per-read kernel (reads with few HSPs) on this stream, the wave-per-read kernels one after the other on a
-        // second one (each hands the reads its LDS arrays cannot hold to the next)
-        uint32_t *d_heavy = c.d_retry, *d_heavy2 = c.d_retry + c.cap_gaps / 2, *d_heavy3 = c.d_retry + c.cap_gaps;      // (d_retry is free again: the gap tasks are done)
-        uint32_t *d_light = c.d_retry + c.cap_gaps + c.cap_gaps / 2;
-        uint32_t *d_heavy1 = c.d_retry2, *d_heap_order = c.d_retry2 + c.cap_gaps;   // (the ordering kernels' lists: done)
-        const uint32_t light_pitch = (uint32_t)c.cap_reads + 1;
-        k_heavy_lists<<<dim3((nheads + 255) / 256), dim3(256), 0, st>>>(c.d_nv, nheads, c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_light, light_pitch, h->best_only ? MC_FH_MIN_BEST : MC_FH_MIN,
-                                                                         d_heavy1, d_heavy2, d_heavy3);
-        HIPCK(hipEventRecord(c.ev_fork, st));
-        {
-            const size_t l1 = (size_t)MC_FH_N1 * 16 + 3 * (size_t)(MC_FH_N1 + 2) * 2, l2 = (size_t)MC_FH_N2 * 16 + 3 * (size_t)(MC_FH_N2 + 2) * 2, l3 = (size_t)MC_FH_N3 * 16 + 3 * (size_t)(MC_FH_N3 + 2) * 2;
-            HIPCK(hipFuncSetAttribute((const void *)k_finish_heavy<MC_FH_N3, C_HEAVY3, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
-            HIPCK(hipStreamWaitEvent(c.side, c.ev_fork, 0));
-            HIPCK(hipStreamWaitEvent(c.side2, c.ev_fork, 0));
-            // the two kernels of the larger reads (few reads, long chains, a fraction of the GPU) beside the first one.  (Round 5, kernel trace:
-            // second + third, 0.84 ms per 1 M reads, is the longer chain in front of MergeRes' heap sort; the third in front of the thread-per-read
-            // kernels on this stream, or in front of the first on its stream, made the stage 0.1 - 0.2 ms LONGER - whatever runs behind the
-            // third waits for its few long reads, and they hold 135 KB of a CU's LDS each.)
-            const unsigned wpc2 = (unsigned)std::min<size_t>(8, std::max<size_t>(1, (size_t)(158 * 1024) / (l2 + 1024)));   // waves per CU the LDS holds
-            // (the lists of the first two kernels with the longest stacks first - k_heavy_order; the third has a few dozen reads)
-            uint32_t *d_sorted1 = c.d_retry2 + c.cap_gaps / 2, *d_sorted2 = c.d_retry2 + c.cap_gaps + c.cap_gaps / 2;      // (lists of at most n reads: cap_gaps >= 10 n)
-            k_heavy_order<<<dim3(1), dim3(1024), 0, c.side2>>>(d_heavy2, c.d_counters + C_HEAVY2, d_heavy, c.d_nv, 2, d_sorted2);
-            k_finish_heavy<MC_FH_N2, C_HEAVY2, -1><<<dim3(256 * wpc2), dim3(64), l2, c.side2>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
-                                                                                            c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_sorted2, nullptr);
-            k_finish_heavy<MC_FH_N3, C_HEAVY3, -1><<<dim3(256), dim3(64), l3, c.side2>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
-                                                                                         c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_heavy3, nullptr);
-            HIPCK(hipEventRecord(c.ev_join2, c.side2));
-            k_heavy_order<<<dim3(1), dim3(1024), 0, c.side>>>(d_heavy1, c.d_counters + C_HEAVY1, d_heavy, c.d_nv, 0, d_sorted1);
-            k_finish_heavy<MC_FH_N1, C_HEAVY1, -1><<<dim3(256 * 12), dim3(64), l1, c.side>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id,
-                                                                                            c.d_nrow, c.d_bestof, c.d_counters, d_heavy, d_sorted1, nullptr);
-            HIPCK(hipStreamWaitEvent(c.side, c.ev_join2, 0));
-            // MergeRes' heap sort of all of them (a lane per read), then their rows (a wave per read)
-            const size_t lh = (size_t)(MC_MAX_M8 + 2) * 64 * 4;
-            HIPCK(hipFuncSetAttribute((const void *)k_heap_lanes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lh));
-            k_heap_order<<<dim3(1), dim3(1024), 0, c.side>>>(d_heavy, c.d_nrow, c.d_counters, d_heap_order);
-            k_heap_lanes<<<dim3(256), dim3(64), lh, c.side>>>(c.d_heads, nheads, nh, c.d_tmp, c.d_nrow, c.d_counters, d_heavy, d_heap_order);
-            k_heavy_rows<<<dim3(256 * 12), dim3(64), 0, c.side>>>(h->d_T, X, h->d_P, h->d_fam, c.d_heads, nheads, c.d_v, c.d_tmp, c.first_read_id, c.d_nrow, c.d_bestof, c.d_counters, d_heavy);
-            HIPCK(hipEventRecord(c.ev_join, c.side));
-        }
-        // the light reads: the four size classes side by side (the counts stay on the device; blocks past a class' count leave at once)
-        {   // (size classes 2, 3 - up to 48 / MC_FH_MIN stacked HSPs - with MC_FH_MIN items of LDS per thread, classes 0, 1 - up to 4 / 16 - with 16; the
-            // items are reached through generic pointers - mc_finish_stacked is shared with the host - and a flat access to LDS must stay
-            // below 64 KB of the workgroup's allocation: 32 and 128 threads per workgroup)
-            const size_t lb = 32 * (MC_FH_MIN * 16 + 16), ls = 128 * (16 * 16 + 16);
-            HIPCK(hipFuncSetAttribute((const void *)k_finish<32, MC_FH_MIN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-            k_finish<32, MC_FH_MIN, 2><<<dim3((nheads + 31) / 32, 2), dim3(32), lb, st>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp,
-                                                                                 c.first_read_id, c.d_nrow, c.d_bestof, d_light, light_pitch, c.d_counters + C_LIGHT0);
-            k_finish<128, 16, 0><<<dim3((nheads + 127) / 128, 2), dim3(128), ls, st>>>(h->d_T, X, h->d_P, h->d_fam, c.d_nv, c.d_heads, nheads, c.d_v, c.d_tmp,
-                                                                                     c.first_read_id, c.d_nrow, c.d_bestof, d_light, light_pitch, c.d_counters + C_LIGHT0);
-        }
-        HIPCK(hipStreamWaitEvent(st, c.ev_join, 0));
-        if (mc_scan_u32(c.d_nrow, nheads, c.d_rowoff, c.d_scan, st)) return -1;
-        if (h->rows_ever) HIPCK(hipStreamWaitEvent(st, h->ev_rows, 0));   // (the rows of the run before may still be leaving d_rows)
-        k_emit_rows<<<dim3((nheads + 255) / 256), dim3(256), 0, st>>>(c.d_heads, nheads, c.d_nrow, c.d_rowoff, c.d_tmp, c.d_rows, c.cap_rows, c.d_bestof, c.d_best, c.d_counters, h->best_only ? 0 : 1);
-    }
+    if (nh && mc_finish_launch(run_of(h), carve_finish(c), nheads, nh, c.first_read_id, h->best_only, st, fork_of(c), h->rows_ever ? (hipEvent_t)h->ev_rows : nullptr)) return -1;
     HIPCK(hipEventRecord(c.ev[6], st));
     if (exp_timing_dump(h, c, 'd')) return -1;
     HIPCK(hipMemcpyAsync(c.h_stats, c.d_stats, sizeof(unsigned long long) * S_N, hipMemcpyDeviceToHost, st));

@@ -8,16 +8,18 @@
 //   dedupe   5 one uint32: the table's slots.  k_gap_dedupe alone.
 //            OUT: leader, key, item (2 n each), the counters.
 //   sort     IN: 0 the number of sets, then per set keys, items, two uint32 (n, cap).  k_gap_sort_hist, k_gap_sort_scan,
-//            k_gap_sort_scatter with the product's grids.
+//            k_gap_sort_scatter (mc_gap_sort_launch).
 //            OUT, per set: the output list (cap entries over a fill of 0xFF), the histogram as the scatter leaves it, the 16 guard words behind the list.
 //   extend   5 the number of cases, then per case the item list and three int32: the grids of the three launches, 0 = the product's
-//            formula.  k_gapped_lds<MC_GAP_WIN, 64, MC_GAP_REFILL>, k_gapped_lds<MC_GAP_WIN2, MC_GAP_LANES2, 1>, k_gapped as stage_b
-//            (mc_hip.hip) issues them, on fresh counters, lists and results for every case.
+//            formula.  k_gapped_lds<MC_GAP_WIN, 64, MC_GAP_REFILL>, k_gapped_lds<MC_GAP_WIN2, MC_GAP_LANES2, 1>, k_gapped
+//            (mc_gap_extend_launch), on fresh counters, lists and results for every case.
 //            OUT, per case: fout with 16 guard records on either side (all over a fill of 0xEE), the two retry lists, the counters.
 //   chain    5 two uint32 (table slots, capacity of the HSP pool), 6 one double: the bit score from which an HSP makes its read a
-//            candidate.  dedupe, sort, extend and k_gap_emit in the product's order with the product's grids.
+//            candidate.  The whole stage: dedupe, sort, extend and k_gap_emit (mc_gap_launch).
 //            OUT: the HSP pool, hkeys, hplace, low, cand, the counters, leader, fout, the guards behind pool, hkeys and hplace,
 //            loge_r, bits_r, loge_thr.
+// Every launch goes through csrc/mc_stages.h, the functions the library's own stage B calls: the grids, the counter slots and the
+// order of the kernels under test are the product's, not a copy of them.
 // A case that is no legal state of the pipeline is refused with status 2 before anything is launched; every HIP call is checked: an
 // error is printed and ends the program with status 3 at once.
 #include "mc_hip_common.h"
@@ -25,6 +27,7 @@
 #include "k_enumerate.h"
 #include "k_eval_seeds.h"
 #include "k_gapped.h"
+#include "mc_stages.h"
 
 #include <set>
 #include <tuple>
@@ -47,10 +50,7 @@ static int sort_verb(Sections &in, Sections &out)
         if (cap > (1u << 28) || (n <= cap && n > nk)) REFUSE("set %u: n = %u of %zu keys, cap %u", c, n, nk, cap);
         for (size_t i = 0; i < nk; i++) if (key[i] < 1 || key[i] > MC_GS_BINS - 1) REFUSE("set %u: key %u", c, key[i]);
         Dev<uint32_t> d_key(key, nk), d_item(item, ni), d_n(&n, 1), d_hist(MC_GS_BINS), d_out(cap, 0xFF);
-        k_gap_sort_hist<<<dim3(512), dim3(256)>>>(d_key, d_n, cap, d_hist);
-        k_gap_sort_scan<<<dim3(1), dim3(1024)>>>(d_hist);
-        k_gap_sort_scatter<<<dim3(512), dim3(256)>>>(d_key, d_item, d_n, cap, d_hist, d_out);
-        CK_LAUNCH();
+        CK_STAGE(mc_gap_sort_launch(d_key, d_item, d_n, cap, d_hist, d_out, nullptr));
         out.put(d_out.host()); out.put(d_hist.host()); out.put(d_out.pad());
     }
     return 0;
@@ -122,29 +122,23 @@ int main(int argc, char **argv)
     McIndex X; memset(&X, 0, sizeof X);
     X.res = d_res.p + 64; X.off = d_off; X.nseq = nseq;
 
-    auto dedupe = [&](uint32_t slots) {
+    // what the launch functions of csrc/mc_stages.h are given: the run, and every array of the stage as a pointer of its own
+    McRun R = {d_T, X, nullptr, nullptr, L, FP};
+    Dev<McGapCell> d_ws((size_t)MC_GAP_THREADS_FULL * MC_GAP_W);     // (full-size rows for all of the last launch's threads: 460 MB)
+    McGapBufs B = {};
+    B.frames = d_frames; B.gaps = d_tasks; B.counters = d_counters; B.leader = d_leader; B.key = d_key; B.item = d_item; B.list = d_list; B.hist = d_hist; B.ws_full = d_ws;
+    auto table = [&](uint32_t slots) {
         if (slots < 2 || (slots & (slots - 1)) || slots > (1u << 27) || slots <= segs.size()) REFUSE("%u table slots for %zu distinct segments: a power of two with a free slot", slots, segs.size());
-        Dev<unsigned long long> d_tab(slots);
-        k_gap_dedupe<<<dim3((n + 255) / 256), dim3(256)>>>(X, L, d_tasks, n, d_tab, slots - 1, d_leader, d_key, d_item, d_counters);
-        CK_LAUNCH();
-    };
-    // the three DP launches; grids 0: the product's formulas.  fout lies 16 records inside its array.
-    Dev<McGapCell> d_ws((size_t)16 * 1024 * MC_GAP_W);                // (full-size rows for the product's 16,384 threads: 460 MB)
-    auto extend = [&](const uint32_t *list, const int32_t *grid, Dev<McFlankOut> &d_fout, Dev<uint32_t> &d_retry, Dev<uint32_t> &d_retry2) {
-        const uint32_t g1 = grid[0] ? (uint32_t)grid[0] : std::min<uint32_t>((2 * n + 63) / 64, 256u * 8u), g2 = grid[1] ? (uint32_t)grid[1] : 256u * 4u, g3 = grid[2] ? (uint32_t)grid[2] : 16u * 1024u / 128u;
-        if (g1 > 2048 || g2 > 1024 || g3 > 128) REFUSE("grids %u, %u, %u", g1, g2, g3);
-        McFlankOut *fout = d_fout.p + 16;
-        k_gapped_lds<MC_GAP_WIN, 64, MC_GAP_REFILL><<<dim3(g1), dim3(64)>>>(d_T, X, d_frames, FP, L, d_tasks, list, d_counters + C_ITEMS, fout, d_counters + C_RETRY, d_retry, d_counters + C_GTAKE);
-        k_gapped_lds<MC_GAP_WIN2, MC_GAP_LANES2, 1><<<dim3(g2), dim3(64)>>>(d_T, X, d_frames, FP, L, d_tasks, d_retry, d_counters + C_RETRY, fout, d_counters + C_RETRY2, d_retry2, d_counters + C_GTAKE2);
-        k_gapped<<<dim3(g3), dim3(128)>>>(d_T, X, d_frames, FP, L, d_tasks, d_retry2, d_counters + C_RETRY2, fout, d_counters, d_ws, MC_GAP_W);
-        CK_LAUNCH();
+        return slots;
     };
 
     if (verb == "dedupe") {
         size_t ns;
         const uint32_t *slots = in.take<uint32_t>(&ns);
         if (ns != 1) REFUSE("the table's slots");
-        dedupe(slots[0]);
+        Dev<unsigned long long> d_tab(table(slots[0]));
+        B.tab = d_tab; B.slots = slots[0];
+        CK_STAGE(mc_gap_dedupe_launch(R, B, n, nullptr));
         out.put(d_leader.host()); out.put(d_key.host()); out.put(d_item.host()); out.put(d_counters.host());
     } else if (verb == "extend") {
         size_t nc;
@@ -160,13 +154,16 @@ int main(int argc, char **argv)
                 int n1, n2;
                 if (list[k] >= 2 * n || tasks[list[k] >> 1].read == MC_TASK_NONE || !flank(tasks[list[k] >> 1], (int)(list[k] & 1), n1, n2) || !seen.insert(list[k]).second) REFUSE("case %u: item %zu (%u) is no flank to extend, or listed twice", c, k, list[k]);
             }
+            const McGapGrids G = mc_gap_grids(n, grid);                // (a grid of 0: the product's)
+            if (G.lds > MC_GAP_GRID_MAX || G.lds2 > MC_GAP_GRID2 || G.full > MC_GAP_GRID_FULL) REFUSE("grids %u, %u, %u", G.lds, G.lds2, G.full);
             const uint32_t nitems = (uint32_t)nl;
-            Dev<McFlankOut> d_fout(2 * (size_t)n + 16, 0xEE);
+            Dev<McFlankOut> d_fout(2 * (size_t)n + 16, 0xEE);          // (fout lies 16 records inside its array)
             Dev<uint32_t> d_retry(2 * (size_t)n + 1, 0xFF), d_retry2(2 * (size_t)n + 1, 0xFF);
             CK(hipMemset(d_counters.p, 0, C_N * sizeof(uint32_t)));
             if (nl) CK(hipMemcpy(d_list.p, list, nl * 4, hipMemcpyHostToDevice));
             CK(hipMemcpy(d_counters.p + C_ITEMS, &nitems, 4, hipMemcpyHostToDevice));
-            extend(d_list, grid, d_fout, d_retry, d_retry2);
+            B.fout = d_fout.p + 16; B.retry = d_retry; B.retry2 = d_retry2;
+            CK_STAGE(mc_gap_extend_launch(R, B, d_list, G, nullptr));
             out.put(d_fout.host()); { std::vector<McFlankOut> p = d_fout.pad(); out.s.back().insert(out.s.back().end(), (const uint8_t *)p.data(), (const uint8_t *)(p.data() + p.size())); }
             out.put(d_retry.host()); out.put(d_retry2.host()); out.put(d_counters.host());
         }
@@ -184,17 +181,13 @@ int main(int argc, char **argv)
         Dev<McHsp> d_hsps(cap_hsps, 0xEE);
         Dev<uint64_t> d_hkeys(cap_hsps, 0xEE), d_hplace(cap_hsps, 0xEE);
         Dev<uint8_t> d_low((size_t)nreads), d_cand((size_t)nreads);
-        dedupe(sc[0]);
-        k_gap_sort_hist<<<dim3(512), dim3(256)>>>(d_key, d_counters + C_ITEMS, 2 * n, d_hist);
-        k_gap_sort_scan<<<dim3(1), dim3(1024)>>>(d_hist);
-        k_gap_sort_scatter<<<dim3(512), dim3(256)>>>(d_key, d_item, d_counters + C_ITEMS, 2 * n, d_hist, d_list);
-        CK_LAUNCH();
-        const int32_t grid[3] = {0, 0, 0};
+        Dev<unsigned long long> d_tab(table(sc[0]));
         Dev<McFlankOut> d_fout(2 * (size_t)n + 16, 0xEE);
         Dev<uint32_t> d_retry(2 * (size_t)n + 1, 0xFF), d_retry2(2 * (size_t)n + 1, 0xFF);
-        extend(d_list, grid, d_fout, d_retry, d_retry2);
-        k_gap_emit<<<dim3((n + 255) / 256), dim3(256)>>>(d_T, X, L, d_tasks, n, d_leader, d_fout.p + 16, d_hsps, cap_hsps, d_counters, d_P, d_fam, d_cand, d_hkeys, d_low, d_hplace);
-        CK_LAUNCH();
+        R.P = d_P; R.fam = d_fam;
+        B.tab = d_tab; B.slots = sc[0]; B.fout = d_fout.p + 16; B.retry = d_retry; B.retry2 = d_retry2;
+        B.hsps = d_hsps; B.cap_hsps = cap_hsps; B.cand = d_cand; B.hkeys = d_hkeys; B.low = d_low; B.hplace = d_hplace;
+        CK_STAGE(mc_gap_launch(R, B, n, nullptr));
         out.put(d_hsps.host()); out.put(d_hkeys.host()); out.put(d_hplace.host()); out.put(d_low.host()); out.put(d_cand.host()); out.put(d_counters.host());
         out.put(d_leader.host()); out.put(d_fout.host());
         out.put(d_hsps.pad()); out.put(d_hkeys.pad()); out.put(d_hplace.pad());

@@ -3,8 +3,11 @@
 // text the library compiles and copies none of it - and links neither the library nor the reader.
 //   device_order CASE IN OUT      (files of sections: order_io.h; tests/order_cases.py writes IN and reads OUT)
 // Cases: wave_sort, thread_sorts, mergesort, order, heap_lanes, counting_sorts, bins_and_scan - and adversary (host only: the frozen
-// keys of McIlroy's adversary, wave_sort_form.h).  The kernels that can be launched as they are, are, with the grids and LDS sizes
-// of their launch sites in mc_hip.hip; the wrapper kernels below (t_*) only stage a function's input in LDS and carry its result out.
+// keys of McIlroy's adversary, wave_sort_form.h).  Stage C's binning and ordering run through csrc/mc_stages.h, the launch functions
+// the library's own stage C calls - fork, joins and all; every LDS size, grid constant and the heavy words' offset come from there and
+// from k_finish.h.  Three single kernels are launched here directly (k_heap_lanes, k_heavy_order, k_heap_order: the header wraps the
+// finishing chain as a whole, and these cases feed one kernel lists and words the chain itself would never hand it); the wrapper kernels below (t_*)
+// only stage a function's input in LDS and carry its result out.
 // Expected values come from the product's host-compilable statements (mc_std_sort, mc_heapsort, mc_build_stacks) and go to OUT beside
 // the device's; the test compares.  Every HIP call is checked: an error is printed and ends the program with status 3 at once.
 #include "mc_hip_common.h"
@@ -14,6 +17,7 @@
 #include "k_gapped.h"
 #include "k_order.h"
 #include "k_finish.h"
+#include "mc_stages.h"
 
 #include "order_io.h"
 #include "wave_sort_form.h"
@@ -40,7 +44,7 @@ template <int MAXN>
 static void wave_sort_set(const uint32_t *off, size_t narr, const double *keys, size_t nkeys, Sections &out)
 {
     for (size_t b = 0; b < narr; b++) if (off[b + 1] - off[b] > (uint32_t)MAXN) { fprintf(stderr, "wave_sort: array %zu longer than %d\n", b, MAXN); exit(2); }
-    const size_t lds = (size_t)MAXN * 16 + 3 * (size_t)(MAXN + 2) * 2;
+    const size_t lds = mc_finish_heavy_lds(MAXN);
     if (lds > 48 * 1024) CK(hipFuncSetAttribute((const void *)t_wave_sort<MAXN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Dev<double> d_keys(keys, nkeys);
     Dev<uint32_t> d_off(off, narr + 1), d_perm(nkeys, 0xFF);
@@ -93,7 +97,7 @@ template <int TPB, int ITEMS>
 static void thread_sorts_set(const uint32_t *off, size_t narr, const double *keys, size_t nkeys, Sections &out)
 {
     for (size_t b = 0; b < narr; b++) if (off[b + 1] - off[b] > (uint32_t)ITEMS) { fprintf(stderr, "thread_sorts: array %zu longer than %d\n", b, ITEMS); exit(2); }
-    const size_t lds = (size_t)TPB * (ITEMS * 16 + 16);
+    const size_t lds = mc_finish_lds(TPB, ITEMS);
     if (lds > 48 * 1024) CK(hipFuncSetAttribute((const void *)t_thread_sorts<TPB, ITEMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Dev<double> d_keys(keys, nkeys);
     Dev<uint32_t> d_off(off, narr + 1);
@@ -145,10 +149,11 @@ static void mergesort_set(const uint32_t *off, size_t narr, const uint64_t *item
         const uint32_t m = off[b + 1] - off[b];
         if (m < 64 || m > CAP || (m & (m - 1))) { fprintf(stderr, "mergesort: array %zu of %u items (a power of two from 64 to %u)\n", b, m, CAP); exit(2); }
     }
-    if (CAP * 18 > 48 * 1024) CK(hipFuncSetAttribute((const void *)t_mergesort<NT, CAP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CAP * 18)));
+    const size_t lds = mc_order_heavy_lds(CAP);
+    if (lds > 48 * 1024) CK(hipFuncSetAttribute((const void *)t_mergesort<NT, CAP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Dev<uint64_t> d_in(items, nitems), d_out(nitems, 0xFF);
     Dev<uint32_t> d_off(off, narr + 1);
-    if (narr) { t_mergesort<NT, CAP><<<dim3((unsigned)narr), dim3(NT), CAP * 18>>>(d_in, d_off, d_out); CK_LAUNCH(); }
+    if (narr) { t_mergesort<NT, CAP><<<dim3((unsigned)narr), dim3(NT), lds>>>(d_in, d_off, d_out); CK_LAUNCH(); }
     out.put(d_out.host());
     std::vector<uint64_t> want(items, items + nitems);
     for (size_t b = 0; b < narr; b++) std::sort(want.begin() + off[b], want.begin() + off[b + 1]);
@@ -191,20 +196,13 @@ static void case_order(Sections &in, Sections &out)
     Dev<uint32_t> d_slots(slots, nslots), d_heads(heads, nh), d_counters((size_t)C_N), d_order(nslots, 0xFF), d_gsz(nslots), d_nv(n + 1), d_nrow(n + 1);
     Dev<uint32_t> heavy(n), heavy2(n), heavy3(n);
     Dev<uint8_t> d_low(low, n);
-    uint64_t *scratch = (uint64_t *)d_tmp.p;
-    k_order_lists<<<dim3((n + 255) / 256), dim3(256)>>>(d_heads, n, d_counters, heavy, heavy2, heavy3);
-    CK_LAUNCH();
-    CK(hipFuncSetAttribute((const void *)k_order_heavy<1024, MC_ORDER_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MC_ORDER_LDS * 18)));
-    k_order_heavy<1024, MC_ORDER_LDS><<<dim3(256u), dim3(1024), MC_ORDER_LDS * 18>>>(d_keys, d_places, d_slots, d_heads, heavy3, d_counters + C_ORDER3, d_counters + C_OTAKE3, d_low, d_order, d_gsz, d_nv, d_nrow, scratch);
-    CK_LAUNCH();
-    k_order_heavy<256, MC_ORDER_MID><<<dim3(256u * 4u), dim3(256), MC_ORDER_MID * 18>>>(d_keys, d_places, d_slots, d_heads, heavy2, d_counters + C_ORDER2, d_counters + C_OTAKE2, d_low, d_order, d_gsz, d_nv, d_nrow, scratch);
-    CK_LAUNCH();
-    k_order_light<<<dim3((n + MC_OL_READS - 1) / MC_OL_READS), dim3(256)>>>(d_keys, d_places, d_slots, d_heads, n, d_low, d_order, d_gsz, d_nv, d_nrow);
-    CK_LAUNCH();
-    k_order_heavy<64, MC_ORDER_SMALL><<<dim3(256u * 16u), dim3(64), MC_ORDER_SMALL * 18>>>(d_keys, d_places, d_slots, d_heads, heavy, d_counters + C_ORDER, d_counters + C_OTAKE, d_low, d_order, d_gsz, d_nv, d_nrow, scratch);
-    CK_LAUNCH();
-    k_order_copy<<<dim3(256u * 8u), dim3(256)>>>(d_order, d_gsz, d_pool, d_heads, n, d_v);
-    CK_LAUNCH();
+    McOrderBufs B = {};
+    B.counters = d_counters; B.heads = d_heads; B.keys = d_keys; B.places = d_places; B.slots = d_slots; B.order = d_order;
+    B.heavy = heavy; B.heavy2 = heavy2; B.heavy3 = heavy3; B.low = d_low; B.gsz = d_gsz; B.nv = d_nv; B.nrow = d_nrow;
+    B.scratch = (uint64_t *)d_tmp.p; B.hsps = d_pool; B.v = d_v;
+    Stream st, side, side2;                                         // the fork and the two joins as the library runs them: a stream of the step's own, two beside it
+    Event fork, join, join2;
+    CK_STAGE(mc_order_launch(B, n, st, McFork{side, side2, fork, join, join2}, false));
     out.put(d_v.host()); out.put(d_nv.host().data(), n); out.put(d_nrow.host().data(), n); out.put(d_counters.host());
     out.put(heavy.host()); out.put(heavy2.host()); out.put(heavy3.host());
     std::vector<McHsp> vexp(nslots + 1);
@@ -216,11 +214,11 @@ static void case_order(Sections &in, Sections &out)
 // ---- e. k_heap_lanes on heap words in the reads' scratch --------------------------------------------------------------------------
 struct HeapWord { uint32_t w; };
 inline bool mc_hless(const HeapWord &a, const HeapWord &b, int) { return (a.w >> 16) < (b.w >> 16); }
-static size_t heavy_words_at(uint32_t a, uint32_t nseg) { return ((size_t)2 * a * sizeof(McHsp) + sizeof(McRow) * (size_t)nseg) / 4; }   // mc_heavy_words, as a word offset into tmp
+static size_t heavy_words_at(uint32_t a, uint32_t nseg) { return mc_heavy_words_at(a, (int)nseg) / 4; }   // mc_heavy_words, as a word offset into tmp
 static void case_heap_lanes(Sections &in, Sections &out)
 {
     const uint32_t nsets = *in.take<uint32_t>();
-    const size_t lh = (size_t)(MC_MAX_M8 + 2) * 64 * 4;
+    const size_t lh = mc_heap_lanes_lds();
     CK(hipFuncSetAttribute((const void *)k_heap_lanes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lh));
     for (uint32_t q = 0; q < nsets; q++) {
         size_t nh, nr, nheavy, no, nw;
@@ -244,7 +242,7 @@ static void case_heap_lanes(Sections &in, Sections &out)
         std::vector<uint32_t> counters(C_N, 0u);
         counters[C_HEAVY] = (uint32_t)nheavy;
         Dev<uint32_t> d_tmp(tmp.data(), tmp.size()), d_heads(heads, nh), d_nrow(nrow, nr), d_counters(counters.data(), counters.size()), d_hf(heavy_first, nheavy), d_order(order, nheavy);
-        k_heap_lanes<<<dim3(256), dim3(64), lh>>>(d_heads, nheads, total, (McHsp *)d_tmp.p, d_nrow, d_counters, d_hf, d_order);
+        k_heap_lanes<<<dim3(MC_CUS), dim3(64), lh>>>(d_heads, nheads, total, (McHsp *)d_tmp.p, d_nrow, d_counters, d_hf, d_order);
         CK_LAUNCH();
         const std::vector<uint32_t> got = d_tmp.host();
         std::vector<uint32_t> dev, want;
@@ -311,16 +309,17 @@ static void case_bins_and_scan(Sections &in, Sections &out)
         Dev<uint64_t> d_hkeys(hkeys, nk), d_hplace(hplace, nk), d_keys(nk, 0xFF), d_places(nk, 0xFF);
         Dev<uint32_t> d_counters(counters.data(), counters.size()), d_heads((size_t)n + 2), d_scan((size_t)n / MC_SCAN_BLK + 2), d_slots(nk, 0xFF);
         Dev<uint8_t> d_cand(cand, n);
-        const uint8_t *cf = par[1] ? d_cand.p : nullptr;
+        McOrderBufs B = {};
+        B.hkeys = d_hkeys; B.hplace = d_hplace; B.cap_hsps = (uint32_t)nk; B.cand = par[1] ? d_cand.p : nullptr; B.counters = d_counters;
+        B.heads = d_heads; B.scan = d_scan; B.keys = d_keys; B.places = d_places; B.slots = d_slots;
         uint32_t *cur = d_heads.p + 1;
-        k_bin_count<<<dim3(256u * 8u), dim3(256)>>>(d_hkeys, d_counters, (uint32_t)nk, cf, cur);
-        CK_LAUNCH();
+        // (mc_bin_launch's three steps one by one: the counts and the starts are read between them)
+        CK_STAGE(mc_bin_count_launch(B, nullptr));
         out.put(d_heads.host().data() + 1, n);
         if (mc_scan_u32(cur, n, cur, d_scan, nullptr)) { fprintf(stderr, "bins: set %u: %s\n", q, g_err.c_str()); exit(2); }
         CK_LAUNCH();
         out.put(d_heads.host().data() + 1, n);
-        k_bin_scatter<<<dim3(256u * 8u), dim3(256)>>>(d_hkeys, d_counters, (uint32_t)nk, cf, cur, d_hplace, d_keys, d_places, d_slots);
-        CK_LAUNCH();
+        CK_STAGE(mc_bin_scatter_launch(B, nullptr));
         out.put(d_heads.host().data() + 1, n);
         out.put(d_keys.host()); out.put(d_places.host()); out.put(d_slots.host());
     }

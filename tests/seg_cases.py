@@ -204,7 +204,7 @@ def sparse_set(L, n, seed):
     return out
 
 
-# ---- where the launch changes the kernel's form: the expression of stage_a (csrc/mc_hip.hip) restated -------------------------
+# ---- where the launch changes the kernel's form: the expression of mc_translate_launch (csrc/mc_stages.h) restated -----------
 def launch_stages_reads(L):
     """True where the launch stages a workgroup's reads in LDS (while that costs no resident workgroup).  The GPU tests hold this
     against what the launch says it did (mc_debug_stage 5) at every length they run."""
