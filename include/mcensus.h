@@ -588,6 +588,31 @@ int32_t mc_curve_k(const mc_handle *h);
  * mc_curve_read. */
 float mc_curve_ms(const mc_handle *h);
 
+/* ---- the bootstrap of the counts: how sure an RPKG is ------------------------------------------------------------------------------
+ * csrc/mc_geneboot.h states the rule.  While it is on every read with a best row - the one mc_set_abundance counts - also appends
+ * (global read id, subject), 8 bytes, to a device list of `capacity` entries: one more kernel behind the counting kernel (and the tie and
+ * curve kernels) of every range, on the same rows where they lie.  A read that does not fit adds 1 to `dropped` and writes nothing.
+ * mc_set_gene_bootstrap(h, capacity) makes the list and zeroes it AND the abundance counters, depth, ties and curve: all describe the
+ * same reads; capacity == 0 frees everything and restores the path without it exactly.  mc_set_abundance(h, 0, ...) also turns it off;
+ * mc_abundance_reset() also empties the list and zeroes mc_gene_bootstrap_ms().
+ * Refused, with a message naming the value: capacity < 0 or > 2^31 - 1, abundance counting off, a range in flight.  While it is on
+ * mc_search_varlen is refused: its rows carry the sorted position, not the caller's read id. */
+int mc_set_gene_bootstrap(mc_handle *h, int64_t capacity);
+/* B Poisson-bootstrap replicates (1 <= B <= 4096) of the counts as they stand: replicate b weighs read q by
+ * mc_boot_weight(mc_boot_key(seed, b), q) - the weights of mc_bootstrap, so replicate b of both is the same resample of the same
+ * reads.  counts (or NULL): the replicate counts c[b][s] at [s * B + b], exact integers.  scale: B doubles; replicate b is used when
+ * scale[b] is finite and > 0, its value is (double)c[b][s] * scale[b].  stats: six doubles per subject at [6 * s]: the sum of the used
+ * values, the sum of their squared distances from their mean, and the sorted used values at floor((m - 1) * 0.025), the next,
+ * floor((m - 1) * 0.975), the next (m the number of used replicates; the next index is clamped to m - 1); all NaN with m == 0.  The sums
+ * are added in the order csrc/mc_geneboot.h writes down: the same bits on every run.  dropped (or NULL): the reads that did not fit
+ * the list; when it is not zero the call returns an error that names the number and computes nothing.  The list is only read: ranges
+ * may go on counting after a call. */
+int mc_gene_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale /* [B] */, int64_t *counts /* [nseq * B] or NULL */, double *stats /* [nseq * 6] */,
+                      int64_t *dropped);
+/* Milliseconds the gene bootstrap's kernels took since the last reset (HIP events): one kernel per completed range plus three per
+ * mc_gene_bootstrap. */
+float mc_gene_bootstrap_ms(const mc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,10 @@ def load_library():
     lib.mc_curve_k.argtypes = [C.c_void_p]
     lib.mc_curve_ms.restype = C.c_float
     lib.mc_curve_ms.argtypes = [C.c_void_p]
+    lib.mc_set_gene_bootstrap.argtypes = [C.c_void_p, C.c_int64]
+    lib.mc_gene_bootstrap.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.mc_gene_bootstrap_ms.restype = C.c_float
+    lib.mc_gene_bootstrap_ms.argtypes = [C.c_void_p]
     lib.mc_debug_live.restype = None
     lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
@@ -258,7 +262,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms",
                     "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms",
                     "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms",
-                    "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms", "mc_debug_live"]
+                    "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms",
+                    "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms", "mc_debug_live"]
 
 
 class DupSet:
@@ -1010,6 +1015,35 @@ class Engine:
     def curve_ms(self):
         """milliseconds the curve's kernels took since the last reset (HIP events): k_curve per range and one scan per curve()"""
         return float(self.lib.mc_curve_ms(self.h))
+
+    def set_gene_bootstrap(self, capacity):
+        """The bootstrap of the counts (mc_set_gene_bootstrap; csrc/mc_geneboot.h states the rule): from now on every read that
+        set_abundance assigns is also kept as (global id, gene) in a device list of `capacity` entries - the most reads that may be
+        assigned before gene_bootstrap() is called; 0 or None turns it off.  Turning it on zeroes the list AND the abundance counters,
+        depth, ties and curve.  Refused while set_abundance is off; search_varlen is refused while it is on."""
+        self._check(self.lib.mc_set_gene_bootstrap(self.h, int(capacity or 0)), "mc_set_gene_bootstrap")
+
+    def gene_bootstrap(self, B, seed, scale, counts=False):
+        """B Poisson-bootstrap replicates of the counts as they stand (mc_gene_bootstrap), under bootstrap()'s weights: {"stats":
+        float64[nseq, 6] - sum, m2, x[lo], x[lo + 1], x[hi], x[hi + 1] of the used values (double)c[b][s] * scale[b] -, "used": m,
+        "dropped": 0} and with counts=True "counts": int64[nseq, B].  scale: B doubles; replicate b is used when scale[b] is finite and
+        > 0.  Raises when a read did not fit the list (the message names how many)."""
+        B, n = int(B), len(self.names)
+        sc = np.ascontiguousarray(scale, dtype=np.float64)
+        if sc.shape != (max(B, 0),):
+            raise ValueError("scale holds %d values, B is %d" % (sc.size, B))
+        out = {"stats": np.zeros((n, 6), np.float64), "used": int((np.isfinite(sc) & (sc > 0)).sum())}
+        if counts:
+            out["counts"] = np.zeros((n, max(B, 0)), np.int64)
+        dropped = C.c_int64(0)
+        self._check(self.lib.mc_gene_bootstrap(self.h, B, int(seed) & 0xFFFFFFFFFFFFFFFF, sc.ctypes.data_as(C.c_void_p), out["counts"].ctypes.data_as(C.c_void_p) if counts else None,
+                                               out["stats"].ctypes.data_as(C.c_void_p), C.byref(dropped)), "mc_gene_bootstrap")
+        out["dropped"] = int(dropped.value)
+        return out
+
+    def gene_bootstrap_ms(self):
+        """milliseconds the gene bootstrap's kernels took since the last reset (HIP events): one kernel per range, three per gene_bootstrap()"""
+        return float(self.lib.mc_gene_bootstrap_ms(self.h))
 
     def ties_ms(self):
         """milliseconds the tie kernels took since the last reset (HIP events)"""

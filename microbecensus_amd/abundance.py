@@ -37,7 +37,15 @@ figure the table is built from at K nested prefixes of the sample, n_k = microbe
 run_pipeline's AGS curve: reads, aligned_aa and covered_aa per gene and, from them by the lines above, RPKG, reads_assigned, the genes
 with reads, the genes detected and the groups with reads.  The sampler is a head-take, so point k is, integer for integer, the table
 of a run with -n n_k, and the last point is the run's own table.  The tie columns stay whole-sample figures: the curve does not
-rarefy them."""
+rarefy them.
+
+How sure is an RPKG?  With bootstrap B (Engine.set_gene_bootstrap; csrc/mc_geneboot.h states the rule) the sampled reads are resampled B
+times with Poisson(1) weights - the weights of run_pipeline's AGS bootstrap, a pure function of (seed, replicate, read id) - and replicate
+b of the gene counts is divided by replicate b of the genome equivalents: numerator and denominator from the SAME resample.  Per gene
+
+    rpkg_boot_se = the standard deviation (ddof 1) of the replicate RPKGs     rpkg_ci95_low / _high = their 2.5th / 97.5th percentile
+
+With a given AGS (--ags, --ags-report) the denominator is fixed and the interval reflects the counts alone."""
 import gzip
 import math
 import os
@@ -57,6 +65,8 @@ TIES_COLUMNS = ("unique_reads", "candidate_reads", "shared_reads", "rpkg_shared"
 TIES_COVERAGE_COLUMNS = ("covered_any_aa", "breadth_any")                            # ... these behind them with coverage, "detected_any" last with min_breadth
 GROUP_TIES_COLUMNS = ("unique_reads", "shared_reads", "rpkg_shared")                 # behind the groups table's columns; "genes_detected_any" last with min_breadth
 CURVE_COLUMNS = ("sampled_reads", "average_genome_size", "genome_equivalents_sampled", "reads_assigned", "genes_with_reads")   # "genes_detected" behind them with min_breadth, "groups_with_reads" with groups
+BOOT_COLUMNS = ("rpkg_boot_se", "rpkg_ci95_low", "rpkg_ci95_high")                  # behind all of them with bootstrap
+MAX_BOOT = 4096                                                                      # MC_GB_MAXB (csrc/mc_geneboot.h)
 MAX_CURVE = 64                                                                       # MC_CURVE_MAXK (csrc/mc_curve.h)
 SHARE_ONE = 4294967296.0                                                             # share[] counts in units of 2^-32 (csrc/k_ties.h)
 
@@ -257,6 +267,40 @@ def read_depth(path, names, length_aa):
     return depth
 
 
+def _lerp(a, b, t):
+    """numpy's linear interpolation between two order statistics (numpy.percentile, method "linear"): a + (b - a) t, and from t = 0.5 on
+    b - (b - a) (1 - t)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    d = b - a
+    return np.where(t >= 0.5, b - d * (1 - t), a + d * t)
+
+
+def boot_scale(ags_values, reads, read_length):
+    """scale[b] = AGS_b / (L x n_b) = 1 / genome_equivalents of replicate b; NaN - the replicate is not used - where AGS_b is None or
+    the replicate drew no read"""
+    return np.array([float("nan") if a is None or n <= 0 else float(a) / (float(read_length) * float(n)) for a, n in zip(ags_values, reads)], np.float64)
+
+
+def boot_columns(stats, used, length_aa):
+    """(rpkg_boot_se, rpkg_ci95_low, rpkg_ci95_high) from the device's six doubles per gene (csrc/mc_geneboot.h: sum, m2 and the order
+    statistics x[lo], x[lo + 1], x[hi], x[hi + 1] of the `used` replicate values reads_b / genome_equivalents_b) - with
+    kb = 3 x length_aa / 1000: se = sqrt(m2 / (used - 1)) / kb, NaN with used < 2; the interval is numpy.percentile(values / kb,
+    [2.5, 97.5]): the order statistics divided by kb, interpolated at the fraction of (used - 1) x 0.025 and (used - 1) x 0.975."""
+    stats = np.asarray(stats, dtype=np.float64).reshape(-1, 6)
+    kb = 3.0 * np.asarray(length_aa, dtype=np.float64) / 1000.0
+    m = int(used)
+    if m < 1:
+        nan = np.full(len(kb), np.nan)
+        return nan, nan.copy(), nan.copy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        se = np.sqrt(stats[:, 1] / (m - 1)) / kb if m > 1 else np.full(len(kb), np.nan)
+        out = []
+        for q, col in ((0.025, 2), (0.975, 4)):
+            v = (m - 1) * q
+            out.append(_lerp(stats[:, col] / kb, stats[:, col + 1] / kb, v - math.floor(v)))
+    return se, out[0], out[1]
+
+
 def header_lines(args, table):
     h = [("metagenome", ",".join(args["seqfiles"])), ("genes", args["genes"]), ("sampled_reads", table["sampled_reads"]),
          ("trimmed_length", table["trimmed_length"]), ("min_ident", args["min_ident"]), ("min_aln", args["min_aln"]), ("min_bits", repr(float(args["min_bits"]))),
@@ -278,10 +322,15 @@ def header_lines(args, table):
 def write_table(path, args, table):
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
+        boot = table.get("rpkg_boot_se") is not None
+        if boot:                                                   # (the gene table's alone: the groups table does not bootstrap)
+            out.writelines("# %s:\t%s\n" % kv for kv in (("bootstrap", table["bootstrap"]), ("bootstrap_seed", table["bootstrap_seed"]),
+                                                         ("bootstrap_replicates", "%d/%d" % (table["boot_used"], table["bootstrap"])),
+                                                         ("bootstrap_denominator", table["bootstrap_denominator"])))
         cov, det = table.get("covered_aa") is not None, table.get("detected") is not None
         ties, tcov, tdet = table.get("unique_reads") is not None, table.get("covered_any_aa") is not None, table.get("detected_any") is not None
         out.write("\t".join(COLUMNS + (COVERAGE_COLUMNS if cov else ()) + (("detected",) if det else ()) + (TIES_COLUMNS if ties else ())
-                            + (TIES_COVERAGE_COLUMNS if tcov else ()) + (("detected_any",) if tdet else ())) + "\n")
+                            + (TIES_COVERAGE_COLUMNS if tcov else ()) + (("detected_any",) if tdet else ()) + (BOOT_COLUMNS if boot else ())) + "\n")
         for k, (nm, ln, r, a, v) in enumerate(zip(table["gene"], table["length_aa"], table["reads"], table["aligned_aa"], table["rpkg"])):
             line = "%s\t%d\t%d\t%d\t%s" % (nm, ln, r, a, repr(float(v)))
             if cov:
@@ -294,6 +343,8 @@ def write_table(path, args, table):
                 line += "\t%d\t%s" % (table["covered_any_aa"][k], repr(float(table["breadth_any"][k])))
             if tdet:
                 line += "\t%d" % table["detected_any"][k]
+            if boot:
+                line += "\t%s\t%s\t%s" % tuple(repr(float(table[c][k])) for c in BOOT_COLUMNS)
             out.write(line + "\n")
 
 
@@ -390,13 +441,28 @@ def check_request(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.get("distributed"):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
-                         ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None)):
+                         ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
+                         ("bootstrap", None), ("bootstrap_seed", None)):
         args.setdefault(key, default)
     if args["curve"] is not None:
         K = args["curve"]
         if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= MAX_CURVE:
             raise AbundanceError("--curve %s is not an integer from 1 to %d" % (K, MAX_CURVE))
         args["curve"] = int(K)
+    if args["bootstrap"] is not None:
+        B = args["bootstrap"]
+        if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MAX_BOOT:
+            raise AbundanceError("--bootstrap %s is not an integer from 1 to %d" % (B, MAX_BOOT))
+        args["bootstrap"] = int(B)
+        if args["curve"] is not None:
+            raise AbundanceError("--bootstrap %d cannot be combined with --curve %d: the curve's points are not bootstrapped" % (args["bootstrap"], args["curve"]))
+    if args["bootstrap_seed"] is not None:
+        S = args["bootstrap_seed"]
+        if args["bootstrap"] is None:
+            raise AbundanceError("--bootstrap-seed %s needs --bootstrap B: it seeds the replicates" % (S,))
+        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 0 <= int(S) < 1 << 64:
+            raise AbundanceError("--bootstrap-seed %s is not an integer from 0 to 2^64 - 1" % (S,))
+        args["bootstrap_seed"] = int(S)
     if args["curve_genes"] is not None:
         if not args["curve_genes"]:
             raise AbundanceError("--curve-genes %r is an empty path" % (args["curve_genes"],))
@@ -458,13 +524,16 @@ def run_abundance(args):
     (implies coverage), depth_out (a path; implies coverage), ties (the genes that tie for a read's best hit: unique, candidate and
     shared reads beside the counts; sets args['ties_ms']), curve (K, 1 .. 64: table['curve'], the table's figures at K prefixes of the sample
     - the sampler then runs to its end before the search starts; sets args['curve_ms']; writes <outfile>.curve.tsv) and curve_genes (a path:
-    the curve's per-gene matrix).  Writes args['outfile'] (and
+    the curve's per-gene matrix), bootstrap (B, 1 .. 4096: the columns rpkg_boot_se, rpkg_ci95_low, rpkg_ci95_high from B Poisson-bootstrap
+    replicates of the sampled reads under bootstrap_seed (default 0) - with run_pipeline's AGS every replicate is divided by its own
+    genome equivalents, with a given AGS by the fixed ones; sets args['gene_bootstrap_ms']; not combined with curve).  Writes args['outfile'] (and
     <outfile>.groups.tsv with groups) when it is set; returns (table, args) - table: the columns as arrays (gene, length_aa, reads,
     aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
     names, seqs, group_of, ags, source = check_request(args)
     microbe_census.check_input(args)
     if ags is None:             # the estimate of the same sample: run_pipeline on the marker engine, same files, same options
-        est = microbe_census.run_pipeline(dict(_pipeline_args(args), curve=args["curve"]) if args["curve"] else _pipeline_args(args))
+        more = {"curve": args["curve"]} if args["curve"] else {"bootstrap": args["bootstrap"], "bootstrap_seed": args["bootstrap_seed"] or 0} if args["bootstrap"] else {}
+        est = microbe_census.run_pipeline(dict(_pipeline_args(args), **more) if more else _pipeline_args(args))
         if est is None:
             raise AbundanceError("run_pipeline gave no AGS estimate for %s" % ",".join(args["seqfiles"]))
         ags, pargs = est
@@ -492,9 +561,21 @@ def run_abundance(args):
                 eng.set_ties(True, gids, len(gnames))
             else:
                 eng.set_ties(True)
-        cu = points = None
+        cu = points = gb = scale = None
+        B, seed = args["bootstrap"], args["bootstrap_seed"] or 0
+        if B and pargs["nreads"] is not None:       # ids lie below -n: the list is sized before the sampler starts, and it samples beside the search
+            eng.set_gene_bootstrap(int(pargs["nreads"]))
         try:
-            if args["curve"]:       # the points depend on how many reads the sampler takes: it runs to its end first, then one search
+            if B and pargs["nreads"] is None:       # no cap: the list's size is the number of reads the sampler takes - it runs to its end first
+                n = rd.run()
+                if n:
+                    eng.set_gene_bootstrap(n)
+                    eng.lib.mc_set_keep_rows(eng.h, 0)
+                    try:
+                        eng.search(rd.reads(n))
+                    finally:
+                        eng.lib.mc_set_keep_rows(eng.h, 1)
+            elif args["curve"]:       # the points depend on how many reads the sampler takes: it runs to its end first, then one search
                 n = rd.run()
                 if n:               # (no read taken: nothing is searched, and the run ends below with "No reads remaining after filtering" as without the switch)
                     points = microbe_census.curve_points(n, args["curve"])
@@ -511,6 +592,18 @@ def run_abundance(args):
         except _native.ReferenceError_ as e:
             raise AbundanceError(str(e))
         ab = eng.abundance()
+        if B and ab["searched"]:
+            if source == "run_pipeline":
+                if len(pargs.get("ags_boot_values") or []) != B or len(pargs.get("ags_boot_reads") or []) != B:
+                    raise AbundanceError("run_pipeline gave %d replicate AGS values for --bootstrap %d" % (len(pargs.get("ags_boot_values") or []), B))
+                scale = boot_scale(pargs["ags_boot_values"], pargs["ags_boot_reads"], L)
+            else:
+                scale = np.full(B, 1.0 / genome_equivalents(ab["searched"], L, ags))
+            try:
+                gb = eng.gene_bootstrap(B, seed, scale)
+            except RuntimeError as e:
+                raise AbundanceError(str(e))
+            args["gene_bootstrap_ms"] = eng.gene_bootstrap_ms()
         cov = eng.coverage() if args["coverage"] else None
         depth = eng.coverage_depth() if args["depth_out"] is not None else None
         args["abundance_ms"], args["search_ms"] = eng.abundance_ms(), eng.stats()["ms_total"]
@@ -530,7 +623,8 @@ def run_abundance(args):
         raise AbundanceError("No reads remaining after filtering")
     if "sampled_reads" in pargs and int(pargs["sampled_reads"]) != sampled or ab["searched"] != sampled:
         raise AbundanceError("the gene search saw %d reads (%d sampled), the AGS estimate %s" % (ab["searched"], sampled, pargs.get("sampled_reads")))
-    for k in ("file_type", "quality_offset", "read_length", "nreads", "min_quality", "mean_quality", "filter_dups", "max_unknown"):
+    for k in ("file_type", "quality_offset", "read_length", "nreads", "min_quality", "mean_quality", "filter_dups", "max_unknown") + (
+            ("ags_boot_se", "ags_ci95", "ags_boot_replicates", "ags_boot_values", "ags_boot_reads") if gb is not None and source == "run_pipeline" else ()):
         if k in pargs:
             args[k] = pargs[k]
     args["sampled_reads"] = sampled
@@ -559,6 +653,10 @@ def run_abundance(args):
             table["reads_ambiguous_across_groups"] = ti["group_ambiguous"]
             table["group_unique"] = ti["group_unique"]
             table["groups_ties"] = group_ties_table(gids, len(gnames), ti["group_unique"], ti["share"], table["rpkg_shared"], table.get("detected_any"))
+    if gb is not None:
+        se, lo, hi = boot_columns(gb["stats"], gb["used"], length_aa)
+        table.update({"rpkg_boot_se": se, "rpkg_ci95_low": lo, "rpkg_ci95_high": hi, "boot_used": gb["used"], "boot_stats": gb["stats"], "boot_scale": scale, "bootstrap": B,
+                      "bootstrap_seed": seed, "bootstrap_denominator": "replicate_ags" if source == "run_pipeline" else "fixed_ags"})
     if group_of is not None:
         table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of, table.get("detected"))
     if cu is not None:

@@ -1,13 +1,14 @@
 // mc_abund.h - the one owner of the per-gene counts (mc_set_abundance), the coverage depth (mc_set_coverage), the tie accounting
-// (mc_set_ties) and the rarefaction curve (mc_set_curve): where their tables lie, how their kernels are launched on the rows of a range,
-// and which buffer exists when.
-// k_abundance.h, k_coverage.h, k_ties.h and k_curve.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
-// hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip and device_curve.hip launch through mc_abund_launch like range_end.
+// (mc_set_ties), the rarefaction curve (mc_set_curve) and the bootstrap of the counts (mc_set_gene_bootstrap): where their tables lie, how
+// their kernels are launched on the rows of a range, and which buffer exists when.
+// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h and k_geneboot.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
+// hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip and device_geneboot.hip launch through mc_abund_launch like range_end.
 #pragma once
 #include "k_abundance.h"
 #include "k_coverage.h"
 #include "k_ties.h"
 #include "k_curve.h"
+#include "k_geneboot.h"
 #include "mc_owned.h"
 
 // ---- Layout: every size and offset of the four tables (k_ties.h, k_coverage.h and k_curve.h, "Layout", say what the slots hold) -----------------
@@ -32,12 +33,17 @@ struct McAbundBufs { int32_t nseq; const uint32_t *off; unsigned long long *coun
 // the curve's part of a launch (null: the curve is off).  pts: the K points on the device; bins: the bin table; first: every residue's
 // lowest covering id, or null while coverage is off; ev: recorded behind k_curve
 struct McCurveBufs { int32_t K; const unsigned long long *pts; unsigned long long *bins; uint32_t *first; hipEvent_t ev; };
+// the bootstrap's part of a launch (null: the gene bootstrap is off).  list: `capacity` entries; cur: the cursor and `dropped`
+// (k_geneboot.h); ev: recorded behind k_geneboot_collect
+struct McGeneBootBufs { McGbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
 
 // The kernels of a range's final rows (ascending read id), in `st`: the counting kernel - k_abundance_cov INSTEAD of k_abundance while
 // coverage is on, the marks ride with the counts - between ev[0] and ev[1]; with ties k_ties behind it on the same rows where they
 // lie, and ev[2] behind that; with the curve k_curve behind those on the same rows, and its event behind that.  The events are recorded
-// with nr == 0 too: whoever reads the times need not know.  Without the curve (C null) nothing more is issued than before it existed.
-static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McRow *rows, uint32_t nr, hipStream_t st, const hipEvent_t (&ev)[3], const McCurveBufs *C = nullptr)
+// with nr == 0 too: whoever reads the times need not know.  Without the curve (C null) nothing more is issued than before it existed;
+// with the gene bootstrap k_geneboot_collect behind all of those on the same rows, and its event behind that - without it (G null) nothing.
+static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McRow *rows, uint32_t nr, hipStream_t st, const hipEvent_t (&ev)[3], const McCurveBufs *C = nullptr,
+                           const McGeneBootBufs *G = nullptr)
 {
     const dim3 grid((nr + 255) / 256), block(256);
     HIPCK(hipEventRecord(ev[0], st));
@@ -49,14 +55,46 @@ static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McR
                                                B.diff_any ? B.off : nullptr, B.diff_any);
         HIPCK(hipEventRecord(ev[2], st));
     }
-    if (!C) return 0;
-    if (nr) k_curve<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, C->pts, C->K, C->bins, B.off, C->first);
-    HIPCK(hipEventRecord(C->ev, st));
+    if (C) {
+        if (nr) k_curve<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, C->pts, C->K, C->bins, B.off, C->first);
+        HIPCK(hipEventRecord(C->ev, st));
+    }
+    if (!G) return 0;
+    if (nr) k_geneboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, G->list, G->capacity, G->cur);
+    HIPCK(hipEventRecord(G->ev, st));
+    return 0;
+}
+
+// The gene bootstrap's read: raw device pointers of one mc_gene_bootstrap.  list: the n collected entries; cursor: nseq slots, every gene's
+// first slot in the grouped list; idx: nseq compact indices; sorted: n entries; mat: ngenes x B counters, zeroed; scale: B doubles, m of
+// them used; out: ngenes x 6 doubles.  mc_gb_plan makes cursor and idx from the count table on the host: nseq values, at read time.
+struct McGeneBootRead { int32_t nseq, ngenes; long long n; const McGbEntry *list; uint32_t *cursor; const int32_t *idx; McGbEntry *sorted; unsigned long long *mat;
+                        const double *scale; int32_t B, m; uint64_t seed; double *out; };
+// start[s]: the exclusive scan of reads[s]; idx[s]: the compact index of a gene with reads, -1 of one without.  Returns the genes with reads
+static int32_t mc_gb_plan(const unsigned long long *tab, int32_t nseq, uint32_t *start, int32_t *idx, unsigned long long *total)
+{
+    unsigned long long at = 0; int32_t ng = 0;
+    for (int32_t s = 0; s < nseq; s++) { const unsigned long long r = tab[mc_pair_at((size_t)s)]; start[s] = (uint32_t)at; idx[s] = r ? ng++ : -1; at += r; }
+    *total = at;
+    return ng;
+}
+// The three kernels of a read between ev[0] and ev[1], in `st`: the scatter and the sums with n > 0, the summary with ngenes > 0
+static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
+{
+    HIPCK(hipEventRecord(ev[0], st));
+    if (R.n > 0) {
+        k_geneboot_scatter<<<dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st>>>(R.list, R.n, R.nseq, R.cursor, R.idx, R.sorted);
+        const long long per = mc_gb_per_tile(R.n, R.B);
+        k_geneboot_sums<<<dim3((unsigned)((R.n + per - 1) / per), (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.n, per, R.B, R.seed, (uint32_t)R.ngenes, R.mat);
+    }
+    if (R.ngenes > 0) k_geneboot_summary<<<dim3((unsigned)R.ngenes), dim3(MC_GB_THREADS), 0, st>>>(R.mat, R.scale, R.B, R.m, R.out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(ev[1], st));
     return 0;
 }
 
 // ---- Owner --------------------------------------------------------------------------------------------------------------------
-// The four switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
+// The five switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
 //     the difference array, the scan's output, its two events                    coverage is on
 //     the tie table, its event                                                   ties are on
@@ -64,18 +102,25 @@ static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McR
 //     the any-depth's difference array                                           coverage and ties are on
 //     the curve's points, bin table, scan output, its three events                the curve is on
 //     the curve's first ids                                                       the curve and coverage are on
-// Coverage, ties and the curve are on only while the counts are.  Every switch that goes on, and reset(), zeroes ALL counters, both
-// difference arrays, the curve's bins (and refills its first ids with 0xFF), `searched` and the times: counts, depth, ties and curve
-// describe the same reads.  A switch that goes off frees its buffers and zeroes nothing of the others; the counts going off take the
-// other three with them.
+//     the bootstrap's list, its cursor and dropped counter, the grouped list,
+//     the genes' cursors and compact indices, the scales, the output, its three events   the gene bootstrap is on
+//     the bootstrap's matrix of replicate counts                                  the gene bootstrap is on and a read has sized it
+// Coverage, ties, the curve and the gene bootstrap are on only while the counts are.  Every switch that goes on, and reset(), zeroes ALL
+// counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the bootstrap's cursor and dropped counter
+// (an empty list), `searched` and the times: counts, depth, ties, curve and bootstrap describe the same reads.  A switch that goes off
+// frees its buffers and zeroes nothing of the others; the counts going off take the other four with them.
 struct McAbundance {
     int32_t nseq = 0; size_t nres = 0; const uint32_t *off = nullptr;   // the database: bind(), once the index is on the device
-    bool on = false, cov = false, ties = false, curve = false; int32_t ngroups = 0, K = 0;
+    bool on = false, cov = false, ties = false, curve = false, gboot = false; int32_t ngroups = 0, K = 0; int64_t gcap = 0;
     McAbundPars pars = {};
     McDev<unsigned long long> d_counts, d_covout, d_ties, d_pts, d_bins, d_curveout; McDev<uint32_t> d_diff, d_diff_any, d_first; McDev<int32_t> d_group;
     McEvent ev_count[2], ev_cov[2], ev_ties;                       // around the counting kernel of a range; around a scan; behind k_ties
     McEvent ev_curve, ev_cscan[2];                                 // behind k_curve; around a scan of the curve
     float curve_ms = 0, cscan_ms = 0;                              // k_curve's, the curve scans' time since the last zeroing
+    McDev<McGbEntry> d_glist, d_gsorted; McDev<unsigned long long> d_gcur, d_gmat; McDev<uint32_t> d_gcursor; McDev<int32_t> d_gidx; McDev<double> d_gscale, d_gout;
+    size_t gmat_slots = 0;                                         // what d_gmat holds: a read grows it to ngenes x B
+    McEvent ev_gboot, ev_gread[2];                                 // behind k_geneboot_collect; around the kernels of a read
+    float gboot_ms = 0, gread_ms = 0;                              // k_geneboot_collect's, the reads' time since the last zeroing
     int64_t searched = 0;                                          // the reads of the completed ranges
     float ms = 0, cov_ms = 0, ties_ms = 0;                         // the counting kernels', the scans', k_ties' time since the last zeroing
 
@@ -105,6 +150,14 @@ struct McAbundance {
         if (mc_owned_ck(hipMemcpy(d_pts, points, sizeof(unsigned long long) * (size_t)K, hipMemcpyHostToDevice), "hipMemcpy(d_pts, points)")) { (void)turn(curve, false); return -1; }
         return 0;
     }
+    // capacity: entries of the list, checked by the caller (mc_set_gene_bootstrap); 0: off.  On while on: a list of another size
+    int set_gene_bootstrap(int64_t capacity)
+    {
+        (void)turn(gboot, false);
+        if (capacity == 0) return 0;
+        gcap = capacity;
+        return turn(gboot, true);
+    }
     int reset()
     {
         HIPCK(hipMemset(d_counts, 0, sizeof(unsigned long long) * mc_pair_slots((size_t)nseq)));
@@ -113,7 +166,8 @@ struct McAbundance {
         if (d_diff_any) HIPCK(hipMemset(d_diff_any, 0, sizeof(uint32_t) * mc_diff_slots(nres, (size_t)nseq)));
         if (d_bins) HIPCK(hipMemset(d_bins, 0, sizeof(unsigned long long) * mc_curve_bin_slots((size_t)K, (size_t)nseq)));
         if (d_first) HIPCK(hipMemset(d_first, 0xFF, sizeof(uint32_t) * nres));
-        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = 0.f;
+        if (d_gcur) HIPCK(hipMemset(d_gcur, 0, sizeof(unsigned long long) * 2));
+        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = 0.f;
         return 0;
     }
 
@@ -123,13 +177,15 @@ struct McAbundance {
         const McAbundBufs B = {nseq, off, d_counts, d_diff, d_ties, d_group, d_diff_any};
         const hipEvent_t ev[3] = {ev_count[0], ev_count[1], ev_ties};
         const McCurveBufs C = {K, d_pts, d_bins, d_first, ev_curve};
-        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr);
+        const McGeneBootBufs G = {d_glist, (unsigned long long)gcap, d_gcur, ev_gboot};
+        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr);
     }
     void range_done(int64_t nreads)
     {
         add_searched(nreads); ms += ev_ms(ev_count[0], ev_count[1]);
         if (ties) ties_ms += ev_ms(ev_count[1], ev_ties);
         if (curve) curve_ms += ev_ms(ties ? ev_ties : ev_count[1], ev_curve);
+        if (gboot) gboot_ms += ev_ms(curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_gboot);
     }
     void add_searched(int64_t nreads) { if (on) searched += nreads; }   // (mc_search_varlen: reads too short to have a frame are searched, and have no rows)
 
@@ -178,6 +234,49 @@ struct McAbundance {
         if (beyond) *beyond = (int64_t)out[tot + nk];
         return 0;
     }
+    // The bootstrap of the counts as they stand (mc_geneboot.h): B replicates under `seed`, scale: B doubles.  counts (or null): nseq x B
+    // replicate counts; stats: nseq x 6 doubles; dropped: the assigned reads that did not fit the list - not zero: an error that names it,
+    // and nothing else is computed.
+    int read_gene_bootstrap(int32_t B, uint64_t seed, const double *scale, int64_t *counts, double *stats, int64_t *dropped)
+    {
+        const size_t ns = (size_t)nseq;
+        unsigned long long cur[2];
+        HIPCK(hipMemcpy(cur, d_gcur, sizeof cur, hipMemcpyDeviceToHost));
+        if (dropped) *dropped = (int64_t)cur[1];
+        if (cur[1] || cur[0] > (unsigned long long)gcap) {
+            g_err = "mc_gene_bootstrap: " + std::to_string(cur[1]) + " assigned reads did not fit the list of " + std::to_string(gcap) + " entries (mc_set_gene_bootstrap): dropped, no replicate is whole";
+            return -1;
+        }
+        std::vector<unsigned long long> tab(mc_pair_slots(ns));
+        HIPCK(hipMemcpy(tab.data(), d_counts, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> start(ns); std::vector<int32_t> idx(ns);
+        unsigned long long total = 0;
+        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
+        if (total != cur[0]) { g_err = "mc_gene_bootstrap: the count table holds " + std::to_string(total) + " assigned reads, the list " + std::to_string(cur[0]); return -1; }
+        int32_t m = 0;
+        for (int32_t b = 0; b < B; b++) m += mc_gb_used(scale[b]) ? 1 : 0;
+        const size_t need = (size_t)ng * (size_t)B;
+        if (need > gmat_slots) { gmat_slots = 0; if (d_gmat.alloc(need)) return -1; gmat_slots = need; }
+        HIPCK(hipMemcpy(d_gcursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_gidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_gscale, scale, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
+        if (need) HIPCK(hipMemsetAsync(d_gmat, 0, sizeof(unsigned long long) * need, 0));
+        const McGeneBootRead R = {nseq, ng, (long long)cur[0], d_glist, d_gcursor, d_gidx, d_gsorted, d_gmat, d_gscale, B, m, seed, d_gout};
+        const hipEvent_t ev[2] = {ev_gread[0], ev_gread[1]};
+        if (mc_geneboot_launch(R, 0, ev)) return -1;
+        HIPCK(hipEventSynchronize(ev_gread[1]));
+        gread_ms += ev_ms(ev_gread[0], ev_gread[1]);
+        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
+        if (ng) HIPCK(hipMemcpy(out.data(), d_gout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; s++)                            // (a gene without reads: zero in every replicate)
+            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * s + k] = idx[s] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)idx[s] + k] : m ? 0.0 : mc_gb_nan();
+        if (!counts) return 0;
+        std::vector<unsigned long long> mat(need);
+        if (need) HIPCK(hipMemcpy(mat.data(), d_gmat, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; s++)
+            for (size_t b = 0; b < (size_t)B; b++) counts[s * (size_t)B + b] = idx[s] >= 0 ? (int64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
+        return 0;
+    }
     int read_depth(uint32_t *depth)                                // nres values
     {
         McDevBuf buf; uint32_t *d_depth = nullptr;
@@ -192,17 +291,20 @@ private:
     // the switches as they stand, made consistent; then the buffer rule: what they need is made where it is missing, everything else freed
     int fit()
     {
-        if (!on) { cov = ties = curve = false; searched = 0; ms = 0.f; }
+        if (!on) { cov = ties = curve = gboot = false; searched = 0; ms = 0.f; }
         if (!cov) cov_ms = 0.f;
         if (!ties) { ngroups = 0; ties_ms = 0.f; }
         if (!curve) { K = 0; curve_ms = cscan_ms = 0.f; }
+        if (!gboot) { gcap = 0; gboot_ms = gread_ms = 0.f; d_gmat.reset(); gmat_slots = 0; }
         const size_t ns = (size_t)nseq, slots = mc_diff_slots(nres, ns);
         return fit_one(d_counts, on, mc_pair_slots(ns)) || fit_one(ev_count[0], on) || fit_one(ev_count[1], on) ||
                fit_one(d_diff, cov, slots) || fit_one(d_covout, cov, 3 * ns) || fit_one(ev_cov[0], cov) || fit_one(ev_cov[1], cov) ||
                fit_one(d_ties, ties, mc_tie_slots(ns, (size_t)ngroups)) || fit_one(ev_ties, ties) || fit_one(d_group, ties && ngroups > 0, ns) ||
                fit_one(d_diff_any, cov && ties, slots) ||
                fit_one(d_pts, curve, MC_CURVE_MAXK) || fit_one(d_bins, curve, mc_curve_bin_slots((size_t)K, ns)) || fit_one(d_curveout, curve, mc_curve_out_slots((size_t)K, ns)) ||
-               fit_one(ev_curve, curve) || fit_one(ev_cscan[0], curve) || fit_one(ev_cscan[1], curve) || fit_one(d_first, curve && cov, nres);
+               fit_one(ev_curve, curve) || fit_one(ev_cscan[0], curve) || fit_one(ev_cscan[1], curve) || fit_one(d_first, curve && cov, nres) ||
+               fit_one(d_glist, gboot, (size_t)gcap) || fit_one(d_gsorted, gboot, (size_t)gcap) || fit_one(d_gcur, gboot, 2) || fit_one(d_gcursor, gboot, ns) || fit_one(d_gidx, gboot, ns) ||
+               fit_one(d_gscale, gboot, MC_GB_MAXB) || fit_one(d_gout, gboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_gboot, gboot) || fit_one(ev_gread[0], gboot) || fit_one(ev_gread[1], gboot);
     }
     // one switch to `to`.  A switch whose buffers cannot be had ends off and leaves the others as they were (freeing cannot fail).
     int turn(bool &sw, bool to)

@@ -19,7 +19,8 @@
 //   k_coverage.h           per-gene coverage breadth and depth beside them: marks in the counting kernel, a scan at read time (mc_set_coverage)
 //   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
 //   k_curve.h              the rarefaction curve beside them: per-gene counts per prefix of the sample, every residue's first read, a scan at read time (mc_set_curve)
-//   mc_abund.h             (host) the owner of those four: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
+//   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
+//   mc_abund.h             (host) the owner of those five: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
 //   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
 // Stage E copies rows and best hits to pinned host memory.  mc_run_range() issues the stages of one range; run_stream() feeds
@@ -1403,6 +1404,7 @@ extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_
     if (nreads > 0x7fffffff) { g_err = "more than 2^31 - 1 reads in one call"; return -1; }
     if (h->pipe_nout) { g_err = "ranges begun with mc_range_begin() are still in flight"; return -1; }
     if (h->ab.curve) { g_err = "mc_search_varlen: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
+    if (h->ab.gboot) { g_err = "mc_search_varlen: refused while the gene bootstrap is on (mc_set_gene_bootstrap, capacity = " + std::to_string(h->ab.gcap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     bool one = true;
     for (int64_t i = 0; i < nreads; i++) {
         const int64_t len = offsets[i + 1] - offsets[i];
@@ -2048,6 +2050,33 @@ extern "C" int32_t mc_curve_k(const mc_handle *h) { return h && h->ab.curve ? h-
 
 // k_curve's time over the completed ranges plus the scans' at the reads, since the last zeroing
 extern "C" float mc_curve_ms(const mc_handle *h) { return h ? h->ab.curve_ms + h->ab.cscan_ms : 0.0f; }
+
+// the bootstrap of the counts: a list of `capacity` entries turns it on and zeroes every counter; capacity == 0 turns it off
+extern "C" int mc_set_gene_bootstrap(mc_handle *h, int64_t capacity)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_gene_bootstrap: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (capacity == 0) return h->ab.set_gene_bootstrap(0);
+    if (capacity < 0 || capacity > 0x7fffffffll) { g_err = "mc_set_gene_bootstrap: capacity " + std::to_string(capacity) + " is not a number of reads from 0 to 2^31 - 1"; return -1; }
+    if (!h->ab.on) { g_err = "mc_set_gene_bootstrap: abundance counting is off (mc_set_abundance) - the replicates are those of the reads it counts (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    return h->ab.set_gene_bootstrap(capacity);
+}
+
+// counts (or NULL): nseq x B replicate counts; stats: nseq x 6 doubles (mc_geneboot.h); dropped: the assigned reads that did not fit
+extern "C" int mc_gene_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale, int64_t *counts, double *stats, int64_t *dropped)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.gboot) { g_err = "mc_gene_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap)"; return -1; }
+    if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_gene_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
+    if (!scale || !stats) { g_err = "mc_gene_bootstrap: B = " + std::to_string(B) + " and a NULL scale or stats array"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_gene_bootstrap: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_gene_bootstrap(B, seed, scale, counts, stats, dropped);
+}
+
+// k_geneboot_collect's time over the completed ranges plus the reads' kernels, since the last zeroing
+extern "C" float mc_gene_bootstrap_ms(const mc_handle *h) { return h ? h->ab.gboot_ms + h->ab.gread_ms : 0.0f; }
 extern "C" float mc_abundance_ms(const mc_handle *h) { return h ? h->ab.ms : 0.0f; }
 extern "C" float mc_coverage_ms(const mc_handle *h) { return h ? h->ab.cov_ms : 0.0f; }
 extern "C" float mc_ties_ms(const mc_handle *h) { return h ? h->ab.ties_ms : 0.0f; }

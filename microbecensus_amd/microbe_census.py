@@ -1049,10 +1049,11 @@ def bootstrap_unclassified(seed, B, n_unclassified):
     return rng.poisson(float(max(0, int(n_unclassified))), size=int(B)).astype(np.int64)
 
 
-def bootstrap_replicates(args, best, fams, sums_i64, sums_f64, sampled_reads, seed):
+def bootstrap_replicates(args, best, fams, sums_i64, sums_f64, sampled_reads, seed, reads_out=None):
     """The replicate AGS values from the replicates' per-family sums (Engine.bootstrap's two arrays, or the host statement's):
     replicate b sampled read_length x (W[b] + N0[b]) bases - W[b] the weights of its classified reads (last column of sums_i64) -
-    and its AGS is _ags_of_sums of its sums.  A list of B floats, None where a replicate has no value."""
+    and its AGS is _ags_of_sums of its sums.  A list of B floats, None where a replicate has no value.  reads_out: a list that is
+    extended by every replicate's read count W[b] + N0[b]."""
     model = _model(args.get("model_dir"))
     optpars = find_opt_pars(args.get("model_dir"), args["read_length"])
     L = args["read_length"]
@@ -1067,6 +1068,8 @@ def bootstrap_replicates(args, best, fams, sums_i64, sums_f64, sampled_reads, se
     for b in range(len(sums_i64)):
         agg = {nm: (cf if c else float(ci)) for nm, c, ci, cf in zip(names, is_cov, cols_i[b], cols_f[b])}
         out.append(_ags_or_none(model, L, agg, L * (wtot[b] + int(n0[b]))))
+        if reads_out is not None:
+            reads_out.append(wtot[b] + int(n0[b]))
     return out
 
 
@@ -1084,7 +1087,7 @@ def _boot_engine(args):
         raise Exception("--bootstrap sums its replicates on the GPU (mc_bootstrap) and there is no CPU fallback: %s" % e)
 
 
-def bootstrap_ags(args, best, fams, sampled_reads=None):
+def bootstrap_ags(args, best, fams, sampled_reads=None, reads_out=None):
     """B = args['bootstrap'] Poisson-bootstrap replicates of the sample whose best hits are `best` (the first sampled_reads reads;
     default args['sampled_reads']): the per-family sums on the device, the replicate AGS values on the host.
     {'se', 'ci95': (low, high), 'used', 'asked', 'values'}."""
@@ -1092,7 +1095,7 @@ def bootstrap_ags(args, best, fams, sampled_reads=None):
     optpars = find_opt_pars(args.get("model_dir"), args["read_length"])
     si, sf = _boot_engine(args).bootstrap(best, [optpars[f]["aln_stat"] for f in fams], B, seed)
     n = args["sampled_reads"] if sampled_reads is None else sampled_reads
-    return _boot_summary(bootstrap_replicates(args, best, fams, si, sf, n, seed), B)
+    return _boot_summary(bootstrap_replicates(args, best, fams, si, sf, n, seed, reads_out), B)
 
 
 def curve_points(sampled_reads, K):
@@ -1119,11 +1122,13 @@ def ags_curve(args, paths, best, fams):
 
 def _uncertainty(args, paths, best, fams):
     """args['bootstrap'] / args['curve'] of run_pipeline: fills args['ags_boot_se'], ['ags_ci95'], ['ags_boot_replicates'] (used,
-    asked), ['ags_boot_values'] and args['ags_curve']."""
+    asked), ['ags_boot_values'], ['ags_boot_reads'] (every replicate's read count, W[b] + N0[b]) and args['ags_curve']."""
     if args.get("bootstrap"):
         if args["verbose"]:
             print("Bootstrapping the estimate (%s replicates)..." % args["bootstrap"])
-        r = bootstrap_ags(args, best, fams)
+        reads = []
+        r = bootstrap_ags(args, best, fams, reads_out=reads)
+        args["ags_boot_reads"] = reads
         args["ags_boot_se"], args["ags_ci95"], args["ags_boot_replicates"], args["ags_boot_values"] = r["se"], r["ci95"], (r["used"], r["asked"]), r["values"]
         if args["verbose"]:
             print("\tstandard error %s bp, 95%% interval %s - %s bp (%s of %s replicates)" % (round(r["se"], 2), round(r["ci95"][0], 2), round(r["ci95"][1], 2), r["used"], r["asked"]))

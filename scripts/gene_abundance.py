@@ -45,6 +45,9 @@ def parse_arguments(argv=None):
     p.add_argument("--curve", dest="curve", type=int, default=None, metavar="K", help="a rarefaction curve: the table's figures at K nested prefixes of the sample (1 - 64), as runs with -n n_k would give them; "
                    "writes <out>.curve.tsv.  The reads are sampled to the end before the search starts; the tie columns are not rarefied")
     p.add_argument("--curve-genes", dest="curve_genes", type=str, default=None, metavar="FILE", help="with --curve: write the per-gene matrix, gene, reads_1 .. reads_K (and covered_aa_1 .. covered_aa_K with coverage)")
+    p.add_argument("--bootstrap", dest="bootstrap", type=int, default=None, metavar="B", help="add rpkg_boot_se, rpkg_ci95_low and rpkg_ci95_high: the standard error and 95%% interval of every RPKG from B Poisson-bootstrap "
+                   "replicates of the sampled reads (1 - 4096); with the default AGS every replicate is divided by its own AGS estimate, with --ags / --ags-report by the given one.  Not combined with --curve")
+    p.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=None, metavar="S", help="with --bootstrap: the seed of the replicates (default = 0)")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""The measurements of DESIGN.md 13.5 (GPU box), one process per mode, warm-up first, the two sides of a comparison alternating inside the
+repetition loop, median with min - max.  One JSON line per figure.  The reads: 1 M reads of 150 bp of bench.py's read recipe (the 30
+genomes) against the marker database - the README's abundance leg.
+
+    geneboot_timing.py files [--root TREE]   wall time of file -> counts, search_files(keep_rows=False) + abundance() on a FASTA of the reads:
+                                             with the gene bootstrap off and - where the tree has the switch - on (a list of as many entries
+                                             as reads, k_geneboot_collect behind every range), alternating; --root: the tree whose package
+                                             and built library are measured - the parent commit's has no switch and gives the off side alone
+    geneboot_timing.py kernel                k_geneboot_collect over the ranges (gene_bootstrap_ms() before the first read) beside
+                                             abundance_ms() and ms_total of the same ranges, the switch off and on alternating; then
+                                             mc_gene_bootstrap at B = 100, 1000 and 4096: its three kernels (HIP events) and the wall
+                                             time of Engine.gene_bootstrap(), with and without the counts matrix
+--reads (1,000,000), --reps (7)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TAG = {}
+
+
+def emit(d):
+    print(json.dumps(dict(d, **TAG)), flush=True)
+
+
+def spread(v):
+    return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "reps": len(v)}
+
+
+def files(a, eng, reads, _native):
+    L, n = 150, len(reads)
+    has = hasattr(eng, "set_gene_bootstrap")
+    with tempfile.TemporaryDirectory() as d:
+        fa = os.path.join(d, "reads.fa")
+        with open(fa, "wb") as f:
+            for s in range(0, n, 50000):
+                f.write(b"".join(b">r%d\n%s\n" % (s + i, bytes(r)) for i, r in enumerate(reads[s:s + 50000])))
+        wall = {"off": [], "on": []}
+        for rep in range(a.reps + 1):
+            for name in (("on", "off") if has else ("off",)):
+                rd = _native.Reader([fa], L, 10 * n, False, 0, -5, -5, 100, False)
+                try:
+                    eng.set_abundance(True)
+                    if has:
+                        eng.set_gene_bootstrap(n if name == "on" else 0)
+                    t0 = time.perf_counter()
+                    eng.search_files(rd, keep_rows=False)
+                    got = eng.abundance()
+                    wall[name].append(1e3 * (time.perf_counter() - t0))
+                finally:
+                    rd.close()
+        out = {"what": "files", "root": a.root, "has_switch": has, "reads": n, "assigned": got["assigned"], "off_wall_ms": spread(wall["off"][1:])}
+        if has:
+            out["on_wall_ms"] = spread(wall["on"][1:])
+        emit(out)
+
+
+def kernel(a, eng, reads):
+    import numpy as np
+    n = len(reads)
+    eng.upload(reads)
+    eng.set_abundance(True)
+    ms = {k: {"abundance": [], "collect": [], "total": []} for k in ("off", "on")}
+    for rep in range(a.reps + 1):
+        for name in ("on", "off"):
+            eng.set_gene_bootstrap(n if name == "on" else 0)
+            eng.abundance_reset()
+            eng.run_range(0, n, 0)
+            st = eng.stats()
+            assert st["range_splits"] == 0
+            ms[name]["abundance"].append(eng.abundance_ms() * 1e6 / n); ms[name]["total"].append(st["ms_total"] * 1e6 / n)
+            ms[name]["collect"].append(eng.gene_bootstrap_ms() * 1e6 / n)
+    got = eng.abundance()
+    out = {"what": "kernel", "reads": n, "rows": st["rows"], "assigned": got["assigned"], "genes_with_reads": int((got["reads"] > 0).sum())}
+    for name in ms:
+        out[name] = {"abundance_ms_per_1M_reads": spread(ms[name]["abundance"][1:]), "k_geneboot_collect_ms_per_1M_reads": spread(ms[name]["collect"][1:]),
+                     "range_ms_total_per_1M_reads": spread(ms[name]["total"][1:])}
+    emit(out)
+    eng.set_gene_bootstrap(n)
+    eng.abundance_reset()
+    eng.run_range(0, n, 0)
+    for B in (100, 1000, 4096):
+        scale = np.full(B, 1e-3)
+        dev, wall, wall_counts = [], [], []
+        for rep in range(a.reps + 1):
+            before = eng.gene_bootstrap_ms()
+            t0 = time.perf_counter()
+            eng.gene_bootstrap(B, 1, scale)
+            wall.append(1e3 * (time.perf_counter() - t0))
+            dev.append(eng.gene_bootstrap_ms() - before)
+            t0 = time.perf_counter()
+            eng.gene_bootstrap(B, 1, scale, counts=True)
+            wall_counts.append(1e3 * (time.perf_counter() - t0))
+        emit({"what": "read", "B": B, "entries": got["assigned"], "genes_with_reads": int((got["reads"] > 0).sum()), "kernels_ms": spread(dev[1:]), "gene_bootstrap_wall_ms": spread(wall[1:]),
+              "gene_bootstrap_with_counts_wall_ms": spread(wall_counts[1:])})
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("what", choices=("files", "kernel"))
+    p.add_argument("--root", default=os.path.dirname(HERE))
+    p.add_argument("--reads", type=int, default=1000000)
+    p.add_argument("--reps", type=int, default=7)
+    p.add_argument("--tag", default=None, help="whose code runs: every line printed carries it as \"tree\"")
+    a = p.parse_args()
+    if a.tag:
+        TAG["tree"] = a.tag
+    sys.path.insert(0, os.path.abspath(a.root))
+    from microbecensus_amd import _native, synth
+    L = 150
+    model = _native.load_model()
+    eng = _native.Engine(device=0)
+    eng.set_run(L, model["pars"][str(L)], model["families"])
+    reads = synth.GenomeReads(device="cpu", seed=20261001).single(a.reads, L).numpy()
+    try:
+        if a.what == "files":
+            files(a, eng, reads, _native)
+        else:
+            kernel(a, eng, reads)
+        eng.set_abundance(False)
+    finally:
+        eng.close()
+
+
+if __name__ == "__main__":
+    main()
