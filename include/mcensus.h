@@ -488,7 +488,7 @@ int mc_set_best_hits_only(mc_handle *h, int on);
  * Refused, with a message naming the value: min_ident outside 0 .. 100, a negative min_aln, a NaN cut-off, a range in flight, best
  * hits only switched on (the counts need every row of a read; mc_set_best_hits_only(h, 1) is refused in turn while they are on).
  * While they are on, mc_search_classes, mc_search_files on a reader of length classes, mc_train_library and mc_community_library are
- * refused.  mc_search_files_multi keeps one table per handle: the caller adds them (integers). */
+ * refused (the first two not under mc_set_abundance_classes, below).  mc_search_files_multi keeps one table per handle: the caller adds them (integers). */
 int mc_set_abundance(mc_handle *h, int on, int32_t min_ident, int32_t min_aln, double min_bits, double max_loge);
 /* Zeroes the counters and mc_abundance_ms() (README "Normalization": one sample, one table).  Refused while the counts are off. */
 int mc_abundance_reset(mc_handle *h);
@@ -612,6 +612,28 @@ int mc_gene_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scal
 /* Milliseconds the gene bootstrap's kernels took since the last reset (HIP events): one kernel per completed range plus three per
  * mc_gene_bootstrap. */
 float mc_gene_bootstrap_ms(const mc_handle *h);
+
+/* ---- the counts on class runs: gene abundances from reads of mixed lengths -------------------------------------------------------
+ * README "Reads of mixed lengths": a class run searches every read at the largest length class it reaches.  With this switch on the
+ * abundance counts ride on such a run: mc_search_classes and mc_search_files on a reader of length classes are no longer refused
+ * while the counts are on; every piece of every class makes its rows, leaves them on the device and adds to the counts, the depth and
+ * the ties as a fixed-length range does (same kernels), and the best hits of the class run are returned as without the counts.
+ * `searched` grows by every row of every batch, the rows below the lowest class included.  The gene bootstrap takes the GLOBAL id of
+ * a read - first_read_id plus its row in the call - through a map that the class prologue leaves on the device: replicate b is the
+ * same resample whatever the classes, batches and pieces.  Ids stay below 2^31.
+ * A per-class table (csrc/k_abund_classes.h) holds, per class, the rows sorted into it and the reads of it assigned to a gene, and
+ * the rows below the lowest class: the n_k of a mixed-length denominator, sum n_k x L_k bases.  It is summed on the device, zeroed
+ * with the counts by every switch that zeroes them and by mc_abundance_reset(), and freed when the switch or the counts go off.
+ * mc_set_abundance_classes(on != 0) zeroes every counter; on == 0 restores the refusal and the path without it exactly.
+ * Refused, with a message naming the value: abundance counting off, a range in flight, the curve on (mc_set_curve is refused in turn
+ * while the switch is on: a prefix of reads of mixed lengths has no one length).  mc_search_varlen stays as it is. */
+int mc_set_abundance_classes(mc_handle *h, int on);
+/* The per-class table as it stands: rows[k] and assigned[k] of class k = 0 .. n - 2 of mc_set_run_classes, and at n - 1 the rows
+ * below the lowest class (assigned 0).  Either pointer may be NULL.  Refused while the switch is off and when n is not the number of
+ * classes + 1 - with both numbers in the message. */
+int mc_abundance_classes_read(mc_handle *h, int64_t *rows /* [n] */, int64_t *assigned /* [n] */, int32_t n);
+/* Milliseconds the per-class table's kernel took since the last reset (HIP events; one single-thread kernel per piece). */
+float mc_abundance_classes_ms(const mc_handle *h);
 
 #ifdef __cplusplus
 }

@@ -243,6 +243,10 @@ def load_library():
     lib.mc_gene_bootstrap.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.mc_gene_bootstrap_ms.restype = C.c_float
     lib.mc_gene_bootstrap_ms.argtypes = [C.c_void_p]
+    lib.mc_set_abundance_classes.argtypes = [C.c_void_p, C.c_int]
+    lib.mc_abundance_classes_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.mc_abundance_classes_ms.restype = C.c_float
+    lib.mc_abundance_classes_ms.argtypes = [C.c_void_p]
     lib.mc_debug_live.restype = None
     lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
@@ -263,7 +267,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms",
                     "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms",
                     "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms",
-                    "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms", "mc_debug_live"]
+                    "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms",
+                    "mc_set_abundance_classes", "mc_abundance_classes_read", "mc_abundance_classes_ms", "mc_debug_live"]
 
 
 class DupSet:
@@ -1040,6 +1045,25 @@ class Engine:
                                                out["stats"].ctypes.data_as(C.c_void_p), C.byref(dropped)), "mc_gene_bootstrap")
         out["dropped"] = int(dropped.value)
         return out
+
+    def set_abundance_classes(self, on=True):
+        """The counts may ride on class runs (mc_set_abundance_classes; csrc/k_abund_classes.h states the rule): while it is on,
+        search_classes and search_files on a class reader are no longer refused under set_abundance - every read is counted at the
+        length class it reaches, coverage, ties and the gene bootstrap (global read ids) with it.  on=True zeroes every counter;
+        on=False frees the per-class table.  Refused while set_abundance is off and while the curve is on."""
+        self._check(self.lib.mc_set_abundance_classes(self.h, 1 if on else 0), "mc_set_abundance_classes")
+
+    def abundance_classes(self):
+        """The per-class table as it stands (mc_abundance_classes_read): {"rows", "assigned"}, int64[K + 1] each - per class of
+        set_run_classes the rows sorted into it and the reads of it assigned to a gene; the last entry is the rows below the lowest class."""
+        n = len(getattr(self, "class_len", [])) + 1
+        out = {k: np.zeros(n, np.int64) for k in ("rows", "assigned")}
+        self._check(self.lib.mc_abundance_classes_read(self.h, out["rows"].ctypes.data_as(C.c_void_p), out["assigned"].ctypes.data_as(C.c_void_p), n), "mc_abundance_classes_read")
+        return out
+
+    def abundance_classes_ms(self):
+        """milliseconds the per-class table's kernel took since the last reset (HIP events): one single-thread kernel per piece"""
+        return float(self.lib.mc_abundance_classes_ms(self.h))
 
     def gene_bootstrap_ms(self):
         """milliseconds the gene bootstrap's kernels took since the last reset (HIP events): one kernel per range, three per gene_bootstrap()"""

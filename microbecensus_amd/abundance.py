@@ -45,7 +45,16 @@ b of the gene counts is divided by replicate b of the genome equivalents: numera
 
     rpkg_boot_se = the standard deviation (ddof 1) of the replicate RPKGs     rpkg_ci95_low / _high = their 2.5th / 97.5th percentile
 
-With a given AGS (--ags, --ags-report) the denominator is fixed and the interval reflects the counts alone."""
+With a given AGS (--ags, --ags-report) the denominator is fixed and the interval reflects the counts alone.
+
+Reads of mixed lengths (mixed_lengths; README "Reads of mixed lengths"): one trimmed length drops every shorter read and the tail of
+every longer one.  Under the switch every read is searched and counted at the largest length class L_k it reaches
+(Engine.set_abundance_classes; csrc/k_abund_classes.h states the rule), and the denominator is that of the bases so sampled:
+
+    sampled_bases = sum over the classes of n_k x L_k       genome_equivalents_sampled = sampled_bases / AGS
+
+n_k the reads of class k, counted on the device beside the reads each class assigned.  The default AGS is run_pipeline's estimate
+under the same classes: numerator and denominator still come from the same sampled bases."""
 import gzip
 import math
 import os
@@ -156,6 +165,54 @@ def check_ags(ags, source):
 
 def genome_equivalents(sampled_reads, read_length, ags):
     return sampled_reads * read_length / ags
+
+
+def sampled_bases(class_reads, length_classes):
+    """sum of n_k x L_k: the bases of a mixed-length sample, an integer"""
+    return sum(int(n) * int(L) for n, L in zip(class_reads, length_classes))
+
+
+def read_report_classes(path):
+    """The length_classes line of a report that run_pipeline wrote under mixed_lengths (`length_classes:\t<L1>\t<L2>...`), or None -
+    the report has none."""
+    if not os.path.isfile(path):
+        raise AbundanceError("AGS report %s not found" % path)
+    with open(path) as f:
+        for line in f:
+            if line.startswith("length_classes:"):
+                txt = line.split(":", 1)[1].split()
+                try:
+                    return [int(x) for x in txt]
+                except ValueError:
+                    raise AbundanceError("AGS report %s: length_classes %r are not integers" % (path, txt))
+    return None
+
+
+def check_length_classes(want, valid, what):
+    """A list of class lengths, sorted and without repeats; refused where one is no length the model was trained for"""
+    try:
+        classes = sorted(set(int(x) for x in want))
+    except (TypeError, ValueError):
+        raise AbundanceError("%s %r is not a list of read lengths" % (what, want))
+    bad = [L for L in classes if L not in valid]
+    if bad or not classes:
+        raise AbundanceError("%s: length classes %s are not lengths the model was trained for: %s" % (what, bad if bad else classes, list(valid)))
+    return classes
+
+
+def resolve_length_classes(args, valid):
+    """args['mixed_lengths'] (True or a list) to the classes of the run, or None - they are to be detected from the reads
+    (microbe_census.auto_detect_length_classes): a given list; otherwise the length_classes line of args['ags_report'] where it has one.
+    A list that contradicts the report's line is refused."""
+    want = args["mixed_lengths"]
+    given = None if want is True else check_length_classes(want, valid, "--mixed-lengths %s" % ",".join(str(x) for x in want))
+    rep = read_report_classes(args["ags_report"]) if args.get("ags_report") is not None else None
+    if rep is not None:
+        rep = check_length_classes(rep, valid, "AGS report %s" % args["ags_report"])
+        if given is not None and given != rep:
+            raise AbundanceError("--mixed-lengths %s contradicts the length_classes %s of the AGS report %s: its AGS is that of other bases"
+                                 % (",".join(str(x) for x in given), ",".join(str(x) for x in rep), args["ags_report"]))
+    return given if given is not None else rep
 
 
 def rpkg(reads, length_aa, ge):
@@ -301,9 +358,15 @@ def boot_columns(stats, used, length_aa):
     return se, out[0], out[1]
 
 
+def _mixed_header(table):
+    if table.get("length_classes") is None:
+        return []
+    return [(k, ",".join(str(int(x)) for x in table[k])) for k in ("length_classes", "class_reads", "class_reads_assigned")] + [("sampled_bases", table["sampled_bases"])]
+
+
 def header_lines(args, table):
     h = [("metagenome", ",".join(args["seqfiles"])), ("genes", args["genes"]), ("sampled_reads", table["sampled_reads"]),
-         ("trimmed_length", table["trimmed_length"]), ("min_ident", args["min_ident"]), ("min_aln", args["min_aln"]), ("min_bits", repr(float(args["min_bits"]))),
+         ("trimmed_length", table["trimmed_length"])] + _mixed_header(table) + [("min_ident", args["min_ident"]), ("min_aln", args["min_aln"]), ("min_bits", repr(float(args["min_bits"]))),
          ("average_genome_size", repr(float(table["ags"]))), ("ags_source", table["ags_source"]),
          ("genome_equivalents_sampled", repr(float(table["genome_equivalents_sampled"]))), ("reads_assigned", table["reads_assigned"])]
     if table.get("covered_aa") is not None:
@@ -442,8 +505,18 @@ def check_request(args):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
                          ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
-                         ("bootstrap", None), ("bootstrap_seed", None)):
+                         ("bootstrap", None), ("bootstrap_seed", None), ("mixed_lengths", None)):
         args.setdefault(key, default)
+    mixed = microbe_census.mixed_lengths_on(args)
+    if mixed:
+        ml = "" if args["mixed_lengths"] is True else " %s" % ",".join(str(x) for x in args["mixed_lengths"])
+        if args.get("read_length") is not None:
+            raise AbundanceError("--mixed-lengths%s cannot be combined with -l %s: every read is cut to its own length class" % (ml, args["read_length"]))
+        if args["curve"] is not None:
+            raise AbundanceError("--mixed-lengths%s cannot be combined with --curve %s: rarefying reads of mixed lengths needs the bases of every prefix" % (ml, args["curve"]))
+        if args["bootstrap"] is not None and args["ags"] is None and args["ags_report"] is None:
+            raise AbundanceError("--mixed-lengths%s with --bootstrap %s needs --ags or --ags-report: the default AGS is run_pipeline's, which does not bootstrap "
+                                 "an estimate of mixed lengths" % (ml, args["bootstrap"]))
     if args["curve"] is not None:
         K = args["curve"]
         if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= MAX_CURVE:
@@ -515,12 +588,15 @@ def check_request(args):
     if args["ags_report"] is not None:
         source = "report %s" % args["ags_report"]
         ags = check_ags(read_ags_report(args["ags_report"]), source)
+    if mixed:                   # (None: to be detected from the reads, once the files are known to be there)
+        args["length_classes"] = resolve_length_classes(args, list(microbe_census._valid_read_lengths(args.get("model_dir"))))
     return names, seqs, group_of, ags, source
 
 
 def run_abundance(args):
     """args: run_pipeline's keys (seqfiles, nreads, read_length, min_quality, mean_quality, filter_dups, max_unknown, device, model_dir,
-    verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and - all off by default - coverage, min_breadth
+    verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and - all off by default - mixed_lengths (True or a list of class lengths: every read
+    at the largest length class it reaches, the denominator from the bases so sampled; not combined with read_length and curve, with bootstrap only under a given AGS), coverage, min_breadth
     (implies coverage), depth_out (a path; implies coverage), ties (the genes that tie for a read's best hit: unique, candidate and
     shared reads beside the counts; sets args['ties_ms']), curve (K, 1 .. 64: table['curve'], the table's figures at K prefixes of the sample
     - the sampler then runs to its end before the search starts; sets args['curve_ms']; writes <outfile>.curve.tsv) and curve_genes (a path:
@@ -531,8 +607,19 @@ def run_abundance(args):
     aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
     names, seqs, group_of, ags, source = check_request(args)
     microbe_census.check_input(args)
+    mixed, classes = microbe_census.mixed_lengths_on(args), None
+    if mixed:                   # neither a list nor a report's line: the classes run_pipeline would detect on the same file
+        classes = args["length_classes"]
+        if classes is None:
+            try:
+                classes = microbe_census.auto_detect_length_classes(args["seqfiles"][0], list(microbe_census._valid_read_lengths(args.get("model_dir"))))
+            except SystemExit as e:
+                raise AbundanceError(str(e))
+        args["length_classes"] = classes = [int(x) for x in classes]
     if ags is None:             # the estimate of the same sample: run_pipeline on the marker engine, same files, same options
         more = {"curve": args["curve"]} if args["curve"] else {"bootstrap": args["bootstrap"], "bootstrap_seed": args["bootstrap_seed"] or 0} if args["bootstrap"] else {}
+        if mixed:               # (check_request has refused the curve and the bootstrap of a default AGS)
+            more = {"mixed_lengths": list(classes)}
         est = microbe_census.run_pipeline(dict(_pipeline_args(args), **more) if more else _pipeline_args(args))
         if est is None:
             raise AbundanceError("run_pipeline gave no AGS estimate for %s" % ",".join(args["seqfiles"]))
@@ -542,15 +629,21 @@ def run_abundance(args):
     else:                       # the same imputation run_pipeline makes (file type, quality offset, read length), without a search
         pargs = _pipeline_args(args)
         microbe_census._cap_host_threads(pargs.get("threads"))
+        if mixed:               # (as run_pipeline: read_length becomes "mixed" and is not detected)
+            pargs["mixed_lengths"] = list(classes)
+            microbe_census.check_mixed_lengths(pargs)
         microbe_census.impute_missing_args(pargs)
         microbe_census.check_arguments(pargs)
-    L = int(pargs["read_length"])
-    rd = _native.Reader(pargs["seqfiles"], L, pargs["nreads"], pargs["file_type"] == "fastq", pargs.get("quality_offset") or 0,
-                        pargs["min_quality"], pargs["mean_quality"], pargs["max_unknown"], pargs["filter_dups"])
+    L = "mixed" if mixed else int(pargs["read_length"])
+    sampler = (pargs["nreads"], pargs["file_type"] == "fastq", pargs.get("quality_offset") or 0, pargs["min_quality"], pargs["mean_quality"], pargs["max_unknown"], pargs["filter_dups"])
+    rd = _native.Reader.with_classes(pargs["seqfiles"], classes, *sampler) if mixed else _native.Reader(pargs["seqfiles"], L, *sampler)
     eng = None
     try:
         eng = _native.Engine(device=int(args.get("device") or 0), names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
-        eng.set_run(L)
+        if mixed:               # (the default parameters: classification does not enter the counts)
+            eng.set_run_classes(classes)
+        else:
+            eng.set_run(L)
         eng.set_abundance(True, min_ident=args["min_ident"], min_aln=args["min_aln"], min_bits=args["min_bits"])
         if args["coverage"]:
             eng.set_coverage(True)
@@ -561,7 +654,9 @@ def run_abundance(args):
                 eng.set_ties(True, gids, len(gnames))
             else:
                 eng.set_ties(True)
-        cu = points = gb = scale = None
+        if mixed:
+            eng.set_abundance_classes(True)
+        cu = points = gb = scale = ac = None
         B, seed = args["bootstrap"], args["bootstrap_seed"] or 0
         if B and pargs["nreads"] is not None:       # ids lie below -n: the list is sized before the sampler starts, and it samples beside the search
             eng.set_gene_bootstrap(int(pargs["nreads"]))
@@ -572,7 +667,10 @@ def run_abundance(args):
                     eng.set_gene_bootstrap(n)
                     eng.lib.mc_set_keep_rows(eng.h, 0)
                     try:
-                        eng.search(rd.reads(n))
+                        if mixed:
+                            eng.search_classes(rd.reads(n))
+                        else:
+                            eng.search(rd.reads(n))
                     finally:
                         eng.lib.mc_set_keep_rows(eng.h, 1)
             elif args["curve"]:       # the points depend on how many reads the sampler takes: it runs to its end first, then one search
@@ -592,13 +690,16 @@ def run_abundance(args):
         except _native.ReferenceError_ as e:
             raise AbundanceError(str(e))
         ab = eng.abundance()
+        if mixed:
+            ac = eng.abundance_classes()
+            args["abundance_classes_ms"] = eng.abundance_classes_ms()
         if B and ab["searched"]:
             if source == "run_pipeline":
                 if len(pargs.get("ags_boot_values") or []) != B or len(pargs.get("ags_boot_reads") or []) != B:
                     raise AbundanceError("run_pipeline gave %d replicate AGS values for --bootstrap %d" % (len(pargs.get("ags_boot_values") or []), B))
                 scale = boot_scale(pargs["ags_boot_values"], pargs["ags_boot_reads"], L)
             else:
-                scale = np.full(B, 1.0 / genome_equivalents(ab["searched"], L, ags))
+                scale = np.full(B, 1.0 / (sampled_bases(ac["rows"], classes) / ags if mixed else genome_equivalents(ab["searched"], L, ags)))
             try:
                 gb = eng.gene_bootstrap(B, seed, scale)
             except RuntimeError as e:
@@ -623,15 +724,27 @@ def run_abundance(args):
         raise AbundanceError("No reads remaining after filtering")
     if "sampled_reads" in pargs and int(pargs["sampled_reads"]) != sampled or ab["searched"] != sampled:
         raise AbundanceError("the gene search saw %d reads (%d sampled), the AGS estimate %s" % (ab["searched"], sampled, pargs.get("sampled_reads")))
+    class_reads = class_assigned = None
+    if mixed:
+        K = len(classes)
+        class_reads, class_assigned = [int(x) for x in ac["rows"][:K]], [int(x) for x in ac["assigned"][:K]]
+        est = source == "run_pipeline"
+        if sum(class_reads) != sampled or int(ac["rows"][K]) != 0 or est and (list(pargs.get("length_classes") or []) != classes or list(pargs.get("class_reads") or []) != class_reads):
+            raise AbundanceError("the gene search saw %d reads (%d sampled): %s reads in the classes %s and %d below them, the AGS estimate %s in the classes %s"
+                                 % (ab["searched"], sampled, class_reads, classes, int(ac["rows"][K]), pargs.get("class_reads") if est else "-", pargs.get("length_classes") if est else "-"))
+        args["class_reads"] = class_reads
     for k in ("file_type", "quality_offset", "read_length", "nreads", "min_quality", "mean_quality", "filter_dups", "max_unknown") + (
             ("ags_boot_se", "ags_ci95", "ags_boot_replicates", "ags_boot_values", "ags_boot_reads") if gb is not None and source == "run_pipeline" else ()):
         if k in pargs:
             args[k] = pargs[k]
     args["sampled_reads"] = sampled
     length_aa = np.array([len(s) for s in seqs], np.int64)
-    ge = genome_equivalents(sampled, L, ags)
+    bases = sampled_bases(class_reads, classes) if mixed else None
+    ge = bases / ags if mixed else genome_equivalents(sampled, L, ags)
     table = {"gene": list(names), "length_aa": length_aa, "reads": ab["reads"], "aligned_aa": ab["aligned"], "rpkg": rpkg(ab["reads"], length_aa, ge),
              "sampled_reads": sampled, "trimmed_length": L, "ags": ags, "ags_source": source, "genome_equivalents_sampled": ge, "reads_assigned": ab["assigned"]}
+    if mixed:
+        table.update({"length_classes": list(classes), "class_reads": class_reads, "class_reads_assigned": class_assigned, "sampled_bases": bases})
     if cov is not None:
         breadth, mean_depth = coverage_columns(length_aa, cov["covered"], cov["spanned"])
         table.update({"covered_aa": cov["covered"], "breadth": breadth, "mean_depth": mean_depth, "max_depth": cov["max_depth"], "spanned_aa": cov["spanned"]})

@@ -51,6 +51,51 @@ __global__ void __launch_bounds__(256) k_geneboot_collect(McAbundPars A, const M
     else atomicAdd(&cur[1], 1ull);
 }
 
+// The id of a read whose rows carry a position `query` of a sorted batch and not the read's id (a class run, mc_set_abundance_classes):
+// base + perm[query], perm the row index of every sorted position (the class prologue's), base the batch's first read id.  The sum
+// is taken in 64 bits and lies below 2^31 (mc_search_classes).
+struct McIdMap { const uint32_t *perm; int64_t base; };
+
+// k_geneboot_collect for the pieces of a class run: launched INSTEAD of it while the owner holds an id map (mc_abund_launch), the same
+// walk, the same slots, and the entry's id taken through `map`.  A second kernel and not a parameter of the first (a fifth copy of the
+// walk: whoever edits one edits all): the kernel of the fixed-length runs stays the instructions it was.
+__global__ void __launch_bounds__(256) k_geneboot_collect_mapped(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, McGbEntry *list, unsigned long long capacity,
+                                                                 unsigned long long *cur, McIdMap map)
+{
+    __shared__ uint32_t wcnt[4];
+    __shared__ unsigned long long base;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool hit = false;
+    McGbEntry mine = {0u, 0u};
+    if (i < nrows) {
+        const int q = rows[i].query;
+        if (i == 0 || rows[i - 1].query != q) {                      // one thread per read: the one at its first row
+            double bbits = 0.0; int bsub = -1;
+            for (uint32_t k = i; k < nrows && rows[k].query == q; k++) {
+                const McRow r = rows[k];
+                if (!mc_abund_passes(A, r.frame, r.alnlen, r.bits, r.loge)) continue;   // (McRow::frame carries the identities)
+                if (bsub < 0 || bbits < r.bits) { bbits = r.bits; bsub = r.subject; }
+            }
+            if (bsub >= 0 && bsub < nseq) { hit = true; mine.q = (uint32_t)(map.base + (int64_t)map.perm[q]); mine.gene = (uint32_t)bsub; }
+        }
+    }
+    const unsigned long long m = __ballot(hit);
+    const int lane = mc_lane(), w = (int)(threadIdx.x >> 6);
+    if (lane == 0) wcnt[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        base = tot ? atomicAdd(&cur[0], (unsigned long long)tot) : 0ull;
+    }
+    __syncthreads();
+    if (!hit) return;
+    uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (int k = 0; k < w; k++) rank += wcnt[k];
+    const unsigned long long slot = base + rank;
+    if (slot < capacity) list[slot] = mine;
+    else atomicAdd(&cur[1], 1ull);
+}
+
 // Grouping by gene: cursor[s] starts at the first slot of gene s in the grouped list - the exclusive scan of the count table's `reads` - and
 // idx[s] is the gene's compact index among the genes with reads.  One thread per entry takes the next slot of its gene; the order within
 // a gene is whatever the atomics give, and free: the sums are integers.  n entries in both lists; a slot not below n, or a gene

@@ -1,14 +1,15 @@
 // mc_abund.h - the one owner of the per-gene counts (mc_set_abundance), the coverage depth (mc_set_coverage), the tie accounting
-// (mc_set_ties), the rarefaction curve (mc_set_curve) and the bootstrap of the counts (mc_set_gene_bootstrap): where their tables lie, how
-// their kernels are launched on the rows of a range, and which buffer exists when.
-// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h and k_geneboot.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
-// hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip and device_geneboot.hip launch through mc_abund_launch like range_end.
+// (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap) and the counts on class runs
+// (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
+// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
+// hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end.
 #pragma once
 #include "k_abundance.h"
 #include "k_coverage.h"
 #include "k_ties.h"
 #include "k_curve.h"
 #include "k_geneboot.h"
+#include "k_abund_classes.h"
 #include "mc_owned.h"
 
 // ---- Layout: every size and offset of the four tables (k_ties.h, k_coverage.h and k_curve.h, "Layout", say what the slots hold) -----------------
@@ -36,14 +37,20 @@ struct McCurveBufs { int32_t K; const unsigned long long *pts; unsigned long lon
 // the bootstrap's part of a launch (null: the gene bootstrap is off).  list: `capacity` entries; cur: the cursor and `dropped`
 // (k_geneboot.h); ev: recorded behind k_geneboot_collect
 struct McGeneBootBufs { McGbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
+// the class ride of a launch (null: the rows are no piece of a class run).  map: the ids of the batch (k_geneboot.h); tab: the per-class
+// table of K classes (k_abund_classes.h); k, nreads: the piece's class and reads; ev: recorded behind k_abund_class_add
+struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigned long long nreads; hipEvent_t ev; };
 
 // The kernels of a range's final rows (ascending read id), in `st`: the counting kernel - k_abundance_cov INSTEAD of k_abundance while
 // coverage is on, the marks ride with the counts - between ev[0] and ev[1]; with ties k_ties behind it on the same rows where they
 // lie, and ev[2] behind that; with the curve k_curve behind those on the same rows, and its event behind that.  The events are recorded
 // with nr == 0 too: whoever reads the times need not know.  Without the curve (C null) nothing more is issued than before it existed;
 // with the gene bootstrap k_geneboot_collect behind all of those on the same rows, and its event behind that - without it (G null) nothing.
+// With a class ride (R not null: the rows are a piece of a class run, mc_set_abundance_classes) k_geneboot_collect_mapped runs INSTEAD of
+// k_geneboot_collect and takes every id through R->map, and k_abund_class_add runs behind everything, with nr == 0 too (a piece without
+// rows has reads), and R->ev behind it.  Without one (R null) nothing more is issued and the kernels are the fixed-length runs'.
 static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McRow *rows, uint32_t nr, hipStream_t st, const hipEvent_t (&ev)[3], const McCurveBufs *C = nullptr,
-                           const McGeneBootBufs *G = nullptr)
+                           const McGeneBootBufs *G = nullptr, const McClassRide *R = nullptr)
 {
     const dim3 grid((nr + 255) / 256), block(256);
     HIPCK(hipEventRecord(ev[0], st));
@@ -59,9 +66,14 @@ static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McR
         if (nr) k_curve<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, C->pts, C->K, C->bins, B.off, C->first);
         HIPCK(hipEventRecord(C->ev, st));
     }
-    if (!G) return 0;
-    if (nr) k_geneboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, G->list, G->capacity, G->cur);
-    HIPCK(hipEventRecord(G->ev, st));
+    if (G) {
+        if (nr && R) k_geneboot_collect_mapped<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, G->list, G->capacity, G->cur, R->map);
+        else if (nr) k_geneboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, G->list, G->capacity, G->cur);
+        HIPCK(hipEventRecord(G->ev, st));
+    }
+    if (!R) return 0;
+    k_abund_class_add<<<dim3(1), dim3(64), 0, st>>>(R->tab, R->K, R->k, R->nreads, B.counts + mc_pair_at((size_t)B.nseq));
+    HIPCK(hipEventRecord(R->ev, st));
     return 0;
 }
 
@@ -94,7 +106,7 @@ static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hip
 }
 
 // ---- Owner --------------------------------------------------------------------------------------------------------------------
-// The five switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
+// The six switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
 //     the difference array, the scan's output, its two events                    coverage is on
 //     the tie table, its event                                                   ties are on
@@ -105,10 +117,11 @@ static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hip
 //     the bootstrap's list, its cursor and dropped counter, the grouped list,
 //     the genes' cursors and compact indices, the scales, the output, its three events   the gene bootstrap is on
 //     the bootstrap's matrix of replicate counts                                  the gene bootstrap is on and a read has sized it
-// Coverage, ties, the curve and the gene bootstrap are on only while the counts are.  Every switch that goes on, and reset(), zeroes ALL
+//     the per-class table (k_abund_classes.h), its event                          the counts may ride on class runs
+// Coverage, ties, the curve, the gene bootstrap and the class ride are on only while the counts are.  Every switch that goes on, and reset(), zeroes ALL
 // counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the bootstrap's cursor and dropped counter
-// (an empty list), `searched` and the times: counts, depth, ties, curve and bootstrap describe the same reads.  A switch that goes off
-// frees its buffers and zeroes nothing of the others; the counts going off take the other four with them.
+// (an empty list), the per-class table, `searched` and the times: counts, depth, ties, curve, bootstrap and classes describe the same reads.  A switch that goes off
+// frees its buffers and zeroes nothing of the others; the counts going off take the other five with them.
 struct McAbundance {
     int32_t nseq = 0; size_t nres = 0; const uint32_t *off = nullptr;   // the database: bind(), once the index is on the device
     bool on = false, cov = false, ties = false, curve = false, gboot = false; int32_t ngroups = 0, K = 0; int64_t gcap = 0;
@@ -121,6 +134,9 @@ struct McAbundance {
     size_t gmat_slots = 0;                                         // what d_gmat holds: a read grows it to ngenes x B
     McEvent ev_gboot, ev_gread[2];                                 // behind k_geneboot_collect; around the kernels of a read
     float gboot_ms = 0, gread_ms = 0;                              // k_geneboot_collect's, the reads' time since the last zeroing
+    bool classes = false;                                          // mc_set_abundance_classes: the counts may ride on class runs
+    McDev<unsigned long long> d_cls; McEvent ev_cls; float cls_ms = 0;   // the per-class table; behind k_abund_class_add; its time since the last zeroing
+    McIdMap map = {nullptr, 0}; int32_t map_K = 0, piece_k = 0;    // held while a batch's pieces run (ride_begin .. ride_end): its ids, its classes; the class of the piece that ends next
     int64_t searched = 0;                                          // the reads of the completed ranges
     float ms = 0, cov_ms = 0, ties_ms = 0;                         // the counting kernels', the scans', k_ties' time since the last zeroing
 
@@ -158,6 +174,8 @@ struct McAbundance {
         gcap = capacity;
         return turn(gboot, true);
     }
+    // on: refused by the caller while the curve is on (mc_set_abundance_classes)
+    int set_classes(bool to) { return turn(classes, to); }
     int reset()
     {
         HIPCK(hipMemset(d_counts, 0, sizeof(unsigned long long) * mc_pair_slots((size_t)nseq)));
@@ -167,18 +185,43 @@ struct McAbundance {
         if (d_bins) HIPCK(hipMemset(d_bins, 0, sizeof(unsigned long long) * mc_curve_bin_slots((size_t)K, (size_t)nseq)));
         if (d_first) HIPCK(hipMemset(d_first, 0xFF, sizeof(uint32_t) * nres));
         if (d_gcur) HIPCK(hipMemset(d_gcur, 0, sizeof(unsigned long long) * 2));
-        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = 0.f;
+        if (d_cls) HIPCK(hipMemset(d_cls, 0, sizeof(unsigned long long) * MC_AC_SLOTS));
+        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = 0.f;
         return 0;
     }
 
     // ---- a range (range_end): its final rows where they lie, and what is kept once its stream has been waited for ----
-    int launch(const McRow *rows, uint32_t nr, hipStream_t st)
+    // nreads: the range's reads - the class table's, while a batch's pieces ride (ride_begin)
+    int launch(const McRow *rows, uint32_t nr, hipStream_t st, int64_t nreads = 0)
     {
         const McAbundBufs B = {nseq, off, d_counts, d_diff, d_ties, d_group, d_diff_any};
         const hipEvent_t ev[3] = {ev_count[0], ev_count[1], ev_ties};
         const McCurveBufs C = {K, d_pts, d_bins, d_first, ev_curve};
         const McGeneBootBufs G = {d_glist, (unsigned long long)gcap, d_gcur, ev_gboot};
-        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr);
+        const McClassRide R = {map, d_cls, map_K, piece_k, (unsigned long long)nreads, ev_cls};
+        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr);
+    }
+    // ---- a batch of a class run under the switch (classes_batch): perm: the row index of every sorted position, on the device, for as
+    // long as the pieces run; base: the batch's first read id; K_: its classes.  ride_piece: the class of the piece whose range ends next.
+    // rows_below: the rows without a class are searched by nobody - they count as searched, and in slot K of the table (no host sync)
+    int ride_begin(const uint32_t *perm, int64_t base, int32_t K_, hipStream_t st)
+    {
+        if (!classes) return 0;
+        k_abund_class_mark<<<dim3(1), dim3(64), 0, st>>>(d_cls, d_counts.get() + mc_pair_at((size_t)nseq));
+        HIPCK(hipGetLastError());
+        map = {perm, base}; map_K = K_; piece_k = 0;
+        return 0;
+    }
+    void ride_piece(int32_t k) { piece_k = k; }
+    void ride_end() { map = {nullptr, 0}; map_K = 0; piece_k = 0; }
+    bool riding() const { return classes && map.perm != nullptr; }
+    int rows_below(int64_t n, hipStream_t st)
+    {
+        if (!riding() || n <= 0) return 0;
+        k_abund_class_add<<<dim3(1), dim3(64), 0, st>>>(d_cls, map_K, map_K, (unsigned long long)n, d_counts.get() + mc_pair_at((size_t)nseq));
+        HIPCK(hipGetLastError());
+        add_searched(n);
+        return 0;
     }
     void range_done(int64_t nreads)
     {
@@ -186,6 +229,7 @@ struct McAbundance {
         if (ties) ties_ms += ev_ms(ev_count[1], ev_ties);
         if (curve) curve_ms += ev_ms(ties ? ev_ties : ev_count[1], ev_curve);
         if (gboot) gboot_ms += ev_ms(curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_gboot);
+        if (riding()) cls_ms += ev_ms(gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
     }
     void add_searched(int64_t nreads) { if (on) searched += nreads; }   // (mc_search_varlen: reads too short to have a frame are searched, and have no rows)
 
@@ -277,6 +321,14 @@ struct McAbundance {
             for (size_t b = 0; b < (size_t)B; b++) counts[s * (size_t)B + b] = idx[s] >= 0 ? (int64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
         return 0;
     }
+    // the per-class table as it stands: n pairs, class 0 .. n - 2 and the rows below the lowest class (the caller knows its K: n = K + 1)
+    int read_classes(int64_t *rows, int64_t *assigned, int32_t n) const
+    {
+        unsigned long long tab[MC_AC_SLOTS];
+        HIPCK(hipMemcpy(tab, d_cls, sizeof tab, hipMemcpyDeviceToHost));
+        for (int32_t k = 0; k < n; k++) { if (rows) rows[k] = (int64_t)tab[2 * k]; if (assigned) assigned[k] = (int64_t)tab[2 * k + 1]; }
+        return 0;
+    }
     int read_depth(uint32_t *depth)                                // nres values
     {
         McDevBuf buf; uint32_t *d_depth = nullptr;
@@ -291,7 +343,8 @@ private:
     // the switches as they stand, made consistent; then the buffer rule: what they need is made where it is missing, everything else freed
     int fit()
     {
-        if (!on) { cov = ties = curve = gboot = false; searched = 0; ms = 0.f; }
+        if (!on) { cov = ties = curve = gboot = classes = false; searched = 0; ms = 0.f; }
+        if (!classes) { cls_ms = 0.f; ride_end(); }
         if (!cov) cov_ms = 0.f;
         if (!ties) { ngroups = 0; ties_ms = 0.f; }
         if (!curve) { K = 0; curve_ms = cscan_ms = 0.f; }
@@ -304,7 +357,8 @@ private:
                fit_one(d_pts, curve, MC_CURVE_MAXK) || fit_one(d_bins, curve, mc_curve_bin_slots((size_t)K, ns)) || fit_one(d_curveout, curve, mc_curve_out_slots((size_t)K, ns)) ||
                fit_one(ev_curve, curve) || fit_one(ev_cscan[0], curve) || fit_one(ev_cscan[1], curve) || fit_one(d_first, curve && cov, nres) ||
                fit_one(d_glist, gboot, (size_t)gcap) || fit_one(d_gsorted, gboot, (size_t)gcap) || fit_one(d_gcur, gboot, 2) || fit_one(d_gcursor, gboot, ns) || fit_one(d_gidx, gboot, ns) ||
-               fit_one(d_gscale, gboot, MC_GB_MAXB) || fit_one(d_gout, gboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_gboot, gboot) || fit_one(ev_gread[0], gboot) || fit_one(ev_gread[1], gboot);
+               fit_one(d_gscale, gboot, MC_GB_MAXB) || fit_one(d_gout, gboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_gboot, gboot) || fit_one(ev_gread[0], gboot) || fit_one(ev_gread[1], gboot) ||
+               fit_one(d_cls, classes, MC_AC_SLOTS) || fit_one(ev_cls, classes);
     }
     // one switch to `to`.  A switch whose buffers cannot be had ends off and leaves the others as they were (freeing cannot fail).
     int turn(bool &sw, bool to)

@@ -20,6 +20,7 @@
 //   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
 //   k_curve.h              the rarefaction curve beside them: per-gene counts per prefix of the sample, every residue's first read, a scan at read time (mc_set_curve)
 //   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
+//   k_abund_classes.h      the per-class table of the counts on class runs (mc_set_abundance_classes)
 //   mc_abund.h             (host) the owner of those five: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
 //   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
@@ -891,7 +892,7 @@ static int range_end(mc_handle *h, McCtx &c, int64_t next_first = 0, int64_t nex
     // the abundance counts of the range: its rows are final and none of its pools overflowed - a range that did has returned above
     // and counts nothing; the pieces mc_run_range cuts it into come through here one by one, each once
     const bool abund = h->ab.active() && !h->best_only;
-    if (abund && h->ab.launch(c.d_rows, std::min(c.nrows, c.cap_rows), c.stream)) return -1;
+    if (abund && h->ab.launch(c.d_rows, std::min(c.nrows, c.cap_rows), c.stream, c.n)) return -1;
     if ((size_t)c.nrows > h->pin_slot_cap[h->pin_cur] && !rows_stay(h)) {   // grow the pinned row buffer
         (void)hipStreamSynchronize(h->rows_stream);                  // (the copy of the run before writes into the other buffer: let it finish before anything is freed)
         const size_t want = (size_t)c.nrows + c.nrows / 4 + 1024;
@@ -1301,6 +1302,7 @@ template <class BlockOf> static int run_pieces(mc_handle *h, McLenBorrow &len, c
         const McPiece *nx = j + 1 < pieces.size() ? &pieces[j + 1] : nullptr;
         const bool ahead = nx && same_bin(q, *nx);
         h->pipe_nout = 0;                                            // (mc_range_end, told the next range: the next piece where it is of this bin, else none)
+        h->ab.ride_piece(q.tag);                                     // (a class run the counts ride on: the piece's class, for range_end and the ranges of a rerun)
         rc = range_end_next(h, ahead ? nx->first : 0, ahead ? nx->n : 0);
         if (rc == -2) rc = mc_run_range(h, q.first, q.n, q.bin_first + q.first);
         if (rc) break;
@@ -1508,11 +1510,15 @@ static int classes_batch(mc_handle *h, const uint8_t *d_rows, int64_t n, int64_t
     const McPieces P = mc_cut_pieces(bins, stream_batch());            // (P.nshort is 0 here: mc_classes_check admits no class under 18 bases)
     for (int k = 0; k <= C.K; k++) reads[k] += (int64_t)(S.start[(size_t)k + 1] - S.start[(size_t)k]);
     R.tot.reads += n - nclassed;
+    // the counts ride (mc_set_abundance_classes): the owner holds the batch's id map, S.d_perm and the batch's first id, while the
+    // pieces run - every piece's range_end launches the counting kernels on its rows - and lets go of it however this returns
+    struct Ride { McAbundance &ab; ~Ride() { ab.ride_end(); } } ride{h->ab};
+    if (h->ab.ride_begin(S.d_perm, first_read_id, C.K, st) || h->ab.rows_below(n - nclassed, st)) return -1;
     if (P.v.empty()) return 0;
     const size_t best0 = R.best.size();
     int rc;
     {
-        McModeGuard mode(h, h->best_only, true);                     // (a class run hands out no rows: they stay on the device)
+        McModeGuard mode(h, h->ab.classes ? false : h->best_only, true);   // (a class run hands out no rows: they stay on the device; under the counts they are made)
         McLenBorrow len(h);
         if ((rc = len.pools(P.Lmax, P.nmax)) == 0)
             rc = run_pieces(h, len, P.v, [&](const McPiece &q) { return S.d_sorted + S.G.word0[q.tag] * 16; }, h->cls_pars.data(), R);
@@ -1570,8 +1576,8 @@ static int classes_ready(mc_handle *h, const char *who)
 {
     if (!h || !h->run_set || !h->cls_set) { g_err = std::string(who) + ": mc_set_run_classes() must be called first"; return -1; }
     if (h->pipe_nout) { g_err = std::string(who) + ": ranges begun with mc_range_begin() are still in flight"; return -1; }
-    if (h->ab.active()) { g_err = std::string(who) + ": a class run is refused while abundance counting is on (mc_set_abundance)"; return -1; }
-    return 0;
+    if (h->ab.active() && !h->ab.classes) { g_err = std::string(who) + ": a class run is refused while abundance counting is on (mc_set_abundance)"; return -1; }
+    return 0;                                                        // (mc_set_abundance_classes: the counts ride on the class run)
 }
 
 extern "C" int mc_search_classes(mc_handle *h, const uint8_t *rows, int64_t nreads, int32_t stride, int64_t first_read_id)
@@ -2023,6 +2029,7 @@ extern "C" int mc_set_curve(mc_handle *h, int32_t K, const int64_t *points)
     if (h->pipe_nout) { g_err = "mc_set_curve: a range begun with mc_range_begin() is still in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     if (K == 0) return h->ab.set_curve(0, nullptr);
+    if (h->ab.classes) { g_err = "mc_set_curve: refused while the counts may ride on class runs (mc_set_abundance_classes) - a prefix of mixed lengths has no one length (K = " + std::to_string(K) + ")"; return -1; }
     if (K < 0 || K > MC_CURVE_MAXK) { g_err = "mc_set_curve: K " + std::to_string(K) + " is not a number of points from 0 to " + std::to_string(MC_CURVE_MAXK); return -1; }
     if (!points) { g_err = "mc_set_curve: " + std::to_string(K) + " points and a NULL array"; return -1; }
     if (!h->ab.on) { g_err = "mc_set_curve: abundance counting is off (mc_set_abundance) - the curve is that of the reads it counts (K = " + std::to_string(K) + ")"; return -1; }
@@ -2074,6 +2081,30 @@ extern "C" int mc_gene_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const d
     HIPCK(hipSetDevice(h->device));
     return h->ab.read_gene_bootstrap(B, seed, scale, counts, stats, dropped);
 }
+
+// the counts on class runs: mc_search_classes and mc_search_files on a class reader are no longer refused, every piece adds to the
+// counts and to the per-class table (k_abund_classes.h), and the gene bootstrap takes the read ids through the batch's id map
+extern "C" int mc_set_abundance_classes(mc_handle *h, int on)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_abundance_classes: a range begun with mc_range_begin() is still in flight (on = " + std::to_string(on) + ")"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (!on) return h->ab.set_classes(false);
+    if (!h->ab.on) { g_err = "mc_set_abundance_classes: abundance counting is off (mc_set_abundance) - the classes are those of the reads it counts (on = " + std::to_string(on) + ")"; return -1; }
+    if (h->ab.curve) { g_err = "mc_set_abundance_classes: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - a prefix of mixed lengths has no one length (on = " + std::to_string(on) + ")"; return -1; }
+    return h->ab.set_classes(true);
+}
+
+// rows[k], assigned[k] of class k = 0 .. n - 2 and, at n - 1, the rows below the lowest class; n: the classes of mc_set_run_classes + 1
+extern "C" int mc_abundance_classes_read(mc_handle *h, int64_t *rows, int64_t *assigned, int32_t n)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.classes) { g_err = "mc_abundance_classes_read: the counts do not ride on class runs (mc_set_abundance_classes)"; return -1; }
+    if (!h->cls_set || n != h->cls.K + 1) { g_err = "mc_abundance_classes_read: the arrays hold " + std::to_string(n) + " values, the run has " + std::to_string(h->cls_set ? h->cls.K : 0) + " classes and the rows below them (mc_set_run_classes)"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_classes(rows, assigned, n);
+}
+extern "C" float mc_abundance_classes_ms(const mc_handle *h) { return h ? h->ab.cls_ms : 0.0f; }
 
 // k_geneboot_collect's time over the completed ranges plus the reads' kernels, since the last zeroing
 extern "C" float mc_gene_bootstrap_ms(const mc_handle *h) { return h ? h->ab.gboot_ms + h->ab.gread_ms : 0.0f; }

@@ -48,6 +48,11 @@ def parse_arguments(argv=None):
     p.add_argument("--bootstrap", dest="bootstrap", type=int, default=None, metavar="B", help="add rpkg_boot_se, rpkg_ci95_low and rpkg_ci95_high: the standard error and 95%% interval of every RPKG from B Poisson-bootstrap "
                    "replicates of the sampled reads (1 - 4096); with the default AGS every replicate is divided by its own AGS estimate, with --ags / --ags-report by the given one.  Not combined with --curve")
     p.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=None, metavar="S", help="with --bootstrap: the seed of the replicates (default = 0)")
+    p.add_argument("--mixed-lengths", dest="mixed_lengths", nargs="?", const=True, default=None, metavar="L1,L2,...",
+                   type=lambda v: [int(x) for x in v.split(",")],
+                   help="count every read at the largest of the model's read lengths it reaches, instead of cutting all reads to one length and dropping the shorter ones; "
+                        "the genome equivalents are those of the bases so sampled.  The optional list names the length classes (default: the length_classes line of --ags-report, "
+                        "else the model's lengths that at least 1%% of the first 10,000 reads fall in).  Not combined with -l and --curve; --bootstrap under it needs --ags or --ags-report")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):
