@@ -635,6 +635,35 @@ int mc_abundance_classes_read(mc_handle *h, int64_t *rows /* [n] */, int64_t *as
 /* Milliseconds the per-class table's kernel took since the last reset (HIP events; one single-thread kernel per piece). */
 float mc_abundance_classes_ms(const mc_handle *h);
 
+/* ---- Genes longer than one database sequence: segments and the fold (csrc/mc_fold.h states the rule) ------------------------------
+ * The engine opens no sequence of more than 1,192 residues (MC_FOLD_SEG_LEN).  A longer gene is searched as overlapping segments -
+ * segment j at offset j x (MC_FOLD_SEG_LEN - MC_FOLD_OVERLAP), consecutive ones sharing MC_FOLD_OVERLAP = 512 residues - each an ordinary
+ * sequence of the index, and a kernel (csrc/k_fold.h) folds every row of a finished range back onto its gene before any abundance
+ * kernel sees it: subject -> the gene's index, sstart and send shifted by the segment's offset.  The caller cuts the genes (the Python
+ * layer: abundance.split_genes) and says how with three maps.
+ * mc_open_stats() is mc_open() with the totals of the UNSPLIT database: stat_nseq sequences of stat_nres residues enter the length
+ * adjustment and the search space of every table, so bits and loge of an alignment are those it has against the unsplit genes.
+ * Nothing else reads them; refused: stat_nseq < 1 or stat_nres < stat_nseq.
+ * mc_set_gene_fold(): seg_gene[s] and seg_off[s], the gene and the offset in it of sequence s of the index; gene_len[g], the residues of
+ * gene g; ngenes == 0 turns the fold off.  While it is on every size of the abundance ABI above - the arrays of mc_abundance_read,
+ * mc_coverage_read, mc_coverage_depth, mc_ties_read (and group_of), mc_ties_coverage_read, mc_curve_read and mc_gene_bootstrap - is
+ * the GENES': mc_abundance_count() sequences, mc_abundance_residues() residues (the index's while it is off).  Rows handed to the host
+ * (mc_result_rows, m8) stay what the engine produced.  Set it BEFORE mc_set_abundance: with the counts on it is refused unless the
+ * tables keep their sizes, and then it zeroes every counter like the other switches.
+ * Refused, with a message naming the value: a range in flight; a map that does not ascend gene by gene from gene 0 to ngenes - 1;
+ * offsets that are not j steps of one step S into their gene; an inner segment that does not have the one length L > S or does not
+ * end before its gene does; a last segment that does not end where gene_len says; a gene of more than 65,535 residues; coverage
+ * offsets (the sum of gene_len + 1) that pass 2^32.
+ * mc_gene_fold_stats(): ngenes (0: off); edge_rows, the rows since the last zeroing whose span touched an interior segment edge
+ * (sstart == 0 on a segment that is not its gene's first, or send on the last residue of one that is not its gene's last) - the
+ * witness that the overlap was wide enough, not a filter; ms, the fold kernel's milliseconds since then (HIP events).  Any may be NULL. */
+mc_handle *mc_open_stats(const char *const *names, const char *const *seqs, int32_t nseq, const int32_t *marker_family, int32_t nfam, int32_t device,
+                         int64_t stat_nres, int32_t stat_nseq);
+int mc_set_gene_fold(mc_handle *h, int32_t ngenes, const int32_t *seg_gene /* [nseq] */, const int32_t *seg_off /* [nseq] */, const int32_t *gene_len /* [ngenes] */);
+int mc_gene_fold_stats(mc_handle *h, int32_t *ngenes, int64_t *edge_rows, float *ms);
+int32_t mc_abundance_count(const mc_handle *h);
+int64_t mc_abundance_residues(const mc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

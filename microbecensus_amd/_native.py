@@ -247,6 +247,14 @@ def load_library():
     lib.mc_abundance_classes_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mc_abundance_classes_ms.restype = C.c_float
     lib.mc_abundance_classes_ms.argtypes = [C.c_void_p]
+    lib.mc_open_stats.restype = C.c_void_p
+    lib.mc_open_stats.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.mc_set_gene_fold.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mc_gene_fold_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mc_abundance_count.restype = C.c_int32
+    lib.mc_abundance_count.argtypes = [C.c_void_p]
+    lib.mc_abundance_residues.restype = C.c_int64
+    lib.mc_abundance_residues.argtypes = [C.c_void_p]
     lib.mc_debug_live.restype = None
     lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
@@ -268,7 +276,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms",
                     "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms",
                     "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms",
-                    "mc_set_abundance_classes", "mc_abundance_classes_read", "mc_abundance_classes_ms", "mc_debug_live"]
+                    "mc_set_abundance_classes", "mc_abundance_classes_read", "mc_abundance_classes_ms", "mc_open_stats", "mc_set_gene_fold", "mc_gene_fold_stats",
+                    "mc_abundance_count", "mc_abundance_residues", "mc_debug_live"]
 
 
 class DupSet:
@@ -743,7 +752,9 @@ def _grid_pids(max_pids):
 class Engine:
     """One MI355X: marker index resident in HBM + the search/classify pipeline."""
 
-    def __init__(self, device=0, names=None, seqs=None, marker_family=None, nfam=None):
+    def __init__(self, device=0, names=None, seqs=None, marker_family=None, nfam=None, stats=None):
+        """stats: (residues, sequences) of the database the alignment statistics are those of, when (names, seqs) are its segments
+        (mc_open_stats; abundance.split_genes); None: the database's own."""
         lib = load_library()
         use_index_cache()
         if names is None:
@@ -755,9 +766,9 @@ class Engine:
         an = (C.c_char_p * n)(*[s.encode() for s in names])
         asq = (C.c_char_p * n)(*[s.encode() for s in seqs])
         fam = (C.c_int32 * n)(*marker_family)
-        self.h = lib.mc_open(an, asq, n, fam, nfam, device)
+        self.h = lib.mc_open(an, asq, n, fam, nfam, device) if stats is None else lib.mc_open_stats(an, asq, n, fam, nfam, device, int(stats[0]), int(stats[1]))
         if not self.h:
-            raise RuntimeError("mc_open failed: %s" % lib.mc_last_error().decode())
+            raise RuntimeError("%s failed: %s" % ("mc_open" if stats is None else "mc_open_stats", lib.mc_last_error().decode()))
         self.read_len = None
 
     @classmethod
@@ -921,9 +932,36 @@ class Engine:
         """Zeroes the abundance counters and abundance_ms() (mc_abundance_reset)."""
         self._check(self.lib.mc_abundance_reset(self.h), "mc_abundance_reset")
 
+    def abundance_count(self):
+        """The sequences every abundance table is sized by (mc_abundance_count): the database's, or the genes' under set_gene_fold."""
+        return int(self.lib.mc_abundance_count(self.h))
+
+    def set_gene_fold(self, seg_gene=None, seg_off=None, gene_len=None):
+        """The fold of long genes (mc_set_gene_fold; csrc/mc_fold.h states the rule): the engine was opened on SEGMENTS - seg_gene[s] and
+        seg_off[s] are the gene and the offset in it of database sequence s, gene_len[g] the residues of gene g (abundance.split_genes
+        makes all three) - and from now on every row of a range is folded onto its gene before the abundance kernels see it: counts,
+        coverage, ties, curve, gene bootstrap and classes are the genes', and every array they return has one entry per GENE.  Rows
+        that reach the host (search, keep_rows) stay the engine's.  None turns it off.  Refused, naming the value: a map that does
+        not ascend gene by gene, offsets or lengths that do not fit the segments, a range in flight, abundance counting on with
+        tables of another size (set it before set_abundance)."""
+        if seg_gene is None:
+            self._check(self.lib.mc_set_gene_fold(self.h, 0, None, None, None), "mc_set_gene_fold")
+            return
+        sg, so, gl = (np.ascontiguousarray(x, dtype=np.int32) for x in (seg_gene, seg_off, gene_len))
+        if sg.shape != (len(self.names),) or so.shape != sg.shape:
+            raise ValueError("seg_gene and seg_off hold %d and %d values, the database %d sequences" % (sg.size, so.size, len(self.names)))
+        self._check(self.lib.mc_set_gene_fold(self.h, int(gl.size), sg.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), gl.ctypes.data_as(C.c_void_p)), "mc_set_gene_fold")
+
+    def gene_fold_stats(self):
+        """{"ngenes": the genes of the fold (0: off), "edge_rows": the rows that touched an interior segment edge since the last reset -
+        the witness that the overlap was wide enough -, "ms": k_fold's milliseconds since then (HIP events)} (mc_gene_fold_stats)."""
+        ng, edge, ms = C.c_int32(0), C.c_int64(0), C.c_float(0)
+        self._check(self.lib.mc_gene_fold_stats(self.h, C.byref(ng), C.byref(edge), C.byref(ms)), "mc_gene_fold_stats")
+        return {"ngenes": int(ng.value), "edge_rows": int(edge.value), "ms": float(ms.value)}
+
     def abundance(self):
         """The counters as they stand (mc_abundance_read): {"reads": int64[nseq], "aligned": int64[nseq], "searched": int, "assigned": int}."""
-        n = len(self.names)
+        n = self.abundance_count()
         reads = np.zeros(n, np.int64); aligned = np.zeros(n, np.int64)
         searched, assigned = C.c_int64(0), C.c_int64(0)
         self._check(self.lib.mc_abundance_read(self.h, reads.ctypes.data_as(C.c_void_p), aligned.ctypes.data_as(C.c_void_p), C.byref(searched), C.byref(assigned)),
@@ -942,7 +980,7 @@ class Engine:
 
     def coverage(self):
         """The per-gene figures as they stand (mc_coverage_read): {"covered", "spanned", "max_depth"}, int64[nseq] each."""
-        n = len(self.names)
+        n = self.abundance_count()
         out = {k: np.zeros(n, np.int64) for k in ("covered", "spanned", "max_depth")}
         self._check(self.lib.mc_coverage_read(self.h, *(out[k].ctypes.data_as(C.c_void_p) for k in ("covered", "spanned", "max_depth"))), "mc_coverage_read")
         return out
@@ -950,10 +988,7 @@ class Engine:
     def coverage_depth(self):
         """The depth of every residue (mc_coverage_depth): one uint32 array, the genes one after the other in FASTA order - the caller
         splits it by the genes' lengths."""
-        p = [C.c_void_p() for _ in range(5)]
-        nres, npost, thr, lp = C.c_int64(), C.c_int64(), C.c_uint32(), (C.c_double * 10)()
-        self._check(self.lib.mc_index_view(self.h, *[C.byref(x) for x in p], C.byref(nres), C.byref(npost), C.byref(thr), lp), "mc_index_view")
-        depth = np.zeros(int(nres.value), np.uint32)
+        depth = np.zeros(int(self.lib.mc_abundance_residues(self.h)), np.uint32)
         self._check(self.lib.mc_coverage_depth(self.h, depth.ctypes.data_as(C.c_void_p), depth.size), "mc_coverage_depth")
         return depth
 
@@ -968,8 +1003,8 @@ class Engine:
         on=False frees them.  Refused while set_abundance is off."""
         if on and group_of is not None:
             g = np.ascontiguousarray(group_of, dtype=np.int32)
-            if g.shape != (len(self.names),):
-                raise ValueError("group_of holds %d values, the database %d sequences" % (g.size, len(self.names)))
+            if g.shape != (self.abundance_count(),):
+                raise ValueError("group_of holds %d values, the database %d sequences" % (g.size, self.abundance_count()))
             rc = self.lib.mc_set_ties(self.h, 1, g.ctypes.data_as(C.c_void_p), int(ngroups))
         else:
             rc = self.lib.mc_set_ties(self.h, 1 if on else 0, None, int(ngroups) if on else 0)
@@ -979,7 +1014,7 @@ class Engine:
     def ties(self):
         """The tie counters as they stand (mc_ties_read): {"candidates", "unique": int64[nseq], "share": uint64[nseq] in units of 2^-32,
         "group_unique": int64[ngroups], "ambiguous", "group_ambiguous": int}."""
-        n = len(self.names)
+        n = self.abundance_count()
         out = {"candidates": np.zeros(n, np.int64), "unique": np.zeros(n, np.int64), "share": np.zeros(n, np.uint64),
                "group_unique": np.zeros(getattr(self, "_ties_ngroups", 0), np.int64)}
         amb, gamb = C.c_int64(0), C.c_int64(0)
@@ -990,7 +1025,7 @@ class Engine:
 
     def ties_coverage(self):
         """The per-gene figures of the any-depth (mc_ties_coverage_read): {"covered_any", "spanned_any", "max_depth_any"}, int64[nseq] each."""
-        n = len(self.names)
+        n = self.abundance_count()
         out = {k: np.zeros(n, np.int64) for k in ("covered_any", "spanned_any", "max_depth_any")}
         self._check(self.lib.mc_ties_coverage_read(self.h, *(out[k].ctypes.data_as(C.c_void_p) for k in ("covered_any", "spanned_any", "max_depth_any"))), "mc_ties_coverage_read")
         return out
@@ -1008,7 +1043,7 @@ class Engine:
         """The curve as it stands (mc_curve_read): {"reads", "aligned": int64[K, nseq], "covered": int64[K, nseq] (with covered=True:
         coverage must be on), "assigned": int64[K], "beyond": int} - row k is what abundance() and coverage()["covered"] return after
         a run on the first n_k reads alone; beyond counts the assigned reads behind the last point."""
-        K, n = int(self.lib.mc_curve_k(self.h)), len(self.names)                  # (the library's K sizes the arrays, however the curve was set)
+        K, n = int(self.lib.mc_curve_k(self.h)), self.abundance_count()                  # (the library's K sizes the arrays, however the curve was set)
         out = {k: np.zeros((K, n), np.int64) for k in (("reads", "aligned", "covered") if covered else ("reads", "aligned"))}
         out["assigned"] = np.zeros(K, np.int64)
         beyond = C.c_int64(0)
@@ -1033,7 +1068,7 @@ class Engine:
         float64[nseq, 6] - sum, m2, x[lo], x[lo + 1], x[hi], x[hi + 1] of the used values (double)c[b][s] * scale[b] -, "used": m,
         "dropped": 0} and with counts=True "counts": int64[nseq, B].  scale: B doubles; replicate b is used when scale[b] is finite and
         > 0.  Raises when a read did not fit the list (the message names how many)."""
-        B, n = int(B), len(self.names)
+        B, n = int(B), self.abundance_count()
         sc = np.ascontiguousarray(scale, dtype=np.float64)
         if sc.shape != (max(B, 0),):
             raise ValueError("scale holds %d values, B is %d" % (sc.size, B))

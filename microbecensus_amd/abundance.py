@@ -58,6 +58,7 @@ under the same classes: numerator and denominator still come from the same sampl
 import gzip
 import math
 import os
+import re
 
 import numpy as np
 
@@ -65,6 +66,18 @@ from . import _native, microbe_census
 
 MAX_GENES = 32767         # MC_POST8 (csrc/mc_core.h): the engine's limits on a protein database
 MAX_GENE_LEN = 2047
+
+
+def _fold_define(name):
+    """an integer constant of csrc/mc_fold.h: the rule of long genes is stated there once, and the library compiles that text"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "mc_fold.h")) as f:
+        return int(re.search(r"^#define %s (\d+)\b" % name, f.read(), re.M).group(1))
+
+
+SEG_LEN = _fold_define("MC_FOLD_SEG_LEN")                 # long genes (long_genes; csrc/mc_fold.h): the longest sequence the engine opens,
+SEG_OVERLAP = _fold_define("MC_FOLD_OVERLAP")         # what consecutive segments of a longer gene share,
+MAX_LONG_GENE_LEN = _fold_define("MC_FOLD_MAX_GENE")   # and the gene-space limits
+MAX_SEGMENTS = _fold_define("MC_FOLD_MAX_SEGS")
 
 COLUMNS = ("gene", "length_aa", "reads", "aligned_aa", "rpkg")
 GROUP_COLUMNS = ("group", "genes", "reads", "rpkg")
@@ -84,9 +97,9 @@ class AbundanceError(Exception):
     """What run_abundance refuses - before any GPU work."""
 
 
-def read_genes(path):
+def read_genes(path, long_genes=False):
     """(names, seqs) of a protein FASTA (plain or .gz): a gene's name is the header's first token.  Refused: an empty FASTA, more than
-    32,767 sequences, a sequence of more than 2,047 residues or of none, duplicate names."""
+    32,767 sequences, a sequence of more than 2,047 residues (with long_genes: of more than 65,535) or of none, duplicate names."""
     if not os.path.isfile(path):
         raise AbundanceError("Gene FASTA %s not found" % path)
     names, seqs = _native.load_markers(path) if not _starts_headless(path) else ([], [])
@@ -99,11 +112,47 @@ def read_genes(path):
         if nm in seen:
             raise AbundanceError("Gene name %s occurs more than once in %s" % (nm, path))
         seen.add(nm)
-        if len(sq) > MAX_GENE_LEN:
-            raise AbundanceError("Gene %s is %d residues long: longer than %d" % (nm, len(sq), MAX_GENE_LEN))
+        if long_genes and len(sq) > MAX_LONG_GENE_LEN:
+            raise AbundanceError("Gene %s is %d residues long: longer than %d, the limit of --long-genes" % (nm, len(sq), MAX_LONG_GENE_LEN))
+        if not long_genes and len(sq) > MAX_GENE_LEN:
+            raise AbundanceError("Gene %s is %d residues long: longer than %d (--long-genes searches a long gene as overlapping segments)" % (nm, len(sq), MAX_GENE_LEN))
         if len(sq) == 0:
             raise AbundanceError("Gene %s has no residues" % nm)
     return names, seqs
+
+
+def segment_offsets(length, seg_len, overlap):
+    """The offsets of the segments of a gene of `length` residues (csrc/mc_fold.h, "the segments"): one at 0 for a gene of at most
+    seg_len residues, otherwise j * (seg_len - overlap) for j = 0, 1, .. up to the first segment that reaches the gene's end."""
+    step = seg_len - overlap
+    n = 1 if length <= seg_len else 1 + -(-(length - seg_len) // step)
+    return [j * step for j in range(n)]
+
+
+def split_genes(names, seqs, seg_len=SEG_LEN, overlap=SEG_OVERLAP):
+    """The genes as the engine takes them under long_genes (csrc/mc_fold.h states the rule): every gene of more than seg_len residues
+    cut into segments of seg_len that overlap by `overlap`, every other gene as it is.  Returns a dict: seg_names and seg_seqs (the
+    database to open - a segment is named <gene>|<offset>, a gene of one segment keeps its name), seg_gene, seg_off (int32 per
+    segment) and gene_len (int32 per gene) - the three maps of Engine.set_gene_fold -, stats (residues, sequences of the GENES: the
+    database the alignment statistics are those of, Engine(stats=)), and genes_split.  Refused, naming the value: a gene of more than
+    65,535 residues, and the gene at which the segments pass 32,767."""
+    if not 0 <= overlap < seg_len:
+        raise AbundanceError("An overlap of %d residues does not fit segments of %d" % (overlap, seg_len))
+    seg_names, seg_seqs, seg_gene, seg_off, split = [], [], [], [], 0
+    for g, (nm, sq) in enumerate(zip(names, seqs)):
+        if len(sq) > MAX_LONG_GENE_LEN:
+            raise AbundanceError("Gene %s is %d residues long: longer than %d, the limit of --long-genes" % (nm, len(sq), MAX_LONG_GENE_LEN))
+        offs = segment_offsets(len(sq), seg_len, overlap)
+        if len(seg_names) + len(offs) > MAX_SEGMENTS:
+            raise AbundanceError("Gene %s (%d residues, %d segments) takes the database past %d segments: %d before it" % (nm, len(sq), len(offs), MAX_SEGMENTS, len(seg_names)))
+        split += len(offs) > 1
+        for o in offs:
+            seg_names.append(nm if len(offs) == 1 else "%s|%d" % (nm, o))
+            seg_seqs.append(sq[o:o + seg_len])
+            seg_gene.append(g)
+            seg_off.append(o)
+    return {"seg_names": seg_names, "seg_seqs": seg_seqs, "seg_gene": np.array(seg_gene, np.int32), "seg_off": np.array(seg_off, np.int32),
+            "gene_len": np.array([len(s) for s in seqs], np.int32), "stats": (sum(len(s) for s in seqs), len(seqs)), "genes_split": int(split)}
 
 
 def _starts_headless(path):
@@ -379,6 +428,8 @@ def header_lines(args, table):
             h.append(("reads_ambiguous_across_groups", table["reads_ambiguous_across_groups"]))
     if table.get("curve") is not None:
         h.append(("curve", len(table["curve"]["points"])))
+    if table.get("long_genes") is not None:
+        h += [("long_genes", "on")] + [(k, table["long_genes"][k]) for k in ("genes_split", "segments", "edge_rows")]
     return ["# %s:\t%s\n" % kv for kv in h]
 
 
@@ -505,7 +556,7 @@ def check_request(args):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
                          ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
-                         ("bootstrap", None), ("bootstrap_seed", None), ("mixed_lengths", None)):
+                         ("bootstrap", None), ("bootstrap_seed", None), ("mixed_lengths", None), ("long_genes", False)):
         args.setdefault(key, default)
     mixed = microbe_census.mixed_lengths_on(args)
     if mixed:
@@ -583,7 +634,11 @@ def check_request(args):
     if args["ags"] is not None:
         source = "--ags"
         ags = check_ags(args["ags"], source)
-    names, seqs = read_genes(args["genes"])
+    if not isinstance(args["long_genes"], (bool, int)) or args["long_genes"] not in (0, 1):
+        raise AbundanceError("long_genes %r is not a switch: True or False" % (args["long_genes"],))
+    args["long_genes"] = bool(args["long_genes"])
+    names, seqs = read_genes(args["genes"], args["long_genes"])
+    args["gene_fold"] = split_genes(names, seqs) if args["long_genes"] else None      # (refused here: before any GPU work)
     group_of = read_groups(args["groups"], names) if args["groups"] else None
     if args["ags_report"] is not None:
         source = "report %s" % args["ags_report"]
@@ -602,7 +657,9 @@ def run_abundance(args):
     - the sampler then runs to its end before the search starts; sets args['curve_ms']; writes <outfile>.curve.tsv) and curve_genes (a path:
     the curve's per-gene matrix), bootstrap (B, 1 .. 4096: the columns rpkg_boot_se, rpkg_ci95_low, rpkg_ci95_high from B Poisson-bootstrap
     replicates of the sampled reads under bootstrap_seed (default 0) - with run_pipeline's AGS every replicate is divided by its own
-    genome equivalents, with a given AGS by the fixed ones; sets args['gene_bootstrap_ms']; not combined with curve).  Writes args['outfile'] (and
+    genome equivalents, with a given AGS by the fixed ones; sets args['gene_bootstrap_ms']; not combined with curve), long_genes (genes of up to
+    65,535 residues: split_genes cuts the long ones into overlapping segments, the engine folds every row back onto its gene, every table is the genes';
+    table['long_genes'] = {genes_split, segments, edge_rows}; sets args['gene_fold_ms']).  Writes args['outfile'] (and
     <outfile>.groups.tsv with groups) when it is set; returns (table, args) - table: the columns as arrays (gene, length_aa, reads,
     aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
     names, seqs, group_of, ags, source = check_request(args)
@@ -639,7 +696,12 @@ def run_abundance(args):
     rd = _native.Reader.with_classes(pargs["seqfiles"], classes, *sampler) if mixed else _native.Reader(pargs["seqfiles"], L, *sampler)
     eng = None
     try:
-        eng = _native.Engine(device=int(args.get("device") or 0), names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
+        fold = args["gene_fold"]
+        if fold is None:
+            eng = _native.Engine(device=int(args.get("device") or 0), names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
+        else:                   # long_genes: the engine on the segments with the genes' statistics, every table below in gene space
+            eng = _native.Engine(device=int(args.get("device") or 0), names=fold["seg_names"], seqs=fold["seg_seqs"], marker_family=[0] * len(fold["seg_names"]), nfam=1, stats=fold["stats"])
+            eng.set_gene_fold(fold["seg_gene"], fold["seg_off"], fold["gene_len"])
         if mixed:               # (the default parameters: classification does not enter the counts)
             eng.set_run_classes(classes)
         else:
@@ -714,6 +776,7 @@ def run_abundance(args):
             args["coverage_ms"] = eng.coverage_ms()
         if args["ties"]:
             args["ties_ms"] = eng.ties_ms()
+        fs = eng.gene_fold_stats() if fold is not None else None
         st = rd.stats()
     finally:
         rd.close()
@@ -745,6 +808,9 @@ def run_abundance(args):
              "sampled_reads": sampled, "trimmed_length": L, "ags": ags, "ags_source": source, "genome_equivalents_sampled": ge, "reads_assigned": ab["assigned"]}
     if mixed:
         table.update({"length_classes": list(classes), "class_reads": class_reads, "class_reads_assigned": class_assigned, "sampled_bases": bases})
+    if fs is not None:
+        table["long_genes"] = {"genes_split": fold["genes_split"], "segments": len(fold["seg_names"]), "edge_rows": fs["edge_rows"]}
+        args["gene_fold_ms"] = fs["ms"]
     if cov is not None:
         breadth, mean_depth = coverage_columns(length_aa, cov["covered"], cov["spanned"])
         table.update({"covered_aa": cov["covered"], "breadth": breadth, "mean_depth": mean_depth, "max_depth": cov["max_depth"], "spanned_aa": cov["spanned"]})

@@ -1,6 +1,7 @@
 // mc_abund.h - the one owner of the per-gene counts (mc_set_abundance), the coverage depth (mc_set_coverage), the tie accounting
 // (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap) and the counts on class runs
 // (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
+// With a gene fold (mc_set_gene_fold, mc_fold.h) it also owns the fold of a range's rows from segments onto genes (k_fold.h), in front of everything else.
 // k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
 // hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end.
 #pragma once
@@ -10,6 +11,7 @@
 #include "k_curve.h"
 #include "k_geneboot.h"
 #include "k_abund_classes.h"
+#include "k_fold.h"
 #include "mc_owned.h"
 
 // ---- Layout: every size and offset of the four tables (k_ties.h, k_coverage.h and k_curve.h, "Layout", say what the slots hold) -----------------
@@ -118,6 +120,8 @@ static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hip
 //     the genes' cursors and compact indices, the scales, the output, its three events   the gene bootstrap is on
 //     the bootstrap's matrix of replicate counts                                  the gene bootstrap is on and a read has sized it
 //     the per-class table (k_abund_classes.h), its event                          the counts may ride on class runs
+//     the segment records, the genes' offsets, the edge counter, its two events   a gene fold is set (set_fold; with the counts on or off)
+//     the folded rows                                                             a gene fold is set and a range has sized them (launch grows them)
 // Coverage, ties, the curve, the gene bootstrap and the class ride are on only while the counts are.  Every switch that goes on, and reset(), zeroes ALL
 // counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the bootstrap's cursor and dropped counter
 // (an empty list), the per-class table, `searched` and the times: counts, depth, ties, curve, bootstrap and classes describe the same reads.  A switch that goes off
@@ -138,9 +142,15 @@ struct McAbundance {
     McDev<unsigned long long> d_cls; McEvent ev_cls; float cls_ms = 0;   // the per-class table; behind k_abund_class_add; its time since the last zeroing
     McIdMap map = {nullptr, 0}; int32_t map_K = 0, piece_k = 0;    // held while a batch's pieces run (ride_begin .. ride_end): its ids, its classes; the class of the piece that ends next
     int64_t searched = 0;                                          // the reads of the completed ranges
+    // the gene fold (mc_set_gene_fold, mc_fold.h): while it is set nseq, nres and off above are the GENES' - every table, scan and reader is
+    // in gene space - and ix_* keep what bind() was given, the segments of the index
+    int32_t ix_nseq = 0; size_t ix_nres = 0; const uint32_t *ix_off = nullptr;
+    bool fold = false; size_t folded_cap = 0;                      // folded_cap: the rows d_folded holds
+    McDev<McFoldSeg> d_seg; McDev<uint32_t> d_goff; McDev<McRow> d_folded; McDev<unsigned long long> d_edge;
+    McEvent ev_fold[2]; float fold_ms = 0;                          // around k_fold of a range; its time since the last zeroing
     float ms = 0, cov_ms = 0, ties_ms = 0;                         // the counting kernels', the scans', k_ties' time since the last zeroing
 
-    void bind(int32_t nseq_, size_t nres_, const uint32_t *d_off) { nseq = nseq_; nres = nres_; off = d_off; }
+    void bind(int32_t nseq_, size_t nres_, const uint32_t *d_off) { nseq = ix_nseq = nseq_; nres = ix_nres = nres_; off = ix_off = d_off; }
     bool active() const { return on; }
 
     // ---- the switches ----
@@ -176,6 +186,31 @@ struct McAbundance {
     }
     // on: refused by the caller while the curve is on (mc_set_abundance_classes)
     int set_classes(bool to) { return turn(classes, to); }
+    // The gene fold: seg: ix_nseq records, goff: ngenes + 1 offsets of the genes' residues (both checked and made by the caller,
+    // mc_set_gene_fold); ngenes == 0: off, the tables are the index's again.  The tables are sized by nseq and nres: with the counts on
+    // and another size the caller has refused, so here a size changes only while every table is off; with the counts on all is zeroed.
+    int set_fold(int32_t ngenes, const McFoldSeg *seg, const uint32_t *goff)
+    {
+        fold = false; folded_cap = 0; fold_ms = 0.f;
+        d_seg.reset(); d_goff.reset(); d_folded.reset(); d_edge.reset(); ev_fold[0].reset(); ev_fold[1].reset();
+        nseq = ix_nseq; nres = ix_nres; off = ix_off;
+        if (ngenes == 0) return on ? reset() : 0;
+        if (d_seg.alloc((size_t)ix_nseq) || d_goff.alloc((size_t)ngenes + 1) || d_edge.alloc(1) || ev_fold[0].create() || ev_fold[1].create() ||
+            mc_owned_ck(hipMemcpy(d_seg, seg, sizeof(McFoldSeg) * (size_t)ix_nseq, hipMemcpyHostToDevice), "hipMemcpy(d_seg, seg)") ||
+            mc_owned_ck(hipMemcpy(d_goff, goff, sizeof(uint32_t) * ((size_t)ngenes + 1), hipMemcpyHostToDevice), "hipMemcpy(d_goff, goff)") ||
+            mc_owned_ck(hipMemset(d_edge, 0, sizeof(unsigned long long)), "hipMemset(d_edge)")) { (void)set_fold(0, nullptr, nullptr); return -1; }
+        fold = true; nseq = ngenes; nres = (size_t)goff[ngenes]; off = d_goff;
+        return on ? reset() : 0;
+    }
+    // what a table would be sized by under a fold of ngenes genes and nres_ residues (0 genes: the index's): the caller's refusal
+    bool fold_keeps_sizes(int32_t ngenes, size_t nres_) const { return ngenes ? ngenes == nseq && nres_ == nres : ix_nseq == nseq && ix_nres == nres; }
+    int read_fold(int64_t *edge_rows) const
+    {
+        unsigned long long e = 0;
+        if (fold) HIPCK(hipMemcpy(&e, d_edge, sizeof e, hipMemcpyDeviceToHost));
+        if (edge_rows) *edge_rows = (int64_t)e;
+        return 0;
+    }
     int reset()
     {
         HIPCK(hipMemset(d_counts, 0, sizeof(unsigned long long) * mc_pair_slots((size_t)nseq)));
@@ -186,14 +221,25 @@ struct McAbundance {
         if (d_first) HIPCK(hipMemset(d_first, 0xFF, sizeof(uint32_t) * nres));
         if (d_gcur) HIPCK(hipMemset(d_gcur, 0, sizeof(unsigned long long) * 2));
         if (d_cls) HIPCK(hipMemset(d_cls, 0, sizeof(unsigned long long) * MC_AC_SLOTS));
+        if (d_edge) HIPCK(hipMemset(d_edge, 0, sizeof(unsigned long long)));
+        fold_ms = 0.f;
         searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = 0.f;
         return 0;
     }
 
     // ---- a range (range_end): its final rows where they lie, and what is kept once its stream has been waited for ----
     // nreads: the range's reads - the class table's, while a batch's pieces ride (ride_begin)
+    // With a gene fold the rows are folded FIRST, into d_folded (grown here when a range has more rows than any before it: the kernels of
+    // the range before have been waited for, range_end), and everything behind sees the folded rows: the one site where segments become genes.
     int launch(const McRow *rows, uint32_t nr, hipStream_t st, int64_t nreads = 0)
     {
+        if (fold) {
+            if (nr > folded_cap) { folded_cap = 0; const size_t want = (size_t)nr + nr / 4 + 1024; if (d_folded.alloc(want)) return -1; folded_cap = want; }
+            HIPCK(hipEventRecord(ev_fold[0], st));
+            if (nr) k_fold<<<dim3((nr + 255) / 256), dim3(256), 0, st>>>(rows, nr, ix_nseq, d_seg, d_folded, d_edge);
+            HIPCK(hipEventRecord(ev_fold[1], st));
+            rows = d_folded;
+        }
         const McAbundBufs B = {nseq, off, d_counts, d_diff, d_ties, d_group, d_diff_any};
         const hipEvent_t ev[3] = {ev_count[0], ev_count[1], ev_ties};
         const McCurveBufs C = {K, d_pts, d_bins, d_first, ev_curve};
@@ -226,6 +272,7 @@ struct McAbundance {
     void range_done(int64_t nreads)
     {
         add_searched(nreads); ms += ev_ms(ev_count[0], ev_count[1]);
+        if (fold) fold_ms += ev_ms(ev_fold[0], ev_fold[1]);
         if (ties) ties_ms += ev_ms(ev_count[1], ev_ties);
         if (curve) curve_ms += ev_ms(ties ? ev_ties : ev_count[1], ev_curve);
         if (gboot) gboot_ms += ev_ms(curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_gboot);

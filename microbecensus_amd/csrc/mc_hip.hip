@@ -21,6 +21,7 @@
 //   k_curve.h              the rarefaction curve beside them: per-gene counts per prefix of the sample, every residue's first read, a scan at read time (mc_set_curve)
 //   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
 //   k_abund_classes.h      the per-class table of the counts on class runs (mc_set_abundance_classes)
+//   k_fold.h, mc_fold.h    genes longer than one sequence of the engine: segments, and the fold of a range's rows onto the genes (mc_set_gene_fold)
 //   mc_abund.h             (host) the owner of those five: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
 //   mc_pieces.h            (host) a batch sorted into bins of one length each, cut into the ranges the pipeline runs once per length
 // and the per-thread algorithms they share with the test-only emulation in mc_core.h / mc_finish.h / mc_index.h.
@@ -276,6 +277,7 @@ static int open_impl(mc_handle *h, const int32_t *marker_family, int32_t nfam, i
     if (nfam > 32) { g_err = "at most 32 gene families are supported"; return -1; }
     const int nseq = h->H.nseq;
     if (nseq > 32767) { g_err = "more than 32767 markers: the HSP sort key (read<<43 | subject<<28 | hit order) holds 15 bits of subject index"; return -1; }
+    static_assert(MC_FOLD_SEG_LEN == MC_GAP_W - 8, "a segment of a long gene (mc_fold.h) is the longest sequence this check lets through");
     for (int s = 0; s < nseq; s++) if ((int)(h->H.off[s + 1] - h->H.off[s]) > MC_GAP_W - 8) { g_err = "marker longer than the gapped-extension workspace"; return -1; }
     if (marker_family) h->fam.assign(marker_family, marker_family + nseq); else h->fam.assign((size_t)nseq, 0);
     h->nfam = nfam; h->device = device;
@@ -385,7 +387,8 @@ extern "C" int mc_index_cache_check(const char *const *names, const char *const 
     return 0;
 }
 
-extern "C" mc_handle *mc_open(const char *const *names, const char *const *seqs, int32_t nseq, const int32_t *marker_family, int32_t nfam, int32_t device)
+// stat_nres, stat_nseq: the statistics pair of the index (mc_index.h), 0, 0: unset
+static mc_handle *open_fasta(const char *const *names, const char *const *seqs, int32_t nseq, const int32_t *marker_family, int32_t nfam, int32_t device, int64_t stat_nres, int32_t stat_nseq)
 {
     mc_handle *h = new mc_handle();
     std::string err;
@@ -407,9 +410,24 @@ extern "C" mc_handle *mc_open(const char *const *names, const char *const *seqs,
         MC_OT("mc_build_index", t0);
         if (!cache.empty()) { (void)mc_index_save(h->H, ih, cache.c_str()); MC_OT("index cache: written", t0); }
     }
+    h->H.stat_nres = stat_nres; h->H.stat_nseq = stat_nseq;         // (not part of the cached index: the same segments serve any statistics)
     if (open_impl(h, marker_family, nfam, device) != 0) { std::string e = g_err; mc_close(h); g_err = e; return nullptr; }
     MC_OT("open_impl (device side)", t0);
     return h;
+}
+
+extern "C" mc_handle *mc_open(const char *const *names, const char *const *seqs, int32_t nseq, const int32_t *marker_family, int32_t nfam, int32_t device)
+{
+    return open_fasta(names, seqs, nseq, marker_family, nfam, device, 0, 0);
+}
+
+// mc_open on the SEGMENTS of a database whose alignment statistics are those of the unsplit sequences (mc_fold.h): stat_nseq sequences of
+// stat_nres residues in all enter the length adjustment and the search space of every table (mc_fill_tables) - bits and loge of an
+// alignment are what they would be against the unsplit database - and nothing else
+extern "C" mc_handle *mc_open_stats(const char *const *names, const char *const *seqs, int32_t nseq, const int32_t *marker_family, int32_t nfam, int32_t device, int64_t stat_nres, int32_t stat_nseq)
+{
+    if (stat_nseq < 1 || stat_nres < stat_nseq) { g_err = "mc_open_stats: " + std::to_string(stat_nseq) + " sequences of " + std::to_string(stat_nres) + " residues are no database"; return nullptr; }
+    return open_fasta(names, seqs, nseq, marker_family, nfam, device, stat_nres, stat_nseq);
 }
 
 extern "C" mc_handle *mc_open_rapdb(const char *rapdb_path, int32_t device)
@@ -1985,7 +2003,7 @@ extern "C" int mc_coverage_depth(mc_handle *h, uint32_t *depth, int64_t n)
 {
     if (!h) { g_err = "null handle"; return -1; }
     if (!h->ab.cov) { g_err = "mc_coverage_depth: coverage is off (mc_set_coverage)"; return -1; }
-    if (n != h->H.nres || !depth) { g_err = "mc_coverage_depth: the array holds " + std::to_string(n) + " values, the database " + std::to_string(h->H.nres) + " residues"; return -1; }
+    if (n != (int64_t)h->ab.nres || !depth) { g_err = "mc_coverage_depth: the array holds " + std::to_string(n) + " values, the database " + std::to_string(h->ab.nres) + " residues"; return -1; }
     HIPCK(hipSetDevice(h->device));
     return h->ab.read_depth(depth);
 }
@@ -2000,7 +2018,7 @@ extern "C" int mc_set_ties(mc_handle *h, int on, const int32_t *group_of, int32_
     if (ngroups < 0) { g_err = "mc_set_ties: ngroups " + std::to_string(ngroups) + " is negative"; return -1; }
     if (ngroups > 0 && !group_of) { g_err = "mc_set_ties: " + std::to_string(ngroups) + " groups and a NULL group map"; return -1; }
     if (ngroups == 0) group_of = nullptr;
-    for (size_t s = 0; group_of && s < (size_t)h->H.nseq; s++)
+    for (size_t s = 0; group_of && s < (size_t)h->ab.nseq; s++)                       // (the genes under a fold, mc_set_gene_fold)
         if (group_of[s] < 0 || group_of[s] >= ngroups) { g_err = "mc_set_ties: group_of[" + std::to_string(s) + "] = " + std::to_string(group_of[s]) + " lies outside 0 .. " + std::to_string(ngroups - 1); return -1; }
     return h->ab.set_ties(true, group_of, ngroups);
 }
@@ -2094,6 +2112,79 @@ extern "C" int mc_set_abundance_classes(mc_handle *h, int on)
     if (h->ab.curve) { g_err = "mc_set_abundance_classes: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - a prefix of mixed lengths has no one length (on = " + std::to_string(on) + ")"; return -1; }
     return h->ab.set_classes(true);
 }
+
+// ---- the gene fold (mc_fold.h): the index holds the segments of long genes, every abundance table the genes.  seg_gene[s], seg_off[s]: the
+// gene and the offset in it of segment s of the index, gene_len[g]: the residues of gene g.  Checked here against the index's own segment
+// lengths - every value that is refused is named - and handed to the owner as records (mc_fold_seg's lo and hi from the same facts).
+// ngenes == 0: off.  From here on every size the abundance ABI speaks of (mc_abundance_count and the arrays of the readers) is the genes'.
+extern "C" int mc_set_gene_fold(mc_handle *h, int32_t ngenes, const int32_t *seg_gene, const int32_t *seg_off, const int32_t *gene_len)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_gene_fold: a range begun with mc_range_begin() is still in flight (ngenes = " + std::to_string(ngenes) + ")"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    const int32_t nseq = h->H.nseq;
+    const auto refuse_sizes = [&](int32_t ng, size_t nr) {
+        g_err = "mc_set_gene_fold: abundance counting is on with tables of " + std::to_string(h->ab.nseq) + " sequences and " + std::to_string(h->ab.nres) + " residues, the fold asks for " +
+                std::to_string(ng) + " and " + std::to_string(nr) + " (mc_set_abundance off first)";
+        return -1;
+    };
+    if (ngenes == 0) {
+        if (h->ab.on && !h->ab.fold_keeps_sizes(0, 0)) return refuse_sizes(nseq, (size_t)h->H.nres);
+        return h->ab.set_fold(0, nullptr, nullptr);
+    }
+    if (ngenes < 0 || ngenes > nseq) { g_err = "mc_set_gene_fold: ngenes " + std::to_string(ngenes) + " is not a number of genes from 0 to the index's " + std::to_string(nseq) + " sequences"; return -1; }
+    if (!seg_gene || !seg_off || !gene_len) { g_err = "mc_set_gene_fold: " + std::to_string(ngenes) + " genes and a NULL map"; return -1; }
+    std::vector<McFoldSeg> seg((size_t)nseq); std::vector<uint32_t> goff((size_t)ngenes + 1, 0u);
+    uint64_t at = 0;
+    for (int32_t g = 0; g < ngenes; g++) {
+        if (gene_len[g] < 1 || gene_len[g] > MC_FOLD_MAX_GENE) { g_err = "mc_set_gene_fold: gene_len[" + std::to_string(g) + "] = " + std::to_string(gene_len[g]) + " lies outside 1 .. " + std::to_string(MC_FOLD_MAX_GENE); return -1; }
+        goff[(size_t)g] = (uint32_t)at; at += (uint64_t)gene_len[g];
+        if (at + (uint64_t)g + 1 > 0xFFFFFFFFull) { g_err = "mc_set_gene_fold: the coverage offsets pass 2^32 at gene " + std::to_string(g) + " (" + std::to_string(at) + " residues)"; return -1; }
+    }
+    goff[(size_t)ngenes] = (uint32_t)at;
+    // the map ascends gene by gene, every gene has its segments; a gene's offsets are j * S with one step S for all, every segment but a
+    // gene's last has one length L > S, and the last is the first that reaches gene_len
+    int32_t L = 0, S = 0;                                            // (what the first gene of more than one segment says; 0, 0: no gene is split)
+    for (int32_t s = 1; s < nseq && S == 0; s++)
+        if (seg_gene[s] == seg_gene[s - 1]) { S = seg_off[s]; L = (int32_t)(h->H.off[(size_t)s] - h->H.off[(size_t)s - 1]); }
+    for (int32_t s = 0, g = -1, j = 0; s < nseq; s++, j++) {
+        const int32_t len = (int32_t)(h->H.off[(size_t)s + 1] - h->H.off[(size_t)s]);
+        if (seg_gene[s] != g) {
+            if (seg_gene[s] != g + 1) { g_err = "mc_set_gene_fold: seg_gene[" + std::to_string(s) + "] = " + std::to_string(seg_gene[s]) + " behind gene " + std::to_string(g) + ": the map does not ascend gene by gene"; return -1; }
+            g++; j = 0;
+            if (g >= ngenes) { g_err = "mc_set_gene_fold: seg_gene[" + std::to_string(s) + "] = " + std::to_string(seg_gene[s]) + " lies outside 0 .. " + std::to_string(ngenes - 1); return -1; }
+        }
+        const bool last = s + 1 == nseq || seg_gene[s + 1] != g;
+        if (seg_off[s] < 0 || (j == 0 && seg_off[s] != 0) || (j > 0 && (S <= 0 || seg_off[s] != j * S))) {
+            g_err = "mc_set_gene_fold: seg_off[" + std::to_string(s) + "] = " + std::to_string(seg_off[s]) + " is not " + std::to_string(j) + " steps of " + std::to_string(S) + " into gene " + std::to_string(g); return -1;
+        }
+        const int64_t end = (int64_t)seg_off[s] + len;
+        if (last ? end != gene_len[g] : (end >= gene_len[g] || len != L || L <= S)) {
+            g_err = "mc_set_gene_fold: segment " + std::to_string(s) + " of " + std::to_string(len) + " residues at seg_off " + std::to_string(seg_off[s]) + " does not fit gene " + std::to_string(g) + " of gene_len " +
+                    std::to_string(gene_len[g]) + (last ? ": the last segment ends at " + std::to_string(end) : ": an inner segment has " + std::to_string(L) + " residues, more than the step " + std::to_string(S) + ", and ends before the gene does");
+            return -1;
+        }
+        seg[(size_t)s].gene = g; seg[(size_t)s].off = seg_off[s]; seg[(size_t)s].lo = j > 0 ? 0 : -1; seg[(size_t)s].hi = last ? -1 : len - 1;
+        if (last && s + 1 == nseq && g != ngenes - 1) { g_err = "mc_set_gene_fold: the map ends at gene " + std::to_string(g) + " of " + std::to_string(ngenes); return -1; }
+    }
+    if (h->ab.on && !h->ab.fold_keeps_sizes(ngenes, (size_t)at)) return refuse_sizes(ngenes, (size_t)at);
+    return h->ab.set_fold(ngenes, seg.data(), goff.data());
+}
+
+// ngenes: the genes of the fold, 0: off; edge_rows: the rows that touched an interior segment edge since the last zeroing (mc_fold.h: the
+// witness that the overlap was wide enough); ms: k_fold's time over the completed ranges since then.  Any of the three may be NULL
+extern "C" int mc_gene_fold_stats(mc_handle *h, int32_t *ngenes, int64_t *edge_rows, float *ms)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (ngenes) *ngenes = h->ab.fold ? h->ab.nseq : 0;
+    if (ms) *ms = h->ab.fold_ms;
+    return h->ab.read_fold(edge_rows);
+}
+
+// the sequences and residues every abundance table is sized by: the index's, or the genes' under a fold
+extern "C" int32_t mc_abundance_count(const mc_handle *h) { return h ? h->ab.nseq : -1; }
+extern "C" int64_t mc_abundance_residues(const mc_handle *h) { return h ? (int64_t)h->ab.nres : -1; }
 
 // rows[k], assigned[k] of class k = 0 .. n - 2 and, at n - 1, the rows below the lowest class; n: the classes of mc_set_run_classes + 1
 extern "C" int mc_abundance_classes_read(mc_handle *h, int64_t *rows, int64_t *assigned, int32_t n)

@@ -37,6 +37,10 @@ struct McHostIndex {
     double letter_p[10];
     int64_t nres;
     int nseq;
+    // the database the alignment statistics are those of, when it is not this index: the residues and sequences of the unsplit genes
+    // behind an index of their segments (mc_open_stats, mc_fold.h).  Read by mc_fill_tables and by nobody else; 0, 0: unset, the index's own
+    int64_t stat_nres = 0;
+    int stat_nseq = 0;
 };
 
 static const char *MC_AA_ORDER = "ARNDCQEGHILKMFPSTWYV";
@@ -685,8 +689,9 @@ inline void mc_fill_tables(McTables &T, const McHostIndex &X, int read_len, doub
     T.freq_thr = X.freq_thr;
     for (int g = 0; g < 10; g++) T.letter_p[g] = X.letter_p[g];
     int m = read_len / 3;
-    int adj = (m <= 10) ? 0 : mc_length_adjustment((double)X.nres, (double)X.nseq, m);
-    T.ell = (double)adj; T.mprime = (double)m - T.ell; T.nprime = (double)X.nres - (double)X.nseq * T.ell; T.logK = log(0.041);
+    const double st_nres = (double)(X.stat_nseq ? X.stat_nres : X.nres), st_nseq = (double)(X.stat_nseq ? X.stat_nseq : X.nseq);   // (the statistics pair, or the index's own)
+    int adj = (m <= 10) ? 0 : mc_length_adjustment(st_nres, st_nseq, m);
+    T.ell = (double)adj; T.mprime = (double)m - T.ell; T.nprime = st_nres - st_nseq * T.ell; T.logK = log(0.041);
     for (int s = 0; s < MC_SMAX; s++) {
         double t = 0.041 * T.nprime; t = t * T.mprime;
         double x = exp((double)s * (-0.267)) * t; x = x / (1.0 - 0.1);

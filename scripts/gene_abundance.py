@@ -53,6 +53,9 @@ def parse_arguments(argv=None):
                    help="count every read at the largest of the model's read lengths it reaches, instead of cutting all reads to one length and dropping the shorter ones; "
                         "the genome equivalents are those of the bases so sampled.  The optional list names the length classes (default: the length_classes line of --ags-report, "
                         "else the model's lengths that at least 1%% of the first 10,000 reads fall in).  Not combined with -l and --curve; --bootstrap under it needs --ags or --ags-report")
+    p.add_argument("--long-genes", dest="long_genes", action="store_true", default=False,
+                   help="accept genes of up to 65,535 residues: a gene longer than the engine's longest sequence is searched as overlapping segments and every table "
+                        "reports the whole gene; adds long_genes, genes_split, segments and edge_rows to the header")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):
