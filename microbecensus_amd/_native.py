@@ -1,5 +1,6 @@
 """ctypes binding of libmcensus_hip.so (include/mcensus.h).  No CPU fallback: if the HIP library is
 missing or no MI355X is visible, importing the engine fails loudly."""
+import contextlib
 import ctypes as C
 import gzip
 import json
@@ -841,13 +842,26 @@ class Engine:
         self.class_len = [int(x) for x in class_len]
         self.read_len = self.class_len[-1]
 
-    def search_classes(self, rows, first_read_id=0):
+    @contextlib.contextmanager
+    def _rows_kept(self, keep_rows):
+        """keep_rows=False: the m8 rows of the searches inside stay on the device (mc_set_keep_rows), as under search_files"""
+        if not keep_rows:
+            self._check(self.lib.mc_set_keep_rows(self.h, 0), "mc_set_keep_rows")
+        try:
+            yield
+        finally:
+            if not keep_rows:
+                self.lib.mc_set_keep_rows(self.h, 1)
+
+    def search_classes(self, rows, first_read_id=0, keep_rows=True):
         """rows: uint8 array (n, class_len[-1]), a read's bases then 0 bytes (mc_search_classes).  Returns (best_hits, classes, class_reads):
-        the best hits in ascending read id, the class index of each, and the rows per class (last entry: rows below the lowest class)."""
+        the best hits in ascending read id, the class index of each, and the rows per class (last entry: rows below the lowest class);
+        with keep_rows=False nothing - the counters that were switched on are what the search is for."""
         rows = np.ascontiguousarray(rows, dtype=np.uint8)
         assert rows.ndim == 2
-        self._check(self.lib.mc_search_classes(self.h, rows.ctypes.data_as(C.c_void_p), rows.shape[0], rows.shape[1], first_read_id), "mc_search_classes")
-        return self.class_results()
+        with self._rows_kept(keep_rows):
+            self._check(self.lib.mc_search_classes(self.h, rows.ctypes.data_as(C.c_void_p), rows.shape[0], rows.shape[1], first_read_id), "mc_search_classes")
+        return self.class_results() if keep_rows else None
 
     def class_results(self):
         best = self.best_hits()
@@ -874,12 +888,13 @@ class Engine:
             raise RuntimeError("mc_debug_classes_prologue failed: %s" % self.lib.mc_last_error().decode())
         return perm, start, word0, (srt[:nb] if want_sorted else None), (ms[0], ms[1])
 
-    def search(self, reads, first_read_id=0):
-        """reads: uint8 array (n, read_len) of bases.  Returns (rows, best_hits) as numpy structured arrays."""
+    def search(self, reads, first_read_id=0, keep_rows=True):
+        """reads: uint8 array (n, read_len) of bases.  Returns (rows, best_hits) as numpy structured arrays; with keep_rows=False nothing."""
         reads = np.ascontiguousarray(reads, dtype=np.uint8)
         assert reads.ndim == 2 and reads.shape[1] == self.read_len
-        self._check(self.lib.mc_search(self.h, reads.ctypes.data_as(C.c_void_p), reads.shape[0], first_read_id), "mc_search")
-        return self.results()
+        with self._rows_kept(keep_rows):
+            self._check(self.lib.mc_search(self.h, reads.ctypes.data_as(C.c_void_p), reads.shape[0], first_read_id), "mc_search")
+        return self.results() if keep_rows else None
 
     def search_varlen(self, reads, first_read_id=0):
         """reads of mixed lengths (mc_search_varlen): a list of bytes / str, or (bases uint8 array, offsets int64 array of n + 1).

@@ -90,6 +90,8 @@ CURVE_COLUMNS = ("sampled_reads", "average_genome_size", "genome_equivalents_sam
 BOOT_COLUMNS = ("rpkg_boot_se", "rpkg_ci95_low", "rpkg_ci95_high")                  # behind all of them with bootstrap
 MAX_BOOT = 4096                                                                      # MC_GB_MAXB (csrc/mc_geneboot.h)
 MAX_CURVE = 64                                                                       # MC_CURVE_MAXK (csrc/mc_curve.h)
+PIPELINE_KEYS = ("seqfiles", "nreads", "read_length", "min_quality", "mean_quality", "filter_dups", "max_unknown", "threads", "device", "model_dir", "verbose")
+TEXT = {"s": str, "d": lambda v: "%d" % v, "f": lambda v: repr(float(v)), "n": lambda v: "NA" if v is None else repr(float(v))}   # a value in a table, by its column's kind
 SHARE_ONE = 4294967296.0                                                             # share[] counts in units of 2^-32 (csrc/k_ties.h)
 
 
@@ -407,15 +409,10 @@ def boot_columns(stats, used, length_aa):
     return se, out[0], out[1]
 
 
-def _mixed_header(table):
-    if table.get("length_classes") is None:
-        return []
-    return [(k, ",".join(str(int(x)) for x in table[k])) for k in ("length_classes", "class_reads", "class_reads_assigned")] + [("sampled_bases", table["sampled_bases"])]
-
-
 def header_lines(args, table):
+    mixed = [] if table.get("length_classes") is None else [(k, ",".join(str(int(x)) for x in table[k])) for k in ("length_classes", "class_reads", "class_reads_assigned")] + [("sampled_bases", table["sampled_bases"])]
     h = [("metagenome", ",".join(args["seqfiles"])), ("genes", args["genes"]), ("sampled_reads", table["sampled_reads"]),
-         ("trimmed_length", table["trimmed_length"])] + _mixed_header(table) + [("min_ident", args["min_ident"]), ("min_aln", args["min_aln"]), ("min_bits", repr(float(args["min_bits"]))),
+         ("trimmed_length", table["trimmed_length"])] + mixed + [("min_ident", args["min_ident"]), ("min_aln", args["min_aln"]), ("min_bits", repr(float(args["min_bits"]))),
          ("average_genome_size", repr(float(table["ags"]))), ("ags_source", table["ags_source"]),
          ("genome_equivalents_sampled", repr(float(table["genome_equivalents_sampled"]))), ("reads_assigned", table["reads_assigned"])]
     if table.get("covered_aa") is not None:
@@ -433,53 +430,44 @@ def header_lines(args, table):
     return ["# %s:\t%s\n" % kv for kv in h]
 
 
+def table_columns(table):
+    """[(column, kind)] of the gene table, from the keys the table has - kind s: the value as it is, d: %d, f: repr(float()), n: f or NA"""
+    has = lambda key: table.get(key) is not None
+    groups = ((True, COLUMNS, "sdddf"), (has("covered_aa"), COVERAGE_COLUMNS, "dffd"), (has("detected"), ("detected",), "d"), (has("unique_reads"), TIES_COLUMNS, "ddff"),
+              (has("covered_any_aa"), TIES_COVERAGE_COLUMNS, "df"), (has("detected_any"), ("detected_any",), "d"), (has("rpkg_boot_se"), BOOT_COLUMNS, "fff"))
+    return [c for on, names, kinds in groups if on for c in zip(names, kinds)]
+
+
+def group_columns(table):
+    """[(column, kind)] of the groups table: those of a row of table['groups'] and, with ties, of the same row of table['groups_ties']"""
+    gt = table.get("groups_ties")
+    ties = GROUP_TIES_COLUMNS + (("genes_detected_any",) if table.get("detected_any") is not None else ()) if gt is not None else ()
+    return list(zip(GROUP_COLUMNS + (("genes_detected",) if table.get("detected") is not None else ()), "sddfd")) + list(zip(ties, "dffd"))
+
+
+def _write_rows(out, columns, values):
+    """the header line and the rows of a table, both from ONE list of (column, kind); values: the columns' values, a sequence per column"""
+    out.write("\t".join(name for name, _ in columns) + "\n")
+    text = [[TEXT[kind](v) for v in (col.tolist() if isinstance(col, np.ndarray) else col)] for (_, kind), col in zip(columns, values)]
+    out.writelines("\t".join(row) + "\n" for row in zip(*text))
+
+
 def write_table(path, args, table):
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
-        boot = table.get("rpkg_boot_se") is not None
-        if boot:                                                   # (the gene table's alone: the groups table does not bootstrap)
+        if table.get("rpkg_boot_se") is not None:                  # (the gene table's alone: the groups table does not bootstrap)
             out.writelines("# %s:\t%s\n" % kv for kv in (("bootstrap", table["bootstrap"]), ("bootstrap_seed", table["bootstrap_seed"]),
                                                          ("bootstrap_replicates", "%d/%d" % (table["boot_used"], table["bootstrap"])),
                                                          ("bootstrap_denominator", table["bootstrap_denominator"])))
-        cov, det = table.get("covered_aa") is not None, table.get("detected") is not None
-        ties, tcov, tdet = table.get("unique_reads") is not None, table.get("covered_any_aa") is not None, table.get("detected_any") is not None
-        out.write("\t".join(COLUMNS + (COVERAGE_COLUMNS if cov else ()) + (("detected",) if det else ()) + (TIES_COLUMNS if ties else ())
-                            + (TIES_COVERAGE_COLUMNS if tcov else ()) + (("detected_any",) if tdet else ()) + (BOOT_COLUMNS if boot else ())) + "\n")
-        for k, (nm, ln, r, a, v) in enumerate(zip(table["gene"], table["length_aa"], table["reads"], table["aligned_aa"], table["rpkg"])):
-            line = "%s\t%d\t%d\t%d\t%s" % (nm, ln, r, a, repr(float(v)))
-            if cov:
-                line += "\t%d\t%s\t%s\t%d" % (table["covered_aa"][k], repr(float(table["breadth"][k])), repr(float(table["mean_depth"][k])), table["max_depth"][k])
-            if det:
-                line += "\t%d" % table["detected"][k]
-            if ties:
-                line += "\t%d\t%d\t%s\t%s" % (table["unique_reads"][k], table["candidate_reads"][k], repr(float(table["shared_reads"][k])), repr(float(table["rpkg_shared"][k])))
-            if tcov:
-                line += "\t%d\t%s" % (table["covered_any_aa"][k], repr(float(table["breadth_any"][k])))
-            if tdet:
-                line += "\t%d" % table["detected_any"][k]
-            if boot:
-                line += "\t%s\t%s\t%s" % tuple(repr(float(table[c][k])) for c in BOOT_COLUMNS)
-            out.write(line + "\n")
+        columns = table_columns(table)
+        _write_rows(out, columns, [table[name] for name, _ in columns])
 
 
 def write_groups(path, args, table):
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
         out.write("# groups:\t%s\n" % args["groups"])
-        det = table.get("detected") is not None
-        gt = table.get("groups_ties")
-        tdet = gt is not None and table.get("detected_any") is not None
-        out.write("\t".join(GROUP_COLUMNS + (("genes_detected",) if det else ()) + (GROUP_TIES_COLUMNS if gt is not None else ()) + (("genes_detected_any",) if tdet else ())) + "\n")
-        for k, row in enumerate(table["groups"]):
-            g, n, r, v = row[:4]
-            more = ""
-            if gt is not None:
-                more = "\t%d\t%s\t%s" % (gt[k][0], repr(float(gt[k][1])), repr(float(gt[k][2]))) + ("\t%d" % gt[k][3] if tdet else "")
-            out.write("%s\t%d\t%d\t%s%s%s\n" % (g, n, r, repr(float(v)), "\t%d" % row[4] if det else "", more))
-
-
-def _na(v, fmt=repr):
-    return "NA" if v is None else fmt(v)
+        _write_rows(out, group_columns(table), list(zip(*table["groups"])) + list(zip(*(table.get("groups_ties") or []))))
 
 
 def curve_figures(names, length_aa, read_length, points, reads, aligned, covered, ags, min_breadth=None, group_of=None):
@@ -509,24 +497,21 @@ def curve_figures(names, length_aa, read_length, points, reads, aligned, covered
 def write_curve(path, args, table):
     """<outfile>.curve.tsv: the gene table's header lines, then one row per point"""
     cu = table["curve"]
-    det, grp = "genes_detected" in cu, "groups_with_reads" in cu
+    more = tuple(k for k in ("genes_detected", "groups_with_reads") if k in cu)
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
-        out.write("\t".join(CURVE_COLUMNS + (("genes_detected",) if det else ()) + (("groups_with_reads",) if grp else ())) + "\n")
-        for k, n_k in enumerate(cu["points"]):
-            line = "%d\t%s\t%s\t%d\t%d" % (n_k, _na(cu["ags"][k]), _na(cu["genome_equivalents_sampled"][k]), cu["reads_assigned"][k], cu["genes_with_reads"][k])
-            out.write(line + ("\t%d" % cu["genes_detected"][k] if det else "") + ("\t%d" % cu["groups_with_reads"][k] if grp else "") + "\n")
+        _write_rows(out, list(zip(CURVE_COLUMNS + more, "dnndddd")),
+                    [cu[k] for k in ("points", "ags", "genome_equivalents_sampled", "reads_assigned", "genes_with_reads") + more])
 
 
 def write_curve_genes(path, table):
     """--curve-genes: gene, reads_1 .. reads_K and with coverage covered_aa_1 .. covered_aa_K - genes in FASTA order"""
     cu = table["curve"]
-    K, cov = len(cu["points"]), cu.get("covered_aa")
+    mats = [("reads", cu["reads"])] + ([("covered_aa", cu["covered_aa"])] if cu.get("covered_aa") is not None else [])
     with open(path, "w") as out:
         out.write("# curve_points:\t%s\n" % "\t".join(str(n) for n in cu["points"]))
-        out.write("\t".join(["gene"] + ["reads_%d" % (k + 1) for k in range(K)] + (["covered_aa_%d" % (k + 1) for k in range(K)] if cov is not None else [])) + "\n")
-        for g, nm in enumerate(table["gene"]):
-            out.write("\t".join([nm] + [str(int(cu["reads"][k, g])) for k in range(K)] + ([str(int(cov[k, g])) for k in range(K)] if cov is not None else [])) + "\n")
+        _write_rows(out, [("gene", "s")] + [("%s_%d" % (what, k + 1), "d") for what, m in mats for k in range(len(m))],
+                    [table["gene"]] + [at_k for _, m in mats for at_k in m])
 
 
 def read_table(path):
@@ -542,12 +527,33 @@ def read_table(path):
     return header, rows[1:]
 
 
-PIPELINE_KEYS = ("seqfiles", "nreads", "read_length", "min_quality", "mean_quality", "filter_dups", "max_unknown", "threads", "device", "model_dir", "verbose")
-
-
 def _pipeline_args(args):
     # (nreads None is run_pipeline's "no cap" and is handed on; any other key that is None is left to impute_missing_args)
     return {k: (list(args[k]) if k == "seqfiles" else args[k]) for k in PIPELINE_KEYS if k in args and (args[k] is not None or k == "nreads")}
+
+
+def _check_int(args, key, lo, hi, span):
+    """args[key] becomes an int; refused where it is none (a bool is none) or lies outside lo .. hi"""
+    v = args[key]
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise AbundanceError("--%s %s is not an integer from %s" % (key.replace("_", "-"), v, span))
+    args[key] = int(v)
+
+
+def _check_switch(args, key):
+    if not isinstance(args[key], (bool, int)) or args[key] not in (0, 1):
+        raise AbundanceError("%s %r is not a switch: True or False" % (key, args[key]))
+    args[key] = bool(args[key])
+
+
+def _check_own_path(args, key, others):
+    """refused: args[key] is the path of another file of the run - of <outfile> + a suffix (the groups table only with groups) or of --depth-out"""
+    what = {"": "the gene table itself", ".curve.tsv": "the curve table (<outfile>.curve.tsv)", ".groups.tsv": "the groups table (<outfile>.groups.tsv)",
+            "depth_out": "the depth file (--depth-out)"}
+    for o in others:
+        other = args["depth_out"] if o == "depth_out" else args["outfile"] + o if args.get("outfile") and (o != ".groups.tsv" or args["groups"]) else None
+        if other and os.path.abspath(args[key]) == os.path.abspath(other):
+            raise AbundanceError("--%s %s is the path of %s: two files" % (key.replace("_", "-"), args[key], what[o]))
 
 
 def check_request(args):
@@ -569,36 +575,21 @@ def check_request(args):
             raise AbundanceError("--mixed-lengths%s with --bootstrap %s needs --ags or --ags-report: the default AGS is run_pipeline's, which does not bootstrap "
                                  "an estimate of mixed lengths" % (ml, args["bootstrap"]))
     if args["curve"] is not None:
-        K = args["curve"]
-        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= MAX_CURVE:
-            raise AbundanceError("--curve %s is not an integer from 1 to %d" % (K, MAX_CURVE))
-        args["curve"] = int(K)
+        _check_int(args, "curve", 1, MAX_CURVE, "1 to %d" % MAX_CURVE)
     if args["bootstrap"] is not None:
-        B = args["bootstrap"]
-        if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or not 1 <= int(B) <= MAX_BOOT:
-            raise AbundanceError("--bootstrap %s is not an integer from 1 to %d" % (B, MAX_BOOT))
-        args["bootstrap"] = int(B)
+        _check_int(args, "bootstrap", 1, MAX_BOOT, "1 to %d" % MAX_BOOT)
         if args["curve"] is not None:
             raise AbundanceError("--bootstrap %d cannot be combined with --curve %d: the curve's points are not bootstrapped" % (args["bootstrap"], args["curve"]))
     if args["bootstrap_seed"] is not None:
-        S = args["bootstrap_seed"]
         if args["bootstrap"] is None:
-            raise AbundanceError("--bootstrap-seed %s needs --bootstrap B: it seeds the replicates" % (S,))
-        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 0 <= int(S) < 1 << 64:
-            raise AbundanceError("--bootstrap-seed %s is not an integer from 0 to 2^64 - 1" % (S,))
-        args["bootstrap_seed"] = int(S)
+            raise AbundanceError("--bootstrap-seed %s needs --bootstrap B: it seeds the replicates" % (args["bootstrap_seed"],))
+        _check_int(args, "bootstrap_seed", 0, (1 << 64) - 1, "0 to 2^64 - 1")
     if args["curve_genes"] is not None:
         if not args["curve_genes"]:
             raise AbundanceError("--curve-genes %r is an empty path" % (args["curve_genes"],))
         if args["curve"] is None:
             raise AbundanceError("--curve-genes %s needs --curve K: it writes the curve's per-gene matrix" % (args["curve_genes"],))
-        where = os.path.abspath(args["curve_genes"])
-        others = [(args.get("outfile"), "the gene table itself"), (args["outfile"] + ".curve.tsv" if args.get("outfile") else None, "the curve table (<outfile>.curve.tsv)"),
-                  (args["outfile"] + ".groups.tsv" if args.get("outfile") and args["groups"] else None, "the groups table (<outfile>.groups.tsv)"),
-                  (args["depth_out"] or None, "the depth file (--depth-out)")]
-        for other, what in others:
-            if other and where == os.path.abspath(other):
-                raise AbundanceError("--curve-genes %s is the path of %s: two files" % (args["curve_genes"], what))
+        _check_own_path(args, "curve_genes", ("", ".curve.tsv", ".groups.tsv", "depth_out"))
     if args["min_breadth"] is not None:
         f = args["min_breadth"]
         try:
@@ -611,14 +602,8 @@ def check_request(args):
     if args["depth_out"] is not None:
         if not args["depth_out"]:
             raise AbundanceError("--depth-out %r is an empty path" % (args["depth_out"],))
-        where = os.path.abspath(args["depth_out"])
-        if args.get("outfile") and where == os.path.abspath(args["outfile"]):
-            raise AbundanceError("--depth-out %s is the path of the gene table itself: two files" % (args["depth_out"],))
-        if args.get("outfile") and args["groups"] and where == os.path.abspath(args["outfile"] + ".groups.tsv"):
-            raise AbundanceError("--depth-out %s is the path of the groups table (<outfile>.groups.tsv): two files" % (args["depth_out"],))
-    if not isinstance(args["ties"], (bool, int)) or args["ties"] not in (0, 1):
-        raise AbundanceError("ties %r is not a switch: True or False" % (args["ties"],))
-    args["ties"] = bool(args["ties"])
+        _check_own_path(args, "depth_out", ("", ".groups.tsv"))
+    _check_switch(args, "ties")
     args["coverage"] = bool(args["coverage"]) or args["min_breadth"] is not None or args["depth_out"] is not None
     if args["ags"] is not None and args["ags_report"] is not None:
         raise AbundanceError("--ags %s and --ags-report %s cannot be combined: one AGS" % (args["ags"], args["ags_report"]))
@@ -630,13 +615,8 @@ def check_request(args):
     if math.isnan(float(args["min_bits"])):
         raise AbundanceError("--min-bits %s is not a number" % (args["min_bits"],))
     args["min_ident"], args["min_aln"], args["min_bits"] = int(mi), int(args["min_aln"]), float(args["min_bits"])
-    ags = source = None
-    if args["ags"] is not None:
-        source = "--ags"
-        ags = check_ags(args["ags"], source)
-    if not isinstance(args["long_genes"], (bool, int)) or args["long_genes"] not in (0, 1):
-        raise AbundanceError("long_genes %r is not a switch: True or False" % (args["long_genes"],))
-    args["long_genes"] = bool(args["long_genes"])
+    ags, source = (check_ags(args["ags"], "--ags"), "--ags") if args["ags"] is not None else (None, None)
+    _check_switch(args, "long_genes")
     names, seqs = read_genes(args["genes"], args["long_genes"])
     args["gene_fold"] = split_genes(names, seqs) if args["long_genes"] else None      # (refused here: before any GPU work)
     group_of = read_groups(args["groups"], names) if args["groups"] else None
@@ -648,22 +628,9 @@ def check_request(args):
     return names, seqs, group_of, ags, source
 
 
-def run_abundance(args):
-    """args: run_pipeline's keys (seqfiles, nreads, read_length, min_quality, mean_quality, filter_dups, max_unknown, device, model_dir,
-    verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and - all off by default - mixed_lengths (True or a list of class lengths: every read
-    at the largest length class it reaches, the denominator from the bases so sampled; not combined with read_length and curve, with bootstrap only under a given AGS), coverage, min_breadth
-    (implies coverage), depth_out (a path; implies coverage), ties (the genes that tie for a read's best hit: unique, candidate and
-    shared reads beside the counts; sets args['ties_ms']), curve (K, 1 .. 64: table['curve'], the table's figures at K prefixes of the sample
-    - the sampler then runs to its end before the search starts; sets args['curve_ms']; writes <outfile>.curve.tsv) and curve_genes (a path:
-    the curve's per-gene matrix), bootstrap (B, 1 .. 4096: the columns rpkg_boot_se, rpkg_ci95_low, rpkg_ci95_high from B Poisson-bootstrap
-    replicates of the sampled reads under bootstrap_seed (default 0) - with run_pipeline's AGS every replicate is divided by its own
-    genome equivalents, with a given AGS by the fixed ones; sets args['gene_bootstrap_ms']; not combined with curve), long_genes (genes of up to
-    65,535 residues: split_genes cuts the long ones into overlapping segments, the engine folds every row back onto its gene, every table is the genes';
-    table['long_genes'] = {genes_split, segments, edge_rows}; sets args['gene_fold_ms']).  Writes args['outfile'] (and
-    <outfile>.groups.tsv with groups) when it is set; returns (table, args) - table: the columns as arrays (gene, length_aa, reads,
-    aligned_aa, rpkg), the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
-    names, seqs, group_of, ags, source = check_request(args)
-    microbe_census.check_input(args)
+def resolve_sample(args, ags, source):
+    """Stage 1 - the record `sample`: ags and source (given, or run_pipeline's estimate on the same files under the same options), pargs (its
+    args - of that run, or of the imputation it makes, without a search), classes (of mixed_lengths, else None), L (the trimmed length or "mixed")"""
     mixed, classes = microbe_census.mixed_lengths_on(args), None
     if mixed:                   # neither a list nor a report's line: the classes run_pipeline would detect on the same file
         classes = args["length_classes"]
@@ -673,17 +640,15 @@ def run_abundance(args):
             except SystemExit as e:
                 raise AbundanceError(str(e))
         args["length_classes"] = classes = [int(x) for x in classes]
-    if ags is None:             # the estimate of the same sample: run_pipeline on the marker engine, same files, same options
+    if ags is None:
         more = {"curve": args["curve"]} if args["curve"] else {"bootstrap": args["bootstrap"], "bootstrap_seed": args["bootstrap_seed"] or 0} if args["bootstrap"] else {}
-        if mixed:               # (check_request has refused the curve and the bootstrap of a default AGS)
-            more = {"mixed_lengths": list(classes)}
+        more = {"mixed_lengths": list(classes)} if mixed else more       # (check_request has refused the curve and the bootstrap of a default AGS)
         est = microbe_census.run_pipeline(dict(_pipeline_args(args), **more) if more else _pipeline_args(args))
         if est is None:
             raise AbundanceError("run_pipeline gave no AGS estimate for %s" % ",".join(args["seqfiles"]))
-        ags, pargs = est
         source = "run_pipeline"
-        ags = check_ags(ags, source)
-    else:                       # the same imputation run_pipeline makes (file type, quality offset, read length), without a search
+        ags, pargs = check_ags(est[0], source), est[1]
+    else:                       # the same imputation run_pipeline makes (file type, quality offset, read length)
         pargs = _pipeline_args(args)
         microbe_census._cap_host_threads(pargs.get("threads"))
         if mixed:               # (as run_pipeline: read_length becomes "mixed" and is not detected)
@@ -691,98 +656,113 @@ def run_abundance(args):
             microbe_census.check_mixed_lengths(pargs)
         microbe_census.impute_missing_args(pargs)
         microbe_census.check_arguments(pargs)
-    L = "mixed" if mixed else int(pargs["read_length"])
+    return {"ags": ags, "source": source, "pargs": pargs, "classes": classes, "L": "mixed" if mixed else int(pargs["read_length"])}
+
+
+def _set_switches(eng, args, sample, names, group_of):
+    """fold, run or run_classes, abundance, coverage, ties, abundance_classes; returns (gids, gnames): the groups the device got, or None twice"""
+    fold, classes = args["gene_fold"], sample["classes"]
+    if fold is not None:        # long_genes: the engine is open on the segments, every counter is in gene space
+        eng.set_gene_fold(fold["seg_gene"], fold["seg_off"], fold["gene_len"])
+    if classes is not None:     # (the default parameters: classification does not enter the counts)
+        eng.set_run_classes(classes)
+    else:
+        eng.set_run(sample["L"])
+    eng.set_abundance(True, min_ident=args["min_ident"], min_aln=args["min_aln"], min_bits=args["min_bits"])
+    if args["coverage"]:
+        eng.set_coverage(True)
+    gids, gnames = group_ids(names, group_of) if args["ties"] and group_of is not None else (None, None)
+    if args["ties"]:
+        eng.set_ties(True, gids, len(gnames or ()))
+    if classes is not None:
+        eng.set_abundance_classes(True)
+    return gids, gnames
+
+
+def _search_once(eng, rd, args, sample):
+    """The one search of a run - no m8 row reaches the host; returns (cu, points): Engine.curve() and the curve's points, or None twice.
+    The bootstrap's list of read ids is sized before the search: by -n, the sampler sampling beside the search, or - no cap - by the reads the
+    sampler takes; the curve's points depend on that number too: there it runs to its end first, and no read taken means no search."""
+    B, cap = args["bootstrap"], sample["pargs"]["nreads"]
+    if B and cap is not None:
+        eng.set_gene_bootstrap(int(cap))
+    if not args["curve"] and not (B and cap is None):
+        eng.search_files(rd, keep_rows=False)
+        return None, None
+    n = rd.run()
+    if not n:
+        return None, None
+    points = microbe_census.curve_points(n, args["curve"]) if args["curve"] else None
+    if points is None:
+        eng.set_gene_bootstrap(n)
+    else:
+        eng.set_curve(points)
+    (eng.search if sample["classes"] is None else eng.search_classes)(rd.reads(n), keep_rows=False)
+    return (None, None) if points is None else (eng.curve(covered=bool(args["coverage"])), points)
+
+
+def _replicate_scale(args, sample, ab, ac):
+    """scale[b] = 1 / the genome equivalents of replicate b: run_pipeline's replicates under its AGS, B times the sample's under a given one"""
+    B, pargs = args["bootstrap"], sample["pargs"]
+    if sample["source"] == "run_pipeline":
+        if len(pargs.get("ags_boot_values") or []) != B or len(pargs.get("ags_boot_reads") or []) != B:
+            raise AbundanceError("run_pipeline gave %d replicate AGS values for --bootstrap %d" % (len(pargs.get("ags_boot_values") or []), B))
+        return boot_scale(pargs["ags_boot_values"], pargs["ags_boot_reads"], sample["L"])
+    return np.full(B, 1.0 / (sampled_bases(ac["rows"], sample["classes"]) / sample["ags"] if ac is not None else genome_equivalents(ab["searched"], sample["L"], sample["ags"])))
+
+
+def device_pass(args, sample, names, seqs, group_of):
+    """Stage 2 - the record `counts`, from the only place that opens a reader or an engine: what the device counted as numpy arrays and ints - ab,
+    ac, cov, depth, ti, tcov, cu and points, gb and scale, fold_stats (None: not asked for), sampled, gids and gnames, search_ms and the *_ms"""
+    pargs, classes, fold = sample["pargs"], sample["classes"], args["gene_fold"]
     sampler = (pargs["nreads"], pargs["file_type"] == "fastq", pargs.get("quality_offset") or 0, pargs["min_quality"], pargs["mean_quality"], pargs["max_unknown"], pargs["filter_dups"])
-    rd = _native.Reader.with_classes(pargs["seqfiles"], classes, *sampler) if mixed else _native.Reader(pargs["seqfiles"], L, *sampler)
+    rd = _native.Reader.with_classes(pargs["seqfiles"], classes, *sampler) if classes is not None else _native.Reader(pargs["seqfiles"], sample["L"], *sampler)
     eng = None
-    try:
-        fold = args["gene_fold"]
-        if fold is None:
-            eng = _native.Engine(device=int(args.get("device") or 0), names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
-        else:                   # long_genes: the engine on the segments with the genes' statistics, every table below in gene space
-            eng = _native.Engine(device=int(args.get("device") or 0), names=fold["seg_names"], seqs=fold["seg_seqs"], marker_family=[0] * len(fold["seg_names"]), nfam=1, stats=fold["stats"])
-            eng.set_gene_fold(fold["seg_gene"], fold["seg_off"], fold["gene_len"])
-        if mixed:               # (the default parameters: classification does not enter the counts)
-            eng.set_run_classes(classes)
-        else:
-            eng.set_run(L)
-        eng.set_abundance(True, min_ident=args["min_ident"], min_aln=args["min_aln"], min_bits=args["min_bits"])
-        if args["coverage"]:
-            eng.set_coverage(True)
-        gids = None
-        if args["ties"]:
-            if group_of is not None:
-                gids, gnames = group_ids(names, group_of)
-                eng.set_ties(True, gids, len(gnames))
-            else:
-                eng.set_ties(True)
-        if mixed:
-            eng.set_abundance_classes(True)
-        cu = points = gb = scale = ac = None
-        B, seed = args["bootstrap"], args["bootstrap_seed"] or 0
-        if B and pargs["nreads"] is not None:       # ids lie below -n: the list is sized before the sampler starts, and it samples beside the search
-            eng.set_gene_bootstrap(int(pargs["nreads"]))
+    try:                        # (long_genes: the engine on the segments, with the genes' statistics)
+        db = {"names": names, "seqs": seqs} if fold is None else {"names": fold["seg_names"], "seqs": fold["seg_seqs"], "stats": fold["stats"]}
+        eng = _native.Engine(device=int(args.get("device") or 0), marker_family=[0] * len(db["names"]), nfam=1, **db)
+        c = dict.fromkeys(("ac", "gb", "scale"))
+        c["gids"], c["gnames"] = _set_switches(eng, args, sample, names, group_of)
         try:
-            if B and pargs["nreads"] is None:       # no cap: the list's size is the number of reads the sampler takes - it runs to its end first
-                n = rd.run()
-                if n:
-                    eng.set_gene_bootstrap(n)
-                    eng.lib.mc_set_keep_rows(eng.h, 0)
-                    try:
-                        if mixed:
-                            eng.search_classes(rd.reads(n))
-                        else:
-                            eng.search(rd.reads(n))
-                    finally:
-                        eng.lib.mc_set_keep_rows(eng.h, 1)
-            elif args["curve"]:       # the points depend on how many reads the sampler takes: it runs to its end first, then one search
-                n = rd.run()
-                if n:               # (no read taken: nothing is searched, and the run ends below with "No reads remaining after filtering" as without the switch)
-                    points = microbe_census.curve_points(n, args["curve"])
-                    eng.set_curve(points)
-                    eng.lib.mc_set_keep_rows(eng.h, 0)
-                    try:
-                        eng.search(rd.reads(n))
-                    finally:
-                        eng.lib.mc_set_keep_rows(eng.h, 1)
-                    cu = eng.curve(covered=bool(args["coverage"]))
-                    args["curve_ms"] = eng.curve_ms()
-            else:
-                eng.search_files(rd, keep_rows=False)
+            c["cu"], c["points"] = _search_once(eng, rd, args, sample)
         except _native.ReferenceError_ as e:
             raise AbundanceError(str(e))
-        ab = eng.abundance()
-        if mixed:
-            ac = eng.abundance_classes()
-            args["abundance_classes_ms"] = eng.abundance_classes_ms()
-        if B and ab["searched"]:
-            if source == "run_pipeline":
-                if len(pargs.get("ags_boot_values") or []) != B or len(pargs.get("ags_boot_reads") or []) != B:
-                    raise AbundanceError("run_pipeline gave %d replicate AGS values for --bootstrap %d" % (len(pargs.get("ags_boot_values") or []), B))
-                scale = boot_scale(pargs["ags_boot_values"], pargs["ags_boot_reads"], L)
-            else:
-                scale = np.full(B, 1.0 / (sampled_bases(ac["rows"], classes) / ags if mixed else genome_equivalents(ab["searched"], L, ags)))
+        c["ab"] = eng.abundance()
+        if classes is not None:
+            c["ac"], c["abundance_classes_ms"] = eng.abundance_classes(), eng.abundance_classes_ms()
+        if args["bootstrap"] and c["ab"]["searched"]:
+            c["scale"] = _replicate_scale(args, sample, c["ab"], c["ac"])
             try:
-                gb = eng.gene_bootstrap(B, seed, scale)
+                c["gb"] = eng.gene_bootstrap(args["bootstrap"], args["bootstrap_seed"] or 0, c["scale"])
             except RuntimeError as e:
                 raise AbundanceError(str(e))
-            args["gene_bootstrap_ms"] = eng.gene_bootstrap_ms()
-        cov = eng.coverage() if args["coverage"] else None
-        depth = eng.coverage_depth() if args["depth_out"] is not None else None
-        args["abundance_ms"], args["search_ms"] = eng.abundance_ms(), eng.stats()["ms_total"]
-        ti = eng.ties() if args["ties"] else None
-        tcov = eng.ties_coverage() if args["ties"] and args["coverage"] else None
+            c["gene_bootstrap_ms"] = eng.gene_bootstrap_ms()
+        c["cov"] = eng.coverage() if args["coverage"] else None
+        c["depth"] = eng.coverage_depth() if args["depth_out"] is not None else None
+        c["ti"] = eng.ties() if args["ties"] else None
+        c["tcov"] = eng.ties_coverage() if args["ties"] and args["coverage"] else None
+        c["fold_stats"] = eng.gene_fold_stats() if fold is not None else None
+        c["abundance_ms"], c["search_ms"] = eng.abundance_ms(), eng.stats()["ms_total"]
         if args["coverage"]:
-            args["coverage_ms"] = eng.coverage_ms()
+            c["coverage_ms"] = eng.coverage_ms()
         if args["ties"]:
-            args["ties_ms"] = eng.ties_ms()
-        fs = eng.gene_fold_stats() if fold is not None else None
-        st = rd.stats()
+            c["ties_ms"] = eng.ties_ms()
+        if c["cu"] is not None:
+            c["curve_ms"] = eng.curve_ms()
+        c["sampled"] = int(rd.stats()["sampled"])
     finally:
         rd.close()
         if eng is not None:
             eng.close()
-    sampled = int(st["sampled"])
+    return c
+
+
+def build_table(args, sample, counts, names, seqs, group_of):
+    """Stage 3 - the table from the two records, in numpy and Python alone (no engine, no reader, no file): the refusals that compare them,
+    every column, groups, curve and long_genes - and what the run leaves in args"""
+    ags, source, pargs, classes, L = (sample[k] for k in ("ags", "source", "pargs", "classes", "L"))
+    ab, ac, cov, ti, tcov, cu, gb, fs = (counts[k] for k in ("ab", "ac", "cov", "ti", "tcov", "cu", "gb", "fold_stats"))
+    mixed, sampled, est = classes is not None, counts["sampled"], source == "run_pipeline"
     if sampled == 0:
         raise AbundanceError("No reads remaining after filtering")
     if "sampled_reads" in pargs and int(pargs["sampled_reads"]) != sampled or ab["searched"] != sampled:
@@ -791,16 +771,14 @@ def run_abundance(args):
     if mixed:
         K = len(classes)
         class_reads, class_assigned = [int(x) for x in ac["rows"][:K]], [int(x) for x in ac["assigned"][:K]]
-        est = source == "run_pipeline"
         if sum(class_reads) != sampled or int(ac["rows"][K]) != 0 or est and (list(pargs.get("length_classes") or []) != classes or list(pargs.get("class_reads") or []) != class_reads):
             raise AbundanceError("the gene search saw %d reads (%d sampled): %s reads in the classes %s and %d below them, the AGS estimate %s in the classes %s"
                                  % (ab["searched"], sampled, class_reads, classes, int(ac["rows"][K]), pargs.get("class_reads") if est else "-", pargs.get("length_classes") if est else "-"))
         args["class_reads"] = class_reads
-    for k in ("file_type", "quality_offset", "read_length", "nreads", "min_quality", "mean_quality", "filter_dups", "max_unknown") + (
-            ("ags_boot_se", "ags_ci95", "ags_boot_replicates", "ags_boot_values", "ags_boot_reads") if gb is not None and source == "run_pipeline" else ()):
-        if k in pargs:
-            args[k] = pargs[k]
+    args.update((k, pargs[k]) for k in ("file_type", "quality_offset", "read_length", "nreads", "min_quality", "mean_quality", "filter_dups", "max_unknown") + (
+        ("ags_boot_se", "ags_ci95", "ags_boot_replicates", "ags_boot_values", "ags_boot_reads") if gb is not None and est else ()) if k in pargs)
     args["sampled_reads"] = sampled
+    args.update((k, v) for k, v in counts.items() if k.endswith("_ms"))
     length_aa = np.array([len(s) for s in seqs], np.int64)
     bases = sampled_bases(class_reads, classes) if mixed else None
     ge = bases / ags if mixed else genome_equivalents(sampled, L, ags)
@@ -809,17 +787,15 @@ def run_abundance(args):
     if mixed:
         table.update({"length_classes": list(classes), "class_reads": class_reads, "class_reads_assigned": class_assigned, "sampled_bases": bases})
     if fs is not None:
-        table["long_genes"] = {"genes_split": fold["genes_split"], "segments": len(fold["seg_names"]), "edge_rows": fs["edge_rows"]}
+        table["long_genes"] = {"genes_split": args["gene_fold"]["genes_split"], "segments": len(args["gene_fold"]["seg_names"]), "edge_rows": fs["edge_rows"]}
         args["gene_fold_ms"] = fs["ms"]
     if cov is not None:
         breadth, mean_depth = coverage_columns(length_aa, cov["covered"], cov["spanned"])
         table.update({"covered_aa": cov["covered"], "breadth": breadth, "mean_depth": mean_depth, "max_depth": cov["max_depth"], "spanned_aa": cov["spanned"]})
         if args["min_breadth"] is not None:
-            table["min_breadth"] = args["min_breadth"]
-            table["detected"] = detect(ab["reads"], cov["covered"], length_aa, args["min_breadth"])
-        if depth is not None:
-            table["depth"] = depth
-            write_depth(args["depth_out"], names, length_aa, depth)
+            table.update({"min_breadth": args["min_breadth"], "detected": detect(ab["reads"], cov["covered"], length_aa, args["min_breadth"])})
+        if counts["depth"] is not None:
+            table["depth"] = counts["depth"]
     if ti is not None:
         sh = shared_reads(ti["share"])
         table.update({"unique_reads": ti["unique"], "candidate_reads": ti["candidates"], "shared_reads": sh, "rpkg_shared": rpkg(sh, length_aa, ge), "share": ti["share"],
@@ -829,32 +805,56 @@ def run_abundance(args):
             if args["min_breadth"] is not None:
                 table["detected_any"] = detect(ti["candidates"], tcov["covered_any"], length_aa, args["min_breadth"])
         if group_of is not None:
-            table["reads_ambiguous_across_groups"] = ti["group_ambiguous"]
-            table["group_unique"] = ti["group_unique"]
-            table["groups_ties"] = group_ties_table(gids, len(gnames), ti["group_unique"], ti["share"], table["rpkg_shared"], table.get("detected_any"))
+            table.update({"reads_ambiguous_across_groups": ti["group_ambiguous"], "group_unique": ti["group_unique"], "groups_ties": group_ties_table(
+                counts["gids"], len(counts["gnames"]), ti["group_unique"], ti["share"], table["rpkg_shared"], table.get("detected_any"))})
     if gb is not None:
         se, lo, hi = boot_columns(gb["stats"], gb["used"], length_aa)
-        table.update({"rpkg_boot_se": se, "rpkg_ci95_low": lo, "rpkg_ci95_high": hi, "boot_used": gb["used"], "boot_stats": gb["stats"], "boot_scale": scale, "bootstrap": B,
-                      "bootstrap_seed": seed, "bootstrap_denominator": "replicate_ags" if source == "run_pipeline" else "fixed_ags"})
+        table.update({"rpkg_boot_se": se, "rpkg_ci95_low": lo, "rpkg_ci95_high": hi, "boot_used": gb["used"], "boot_stats": gb["stats"], "boot_scale": counts["scale"],
+                      "bootstrap": args["bootstrap"], "bootstrap_seed": args["bootstrap_seed"] or 0, "bootstrap_denominator": "replicate_ags" if est else "fixed_ags"})
     if group_of is not None:
         table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of, table.get("detected"))
     if cu is not None:
+        points = [int(n) for n in counts["points"]]
         if cu["beyond"] != 0:
             raise AbundanceError("the curve: %d assigned reads lie behind the last point %d (%d sampled)" % (cu["beyond"], points[-1], sampled))
-        if source == "run_pipeline":
+        ags_k = [ags] * len(points)
+        if est:
             est_curve = pargs.get("ags_curve") or []
             if [p["reads"] for p in est_curve] != points:
                 raise AbundanceError("the AGS curve's points %s are not the gene curve's %s" % ([p["reads"] for p in est_curve], points))
             ags_k = [p["ags"] for p in est_curve]
-        else:
-            ags_k = [ags] * len(points)
         table["curve"] = curve_figures(names, length_aa, L, points, cu["reads"], cu["aligned"], cu.get("covered"), ags_k, args["min_breadth"], group_of)
+    return table
+
+
+def write_outputs(args, table):
+    """Stage 4 - the files: the depth file; under outfile the gene, groups and curve tables; the curve's per-gene matrix"""
+    if table.get("depth") is not None:
+        write_depth(args["depth_out"], table["gene"], table["length_aa"], table["depth"])
     if args.get("outfile"):
         write_table(args["outfile"], args, table)
-        if group_of is not None:
+        if "groups" in table:
             write_groups(args["outfile"] + ".groups.tsv", args, table)
-        if cu is not None:
+        if "curve" in table:
             write_curve(args["outfile"] + ".curve.tsv", args, table)
-    if cu is not None and args["curve_genes"] is not None:
+    if "curve" in table and args["curve_genes"] is not None:
         write_curve_genes(args["curve_genes"], table)
+
+
+def run_abundance(args):
+    """args: run_pipeline's keys (seqfiles, nreads, read_length, min_quality, mean_quality, filter_dups, max_unknown, device, model_dir,
+    verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and the switches the module's docstring describes,
+    all off by default: coverage, min_breadth and depth_out (a path; both imply coverage), ties, curve (K, 1 .. 64: table['curve']; writes
+    <outfile>.curve.tsv) with curve_genes (a path: the curve's per-gene matrix), bootstrap (B, 1 .. 4096) with bootstrap_seed (default 0; not
+    combined with curve), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
+    given AGS), long_genes (genes of up to 65,535 residues; table['long_genes'] = {genes_split, segments, edge_rows}).  Four stages with two
+    records between them - DESIGN.md 13, "How a run is laid out on the host".  Writes args['outfile'] (and <outfile>.groups.tsv with groups)
+    when it is set; leaves in args the sampler's options as imputed, sampled_reads, search_ms and the *_ms of every switch that ran; returns
+    (table, args) - table: the columns as arrays, the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""
+    names, seqs, group_of, ags, source = check_request(args)
+    microbe_census.check_input(args)
+    sample = resolve_sample(args, ags, source)
+    counts = device_pass(args, sample, names, seqs, group_of)
+    table = build_table(args, sample, counts, names, seqs, group_of)
+    write_outputs(args, table)
     return table, args

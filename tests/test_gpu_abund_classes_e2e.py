@@ -8,32 +8,25 @@ import os
 import numpy as np
 import pytest
 
-from microbecensus_amd import _native, abundance, microbe_census as mc, synth
+from microbecensus_amd import _native, abundance, microbe_census as mc
 
+import abundance_table_cases as TC
 import classes_restated as cr
 import geneboot_restated as GR
 
 pytestmark = pytest.mark.gpu
 
-CLASSES = [100, 150]
+CLASSES = TC.CLASSES            # [100, 150]
 GENES = os.path.join(_native.DATA_DIR, "markers.faa.gz")
 
 
-def _write_fasta(path, seqs):
-    with open(path, "w") as f:
-        for i, s in enumerate(seqs):
-            f.write(">r%d\n%s\n" % (i, s.decode()))
-    return str(path)
+_write_fasta = TC.write_fasta
 
 
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
     """the mixed FASTA, one FASTA per class (the reads of that class, uncut), and the reads of at least 100 bp"""
-    _, seqs = _native.load_markers()
-    genome = synth.build_genomes(seqs, total_bp=1_500_000, seed=31, marker_gene_fraction=0.3)
-    full = synth.sample_reads(genome, 30_000, 320, seed=32)
-    lens = np.random.default_rng(33).integers(40, 321, size=len(full))
-    reads = [bytes(full[i, :lens[i]]) for i in range(len(full))]
+    reads, lens = TC.mixed_reads()      # (the recipe: shared with the `mixed` case of the recorded tables)
     cls = cr.class_of(lens, CLASSES)
     d = tmp_path_factory.mktemp("abund_classes_e2e")
     return {"dir": d, "mixed": _write_fasta(d / "mixed.fa", reads), "cls": cls,

@@ -146,6 +146,30 @@ def test_counters_do_not_depend_on_batches_ranges_or_entry_point(engine, reads, 
         engine.abundance()
 
 
+def test_search_without_rows_returns_nothing_and_counts_what_search_files_counts(engine, reads, tmp_path):
+    """Engine.search(reads, keep_rows=False): nothing comes back and no row reaches the host, the counters are those of
+    search_files(keep_rows=False) on the same reads, and the next plain search returns its rows again"""
+    from microbecensus_amd import _native
+    engine.set_abundance(True, **CUTS[2])
+    try:
+        assert engine.search(reads, keep_rows=False) is None and len(engine.rows()) == 0 and engine.stats()["rows"] > 0
+        got = engine.abundance()
+        engine.abundance_reset()
+        fa = tmp_path / "reads.fa"
+        fa.write_bytes(gzip.open(os.path.join(GOLD, CASE + ".reads.fa.gz"), "rb").read())
+        rd = _native.Reader([str(fa)], 100, 10_000_000, False, 0, -5, -5, 100, False)
+        try:
+            engine.search_files(rd, keep_rows=False)
+        finally:
+            rd.close()
+        want = engine.abundance()
+        assert got["searched"] == want["searched"] == len(reads) and want["assigned"] > 0 and _same(got, want)
+        rows, best = engine.search(reads)
+        assert len(rows) == engine.stats()["rows"] > 0 and len(best) > 0 and len(engine.rows()) == len(rows)
+    finally:
+        engine.set_abundance(False)
+
+
 def test_a_range_that_overflows_its_pools_counts_once(monkeypatch):
     """The marker-dense library (abund_inputs.dense_runs says why 24,000 reads), and the test asserts that it takes the halving path.  The
     counters must be those of 5,000-read batches (which fit: no split), and the restatement's on that run's own host rows - the one place

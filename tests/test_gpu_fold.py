@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import abund_inputs as AI
+import abundance_table_cases as TC
 import abundance_restated as R
 import coverage_restated as CV
 import fold_restated as FR
@@ -38,8 +39,7 @@ def _run(eng, reads, rows=False):
 
 @pytest.fixture(scope="module")
 def runs():
-    names, seqs = _native.load_markers()
-    names, seqs = names[::2], seqs[::2]
+    names, seqs = TC.long_gene_markers()
     reads = AI.example_reads()
     sp = abundance.split_genes(names, seqs, seg_len=SEG, overlap=FR.V)
     eng = _native.Engine(device=0, names=names, seqs=seqs, marker_family=[0] * len(names), nfam=1)
@@ -116,22 +116,14 @@ def test_the_split_runs_tables_are_the_restatements_of_its_folded_rows(runs):
     assert not missing and len(full) <= 0.01 * spl["ab"]["assigned"]
 
 
-def _fasta(path, names, seqs):
-    with open(path, "w") as f:
-        for nm, sq in zip(names, seqs):
-            f.write(">%s\n%s\n" % (nm, sq))
-    return str(path)
-
-
 def test_three_markers_joined_are_counted_as_one_long_gene(runs, tmp_path):
     names, seqs, un = runs["names"], runs["seqs"], runs["un"]
     # three markers of about 1,000 residues with the most unique reads
-    order = [g for g in np.argsort(-un["ti"]["unique"]) if 800 <= len(seqs[g]) <= 1183][:3]
+    order = TC.pick_joined(seqs, un["ti"]["unique"])
     assert len(order) == 3 and all(un["ti"]["unique"][g] > 0 for g in order)
-    joined = "".join(seqs[g] for g in order)
+    assert [names[g] for g in order] == TC.recorded()["long_joined"]         # (the `long` case of the recorded tables joins the same three)
+    genes, joined, keep = TC.write_joined_genes(tmp_path / "genes.faa", names, seqs, order)
     assert 2400 <= len(joined) <= 3549
-    keep = [g for g in range(len(names)) if g not in order]
-    genes = _fasta(tmp_path / "genes.faa", ["joined"] + [names[g] for g in keep], [joined] + [seqs[g] for g in keep])
     fq = os.path.join(AI.GOLD, "inputs", "example.fq.gz")
     base = {"seqfiles": [fq], "genes": genes, "nreads": 10000, "read_length": 100, "device": 0, "ags": 3.0e6, "ties": True, "coverage": True, "depth_out": str(tmp_path / "depth.tsv")}
     with pytest.raises(abundance.AbundanceError, match="Gene joined is %d residues long: longer than 2047" % len(joined)):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import abund_inputs as I
+import abundance_table_cases as TC
 import abundance_restated as R
 import coverage_restated as V
 import ties_restated as T
@@ -50,7 +51,7 @@ def golden():
     from microbecensus_amd import _native, abundance
     names, seqs = _native.load_markers()
     lengths = [len(s) for s in seqs]
-    gmap = {n: n.split("_")[0] for n in names[:4000]}
+    gmap = TC.group_map(names)
     group_of, gnames = abundance.group_ids(names, gmap)
     rows = V.rows_from_m8(os.path.join(GOLD, CASE + ".m8.gz"), names)
     return {"rows": rows, "lengths": lengths, "group_of": group_of, "ngroups": len(gnames), "gnames": gnames, "gmap": gmap, "names": names,
