@@ -612,6 +612,24 @@ int mc_gene_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scal
 /* Milliseconds the gene bootstrap's kernels took since the last reset (HIP events): one kernel per completed range plus three per
  * mc_gene_bootstrap. */
 float mc_gene_bootstrap_ms(const mc_handle *h);
+/* The bootstrap of a table of GROUPS of genes (csrc/mc_groupboot.h states the rule) on the same replicates: group_of[s] in
+ * 0 .. ngroups - 1 is the group of gene s, gene_kb[s] a finite double > 0, the gene's length in kb.  A group's replicate count is the sum
+ * of its members' replicate counts; its replicate value, of a used b, is the sum over its members, in ascending gene index, of
+ * (double)c[b][s] * scale[b] / gene_kb[s].  counts (or NULL): the group replicate counts at [G * B + b]; stats: per group the six
+ * doubles mc_gene_bootstrap gives per gene, of the group's used replicate values (a group without reads: zeros; no used replicate:
+ * NaN).  The sums are added in the order the header writes down: the same bits on every run.  The replicate counts of the genes stay on
+ * the device: they are those a preceding mc_gene_bootstrap left there when that call had the same B and seed and no range has
+ * completed since, and made here otherwise - either way the same bits.  dropped: as mc_gene_bootstrap's.
+ * Refused, with a message naming the value: the gene bootstrap off, B outside 1 .. 4096, a NULL array, ngroups outside 1 .. the genes,
+ * a group_of entry outside 0 .. ngroups - 1, a gene_kb entry that is not finite and > 0, a range in flight, dropped != 0. */
+int mc_group_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale /* [B] */,
+                       const int32_t *group_of /* [nseq] */, int32_t ngroups, const double *gene_kb /* [nseq] */,
+                       int64_t *counts /* [ngroups * B] or NULL */, double *stats /* [ngroups * 6] */, int64_t *dropped);
+/* Milliseconds the kernels of the mc_group_bootstrap calls took since the last reset (HIP events): two per call, and three more where
+ * the call had to make the genes' replicate counts. */
+float mc_group_bootstrap_ms(const mc_handle *h);
+/* Of those, the milliseconds of k_groupboot_values and of k_groupboot_summary (either pointer may be NULL). */
+void mc_group_bootstrap_kernels_ms(const mc_handle *h, float *values_ms, float *summary_ms);
 
 /* ---- the counts on class runs: gene abundances from reads of mixed lengths -------------------------------------------------------
  * README "Reads of mixed lengths": a class run searches every read at the largest length class it reaches.  With this switch on the

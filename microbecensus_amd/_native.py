@@ -244,6 +244,11 @@ def load_library():
     lib.mc_gene_bootstrap.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.mc_gene_bootstrap_ms.restype = C.c_float
     lib.mc_gene_bootstrap_ms.argtypes = [C.c_void_p]
+    lib.mc_group_bootstrap.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.mc_group_bootstrap_ms.restype = C.c_float
+    lib.mc_group_bootstrap_ms.argtypes = [C.c_void_p]
+    lib.mc_group_bootstrap_kernels_ms.restype = None
+    lib.mc_group_bootstrap_kernels_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.mc_set_abundance_classes.argtypes = [C.c_void_p, C.c_int]
     lib.mc_abundance_classes_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mc_abundance_classes_ms.restype = C.c_float
@@ -276,7 +281,7 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms",
                     "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms",
                     "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms",
-                    "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms",
+                    "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms", "mc_group_bootstrap", "mc_group_bootstrap_ms", "mc_group_bootstrap_kernels_ms",
                     "mc_set_abundance_classes", "mc_abundance_classes_read", "mc_abundance_classes_ms", "mc_open_stats", "mc_set_gene_fold", "mc_gene_fold_stats",
                     "mc_abundance_count", "mc_abundance_residues", "mc_debug_live"]
 
@@ -1095,6 +1100,41 @@ class Engine:
                                                out["stats"].ctypes.data_as(C.c_void_p), C.byref(dropped)), "mc_gene_bootstrap")
         out["dropped"] = int(dropped.value)
         return out
+
+    def group_bootstrap(self, B, seed, scale, group_of, ngroups, gene_kb, counts=False):
+        """The same B replicates summed over groups of genes (mc_group_bootstrap; csrc/mc_groupboot.h states the rule): group_of: every
+        gene's group in 0 .. ngroups - 1, gene_kb: every gene's length in kb, finite and > 0.  {"stats": float64[ngroups, 6] - sum, m2
+        and the four order statistics of the group's used replicate values, the sum over its members in ascending gene index of
+        (double)c[b][s] * scale[b] / gene_kb[s] -, "used": m, "dropped": 0} and with counts=True "counts": int64[ngroups, B], the
+        members' replicate counts added.  The genes' replicate counts never leave the device.  Raises as gene_bootstrap does, and on a
+        map or a gene_kb the library refuses (the message names the value)."""
+        B, n, ngroups = int(B), self.abundance_count(), int(ngroups)
+        sc = np.ascontiguousarray(scale, dtype=np.float64)
+        if sc.shape != (max(B, 0),):
+            raise ValueError("scale holds %d values, B is %d" % (sc.size, B))
+        gof, kb = np.ascontiguousarray(group_of, dtype=np.int32), np.ascontiguousarray(gene_kb, dtype=np.float64)
+        if gof.shape != (n,) or kb.shape != (n,):
+            raise ValueError("group_of holds %d values and gene_kb %d, the genes are %d" % (gof.size, kb.size, n))
+        out = {"stats": np.zeros((max(ngroups, 0), 6), np.float64), "used": int((np.isfinite(sc) & (sc > 0)).sum())}
+        if counts:
+            out["counts"] = np.zeros((max(ngroups, 0), max(B, 0)), np.int64)
+        dropped = C.c_int64(0)
+        self._check(self.lib.mc_group_bootstrap(self.h, B, int(seed) & 0xFFFFFFFFFFFFFFFF, sc.ctypes.data_as(C.c_void_p), gof.ctypes.data_as(C.c_void_p), ngroups,
+                                                kb.ctypes.data_as(C.c_void_p), out["counts"].ctypes.data_as(C.c_void_p) if counts else None,
+                                                out["stats"].ctypes.data_as(C.c_void_p), C.byref(dropped)), "mc_group_bootstrap")
+        out["dropped"] = int(dropped.value)
+        return out
+
+    def group_bootstrap_ms(self):
+        """milliseconds the kernels of the group_bootstrap() calls took since the last reset (HIP events): two per call, and three more
+        where the call had to make the genes' replicate counts"""
+        return float(self.lib.mc_group_bootstrap_ms(self.h))
+
+    def group_bootstrap_kernels_ms(self):
+        """of group_bootstrap_ms(), the share of each of the two kernels: {"values", "summary"}"""
+        v, s = C.c_float(0), C.c_float(0)
+        self.lib.mc_group_bootstrap_kernels_ms(self.h, C.byref(v), C.byref(s))
+        return {"values": float(v.value), "summary": float(s.value)}
 
     def set_abundance_classes(self, on=True):
         """The counts may ride on class runs (mc_set_abundance_classes; csrc/k_abund_classes.h states the rule): while it is on,

@@ -47,6 +47,13 @@ b of the gene counts is divided by replicate b of the genome equivalents: numera
 
 With a given AGS (--ags, --ags-report) the denominator is fixed and the interval reflects the counts alone.
 
+And how sure is a group's?  Not by its members' columns: a group's RPKG is the sum of theirs, their replicates are correlated - the genome
+equivalents of replicate b divide all of them, and alleles that compete for the same reads move against each other - so neither the standard
+error nor a percentile of the sum follows from the members'.  With bootstrap_groups (Engine.group_bootstrap; csrc/mc_groupboot.h states the
+rule) replicate b of a group is the sum of its members' replicate RPKGs, added on the device in FASTA order, and the groups table gets the same
+three columns from those sums.  It is also the level at which the bootstrap is most trustworthy: without ties a read that ties between alleles
+goes to whichever row comes first, and tying alleles normally share a group.  The groups' tie columns stay whole-sample figures.
+
 Reads of mixed lengths (mixed_lengths; README "Reads of mixed lengths"): one trimmed length drops every shorter read and the tail of
 every longer one.  Under the switch every read is searched and counted at the largest length class L_k it reaches
 (Engine.set_abundance_classes; csrc/k_abund_classes.h states the rule), and the denominator is that of the bases so sampled:
@@ -87,7 +94,7 @@ TIES_COLUMNS = ("unique_reads", "candidate_reads", "shared_reads", "rpkg_shared"
 TIES_COVERAGE_COLUMNS = ("covered_any_aa", "breadth_any")                            # ... these behind them with coverage, "detected_any" last with min_breadth
 GROUP_TIES_COLUMNS = ("unique_reads", "shared_reads", "rpkg_shared")                 # behind the groups table's columns; "genes_detected_any" last with min_breadth
 CURVE_COLUMNS = ("sampled_reads", "average_genome_size", "genome_equivalents_sampled", "reads_assigned", "genes_with_reads")   # "genes_detected" behind them with min_breadth, "groups_with_reads" with groups
-BOOT_COLUMNS = ("rpkg_boot_se", "rpkg_ci95_low", "rpkg_ci95_high")                  # behind all of them with bootstrap
+BOOT_COLUMNS = ("rpkg_boot_se", "rpkg_ci95_low", "rpkg_ci95_high")                  # behind all of them with bootstrap; behind the groups table's with bootstrap_groups
 MAX_BOOT = 4096                                                                      # MC_GB_MAXB (csrc/mc_geneboot.h)
 MAX_CURVE = 64                                                                       # MC_CURVE_MAXK (csrc/mc_curve.h)
 PIPELINE_KEYS = ("seqfiles", "nreads", "read_length", "min_quality", "mean_quality", "filter_dups", "max_unknown", "threads", "device", "model_dir", "verbose")
@@ -409,6 +416,25 @@ def boot_columns(stats, used, length_aa):
     return se, out[0], out[1]
 
 
+def group_boot_columns(stats, used):
+    """(rpkg_boot_se, rpkg_ci95_low, rpkg_ci95_high) of the groups from the device's six doubles per group (csrc/mc_groupboot.h: sum, m2 and
+    the order statistics of the `used` replicate values, every one a sum of the members' replicate RPKGs): se = sqrt(m2 / (used - 1)), NaN with
+    used < 2; the interval is numpy.percentile(values, [2.5, 97.5]) by boot_columns' interpolation.  No division by a length: it is inside
+    the values."""
+    stats = np.asarray(stats, dtype=np.float64).reshape(-1, 6)
+    m = int(used)
+    if m < 1:
+        nan = np.full(len(stats), np.nan)
+        return nan, nan.copy(), nan.copy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        se = np.sqrt(stats[:, 1] / (m - 1)) if m > 1 else np.full(len(stats), np.nan)
+        out = []
+        for q, col in ((0.025, 2), (0.975, 4)):
+            v = (m - 1) * q
+            out.append(_lerp(stats[:, col], stats[:, col + 1], v - math.floor(v)))
+    return se, out[0], out[1]
+
+
 def header_lines(args, table):
     mixed = [] if table.get("length_classes") is None else [(k, ",".join(str(int(x)) for x in table[k])) for k in ("length_classes", "class_reads", "class_reads_assigned")] + [("sampled_bases", table["sampled_bases"])]
     h = [("metagenome", ",".join(args["seqfiles"])), ("genes", args["genes"]), ("sampled_reads", table["sampled_reads"]),
@@ -442,7 +468,8 @@ def group_columns(table):
     """[(column, kind)] of the groups table: those of a row of table['groups'] and, with ties, of the same row of table['groups_ties']"""
     gt = table.get("groups_ties")
     ties = GROUP_TIES_COLUMNS + (("genes_detected_any",) if table.get("detected_any") is not None else ()) if gt is not None else ()
-    return list(zip(GROUP_COLUMNS + (("genes_detected",) if table.get("detected") is not None else ()), "sddfd")) + list(zip(ties, "dffd"))
+    boot = BOOT_COLUMNS if table.get("groups_boot") is not None else ()
+    return list(zip(GROUP_COLUMNS + (("genes_detected",) if table.get("detected") is not None else ()), "sddfd")) + list(zip(ties, "dffd")) + list(zip(boot, "fff"))
 
 
 def _write_rows(out, columns, values):
@@ -452,22 +479,31 @@ def _write_rows(out, columns, values):
     out.writelines("\t".join(row) + "\n" for row in zip(*text))
 
 
+def boot_header_lines(table):
+    """the four header lines of a bootstrapped table"""
+    return ["# %s:\t%s\n" % kv for kv in (("bootstrap", table["bootstrap"]), ("bootstrap_seed", table["bootstrap_seed"]),
+                                          ("bootstrap_replicates", "%d/%d" % (table["boot_used"], table["bootstrap"])),
+                                          ("bootstrap_denominator", table["bootstrap_denominator"]))]
+
+
 def write_table(path, args, table):
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
-        if table.get("rpkg_boot_se") is not None:                  # (the gene table's alone: the groups table does not bootstrap)
-            out.writelines("# %s:\t%s\n" % kv for kv in (("bootstrap", table["bootstrap"]), ("bootstrap_seed", table["bootstrap_seed"]),
-                                                         ("bootstrap_replicates", "%d/%d" % (table["boot_used"], table["bootstrap"])),
-                                                         ("bootstrap_denominator", table["bootstrap_denominator"])))
+        if table.get("rpkg_boot_se") is not None:
+            out.writelines(boot_header_lines(table))
         columns = table_columns(table)
         _write_rows(out, columns, [table[name] for name, _ in columns])
 
 
 def write_groups(path, args, table):
+    """the groups table; it bootstraps only with table['groups_boot'] (bootstrap_groups): without it the file is what it was before the switch existed"""
+    boot = table.get("groups_boot")
     with open(path, "w") as out:
         out.writelines(header_lines(args, table))
         out.write("# groups:\t%s\n" % args["groups"])
-        _write_rows(out, group_columns(table), list(zip(*table["groups"])) + list(zip(*(table.get("groups_ties") or []))))
+        if boot is not None:
+            out.writelines(boot_header_lines(table) + ["# bootstrap_groups:\ton\n"])
+        _write_rows(out, group_columns(table), list(zip(*table["groups"])) + list(zip(*(table.get("groups_ties") or []))) + list(zip(*(boot or []))))
 
 
 def curve_figures(names, length_aa, read_length, points, reads, aligned, covered, ags, min_breadth=None, group_of=None):
@@ -562,7 +598,7 @@ def check_request(args):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
                          ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
-                         ("bootstrap", None), ("bootstrap_seed", None), ("mixed_lengths", None), ("long_genes", False)):
+                         ("bootstrap", None), ("bootstrap_seed", None), ("bootstrap_groups", False), ("mixed_lengths", None), ("long_genes", False)):
         args.setdefault(key, default)
     mixed = microbe_census.mixed_lengths_on(args)
     if mixed:
@@ -584,6 +620,12 @@ def check_request(args):
         if args["bootstrap"] is None:
             raise AbundanceError("--bootstrap-seed %s needs --bootstrap B: it seeds the replicates" % (args["bootstrap_seed"],))
         _check_int(args, "bootstrap_seed", 0, (1 << 64) - 1, "0 to 2^64 - 1")
+    _check_switch(args, "bootstrap_groups")
+    if args["bootstrap_groups"]:
+        if args["bootstrap"] is None:
+            raise AbundanceError("--bootstrap-groups needs --bootstrap B (--bootstrap %s): it sums the gene bootstrap's replicates over every group" % (args["bootstrap"],))
+        if not args["groups"]:
+            raise AbundanceError("--bootstrap-groups needs --groups map.tsv (--groups %s): it bootstraps the groups table" % (args["groups"],))
     if args["curve_genes"] is not None:
         if not args["curve_genes"]:
             raise AbundanceError("--curve-genes %r is an empty path" % (args["curve_genes"],))
@@ -713,7 +755,7 @@ def _replicate_scale(args, sample, ab, ac):
 
 def device_pass(args, sample, names, seqs, group_of):
     """Stage 2 - the record `counts`, from the only place that opens a reader or an engine: what the device counted as numpy arrays and ints - ab,
-    ac, cov, depth, ti, tcov, cu and points, gb and scale, fold_stats (None: not asked for), sampled, gids and gnames, search_ms and the *_ms"""
+    ac, cov, depth, ti, tcov, cu and points, gb, gbg (the groups') and scale, fold_stats (None: not asked for), sampled, gids and gnames, search_ms and the *_ms"""
     pargs, classes, fold = sample["pargs"], sample["classes"], args["gene_fold"]
     sampler = (pargs["nreads"], pargs["file_type"] == "fastq", pargs.get("quality_offset") or 0, pargs["min_quality"], pargs["mean_quality"], pargs["max_unknown"], pargs["filter_dups"])
     rd = _native.Reader.with_classes(pargs["seqfiles"], classes, *sampler) if classes is not None else _native.Reader(pargs["seqfiles"], sample["L"], *sampler)
@@ -721,7 +763,7 @@ def device_pass(args, sample, names, seqs, group_of):
     try:                        # (long_genes: the engine on the segments, with the genes' statistics)
         db = {"names": names, "seqs": seqs} if fold is None else {"names": fold["seg_names"], "seqs": fold["seg_seqs"], "stats": fold["stats"]}
         eng = _native.Engine(device=int(args.get("device") or 0), marker_family=[0] * len(db["names"]), nfam=1, **db)
-        c = dict.fromkeys(("ac", "gb", "scale"))
+        c = dict.fromkeys(("ac", "gb", "gbg", "scale"))
         c["gids"], c["gnames"] = _set_switches(eng, args, sample, names, group_of)
         try:
             c["cu"], c["points"] = _search_once(eng, rd, args, sample)
@@ -737,6 +779,13 @@ def device_pass(args, sample, names, seqs, group_of):
             except RuntimeError as e:
                 raise AbundanceError(str(e))
             c["gene_bootstrap_ms"] = eng.gene_bootstrap_ms()
+            if args["bootstrap_groups"]:                            # the same replicates and scales, summed over group_ids' groups on the device
+                ids, gn = group_ids(names, group_of)
+                try:
+                    c["gbg"] = eng.group_bootstrap(args["bootstrap"], args["bootstrap_seed"] or 0, c["scale"], ids, len(gn), 3.0 * np.array([len(s) for s in seqs], np.float64) / 1000.0)
+                except RuntimeError as e:
+                    raise AbundanceError(str(e))
+                c["group_bootstrap_ms"] = eng.group_bootstrap_ms()
         c["cov"] = eng.coverage() if args["coverage"] else None
         c["depth"] = eng.coverage_depth() if args["depth_out"] is not None else None
         c["ti"] = eng.ties() if args["ties"] else None
@@ -813,6 +862,9 @@ def build_table(args, sample, counts, names, seqs, group_of):
                       "bootstrap": args["bootstrap"], "bootstrap_seed": args["bootstrap_seed"] or 0, "bootstrap_denominator": "replicate_ags" if est else "fixed_ags"})
     if group_of is not None:
         table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of, table.get("detected"))
+    gbg = counts.get("gbg")                                        # (a record from before the switch has no such key)
+    if gbg is not None:                                             # (group_ids numbers the groups in group_table's order)
+        table.update({"groups_boot": list(zip(*(col.tolist() for col in group_boot_columns(gbg["stats"], gbg["used"])))), "groups_boot_stats": gbg["stats"]})
     if cu is not None:
         points = [int(n) for n in counts["points"]]
         if cu["beyond"] != 0:
@@ -846,7 +898,8 @@ def run_abundance(args):
     verbose, outfile) plus genes, min_ident, min_aln, min_bits, groups, ags, ags_report and the switches the module's docstring describes,
     all off by default: coverage, min_breadth and depth_out (a path; both imply coverage), ties, curve (K, 1 .. 64: table['curve']; writes
     <outfile>.curve.tsv) with curve_genes (a path: the curve's per-gene matrix), bootstrap (B, 1 .. 4096) with bootstrap_seed (default 0; not
-    combined with curve), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
+    combined with curve) and bootstrap_groups (needs bootstrap and groups: table['groups_boot'], one (se, low, high) per row of table['groups'],
+    table['groups_boot_stats'], and the three columns behind every column of <outfile>.groups.tsv), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
     given AGS), long_genes (genes of up to 65,535 residues; table['long_genes'] = {genes_split, segments, edge_rows}).  Four stages with two
     records between them - DESIGN.md 13, "How a run is laid out on the host".  Writes args['outfile'] (and <outfile>.groups.tsv with groups)
     when it is set; leaves in args the sampler's options as imputed, sampled_reads, search_ms and the *_ms of every switch that ran; returns

@@ -2,14 +2,16 @@
 // (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap) and the counts on class runs
 // (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
 // With a gene fold (mc_set_gene_fold, mc_fold.h) it also owns the fold of a range's rows from segments onto genes (k_fold.h), in front of everything else.
-// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
-// hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end.
+// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_groupboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
+// hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end
+// (device_groupboot.hip also through mc_groupboot_launch, like the group bootstrap's read).
 #pragma once
 #include "k_abundance.h"
 #include "k_coverage.h"
 #include "k_ties.h"
 #include "k_curve.h"
 #include "k_geneboot.h"
+#include "k_groupboot.h"
 #include "k_abund_classes.h"
 #include "k_fold.h"
 #include "mc_owned.h"
@@ -107,6 +109,23 @@ static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hip
     return 0;
 }
 
+// The group bootstrap's read (mc_groupboot.h): raw device pointers of one mc_group_bootstrap, behind a read that left mat.  mat: ngenes x B
+// replicate counts; start, member, kb: the CSR of the ngrp groups with reads, made by mc_grb_plan on the host; val: ngrp x B doubles;
+// cnt: ngrp x B counts, or null; scale: B doubles, m of them used; out: ngrp x 6 doubles
+struct McGroupBootRead { int32_t ngenes, ngrp; const unsigned long long *mat; const uint32_t *start; const uint32_t *member; const double *kb; double *val; unsigned long long *cnt;
+                         const double *scale; int32_t B, m; double *out; };
+// The two kernels of a read between ev[0] and ev[1], in `st`, and ev[2] between them; with ngrp == 0 only the events
+static int mc_groupboot_launch(const McGroupBootRead &R, hipStream_t st, const hipEvent_t (&ev)[3])
+{
+    HIPCK(hipEventRecord(ev[0], st));
+    if (R.ngrp > 0) k_groupboot_values<<<dim3((unsigned)R.ngrp, (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.mat, (uint32_t)R.ngenes, R.B, R.scale, R.start, R.member, R.kb, R.val, R.cnt);
+    HIPCK(hipEventRecord(ev[2], st));
+    if (R.ngrp > 0) k_groupboot_summary<<<dim3((unsigned)R.ngrp), dim3(MC_GB_THREADS), 0, st>>>(R.val, R.scale, R.B, R.m, R.out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(ev[1], st));
+    return 0;
+}
+
 // ---- Owner --------------------------------------------------------------------------------------------------------------------
 // The six switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
@@ -119,6 +138,7 @@ static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hip
 //     the bootstrap's list, its cursor and dropped counter, the grouped list,
 //     the genes' cursors and compact indices, the scales, the output, its three events   the gene bootstrap is on
 //     the bootstrap's matrix of replicate counts                                  the gene bootstrap is on and a read has sized it
+//     the group bootstrap's CSR, gene_kb, output and its three events; its values and counts   the gene bootstrap is on and a group read has sized them
 //     the per-class table (k_abund_classes.h), its event                          the counts may ride on class runs
 //     the segment records, the genes' offsets, the edge counter, its two events   a gene fold is set (set_fold; with the counts on or off)
 //     the folded rows                                                             a gene fold is set and a range has sized them (launch grows them)
@@ -138,6 +158,14 @@ struct McAbundance {
     size_t gmat_slots = 0;                                         // what d_gmat holds: a read grows it to ngenes x B
     McEvent ev_gboot, ev_gread[2];                                 // behind k_geneboot_collect; around the kernels of a read
     float gboot_ms = 0, gread_ms = 0;                              // k_geneboot_collect's, the reads' time since the last zeroing
+    // what d_gmat holds, so that a group read may take it over from the read before it: the replicates, the seed and the entries of the read that
+    // made it; gmat_n < 0: nothing - no read yet, or a range, a reset or a switch since (launch, reset, fit)
+    int32_t gmat_B = 0; uint64_t gmat_seed = 0; long long gmat_n = -1;
+    // the group bootstrap (mc_groupboot.h): the CSR of the groups with reads, the members' gene_kb, the replicate values and counts, the output
+    McDev<uint32_t> d_grstart, d_grmember; McDev<double> d_grkb, d_grval, d_grout; McDev<unsigned long long> d_grcnt;
+    size_t grval_slots = 0, grcnt_slots = 0;                       // what d_grval, d_grcnt hold: a group read grows them to ngrp x B
+    McEvent ev_grp[3];                                             // around the two kernels of a group read, and between them
+    float grp_ms = 0, grp_values_ms = 0, grp_summary_ms = 0;       // the group reads' time since the last zeroing (with the mat they had to make), and the two kernels'
     bool classes = false;                                          // mc_set_abundance_classes: the counts may ride on class runs
     McDev<unsigned long long> d_cls; McEvent ev_cls; float cls_ms = 0;   // the per-class table; behind k_abund_class_add; its time since the last zeroing
     McIdMap map = {nullptr, 0}; int32_t map_K = 0, piece_k = 0;    // held while a batch's pieces run (ride_begin .. ride_end): its ids, its classes; the class of the piece that ends next
@@ -224,6 +252,7 @@ struct McAbundance {
         if (d_edge) HIPCK(hipMemset(d_edge, 0, sizeof(unsigned long long)));
         fold_ms = 0.f;
         searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = 0.f;
+        gmat_n = -1; grp_ms = grp_values_ms = grp_summary_ms = 0.f;
         return 0;
     }
 
@@ -233,6 +262,7 @@ struct McAbundance {
     // the range before have been waited for, range_end), and everything behind sees the folded rows: the one site where segments become genes.
     int launch(const McRow *rows, uint32_t nr, hipStream_t st, int64_t nreads = 0)
     {
+        gmat_n = -1;
         if (fold) {
             if (nr > folded_cap) { folded_cap = 0; const size_t want = (size_t)nr + nr / 4 + 1024; if (d_folded.alloc(want)) return -1; folded_cap = want; }
             HIPCK(hipEventRecord(ev_fold[0], st));
@@ -331,32 +361,11 @@ struct McAbundance {
     int read_gene_bootstrap(int32_t B, uint64_t seed, const double *scale, int64_t *counts, double *stats, int64_t *dropped)
     {
         const size_t ns = (size_t)nseq;
-        unsigned long long cur[2];
-        HIPCK(hipMemcpy(cur, d_gcur, sizeof cur, hipMemcpyDeviceToHost));
-        if (dropped) *dropped = (int64_t)cur[1];
-        if (cur[1] || cur[0] > (unsigned long long)gcap) {
-            g_err = "mc_gene_bootstrap: " + std::to_string(cur[1]) + " assigned reads did not fit the list of " + std::to_string(gcap) + " entries (mc_set_gene_bootstrap): dropped, no replicate is whole";
-            return -1;
-        }
-        std::vector<unsigned long long> tab(mc_pair_slots(ns));
-        HIPCK(hipMemcpy(tab.data(), d_counts, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> start(ns); std::vector<int32_t> idx(ns);
-        unsigned long long total = 0;
-        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
-        if (total != cur[0]) { g_err = "mc_gene_bootstrap: the count table holds " + std::to_string(total) + " assigned reads, the list " + std::to_string(cur[0]); return -1; }
-        int32_t m = 0;
-        for (int32_t b = 0; b < B; b++) m += mc_gb_used(scale[b]) ? 1 : 0;
+        std::vector<int32_t> idx(ns);
+        int32_t ng = 0, m = 0; float took = 0.f;
+        if (make_mat("mc_gene_bootstrap", B, seed, scale, false, idx, &ng, &m, dropped, &took)) return -1;
+        gread_ms += took;
         const size_t need = (size_t)ng * (size_t)B;
-        if (need > gmat_slots) { gmat_slots = 0; if (d_gmat.alloc(need)) return -1; gmat_slots = need; }
-        HIPCK(hipMemcpy(d_gcursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(d_gidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(d_gscale, scale, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
-        if (need) HIPCK(hipMemsetAsync(d_gmat, 0, sizeof(unsigned long long) * need, 0));
-        const McGeneBootRead R = {nseq, ng, (long long)cur[0], d_glist, d_gcursor, d_gidx, d_gsorted, d_gmat, d_gscale, B, m, seed, d_gout};
-        const hipEvent_t ev[2] = {ev_gread[0], ev_gread[1]};
-        if (mc_geneboot_launch(R, 0, ev)) return -1;
-        HIPCK(hipEventSynchronize(ev_gread[1]));
-        gread_ms += ev_ms(ev_gread[0], ev_gread[1]);
         std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
         if (ng) HIPCK(hipMemcpy(out.data(), d_gout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (size_t s = 0; s < ns; s++)                            // (a gene without reads: zero in every replicate)
@@ -366,6 +375,43 @@ struct McAbundance {
         if (need) HIPCK(hipMemcpy(mat.data(), d_gmat, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         for (size_t s = 0; s < ns; s++)
             for (size_t b = 0; b < (size_t)B; b++) counts[s * (size_t)B + b] = idx[s] >= 0 ? (int64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
+        return 0;
+    }
+    // The bootstrap of the GROUPS (mc_groupboot.h) on the counts as they stand: group_of: nseq groups below ngroups_, gene_kb: nseq doubles, all
+    // checked by the caller (mc_group_bootstrap).  counts (or null): ngroups_ x B group replicate counts; stats: ngroups_ x 6 doubles.  mat is
+    // that of the read before when it is still this one's (the same B, seed and entries, no range since), and made here otherwise.
+    int read_group_bootstrap(int32_t B, uint64_t seed, const double *scale, const int32_t *group_of, int32_t ngroups_, const double *gene_kb, int64_t *counts, double *stats, int64_t *dropped)
+    {
+        const size_t ns = (size_t)nseq, ngr = (size_t)ngroups_;
+        std::vector<int32_t> idx(ns);
+        int32_t ng = 0, m = 0; float took = 0.f;
+        if (make_mat("mc_group_bootstrap", B, seed, scale, true, idx, &ng, &m, dropped, &took)) return -1;
+        std::vector<int32_t> gidx(ngr); std::vector<uint32_t> start(ngr + 1), member((size_t)ng); std::vector<double> kb((size_t)ng);
+        const int32_t ngrp = mc_grb_plan(idx.data(), nseq, group_of, ngroups_, gene_kb, gidx.data(), start.data(), member.data(), kb.data());
+        const size_t need = (size_t)ngrp * (size_t)B;
+        if (!d_grstart && (d_grstart.alloc(ns + 1) || d_grmember.alloc(ns) || d_grkb.alloc(ns) || d_grout.alloc((size_t)MC_GB_NOUT * ns) || ev_grp[0].create() || ev_grp[1].create() || ev_grp[2].create())) {
+            d_grstart.reset(); return -1;
+        }
+        if (need > grval_slots) { grval_slots = 0; if (d_grval.alloc(need)) return -1; grval_slots = need; }
+        if (counts && need > grcnt_slots) { grcnt_slots = 0; if (d_grcnt.alloc(need)) return -1; grcnt_slots = need; }
+        HIPCK(hipMemcpy(d_grstart, start.data(), sizeof(uint32_t) * ((size_t)ngrp + 1), hipMemcpyHostToDevice));
+        if (ng) HIPCK(hipMemcpy(d_grmember, member.data(), sizeof(uint32_t) * (size_t)ng, hipMemcpyHostToDevice));
+        if (ng) HIPCK(hipMemcpy(d_grkb, kb.data(), sizeof(double) * (size_t)ng, hipMemcpyHostToDevice));
+        const McGroupBootRead R = {ng, ngrp, d_gmat, d_grstart, d_grmember, d_grkb, d_grval, counts ? d_grcnt.get() : nullptr, d_gscale, B, m, d_grout};
+        const hipEvent_t ev[3] = {ev_grp[0], ev_grp[1], ev_grp[2]};
+        if (mc_groupboot_launch(R, 0, ev)) return -1;
+        HIPCK(hipEventSynchronize(ev_grp[1]));
+        const float tv = ev_ms(ev_grp[0], ev_grp[2]), ts = ev_ms(ev_grp[2], ev_grp[1]);
+        grp_values_ms += tv; grp_summary_ms += ts; grp_ms += took + tv + ts;
+        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ngrp);
+        if (ngrp) HIPCK(hipMemcpy(out.data(), d_grout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t G = 0; G < ngr; G++)                           // (a group without reads: zero in every replicate)
+            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * G + k] = gidx[G] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)gidx[G] + k] : m ? 0.0 : mc_gb_nan();
+        if (!counts) return 0;
+        std::vector<unsigned long long> cm(need);
+        if (need) HIPCK(hipMemcpy(cm.data(), d_grcnt, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t G = 0; G < ngr; G++)
+            for (size_t b = 0; b < (size_t)B; b++) counts[G * (size_t)B + b] = gidx[G] >= 0 ? (int64_t)cm[(size_t)gidx[G] * (size_t)B + b] : 0;
         return 0;
     }
     // the per-class table as it stands: n pairs, class 0 .. n - 2 and the rows below the lowest class (the caller knows its K: n = K + 1)
@@ -385,6 +431,45 @@ struct McAbundance {
     }
 
 private:
+    // mat of the counts as they stand - genes with reads x B replicate counts under `seed` - and the six doubles of every gene with reads in d_gout,
+    // through ONE copy of the count table: the list's refusals under the caller's name `who`, mc_gb_plan, the three kernels of mc_geneboot_launch.
+    // idx: nseq compact indices; ng: the genes with reads; m: the used replicates; took: the kernels' milliseconds.  With reuse, a mat that is
+    // still this one's (gmat_*) is kept and nothing is launched: the scales alone go to the device.
+    int make_mat(const char *who, int32_t B, uint64_t seed, const double *scale, bool reuse, std::vector<int32_t> &idx, int32_t *ng_out, int32_t *m_out, int64_t *dropped, float *took)
+    {
+        const size_t ns = (size_t)nseq;
+        unsigned long long cur[2];
+        HIPCK(hipMemcpy(cur, d_gcur, sizeof cur, hipMemcpyDeviceToHost));
+        if (dropped) *dropped = (int64_t)cur[1];
+        if (cur[1] || cur[0] > (unsigned long long)gcap) {
+            g_err = std::string(who) + ": " + std::to_string(cur[1]) + " assigned reads did not fit the list of " + std::to_string(gcap) + " entries (mc_set_gene_bootstrap): dropped, no replicate is whole";
+            return -1;
+        }
+        std::vector<unsigned long long> tab(mc_pair_slots(ns));
+        HIPCK(hipMemcpy(tab.data(), d_counts, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> start(ns);
+        unsigned long long total = 0;
+        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
+        if (total != cur[0]) { g_err = std::string(who) + ": the count table holds " + std::to_string(total) + " assigned reads, the list " + std::to_string(cur[0]); return -1; }
+        int32_t m = 0;
+        for (int32_t b = 0; b < B; b++) m += mc_gb_used(scale[b]) ? 1 : 0;
+        *ng_out = ng; *m_out = m; *took = 0.f;
+        HIPCK(hipMemcpy(d_gscale, scale, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
+        if (reuse && gmat_n == (long long)cur[0] && gmat_B == B && gmat_seed == seed) return 0;
+        gmat_n = -1;
+        const size_t need = (size_t)ng * (size_t)B;
+        if (need > gmat_slots) { gmat_slots = 0; if (d_gmat.alloc(need)) return -1; gmat_slots = need; }
+        HIPCK(hipMemcpy(d_gcursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_gidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
+        if (need) HIPCK(hipMemsetAsync(d_gmat, 0, sizeof(unsigned long long) * need, 0));
+        const McGeneBootRead R = {nseq, ng, (long long)cur[0], d_glist, d_gcursor, d_gidx, d_gsorted, d_gmat, d_gscale, B, m, seed, d_gout};
+        const hipEvent_t ev[2] = {ev_gread[0], ev_gread[1]};
+        if (mc_geneboot_launch(R, 0, ev)) return -1;
+        HIPCK(hipEventSynchronize(ev_gread[1]));
+        *took = ev_ms(ev_gread[0], ev_gread[1]);
+        gmat_B = B; gmat_seed = seed; gmat_n = (long long)cur[0];
+        return 0;
+    }
     template <class Tp> static int fit_one(McDev<Tp> &d, bool want, size_t n) { if (!want) d.reset(); return want && !d ? d.alloc(n) : 0; }
     static int fit_one(McEvent &e, bool want) { if (!want) e.reset(); return want && !e ? e.create() : 0; }
     // the switches as they stand, made consistent; then the buffer rule: what they need is made where it is missing, everything else freed
@@ -395,7 +480,11 @@ private:
         if (!cov) cov_ms = 0.f;
         if (!ties) { ngroups = 0; ties_ms = 0.f; }
         if (!curve) { K = 0; curve_ms = cscan_ms = 0.f; }
-        if (!gboot) { gcap = 0; gboot_ms = gread_ms = 0.f; d_gmat.reset(); gmat_slots = 0; }
+        if (!gboot) {
+            gcap = 0; gboot_ms = gread_ms = grp_ms = grp_values_ms = grp_summary_ms = 0.f; d_gmat.reset(); gmat_slots = 0; gmat_n = -1;
+            d_grstart.reset(); d_grmember.reset(); d_grkb.reset(); d_grval.reset(); d_grcnt.reset(); d_grout.reset(); grval_slots = grcnt_slots = 0;
+            for (McEvent &e : ev_grp) e.reset();
+        }
         const size_t ns = (size_t)nseq, slots = mc_diff_slots(nres, ns);
         return fit_one(d_counts, on, mc_pair_slots(ns)) || fit_one(ev_count[0], on) || fit_one(ev_count[1], on) ||
                fit_one(d_diff, cov, slots) || fit_one(d_covout, cov, 3 * ns) || fit_one(ev_cov[0], cov) || fit_one(ev_cov[1], cov) ||

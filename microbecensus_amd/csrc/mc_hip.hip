@@ -20,6 +20,7 @@
 //   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
 //   k_curve.h              the rarefaction curve beside them: per-gene counts per prefix of the sample, every residue's first read, a scan at read time (mc_set_curve)
 //   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
+//   k_groupboot.h          the bootstrap of the groups table behind it: every group's replicate values walked over its members' rows of the replicate sums, sort and summary (mc_group_bootstrap)
 //   k_abund_classes.h      the per-class table of the counts on class runs (mc_set_abundance_classes)
 //   k_fold.h, mc_fold.h    genes longer than one sequence of the engine: segments, and the fold of a range's rows onto the genes (mc_set_gene_fold)
 //   mc_abund.h             (host) the owner of those five: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
@@ -2100,6 +2101,25 @@ extern "C" int mc_gene_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const d
     return h->ab.read_gene_bootstrap(B, seed, scale, counts, stats, dropped);
 }
 
+// the bootstrap of the groups table (mc_groupboot.h): counts (or NULL): ngroups x B group replicate counts; stats: ngroups x 6 doubles
+extern "C" int mc_group_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale, const int32_t *group_of, int32_t ngroups, const double *gene_kb, int64_t *counts,
+                                  double *stats, int64_t *dropped)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.gboot) { g_err = "mc_group_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap)"; return -1; }
+    if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_group_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
+    if (!scale || !stats || !group_of || !gene_kb) { g_err = "mc_group_bootstrap: B = " + std::to_string(B) + " and a NULL scale, group_of, gene_kb or stats array"; return -1; }
+    const int32_t nseq = h->ab.nseq;
+    if (ngroups < 1 || ngroups > nseq) { g_err = "mc_group_bootstrap: ngroups " + std::to_string(ngroups) + " is not a number of groups from 1 to " + std::to_string(nseq) + ", the genes"; return -1; }
+    for (int32_t s = 0; s < nseq; s++) {
+        if (group_of[s] < 0 || group_of[s] >= ngroups) { g_err = "mc_group_bootstrap: group_of[" + std::to_string(s) + "] = " + std::to_string(group_of[s]) + " is not a group from 0 to " + std::to_string(ngroups - 1); return -1; }
+        if (!(gene_kb[s] > 0.0 && gene_kb[s] <= 1.7976931348623157e308)) { g_err = "mc_group_bootstrap: gene_kb[" + std::to_string(s) + "] = " + std::to_string(gene_kb[s]) + " is not a finite number > 0"; return -1; }
+    }
+    if (h->pipe_nout) { g_err = "mc_group_bootstrap: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_group_bootstrap(B, seed, scale, group_of, ngroups, gene_kb, counts, stats, dropped);
+}
+
 // the counts on class runs: mc_search_classes and mc_search_files on a class reader are no longer refused, every piece adds to the
 // counts and to the per-class table (k_abund_classes.h), and the gene bootstrap takes the read ids through the batch's id map
 extern "C" int mc_set_abundance_classes(mc_handle *h, int on)
@@ -2199,6 +2219,14 @@ extern "C" float mc_abundance_classes_ms(const mc_handle *h) { return h ? h->ab.
 
 // k_geneboot_collect's time over the completed ranges plus the reads' kernels, since the last zeroing
 extern "C" float mc_gene_bootstrap_ms(const mc_handle *h) { return h ? h->ab.gboot_ms + h->ab.gread_ms : 0.0f; }
+// the group reads' kernels since the last zeroing: k_groupboot_values and k_groupboot_summary, and the kernels of a mat a group read had to make
+extern "C" float mc_group_bootstrap_ms(const mc_handle *h) { return h ? h->ab.grp_ms : 0.0f; }
+// the two kernels' shares of it (either may be NULL)
+extern "C" void mc_group_bootstrap_kernels_ms(const mc_handle *h, float *values_ms, float *summary_ms)
+{
+    if (values_ms) *values_ms = h ? h->ab.grp_values_ms : 0.0f;
+    if (summary_ms) *summary_ms = h ? h->ab.grp_summary_ms : 0.0f;
+}
 extern "C" float mc_abundance_ms(const mc_handle *h) { return h ? h->ab.ms : 0.0f; }
 extern "C" float mc_coverage_ms(const mc_handle *h) { return h ? h->ab.cov_ms : 0.0f; }
 extern "C" float mc_ties_ms(const mc_handle *h) { return h ? h->ab.ties_ms : 0.0f; }

@@ -48,6 +48,9 @@ def parse_arguments(argv=None):
     p.add_argument("--bootstrap", dest="bootstrap", type=int, default=None, metavar="B", help="add rpkg_boot_se, rpkg_ci95_low and rpkg_ci95_high: the standard error and 95%% interval of every RPKG from B Poisson-bootstrap "
                    "replicates of the sampled reads (1 - 4096); with the default AGS every replicate is divided by its own AGS estimate, with --ags / --ags-report by the given one.  Not combined with --curve")
     p.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=None, metavar="S", help="with --bootstrap: the seed of the replicates (default = 0)")
+    p.add_argument("--bootstrap-groups", dest="bootstrap_groups", action="store_true", default=False,
+                   help="with --bootstrap and --groups: add rpkg_boot_se, rpkg_ci95_low and rpkg_ci95_high to <out>.groups.tsv, from the same replicates summed over every group's genes "
+                        "(a group's error bar does not follow from its members': their replicates are correlated)")
     p.add_argument("--mixed-lengths", dest="mixed_lengths", nargs="?", const=True, default=None, metavar="L1,L2,...",
                    type=lambda v: [int(x) for x in v.split(",")],
                    help="count every read at the largest of the model's read lengths it reaches, instead of cutting all reads to one length and dropping the shorter ones; "
