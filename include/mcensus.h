@@ -631,6 +631,31 @@ float mc_group_bootstrap_ms(const mc_handle *h);
 /* Of those, the milliseconds of k_groupboot_values and of k_groupboot_summary (either pointer may be NULL). */
 void mc_group_bootstrap_kernels_ms(const mc_handle *h, float *values_ms, float *summary_ms);
 
+/* ---- the bootstrap of the tie shares: how sure an rpkg_shared is ---------------------------------------------------------------------
+ * csrc/mc_tieboot.h states the rule.  It extends mc_set_gene_bootstrap from the counts to the shares of mc_set_ties: while it is on every
+ * read that mc_set_ties counts also appends one entry per subject of its tied set - (global read id, subject, share - 1), 12 bytes; a
+ * share is the floor(2^32 / k), plus the remainder for the first tied subject, that mc_ties_read adds to share[] - to a device list of
+ * `capacity` entries: one more kernel behind the gene bootstrap's of every range, on the same rows where they lie.  An entry that does
+ * not fit adds 1 to `dropped` and writes nothing.  mc_set_tie_bootstrap(h, capacity) makes the list and zeroes it AND every abundance
+ * counter, as the other switches do; capacity == 0 frees everything and restores the path without it exactly.  mc_set_ties and
+ * mc_set_gene_bootstrap - off, or set anew - also turn it off: set it behind them.  mc_abundance_reset() also empties the list and zeroes
+ * mc_tie_bootstrap_ms().
+ * Refused, with a message naming the value: capacity < 0 or > 2^27 (no replicate sum can wrap below that), ties off, the gene bootstrap
+ * off, a range in flight.  While it is on mc_search_varlen is refused, as under mc_set_gene_bootstrap. */
+int mc_set_tie_bootstrap(mc_handle *h, int64_t capacity);
+/* mc_gene_bootstrap's contract on the shares (it extends it: the same B, seed, scale, weights and six doubles): shares (or NULL): the
+ * replicate shares cs[b][s] at [s * B + b], exact integers in units of 2^-32 - the sum over the reads whose tied set holds s of
+ * weight x share.  Replicate b is used when scale[b] * 2^-32 is finite and > 0, its value is (double)cs[b][s] * (scale[b] * 2^-32).
+ * For every b the shares add up to 2^32 times mc_gene_bootstrap's counts.  stats, dropped: as mc_gene_bootstrap's, dropped counting
+ * entries; when it is not zero the call returns an error that names the number and computes nothing. */
+int mc_tie_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale /* [B] */, uint64_t *shares /* [nseq * B] or NULL */, double *stats /* [nseq * 6] */,
+                     int64_t *dropped);
+/* Milliseconds the tie bootstrap's kernels took since the last reset (HIP events), as mc_gene_bootstrap_ms: one kernel per completed
+ * range plus three per mc_tie_bootstrap. */
+float mc_tie_bootstrap_ms(const mc_handle *h);
+/* Of those, the milliseconds of k_tieboot_collect and of the reads' kernels (as mc_group_bootstrap_kernels_ms; either pointer may be NULL). */
+void mc_tie_bootstrap_kernels_ms(const mc_handle *h, float *collect_ms, float *read_ms);
+
 /* ---- the counts on class runs: gene abundances from reads of mixed lengths -------------------------------------------------------
  * README "Reads of mixed lengths": a class run searches every read at the largest length class it reaches.  With this switch on the
  * abundance counts ride on such a run: mc_search_classes and mc_search_files on a reader of length classes are no longer refused

@@ -249,6 +249,12 @@ def load_library():
     lib.mc_group_bootstrap_ms.argtypes = [C.c_void_p]
     lib.mc_group_bootstrap_kernels_ms.restype = None
     lib.mc_group_bootstrap_kernels_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.mc_set_tie_bootstrap.argtypes = [C.c_void_p, C.c_int64]
+    lib.mc_tie_bootstrap.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.mc_tie_bootstrap_ms.restype = C.c_float
+    lib.mc_tie_bootstrap_ms.argtypes = [C.c_void_p]
+    lib.mc_tie_bootstrap_kernels_ms.restype = None
+    lib.mc_tie_bootstrap_kernels_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.mc_set_abundance_classes.argtypes = [C.c_void_p, C.c_int]
     lib.mc_abundance_classes_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mc_abundance_classes_ms.restype = C.c_float
@@ -282,6 +288,7 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms",
                     "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms",
                     "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms", "mc_group_bootstrap", "mc_group_bootstrap_ms", "mc_group_bootstrap_kernels_ms",
+                    "mc_set_tie_bootstrap", "mc_tie_bootstrap", "mc_tie_bootstrap_ms", "mc_tie_bootstrap_kernels_ms",
                     "mc_set_abundance_classes", "mc_abundance_classes_read", "mc_abundance_classes_ms", "mc_open_stats", "mc_set_gene_fold", "mc_gene_fold_stats",
                     "mc_abundance_count", "mc_abundance_residues", "mc_debug_live"]
 
@@ -1082,6 +1089,7 @@ class Engine:
         assigned before gene_bootstrap() is called; 0 or None turns it off.  Turning it on zeroes the list AND the abundance counters,
         depth, ties and curve.  Refused while set_abundance is off; search_varlen is refused while it is on."""
         self._check(self.lib.mc_set_gene_bootstrap(self.h, int(capacity or 0)), "mc_set_gene_bootstrap")
+        self.gene_bootstrap_capacity = int(capacity or 0)          # (what the tie list is sized by: abundance.tie_list_capacity)
 
     def gene_bootstrap(self, B, seed, scale, counts=False):
         """B Poisson-bootstrap replicates of the counts as they stand (mc_gene_bootstrap), under bootstrap()'s weights: {"stats":
@@ -1135,6 +1143,43 @@ class Engine:
         v, s = C.c_float(0), C.c_float(0)
         self.lib.mc_group_bootstrap_kernels_ms(self.h, C.byref(v), C.byref(s))
         return {"values": float(v.value), "summary": float(s.value)}
+
+    def set_tie_bootstrap(self, capacity):
+        """The bootstrap of the tie shares (mc_set_tie_bootstrap; csrc/mc_tieboot.h states the rule): from now on every read that set_ties
+        counts is also kept as one (global id, gene, share) per gene of its tied set in a device list of `capacity` entries, at most 2^27 -
+        the most entries (the sum of ties()["candidates"]) there may be before tie_bootstrap() is called; 0 or None turns it off.  Turning
+        it on zeroes the list AND every abundance counter.  Refused while set_ties or set_gene_bootstrap is off - and either of them, set
+        again or turned off, turns it off: call it behind them.  search_varlen is refused while it is on."""
+        self._check(self.lib.mc_set_tie_bootstrap(self.h, int(capacity or 0)), "mc_set_tie_bootstrap")
+
+    def tie_bootstrap(self, B, seed, scale, shares=False):
+        """gene_bootstrap() on the tie shares as they stand (mc_tie_bootstrap): the same replicates, {"stats": float64[nseq, 6] - sum, m2,
+        x[lo], x[lo + 1], x[hi], x[hi + 1] of the used values (double)cs[b][s] * (scale[b] * 2^-32) -, "used": m, "dropped": 0} and with
+        shares=True "shares": uint64[nseq, B] in units of 2^-32.  Replicate b is used when scale[b] * 2^-32 is finite and > 0.  Raises when
+        an entry did not fit the list (the message names how many)."""
+        B, n = int(B), self.abundance_count()
+        sc = np.ascontiguousarray(scale, dtype=np.float64)
+        if sc.shape != (max(B, 0),):
+            raise ValueError("scale holds %d values, B is %d" % (sc.size, B))
+        s32 = sc * 2.0 ** -32
+        out = {"stats": np.zeros((n, 6), np.float64), "used": int((np.isfinite(s32) & (s32 > 0)).sum())}
+        if shares:
+            out["shares"] = np.zeros((n, max(B, 0)), np.uint64)
+        dropped = C.c_int64(0)
+        self._check(self.lib.mc_tie_bootstrap(self.h, B, int(seed) & 0xFFFFFFFFFFFFFFFF, sc.ctypes.data_as(C.c_void_p), out["shares"].ctypes.data_as(C.c_void_p) if shares else None,
+                                              out["stats"].ctypes.data_as(C.c_void_p), C.byref(dropped)), "mc_tie_bootstrap")
+        out["dropped"] = int(dropped.value)
+        return out
+
+    def tie_bootstrap_ms(self):
+        """milliseconds the tie bootstrap's kernels took since the last reset (HIP events): one kernel per range, three per tie_bootstrap()"""
+        return float(self.lib.mc_tie_bootstrap_ms(self.h))
+
+    def tie_bootstrap_kernels_ms(self):
+        """of tie_bootstrap_ms(), the share of k_tieboot_collect and of the reads' kernels: {"collect", "read"}"""
+        c, r = C.c_float(0), C.c_float(0)
+        self.lib.mc_tie_bootstrap_kernels_ms(self.h, C.byref(c), C.byref(r))
+        return {"collect": float(c.value), "read": float(r.value)}
 
     def set_abundance_classes(self, on=True):
         """The counts may ride on class runs (mc_set_abundance_classes; csrc/k_abund_classes.h states the rule): while it is on,

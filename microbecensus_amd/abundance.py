@@ -54,6 +54,14 @@ rule) replicate b of a group is the sum of its members' replicate RPKGs, added o
 three columns from those sums.  It is also the level at which the bootstrap is most trustworthy: without ties a read that ties between alleles
 goes to whichever row comes first, and tying alleles normally share a group.  The groups' tie columns stay whole-sample figures.
 
+And a single allele's, variant's or family member's?  The figure to trust there is rpkg_shared, the column that splits a tied read evenly.  With
+bootstrap_ties (Engine.set_tie_bootstrap; csrc/mc_tieboot.h states the rule; needs bootstrap and ties) replicate b of a gene's shared reads is
+the sum over the reads it ties for of weight(b, read) x 1 / k - the same weights, so the same resample as replicate b of the counts and of the
+genome equivalents - and the gene table gets rpkg_shared_boot_se, rpkg_shared_ci95_low and rpkg_shared_ci95_high behind every other column.  The
+device keeps one entry per (read, tied gene) in a list of tie_list_factor (default 4, 1 .. 500) times the gene bootstrap's list, at most 2^27
+entries; a run whose tied sets do not fit is refused and told the factor that fits.  For a gene none of whose reads tie the three columns are
+rpkg's, bit for bit.  candidate_reads, unique_reads, the any-coverage columns and the groups table's tie columns are not bootstrapped.
+
 Reads of mixed lengths (mixed_lengths; README "Reads of mixed lengths"): one trimmed length drops every shorter read and the tail of
 every longer one.  Under the switch every read is searched and counted at the largest length class L_k it reaches
 (Engine.set_abundance_classes; csrc/k_abund_classes.h states the rule), and the denominator is that of the bases so sampled:
@@ -94,6 +102,10 @@ TIES_COLUMNS = ("unique_reads", "candidate_reads", "shared_reads", "rpkg_shared"
 TIES_COVERAGE_COLUMNS = ("covered_any_aa", "breadth_any")                            # ... these behind them with coverage, "detected_any" last with min_breadth
 GROUP_TIES_COLUMNS = ("unique_reads", "shared_reads", "rpkg_shared")                 # behind the groups table's columns; "genes_detected_any" last with min_breadth
 CURVE_COLUMNS = ("sampled_reads", "average_genome_size", "genome_equivalents_sampled", "reads_assigned", "genes_with_reads")   # "genes_detected" behind them with min_breadth, "groups_with_reads" with groups
+TIE_BOOT_COLUMNS = ("rpkg_shared_boot_se", "rpkg_shared_ci95_low", "rpkg_shared_ci95_high")   # behind every other column with bootstrap_ties
+MAX_TIE_LIST = 1 << 27                                                               # MC_TB_MAXCAP (csrc/mc_tieboot.h): the most entries the tie list holds
+MAX_TIE_FACTOR = 500                                                                 # MC_MAX_M8 (csrc/mc_core.h): no read ties across more genes
+TIE_FACTOR = 4                                                                       # tie_list_factor's default
 BOOT_COLUMNS = ("rpkg_boot_se", "rpkg_ci95_low", "rpkg_ci95_high")                  # behind all of them with bootstrap; behind the groups table's with bootstrap_groups
 MAX_BOOT = 4096                                                                      # MC_GB_MAXB (csrc/mc_geneboot.h)
 MAX_CURVE = 64                                                                       # MC_CURVE_MAXK (csrc/mc_curve.h)
@@ -460,7 +472,8 @@ def table_columns(table):
     """[(column, kind)] of the gene table, from the keys the table has - kind s: the value as it is, d: %d, f: repr(float()), n: f or NA"""
     has = lambda key: table.get(key) is not None
     groups = ((True, COLUMNS, "sdddf"), (has("covered_aa"), COVERAGE_COLUMNS, "dffd"), (has("detected"), ("detected",), "d"), (has("unique_reads"), TIES_COLUMNS, "ddff"),
-              (has("covered_any_aa"), TIES_COVERAGE_COLUMNS, "df"), (has("detected_any"), ("detected_any",), "d"), (has("rpkg_boot_se"), BOOT_COLUMNS, "fff"))
+              (has("covered_any_aa"), TIES_COVERAGE_COLUMNS, "df"), (has("detected_any"), ("detected_any",), "d"), (has("rpkg_boot_se"), BOOT_COLUMNS, "fff"),
+              (has("rpkg_shared_boot_se"), TIE_BOOT_COLUMNS, "fff"))
     return [c for on, names, kinds in groups if on for c in zip(names, kinds)]
 
 
@@ -491,6 +504,8 @@ def write_table(path, args, table):
         out.writelines(header_lines(args, table))
         if table.get("rpkg_boot_se") is not None:
             out.writelines(boot_header_lines(table))
+        if table.get("rpkg_shared_boot_se") is not None:
+            out.writelines(["# bootstrap_ties:\ton\n", "# tie_list:\t%d/%d\n" % (table["tie_list_entries"], table["tie_list_capacity"])])
         columns = table_columns(table)
         _write_rows(out, columns, [table[name] for name, _ in columns])
 
@@ -598,7 +613,8 @@ def check_request(args):
         raise AbundanceError("Gene abundances are not computed by a distributed run (WORLD_SIZE %s): run one process" % os.environ.get("WORLD_SIZE", "1"))
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
                          ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
-                         ("bootstrap", None), ("bootstrap_seed", None), ("bootstrap_groups", False), ("mixed_lengths", None), ("long_genes", False)):
+                         ("bootstrap", None), ("bootstrap_seed", None), ("bootstrap_groups", False), ("mixed_lengths", None), ("long_genes", False),
+                         ("bootstrap_ties", False), ("tie_list_factor", None)):
         args.setdefault(key, default)
     mixed = microbe_census.mixed_lengths_on(args)
     if mixed:
@@ -646,6 +662,16 @@ def check_request(args):
             raise AbundanceError("--depth-out %r is an empty path" % (args["depth_out"],))
         _check_own_path(args, "depth_out", ("", ".groups.tsv"))
     _check_switch(args, "ties")
+    _check_switch(args, "bootstrap_ties")
+    if args["bootstrap_ties"]:
+        if args["bootstrap"] is None:
+            raise AbundanceError("--bootstrap-ties needs --bootstrap B (--bootstrap %s): it sums the gene bootstrap's weights over every gene's tied reads" % (args["bootstrap"],))
+        if not args["ties"]:
+            raise AbundanceError("--bootstrap-ties needs --ties (--ties %s): it bootstraps rpkg_shared" % (args["ties"],))
+    if args["tie_list_factor"] is not None:
+        if not args["bootstrap_ties"]:
+            raise AbundanceError("--tie-list-factor %s needs --bootstrap-ties: it sizes the list of tie entries" % (args["tie_list_factor"],))
+        _check_int(args, "tie_list_factor", 1, MAX_TIE_FACTOR, "1 to %d" % MAX_TIE_FACTOR)
     args["coverage"] = bool(args["coverage"]) or args["min_breadth"] is not None or args["depth_out"] is not None
     if args["ags"] is not None and args["ags_report"] is not None:
         raise AbundanceError("--ags %s and --ags-report %s cannot be combined: one AGS" % (args["ags"], args["ags_report"]))
@@ -721,13 +747,33 @@ def _set_switches(eng, args, sample, names, group_of):
     return gids, gnames
 
 
+def tie_list_capacity(gene_capacity, factor):
+    """the entries of the tie list: min(2^27, factor x the gene list's capacity), factor None: the default"""
+    return min(MAX_TIE_LIST, int(TIE_FACTOR if factor is None else factor) * int(gene_capacity))
+
+
+def tie_list_overflow(dropped, candidates_sum, gene_capacity, factor):
+    """the refusal of a run whose tied sets did not fit the tie list: the entries dropped and the smallest factor that would have fitted,
+    ceil(sum(candidates) / the gene list's capacity)"""
+    fits = -(-int(candidates_sum) // max(int(gene_capacity), 1))
+    return AbundanceError("--bootstrap-ties: %d tie entries did not fit the list of %d (--tie-list-factor %d x %d reads): --tie-list-factor %d fits all %d"
+                          % (dropped, tie_list_capacity(gene_capacity, factor), TIE_FACTOR if factor is None else factor, gene_capacity, fits, candidates_sum))
+
+
+def _size_lists(eng, args, n):
+    """the gene bootstrap's list of n reads and, with bootstrap_ties, the tie list behind it: one moment, one count"""
+    eng.set_gene_bootstrap(n)
+    if args["bootstrap_ties"] and n:
+        eng.set_tie_bootstrap(tie_list_capacity(n, args["tie_list_factor"]))
+
+
 def _search_once(eng, rd, args, sample):
     """The one search of a run - no m8 row reaches the host; returns (cu, points): Engine.curve() and the curve's points, or None twice.
     The bootstrap's list of read ids is sized before the search: by -n, the sampler sampling beside the search, or - no cap - by the reads the
     sampler takes; the curve's points depend on that number too: there it runs to its end first, and no read taken means no search."""
     B, cap = args["bootstrap"], sample["pargs"]["nreads"]
     if B and cap is not None:
-        eng.set_gene_bootstrap(int(cap))
+        _size_lists(eng, args, int(cap))
     if not args["curve"] and not (B and cap is None):
         eng.search_files(rd, keep_rows=False)
         return None, None
@@ -736,7 +782,7 @@ def _search_once(eng, rd, args, sample):
         return None, None
     points = microbe_census.curve_points(n, args["curve"]) if args["curve"] else None
     if points is None:
-        eng.set_gene_bootstrap(n)
+        _size_lists(eng, args, n)
     else:
         eng.set_curve(points)
     (eng.search if sample["classes"] is None else eng.search_classes)(rd.reads(n), keep_rows=False)
@@ -763,7 +809,7 @@ def device_pass(args, sample, names, seqs, group_of):
     try:                        # (long_genes: the engine on the segments, with the genes' statistics)
         db = {"names": names, "seqs": seqs} if fold is None else {"names": fold["seg_names"], "seqs": fold["seg_seqs"], "stats": fold["stats"]}
         eng = _native.Engine(device=int(args.get("device") or 0), marker_family=[0] * len(db["names"]), nfam=1, **db)
-        c = dict.fromkeys(("ac", "gb", "gbg", "scale"))
+        c = dict.fromkeys(("ac", "gb", "gbg", "scale", "tb"))
         c["gids"], c["gnames"] = _set_switches(eng, args, sample, names, group_of)
         try:
             c["cu"], c["points"] = _search_once(eng, rd, args, sample)
@@ -786,6 +832,15 @@ def device_pass(args, sample, names, seqs, group_of):
                 except RuntimeError as e:
                     raise AbundanceError(str(e))
                 c["group_bootstrap_ms"] = eng.group_bootstrap_ms()
+            if args["bootstrap_ties"]:                              # the same replicates and scales on the shares of every tied set
+                glist = eng.gene_bootstrap_capacity
+                total, cap_t = int(eng.ties()["candidates"].sum()), tie_list_capacity(glist, args["tie_list_factor"])      # (the tie table knows the sum whether or not the list held it)
+                try:
+                    c["tb"] = eng.tie_bootstrap(args["bootstrap"], args["bootstrap_seed"] or 0, c["scale"])
+                except RuntimeError as e:
+                    raise tie_list_overflow(total - cap_t, total, glist, args["tie_list_factor"]) if total > cap_t else AbundanceError(str(e))
+                c["tie_list"] = (total, cap_t)
+                c["tie_bootstrap_ms"] = eng.tie_bootstrap_ms()
         c["cov"] = eng.coverage() if args["coverage"] else None
         c["depth"] = eng.coverage_depth() if args["depth_out"] is not None else None
         c["ti"] = eng.ties() if args["ties"] else None
@@ -862,6 +917,11 @@ def build_table(args, sample, counts, names, seqs, group_of):
                       "bootstrap": args["bootstrap"], "bootstrap_seed": args["bootstrap_seed"] or 0, "bootstrap_denominator": "replicate_ags" if est else "fixed_ags"})
     if group_of is not None:
         table["groups"] = group_table(names, table["reads"], table["rpkg"], group_of, table.get("detected"))
+    tb = counts.get("tb")                                          # (a record from before the switch has no such key)
+    if tb is not None:
+        se, lo, hi = boot_columns(tb["stats"], tb["used"], length_aa)
+        table.update({"rpkg_shared_boot_se": se, "rpkg_shared_ci95_low": lo, "rpkg_shared_ci95_high": hi, "tie_boot_stats": tb["stats"], "tie_boot_used": tb["used"],
+                      "tie_list_entries": counts["tie_list"][0], "tie_list_capacity": counts["tie_list"][1]})
     gbg = counts.get("gbg")                                        # (a record from before the switch has no such key)
     if gbg is not None:                                             # (group_ids numbers the groups in group_table's order)
         table.update({"groups_boot": list(zip(*(col.tolist() for col in group_boot_columns(gbg["stats"], gbg["used"])))), "groups_boot_stats": gbg["stats"]})
@@ -899,7 +959,9 @@ def run_abundance(args):
     all off by default: coverage, min_breadth and depth_out (a path; both imply coverage), ties, curve (K, 1 .. 64: table['curve']; writes
     <outfile>.curve.tsv) with curve_genes (a path: the curve's per-gene matrix), bootstrap (B, 1 .. 4096) with bootstrap_seed (default 0; not
     combined with curve) and bootstrap_groups (needs bootstrap and groups: table['groups_boot'], one (se, low, high) per row of table['groups'],
-    table['groups_boot_stats'], and the three columns behind every column of <outfile>.groups.tsv), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
+    table['groups_boot_stats'], and the three columns behind every column of <outfile>.groups.tsv) and bootstrap_ties (needs bootstrap and ties:
+    rpkg_shared_boot_se, rpkg_shared_ci95_low, rpkg_shared_ci95_high behind every column of the gene table, table['tie_boot_stats'] and
+    table['tie_boot_used']; tie_list_factor, 1 .. 500, default 4, sizes its list; leaves args['tie_bootstrap_ms']), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
     given AGS), long_genes (genes of up to 65,535 residues; table['long_genes'] = {genes_split, segments, edge_rows}).  Four stages with two
     records between them - DESIGN.md 13, "How a run is laid out on the host".  Writes args['outfile'] (and <outfile>.groups.tsv with groups)
     when it is set; leaves in args the sampler's options as imputed, sampled_reads, search_ms and the *_ms of every switch that ran; returns

@@ -1,16 +1,18 @@
 // mc_abund.h - the one owner of the per-gene counts (mc_set_abundance), the coverage depth (mc_set_coverage), the tie accounting
-// (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap) and the counts on class runs
-// (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
+// (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap), the bootstrap of the tie
+// shares (mc_set_tie_bootstrap) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
 // With a gene fold (mc_set_gene_fold, mc_fold.h) it also owns the fold of a range's rows from segments onto genes (k_fold.h), in front of everything else.
-// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_groupboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
+// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_groupboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
 // hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end
-// (device_groupboot.hip also through mc_groupboot_launch, like the group bootstrap's read).
+// (device_groupboot.hip also through mc_groupboot_launch, like the group bootstrap's read; device_tieboot.hip through mc_abund_launch and
+// mc_tieboot_launch, like the tie bootstrap's read).
 #pragma once
 #include "k_abundance.h"
 #include "k_coverage.h"
 #include "k_ties.h"
 #include "k_curve.h"
 #include "k_geneboot.h"
+#include "k_tieboot.h"
 #include "k_groupboot.h"
 #include "k_abund_classes.h"
 #include "k_fold.h"
@@ -43,6 +45,9 @@ struct McCurveBufs { int32_t K; const unsigned long long *pts; unsigned long lon
 struct McGeneBootBufs { McGbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
 // the class ride of a launch (null: the rows are no piece of a class run).  map: the ids of the batch (k_geneboot.h); tab: the per-class
 // table of K classes (k_abund_classes.h); k, nreads: the piece's class and reads; ev: recorded behind k_abund_class_add
+// the tie bootstrap's part of a launch (null: it is off).  list: `capacity` entries; cur: the cursor and `dropped` (k_tieboot.h); ev:
+// recorded behind k_tieboot_collect
+struct McTieBootBufs { McTbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
 struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigned long long nreads; hipEvent_t ev; };
 
 // The kernels of a range's final rows (ascending read id), in `st`: the counting kernel - k_abundance_cov INSTEAD of k_abundance while
@@ -53,8 +58,10 @@ struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigne
 // With a class ride (R not null: the rows are a piece of a class run, mc_set_abundance_classes) k_geneboot_collect_mapped runs INSTEAD of
 // k_geneboot_collect and takes every id through R->map, and k_abund_class_add runs behind everything, with nr == 0 too (a piece without
 // rows has reads), and R->ev behind it.  Without one (R null) nothing more is issued and the kernels are the fixed-length runs'.
+// With the tie bootstrap (T not null) k_tieboot_collect runs behind the gene bootstrap's kernel on the same rows - with a class ride it
+// takes every id through R->map, without one the map it is handed has a null perm - and T->ev behind it; without it (T null) nothing.
 static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McRow *rows, uint32_t nr, hipStream_t st, const hipEvent_t (&ev)[3], const McCurveBufs *C = nullptr,
-                           const McGeneBootBufs *G = nullptr, const McClassRide *R = nullptr)
+                           const McGeneBootBufs *G = nullptr, const McClassRide *R = nullptr, const McTieBootBufs *T = nullptr)
 {
     const dim3 grid((nr + 255) / 256), block(256);
     HIPCK(hipEventRecord(ev[0], st));
@@ -74,6 +81,11 @@ static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McR
         if (nr && R) k_geneboot_collect_mapped<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, G->list, G->capacity, G->cur, R->map);
         else if (nr) k_geneboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, G->list, G->capacity, G->cur);
         HIPCK(hipEventRecord(G->ev, st));
+    }
+    if (T) {
+        const McIdMap own = {nullptr, 0};
+        if (nr) k_tieboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, T->list, T->capacity, T->cur, R ? R->map : own);
+        HIPCK(hipEventRecord(T->ev, st));
     }
     if (!R) return 0;
     k_abund_class_add<<<dim3(1), dim3(64), 0, st>>>(R->tab, R->K, R->k, R->nreads, B.counts + mc_pair_at((size_t)B.nseq));
@@ -109,6 +121,27 @@ static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hip
     return 0;
 }
 
+// The tie bootstrap's read: raw device pointers of one mc_tie_bootstrap, McGeneBootRead on the other entry.  list: the n collected entries;
+// cursor, idx: made by mc_gb_plan from the TIE table on the host (its pairs hold `candidates` where the count table holds `reads`);
+// sorted: n entries; mat: ngenes x B shares in units of 2^-32, zeroed; s32: B doubles, scale x 2^-32 (mc_tb_scale), m of them used
+struct McTieBootRead { int32_t nseq, ngenes; long long n; const McTbEntry *list; uint32_t *cursor; const int32_t *idx; McTbEntry *sorted; unsigned long long *mat;
+                       const double *s32; int32_t B, m; uint64_t seed; double *out; };
+// The three kernels of a read between ev[0] and ev[1], in `st`: the scatter and the sums with n > 0, k_geneboot_summary - the gene
+// bootstrap's own kernel, on this matrix and these scales - with ngenes > 0
+static int mc_tieboot_launch(const McTieBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
+{
+    HIPCK(hipEventRecord(ev[0], st));
+    if (R.n > 0) {
+        k_tieboot_scatter<<<dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st>>>(R.list, R.n, R.nseq, R.cursor, R.idx, R.sorted);
+        const long long per = mc_gb_per_tile(R.n, R.B);
+        k_tieboot_sums<<<dim3((unsigned)((R.n + per - 1) / per), (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.n, per, R.B, R.seed, (uint32_t)R.ngenes, R.mat);
+    }
+    if (R.ngenes > 0) k_geneboot_summary<<<dim3((unsigned)R.ngenes), dim3(MC_GB_THREADS), 0, st>>>(R.mat, R.s32, R.B, R.m, R.out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(ev[1], st));
+    return 0;
+}
+
 // The group bootstrap's read (mc_groupboot.h): raw device pointers of one mc_group_bootstrap, behind a read that left mat.  mat: ngenes x B
 // replicate counts; start, member, kb: the CSR of the ngrp groups with reads, made by mc_grb_plan on the host; val: ngrp x B doubles;
 // cnt: ngrp x B counts, or null; scale: B doubles, m of them used; out: ngrp x 6 doubles
@@ -127,7 +160,7 @@ static int mc_groupboot_launch(const McGroupBootRead &R, hipStream_t st, const h
 }
 
 // ---- Owner --------------------------------------------------------------------------------------------------------------------
-// The six switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
+// The seven switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
 //     the difference array, the scan's output, its two events                    coverage is on
 //     the tie table, its event                                                   ties are on
@@ -139,12 +172,16 @@ static int mc_groupboot_launch(const McGroupBootRead &R, hipStream_t st, const h
 //     the genes' cursors and compact indices, the scales, the output, its three events   the gene bootstrap is on
 //     the bootstrap's matrix of replicate counts                                  the gene bootstrap is on and a read has sized it
 //     the group bootstrap's CSR, gene_kb, output and its three events; its values and counts   the gene bootstrap is on and a group read has sized them
+//     the tie bootstrap's list, its cursor and dropped counter, the grouped list,
+//     the genes' cursors and compact indices, the scales, the output, its three events   the tie bootstrap is on
+//     the tie bootstrap's matrix of replicate shares                              the tie bootstrap is on and a read has sized it
 //     the per-class table (k_abund_classes.h), its event                          the counts may ride on class runs
 //     the segment records, the genes' offsets, the edge counter, its two events   a gene fold is set (set_fold; with the counts on or off)
 //     the folded rows                                                             a gene fold is set and a range has sized them (launch grows them)
-// Coverage, ties, the curve, the gene bootstrap and the class ride are on only while the counts are.  Every switch that goes on, and reset(), zeroes ALL
-// counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the bootstrap's cursor and dropped counter
-// (an empty list), the per-class table, `searched` and the times: counts, depth, ties, curve, bootstrap and classes describe the same reads.  A switch that goes off
+// Coverage, ties, the curve, the gene bootstrap and the class ride are on only while the counts are; the tie bootstrap only while ties AND the gene
+// bootstrap are (either going off, or being set anew, takes it with it).  Every switch that goes on, and reset(), zeroes ALL
+// counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the cursor and dropped counter of both bootstraps
+// (empty lists), the per-class table, `searched` and the times: counts, depth, ties, curve, bootstrap and classes describe the same reads.  A switch that goes off
 // frees its buffers and zeroes nothing of the others; the counts going off take the other five with them.
 struct McAbundance {
     int32_t nseq = 0; size_t nres = 0; const uint32_t *off = nullptr;   // the database: bind(), once the index is on the device
@@ -161,6 +198,12 @@ struct McAbundance {
     // what d_gmat holds, so that a group read may take it over from the read before it: the replicates, the seed and the entries of the read that
     // made it; gmat_n < 0: nothing - no read yet, or a range, a reset or a switch since (launch, reset, fit)
     int32_t gmat_B = 0; uint64_t gmat_seed = 0; long long gmat_n = -1;
+    // the tie bootstrap (mc_tieboot.h): the switch, the list's capacity, and the gene bootstrap's set of buffers once more on the other entry
+    bool tboot = false; int64_t tcap = 0;
+    McDev<McTbEntry> d_tlist, d_tsorted; McDev<unsigned long long> d_tcur, d_tmat; McDev<uint32_t> d_tcursor; McDev<int32_t> d_tidx; McDev<double> d_tscale, d_tout;
+    size_t tmat_slots = 0;                                         // what d_tmat holds: a read grows it to ngenes x B
+    McEvent ev_tboot, ev_tread[2];                                 // behind k_tieboot_collect; around the kernels of a read
+    float tboot_ms = 0, tread_ms = 0;                              // k_tieboot_collect's, the reads' time since the last zeroing
     // the group bootstrap (mc_groupboot.h): the CSR of the groups with reads, the members' gene_kb, the replicate values and counts, the output
     McDev<uint32_t> d_grstart, d_grmember; McDev<double> d_grkb, d_grval, d_grout; McDev<unsigned long long> d_grcnt;
     size_t grval_slots = 0, grcnt_slots = 0;                       // what d_grval, d_grcnt hold: a group read grows them to ngrp x B
@@ -212,6 +255,14 @@ struct McAbundance {
         gcap = capacity;
         return turn(gboot, true);
     }
+    // capacity: entries of the tie list, checked by the caller (mc_set_tie_bootstrap: ties and the gene bootstrap are on); 0: off.  On while on: a list of another size
+    int set_tie_bootstrap(int64_t capacity)
+    {
+        (void)turn(tboot, false);
+        if (capacity == 0) return 0;
+        tcap = capacity;
+        return turn(tboot, true);
+    }
     // on: refused by the caller while the curve is on (mc_set_abundance_classes)
     int set_classes(bool to) { return turn(classes, to); }
     // The gene fold: seg: ix_nseq records, goff: ngenes + 1 offsets of the genes' residues (both checked and made by the caller,
@@ -248,10 +299,11 @@ struct McAbundance {
         if (d_bins) HIPCK(hipMemset(d_bins, 0, sizeof(unsigned long long) * mc_curve_bin_slots((size_t)K, (size_t)nseq)));
         if (d_first) HIPCK(hipMemset(d_first, 0xFF, sizeof(uint32_t) * nres));
         if (d_gcur) HIPCK(hipMemset(d_gcur, 0, sizeof(unsigned long long) * 2));
+        if (d_tcur) HIPCK(hipMemset(d_tcur, 0, sizeof(unsigned long long) * 2));
         if (d_cls) HIPCK(hipMemset(d_cls, 0, sizeof(unsigned long long) * MC_AC_SLOTS));
         if (d_edge) HIPCK(hipMemset(d_edge, 0, sizeof(unsigned long long)));
         fold_ms = 0.f;
-        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = 0.f;
+        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = tboot_ms = tread_ms = 0.f;
         gmat_n = -1; grp_ms = grp_values_ms = grp_summary_ms = 0.f;
         return 0;
     }
@@ -275,7 +327,8 @@ struct McAbundance {
         const McCurveBufs C = {K, d_pts, d_bins, d_first, ev_curve};
         const McGeneBootBufs G = {d_glist, (unsigned long long)gcap, d_gcur, ev_gboot};
         const McClassRide R = {map, d_cls, map_K, piece_k, (unsigned long long)nreads, ev_cls};
-        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr);
+        const McTieBootBufs T = {d_tlist, (unsigned long long)tcap, d_tcur, ev_tboot};
+        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr, tboot ? &T : nullptr);
     }
     // ---- a batch of a class run under the switch (classes_batch): perm: the row index of every sorted position, on the device, for as
     // long as the pieces run; base: the batch's first read id; K_: its classes.  ride_piece: the class of the piece whose range ends next.
@@ -306,7 +359,8 @@ struct McAbundance {
         if (ties) ties_ms += ev_ms(ev_count[1], ev_ties);
         if (curve) curve_ms += ev_ms(ties ? ev_ties : ev_count[1], ev_curve);
         if (gboot) gboot_ms += ev_ms(curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_gboot);
-        if (riding()) cls_ms += ev_ms(gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
+        if (tboot) tboot_ms += ev_ms(ev_gboot, ev_tboot);          // (on only with the gene bootstrap)
+        if (riding()) cls_ms += ev_ms(tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
     }
     void add_searched(int64_t nreads) { if (on) searched += nreads; }   // (mc_search_varlen: reads too short to have a frame are searched, and have no rows)
 
@@ -375,6 +429,50 @@ struct McAbundance {
         if (need) HIPCK(hipMemcpy(mat.data(), d_gmat, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         for (size_t s = 0; s < ns; s++)
             for (size_t b = 0; b < (size_t)B; b++) counts[s * (size_t)B + b] = idx[s] >= 0 ? (int64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
+        return 0;
+    }
+    // The bootstrap of the tie shares as they stand (mc_tieboot.h): read_gene_bootstrap's contract on the other list.  shares (or null): nseq x B
+    // replicate shares in units of 2^-32; stats: nseq x 6 doubles of the values share x scale x 2^-32; dropped: the entries that did not fit the
+    // list - not zero: an error that names it, and nothing else is computed.
+    int read_tie_bootstrap(int32_t B, uint64_t seed, const double *scale, uint64_t *shares, double *stats, int64_t *dropped)
+    {
+        const size_t ns = (size_t)nseq;
+        unsigned long long cur[2];
+        HIPCK(hipMemcpy(cur, d_tcur, sizeof cur, hipMemcpyDeviceToHost));
+        if (dropped) *dropped = (int64_t)cur[1];
+        if (cur[1] || cur[0] > (unsigned long long)tcap) {
+            g_err = "mc_tie_bootstrap: " + std::to_string(cur[1]) + " entries did not fit the list of " + std::to_string(tcap) + " entries (mc_set_tie_bootstrap): dropped, no replicate is whole";
+            return -1;
+        }
+        std::vector<unsigned long long> tab(mc_pair_slots(ns));      // (the head of the tie table: candidates where the count table has reads)
+        HIPCK(hipMemcpy(tab.data(), d_ties, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> start(ns); std::vector<int32_t> idx(ns);
+        unsigned long long total = 0;
+        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
+        if (total != cur[0]) { g_err = "mc_tie_bootstrap: the tie table holds " + std::to_string(total) + " candidates, the list " + std::to_string(cur[0]) + " entries"; return -1; }
+        std::vector<double> s32((size_t)B);
+        int32_t m = 0;
+        for (int32_t b = 0; b < B; b++) { s32[(size_t)b] = mc_tb_scale(scale[b]); m += mc_gb_used(s32[(size_t)b]) ? 1 : 0; }
+        const size_t need = (size_t)ng * (size_t)B;
+        if (need > tmat_slots) { tmat_slots = 0; if (d_tmat.alloc(need)) return -1; tmat_slots = need; }
+        HIPCK(hipMemcpy(d_tscale, s32.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_tcursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_tidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
+        if (need) HIPCK(hipMemsetAsync(d_tmat, 0, sizeof(unsigned long long) * need, 0));
+        const McTieBootRead R = {nseq, ng, (long long)cur[0], d_tlist, d_tcursor, d_tidx, d_tsorted, d_tmat, d_tscale, B, m, seed, d_tout};
+        const hipEvent_t ev[2] = {ev_tread[0], ev_tread[1]};
+        if (mc_tieboot_launch(R, 0, ev)) return -1;
+        HIPCK(hipEventSynchronize(ev_tread[1]));
+        tread_ms += ev_ms(ev_tread[0], ev_tread[1]);
+        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
+        if (ng) HIPCK(hipMemcpy(out.data(), d_tout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; s++)                            // (a gene without candidates: zero in every replicate)
+            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * s + k] = idx[s] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)idx[s] + k] : m ? 0.0 : mc_gb_nan();
+        if (!shares) return 0;
+        std::vector<unsigned long long> mat(need);
+        if (need) HIPCK(hipMemcpy(mat.data(), d_tmat, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; s++)
+            for (size_t b = 0; b < (size_t)B; b++) shares[s * (size_t)B + b] = idx[s] >= 0 ? (uint64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
         return 0;
     }
     // The bootstrap of the GROUPS (mc_groupboot.h) on the counts as they stand: group_of: nseq groups below ngroups_, gene_kb: nseq doubles, all
@@ -476,6 +574,8 @@ private:
     int fit()
     {
         if (!on) { cov = ties = curve = gboot = classes = false; searched = 0; ms = 0.f; }
+        if (!ties || !gboot) tboot = false;
+        if (!tboot) { tcap = 0; tboot_ms = tread_ms = 0.f; d_tmat.reset(); tmat_slots = 0; }
         if (!classes) { cls_ms = 0.f; ride_end(); }
         if (!cov) cov_ms = 0.f;
         if (!ties) { ngroups = 0; ties_ms = 0.f; }
@@ -494,6 +594,8 @@ private:
                fit_one(ev_curve, curve) || fit_one(ev_cscan[0], curve) || fit_one(ev_cscan[1], curve) || fit_one(d_first, curve && cov, nres) ||
                fit_one(d_glist, gboot, (size_t)gcap) || fit_one(d_gsorted, gboot, (size_t)gcap) || fit_one(d_gcur, gboot, 2) || fit_one(d_gcursor, gboot, ns) || fit_one(d_gidx, gboot, ns) ||
                fit_one(d_gscale, gboot, MC_GB_MAXB) || fit_one(d_gout, gboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_gboot, gboot) || fit_one(ev_gread[0], gboot) || fit_one(ev_gread[1], gboot) ||
+               fit_one(d_tlist, tboot, (size_t)tcap) || fit_one(d_tsorted, tboot, (size_t)tcap) || fit_one(d_tcur, tboot, 2) || fit_one(d_tcursor, tboot, ns) || fit_one(d_tidx, tboot, ns) ||
+               fit_one(d_tscale, tboot, MC_GB_MAXB) || fit_one(d_tout, tboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_tboot, tboot) || fit_one(ev_tread[0], tboot) || fit_one(ev_tread[1], tboot) ||
                fit_one(d_cls, classes, MC_AC_SLOTS) || fit_one(ev_cls, classes);
     }
     // one switch to `to`.  A switch whose buffers cannot be had ends off and leaves the others as they were (freeing cannot fail).

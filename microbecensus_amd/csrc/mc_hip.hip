@@ -19,6 +19,7 @@
 //   k_coverage.h           per-gene coverage breadth and depth beside them: marks in the counting kernel, a scan at read time (mc_set_coverage)
 //   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
 //   k_curve.h              the rarefaction curve beside them: per-gene counts per prefix of the sample, every residue's first read, a scan at read time (mc_set_curve)
+//   k_tieboot.h            the bootstrap of the tie shares beside both: a device list of (read id, gene, share), per-gene replicate sums at read time (mc_set_tie_bootstrap)
 //   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
 //   k_groupboot.h          the bootstrap of the groups table behind it: every group's replicate values walked over its members' rows of the replicate sums, sort and summary (mc_group_bootstrap)
 //   k_abund_classes.h      the per-class table of the counts on class runs (mc_set_abundance_classes)
@@ -1425,6 +1426,7 @@ extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_
     if (nreads > 0x7fffffff) { g_err = "more than 2^31 - 1 reads in one call"; return -1; }
     if (h->pipe_nout) { g_err = "ranges begun with mc_range_begin() are still in flight"; return -1; }
     if (h->ab.curve) { g_err = "mc_search_varlen: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
+    if (h->ab.tboot) { g_err = "mc_search_varlen: refused while the tie bootstrap is on (mc_set_tie_bootstrap, capacity = " + std::to_string(h->ab.tcap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     if (h->ab.gboot) { g_err = "mc_search_varlen: refused while the gene bootstrap is on (mc_set_gene_bootstrap, capacity = " + std::to_string(h->ab.gcap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     bool one = true;
     for (int64_t i = 0; i < nreads; i++) {
@@ -2120,6 +2122,32 @@ extern "C" int mc_group_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const 
     return h->ab.read_group_bootstrap(B, seed, scale, group_of, ngroups, gene_kb, counts, stats, dropped);
 }
 
+// the bootstrap of the tie shares (mc_tieboot.h; it extends mc_set_gene_bootstrap from the counts to the shares of mc_set_ties): a list of
+// `capacity` entries turns it on and zeroes every counter; capacity == 0 turns it off
+extern "C" int mc_set_tie_bootstrap(mc_handle *h, int64_t capacity)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_tie_bootstrap: a range begun with mc_range_begin() is still in flight (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (capacity == 0) return h->ab.set_tie_bootstrap(0);
+    if (capacity < 0 || capacity > (int64_t)MC_TB_MAXCAP) { g_err = "mc_set_tie_bootstrap: capacity " + std::to_string(capacity) + " is not a number of entries from 0 to 2^27"; return -1; }
+    if (!h->ab.ties) { g_err = "mc_set_tie_bootstrap: ties are off (mc_set_ties) - the entries are the tied sets it counts (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    if (!h->ab.gboot) { g_err = "mc_set_tie_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap) - the replicates are its replicates (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    return h->ab.set_tie_bootstrap(capacity);
+}
+
+// shares (or NULL): nseq x B replicate shares in units of 2^-32; stats: nseq x 6 doubles (mc_tieboot.h); dropped: the entries that did not fit
+extern "C" int mc_tie_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale, uint64_t *shares, double *stats, int64_t *dropped)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.tboot) { g_err = "mc_tie_bootstrap: the tie bootstrap is off (mc_set_tie_bootstrap)"; return -1; }
+    if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_tie_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
+    if (!scale || !stats) { g_err = "mc_tie_bootstrap: B = " + std::to_string(B) + " and a NULL scale or stats array"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_tie_bootstrap: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_tie_bootstrap(B, seed, scale, shares, stats, dropped);
+}
+
 // the counts on class runs: mc_search_classes and mc_search_files on a class reader are no longer refused, every piece adds to the
 // counts and to the per-class table (k_abund_classes.h), and the gene bootstrap takes the read ids through the batch's id map
 extern "C" int mc_set_abundance_classes(mc_handle *h, int on)
@@ -2219,6 +2247,13 @@ extern "C" float mc_abundance_classes_ms(const mc_handle *h) { return h ? h->ab.
 
 // k_geneboot_collect's time over the completed ranges plus the reads' kernels, since the last zeroing
 extern "C" float mc_gene_bootstrap_ms(const mc_handle *h) { return h ? h->ab.gboot_ms + h->ab.gread_ms : 0.0f; }
+// k_tieboot_collect's time over the completed ranges plus the tie reads' kernels, since the last zeroing; the two parts (either may be NULL)
+extern "C" float mc_tie_bootstrap_ms(const mc_handle *h) { return h ? h->ab.tboot_ms + h->ab.tread_ms : 0.0f; }
+extern "C" void mc_tie_bootstrap_kernels_ms(const mc_handle *h, float *collect_ms, float *read_ms)
+{
+    if (collect_ms) *collect_ms = h ? h->ab.tboot_ms : 0.0f;
+    if (read_ms) *read_ms = h ? h->ab.tread_ms : 0.0f;
+}
 // the group reads' kernels since the last zeroing: k_groupboot_values and k_groupboot_summary, and the kernels of a mat a group read had to make
 extern "C" float mc_group_bootstrap_ms(const mc_handle *h) { return h ? h->ab.grp_ms : 0.0f; }
 // the two kernels' shares of it (either may be NULL)

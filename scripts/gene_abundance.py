@@ -51,6 +51,12 @@ def parse_arguments(argv=None):
     p.add_argument("--bootstrap-groups", dest="bootstrap_groups", action="store_true", default=False,
                    help="with --bootstrap and --groups: add rpkg_boot_se, rpkg_ci95_low and rpkg_ci95_high to <out>.groups.tsv, from the same replicates summed over every group's genes "
                         "(a group's error bar does not follow from its members': their replicates are correlated)")
+    p.add_argument("--bootstrap-ties", dest="bootstrap_ties", action="store_true", default=False,
+                   help="with --bootstrap and --ties: add rpkg_shared_boot_se, rpkg_shared_ci95_low and rpkg_shared_ci95_high behind every column of the gene table, from the same replicates "
+                        "on every gene's even share of the reads it ties for (the error bar of a single allele, variant or family member)")
+    p.add_argument("--tie-list-factor", dest="tie_list_factor", type=int, default=None, metavar="F",
+                   help="with --bootstrap-ties: the device keeps one entry per read and tied gene in a list of F times the sampled reads, at most 2^27 entries (1 - 500; default = 4); "
+                        "a run whose tied sets do not fit is refused and names the F that fits")
     p.add_argument("--mixed-lengths", dest="mixed_lengths", nargs="?", const=True, default=None, metavar="L1,L2,...",
                    type=lambda v: [int(x) for x in v.split(",")],
                    help="count every read at the largest of the model's read lengths it reaches, instead of cutting all reads to one length and dropping the shorter ones; "
