@@ -656,6 +656,33 @@ float mc_tie_bootstrap_ms(const mc_handle *h);
 /* Of those, the milliseconds of k_tieboot_collect and of the reads' kernels (as mc_group_bootstrap_kernels_ms; either pointer may be NULL). */
 void mc_tie_bootstrap_kernels_ms(const mc_handle *h, float *collect_ms, float *read_ms);
 
+/* ---- the bootstrap of the coverage columns: how much a breadth and a detection call hang on single reads ----------------------------
+ * csrc/mc_covboot.h states the rule.  While it is on every read that mc_set_abundance assigns also appends one entry - (global read id,
+ * subject, sstart, send of its best row), 12 bytes; a span that mc_set_coverage keeps out of the depth is stored as the empty span - to a
+ * device list of `capacity` entries: one more kernel behind the other bootstraps' of every range, on the same rows where they lie (behind
+ * the gene fold: in gene space).  An entry that does not fit adds 1 to `dropped` and writes nothing.  mc_set_coverage_bootstrap(h,
+ * capacity) makes the list and zeroes it AND every abundance counter, as the other switches do; capacity == 0 frees everything and restores
+ * the path without it exactly.  mc_set_abundance(off) and mc_set_coverage(off) also turn it off: set it behind them.  It needs neither
+ * mc_set_gene_bootstrap nor mc_set_ties.  mc_abundance_reset() also empties the list and zeroes mc_coverage_bootstrap_ms().
+ * Refused, with a message naming the value: capacity < 0 or > 2^31 - 1, the counts off, coverage off, a range in flight.  While it is on
+ * mc_search_varlen is refused, as under mc_set_gene_bootstrap. */
+int mc_set_coverage_bootstrap(mc_handle *h, int64_t capacity);
+/* B replicates (1 .. 4096) of the covered residues as they stand, under mc_bootstrap's weights: read q is present in replicate b when its
+ * weight under (seed, b) is > 0, and covered[s * B + b] (or NULL) is the number of residues of gene s that the best rows of its present
+ * reads cover - at most mc_coverage_read's covered[s], since a Poisson(1) resample leaves out about 37 % of the reads.  stats: the six
+ * doubles of mc_gene_bootstrap (sum, m2, x[lo], x[lo + 1], x[hi], x[hi + 1]) of those B values, in residues, every replicate used; zeros
+ * for a gene without reads.  need (or NULL): nseq values >= 1; detected (or NULL, only with need): detected[s] is the number of
+ * replicates with covered >= need[s].  dropped: the assigned reads that did not fit the list; when it is not zero the call returns an
+ * error that names the number and computes nothing.  Refused too: B outside 1 .. 4096, a need of 0, detected without need, the switch
+ * off, a range in flight. */
+int mc_coverage_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const uint32_t *need /* [nseq] or NULL */, int64_t *covered /* [nseq * B] or NULL */,
+                          double *stats /* [nseq * 6] */, int64_t *detected /* [nseq] or NULL */, int64_t *dropped);
+/* Milliseconds the coverage bootstrap's kernels took since the last reset (HIP events), as mc_gene_bootstrap_ms: one kernel per
+ * completed range plus three per mc_coverage_bootstrap. */
+float mc_coverage_bootstrap_ms(const mc_handle *h);
+/* Of those, the milliseconds of k_covboot_collect and of the reads' kernels (either pointer may be NULL). */
+void mc_coverage_bootstrap_kernels_ms(const mc_handle *h, float *collect_ms, float *read_ms);
+
 /* ---- the counts on class runs: gene abundances from reads of mixed lengths -------------------------------------------------------
  * README "Reads of mixed lengths": a class run searches every read at the largest length class it reaches.  With this switch on the
  * abundance counts ride on such a run: mc_search_classes and mc_search_files on a reader of length classes are no longer refused

@@ -255,6 +255,12 @@ def load_library():
     lib.mc_tie_bootstrap_ms.argtypes = [C.c_void_p]
     lib.mc_tie_bootstrap_kernels_ms.restype = None
     lib.mc_tie_bootstrap_kernels_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.mc_set_coverage_bootstrap.argtypes = [C.c_void_p, C.c_int64]
+    lib.mc_coverage_bootstrap.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.mc_coverage_bootstrap_ms.restype = C.c_float
+    lib.mc_coverage_bootstrap_ms.argtypes = [C.c_void_p]
+    lib.mc_coverage_bootstrap_kernels_ms.restype = None
+    lib.mc_coverage_bootstrap_kernels_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.mc_set_abundance_classes.argtypes = [C.c_void_p, C.c_int]
     lib.mc_abundance_classes_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.mc_abundance_classes_ms.restype = C.c_float
@@ -289,6 +295,7 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms",
                     "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms", "mc_group_bootstrap", "mc_group_bootstrap_ms", "mc_group_bootstrap_kernels_ms",
                     "mc_set_tie_bootstrap", "mc_tie_bootstrap", "mc_tie_bootstrap_ms", "mc_tie_bootstrap_kernels_ms",
+                    "mc_set_coverage_bootstrap", "mc_coverage_bootstrap", "mc_coverage_bootstrap_ms", "mc_coverage_bootstrap_kernels_ms",
                     "mc_set_abundance_classes", "mc_abundance_classes_read", "mc_abundance_classes_ms", "mc_open_stats", "mc_set_gene_fold", "mc_gene_fold_stats",
                     "mc_abundance_count", "mc_abundance_residues", "mc_debug_live"]
 
@@ -1179,6 +1186,46 @@ class Engine:
         """of tie_bootstrap_ms(), the share of k_tieboot_collect and of the reads' kernels: {"collect", "read"}"""
         c, r = C.c_float(0), C.c_float(0)
         self.lib.mc_tie_bootstrap_kernels_ms(self.h, C.byref(c), C.byref(r))
+        return {"collect": float(c.value), "read": float(r.value)}
+
+    def set_coverage_bootstrap(self, capacity):
+        """The bootstrap of the coverage columns (mc_set_coverage_bootstrap; csrc/mc_covboot.h states the rule): from now on every read that
+        set_abundance assigns is also kept as (global id, gene, sstart, send) in a device list of `capacity` entries - the most reads there may
+        be assigned before coverage_bootstrap() is called; 0 or None turns it off.  Turning it on zeroes the list AND every abundance counter.
+        Refused while set_abundance or set_coverage is off - and either of them turned off turns it off: call it behind them.  It needs
+        neither set_gene_bootstrap nor set_ties.  search_varlen is refused while it is on."""
+        self._check(self.lib.mc_set_coverage_bootstrap(self.h, int(capacity or 0)), "mc_set_coverage_bootstrap")
+
+    def coverage_bootstrap(self, B, seed, need=None, covered=False):
+        """B Poisson-bootstrap replicates of the covered residues as they stand (mc_coverage_bootstrap), under bootstrap()'s weights: a read is
+        present in replicate b when its weight is > 0.  {"stats": float64[nseq, 6] - sum, m2, x[lo], x[lo + 1], x[hi], x[hi + 1] of the B
+        values covered_b, in residues -, "dropped": 0}; with need (uint32[nseq], every one >= 1) "detected": int64[nseq], the replicates with
+        covered_b >= need; with covered=True "covered": int64[nseq, B].  Raises when a read did not fit the list (the message names how many)."""
+        B, n = int(B), self.abundance_count()
+        out = {"stats": np.zeros((n, 6), np.float64)}
+        nd = None
+        if need is not None:
+            nd = np.ascontiguousarray(need, dtype=np.uint32)
+            if nd.shape != (n,):
+                raise ValueError("need holds %d values, the database %d genes" % (nd.size, n))
+            out["detected"] = np.zeros(n, np.int64)
+        if covered:
+            out["covered"] = np.zeros((n, max(B, 0)), np.int64)
+        dropped = C.c_int64(0)
+        self._check(self.lib.mc_coverage_bootstrap(self.h, B, int(seed) & 0xFFFFFFFFFFFFFFFF, nd.ctypes.data_as(C.c_void_p) if nd is not None else None,
+                                                   out["covered"].ctypes.data_as(C.c_void_p) if covered else None, out["stats"].ctypes.data_as(C.c_void_p),
+                                                   out["detected"].ctypes.data_as(C.c_void_p) if nd is not None else None, C.byref(dropped)), "mc_coverage_bootstrap")
+        out["dropped"] = int(dropped.value)
+        return out
+
+    def coverage_bootstrap_ms(self):
+        """milliseconds the coverage bootstrap's kernels took since the last reset (HIP events): one kernel per range, three per coverage_bootstrap()"""
+        return float(self.lib.mc_coverage_bootstrap_ms(self.h))
+
+    def coverage_bootstrap_kernels_ms(self):
+        """of coverage_bootstrap_ms(), the share of k_covboot_collect and of the reads' kernels: {"collect", "read"}"""
+        c, r = C.c_float(0), C.c_float(0)
+        self.lib.mc_coverage_bootstrap_kernels_ms(self.h, C.byref(c), C.byref(r))
         return {"collect": float(c.value), "read": float(r.value)}
 
     def set_abundance_classes(self, on=True):

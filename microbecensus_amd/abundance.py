@@ -62,6 +62,15 @@ device keeps one entry per (read, tied gene) in a list of tie_list_factor (defau
 entries; a run whose tied sets do not fit is refused and told the factor that fits.  For a gene none of whose reads tie the three columns are
 rpkg's, bit for bit.  candidate_reads, unique_reads, the any-coverage columns and the groups table's tie columns are not bootstrapped.
 
+How sure is `detected`?  breadth and detected are the most fragile figures of the table: three reads that happen to tile a gene lift it over
+min_breadth exactly like a gene covered ten deep.  With bootstrap_coverage (Engine.set_coverage_bootstrap; csrc/mc_covboot.h states the rule;
+needs bootstrap and coverage) replicate b of a gene's covered residues is what the best rows of the reads PRESENT in replicate b - weight(b,
+read) > 0, the same resample as replicate b of the counts - cover, and the gene table gets breadth_boot_mean, breadth_boot_se, breadth_ci95_low
+and breadth_ci95_high behind every other column and, with min_breadth, detected_support: the share of the B replicates that detect the gene.  A
+Poisson(1) resample leaves out about 37 % of the reads, so covered_b <= covered_aa in every replicate and the interval lies at or below
+breadth: it is no confidence interval of the true breadth but a measure of how much the figure hangs on single reads.  covered_any_aa,
+detected_any, mean_depth, max_depth, the depth file and the groups table's genes_detected are not bootstrapped.
+
 Reads of mixed lengths (mixed_lengths; README "Reads of mixed lengths"): one trimmed length drops every shorter read and the tail of
 every longer one.  Under the switch every read is searched and counted at the largest length class L_k it reaches
 (Engine.set_abundance_classes; csrc/k_abund_classes.h states the rule), and the denominator is that of the bases so sampled:
@@ -106,6 +115,7 @@ TIE_BOOT_COLUMNS = ("rpkg_shared_boot_se", "rpkg_shared_ci95_low", "rpkg_shared_
 MAX_TIE_LIST = 1 << 27                                                               # MC_TB_MAXCAP (csrc/mc_tieboot.h): the most entries the tie list holds
 MAX_TIE_FACTOR = 500                                                                 # MC_MAX_M8 (csrc/mc_core.h): no read ties across more genes
 TIE_FACTOR = 4                                                                       # tie_list_factor's default
+COV_BOOT_COLUMNS = ("breadth_boot_mean", "breadth_boot_se", "breadth_ci95_low", "breadth_ci95_high")   # behind those with bootstrap_coverage; "detected_support" last with min_breadth
 BOOT_COLUMNS = ("rpkg_boot_se", "rpkg_ci95_low", "rpkg_ci95_high")                  # behind all of them with bootstrap; behind the groups table's with bootstrap_groups
 MAX_BOOT = 4096                                                                      # MC_GB_MAXB (csrc/mc_geneboot.h)
 MAX_CURVE = 64                                                                       # MC_CURVE_MAXK (csrc/mc_curve.h)
@@ -447,6 +457,30 @@ def group_boot_columns(stats, used):
     return se, out[0], out[1]
 
 
+def coverage_need(length_aa, min_breadth):
+    """need[g] = max(1, ceil(F x length_aa)) in float64, as uint32: the integer form of detect()'s comparison - an integer covered_aa is
+    >= F x length_aa exactly when it is >= ceil(F x length_aa), and need >= 1 makes reads > 0 implied (csrc/mc_covboot.h, DETECTION)"""
+    return np.maximum(1.0, np.ceil(np.float64(min_breadth) * np.asarray(length_aa, dtype=np.float64))).astype(np.uint32)
+
+
+def cov_boot_columns(stats, B, length_aa):
+    """(breadth_boot_mean, breadth_boot_se, breadth_ci95_low, breadth_ci95_high) from the device's six doubles per gene (csrc/mc_covboot.h: sum,
+    m2 and the order statistics x[lo], x[lo + 1], x[hi], x[hi + 1] of the B replicate values covered_b, in residues): mean = sum / B /
+    length_aa, se = sqrt(m2 / (B - 1)) / length_aa, NaN with B < 2; the interval is numpy.percentile(covered_b / length_aa, [2.5, 97.5]) by
+    boot_columns' interpolation."""
+    stats = np.asarray(stats, dtype=np.float64).reshape(-1, 6)
+    ln = np.asarray(length_aa, dtype=np.float64)
+    m = int(B)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = stats[:, 0] / m / ln
+        se = np.sqrt(stats[:, 1] / (m - 1)) / ln if m > 1 else np.full(len(ln), np.nan)
+        out = []
+        for q, col in ((0.025, 2), (0.975, 4)):
+            v = (m - 1) * q
+            out.append(_lerp(stats[:, col] / ln, stats[:, col + 1] / ln, v - math.floor(v)))
+    return mean, se, out[0], out[1]
+
+
 def header_lines(args, table):
     mixed = [] if table.get("length_classes") is None else [(k, ",".join(str(int(x)) for x in table[k])) for k in ("length_classes", "class_reads", "class_reads_assigned")] + [("sampled_bases", table["sampled_bases"])]
     h = [("metagenome", ",".join(args["seqfiles"])), ("genes", args["genes"]), ("sampled_reads", table["sampled_reads"]),
@@ -473,7 +507,7 @@ def table_columns(table):
     has = lambda key: table.get(key) is not None
     groups = ((True, COLUMNS, "sdddf"), (has("covered_aa"), COVERAGE_COLUMNS, "dffd"), (has("detected"), ("detected",), "d"), (has("unique_reads"), TIES_COLUMNS, "ddff"),
               (has("covered_any_aa"), TIES_COVERAGE_COLUMNS, "df"), (has("detected_any"), ("detected_any",), "d"), (has("rpkg_boot_se"), BOOT_COLUMNS, "fff"),
-              (has("rpkg_shared_boot_se"), TIE_BOOT_COLUMNS, "fff"))
+              (has("rpkg_shared_boot_se"), TIE_BOOT_COLUMNS, "fff"), (has("breadth_boot_se"), COV_BOOT_COLUMNS, "ffff"), (has("detected_support"), ("detected_support",), "f"))
     return [c for on, names, kinds in groups if on for c in zip(names, kinds)]
 
 
@@ -506,6 +540,8 @@ def write_table(path, args, table):
             out.writelines(boot_header_lines(table))
         if table.get("rpkg_shared_boot_se") is not None:
             out.writelines(["# bootstrap_ties:\ton\n", "# tie_list:\t%d/%d\n" % (table["tie_list_entries"], table["tie_list_capacity"])])
+        if table.get("breadth_boot_se") is not None:
+            out.write("# bootstrap_coverage:\ton\n")
         columns = table_columns(table)
         _write_rows(out, columns, [table[name] for name, _ in columns])
 
@@ -614,7 +650,7 @@ def check_request(args):
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
                          ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
                          ("bootstrap", None), ("bootstrap_seed", None), ("bootstrap_groups", False), ("mixed_lengths", None), ("long_genes", False),
-                         ("bootstrap_ties", False), ("tie_list_factor", None)):
+                         ("bootstrap_ties", False), ("tie_list_factor", None), ("bootstrap_coverage", False)):
         args.setdefault(key, default)
     mixed = microbe_census.mixed_lengths_on(args)
     if mixed:
@@ -673,6 +709,12 @@ def check_request(args):
             raise AbundanceError("--tie-list-factor %s needs --bootstrap-ties: it sizes the list of tie entries" % (args["tie_list_factor"],))
         _check_int(args, "tie_list_factor", 1, MAX_TIE_FACTOR, "1 to %d" % MAX_TIE_FACTOR)
     args["coverage"] = bool(args["coverage"]) or args["min_breadth"] is not None or args["depth_out"] is not None
+    _check_switch(args, "bootstrap_coverage")
+    if args["bootstrap_coverage"]:
+        if args["bootstrap"] is None:
+            raise AbundanceError("--bootstrap-coverage needs --bootstrap B (--bootstrap %s): it covers every gene with the reads of the gene bootstrap's replicates" % (args["bootstrap"],))
+        if not args["coverage"]:
+            raise AbundanceError("--bootstrap-coverage needs --coverage, --min-breadth or --depth-out (--coverage %s): it bootstraps breadth and detected" % (args["coverage"],))
     if args["ags"] is not None and args["ags_report"] is not None:
         raise AbundanceError("--ags %s and --ags-report %s cannot be combined: one AGS" % (args["ags"], args["ags_report"]))
     mi = args["min_ident"]
@@ -761,10 +803,12 @@ def tie_list_overflow(dropped, candidates_sum, gene_capacity, factor):
 
 
 def _size_lists(eng, args, n):
-    """the gene bootstrap's list of n reads and, with bootstrap_ties, the tie list behind it: one moment, one count"""
+    """the gene bootstrap's list of n reads and, with bootstrap_ties, the tie list behind it, with bootstrap_coverage the coverage list: one moment, one count"""
     eng.set_gene_bootstrap(n)
     if args["bootstrap_ties"] and n:
         eng.set_tie_bootstrap(tie_list_capacity(n, args["tie_list_factor"]))
+    if args["bootstrap_coverage"] and n:                            # (one entry per assigned read: no more than the reads)
+        eng.set_coverage_bootstrap(n)
 
 
 def _search_once(eng, rd, args, sample):
@@ -809,7 +853,7 @@ def device_pass(args, sample, names, seqs, group_of):
     try:                        # (long_genes: the engine on the segments, with the genes' statistics)
         db = {"names": names, "seqs": seqs} if fold is None else {"names": fold["seg_names"], "seqs": fold["seg_seqs"], "stats": fold["stats"]}
         eng = _native.Engine(device=int(args.get("device") or 0), marker_family=[0] * len(db["names"]), nfam=1, **db)
-        c = dict.fromkeys(("ac", "gb", "gbg", "scale", "tb"))
+        c = dict.fromkeys(("ac", "gb", "gbg", "scale", "tb", "cb"))
         c["gids"], c["gnames"] = _set_switches(eng, args, sample, names, group_of)
         try:
             c["cu"], c["points"] = _search_once(eng, rd, args, sample)
@@ -841,6 +885,13 @@ def device_pass(args, sample, names, seqs, group_of):
                     raise tie_list_overflow(total - cap_t, total, glist, args["tie_list_factor"]) if total > cap_t else AbundanceError(str(e))
                 c["tie_list"] = (total, cap_t)
                 c["tie_bootstrap_ms"] = eng.tie_bootstrap_ms()
+            if args["bootstrap_coverage"]:                          # the same replicates: what the reads present in each of them cover
+                need = coverage_need([len(s) for s in seqs], args["min_breadth"]) if args["min_breadth"] is not None else None
+                try:
+                    c["cb"] = eng.coverage_bootstrap(args["bootstrap"], args["bootstrap_seed"] or 0, need)
+                except RuntimeError as e:
+                    raise AbundanceError(str(e))
+                c["coverage_bootstrap_ms"] = eng.coverage_bootstrap_ms()
         c["cov"] = eng.coverage() if args["coverage"] else None
         c["depth"] = eng.coverage_depth() if args["depth_out"] is not None else None
         c["ti"] = eng.ties() if args["ties"] else None
@@ -922,6 +973,12 @@ def build_table(args, sample, counts, names, seqs, group_of):
         se, lo, hi = boot_columns(tb["stats"], tb["used"], length_aa)
         table.update({"rpkg_shared_boot_se": se, "rpkg_shared_ci95_low": lo, "rpkg_shared_ci95_high": hi, "tie_boot_stats": tb["stats"], "tie_boot_used": tb["used"],
                       "tie_list_entries": counts["tie_list"][0], "tie_list_capacity": counts["tie_list"][1]})
+    cb = counts.get("cb")                                          # (a record from before the switch has no such key)
+    if cb is not None:
+        table.update(zip(COV_BOOT_COLUMNS, cov_boot_columns(cb["stats"], args["bootstrap"], length_aa)))
+        table["cov_boot_stats"] = cb["stats"]
+        if cb.get("detected") is not None:
+            table.update({"cov_boot_detected": cb["detected"], "detected_support": np.asarray(cb["detected"], np.float64) / float(args["bootstrap"])})
     gbg = counts.get("gbg")                                        # (a record from before the switch has no such key)
     if gbg is not None:                                             # (group_ids numbers the groups in group_table's order)
         table.update({"groups_boot": list(zip(*(col.tolist() for col in group_boot_columns(gbg["stats"], gbg["used"])))), "groups_boot_stats": gbg["stats"]})
@@ -961,7 +1018,10 @@ def run_abundance(args):
     combined with curve) and bootstrap_groups (needs bootstrap and groups: table['groups_boot'], one (se, low, high) per row of table['groups'],
     table['groups_boot_stats'], and the three columns behind every column of <outfile>.groups.tsv) and bootstrap_ties (needs bootstrap and ties:
     rpkg_shared_boot_se, rpkg_shared_ci95_low, rpkg_shared_ci95_high behind every column of the gene table, table['tie_boot_stats'] and
-    table['tie_boot_used']; tie_list_factor, 1 .. 500, default 4, sizes its list; leaves args['tie_bootstrap_ms']), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
+    table['tie_boot_used']; tie_list_factor, 1 .. 500, default 4, sizes its list; leaves args['tie_bootstrap_ms']) and bootstrap_coverage (needs
+    bootstrap and coverage: breadth_boot_mean, breadth_boot_se, breadth_ci95_low, breadth_ci95_high and, with min_breadth, detected_support behind
+    every column of the gene table, table['cov_boot_stats'] - six doubles per gene, in residues - and table['cov_boot_detected']; leaves
+    args['coverage_bootstrap_ms']), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
     given AGS), long_genes (genes of up to 65,535 residues; table['long_genes'] = {genes_split, segments, edge_rows}).  Four stages with two
     records between them - DESIGN.md 13, "How a run is laid out on the host".  Writes args['outfile'] (and <outfile>.groups.tsv with groups)
     when it is set; leaves in args the sampler's options as imputed, sampled_reads, search_ms and the *_ms of every switch that ran; returns

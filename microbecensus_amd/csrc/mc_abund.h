@@ -1,11 +1,12 @@
 // mc_abund.h - the one owner of the per-gene counts (mc_set_abundance), the coverage depth (mc_set_coverage), the tie accounting
 // (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap), the bootstrap of the tie
-// shares (mc_set_tie_bootstrap) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
+// shares (mc_set_tie_bootstrap), the bootstrap of the coverage columns (mc_set_coverage_bootstrap) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
 // With a gene fold (mc_set_gene_fold, mc_fold.h) it also owns the fold of a range's rows from segments onto genes (k_fold.h), in front of everything else.
-// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_groupboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
+// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_covboot.h, k_groupboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
 // hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end
 // (device_groupboot.hip also through mc_groupboot_launch, like the group bootstrap's read; device_tieboot.hip through mc_abund_launch and
-// mc_tieboot_launch, like the tie bootstrap's read).
+// mc_tieboot_launch, like the tie bootstrap's read; device_covboot.hip through mc_abund_launch and mc_covboot_launch, like the coverage
+// bootstrap's read).
 #pragma once
 #include "k_abundance.h"
 #include "k_coverage.h"
@@ -13,6 +14,7 @@
 #include "k_curve.h"
 #include "k_geneboot.h"
 #include "k_tieboot.h"
+#include "k_covboot.h"
 #include "k_groupboot.h"
 #include "k_abund_classes.h"
 #include "k_fold.h"
@@ -48,6 +50,9 @@ struct McGeneBootBufs { McGbEntry *list; unsigned long long capacity; unsigned l
 // the tie bootstrap's part of a launch (null: it is off).  list: `capacity` entries; cur: the cursor and `dropped` (k_tieboot.h); ev:
 // recorded behind k_tieboot_collect
 struct McTieBootBufs { McTbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
+// the coverage bootstrap's part of a launch (null: it is off).  list: `capacity` entries; cur: the cursor and `dropped` (k_covboot.h); ev:
+// recorded behind k_covboot_collect.  The launch's B.off gives the genes' residues
+struct McCovBootBufs { McCbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
 struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigned long long nreads; hipEvent_t ev; };
 
 // The kernels of a range's final rows (ascending read id), in `st`: the counting kernel - k_abundance_cov INSTEAD of k_abundance while
@@ -60,8 +65,10 @@ struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigne
 // rows has reads), and R->ev behind it.  Without one (R null) nothing more is issued and the kernels are the fixed-length runs'.
 // With the tie bootstrap (T not null) k_tieboot_collect runs behind the gene bootstrap's kernel on the same rows - with a class ride it
 // takes every id through R->map, without one the map it is handed has a null perm - and T->ev behind it; without it (T null) nothing.
+// With the coverage bootstrap (V not null; B.off is there: coverage is on) k_covboot_collect runs behind the tie bootstrap's kernel on the same
+// rows, its ids taken as k_tieboot_collect takes them, and V->ev behind it; without it (V null) nothing.
 static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McRow *rows, uint32_t nr, hipStream_t st, const hipEvent_t (&ev)[3], const McCurveBufs *C = nullptr,
-                           const McGeneBootBufs *G = nullptr, const McClassRide *R = nullptr, const McTieBootBufs *T = nullptr)
+                           const McGeneBootBufs *G = nullptr, const McClassRide *R = nullptr, const McTieBootBufs *T = nullptr, const McCovBootBufs *V = nullptr)
 {
     const dim3 grid((nr + 255) / 256), block(256);
     HIPCK(hipEventRecord(ev[0], st));
@@ -86,6 +93,11 @@ static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McR
         const McIdMap own = {nullptr, 0};
         if (nr) k_tieboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, T->list, T->capacity, T->cur, R ? R->map : own);
         HIPCK(hipEventRecord(T->ev, st));
+    }
+    if (V) {
+        const McIdMap own = {nullptr, 0};
+        if (nr) k_covboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, B.off, V->list, V->capacity, V->cur, R ? R->map : own);
+        HIPCK(hipEventRecord(V->ev, st));
     }
     if (!R) return 0;
     k_abund_class_add<<<dim3(1), dim3(64), 0, st>>>(R->tab, R->K, R->k, R->nreads, B.counts + mc_pair_at((size_t)B.nseq));
@@ -142,6 +154,26 @@ static int mc_tieboot_launch(const McTieBootRead &R, hipStream_t st, const hipEv
     return 0;
 }
 
+// The coverage bootstrap's read (mc_covboot.h): raw device pointers of one mc_coverage_bootstrap.  list: the n collected entries; cursor, idx:
+// made by mc_gb_plan from the count table on the host; sorted: n entries; genes: the ngenes genes with reads - slice, residues, need (0: no
+// detection) - made on the host; mat: ngenes x B covered residues; det: ngenes counts, zeroed, or null; ones: B doubles of 1.0; out: ngenes x 6
+struct McCovBootRead { int32_t nseq, ngenes; long long n; const McCbEntry *list; uint32_t *cursor; const int32_t *idx; McCbEntry *sorted; const McCbGene *genes; unsigned long long *mat;
+                       unsigned long long *det; const double *ones; int32_t B; uint64_t seed; double *out; };
+// The three kernels of a read between ev[0] and ev[1], in `st`: the scatter with n > 0, the cover kernel and k_geneboot_summary - the gene
+// bootstrap's own kernel, on this matrix, every replicate used - with ngenes > 0
+static int mc_covboot_launch(const McCovBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
+{
+    HIPCK(hipEventRecord(ev[0], st));
+    if (R.n > 0) k_covboot_scatter<<<dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st>>>(R.list, R.n, R.nseq, R.cursor, R.idx, R.sorted);
+    if (R.ngenes > 0) {
+        k_covboot_cover<<<dim3((unsigned)R.ngenes, (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.genes, R.B, R.seed, R.mat, R.det);
+        k_geneboot_summary<<<dim3((unsigned)R.ngenes), dim3(MC_GB_THREADS), 0, st>>>(R.mat, R.ones, R.B, R.B, R.out);
+    }
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(ev[1], st));
+    return 0;
+}
+
 // The group bootstrap's read (mc_groupboot.h): raw device pointers of one mc_group_bootstrap, behind a read that left mat.  mat: ngenes x B
 // replicate counts; start, member, kb: the CSR of the ngrp groups with reads, made by mc_grb_plan on the host; val: ngrp x B doubles;
 // cnt: ngrp x B counts, or null; scale: B doubles, m of them used; out: ngrp x 6 doubles
@@ -160,7 +192,7 @@ static int mc_groupboot_launch(const McGroupBootRead &R, hipStream_t st, const h
 }
 
 // ---- Owner --------------------------------------------------------------------------------------------------------------------
-// The seven switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
+// The eight switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
 //     the difference array, the scan's output, its two events                    coverage is on
 //     the tie table, its event                                                   ties are on
@@ -175,12 +207,16 @@ static int mc_groupboot_launch(const McGroupBootRead &R, hipStream_t st, const h
 //     the tie bootstrap's list, its cursor and dropped counter, the grouped list,
 //     the genes' cursors and compact indices, the scales, the output, its three events   the tie bootstrap is on
 //     the tie bootstrap's matrix of replicate shares                              the tie bootstrap is on and a read has sized it
+//     the coverage bootstrap's list, its cursor and dropped counter, the grouped list, the genes' cursors,
+//     compact indices and records, the ones, need's counts, the output, its three events   the coverage bootstrap is on
+//     the coverage bootstrap's matrix of covered residues                         the coverage bootstrap is on and a read has sized it
 //     the per-class table (k_abund_classes.h), its event                          the counts may ride on class runs
 //     the segment records, the genes' offsets, the edge counter, its two events   a gene fold is set (set_fold; with the counts on or off)
 //     the folded rows                                                             a gene fold is set and a range has sized them (launch grows them)
 // Coverage, ties, the curve, the gene bootstrap and the class ride are on only while the counts are; the tie bootstrap only while ties AND the gene
-// bootstrap are (either going off, or being set anew, takes it with it).  Every switch that goes on, and reset(), zeroes ALL
-// counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the cursor and dropped counter of both bootstraps
+// bootstrap are (either going off, or being set anew, takes it with it); the coverage bootstrap only while coverage is (it is independent of the gene
+// bootstrap: a list, a seed and a B of its own).  Every switch that goes on, and reset(), zeroes ALL
+// counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the cursor and dropped counter of the three bootstraps' lists
 // (empty lists), the per-class table, `searched` and the times: counts, depth, ties, curve, bootstrap and classes describe the same reads.  A switch that goes off
 // frees its buffers and zeroes nothing of the others; the counts going off take the other five with them.
 struct McAbundance {
@@ -204,6 +240,12 @@ struct McAbundance {
     size_t tmat_slots = 0;                                         // what d_tmat holds: a read grows it to ngenes x B
     McEvent ev_tboot, ev_tread[2];                                 // behind k_tieboot_collect; around the kernels of a read
     float tboot_ms = 0, tread_ms = 0;                              // k_tieboot_collect's, the reads' time since the last zeroing
+    // the coverage bootstrap (mc_covboot.h): the switch, the list's capacity, and the gene bootstrap's set of buffers once more on the third entry
+    bool cboot = false; int64_t ccap = 0;
+    McDev<McCbEntry> d_clist, d_csorted; McDev<unsigned long long> d_ccur, d_cmat, d_cdet; McDev<uint32_t> d_ccursor; McDev<int32_t> d_cidx; McDev<McCbGene> d_cgene; McDev<double> d_cones, d_cout;
+    size_t cmat_slots = 0;                                         // what d_cmat holds: a read grows it to ngenes x B
+    McEvent ev_cboot, ev_cread[2];                                 // behind k_covboot_collect; around the kernels of a read
+    float cboot_ms = 0, cread_ms = 0;                              // k_covboot_collect's, the reads' time since the last zeroing
     // the group bootstrap (mc_groupboot.h): the CSR of the groups with reads, the members' gene_kb, the replicate values and counts, the output
     McDev<uint32_t> d_grstart, d_grmember; McDev<double> d_grkb, d_grval, d_grout; McDev<unsigned long long> d_grcnt;
     size_t grval_slots = 0, grcnt_slots = 0;                       // what d_grval, d_grcnt hold: a group read grows them to ngrp x B
@@ -263,6 +305,14 @@ struct McAbundance {
         tcap = capacity;
         return turn(tboot, true);
     }
+    // capacity: entries of the coverage list, checked by the caller (mc_set_coverage_bootstrap: counts and coverage are on); 0: off.  On while on: a list of another size
+    int set_coverage_bootstrap(int64_t capacity)
+    {
+        (void)turn(cboot, false);
+        if (capacity == 0) return 0;
+        ccap = capacity;
+        return turn(cboot, true);
+    }
     // on: refused by the caller while the curve is on (mc_set_abundance_classes)
     int set_classes(bool to) { return turn(classes, to); }
     // The gene fold: seg: ix_nseq records, goff: ngenes + 1 offsets of the genes' residues (both checked and made by the caller,
@@ -300,10 +350,11 @@ struct McAbundance {
         if (d_first) HIPCK(hipMemset(d_first, 0xFF, sizeof(uint32_t) * nres));
         if (d_gcur) HIPCK(hipMemset(d_gcur, 0, sizeof(unsigned long long) * 2));
         if (d_tcur) HIPCK(hipMemset(d_tcur, 0, sizeof(unsigned long long) * 2));
+        if (d_ccur) HIPCK(hipMemset(d_ccur, 0, sizeof(unsigned long long) * 2));
         if (d_cls) HIPCK(hipMemset(d_cls, 0, sizeof(unsigned long long) * MC_AC_SLOTS));
         if (d_edge) HIPCK(hipMemset(d_edge, 0, sizeof(unsigned long long)));
         fold_ms = 0.f;
-        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = tboot_ms = tread_ms = 0.f;
+        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = tboot_ms = tread_ms = cboot_ms = cread_ms = 0.f;
         gmat_n = -1; grp_ms = grp_values_ms = grp_summary_ms = 0.f;
         return 0;
     }
@@ -328,7 +379,8 @@ struct McAbundance {
         const McGeneBootBufs G = {d_glist, (unsigned long long)gcap, d_gcur, ev_gboot};
         const McClassRide R = {map, d_cls, map_K, piece_k, (unsigned long long)nreads, ev_cls};
         const McTieBootBufs T = {d_tlist, (unsigned long long)tcap, d_tcur, ev_tboot};
-        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr, tboot ? &T : nullptr);
+        const McCovBootBufs V = {d_clist, (unsigned long long)ccap, d_ccur, ev_cboot};
+        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr, tboot ? &T : nullptr, cboot ? &V : nullptr);
     }
     // ---- a batch of a class run under the switch (classes_batch): perm: the row index of every sorted position, on the device, for as
     // long as the pieces run; base: the batch's first read id; K_: its classes.  ride_piece: the class of the piece whose range ends next.
@@ -360,7 +412,8 @@ struct McAbundance {
         if (curve) curve_ms += ev_ms(ties ? ev_ties : ev_count[1], ev_curve);
         if (gboot) gboot_ms += ev_ms(curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_gboot);
         if (tboot) tboot_ms += ev_ms(ev_gboot, ev_tboot);          // (on only with the gene bootstrap)
-        if (riding()) cls_ms += ev_ms(tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
+        if (cboot) cboot_ms += ev_ms(tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cboot);
+        if (riding()) cls_ms += ev_ms(cboot ? ev_cboot : tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
     }
     void add_searched(int64_t nreads) { if (on) searched += nreads; }   // (mc_search_varlen: reads too short to have a frame are searched, and have no rows)
 
@@ -475,6 +528,59 @@ struct McAbundance {
             for (size_t b = 0; b < (size_t)B; b++) shares[s * (size_t)B + b] = idx[s] >= 0 ? (uint64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
         return 0;
     }
+    // The bootstrap of the coverage columns as they stand (mc_covboot.h): B replicates under `seed`.  need (or null): nseq values, none of them 0,
+    // checked by the caller; covered (or null): nseq x B covered residues; stats: nseq x 6 doubles of those values, every replicate used;
+    // detected (or null; only with need): nseq counts of the replicates with covered >= need; dropped: the assigned reads that did not fit the
+    // list - not zero: an error that names it, and nothing else is computed.
+    int read_coverage_bootstrap(int32_t B, uint64_t seed, const uint32_t *need, int64_t *covered, double *stats, int64_t *detected, int64_t *dropped)
+    {
+        const size_t ns = (size_t)nseq;
+        unsigned long long cur[2];
+        HIPCK(hipMemcpy(cur, d_ccur, sizeof cur, hipMemcpyDeviceToHost));
+        if (dropped) *dropped = (int64_t)cur[1];
+        if (cur[1] || cur[0] > (unsigned long long)ccap) {
+            g_err = "mc_coverage_bootstrap: " + std::to_string(cur[1]) + " assigned reads did not fit the list of " + std::to_string(ccap) + " entries (mc_set_coverage_bootstrap): dropped, no replicate is whole";
+            return -1;
+        }
+        std::vector<unsigned long long> tab(mc_pair_slots(ns));
+        HIPCK(hipMemcpy(tab.data(), d_counts, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> start(ns), hoff(ns + 1); std::vector<int32_t> idx(ns);
+        unsigned long long total = 0;
+        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
+        if (total != cur[0]) { g_err = "mc_coverage_bootstrap: the count table holds " + std::to_string(total) + " assigned reads, the list " + std::to_string(cur[0]); return -1; }
+        HIPCK(hipMemcpy(hoff.data(), off, sizeof(uint32_t) * (ns + 1), hipMemcpyDeviceToHost));   // (the genes' residues: the index's offsets, or the fold's)
+        std::vector<McCbGene> genes((size_t)ng);
+        for (size_t s = 0; s < ns; s++)
+            if (idx[s] >= 0) genes[(size_t)idx[s]] = {start[s], (uint32_t)tab[mc_pair_at(s)], hoff[s + 1] - hoff[s], need ? need[s] : 0u};
+        const std::vector<double> ones((size_t)B, 1.0);
+        const size_t want = (size_t)ng * (size_t)B;
+        if (want > cmat_slots) { cmat_slots = 0; if (d_cmat.alloc(want)) return -1; cmat_slots = want; }
+        HIPCK(hipMemcpy(d_cones, ones.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_ccursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_cidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
+        if (ng) HIPCK(hipMemcpy(d_cgene, genes.data(), sizeof(McCbGene) * (size_t)ng, hipMemcpyHostToDevice));
+        HIPCK(hipMemsetAsync(d_cdet, 0, sizeof(unsigned long long) * ns, 0));
+        const McCovBootRead R = {nseq, ng, (long long)cur[0], d_clist, d_ccursor, d_cidx, d_csorted, d_cgene, d_cmat, need ? d_cdet.get() : nullptr, d_cones, B, seed, d_cout};
+        const hipEvent_t ev[2] = {ev_cread[0], ev_cread[1]};
+        if (mc_covboot_launch(R, 0, ev)) return -1;
+        HIPCK(hipEventSynchronize(ev_cread[1]));
+        cread_ms += ev_ms(ev_cread[0], ev_cread[1]);
+        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
+        if (ng) HIPCK(hipMemcpy(out.data(), d_cout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; s++)                            // (a gene without reads: nothing covered in any replicate)
+            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * s + k] = idx[s] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)idx[s] + k] : 0.0;
+        if (detected) {
+            std::vector<unsigned long long> det((size_t)ng);
+            if (ng) HIPCK(hipMemcpy(det.data(), d_cdet, sizeof(unsigned long long) * (size_t)ng, hipMemcpyDeviceToHost));
+            for (size_t s = 0; s < ns; s++) detected[s] = idx[s] >= 0 ? (int64_t)det[(size_t)idx[s]] : 0;
+        }
+        if (!covered) return 0;
+        std::vector<unsigned long long> mat(want);
+        if (want) HIPCK(hipMemcpy(mat.data(), d_cmat, want * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; s++)
+            for (size_t b = 0; b < (size_t)B; b++) covered[s * (size_t)B + b] = idx[s] >= 0 ? (int64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
+        return 0;
+    }
     // The bootstrap of the GROUPS (mc_groupboot.h) on the counts as they stand: group_of: nseq groups below ngroups_, gene_kb: nseq doubles, all
     // checked by the caller (mc_group_bootstrap).  counts (or null): ngroups_ x B group replicate counts; stats: ngroups_ x 6 doubles.  mat is
     // that of the read before when it is still this one's (the same B, seed and entries, no range since), and made here otherwise.
@@ -575,6 +681,8 @@ private:
     {
         if (!on) { cov = ties = curve = gboot = classes = false; searched = 0; ms = 0.f; }
         if (!ties || !gboot) tboot = false;
+        if (!cov) cboot = false;
+        if (!cboot) { ccap = 0; cboot_ms = cread_ms = 0.f; d_cmat.reset(); cmat_slots = 0; }
         if (!tboot) { tcap = 0; tboot_ms = tread_ms = 0.f; d_tmat.reset(); tmat_slots = 0; }
         if (!classes) { cls_ms = 0.f; ride_end(); }
         if (!cov) cov_ms = 0.f;
@@ -596,6 +704,9 @@ private:
                fit_one(d_gscale, gboot, MC_GB_MAXB) || fit_one(d_gout, gboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_gboot, gboot) || fit_one(ev_gread[0], gboot) || fit_one(ev_gread[1], gboot) ||
                fit_one(d_tlist, tboot, (size_t)tcap) || fit_one(d_tsorted, tboot, (size_t)tcap) || fit_one(d_tcur, tboot, 2) || fit_one(d_tcursor, tboot, ns) || fit_one(d_tidx, tboot, ns) ||
                fit_one(d_tscale, tboot, MC_GB_MAXB) || fit_one(d_tout, tboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_tboot, tboot) || fit_one(ev_tread[0], tboot) || fit_one(ev_tread[1], tboot) ||
+               fit_one(d_clist, cboot, (size_t)ccap) || fit_one(d_csorted, cboot, (size_t)ccap) || fit_one(d_ccur, cboot, 2) || fit_one(d_ccursor, cboot, ns) || fit_one(d_cidx, cboot, ns) ||
+               fit_one(d_cgene, cboot, ns) || fit_one(d_cdet, cboot, ns) || fit_one(d_cones, cboot, MC_GB_MAXB) || fit_one(d_cout, cboot, (size_t)MC_GB_NOUT * ns) ||
+               fit_one(ev_cboot, cboot) || fit_one(ev_cread[0], cboot) || fit_one(ev_cread[1], cboot) ||
                fit_one(d_cls, classes, MC_AC_SLOTS) || fit_one(ev_cls, classes);
     }
     // one switch to `to`.  A switch whose buffers cannot be had ends off and leaves the others as they were (freeing cannot fail).

@@ -20,6 +20,7 @@
 //   k_ties.h               the tie accounting beside them: unique, candidate and shared reads of the genes that tie for a read's best hit (mc_set_ties)
 //   k_curve.h              the rarefaction curve beside them: per-gene counts per prefix of the sample, every residue's first read, a scan at read time (mc_set_curve)
 //   k_tieboot.h            the bootstrap of the tie shares beside both: a device list of (read id, gene, share), per-gene replicate sums at read time (mc_set_tie_bootstrap)
+//   k_covboot.h            the bootstrap of the coverage columns: a device list of (read id, gene, span), per-gene replicate covered residues at read time (mc_set_coverage_bootstrap)
 //   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
 //   k_groupboot.h          the bootstrap of the groups table behind it: every group's replicate values walked over its members' rows of the replicate sums, sort and summary (mc_group_bootstrap)
 //   k_abund_classes.h      the per-class table of the counts on class runs (mc_set_abundance_classes)
@@ -1426,6 +1427,7 @@ extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_
     if (nreads > 0x7fffffff) { g_err = "more than 2^31 - 1 reads in one call"; return -1; }
     if (h->pipe_nout) { g_err = "ranges begun with mc_range_begin() are still in flight"; return -1; }
     if (h->ab.curve) { g_err = "mc_search_varlen: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
+    if (h->ab.cboot) { g_err = "mc_search_varlen: refused while the coverage bootstrap is on (mc_set_coverage_bootstrap, capacity = " + std::to_string(h->ab.ccap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     if (h->ab.tboot) { g_err = "mc_search_varlen: refused while the tie bootstrap is on (mc_set_tie_bootstrap, capacity = " + std::to_string(h->ab.tcap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     if (h->ab.gboot) { g_err = "mc_search_varlen: refused while the gene bootstrap is on (mc_set_gene_bootstrap, capacity = " + std::to_string(h->ab.gcap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     bool one = true;
@@ -2148,6 +2150,35 @@ extern "C" int mc_tie_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const do
     return h->ab.read_tie_bootstrap(B, seed, scale, shares, stats, dropped);
 }
 
+// the bootstrap of the coverage columns (mc_covboot.h): a list of `capacity` entries turns it on and zeroes every counter; capacity == 0 turns it off
+extern "C" int mc_set_coverage_bootstrap(mc_handle *h, int64_t capacity)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_coverage_bootstrap: a range begun with mc_range_begin() is still in flight (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (capacity == 0) return h->ab.set_coverage_bootstrap(0);
+    if (capacity < 0 || capacity > (int64_t)MC_CB_MAXCAP) { g_err = "mc_set_coverage_bootstrap: capacity " + std::to_string(capacity) + " is not a number of entries from 0 to 2^31 - 1"; return -1; }
+    if (!h->ab.active()) { g_err = "mc_set_coverage_bootstrap: the counts are off (mc_set_abundance) - the entries are the reads they assign (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    if (!h->ab.cov) { g_err = "mc_set_coverage_bootstrap: coverage is off (mc_set_coverage) - the entries are the spans it marks (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    return h->ab.set_coverage_bootstrap(capacity);
+}
+
+// need (or NULL): nseq values, none 0; covered (or NULL): nseq x B covered residues; stats: nseq x 6 doubles (mc_covboot.h); detected (or NULL;
+// only with need): nseq counts; dropped: the assigned reads that did not fit
+extern "C" int mc_coverage_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const uint32_t *need, int64_t *covered, double *stats, int64_t *detected, int64_t *dropped)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.cboot) { g_err = "mc_coverage_bootstrap: the coverage bootstrap is off (mc_set_coverage_bootstrap)"; return -1; }
+    if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_coverage_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
+    if (!stats) { g_err = "mc_coverage_bootstrap: B = " + std::to_string(B) + " and a NULL stats array"; return -1; }
+    if (detected && !need) { g_err = "mc_coverage_bootstrap: detected without need (B = " + std::to_string(B) + ") - a replicate detects a gene that covers need[g] residues"; return -1; }
+    for (int32_t s = 0; need && s < h->ab.nseq; s++)
+        if (need[s] == 0) { g_err = "mc_coverage_bootstrap: need[" + std::to_string(s) + "] = 0 - every replicate would detect the gene; the least is 1"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_coverage_bootstrap: a range begun with mc_range_begin() is still in flight"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_coverage_bootstrap(B, seed, need, covered, stats, detected, dropped);
+}
+
 // the counts on class runs: mc_search_classes and mc_search_files on a class reader are no longer refused, every piece adds to the
 // counts and to the per-class table (k_abund_classes.h), and the gene bootstrap takes the read ids through the batch's id map
 extern "C" int mc_set_abundance_classes(mc_handle *h, int on)
@@ -2253,6 +2284,13 @@ extern "C" void mc_tie_bootstrap_kernels_ms(const mc_handle *h, float *collect_m
 {
     if (collect_ms) *collect_ms = h ? h->ab.tboot_ms : 0.0f;
     if (read_ms) *read_ms = h ? h->ab.tread_ms : 0.0f;
+}
+// k_covboot_collect's time over the completed ranges plus the coverage reads' kernels, since the last zeroing; the two parts (either may be NULL)
+extern "C" float mc_coverage_bootstrap_ms(const mc_handle *h) { return h ? h->ab.cboot_ms + h->ab.cread_ms : 0.0f; }
+extern "C" void mc_coverage_bootstrap_kernels_ms(const mc_handle *h, float *collect_ms, float *read_ms)
+{
+    if (collect_ms) *collect_ms = h ? h->ab.cboot_ms : 0.0f;
+    if (read_ms) *read_ms = h ? h->ab.cread_ms : 0.0f;
 }
 // the group reads' kernels since the last zeroing: k_groupboot_values and k_groupboot_summary, and the kernels of a mat a group read had to make
 extern "C" float mc_group_bootstrap_ms(const mc_handle *h) { return h ? h->ab.grp_ms : 0.0f; }

@@ -57,6 +57,10 @@ def parse_arguments(argv=None):
     p.add_argument("--tie-list-factor", dest="tie_list_factor", type=int, default=None, metavar="F",
                    help="with --bootstrap-ties: the device keeps one entry per read and tied gene in a list of F times the sampled reads, at most 2^27 entries (1 - 500; default = 4); "
                         "a run whose tied sets do not fit is refused and names the F that fits")
+    p.add_argument("--bootstrap-coverage", dest="bootstrap_coverage", action="store_true", default=False,
+                   help="with --bootstrap and --coverage, --min-breadth or --depth-out: add breadth_boot_mean, breadth_boot_se, breadth_ci95_low and breadth_ci95_high behind every column of "
+                        "the gene table and, with --min-breadth, detected_support: the share of the replicates in which the gene is detected (how much breadth and the detection call hang on "
+                        "single reads; the interval lies at or below breadth)")
     p.add_argument("--mixed-lengths", dest="mixed_lengths", nargs="?", const=True, default=None, metavar="L1,L2,...",
                    type=lambda v: [int(x) for x in v.split(",")],
                    help="count every read at the largest of the model's read lengths it reaches, instead of cutting all reads to one length and dropping the shorter ones; "
