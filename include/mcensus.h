@@ -734,6 +734,34 @@ int mc_gene_fold_stats(mc_handle *h, int32_t *ngenes, int64_t *edge_rows, float 
 int32_t mc_abundance_count(const mc_handle *h);
 int64_t mc_abundance_residues(const mc_handle *h);
 
+/* ---- How similar the assigned reads are to the database's sequence, beside the counts (csrc/mc_identity.h states the rule) ----------
+ * "Reads mapped to gene" (README "Normalization") says how many reads a gene got, not how close they are to it: at 99 % identity they
+ * are that allele, at 65 % a distant homolog.  A read's best row - the very row that mc_set_abundance counts, under the same
+ * 0 <= subject < nseq - adds 1 to hist[subject][bin], bin = alnlen < 1 ? 0 : (100 * nmatch) / alnlen in integer division (the floor of
+ * the identity in percent, 0 .. 100: 101 bins of 32 bits), and nmatch, mismatch and gapopen to three 64-bit sums of the subject.  Exact
+ * integers, whatever the batches, ranges, classes and launch geometry.
+ * mc_set_identity(on != 0) allocates the histogram (128 counters per sequence: 101 bins, padded) and the sums, and zeroes them AND every
+ * other abundance counter: all describe the same reads.  From then on every range that adds to the counts adds to them, in a kernel of
+ * its own behind the others (csrc/k_identity.h), pieces of class runs included; under a gene fold in gene space.  on == 0 frees them and
+ * restores the path without it exactly.  mc_set_abundance(h, 0, ...) also turns the identity off; mc_abundance_reset() also zeroes it and
+ * both times below.
+ * Refused, with a message naming the value: abundance counting off (mc_set_abundance first), a range in flight. */
+int mc_set_identity(mc_handle *h, int on);
+/* The identity as it stands, per sequence s (arrays of mc_abundance_count() values; any may be NULL): the three sums; ident_min and
+ * ident_max, the lowest and highest non-empty bin; ident_median, the LOWER median - the smallest bin whose cumulative count reaches
+ * (n - 1) / 2 + 1, n the reads of s; ge[s * nlevels + j], the reads of s in bins >= levels[j].  A sequence without reads gets -1 for the
+ * three bins and 0 elsewhere.  One scan kernel per call, a wave per sequence: the histogram stays on the device.
+ * Refused, naming the value: the identity off; nlevels outside 0 .. 8; a level outside 0 .. 100 or not above the one before it. */
+int mc_identity_read(mc_handle *h, const int32_t *levels /* [nlevels] */, int32_t nlevels, int64_t *matched /* [nseq] */, int64_t *mismatched /* [nseq] */,
+                     int64_t *gap_opens /* [nseq] */, int32_t *ident_min /* [nseq] */, int32_t *ident_median /* [nseq] */, int32_t *ident_max /* [nseq] */,
+                     int64_t *ge /* [nseq * nlevels] or NULL */);
+/* The histogram itself, without its padding: hist[s * 101 + bin].  Refused while the identity is off, and a NULL array. */
+int mc_identity_hist(mc_handle *h, uint32_t *hist /* [nseq * 101] */);
+/* Milliseconds since the last reset (HIP events): of the counting side's kernel over the completed ranges, and of the scan kernels of
+ * mc_identity_read. */
+float mc_identity_ms(const mc_handle *h);
+float mc_identity_scan_ms(const mc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -273,6 +273,13 @@ def load_library():
     lib.mc_abundance_count.argtypes = [C.c_void_p]
     lib.mc_abundance_residues.restype = C.c_int64
     lib.mc_abundance_residues.argtypes = [C.c_void_p]
+    lib.mc_set_identity.argtypes = [C.c_void_p, C.c_int]
+    lib.mc_identity_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mc_identity_hist.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mc_identity_ms.restype = C.c_float
+    lib.mc_identity_ms.argtypes = [C.c_void_p]
+    lib.mc_identity_scan_ms.restype = C.c_float
+    lib.mc_identity_scan_ms.argtypes = [C.c_void_p]
     lib.mc_debug_live.restype = None
     lib.mc_debug_live.argtypes = [C.POINTER(C.c_int64)]
     _lib = lib
@@ -297,7 +304,8 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_set_tie_bootstrap", "mc_tie_bootstrap", "mc_tie_bootstrap_ms", "mc_tie_bootstrap_kernels_ms",
                     "mc_set_coverage_bootstrap", "mc_coverage_bootstrap", "mc_coverage_bootstrap_ms", "mc_coverage_bootstrap_kernels_ms",
                     "mc_set_abundance_classes", "mc_abundance_classes_read", "mc_abundance_classes_ms", "mc_open_stats", "mc_set_gene_fold", "mc_gene_fold_stats",
-                    "mc_abundance_count", "mc_abundance_residues", "mc_debug_live"]
+                    "mc_abundance_count", "mc_abundance_residues",
+                    "mc_set_identity", "mc_identity_read", "mc_identity_hist", "mc_identity_ms", "mc_identity_scan_ms", "mc_debug_live"]
 
 
 class DupSet:
@@ -1029,6 +1037,42 @@ class Engine:
     def coverage_ms(self):
         """milliseconds the coverage scan kernels took since the last reset (HIP events); the marks are part of abundance_ms()"""
         return float(self.lib.mc_coverage_ms(self.h))
+
+    def set_identity(self, on=True):
+        """The alignment identity of the assigned reads beside the counts (mc_set_identity; csrc/mc_identity.h states the rule): from now on
+        a read's best row - the one set_abundance counts - adds 1 to its gene's bin floor(100 x nmatch / alnlen) and its nmatch, mismatch and
+        gapopen to the gene's three sums.  on=True zeroes them AND every other abundance counter; on=False frees them.  Refused while
+        set_abundance is off."""
+        self._check(self.lib.mc_set_identity(self.h, 1 if on else 0), "mc_set_identity")
+
+    def identity(self, levels=()):
+        """The per-gene figures as they stand (mc_identity_read; one scan kernel, the histogram stays on the device): {"matched", "mismatched",
+        "gap_opens": int64[nseq]; "ident_min", "ident_median", "ident_max": int32[nseq], -1 for a gene without reads (the median is the lower
+        one); "levels": the levels as given; "ge": int64[nseq, len(levels)], the reads in bins >= each level}.  levels: up to 8 integers in
+        0 .. 100, strictly ascending - anything else is refused."""
+        n = self.abundance_count()
+        lv = np.ascontiguousarray(list(levels), dtype=np.int32)
+        out = {k: np.zeros(n, np.int64) for k in ("matched", "mismatched", "gap_opens")}
+        out.update({k: np.zeros(n, np.int32) for k in ("ident_min", "ident_median", "ident_max")})
+        ge = np.zeros((n, lv.size), np.int64)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        self._check(self.lib.mc_identity_read(self.h, ptr(lv), int(lv.size), *(out[k].ctypes.data_as(C.c_void_p) for k in ("matched", "mismatched", "gap_opens", "ident_min", "ident_median", "ident_max")),
+                                              ptr(ge)), "mc_identity_read")
+        out.update({"levels": [int(x) for x in lv], "ge": ge})
+        return out
+
+    def identity_hist(self):
+        """The histogram itself (mc_identity_hist): uint32[nseq, 101], the reads of every gene by the floor of their best row's identity."""
+        hist = np.zeros((self.abundance_count(), 101), np.uint32)
+        self._check(self.lib.mc_identity_hist(self.h, hist.ctypes.data_as(C.c_void_p)), "mc_identity_hist")
+        return hist
+
+    def identity_ms(self):
+        """milliseconds k_identity took over the completed ranges since the last reset (HIP events); identity_scan_ms(): the scans of identity()"""
+        return float(self.lib.mc_identity_ms(self.h))
+
+    def identity_scan_ms(self):
+        return float(self.lib.mc_identity_scan_ms(self.h))
 
     def set_ties(self, on=True, group_of=None, ngroups=0):
         """The tie accounting beside the counts (mc_set_ties; csrc/k_ties.h states the rule): from now on every read that set_abundance

@@ -78,7 +78,19 @@ every longer one.  Under the switch every read is searched and counted at the la
     sampled_bases = sum over the classes of n_k x L_k       genome_equivalents_sampled = sampled_bases / AGS
 
 n_k the reads of class k, counted on the device beside the reads each class assigned.  The default AGS is run_pipeline's estimate
-under the same classes: numerator and denominator still come from the same sampled bases."""
+under the same classes: numerator and denominator still come from the same sampled bases.
+
+How close is the gene to the database's?  A gene covered over 90 % of its length at 99 % identity is that allele; the same breadth at 65 % is a
+distant homolog.  With identity (Engine.set_identity; csrc/mc_identity.h states the rule) the device also keeps, per gene, a histogram of the
+floor of the identity in percent of every assigned read's BEST ROW - 100 x nmatch / alnlen, the row the counts take - and the sums of those
+rows' identical, mismatched and gap-opening columns, and the gene table gets, behind every other column,
+
+    matched_aa, mismatched_aa, gap_opens     ident_mean = 100 x matched_aa / aligned_aa     ident_median (the lower one), ident_min, ident_max
+
+and per level T of ident_levels reads_ident_ge<T> - the reads whose best row has an identity of at least T percent - and rpkg_ident_ge<T>, the
+rpkg formula on them.  That is NOT the reads column of a run with min_ident T: there a lower-scoring row of higher identity may win a read
+whose best row fails the cut-off; the two agree for a read with one row.  ident_out writes the histogram (gene, ident, reads: one line per
+non-empty bin).  The figures are whole-sample figures of the best row: not rarefied, not bootstrapped, not shared among tied genes."""
 import gzip
 import math
 import os
@@ -119,8 +131,13 @@ COV_BOOT_COLUMNS = ("breadth_boot_mean", "breadth_boot_se", "breadth_ci95_low", 
 BOOT_COLUMNS = ("rpkg_boot_se", "rpkg_ci95_low", "rpkg_ci95_high")                  # behind all of them with bootstrap; behind the groups table's with bootstrap_groups
 MAX_BOOT = 4096                                                                      # MC_GB_MAXB (csrc/mc_geneboot.h)
 MAX_CURVE = 64                                                                       # MC_CURVE_MAXK (csrc/mc_curve.h)
+IDENT_COLUMNS = ("matched_aa", "mismatched_aa", "gap_opens", "ident_mean", "ident_median", "ident_min", "ident_max")   # behind every other column with identity; reads_ident_ge<T>, rpkg_ident_ge<T> per level behind them
+IDENT_OUT_COLUMNS = ("gene", "ident", "reads")
+IDENT_BINS = 101                                                                     # MC_ID_BINS (csrc/mc_identity.h)
+MAX_IDENT_LEVELS = 8                                                                 # MC_ID_LEVELS
 PIPELINE_KEYS = ("seqfiles", "nreads", "read_length", "min_quality", "mean_quality", "filter_dups", "max_unknown", "threads", "device", "model_dir", "verbose")
-TEXT = {"s": str, "d": lambda v: "%d" % v, "f": lambda v: repr(float(v)), "n": lambda v: "NA" if v is None else repr(float(v))}   # a value in a table, by its column's kind
+TEXT = {"s": str, "d": lambda v: "%d" % v, "f": lambda v: repr(float(v)), "n": lambda v: "NA" if v is None else repr(float(v)),
+        "i": lambda v: "NA" if v is None else "%d" % v}   # a value in a table, by its column's kind
 SHARE_ONE = 4294967296.0                                                             # share[] counts in units of 2^-32 (csrc/k_ties.h)
 
 
@@ -404,6 +421,72 @@ def read_depth(path, names, length_aa):
     return depth
 
 
+def identity_columns(idn, reads, aligned, length_aa, ge):
+    """The identity columns of the gene table from Engine.identity()'s arrays: the three sums as they are; ident_mean = 100.0 x matched_aa /
+    aligned_aa in float64; ident_median, ident_min, ident_max as integer percents - all four None (NA) for a gene without reads; and per level T
+    reads_ident_ge<T> and rpkg_ident_ge<T>, the rpkg formula on those reads."""
+    has = (np.asarray(reads) > 0) & (np.asarray(aligned) > 0)
+    mean = 100.0 * np.asarray(idn["matched"], np.float64) / np.where(has, aligned, 1).astype(np.float64)
+    cols = {"matched_aa": idn["matched"], "mismatched_aa": idn["mismatched"], "gap_opens": idn["gap_opens"], "ident_mean": [float(v) if h else None for v, h in zip(mean.tolist(), has.tolist())]}
+    for k in ("ident_median", "ident_min", "ident_max"):
+        cols[k] = [None if v < 0 else int(v) for v in np.asarray(idn[k]).tolist()]
+    for j, t in enumerate(idn["levels"]):
+        cols["reads_ident_ge%d" % t] = np.ascontiguousarray(idn["ge"][:, j])
+        cols["rpkg_ident_ge%d" % t] = rpkg(idn["ge"][:, j], length_aa, ge)
+    return cols
+
+
+def level_columns(levels):
+    """[(column, kind)] of the levels: reads_ident_ge<T> and rpkg_ident_ge<T> per level, in the levels' order"""
+    return [c for t in levels for c in (("reads_ident_ge%d" % t, "d"), ("rpkg_ident_ge%d" % t, "f"))]
+
+
+def group_ident_table(names, group_of, table):
+    """[(matched_aa, ident_mean, reads_ident_ge<T1>, rpkg_ident_ge<T1>, ...)] per group in group_table's order: sums over the members in FASTA
+    order; ident_mean from the members' summed matched_aa and aligned_aa, None for a group without aligned residues"""
+    cols = [table[name] for name, _ in level_columns(table["ident_levels"])]
+    order, acc = [], {}
+    for k, nm in enumerate(names):
+        g = group_of.get(nm, nm)
+        if g not in acc:
+            acc[g] = [0, 0] + [0 if i % 2 == 0 else 0.0 for i in range(len(cols))]
+            order.append(g)
+        a = acc[g]
+        a[0] += int(table["matched_aa"][k])
+        a[1] += int(table["aligned_aa"][k])
+        for i, col in enumerate(cols):
+            a[2 + i] += int(col[k]) if i % 2 == 0 else float(col[k])
+    return [(acc[g][0], 100.0 * acc[g][0] / acc[g][1] if acc[g][1] > 0 else None) + tuple(acc[g][2:]) for g in order]
+
+
+def write_ident(path, names, hist):
+    """--ident-out: gene, ident, reads - one line per non-empty bin of the histogram (Engine.identity_hist), genes in FASTA order, bins
+    ascending, only the genes with reads"""
+    hist = np.asarray(hist)
+    g, b = np.nonzero(hist)
+    with open(path, "w") as out:
+        out.write("#" + "\t".join(IDENT_OUT_COLUMNS) + "\n")
+        out.writelines("%s\t%d\t%d\n" % (names[k], x, v) for k, x, v in zip(g.tolist(), b.tolist(), hist[g, b].tolist()))
+
+
+def read_ident(path, names):
+    """The public inverse of write_ident, for whoever reads the file back (a plot, a test): uint32[genes, 101], zeros where the file has no
+    line.  names: the gene FASTA's, in its order."""
+    index = {nm: k for k, nm in enumerate(names)}
+    hist = np.zeros((len(names), IDENT_BINS), np.uint32)
+    with open(path) as f:
+        for line in f:
+            if line.startswith("#"):
+                continue
+            nm, b, v = line.rstrip("\n").split("\t")
+            hist[index[nm], int(b)] = int(v)
+    return hist
+
+
+def ident_header_lines(table):
+    return ["# identity:\ton\n"] + (["# ident_levels:\t%s\n" % ",".join(str(t) for t in table["ident_levels"])] if table["ident_levels"] else [])
+
+
 def _lerp(a, b, t):
     """numpy's linear interpolation between two order statistics (numpy.percentile, method "linear"): a + (b - a) t, and from t = 0.5 on
     b - (b - a) (1 - t)"""
@@ -507,8 +590,9 @@ def table_columns(table):
     has = lambda key: table.get(key) is not None
     groups = ((True, COLUMNS, "sdddf"), (has("covered_aa"), COVERAGE_COLUMNS, "dffd"), (has("detected"), ("detected",), "d"), (has("unique_reads"), TIES_COLUMNS, "ddff"),
               (has("covered_any_aa"), TIES_COVERAGE_COLUMNS, "df"), (has("detected_any"), ("detected_any",), "d"), (has("rpkg_boot_se"), BOOT_COLUMNS, "fff"),
-              (has("rpkg_shared_boot_se"), TIE_BOOT_COLUMNS, "fff"), (has("breadth_boot_se"), COV_BOOT_COLUMNS, "ffff"), (has("detected_support"), ("detected_support",), "f"))
-    return [c for on, names, kinds in groups if on for c in zip(names, kinds)]
+              (has("rpkg_shared_boot_se"), TIE_BOOT_COLUMNS, "fff"), (has("breadth_boot_se"), COV_BOOT_COLUMNS, "ffff"), (has("detected_support"), ("detected_support",), "f"),
+              (has("identity"), IDENT_COLUMNS, "dddniii"))
+    return [c for on, names, kinds in groups if on for c in zip(names, kinds)] + (level_columns(table["ident_levels"]) if has("identity") else [])
 
 
 def group_columns(table):
@@ -516,7 +600,8 @@ def group_columns(table):
     gt = table.get("groups_ties")
     ties = GROUP_TIES_COLUMNS + (("genes_detected_any",) if table.get("detected_any") is not None else ()) if gt is not None else ()
     boot = BOOT_COLUMNS if table.get("groups_boot") is not None else ()
-    return list(zip(GROUP_COLUMNS + (("genes_detected",) if table.get("detected") is not None else ()), "sddfd")) + list(zip(ties, "dffd")) + list(zip(boot, "fff"))
+    ident = [("matched_aa", "d"), ("ident_mean", "n")] + level_columns(table["ident_levels"]) if table.get("groups_ident") is not None else []
+    return list(zip(GROUP_COLUMNS + (("genes_detected",) if table.get("detected") is not None else ()), "sddfd")) + list(zip(ties, "dffd")) + list(zip(boot, "fff")) + ident
 
 
 def _write_rows(out, columns, values):
@@ -542,6 +627,8 @@ def write_table(path, args, table):
             out.writelines(["# bootstrap_ties:\ton\n", "# tie_list:\t%d/%d\n" % (table["tie_list_entries"], table["tie_list_capacity"])])
         if table.get("breadth_boot_se") is not None:
             out.write("# bootstrap_coverage:\ton\n")
+        if table.get("identity") is not None:
+            out.writelines(ident_header_lines(table))
         columns = table_columns(table)
         _write_rows(out, columns, [table[name] for name, _ in columns])
 
@@ -554,7 +641,9 @@ def write_groups(path, args, table):
         out.write("# groups:\t%s\n" % args["groups"])
         if boot is not None:
             out.writelines(boot_header_lines(table) + ["# bootstrap_groups:\ton\n"])
-        _write_rows(out, group_columns(table), list(zip(*table["groups"])) + list(zip(*(table.get("groups_ties") or []))) + list(zip(*(boot or []))))
+        if table.get("groups_ident") is not None:
+            out.writelines(ident_header_lines(table))
+        _write_rows(out, group_columns(table), list(zip(*table["groups"])) + list(zip(*(table.get("groups_ties") or []))) + list(zip(*(boot or []))) + list(zip(*(table.get("groups_ident") or []))))
 
 
 def curve_figures(names, length_aa, read_length, points, reads, aligned, covered, ags, min_breadth=None, group_of=None):
@@ -634,11 +723,12 @@ def _check_switch(args, key):
 
 
 def _check_own_path(args, key, others):
-    """refused: args[key] is the path of another file of the run - of <outfile> + a suffix (the groups table only with groups) or of --depth-out"""
+    """refused: args[key] is the path of another file of the run - of <outfile> + a suffix (the groups table only with groups, the curve table only
+    with curve when it is asked about by name) or of --depth-out / --curve-genes"""
     what = {"": "the gene table itself", ".curve.tsv": "the curve table (<outfile>.curve.tsv)", ".groups.tsv": "the groups table (<outfile>.groups.tsv)",
-            "depth_out": "the depth file (--depth-out)"}
+            "depth_out": "the depth file (--depth-out)", "curve_genes": "the curve's per-gene matrix (--curve-genes)"}
     for o in others:
-        other = args["depth_out"] if o == "depth_out" else args["outfile"] + o if args.get("outfile") and (o != ".groups.tsv" or args["groups"]) else None
+        other = args[o] if o in ("depth_out", "curve_genes") else args["outfile"] + o if args.get("outfile") and (o != ".groups.tsv" or args["groups"]) and (o != ".curve.tsv" or args["curve"] is not None) else None
         if other and os.path.abspath(args[key]) == os.path.abspath(other):
             raise AbundanceError("--%s %s is the path of %s: two files" % (key.replace("_", "-"), args[key], what[o]))
 
@@ -650,7 +740,7 @@ def check_request(args):
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
                          ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
                          ("bootstrap", None), ("bootstrap_seed", None), ("bootstrap_groups", False), ("mixed_lengths", None), ("long_genes", False),
-                         ("bootstrap_ties", False), ("tie_list_factor", None), ("bootstrap_coverage", False)):
+                         ("bootstrap_ties", False), ("tie_list_factor", None), ("bootstrap_coverage", False), ("identity", False), ("ident_levels", None), ("ident_out", None)):
         args.setdefault(key, default)
     mixed = microbe_census.mixed_lengths_on(args)
     if mixed:
@@ -715,6 +805,19 @@ def check_request(args):
             raise AbundanceError("--bootstrap-coverage needs --bootstrap B (--bootstrap %s): it covers every gene with the reads of the gene bootstrap's replicates" % (args["bootstrap"],))
         if not args["coverage"]:
             raise AbundanceError("--bootstrap-coverage needs --coverage, --min-breadth or --depth-out (--coverage %s): it bootstraps breadth and detected" % (args["coverage"],))
+    _check_switch(args, "identity")
+    if args["ident_levels"] is not None:
+        lv = args["ident_levels"]
+        ok = isinstance(lv, (list, tuple)) and 1 <= len(lv) <= MAX_IDENT_LEVELS and all(not isinstance(t, bool) and isinstance(t, (int, np.integer)) and 0 <= int(t) <= 100 for t in lv)
+        if not ok or any(int(b) <= int(a) for a, b in zip(lv, lv[1:])):
+            raise AbundanceError("--ident-levels %s is not a list of 1 to %d integer percents from 0 to 100, strictly ascending"
+                                 % (",".join(str(t) for t in lv) if isinstance(lv, (list, tuple)) else lv, MAX_IDENT_LEVELS))
+        args["ident_levels"] = [int(t) for t in lv]
+    if args["ident_out"] is not None:
+        if not args["ident_out"]:
+            raise AbundanceError("--ident-out %r is an empty path" % (args["ident_out"],))
+        _check_own_path(args, "ident_out", ("", ".curve.tsv", ".groups.tsv", "depth_out", "curve_genes"))
+    args["identity"] = args["identity"] or args["ident_levels"] is not None or args["ident_out"] is not None
     if args["ags"] is not None and args["ags_report"] is not None:
         raise AbundanceError("--ags %s and --ags-report %s cannot be combined: one AGS" % (args["ags"], args["ags_report"]))
     mi = args["min_ident"]
@@ -770,7 +873,7 @@ def resolve_sample(args, ags, source):
 
 
 def _set_switches(eng, args, sample, names, group_of):
-    """fold, run or run_classes, abundance, coverage, ties, abundance_classes; returns (gids, gnames): the groups the device got, or None twice"""
+    """fold, run or run_classes, abundance, coverage, ties, identity, abundance_classes; returns (gids, gnames): the groups the device got, or None twice"""
     fold, classes = args["gene_fold"], sample["classes"]
     if fold is not None:        # long_genes: the engine is open on the segments, every counter is in gene space
         eng.set_gene_fold(fold["seg_gene"], fold["seg_off"], fold["gene_len"])
@@ -784,6 +887,8 @@ def _set_switches(eng, args, sample, names, group_of):
     gids, gnames = group_ids(names, group_of) if args["ties"] and group_of is not None else (None, None)
     if args["ties"]:
         eng.set_ties(True, gids, len(gnames or ()))
+    if args.get("identity"):
+        eng.set_identity(True)
     if classes is not None:
         eng.set_abundance_classes(True)
     return gids, gnames
@@ -845,7 +950,7 @@ def _replicate_scale(args, sample, ab, ac):
 
 def device_pass(args, sample, names, seqs, group_of):
     """Stage 2 - the record `counts`, from the only place that opens a reader or an engine: what the device counted as numpy arrays and ints - ab,
-    ac, cov, depth, ti, tcov, cu and points, gb, gbg (the groups') and scale, fold_stats (None: not asked for), sampled, gids and gnames, search_ms and the *_ms"""
+    ac, cov, depth, ti, tcov, cu and points, gb, gbg (the groups') and scale, idn (the identity's figures, with the histogram under "hist" for ident_out), fold_stats (None: not asked for), sampled, gids and gnames, search_ms and the *_ms"""
     pargs, classes, fold = sample["pargs"], sample["classes"], args["gene_fold"]
     sampler = (pargs["nreads"], pargs["file_type"] == "fastq", pargs.get("quality_offset") or 0, pargs["min_quality"], pargs["mean_quality"], pargs["max_unknown"], pargs["filter_dups"])
     rd = _native.Reader.with_classes(pargs["seqfiles"], classes, *sampler) if classes is not None else _native.Reader(pargs["seqfiles"], sample["L"], *sampler)
@@ -853,7 +958,7 @@ def device_pass(args, sample, names, seqs, group_of):
     try:                        # (long_genes: the engine on the segments, with the genes' statistics)
         db = {"names": names, "seqs": seqs} if fold is None else {"names": fold["seg_names"], "seqs": fold["seg_seqs"], "stats": fold["stats"]}
         eng = _native.Engine(device=int(args.get("device") or 0), marker_family=[0] * len(db["names"]), nfam=1, **db)
-        c = dict.fromkeys(("ac", "gb", "gbg", "scale", "tb", "cb"))
+        c = dict.fromkeys(("ac", "gb", "gbg", "scale", "tb", "cb", "idn"))
         c["gids"], c["gnames"] = _set_switches(eng, args, sample, names, group_of)
         try:
             c["cu"], c["points"] = _search_once(eng, rd, args, sample)
@@ -896,6 +1001,11 @@ def device_pass(args, sample, names, seqs, group_of):
         c["depth"] = eng.coverage_depth() if args["depth_out"] is not None else None
         c["ti"] = eng.ties() if args["ties"] else None
         c["tcov"] = eng.ties_coverage() if args["ties"] and args["coverage"] else None
+        if args.get("identity"):                                    # the scan runs on the device; the histogram itself comes over only for ident_out
+            c["idn"] = eng.identity(args["ident_levels"] or ())
+            if args["ident_out"] is not None:
+                c["idn"]["hist"] = eng.identity_hist()
+            c["identity_ms"] = eng.identity_ms()
         c["fold_stats"] = eng.gene_fold_stats() if fold is not None else None
         c["abundance_ms"], c["search_ms"] = eng.abundance_ms(), eng.stats()["ms_total"]
         if args["coverage"]:
@@ -979,6 +1089,12 @@ def build_table(args, sample, counts, names, seqs, group_of):
         table["cov_boot_stats"] = cb["stats"]
         if cb.get("detected") is not None:
             table.update({"cov_boot_detected": cb["detected"], "detected_support": np.asarray(cb["detected"], np.float64) / float(args["bootstrap"])})
+    idn = counts.get("idn")                                        # (a record from before the switch has no such key)
+    if idn is not None:
+        table.update(identity_columns(idn, ab["reads"], ab["aligned"], length_aa, ge))
+        table.update({"identity": idn, "ident_levels": list(idn["levels"])})
+        if group_of is not None:
+            table["groups_ident"] = group_ident_table(names, group_of, table)
     gbg = counts.get("gbg")                                        # (a record from before the switch has no such key)
     if gbg is not None:                                             # (group_ids numbers the groups in group_table's order)
         table.update({"groups_boot": list(zip(*(col.tolist() for col in group_boot_columns(gbg["stats"], gbg["used"])))), "groups_boot_stats": gbg["stats"]})
@@ -997,9 +1113,11 @@ def build_table(args, sample, counts, names, seqs, group_of):
 
 
 def write_outputs(args, table):
-    """Stage 4 - the files: the depth file; under outfile the gene, groups and curve tables; the curve's per-gene matrix"""
+    """Stage 4 - the files: the depth file; the identity histogram; under outfile the gene, groups and curve tables; the curve's per-gene matrix"""
     if table.get("depth") is not None:
         write_depth(args["depth_out"], table["gene"], table["length_aa"], table["depth"])
+    if table.get("identity") is not None and args.get("ident_out") is not None:
+        write_ident(args["ident_out"], table["gene"], table["identity"]["hist"])
     if args.get("outfile"):
         write_table(args["outfile"], args, table)
         if "groups" in table:
@@ -1022,7 +1140,11 @@ def run_abundance(args):
     bootstrap and coverage: breadth_boot_mean, breadth_boot_se, breadth_ci95_low, breadth_ci95_high and, with min_breadth, detected_support behind
     every column of the gene table, table['cov_boot_stats'] - six doubles per gene, in residues - and table['cov_boot_detected']; leaves
     args['coverage_bootstrap_ms']), mixed_lengths (True or a list of class lengths; not combined with read_length and curve, with bootstrap only under a
-    given AGS), long_genes (genes of up to 65,535 residues; table['long_genes'] = {genes_split, segments, edge_rows}).  Four stages with two
+    given AGS), long_genes (genes of up to 65,535 residues; table['long_genes'] = {genes_split, segments, edge_rows}), identity with ident_levels (a
+    list of 1 .. 8 ascending integer percents) and ident_out (a path; both imply identity: matched_aa, mismatched_aa, gap_opens, ident_mean,
+    ident_median, ident_min, ident_max and per level reads_ident_ge<T>, rpkg_ident_ge<T> behind every column of the gene table, matched_aa,
+    ident_mean and the levels' columns behind every column of <outfile>.groups.tsv, table['identity'] - Engine.identity()'s arrays -; leaves
+    args['identity_ms']).  Four stages with two
     records between them - DESIGN.md 13, "How a run is laid out on the host".  Writes args['outfile'] (and <outfile>.groups.tsv with groups)
     when it is set; leaves in args the sampler's options as imputed, sampled_reads, search_ms and the *_ms of every switch that ran; returns
     (table, args) - table: the columns as arrays, the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""

@@ -1,8 +1,8 @@
 // mc_abund.h - the one owner of the per-gene counts (mc_set_abundance), the coverage depth (mc_set_coverage), the tie accounting
 // (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap), the bootstrap of the tie
-// shares (mc_set_tie_bootstrap), the bootstrap of the coverage columns (mc_set_coverage_bootstrap) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
+// shares (mc_set_tie_bootstrap), the bootstrap of the coverage columns (mc_set_coverage_bootstrap), the identity of the assigned reads (mc_set_identity) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
 // With a gene fold (mc_set_gene_fold, mc_fold.h) it also owns the fold of a range's rows from segments onto genes (k_fold.h), in front of everything else.
-// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_covboot.h, k_groupboot.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
+// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_covboot.h, k_groupboot.h, k_identity.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
 // hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end
 // (device_groupboot.hip also through mc_groupboot_launch, like the group bootstrap's read; device_tieboot.hip through mc_abund_launch and
 // mc_tieboot_launch, like the tie bootstrap's read; device_covboot.hip through mc_abund_launch and mc_covboot_launch, like the coverage
@@ -18,6 +18,7 @@
 #include "k_groupboot.h"
 #include "k_abund_classes.h"
 #include "k_fold.h"
+#include "k_identity.h"
 #include "mc_owned.h"
 
 // ---- Layout: every size and offset of the four tables (k_ties.h, k_coverage.h and k_curve.h, "Layout", say what the slots hold) -----------------
@@ -53,6 +54,9 @@ struct McTieBootBufs { McTbEntry *list; unsigned long long capacity; unsigned lo
 // the coverage bootstrap's part of a launch (null: it is off).  list: `capacity` entries; cur: the cursor and `dropped` (k_covboot.h); ev:
 // recorded behind k_covboot_collect.  The launch's B.off gives the genes' residues
 struct McCovBootBufs { McCbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
+// the identity's part of a launch (null: it is off).  hist: nseq x MC_ID_STRIDE counters; sums: nseq records (mc_identity.h, "Layout"); ev: recorded
+// behind k_identity
+struct McIdentBufs { uint32_t *hist; McIdSums *sums; hipEvent_t ev; };
 struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigned long long nreads; hipEvent_t ev; };
 
 // The kernels of a range's final rows (ascending read id), in `st`: the counting kernel - k_abundance_cov INSTEAD of k_abundance while
@@ -67,8 +71,11 @@ struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigne
 // takes every id through R->map, without one the map it is handed has a null perm - and T->ev behind it; without it (T null) nothing.
 // With the coverage bootstrap (V not null; B.off is there: coverage is on) k_covboot_collect runs behind the tie bootstrap's kernel on the same
 // rows, its ids taken as k_tieboot_collect takes them, and V->ev behind it; without it (V null) nothing.
+// With the identity (I not null) k_identity runs behind the coverage bootstrap's kernel on the same rows - its tables are per gene, it takes no
+// read id - and I->ev behind it, in front of k_abund_class_add; without it (I null) nothing.
 static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McRow *rows, uint32_t nr, hipStream_t st, const hipEvent_t (&ev)[3], const McCurveBufs *C = nullptr,
-                           const McGeneBootBufs *G = nullptr, const McClassRide *R = nullptr, const McTieBootBufs *T = nullptr, const McCovBootBufs *V = nullptr)
+                           const McGeneBootBufs *G = nullptr, const McClassRide *R = nullptr, const McTieBootBufs *T = nullptr, const McCovBootBufs *V = nullptr,
+                           const McIdentBufs *I = nullptr)
 {
     const dim3 grid((nr + 255) / 256), block(256);
     HIPCK(hipEventRecord(ev[0], st));
@@ -98,6 +105,10 @@ static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McR
         const McIdMap own = {nullptr, 0};
         if (nr) k_covboot_collect<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, B.off, V->list, V->capacity, V->cur, R ? R->map : own);
         HIPCK(hipEventRecord(V->ev, st));
+    }
+    if (I) {
+        if (nr) k_identity<<<grid, block, 0, st>>>(A, rows, nr, B.nseq, I->hist, I->sums);
+        HIPCK(hipEventRecord(I->ev, st));
     }
     if (!R) return 0;
     k_abund_class_add<<<dim3(1), dim3(64), 0, st>>>(R->tab, R->K, R->k, R->nreads, B.counts + mc_pair_at((size_t)B.nseq));
@@ -191,8 +202,21 @@ static int mc_groupboot_launch(const McGroupBootRead &R, hipStream_t st, const h
     return 0;
 }
 
+// The identity's read (mc_identity.h): raw device pointers of one mc_identity_read.  hist: nseq x MC_ID_STRIDE counters; level: nlevels checked
+// levels; out: nseq x (3 + nlevels) values
+struct McIdentRead { int32_t nseq; const uint32_t *hist; const int32_t *level; int32_t nlevels; long long *out; };
+// The scan between ev[0] and ev[1], in `st`; with nseq == 0 only the events
+static int mc_identity_launch(const McIdentRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
+{
+    HIPCK(hipEventRecord(ev[0], st));
+    if (R.nseq > 0) k_identity_scan<<<dim3(((unsigned)R.nseq + 3) / 4), dim3(256), 0, st>>>(R.hist, R.nseq, R.level, R.nlevels, R.out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(ev[1], st));
+    return 0;
+}
+
 // ---- Owner --------------------------------------------------------------------------------------------------------------------
-// The eight switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
+// The nine switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
 //     the difference array, the scan's output, its two events                    coverage is on
 //     the tie table, its event                                                   ties are on
@@ -211,14 +235,15 @@ static int mc_groupboot_launch(const McGroupBootRead &R, hipStream_t st, const h
 //     compact indices and records, the ones, need's counts, the output, its three events   the coverage bootstrap is on
 //     the coverage bootstrap's matrix of covered residues                         the coverage bootstrap is on and a read has sized it
 //     the per-class table (k_abund_classes.h), its event                          the counts may ride on class runs
+//     the identity's histogram, sum records, scan output, levels, its three events   the identity is on
 //     the segment records, the genes' offsets, the edge counter, its two events   a gene fold is set (set_fold; with the counts on or off)
 //     the folded rows                                                             a gene fold is set and a range has sized them (launch grows them)
-// Coverage, ties, the curve, the gene bootstrap and the class ride are on only while the counts are; the tie bootstrap only while ties AND the gene
+// Coverage, ties, the curve, the gene bootstrap, the class ride and the identity are on only while the counts are; the tie bootstrap only while ties AND the gene
 // bootstrap are (either going off, or being set anew, takes it with it); the coverage bootstrap only while coverage is (it is independent of the gene
 // bootstrap: a list, a seed and a B of its own).  Every switch that goes on, and reset(), zeroes ALL
 // counters, both difference arrays, the curve's bins (and refills its first ids with 0xFF), the cursor and dropped counter of the three bootstraps' lists
-// (empty lists), the per-class table, `searched` and the times: counts, depth, ties, curve, bootstrap and classes describe the same reads.  A switch that goes off
-// frees its buffers and zeroes nothing of the others; the counts going off take the other five with them.
+// (empty lists), the per-class table, the identity's histogram and sums, `searched` and the times: counts, depth, ties, curve, bootstrap, classes and identity describe the same reads.  A switch that goes off
+// frees its buffers and zeroes nothing of the others; the counts going off take the others with them.
 struct McAbundance {
     int32_t nseq = 0; size_t nres = 0; const uint32_t *off = nullptr;   // the database: bind(), once the index is on the device
     bool on = false, cov = false, ties = false, curve = false, gboot = false; int32_t ngroups = 0, K = 0; int64_t gcap = 0;
@@ -253,6 +278,11 @@ struct McAbundance {
     float grp_ms = 0, grp_values_ms = 0, grp_summary_ms = 0;       // the group reads' time since the last zeroing (with the mat they had to make), and the two kernels'
     bool classes = false;                                          // mc_set_abundance_classes: the counts may ride on class runs
     McDev<unsigned long long> d_cls; McEvent ev_cls; float cls_ms = 0;   // the per-class table; behind k_abund_class_add; its time since the last zeroing
+    // the identity (mc_identity.h): the switch, the histogram, the sum records, the scan's output and levels
+    bool ident = false;
+    McDev<uint32_t> d_idhist; McDev<McIdSums> d_idsums; McDev<long long> d_idout; McDev<int32_t> d_idlev;
+    McEvent ev_ident, ev_iscan[2];                                 // behind k_identity; around a scan
+    float ident_ms = 0, iscan_ms = 0;                              // k_identity's, the scans' time since the last zeroing
     McIdMap map = {nullptr, 0}; int32_t map_K = 0, piece_k = 0;    // held while a batch's pieces run (ride_begin .. ride_end): its ids, its classes; the class of the piece that ends next
     int64_t searched = 0;                                          // the reads of the completed ranges
     // the gene fold (mc_set_gene_fold, mc_fold.h): while it is set nseq, nres and off above are the GENES' - every table, scan and reader is
@@ -315,6 +345,7 @@ struct McAbundance {
     }
     // on: refused by the caller while the curve is on (mc_set_abundance_classes)
     int set_classes(bool to) { return turn(classes, to); }
+    int set_identity(bool to) { return turn(ident, to); }
     // The gene fold: seg: ix_nseq records, goff: ngenes + 1 offsets of the genes' residues (both checked and made by the caller,
     // mc_set_gene_fold); ngenes == 0: off, the tables are the index's again.  The tables are sized by nseq and nres: with the counts on
     // and another size the caller has refused, so here a size changes only while every table is off; with the counts on all is zeroed.
@@ -353,7 +384,9 @@ struct McAbundance {
         if (d_ccur) HIPCK(hipMemset(d_ccur, 0, sizeof(unsigned long long) * 2));
         if (d_cls) HIPCK(hipMemset(d_cls, 0, sizeof(unsigned long long) * MC_AC_SLOTS));
         if (d_edge) HIPCK(hipMemset(d_edge, 0, sizeof(unsigned long long)));
-        fold_ms = 0.f;
+        if (d_idhist) HIPCK(hipMemset(d_idhist, 0, sizeof(uint32_t) * mc_id_hist_slots((size_t)nseq)));
+        if (d_idsums) HIPCK(hipMemset(d_idsums, 0, sizeof(McIdSums) * (size_t)nseq));
+        fold_ms = ident_ms = iscan_ms = 0.f;
         searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = tboot_ms = tread_ms = cboot_ms = cread_ms = 0.f;
         gmat_n = -1; grp_ms = grp_values_ms = grp_summary_ms = 0.f;
         return 0;
@@ -380,7 +413,8 @@ struct McAbundance {
         const McClassRide R = {map, d_cls, map_K, piece_k, (unsigned long long)nreads, ev_cls};
         const McTieBootBufs T = {d_tlist, (unsigned long long)tcap, d_tcur, ev_tboot};
         const McCovBootBufs V = {d_clist, (unsigned long long)ccap, d_ccur, ev_cboot};
-        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr, tboot ? &T : nullptr, cboot ? &V : nullptr);
+        const McIdentBufs I = {d_idhist, d_idsums, ev_ident};
+        return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr, tboot ? &T : nullptr, cboot ? &V : nullptr, ident ? &I : nullptr);
     }
     // ---- a batch of a class run under the switch (classes_batch): perm: the row index of every sorted position, on the device, for as
     // long as the pieces run; base: the batch's first read id; K_: its classes.  ride_piece: the class of the piece whose range ends next.
@@ -413,7 +447,8 @@ struct McAbundance {
         if (gboot) gboot_ms += ev_ms(curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_gboot);
         if (tboot) tboot_ms += ev_ms(ev_gboot, ev_tboot);          // (on only with the gene bootstrap)
         if (cboot) cboot_ms += ev_ms(tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cboot);
-        if (riding()) cls_ms += ev_ms(cboot ? ev_cboot : tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
+        if (ident) ident_ms += ev_ms(cboot ? ev_cboot : tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_ident);
+        if (riding()) cls_ms += ev_ms(ident ? ev_ident : cboot ? ev_cboot : tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
     }
     void add_searched(int64_t nreads) { if (on) searched += nreads; }   // (mc_search_varlen: reads too short to have a frame are searched, and have no rows)
 
@@ -626,6 +661,34 @@ struct McAbundance {
         for (int32_t k = 0; k < n; k++) { if (rows) rows[k] = (int64_t)tab[2 * k]; if (assigned) assigned[k] = (int64_t)tab[2 * k + 1]; }
         return 0;
     }
+    // The identity as it stands (mc_identity.h): level: nlevels levels, checked by the caller (mc_identity_read).  The sums and the three bins per
+    // gene (MC_ID_NONE for a gene without reads), every one or null; ge (or null): nseq x nlevels counts, gene by gene.  The scan runs on the
+    // device: the histogram does not come to the host
+    int read_identity(const int32_t *level, int32_t nlevels, int64_t *matched, int64_t *mismatched, int64_t *gap_opens, int32_t *imin, int32_t *imedian, int32_t *imax, int64_t *ge)
+    {
+        const size_t ns = (size_t)nseq, nout = 3 + (size_t)nlevels;
+        if (nlevels) HIPCK(hipMemcpy(d_idlev, level, sizeof(int32_t) * (size_t)nlevels, hipMemcpyHostToDevice));
+        const McIdentRead R = {nseq, d_idhist, d_idlev, nlevels, d_idout};
+        const hipEvent_t ev[2] = {ev_iscan[0], ev_iscan[1]};
+        if (mc_identity_launch(R, 0, ev)) return -1;
+        HIPCK(hipEventSynchronize(ev_iscan[1]));
+        iscan_ms += ev_ms(ev_iscan[0], ev_iscan[1]);
+        std::vector<long long> out(nout * ns); std::vector<McIdSums> sums(ns);
+        HIPCK(hipMemcpy(out.data(), d_idout, out.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(sums.data(), d_idsums, ns * sizeof(McIdSums), hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < ns; s++) {
+            if (matched) matched[s] = (int64_t)sums[s].matched; if (mismatched) mismatched[s] = (int64_t)sums[s].mismatched; if (gap_opens) gap_opens[s] = (int64_t)sums[s].gap_opens;
+            if (imin) imin[s] = (int32_t)out[nout * s]; if (imedian) imedian[s] = (int32_t)out[nout * s + 1]; if (imax) imax[s] = (int32_t)out[nout * s + 2];
+            for (size_t j = 0; ge && j < (size_t)nlevels; j++) ge[(size_t)nlevels * s + j] = (int64_t)out[nout * s + 3 + j];
+        }
+        return 0;
+    }
+    // the histogram without its padding: nseq x MC_ID_BINS counters
+    int read_identity_hist(uint32_t *hist) const
+    {
+        if (nseq) HIPCK(hipMemcpy2D(hist, sizeof(uint32_t) * MC_ID_BINS, d_idhist, sizeof(uint32_t) * MC_ID_STRIDE, sizeof(uint32_t) * MC_ID_BINS, (size_t)nseq, hipMemcpyDeviceToHost));
+        return 0;
+    }
     int read_depth(uint32_t *depth)                                // nres values
     {
         McDevBuf buf; uint32_t *d_depth = nullptr;
@@ -679,7 +742,8 @@ private:
     // the switches as they stand, made consistent; then the buffer rule: what they need is made where it is missing, everything else freed
     int fit()
     {
-        if (!on) { cov = ties = curve = gboot = classes = false; searched = 0; ms = 0.f; }
+        if (!on) { cov = ties = curve = gboot = classes = ident = false; searched = 0; ms = 0.f; }
+        if (!ident) ident_ms = iscan_ms = 0.f;
         if (!ties || !gboot) tboot = false;
         if (!cov) cboot = false;
         if (!cboot) { ccap = 0; cboot_ms = cread_ms = 0.f; d_cmat.reset(); cmat_slots = 0; }
@@ -707,7 +771,9 @@ private:
                fit_one(d_clist, cboot, (size_t)ccap) || fit_one(d_csorted, cboot, (size_t)ccap) || fit_one(d_ccur, cboot, 2) || fit_one(d_ccursor, cboot, ns) || fit_one(d_cidx, cboot, ns) ||
                fit_one(d_cgene, cboot, ns) || fit_one(d_cdet, cboot, ns) || fit_one(d_cones, cboot, MC_GB_MAXB) || fit_one(d_cout, cboot, (size_t)MC_GB_NOUT * ns) ||
                fit_one(ev_cboot, cboot) || fit_one(ev_cread[0], cboot) || fit_one(ev_cread[1], cboot) ||
-               fit_one(d_cls, classes, MC_AC_SLOTS) || fit_one(ev_cls, classes);
+               fit_one(d_cls, classes, MC_AC_SLOTS) || fit_one(ev_cls, classes) ||
+               fit_one(d_idhist, ident, mc_id_hist_slots(ns)) || fit_one(d_idsums, ident, ns) || fit_one(d_idout, ident, mc_id_out_slots(ns)) || fit_one(d_idlev, ident, MC_ID_LEVELS) ||
+               fit_one(ev_ident, ident) || fit_one(ev_iscan[0], ident) || fit_one(ev_iscan[1], ident);
     }
     // one switch to `to`.  A switch whose buffers cannot be had ends off and leaves the others as they were (freeing cannot fail).
     int turn(bool &sw, bool to)

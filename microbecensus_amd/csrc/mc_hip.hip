@@ -23,6 +23,7 @@
 //   k_covboot.h            the bootstrap of the coverage columns: a device list of (read id, gene, span), per-gene replicate covered residues at read time (mc_set_coverage_bootstrap)
 //   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
 //   k_groupboot.h          the bootstrap of the groups table behind it: every group's replicate values walked over its members' rows of the replicate sums, sort and summary (mc_group_bootstrap)
+//   k_identity.h, mc_identity.h   the identity of the assigned reads: a histogram and three sums per gene on the rows of a range, min / median / max and levels by a scan at read time (mc_set_identity)
 //   k_abund_classes.h      the per-class table of the counts on class runs (mc_set_abundance_classes)
 //   k_fold.h, mc_fold.h    genes longer than one sequence of the engine: segments, and the fold of a range's rows onto the genes (mc_set_gene_fold)
 //   mc_abund.h             (host) the owner of those five: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
@@ -2191,6 +2192,47 @@ extern "C" int mc_set_abundance_classes(mc_handle *h, int on)
     if (h->ab.curve) { g_err = "mc_set_abundance_classes: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - a prefix of mixed lengths has no one length (on = " + std::to_string(on) + ")"; return -1; }
     return h->ab.set_classes(true);
 }
+
+// the identity of the assigned reads (mc_identity.h): a histogram of the best rows' identities and three sums per gene; on zeroes every counter
+extern "C" int mc_set_identity(mc_handle *h, int on)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_set_identity: a range begun with mc_range_begin() is still in flight (on = " + std::to_string(on) + ")"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    if (on && !h->ab.on) { g_err = "mc_set_identity: abundance counting is off (mc_set_abundance) - the identities are those of the reads it counts (on = " + std::to_string(on) + ")"; return -1; }
+    return h->ab.set_identity(on != 0);
+}
+
+// levels: nlevels of them, 0 .. MC_ID_LEVELS, each 0 .. 100, strictly ascending; every output array holds nseq values (ge: nseq x nlevels) or is NULL
+extern "C" int mc_identity_read(mc_handle *h, const int32_t *levels, int32_t nlevels, int64_t *matched, int64_t *mismatched, int64_t *gap_opens, int32_t *ident_min, int32_t *ident_median,
+                                int32_t *ident_max, int64_t *ge)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.ident) { g_err = "mc_identity_read: the identity is off (mc_set_identity)"; return -1; }
+    if (nlevels < 0 || nlevels > MC_ID_LEVELS) { g_err = "mc_identity_read: nlevels " + std::to_string(nlevels) + " is not a number of levels from 0 to " + std::to_string(MC_ID_LEVELS); return -1; }
+    if (nlevels > 0 && !levels) { g_err = "mc_identity_read: " + std::to_string(nlevels) + " levels and a NULL array"; return -1; }
+    const int bad = mc_id_bad_level(levels, nlevels);
+    if (bad >= 0) {
+        g_err = "mc_identity_read: level " + std::to_string(bad) + " is " + std::to_string(levels[bad]) +
+                (levels[bad] < 0 || levels[bad] > 100 ? ": not a percent from 0 to 100" : ": not above the level before it, " + std::to_string(levels[bad - 1]));
+        return -1;
+    }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_identity(levels, nlevels, matched, mismatched, gap_opens, ident_min, ident_median, ident_max, nlevels ? ge : nullptr);
+}
+
+// hist: nseq x MC_ID_BINS counters, gene by gene
+extern "C" int mc_identity_hist(mc_handle *h, uint32_t *hist)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (!h->ab.ident) { g_err = "mc_identity_hist: the identity is off (mc_set_identity)"; return -1; }
+    if (!hist) { g_err = "mc_identity_hist: a NULL array for " + std::to_string(h->ab.nseq) + " genes"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_identity_hist(hist);
+}
+// k_identity's time over the completed ranges, and the scans' of the reads, since the last zeroing
+extern "C" float mc_identity_ms(const mc_handle *h) { return h ? h->ab.ident_ms : 0.0f; }
+extern "C" float mc_identity_scan_ms(const mc_handle *h) { return h ? h->ab.iscan_ms : 0.0f; }
 
 // ---- the gene fold (mc_fold.h): the index holds the segments of long genes, every abundance table the genes.  seg_gene[s], seg_off[s]: the
 // gene and the offset in it of segment s of the index, gene_len[g]: the residues of gene g.  Checked here against the index's own segment

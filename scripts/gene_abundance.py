@@ -69,6 +69,13 @@ def parse_arguments(argv=None):
     p.add_argument("--long-genes", dest="long_genes", action="store_true", default=False,
                    help="accept genes of up to 65,535 residues: a gene longer than the engine's longest sequence is searched as overlapping segments and every table "
                         "reports the whole gene; adds long_genes, genes_split, segments and edge_rows to the header")
+    p.add_argument("--identity", dest="identity", action="store_true", default=False,
+                   help="add matched_aa, mismatched_aa, gap_opens, ident_mean, ident_median, ident_min and ident_max behind every column of the gene table: how similar the reads "
+                        "assigned to a gene are to its sequence (percent identity of every read's best row; with --groups matched_aa and ident_mean in <out>.groups.tsv)")
+    p.add_argument("--ident-levels", dest="ident_levels", default=None, metavar="T1,T2,...", type=lambda v: [int(x) for x in v.split(",")],
+                   help="per level T add reads_ident_ge<T> and rpkg_ident_ge<T>: the reads whose BEST ROW has at least T percent identity (1 - 8 integers, 0 - 100, ascending); "
+                        "not the reads of a run with --min-ident T, where a lower-scoring row of higher identity may win; implies --identity")
+    p.add_argument("--ident-out", dest="ident_out", type=str, default=None, metavar="FILE", help="write the identity histogram as gene, ident, reads: one line per gene and percent that has reads; implies --identity")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):
