@@ -775,24 +775,27 @@ typedef struct {
     trace_t tr_r, tr_l;
     uint8_t *rev1, *rev2;
     int revcap;
+    rs_range *ranges; /* rs_seed_ranges: where extend_seq2set lists its ranges instead of evaluating their hits */
+    int nranges, max_ranges;
 } qstate;
 
-/* CHashSearch::CalRes@0x4077a0 */
-static void cal_res(qstate *qs, int frame, int qbeg, int sidx, int dbeg, int seedlen,
-                    int score, int nmatch, int qfwd, int dfwd, int qbwd, int dbwd,
-                    int alnlen, int gapopens, int gaptotal)
+/* CHashSearch::CalRes@0x4077a0 up to the keep test: the record of one alignment; 0 when CalRes drops it (h->loge is set either way).
+ * L: the read's length in bases. */
+static int cal_res_record(const ka_eff *eff, int L, int frame, int qbeg, int sidx, int dbeg, int seedlen,
+                          int score, int nmatch, int qfwd, int dfwd, int qbwd, int dbwd,
+                          int alnlen, int gapopens, int gaptotal, hsp_t *hp)
 {
-    double le = ka_loge(&qs->eff, (double)score), bits;
-    hsp_t h, *v;
-    int lo, hi, pos, L = qs->ntlen;
+    double le = ka_loge(eff, (double)score), bits;
+    hsp_t h;
     if (le > 0.0) le = floor(le * 100.0 + 0.5) / 100.0; /* 0x4077ec-0x407829 */
     else le = floor(le * 100.0 - 0.5) / 100.0;          /* 0x407b60-0x407b8f */
     bits = floor(ka_bits((double)score) * 100.0 + 0.5) / 100.0;
-    if (!(score > 30) && !(LOGE_THR > le)) return;      /* 0x4078e4-0x4078f9 */
+    hp->loge = le;
+    if (!(score > 30) && !(LOGE_THR > le)) return 0;    /* 0x4078e4-0x4078f9 */
     h.sidx = sidx; h.score = score; h.bits = bits; h.loge = le;
     h.alnlen = alnlen; h.gaps = gapopens; h.mism = alnlen - nmatch - gaptotal;
     h.ident = (double)nmatch * 100.0 / (double)alnlen;
-    h.frame = frame; { static int seqno = 0; if (getenv("RS_SEQNO")) h.mism = seqno++; }
+    h.frame = frame;
     h.qaas = qbeg - qbwd;
     h.qaae = qbeg + qfwd - 1 + seedlen;
     h.ds = dbeg - dbwd;
@@ -804,6 +807,19 @@ static void cal_res(qstate *qs, int frame, int qbeg, int sidx, int dbeg, int see
         h.qnts = L - (qbeg - qbwd) * 3 - (frame - 3);
         h.qnte = h.qnts + 1 - (qfwd + qbwd + seedlen) * 3;
     }
+    *hp = h;
+    return 1;
+}
+
+/* ... and the rest of CalRes: the record into the read's results */
+static void cal_res(qstate *qs, int frame, int qbeg, int sidx, int dbeg, int seedlen,
+                    int score, int nmatch, int qfwd, int dfwd, int qbwd, int dbwd,
+                    int alnlen, int gapopens, int gaptotal)
+{
+    hsp_t h, *v;
+    int lo, hi, pos;
+    if (!cal_res_record(&qs->eff, qs->ntlen, frame, qbeg, sidx, dbeg, seedlen, score, nmatch, qfwd, dfwd, qbwd, dbwd, alnlen, gapopens, gaptotal, &h)) return;
+    { static int seqno = 0; if (getenv("RS_SEQNO")) h.mism = seqno++; }
     /* lower_bound on subject (0x4082b0-0x40831e), duplicate test against that one element
      * (0x4083b0-0x408446), otherwise insert in front of it (_M_insert_equal_ with hint) */
     v = qs->res.v; lo = 0; hi = qs->res.n;
@@ -823,14 +839,12 @@ static void cal_res(qstate *qs, int frame, int qbeg, int sidx, int dbeg, int see
     v[pos] = h; qs->res.n++;
 }
 
-/* CHashSearch::AlignSeqs@0x413370 followed by the CalRes call of ExtendSeq2Set 0x414150-0x41422a.
- * q/qlen: frame codes; qpos: start of the (grown) seed; d/dlen/dpos likewise; L grown seed length. */
-static void align_and_record(qstate *qs, int frame, const uint8_t *q, int qlen, int qpos,
-                             int sidx, const uint8_t *d, int dlen, int dpos, int L, int score, int nmatch)
+/* the two ungapped x-drop walks of AlignSeqs@0x413370 from the grown seed (qpos, dpos, L) with the seed's score s0: how far each went, the
+ * score and the identities of the ungapped segment (nmatch comes in as the seed's identities) */
+static void ungapped_walks(const uint8_t *q, int qlen, int qpos, const uint8_t *d, int dlen, int dpos, int L, int s0,
+                           int *qfwd_o, int *qbwd_o, int *score_o, int *nmatch_io)
 {
-    int qfwd = 0, dfwd = 0, qbwd = 0, dbwd = 0, s0 = score, total, i;
-    int ungapped_len, alnlen, gapopens = 0, gaptotal = 0;
-    int nr = 0, nl = 0; /* gapped runs on the right / left */
+    int qfwd = 0, qbwd = 0, score, total, i, nmatch = *nmatch_io;
     /* forward ungapped x-drop (0x4136e0-0x4137a7) */
     {
         int n1 = qlen - qpos - L, n2 = dlen - dpos - L, gain = 0, bl = 0, bi = 0;
@@ -847,7 +861,7 @@ static void align_and_record(qstate *qs, int frame, const uint8_t *q, int qlen, 
             }
             gain = best - s0;
         }
-        nmatch += bi; qfwd += bl; dfwd += bl; score = s0 + gain;
+        nmatch += bi; qfwd += bl; score = s0 + gain;
         total = gain;
     }
     /* backward ungapped x-drop from the seed score (0x413600-0x4136d7) */
@@ -866,8 +880,21 @@ static void align_and_record(qstate *qs, int frame, const uint8_t *q, int qlen, 
             }
             gain = best - s0;
         }
-        nmatch += bi; qbwd += bl; dbwd += bl; score = s0 + gain + total;
+        nmatch += bi; qbwd += bl; score = s0 + gain + total;
     }
+    *qfwd_o = qfwd; *qbwd_o = qbwd; *score_o = score; *nmatch_io = nmatch;
+}
+
+/* CHashSearch::AlignSeqs@0x413370 followed by the CalRes call of ExtendSeq2Set 0x414150-0x41422a.
+ * q/qlen: frame codes; qpos: start of the (grown) seed; d/dlen/dpos likewise; L grown seed length. */
+static void align_and_record(qstate *qs, int frame, const uint8_t *q, int qlen, int qpos,
+                             int sidx, const uint8_t *d, int dlen, int dpos, int L, int score, int nmatch)
+{
+    int qfwd, dfwd, qbwd, dbwd, i;
+    int ungapped_len, alnlen, gapopens = 0, gaptotal = 0;
+    int nr = 0, nl = 0; /* gapped runs on the right / left */
+    ungapped_walks(q, qlen, qpos, d, dlen, dpos, L, score, &qfwd, &qbwd, &score, &nmatch);
+    dfwd = qfwd; dbwd = qbwd;
     ungapped_len = qfwd + L + qbwd;
     /* gapped extension of both flanks (0x4134c8-0x413b38) */
     if (!(T_GAPTRIG > (double)score)) {
@@ -918,15 +945,13 @@ static int key_ub_less(unsigned qk, unsigned dbk)
     { int sh = (4 - n) * 4; int a = (int)qk >> sh, b = (int)dbk >> sh; if (a == b) return 0; return a < b; }
 }
 
-/* CHashSearch::ExtendSeq2Set@0x413b90 */
-static int extend_seq2set(qstate *qs, int seed, int seedlen, const uint8_t *key, int nkey,
-                          int frame, const uint8_t *q, int qlen, int qpos)
+/* the first part of ExtendSeq2Set@0x413b90: the postings [*nst_o, *ned_o) of bucket `seed` that the key selects; 0 when the function returns 0 before its posting loop */
+static int seed_range(const rs_db *db, int seed, int seedlen, const uint8_t *key, int nkey, int *nst_o, int *ned_o)
 {
-    const rs_db *db = qs->db;
     int64_t b0 = db->bstart[seed];
     int n = (int)(db->bstart[seed + 1] - b0), nst = 0, ned = n, i;
-    const uint32_t *post = db->post + b0;
     const uint16_t *keys = db->keys + b0;
+    *nst_o = *ned_o = 0;
     if (seedlen > 6) {
         unsigned qk = 0;
         int lo, len, m;
@@ -945,29 +970,58 @@ static int extend_seq2set(qstate *qs, int seed, int seedlen, const uint8_t *key,
         while (len > 0) { int half = len >> 1; if (key_ub_less(qk, keys[lo + half])) len = half; else { lo += half + 1; len -= half + 1; } }
         ned = lo;
     }
+    *nst_o = nst; *ned_o = ned;
+    return ned - nst;
+}
+
+/* the body of its posting loop for one hit, up to the gate: RS_HIT_PAST_END / _REDUNDANT / _GATE when the hit is dropped, else
+ * RS_HIT_EXTENDED; the grown seed, its score and identities are set in the last two cases */
+static int grow_hit(const uint8_t *q, int qlen, int qpos, const uint8_t *d, int dlen, int dpos, int seedlen, int nkey,
+                    int *qp_o, int *dp_o, int *L_o, int *score_o, int *ident_o)
+{
+    int score = 0, ident = 0, L, k, lim, qp = qpos, dp = dpos, back;
+    if ((unsigned)(dpos + seedlen) > (unsigned)dlen) return RS_HIT_PAST_END;             /* 0x413e96-0x413e9e */
+    if (qpos != 0 && dpos != 0 && g_grp[q[qpos - 1]] == g_grp[d[dpos - 1]] && nkey != 4) return RS_HIT_REDUNDANT; /* 0x4140c0-0x414132 */
+    for (k = 0; k < seedlen; k++) { score += SUB(q[qpos + k], d[dpos + k]); ident += (q[qpos + k] == d[dpos + k]); }
+    L = seedlen;
+    lim = dlen - dpos; if (lim > qlen - qpos) lim = qlen - qpos;                        /* 0x413fd2-0x413fe3 */
+    while (lim > L && g_grp[q[qpos + L]] == g_grp[d[dpos + L]]) {                       /* 0x413fe8-0x4142e3 */
+        score += SUB(q[qpos + L], d[dpos + L]); ident += (q[qpos + L] == d[dpos + L]); L++;
+    }
+    back = qpos < dpos ? qpos : dpos;                                                   /* 0x414020-0x41438f */
+    while (back > 0 && g_grp[q[qp - 1]] == g_grp[d[dp - 1]]) {
+        qp--; dp--; back--; L++;
+        score += SUB(q[qp], d[dp]); ident += (q[qp] == d[dp]);
+    }
+    *qp_o = qp; *dp_o = dp; *L_o = L; *score_o = score; *ident_o = ident;
+    return ((double)score >= T_SEEDSCORE && ident >= T_SEEDIDENT) ? RS_HIT_EXTENDED : RS_HIT_GATE; /* 0x414058-0x414073 */
+}
+
+/* CHashSearch::ExtendSeq2Set@0x413b90 (phase: the number of this call within the position, which only rs_seed_ranges reports) */
+static int extend_seq2set(qstate *qs, int seed, int seedlen, const uint8_t *key, int nkey,
+                          int frame, const uint8_t *q, int qlen, int qpos, int phase)
+{
+    const rs_db *db = qs->db;
+    const uint32_t *post = db->post + db->bstart[seed];
+    int nst, ned, i, r = seed_range(db, seed, seedlen, key, nkey, &nst, &ned);
+    if (qs->ranges) { /* rs_seed_ranges: the range is listed, its hits are not evaluated */
+        if (ned > nst && qs->nranges < qs->max_ranges) {
+            rs_range *g = &qs->ranges[qs->nranges];
+            g->pos = qpos; g->bucket = seed; g->seedlen = seedlen; g->nkey = nkey; g->nst = nst; g->ned = ned; g->phase = phase;
+        }
+        if (ned > nst) qs->nranges++;
+        return r;
+    }
     for (i = nst; i < ned; i++) {
         unsigned p = post[i];
         int dpos = (int)(p & 0x7ff), sidx = (int)(p >> 11);
         int dlen = (int)(db->off[sidx + 1] - db->off[sidx]);
         const uint8_t *d = db->res + db->off[sidx];
-        int score = 0, ident = 0, L, k, lim, qp = qpos, dp = dpos, back;
-        if ((unsigned)(dpos + seedlen) > (unsigned)dlen) continue;                       /* 0x413e96-0x413e9e */
-        if (qpos != 0 && dpos != 0 && g_grp[q[qpos - 1]] == g_grp[d[dpos - 1]] && nkey != 4) continue; /* 0x4140c0-0x414132 */
-        for (k = 0; k < seedlen; k++) { score += SUB(q[qpos + k], d[dpos + k]); ident += (q[qpos + k] == d[dpos + k]); }
-        L = seedlen;
-        lim = dlen - dpos; if (lim > qlen - qpos) lim = qlen - qpos;                    /* 0x413fd2-0x413fe3 */
-        while (lim > L && g_grp[q[qpos + L]] == g_grp[d[dpos + L]]) {                   /* 0x413fe8-0x4142e3 */
-            score += SUB(q[qpos + L], d[dpos + L]); ident += (q[qpos + L] == d[dpos + L]); L++;
-        }
-        back = qpos < dpos ? qpos : dpos;                                               /* 0x414020-0x41438f */
-        while (back > 0 && g_grp[q[qp - 1]] == g_grp[d[dp - 1]]) {
-            qp--; dp--; back--; L++;
-            score += SUB(q[qp], d[dp]); ident += (q[qp] == d[dp]);
-        }
-        if ((double)score >= T_SEEDSCORE && ident >= T_SEEDIDENT)                       /* 0x414058-0x414073 */
+        int score, ident, L, qp, dp;
+        if (grow_hit(q, qlen, qpos, d, dlen, dpos, seedlen, nkey, &qp, &dp, &L, &score, &ident) == RS_HIT_EXTENDED)
             align_and_record(qs, frame, q, qlen, qp, sidx, d, dlen, dp, L, score, ident);
     }
-    return ned - nst;
+    return r;
 }
 
 /* CHashSearch::Searching@0x415050, one frame */
@@ -1012,7 +1066,7 @@ static void search_frame(qstate *qs, int frame, const uint8_t *q, int qlen)
         if (qlen < pos + used) continue;            /* 0x415404-0x41540c */
         for (k = 6; k < used; k++) key[k - 6] = g_grp[q[pos + k]];
         if (freq != 0) {
-            r = extend_seq2set(qs, seed, used, key, used - 6, frame, q, qlen, pos);
+            r = extend_seq2set(qs, seed, used, key, used - 6, frame, q, qlen, pos, 0);
             prev = used;
             if (r <= 0) prev = 6;
         }
@@ -1027,7 +1081,7 @@ static void search_frame(qstate *qs, int frame, const uint8_t *q, int qlen)
                 for (j = 0; j < 10; j++) {
                     int v = start + j * st;
                     if (v == seed) continue;
-                    if (db->bstart[v + 1] != db->bstart[v]) extend_seq2set(qs, v, 10, key, 4, frame, q, qlen, pos);
+                    if (db->bstart[v + 1] != db->bstart[v]) extend_seq2set(qs, v, 10, key, 4, frame, q, qlen, pos, 1 + m * 10 + j);
                 }
             }
             /* then the same bucket with the first key residue substituted (0x416020-0x4165d6):
@@ -1037,7 +1091,7 @@ static void search_frame(qstate *qs, int frame, const uint8_t *q, int qlen)
                 for (k = 0; k < 10; k++) {
                     if (k == orig) continue;
                     key[0] = (uint8_t)k;
-                    extend_seq2set(qs, seed, 10, key, 4, frame, q, qlen, pos);
+                    extend_seq2set(qs, seed, 10, key, 4, frame, q, qlen, pos, 31 + k);
                 }
             }
         }
@@ -1177,6 +1231,40 @@ int rs_search_read(const rs_db *db, int query_index, const char *seq, int len, r
     for (f = 0; f < 6; f++) free(fr[f]);
     free(qs.res.v); free(qs.tr_r.m); free(qs.tr_r.l); free(qs.tr_l.m); free(qs.tr_l.l); free(qs.rev1); free(qs.rev2);
     return n;
+}
+
+int rs_extend_hit(const rs_db *db, int ntlen, int frame, int sidx, const uint8_t *q, int qlen, int qpos,
+                  const uint8_t *d, int dlen, int dpos, int seedlen, int nkey, rs_hit *out)
+{
+    init_tables();
+    memset(out, 0, sizeof *out);
+    if (!d) { d = db->res + db->off[sidx]; dlen = (int)(db->off[sidx + 1] - db->off[sidx]); }
+    out->why = grow_hit(q, qlen, qpos, d, dlen, dpos, seedlen, nkey, &out->qp, &out->dp, &out->L, &out->seed_score, &out->seed_ident);
+    if (out->why != RS_HIT_EXTENDED) return out->why;
+    out->nmatch = out->seed_ident;
+    ungapped_walks(q, qlen, out->qp, d, dlen, out->dp, out->L, out->seed_score, &out->qfwd, &out->qbwd, &out->score, &out->nmatch);
+    out->gapped = !(T_GAPTRIG > (double)out->score);
+    if (db && !out->gapped) {
+        ka_eff eff = ka_effective(db, ntlen / 3);
+        hsp_t h;
+        int alnlen = out->qfwd + out->L + out->qbwd;
+        memset(&h, 0, sizeof h);
+        out->kept = cal_res_record(&eff, ntlen, frame, out->qp, sidx, out->dp, out->L, out->score, out->nmatch, out->qfwd, out->qfwd,
+                                   out->qbwd, out->qbwd, alnlen, 0, 0, &h);
+        out->loge = h.loge;
+        if (out->kept) { out->qaas = h.qaas; out->qaae = h.qaae; out->ds = h.ds; out->de = h.de; out->qnts = h.qnts; out->qnte = h.qnte; out->alnlen = h.alnlen; out->mism = h.mism; }
+    }
+    return out->why;
+}
+
+int rs_seed_ranges(const rs_db *db, int frame, const uint8_t *q, int qlen, rs_range *out, int max_ranges)
+{
+    qstate qs;
+    rs_range none;
+    memset(&qs, 0, sizeof qs);
+    qs.db = db; qs.ranges = out ? out : &none; qs.max_ranges = out ? max_ranges : 0;
+    search_frame(&qs, frame, q, qlen);
+    return qs.nranges;
 }
 
 int rs_format_row(const rs_db *db, const rs_row *r, const char *qname, char *buf, int buflen)

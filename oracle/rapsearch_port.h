@@ -60,6 +60,30 @@ void rs_translate6(const char *seq, int len, uint8_t *out[6], int lens[6]);
  * the cells written), the DP rows that were run. */
 int rs_align_gapped(const uint8_t *seq1, const uint8_t *seq2, int n1, int n2, int out[8]);
 
+/* One seed hit: the body of ExtendSeq2Set's posting loop (0x413e68-0x414073) and the two ungapped walks of AlignSeqs
+ * (0x413600-0x4137a7), the pieces rs_search_read itself runs.  q, d: residue codes as rs_translate6 / rs_db_residues give them; d = NULL:
+ * subject sidx of db.  Returns `why`. */
+enum { RS_HIT_EXTENDED = 0, RS_HIT_PAST_END = 1, RS_HIT_REDUNDANT = 2, RS_HIT_GATE = 3 };
+typedef struct {
+    int32_t why;                        /* RS_HIT_*: the rest is set as far as the hit came */
+    int32_t qp, dp, L;                  /* the grown seed (why = EXTENDED or GATE) */
+    int32_t seed_score, seed_ident;     /* ... its score and identities, what the gate tests */
+    int32_t qfwd, qbwd, score, nmatch;  /* the ungapped segment (EXTENDED) */
+    int32_t gapped;                     /* T_GAPTRIG sends it to the gapped extension */
+    /* with a database, for a hit that is complete without the gapped extension: the record CalRes makes of it */
+    int32_t kept;                       /* CalRes keeps it (0: score <= 30 and log E not under the threshold) */
+    int32_t qaas, qaae, ds, de, qnts, qnte, alnlen, mism;
+    double  loge;                       /* rounded log10(E) (set whether kept or not) */
+} rs_hit;
+int rs_extend_hit(const rs_db *db, int ntlen, int frame, int sidx, const uint8_t *q, int qlen, int qpos,
+                  const uint8_t *d, int dlen, int dpos, int seedlen, int nkey, rs_hit *out);
+
+/* One frame: the posting ranges Searching@0x415050 hands to ExtendSeq2Set, in order - postings [nst, ned) of `bucket` - with the
+ * phase number csrc/mc_core.h documents above mc_enumerate_seeds (0 exact; 1 + 10 * stride index + j; 31 + substituted key residue).
+ * Empty ranges are not listed.  Returns the number of ranges (more than max_ranges: the list is truncated). */
+typedef struct { int32_t pos, bucket, seedlen, nkey, nst, ned, phase; } rs_range;
+int rs_seed_ranges(const rs_db *db, int frame, const uint8_t *q, int qlen, rs_range *out, int max_ranges);
+
 /* Format one row the way the binary does (ostream default %g precision, tab separated). */
 int rs_format_row(const rs_db *db, const rs_row *r, const char *qname, char *buf, int buflen);
 
