@@ -182,7 +182,8 @@ float mc_ahead_kernel_ms(const mc_handle *h);
  * of kernels (tests/test_gpu_gapped_chain.py), three uint32 - the distinct flanks it extended, those it sent to the second, wider
  * window, those it sent on to full-size rows (AlignGapped@0x40a550); defined for a range that ran unsplit (mc_stats.range_splits
  * == 0), 5: one uint32, the form of k_translate_seg the last range launched - 1: the block's reads staged in LDS, 0: read from global
- * memory (tests/test_gpu_translate_seg.py).  Returns the number of bytes (copied to dst when they fit cap_bytes; dst may be NULL to ask for the size), -1 on error. */
+ * memory (tests/test_gpu_translate_seg.py), 6: one uint32, its instantiation - 1: narrow (frames of at most 63 residues, reads up to
+ * 191 bp), 0: wide (tests/test_gpu_translate_seg_narrow.py).  Returns the number of bytes (copied to dst when they fit cap_bytes; dst may be NULL to ask for the size), -1 on error. */
 int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap_bytes, int32_t *record_bytes);
 /* Test aid (tests/test_gpu_owned.py): what the library holds of the HIP runtime in this process, over all handles - out[0] device
  * buffers, [1] pinned host buffers, [2] streams, [3] events.  Counted where each is made and destroyed (csrc/mc_owned.h). */

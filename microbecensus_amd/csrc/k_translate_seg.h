@@ -11,6 +11,12 @@
 // fall into different LDS banks (a pitch of 128 bytes put all of them into one)
 #define MC_TS_NLNF(FP) ((FP) + 2 > 24 ? (FP) + 2 : 24)
 #define MC_TS_STRIDE(FP) (((((FP) + 76 + 3) >> 2) | 1) << 2)
+// The narrow form (frames of at most MC_NARROW_MAXAA residues, reads up to 191 bp): the row's work list has MC_SEG_STK_NARROW entries,
+// prot[FP] comp[20] sv[24] stk[8], and only the 60 lanes that can have a frame get a row; lanes 60 - 63 are dealt windows of the
+// others' stretches like every lane, which takes comp and sv only: MC_TS_SPARE bytes each behind the rows.
+#define MC_TS_STRIDE_N(FP) (((((FP) + 44 + 2 * MC_SEG_STK_NARROW + 3) >> 2) | 1) << 2)
+#define MC_TS_SPARE 48
+#define MC_TS_ROWS_N(FP) ((size_t)(6 * MC_TS_READS) * MC_TS_STRIDE_N(FP) + (size_t)(MC_TS_THREADS - 6 * MC_TS_READS) * MC_TS_SPARE)
 #define MC_TS_STAGE(L) ((((MC_TS_READS * (L)) > MC_TS_WAVES * 1488 ? (MC_TS_READS * (L)) : MC_TS_WAVES * 1488) + 15) & ~15)   // read staging, later one McSegWaveLds per wave
 
 // ---- SEG for the 64 frames of a wave -----------------------------------------------------------------------------------
@@ -49,6 +55,7 @@ __device__ __forceinline__ unsigned long long mc_seg_key(double x)
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
+template <class BS>                                              // the bit sets of a frame: McBits192, or McBits64 for frames of at most MC_NARROW_MAXAA residues
 __device__ __forceinline__ void mc_seg_wave(const double *lnf, const int32_t *fx, const uint64_t *__restrict__ segtab, uint8_t *prot, int n, bool act, const McSegWS ws, McSegWaveLds *WL,
                                          const uint8_t *lds0, int lane MC_TS_PARAMS)
 {
@@ -58,11 +65,11 @@ __device__ __forceinline__ void mc_seg_wave(const double *lnf, const int32_t *fx
     int st = (act && W <= n) ? POP : DONE;
     // the window flags of the frame, once (mc_seg_mask_fx2 in mc_core.h is this function for one frame): every segment the
     // reference scans again reads its flags off them
-    McBits192 Flo, Fhi, lo, nhi, mk;
+    BS Flo, Fhi, lo, nhi, mk;
     mc_bits_clear(Flo); mc_bits_clear(Fhi); mc_bits_clear(lo); mc_bits_clear(nhi); mc_bits_clear(mk);
     if (st != DONE) {
         mc_seg_window_flags_rg(fx, prot, n, W, Flo, Fhi);
-        if (!(Flo.a | Flo.b | Flo.c)) st = DONE;
+        if (!mc_bits_any(Flo)) st = DONE;
     }
     int sp = 1, base = 0, m = 0, i = 0, lowlim = 0, loi = 0, hii = 0;
     bool any = false;
@@ -80,7 +87,7 @@ __device__ __forceinline__ void mc_seg_wave(const double *lnf, const int32_t *fx
                 lo = mc_seg_flags_of(Flo, base, m, W);
                 i = mc_bits_next(lo, 0);
                 if (i >= m) continue;
-                nhi = mc_bits_andnot(mc_bits_low(m), mc_seg_flags_of(Fhi, base, m, W));
+                nhi = mc_bits_andnot(mc_bits_low(mk, m), mc_seg_flags_of(Fhi, base, m, W));
                 lowlim = 0; st = SCAN;
             }
             loi = mc_bits_prev(nhi, i) + 1; if (loi < lowlim) loi = lowlim;
@@ -229,9 +236,9 @@ __device__ __forceinline__ void mc_seg_wave(const double *lnf, const int32_t *fx
             const int leftend = loi + lend, rightend = hii - (myn - rend - 1);
             if (i < leftend) {
                 const int l2 = loi, r2 = leftend - 1;
-                sp = mc_seg_push(ws.stk, sp, W, base + l2, r2 - l2 + 1);   // (never full: the bound at MC_SEG_STK, mc_core.h)
+                sp = mc_seg_push_cap(ws.stk, sp, W, base + l2, r2 - l2 + 1, BS::STK);   // (never full: the bound at MC_SEG_STK, mc_core.h)
             }
-            mk = mc_bits_or(mk, mc_bits_range(base + leftend, base + rightend));
+            mk = mc_bits_or(mk, mc_bits_range(mk, base + leftend, base + rightend));
             any = true;
             lowlim = ((hii < rightend) ? hii : rightend) + 1;
             i = mc_bits_next(lo, lowlim);
@@ -283,9 +290,15 @@ __device__ __forceinline__ int mc_translate_frame_lds(const uint8_t *cod, const 
 // One thread per (read, frame).  The workgroup's reads are staged into LDS with coalesced loads, every thread translates its
 // frame into its own LDS row, the wave runs SEG on its frames (mc_seg_wave) and writes them back with coalesced stores.
 // LDS per workgroup: max(10 L, 1,488) + ln n! + 64 (FP + 76) bytes (~10 KB at 150 bp; the staging area is reused by the SEG
-// queues) - the registers (127) allow 16 waves per CU, the LDS holds 15.
-template <bool STAGED>                                           // STAGED: the block's reads go through LDS (coalesced); otherwise each thread
-__global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(MC_TS_THREADS) k_translate_seg(const McTables *__restrict__ T, const uint8_t *__restrict__ reads, int L,   // walks its read in global memory and the LDS it saves buys a workgroup per CU (long reads)
+// queues) - the registers (127) allow 16 waves per CU, the LDS holds 15.  NARROW: max(10 L, 1,488) + ln n! + 60 (FP + 52) + 4 x 48 bytes
+// (8,608 at 150 bp, 8,928 with the static 320) and 92 registers.
+// NARROW (frames of at most MC_NARROW_MAXAA residues): one-word bit sets and the short row.  Beside the seed kernel (80 registers, four
+// waves per SIMD, 2 x 53,248 B of LDS at 150 bp) a wave of 120 registers and 10,704 B is resident once per SIMD and five times per CU;
+// at 96 registers and under 9,216 B it is resident twice per SIMD and six times per CU: hence five waves per SIMD here.
+template <bool NARROW> struct McTsBits { typedef McBits192 T; };
+template <> struct McTsBits<true> { typedef McBits64 T; };
+template <bool STAGED, bool NARROW = false>                      // STAGED: the block's reads go through LDS (coalesced); otherwise each thread
+__global__ void __attribute__((amdgpu_waves_per_eu(NARROW ? 5 : 4, NARROW ? 5 : 4))) __launch_bounds__(MC_TS_THREADS) k_translate_seg(const McTables *__restrict__ T, const uint8_t *__restrict__ reads, int L,   // walks its read in global memory and the LDS it saves buys a workgroup per CU (long reads)
                                                        int64_t nreads, uint8_t *__restrict__ frames, int FP, const uint64_t *__restrict__ segtab)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -293,7 +306,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(MC_
     const int64_t r0 = (int64_t)blockIdx.x * MC_TS_READS;
     const int nr = (int)((nreads - r0) < MC_TS_READS ? (nreads - r0) : MC_TS_READS);
     const int rbytes = nr * L;
-    const int stride = MC_TS_STRIDE(FP);                         // per-thread LDS row: prot[FP] comp[20] sv[24] stk[32]
+    const int stride = NARROW ? MC_TS_STRIDE_N(FP) : MC_TS_STRIDE(FP);   // per-thread LDS row: prot[FP] comp[20] sv[24] stk[32] (NARROW: stk[8])
     __shared__ int32_t fxs[64];                                  // fixed-point entropy tables (mc_seg_mask_fx)
 #ifdef MC_EXP_TIMING
     const int lane = mc_lane();
@@ -320,12 +333,14 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(MC_
     MC_TS_TICK(9);
     const int lr = tid / 6, f = tid - lr * 6;
     uint8_t *prot = rows + (size_t)tid * stride;
+    uint8_t *wsp = prot + FP;                                    // comp, sv and the work list
+    if (NARROW && tid >= 6 * MC_TS_READS) { prot = rows; wsp = rows + (size_t)(6 * MC_TS_READS) * stride + (size_t)(tid - 6 * MC_TS_READS) * MC_TS_SPARE; }   // (lr == MC_TS_READS >= nr: no frame, prot is never touched)
     int n = 0;
     if (lr < nr) n = mc_translate_frame_lds(cod, STAGED ? sreads + lr * L : reads + (r0 + lr) * L, L, f, prot);
     __syncthreads();                                             // the staged reads are dead: their space becomes the SEG queues
     {
-        McSegWS ws; ws.comp = prot + FP; ws.sv = prot + FP + 20; ws.stk = (int16_t *)(prot + FP + 44);
-        mc_seg_wave(lnf, fxs, segtab, prot, n, lr < nr, ws, (McSegWaveLds *)smem + (tid >> 6), rows, mc_lane() MC_TS_ARGS);   // (stretch offsets are kept relative to the rows: 256 x 252 bytes at most, 16 bits)
+        McSegWS ws; ws.comp = wsp; ws.sv = wsp + 20; ws.stk = (int16_t *)(wsp + 44);
+        mc_seg_wave<typename McTsBits<NARROW>::T>(lnf, fxs, segtab, prot, n, lr < nr, ws, (McSegWaveLds *)smem + (tid >> 6), rows, mc_lane() MC_TS_ARGS);   // (stretch offsets are kept relative to the rows: 256 x 252 bytes at most, 16 bits)
         if (lr < nr) for (int i = n; i < FP; i++) prot[i] = MC_INV;
     }
     __syncthreads();

@@ -293,13 +293,20 @@ static_assert(MC_MAXAA / 13 < MC_SEG_STK && MC_MAXAA <= 255, "the SEG work list:
 #endif
 #define MC_SEG_START(e) ((int)((uint16_t)(e) & 255))
 #define MC_SEG_LEN(e) ((int)((uint16_t)(e) >> 8))
-MC_HD int mc_seg_push(int16_t *stk, int sp, int W, int start, int len)
+MC_HD int mc_seg_push_cap(int16_t *stk, int sp, int W, int start, int len, int cap)
 { // returns the new number of entries
     if (len < W) return sp;
-    if (sp >= MC_SEG_STK) { MC_SEG_ON_FULL(); return sp; }
+    if (sp >= cap) { MC_SEG_ON_FULL(); return sp; }
     stk[sp] = (int16_t)(uint16_t)(start | (len << 8));
     return sp + 1;
 }
+MC_HD int mc_seg_push(int16_t *stk, int sp, int W, int start, int len) { return mc_seg_push_cap(stk, sp, W, start, len, MC_SEG_STK); }
+// Frames of at most MC_NARROW_MAXAA residues (reads up to 191 bp): the same bound, n / (W + 1), gives 63 / 13 = 4 entries for
+// W = 12 and 11 / 9 = 1 for W = 8.  The narrow form of k_translate_seg keeps a list of that size in its LDS row, and the bit sets
+// of such a frame fit one word (McBits64).  63 and not 64: a set over 64 positions would need a full-word mc_bits_low(64).
+#define MC_NARROW_MAXAA 63
+#define MC_SEG_STK_NARROW 4
+static_assert(MC_NARROW_MAXAA / 13 <= MC_SEG_STK_NARROW && MC_NARROW_MAXAA < 64, "the narrow SEG work list; no shift by 64 in McBits64");
 // Seg::segseq@0x43a9e0 with the recursion turned into a work list (the result is a set of positions,
 // so the order in which sub-ranges are handled does not matter).  H must hold n doubles.
 MC_HDN void mc_seg_mask(const McTables &T, const uint8_t *prot, int n, uint8_t *maskbits /* (MC_MAXAA+7)/8 */, double *H)
@@ -541,10 +548,20 @@ MC_HD void mc_seg_trim_rg(const double *lnfac, const uint8_t *s, int n, int *lef
     *leftend = *leftend + lend;
     *rightend = *rightend - (n - rend - 1);
 }
-struct McBits192 { uint64_t a, b, c; };   // bit set over <= 192 positions kept in registers (no dynamic indexing)
+struct McBits192 { uint64_t a, b, c; static constexpr int WORDS = 3, STK = MC_SEG_STK; };   // bit set over <= 192 positions kept in registers (no dynamic indexing)
 MC_HD void mc_bits_clear(McBits192 &x) { x.a = 0; x.b = 0; x.c = 0; }
 MC_HD void mc_bits_set(McBits192 &x, int i) { uint64_t m = 1ull << (i & 63); if (i < 64) x.a |= m; else if (i < 128) x.b |= m; else x.c |= m; }
 MC_HD bool mc_bits_test(const McBits192 &x, int i) { uint64_t w = (i < 64) ? x.a : (i < 128) ? x.b : x.c; return (w >> (i & 63)) & 1; }
+MC_HD bool mc_bits_any(const McBits192 &x) { return (x.a | x.b | x.c) != 0; }
+MC_HD void mc_bits_from_words(McBits192 &x, const uint64_t *w) { x.a = w[0]; x.b = w[1]; x.c = w[2]; }
+// The same set over <= MC_NARROW_MAXAA = 63 positions: one word, and every operation below is one shift or one scan.  Positions and
+// counts are 0 .. 63 throughout (a frame's residues, a segment's length m <= 63), so no shift count reaches 64.
+struct McBits64 { uint64_t a; static constexpr int WORDS = 1, STK = MC_SEG_STK_NARROW; };
+MC_HD void mc_bits_clear(McBits64 &x) { x.a = 0; }
+MC_HD void mc_bits_set(McBits64 &x, int i) { x.a |= 1ull << i; }
+MC_HD bool mc_bits_test(const McBits64 &x, int i) { return (x.a >> i) & 1; }
+MC_HD bool mc_bits_any(const McBits64 &x) { return x.a != 0; }
+MC_HD void mc_bits_from_words(McBits64 &x, const uint64_t *w) { x.a = w[0]; }
 
 MC_HDN void mc_seg_mask_ws(const McTables &T, uint8_t *prot, int n, const McSegWS &ws)
 { // masks prot in place (masked residues become MC_INV) - only AFTER all ranges were analysed on the original residues
@@ -723,15 +740,41 @@ MC_HD int mc_bits_prev(const McBits192 &x, int from)
     if (y.a) return 63 - __builtin_clzll(y.a);
     return -1;
 }
-// the flags of segment [base, base + m) read off the frame's window flags F (windows 0 .. nF-1 ... nF = n - W + 1)
-MC_HD McBits192 mc_seg_flags_of(const McBits192 &F, int base, int m, int W)
+// McBits64: x >> k, 0 <= k <= 63; bits [0, n), 0 <= n <= 63 (the callers' counts are positions of a frame of <= 63 residues, or
+// one more than a position <= 62)
+MC_HD McBits64 mc_bits_shr(const McBits64 &x, int k) { McBits64 r; r.a = x.a >> k; return r; }
+MC_HD McBits64 mc_bits_low(const McBits64 &, int n) { McBits64 r; r.a = (1ull << n) - 1; return r; }
+MC_HD McBits192 mc_bits_low(const McBits192 &, int n) { return mc_bits_low(n); }   // (the set's type chooses the form)
+MC_HD McBits64 mc_bits_and(const McBits64 &x, const McBits64 &y) { McBits64 r; r.a = x.a & y.a; return r; }
+MC_HD McBits64 mc_bits_or(const McBits64 &x, const McBits64 &y) { McBits64 r; r.a = x.a | y.a; return r; }
+MC_HD McBits64 mc_bits_andnot(const McBits64 &x, const McBits64 &y) { McBits64 r; r.a = x.a & ~y.a; return r; }
+MC_HD McBits64 mc_bits_range(const McBits64 &t, int lo, int hi) { return mc_bits_andnot(mc_bits_low(t, hi + 1), mc_bits_low(t, lo)); }   // bits [lo, hi], hi <= 62
+MC_HD McBits192 mc_bits_range(const McBits192 &, int lo, int hi) { return mc_bits_range(lo, hi); }
+// lowest set bit at or above `from` (64 if none: at or beyond every segment's length, which is all the callers' `i < m` ask)
+MC_HD int mc_bits_next(const McBits64 &x, int from)
 {
-    McBits192 r = mc_bits_and(mc_bits_shr(F, base), mc_bits_low(m - W + 1));
-    if (mc_bits_test(r, m - W)) r = mc_bits_or(r, mc_bits_range(m - W + 1, m - 1));
+    if (from >= 64) return 64;
+    const uint64_t y = x.a & (~0ull << from);
+    return y ? __builtin_ctzll(y) : 64;
+}
+// highest set bit at or below `from` (-1 if none), from <= 62
+MC_HD int mc_bits_prev(const McBits64 &x, int from)
+{
+    if (from < 0) return -1;
+    const uint64_t y = x.a & ((2ull << from) - 1);
+    return y ? 63 - __builtin_clzll(y) : -1;
+}
+// the flags of segment [base, base + m) read off the frame's window flags F (windows 0 .. nF-1 ... nF = n - W + 1)
+template <class B>
+MC_HD B mc_seg_flags_of(const B &F, int base, int m, int W)
+{
+    B r = mc_bits_and(mc_bits_shr(F, base), mc_bits_low(F, m - W + 1));
+    if (mc_bits_test(r, m - W)) r = mc_bits_or(r, mc_bits_range(F, m - W + 1, m - 1));
     return r;
 }
 // F: the window flags of a frame (one incremental pass; comp: 20 bytes of workspace)
-MC_HD void mc_seg_window_flags(const int32_t *fx, const uint8_t *s, int n, int W, uint8_t *comp, McBits192 &Flo, McBits192 &Fhi)
+template <class B>
+MC_HD void mc_seg_window_flags(const int32_t *fx, const uint8_t *s, int n, int W, uint8_t *comp, B &Flo, B &Fhi)
 {
     mc_bits_clear(Flo); mc_bits_clear(Fhi);
     int S = 0, t = 0;
@@ -749,7 +792,8 @@ MC_HD void mc_seg_window_flags(const int32_t *fx, const uint8_t *s, int n, int W
 // The same pass with the composition in registers (20 counts of 4 bits: a window holds at most 12 residues).  With the counts in
 // memory every step is a chain of dependent byte accesses - read a count, look its term up, write it back, and the next read
 // must wait for that write; here the loop stores nothing, so the loads of the residues and of the terms run ahead.
-MC_HD void mc_seg_window_flags_rg(const int32_t *fx, const uint8_t *s, int n, int W, McBits192 &Flo, McBits192 &Fhi)
+template <class B>
+MC_HD void mc_seg_window_flags_rg(const int32_t *fx, const uint8_t *s, int n, int W, B &Flo, B &Fhi)
 {
     uint64_t clo = 0; uint32_t chi = 0;
     int S = 0, t = 0;
@@ -767,7 +811,7 @@ MC_HD void mc_seg_window_flags_rg(const int32_t *fx, const uint8_t *s, int n, in
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-    for (int q = 0; q < 3; q++) {
+    for (int q = 0; q < B::WORDS; q++) {
         uint64_t a = 0, b = 0;
         const int x1 = nwin - 64 * q < 64 ? nwin - 64 * q : 64;
         for (int xx = 0; xx < x1; xx++) {
@@ -792,17 +836,19 @@ MC_HD void mc_seg_window_flags_rg(const int32_t *fx, const uint8_t *s, int n, in
         }
         wl[q] = a; wh[q] = b;
     }
-    Flo.a = wl[0]; Flo.b = wl[1]; Flo.c = wl[2];
-    Fhi.a = wh[0]; Fhi.b = wh[1]; Fhi.c = wh[2];
+    mc_bits_from_words(Flo, wl);
+    mc_bits_from_words(Fhi, wh);
 }
+// B = McBits192: any frame; B = McBits64: frames of at most MC_NARROW_MAXAA residues, with a work list of MC_SEG_STK_NARROW entries
+template <class B = McBits192>
 MC_HDN void mc_seg_mask_fx2(const double *lnfac, const int32_t *fx, uint8_t *prot, int n, const McSegWS &ws)
 {
     const int W = (n <= 11) ? 8 : 12;
     if (W > n) return;
-    McBits192 Flo, Fhi, mk;
+    B Flo, Fhi, mk;
     mc_bits_clear(mk);
     mc_seg_window_flags(fx, prot, n, W, ws.comp, Flo, Fhi);
-    if (!(Flo.a | Flo.b | Flo.c)) return;
+    if (!mc_bits_any(Flo)) return;
     int sp = 1;
     ws.stk[0] = (int16_t)(uint16_t)(n << 8);
     bool any = false;
@@ -811,8 +857,8 @@ MC_HDN void mc_seg_mask_fx2(const double *lnfac, const int32_t *fx, uint8_t *pro
         const int base = MC_SEG_START(ws.stk[sp]), m = MC_SEG_LEN(ws.stk[sp]);
         const uint8_t *s = prot + base;
         if (W > m) continue;
-        const McBits192 lo = mc_seg_flags_of(Flo, base, m, W), hi = mc_seg_flags_of(Fhi, base, m, W);
-        const McBits192 nhi = mc_bits_andnot(mc_bits_low(m), hi);                 // positions of the segment that are NOT high
+        const B lo = mc_seg_flags_of(Flo, base, m, W), hi = mc_seg_flags_of(Fhi, base, m, W);
+        const B nhi = mc_bits_andnot(mc_bits_low(mk, m), hi);                     // positions of the segment that are NOT high
         int lowlim = 0;
         for (int i = mc_bits_next(lo, 0); i < m; i = mc_bits_next(lo, i + 1)) {
             int loi = mc_bits_prev(nhi, i) + 1; if (loi < lowlim) loi = lowlim;
@@ -822,9 +868,9 @@ MC_HDN void mc_seg_mask_fx2(const double *lnfac, const int32_t *fx, uint8_t *pro
             else mc_seg_trim_ws(lnfac, s + leftend, rightend - leftend + 1, &leftend, &rightend, ws);
             if (i < leftend) {
                 const int lend = loi, rend = leftend - 1;
-                sp = mc_seg_push(ws.stk, sp, W, base + lend, rend - lend + 1);
+                sp = mc_seg_push_cap(ws.stk, sp, W, base + lend, rend - lend + 1, B::STK);
             }
-            mk = mc_bits_or(mk, mc_bits_range(base + leftend, base + rightend));
+            mk = mc_bits_or(mk, mc_bits_range(mk, base + leftend, base + rightend));
             any = true;
             i = (hii < rightend) ? hii : rightend;
             lowlim = i + 1;

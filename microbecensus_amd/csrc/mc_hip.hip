@@ -65,6 +65,7 @@ struct McCtx {
     McEvent ev_wait[2]; bool waited = false;                       // around the stream's wait for a lookahead's kernel (range_begin); waited: this range's stream had one
     int64_t cap_reads = 0; int pool_len = 0;                       // the pools hold cap_reads reads of up to pool_len bases
     int ts_staged = -1;                                            // the form of k_translate_seg the last range launched (mc_debug_stage 5)
+    int ts_narrow = -1;                                            // ... and whether it was the narrow instantiation (mc_debug_stage 6)
     uint32_t cap_tasks = 0, cap_gaps = 0, cap_hsps = 0, cap_rows = 0;
     // Two frame buffers (mc_ahead.h): d_frames is the RUNNING range's - the one every reader means - and a lookahead writes the other;
     // a range_begin that takes a lookahead makes that buffer the current one (frames_use).  Views 64 bytes in, behind an apron of MC_INV:
@@ -672,7 +673,7 @@ static int stage_a0(mc_handle *h, McCtx &c, hipStream_t st, const uint8_t *reads
 {
     uint8_t *frames = into + at * 6 * h->FP;                      // (FP is a multiple of 4: the kernel's word stores stay aligned)
     HIPCK(hipEventRecord(e0, st));
-    if (mc_translate_launch(h->d_T, h->d_segtab, reads, h->read_len, h->FP, n, frames, st, &c.ts_staged)) return -1;
+    if (mc_translate_launch(h->d_T, h->d_segtab, reads, h->read_len, h->FP, n, frames, st, &c.ts_staged, &c.ts_narrow)) return -1;
     HIPCK(hipEventRecord(e1, st));
     return 0;
 }
@@ -1020,9 +1021,11 @@ extern "C" int mc_ranges_in_flight(const mc_handle *h) { return h ? h->pipe_nout
 // (C_RETRY), those sent to full-size rows (C_RETRY2) - from the host copy of the counters that ended the range: only stage_b's
 // kernels touch these three, and the block is cleared by the next range's stage A.  Defined for a range that ran unsplit (after a
 // split they are the last piece's).
+// 5: the form of k_translate_seg the last range launched, one uint32 - 1 reads staged in LDS, 0 read from global memory.  6: its
+// instantiation, one uint32 - 1 narrow (frames of at most 63 residues: reads up to 191 bp), 0 wide.
 extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap_bytes, int32_t *record_bytes)
 {
-    if (!h || !h->run_set || what < 0 || what > 5) { g_err = "mc_debug_stage: bad argument"; return -1; }
+    if (!h || !h->run_set || what < 0 || what > 6) { g_err = "mc_debug_stage: bad argument"; return -1; }
     if (h->pipe_nout) { g_err = "mc_debug_stage: ranges are in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     ahead_drop(h);
@@ -1034,9 +1037,9 @@ extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap
         if (dst && (int64_t)sizeof v <= cap_bytes) memcpy(dst, v, sizeof v);
         return (int64_t)sizeof v;
     }
-    if (what == 5) {
-        if (c.ts_staged < 0) { g_err = "mc_debug_stage: no range has run"; return -1; }
-        const uint32_t v = (uint32_t)c.ts_staged;
+    if (what == 5 || what == 6) {
+        if (c.ts_staged < 0 || c.ts_narrow < 0) { g_err = "mc_debug_stage: no range has run"; return -1; }
+        const uint32_t v = (uint32_t)(what == 5 ? c.ts_staged : c.ts_narrow);
         if (record_bytes) *record_bytes = (int32_t)sizeof v;
         if (dst && (int64_t)sizeof v <= cap_bytes) memcpy(dst, &v, sizeof v);
         return (int64_t)sizeof v;

@@ -35,8 +35,10 @@ struct McRun { const McTables *T; McIndex X; const McClassPars *P; const int32_t
 struct McFork { hipStream_t side, side2; hipEvent_t fork, join, join2; };
 
 // ---- A0: translation + SEG ---------------------------------------------------------------------------------------------------------
-// k_translate_seg of n reads of L bases at `reads` into `frames`, in st.  staged (if given) receives the form that was launched.
-static int mc_translate_launch(const McTables *T, const uint64_t *segtab, const uint8_t *reads, int L, int FP, int64_t n, uint8_t *frames, hipStream_t st, int *staged_out = nullptr)
+// k_translate_seg of n reads of L bases at `reads` into `frames`, in st.  staged (if given) receives the form that was launched, narrow
+// (if given) whether it was the instantiation for frames of at most MC_NARROW_MAXAA residues.
+static int mc_translate_launch(const McTables *T, const uint64_t *segtab, const uint8_t *reads, int L, int FP, int64_t n, uint8_t *frames, hipStream_t st, int *staged_out = nullptr,
+                               int *narrow_out = nullptr)
 {
     const size_t lds_rest = (size_t)MC_TS_NLNF(FP) * 8 + (size_t)MC_TS_THREADS * MC_TS_STRIDE(FP);
     const size_t lds_staged = (size_t)MC_TS_STAGE(L) + lds_rest, lds_direct = (size_t)MC_TS_STAGE(0) + lds_rest;
@@ -46,7 +48,17 @@ static int mc_translate_launch(const McTables *T, const uint64_t *segtab, const 
     const size_t lds = staged ? lds_staged : lds_direct;
     if (staged_out) *staged_out = staged ? 1 : 0;
     const unsigned ts_blocks = (unsigned)((n + MC_TS_READS - 1) / MC_TS_READS);
-    if (staged) {
+    // Reads up to 191 bp: no frame has more than L / 3 <= MC_NARROW_MAXAA = 63 residues, so every position and every count of the SEG bit
+    // sets is below 64 (McBits64 never shifts by 64) and the work list holds at most 63 / 13 = 4 entries.  The choice between staged and
+    // direct stays the one above, made from the wide layout's sizes; the narrow launch only asks for less LDS (under 11 KB: no attribute).
+    const bool narrow = L / 3 <= MC_NARROW_MAXAA;
+    static_assert(MC_NARROW_MAXAA <= 63 && MC_SEG_STK_NARROW * 13 + 12 >= MC_NARROW_MAXAA, "the narrow form's one-word bit sets and four-entry work list");
+    if (narrow_out) *narrow_out = narrow ? 1 : 0;
+    if (narrow) {
+        const size_t lds_n = (size_t)MC_TS_STAGE(staged ? L : 0) + (size_t)MC_TS_NLNF(FP) * 8 + MC_TS_ROWS_N(FP);
+        if (staged) k_translate_seg<true, true><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds_n, st>>>(T, reads, L, n, frames, FP, segtab);
+        else k_translate_seg<false, true><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds_n, st>>>(T, reads, L, n, frames, FP, segtab);
+    } else if (staged) {
         if (lds > 48 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_translate_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         k_translate_seg<true><<<dim3(ts_blocks), dim3(MC_TS_THREADS), lds, st>>>(T, reads, L, n, frames, FP, segtab);
     } else {
