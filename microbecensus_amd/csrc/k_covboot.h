@@ -15,17 +15,13 @@ struct McCbLen {                                                    // the resid
 };
 
 // The shape of k_geneboot_collect: one thread per read, the one at its first row, walks the read's rows (mc_cb_read: k_abundance_cov's
-// walk with the span kept, a further copy of it - whoever edits one edits all) and slots are reserved per workgroup: ballot, per-wave
-// popcount, ONE atomic on the cursor per workgroup that assigned any; a lane writes at the workgroup's base + its rank among the
-// workgroup's assigned reads.  cur[0]: the cursor - it counts every assigned read, fitting or not; cur[1]: dropped.  A read whose slot is
-// not below capacity adds 1 to dropped and writes nothing: nothing is ever written behind the list.  map: the ids of a class run's batch,
-// or a null perm: the row's query is the id (one kernel for both: it is new, no fixed-length run's instructions change with it).
+// walk with the span kept, a further copy of it - whoever edits one edits all) and puts the read's entry into the list (mc_boot_put,
+// k_geneboot.h).  map: the ids of a class run's batch, or a null perm: the row's query is the id (one kernel for both: it is new, no
+// fixed-length run's instructions change with it).
 // Launched behind the tie bootstrap's kernel on the same rows where they lie (mc_abund_launch, mc_abund.h) - behind the fold, in gene space.
 __global__ void __launch_bounds__(256) k_covboot_collect(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, const uint32_t *__restrict__ off,
                                                          McCbEntry *list, unsigned long long capacity, unsigned long long *cur, McIdMap map)
 {
-    __shared__ uint32_t wcnt[4];
-    __shared__ unsigned long long base;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     bool hit = false;
     McCbEntry mine = {0u, 0u, 1, 0};
@@ -34,37 +30,14 @@ __global__ void __launch_bounds__(256) k_covboot_collect(McAbundPars A, const Mc
         const McCbLen len = {off};
         hit = mc_cb_read(pass, len, rows, nrows, i, nseq, mc_cb_id(map.perm, map.base, rows[i].query), &mine);
     }
-    const unsigned long long m = __ballot(hit);
-    const int lane = mc_lane(), w = (int)(threadIdx.x >> 6);
-    if (lane == 0) wcnt[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        base = tot ? atomicAdd(&cur[0], (unsigned long long)tot) : 0ull;
-    }
-    __syncthreads();
-    if (!hit) return;
-    uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; k++) rank += wcnt[k];
-    const unsigned long long slot = base + rank;
-    if (slot < capacity) list[slot] = mine;
-    else atomicAdd(&cur[1], 1ull);
+    mc_boot_put(hit, mine, list, capacity, cur);
 }
 
-// Grouping by gene, k_geneboot_scatter's scheme on the other entry: cursor[s] starts at the first slot of gene s in the grouped list - the
-// exclusive scan of the count table's `reads` - and idx[s] is the gene's compact index among the genes with reads.  One thread per entry
-// takes the next slot of its gene; the order within a gene is whatever the atomics give, and free: covering is an OR.  n entries in both
-// lists; a slot not below n, or a gene the count table has no read of (the table and the list disagree - the caller has checked that they
-// do not), is not written.
+// Grouping by gene (mc_boot_scatter, k_geneboot.h), into slices the count table's `reads` size
 __global__ void __launch_bounds__(256) k_covboot_scatter(const McCbEntry *__restrict__ list, long long n, int32_t nseq, uint32_t *cursor, const int32_t *__restrict__ idx,
                                                          McCbEntry *sorted)
 {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const McCbEntry e = list[i];
-    if (e.gene >= (uint32_t)nseq || idx[e.gene] < 0) return;
-    const uint32_t pos = atomicAdd(&cursor[e.gene], 1u);
-    if ((long long)pos < n) { McCbEntry o = e; o.gene = (uint32_t)idx[e.gene]; sorted[pos] = o; }
+    mc_boot_scatter(list, n, nseq, cursor, idx, sorted);
 }
 
 // The hot kernel.  A 2-D grid of (genes with reads) x (replicate tiles of MC_GB_LANES), one wave per block; a lane owns one replicate (its

@@ -7,18 +7,39 @@
 #include "k_abundance.h"
 #include "mc_geneboot.h"
 
-// The shape of k_abundance, and a walk of its own over a read's rows (a fourth copy of k_abundance's walk: whoever edits one edits all;
-// DESIGN.md 13.3 has why the walks are separate kernels - and this way the counting kernels are the same instructions with the switch on
-// or off).  Launched behind the counting kernel, k_ties and k_curve on the same rows (mc_abund_launch, mc_abund.h).
-// Slots are reserved per workgroup, k_abundance's `assigned` idiom: ballot, per-wave popcount, ONE atomic on the cursor per workgroup
-// that assigned any; a lane writes at the workgroup's base + its rank among the workgroup's assigned reads.  cur[0]: the cursor - it
-// counts every assigned read, fitting or not; cur[1]: dropped.  A read whose slot is not below capacity adds 1 to dropped and writes
-// nothing: nothing is ever written behind the list.
-__global__ void __launch_bounds__(256) k_geneboot_collect(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, McGbEntry *list, unsigned long long capacity,
-                                                          unsigned long long *cur)
+// Slot reservation at the end of a collect kernel of 256 threads, k_abundance's `assigned` idiom: ballot, per-wave popcount, ONE atomic on
+// the cursor per workgroup that has any hit; a lane writes `mine` at the workgroup's base + its rank among the workgroup's hits.  cur[0]:
+// the cursor - it counts every hit, fitting or not; cur[1]: dropped.  A hit whose slot is not below capacity adds 1 to dropped and writes
+// nothing: nothing is ever written behind the list.  Every thread of the workgroup calls it (two barriers).  The entry goes by value: by
+// reference the kernels come out longer.
+template <class E> __device__ __forceinline__ void mc_boot_put(bool hit, const E mine, E *list, unsigned long long capacity, unsigned long long *cur)
 {
     __shared__ uint32_t wcnt[4];
     __shared__ unsigned long long base;
+    const unsigned long long m = __ballot(hit);
+    const int lane = mc_lane(), w = (int)(threadIdx.x >> 6);
+    if (lane == 0) wcnt[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        base = tot ? atomicAdd(&cur[0], (unsigned long long)tot) : 0ull;
+    }
+    __syncthreads();
+    if (!hit) return;
+    uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (int k = 0; k < w; k++) rank += wcnt[k];
+    const unsigned long long slot = base + rank;
+    if (slot < capacity) list[slot] = mine;
+    else atomicAdd(&cur[1], 1ull);
+}
+
+// The shape of k_abundance, and a walk of its own over a read's rows (a fourth copy of k_abundance's walk: whoever edits one edits all;
+// DESIGN.md 13.3 has why the walks are separate kernels - and this way the counting kernels are the same instructions with the switch on
+// or off), and the read's entry into the list (mc_boot_put).  Launched behind the counting kernel, k_ties and k_curve on the same rows
+// (mc_abund_launch, mc_abund.h).
+__global__ void __launch_bounds__(256) k_geneboot_collect(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, McGbEntry *list, unsigned long long capacity,
+                                                          unsigned long long *cur)
+{
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     bool hit = false;
     McGbEntry mine = {0u, 0u};
@@ -34,21 +55,7 @@ __global__ void __launch_bounds__(256) k_geneboot_collect(McAbundPars A, const M
             if (bsub >= 0 && bsub < nseq) { hit = true; mine.q = (uint32_t)q; mine.gene = (uint32_t)bsub; }
         }
     }
-    const unsigned long long m = __ballot(hit);
-    const int lane = mc_lane(), w = (int)(threadIdx.x >> 6);
-    if (lane == 0) wcnt[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        base = tot ? atomicAdd(&cur[0], (unsigned long long)tot) : 0ull;
-    }
-    __syncthreads();
-    if (!hit) return;
-    uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; k++) rank += wcnt[k];
-    const unsigned long long slot = base + rank;
-    if (slot < capacity) list[slot] = mine;
-    else atomicAdd(&cur[1], 1ull);
+    mc_boot_put(hit, mine, list, capacity, cur);
 }
 
 // The id of a read whose rows carry a position `query` of a sorted batch and not the read's id (a class run, mc_set_abundance_classes):
@@ -58,12 +65,11 @@ struct McIdMap { const uint32_t *perm; int64_t base; };
 
 // k_geneboot_collect for the pieces of a class run: launched INSTEAD of it while the owner holds an id map (mc_abund_launch), the same
 // walk, the same slots, and the entry's id taken through `map`.  A second kernel and not a parameter of the first (a fifth copy of the
-// walk: whoever edits one edits all): the kernel of the fixed-length runs stays the instructions it was.
+// walk: whoever edits one edits all): the kernel of the fixed-length runs stays the instructions it was - and no body shared by the two
+// came out as the instructions they are (DESIGN.md 13.13 has the forms tried).
 __global__ void __launch_bounds__(256) k_geneboot_collect_mapped(McAbundPars A, const McRow *__restrict__ rows, uint32_t nrows, int32_t nseq, McGbEntry *list, unsigned long long capacity,
                                                                  unsigned long long *cur, McIdMap map)
 {
-    __shared__ uint32_t wcnt[4];
-    __shared__ unsigned long long base;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     bool hit = false;
     McGbEntry mine = {0u, 0u};
@@ -79,36 +85,27 @@ __global__ void __launch_bounds__(256) k_geneboot_collect_mapped(McAbundPars A, 
             if (bsub >= 0 && bsub < nseq) { hit = true; mine.q = (uint32_t)(map.base + (int64_t)map.perm[q]); mine.gene = (uint32_t)bsub; }
         }
     }
-    const unsigned long long m = __ballot(hit);
-    const int lane = mc_lane(), w = (int)(threadIdx.x >> 6);
-    if (lane == 0) wcnt[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t tot = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        base = tot ? atomicAdd(&cur[0], (unsigned long long)tot) : 0ull;
-    }
-    __syncthreads();
-    if (!hit) return;
-    uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; k++) rank += wcnt[k];
-    const unsigned long long slot = base + rank;
-    if (slot < capacity) list[slot] = mine;
-    else atomicAdd(&cur[1], 1ull);
+    mc_boot_put(hit, mine, list, capacity, cur);
 }
 
-// Grouping by gene: cursor[s] starts at the first slot of gene s in the grouped list - the exclusive scan of the count table's `reads` - and
-// idx[s] is the gene's compact index among the genes with reads.  One thread per entry takes the next slot of its gene; the order within
-// a gene is whatever the atomics give, and free: the sums are integers.  n entries in both lists; a slot not below n, or a gene
-// the count table has no read of (the count table and the list disagree - the caller has checked that they do not), is not written.
-__global__ void __launch_bounds__(256) k_geneboot_scatter(const McGbEntry *__restrict__ list, long long n, int32_t nseq, uint32_t *cursor, const int32_t *__restrict__ idx,
-                                                          McGbEntry *sorted)
+// Grouping by gene, for every entry type (q, gene, ..): cursor[s] starts at the first slot of gene s in the grouped list - the exclusive
+// scan of the pair table's first column (the count table's `reads`, the tie table's `candidates`) - and idx[s] is the gene's compact index
+// among the genes with entries.  One thread per entry takes the next slot of its gene; the order within a gene is whatever the atomics
+// give, and free: the sums are integers, covering is an OR.  n entries in both lists; a slot not below n, or a gene the table has no
+// entry of (the table and the list disagree - the caller has checked that they do not), is not written.
+template <class E> __device__ __forceinline__ void mc_boot_scatter(const E *__restrict__ list, long long n, int32_t nseq, uint32_t *cursor, const int32_t *__restrict__ idx, E *sorted)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const McGbEntry e = list[i];
+    const E e = list[i];
     if (e.gene >= (uint32_t)nseq || idx[e.gene] < 0) return;
     const uint32_t pos = atomicAdd(&cursor[e.gene], 1u);
-    if ((long long)pos < n) { McGbEntry o; o.q = e.q; o.gene = (uint32_t)idx[e.gene]; sorted[pos] = o; }
+    if ((long long)pos < n) { E o = e; o.gene = (uint32_t)idx[e.gene]; sorted[pos] = o; }
+}
+__global__ void __launch_bounds__(256) k_geneboot_scatter(const McGbEntry *__restrict__ list, long long n, int32_t nseq, uint32_t *cursor, const int32_t *__restrict__ idx,
+                                                          McGbEntry *sorted)
+{
+    mc_boot_scatter(list, n, nseq, cursor, idx, sorted);
 }
 
 // The shape of k_bootstrap: a 2-D grid of entry tiles x replicate tiles of MC_GB_LANES, one wave per block.  A lane owns one replicate
@@ -118,6 +115,8 @@ __global__ void __launch_bounds__(256) k_geneboot_scatter(const McGbEntry *__res
 // changes, and at the tile's end - the 64 lanes of a flush touch 512 consecutive bytes.  A gene that holds every read is spread over all
 // the tiles.  mat: ngenes x B counters, zeroed by the caller; an entry whose gene is not below ngenes (a slot the scatter left out) adds
 // nothing.
+// (k_tieboot_sums is this text on the other entry with one factor more: no body shared by the two came out as the instructions they
+// are - DESIGN.md 13.13 has the forms tried - so whoever edits one edits both.)
 __global__ void __launch_bounds__(MC_GB_LANES) k_geneboot_sums(const McGbEntry *__restrict__ sorted, long long n, long long per_tile, int32_t B, uint64_t seed, uint32_t ngenes, unsigned long long *mat)
 {
     const int lane = (int)threadIdx.x;

@@ -42,27 +42,19 @@ __global__ void __launch_bounds__(256) k_tieboot_collect(McAbundPars A, const Mc
     if (dropped) atomicAdd(&cur[1], (unsigned long long)dropped);
 }
 
-// Grouping by gene, k_geneboot_scatter's scheme on the other entry: cursor[s] starts at the first slot of gene s in the grouped list - the
-// exclusive scan of the tie table's `candidates` - and idx[s] is the gene's compact index among the genes with candidates.  One thread per
-// entry takes the next slot of its gene; the order within a gene is whatever the atomics give, and free: the sums are integers.  n
-// entries in both lists; a slot not below n, or a gene the tie table has no candidate of (the table and the list disagree - the caller has
-// checked that they do not), is not written.
+// Grouping by gene (mc_boot_scatter, k_geneboot.h), into slices the tie table's `candidates` size
 __global__ void __launch_bounds__(256) k_tieboot_scatter(const McTbEntry *__restrict__ list, long long n, int32_t nseq, uint32_t *cursor, const int32_t *__restrict__ idx,
                                                          McTbEntry *sorted)
 {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const McTbEntry e = list[i];
-    if (e.gene >= (uint32_t)nseq || idx[e.gene] < 0) return;
-    const uint32_t pos = atomicAdd(&cursor[e.gene], 1u);
-    if ((long long)pos < n) { McTbEntry o; o.q = e.q; o.gene = (uint32_t)idx[e.gene]; o.share_m1 = e.share_m1; sorted[pos] = o; }
+    mc_boot_scatter(list, n, nseq, cursor, idx, sorted);
 }
 
-// k_geneboot_sums on the other entry: the same 2-D grid of entry tiles x replicate tiles of MC_GB_LANES, one wave per block, per_tile =
-// mc_gb_per_tile of the ENTRY count; a lane owns one replicate and adds weight x share of every entry of the tile into a register (the
-// entry is the same for the whole wave: a uniform address), flushed with one 64-bit atomicAdd into mat[gene][b] whenever the tile's gene
-// changes, and at the tile's end.  mat: ngenes x B counters in units of 2^-32, zeroed by the caller; an entry whose gene is not below
-// ngenes (a slot the scatter left out) adds nothing.  No sum can wrap (mc_tieboot.h).
+// k_geneboot_sums on the other entry (its text with one factor more: whoever edits one edits both - no body shared by the two came out as
+// the instructions they are): the same 2-D grid of entry tiles x replicate tiles of MC_GB_LANES, one wave per block,
+// per_tile = mc_gb_per_tile of the ENTRY count; a lane owns one replicate and adds weight x share of every entry of the tile into a
+// register, flushed with one 64-bit atomicAdd into mat[gene][b] whenever the tile's gene changes, and at the tile's end.  mat: ngenes x B
+// counters in units of 2^-32, zeroed by the caller; an entry whose gene is not below ngenes (a slot the scatter left out) adds nothing.
+// No sum can wrap (mc_tieboot.h).
 __global__ void __launch_bounds__(MC_GB_LANES) k_tieboot_sums(const McTbEntry *__restrict__ sorted, long long n, long long per_tile, int32_t B, uint64_t seed, uint32_t ngenes, unsigned long long *mat)
 {
     const int lane = (int)threadIdx.x;

@@ -1,12 +1,12 @@
 // mc_abund.h - the one owner of the per-gene counts (mc_set_abundance), the coverage depth (mc_set_coverage), the tie accounting
-// (mc_set_ties), the rarefaction curve (mc_set_curve), the bootstrap of the counts (mc_set_gene_bootstrap), the bootstrap of the tie
-// shares (mc_set_tie_bootstrap), the bootstrap of the coverage columns (mc_set_coverage_bootstrap), the identity of the assigned reads (mc_set_identity) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels are launched on the rows of a range, and which buffer exists when.
+// (mc_set_ties), the rarefaction curve (mc_set_curve), the three list bootstraps - of the counts (mc_set_gene_bootstrap), of the tie
+// shares (mc_set_tie_bootstrap) and of the coverage columns (mc_set_coverage_bootstrap): one McBootList each - the identity of the
+// assigned reads (mc_set_identity) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels
+// are launched on the rows of a range, and which buffer exists when.
 // With a gene fold (mc_set_gene_fold, mc_fold.h) it also owns the fold of a range's rows from segments onto genes (k_fold.h), in front of everything else.
 // k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_covboot.h, k_groupboot.h, k_identity.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
-// hipSetDevice, a call here) and tests/emul/device_coverage.hip, device_ties.hip, device_curve.hip, device_geneboot.hip and device_abund_classes.hip launch through mc_abund_launch like range_end
-// (device_groupboot.hip also through mc_groupboot_launch, like the group bootstrap's read; device_tieboot.hip through mc_abund_launch and
-// mc_tieboot_launch, like the tie bootstrap's read; device_covboot.hip through mc_abund_launch and mc_covboot_launch, like the coverage
-// bootstrap's read).
+// hipSetDevice, a call here) and the harnesses of tests/emul/ launch through mc_abund_launch like range_end, and through mc_geneboot_launch,
+// mc_tieboot_launch, mc_covboot_launch, mc_groupboot_launch and mc_identity_launch like the reads.
 #pragma once
 #include "k_abundance.h"
 #include "k_coverage.h"
@@ -43,20 +43,16 @@ struct McAbundBufs { int32_t nseq; const uint32_t *off; unsigned long long *coun
 // the curve's part of a launch (null: the curve is off).  pts: the K points on the device; bins: the bin table; first: every residue's
 // lowest covering id, or null while coverage is off; ev: recorded behind k_curve
 struct McCurveBufs { int32_t K; const unsigned long long *pts; unsigned long long *bins; uint32_t *first; hipEvent_t ev; };
-// the bootstrap's part of a launch (null: the gene bootstrap is off).  list: `capacity` entries; cur: the cursor and `dropped`
-// (k_geneboot.h); ev: recorded behind k_geneboot_collect
-struct McGeneBootBufs { McGbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
-// the class ride of a launch (null: the rows are no piece of a class run).  map: the ids of the batch (k_geneboot.h); tab: the per-class
-// table of K classes (k_abund_classes.h); k, nreads: the piece's class and reads; ev: recorded behind k_abund_class_add
-// the tie bootstrap's part of a launch (null: it is off).  list: `capacity` entries; cur: the cursor and `dropped` (k_tieboot.h); ev:
-// recorded behind k_tieboot_collect
-struct McTieBootBufs { McTbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
-// the coverage bootstrap's part of a launch (null: it is off).  list: `capacity` entries; cur: the cursor and `dropped` (k_covboot.h); ev:
-// recorded behind k_covboot_collect.  The launch's B.off gives the genes' residues
-struct McCovBootBufs { McCbEntry *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
+// a list bootstrap's part of a launch (null: it is off), for the entry E of the gene (McGbEntry), tie (McTbEntry) or coverage bootstrap
+// (McCbEntry; the launch's B.off gives the genes' residues).  list: `capacity` entries; cur: the cursor and `dropped` (mc_boot_put,
+// k_geneboot.h); ev: recorded behind the collect kernel
+template <class E> struct McBootBufs { E *list; unsigned long long capacity; unsigned long long *cur; hipEvent_t ev; };
+using McGeneBootBufs = McBootBufs<McGbEntry>; using McTieBootBufs = McBootBufs<McTbEntry>; using McCovBootBufs = McBootBufs<McCbEntry>;
 // the identity's part of a launch (null: it is off).  hist: nseq x MC_ID_STRIDE counters; sums: nseq records (mc_identity.h, "Layout"); ev: recorded
 // behind k_identity
 struct McIdentBufs { uint32_t *hist; McIdSums *sums; hipEvent_t ev; };
+// the class ride of a launch (null: the rows are no piece of a class run).  map: the ids of the batch (k_geneboot.h); tab: the per-class
+// table of K classes (k_abund_classes.h); k, nreads: the piece's class and reads; ev: recorded behind k_abund_class_add
 struct McClassRide { McIdMap map; unsigned long long *tab; int32_t K, k; unsigned long long nreads; hipEvent_t ev; };
 
 // The kernels of a range's final rows (ascending read id), in `st`: the counting kernel - k_abundance_cov INSTEAD of k_abundance while
@@ -116,11 +112,14 @@ static int mc_abund_launch(const McAbundPars &A, const McAbundBufs &B, const McR
     return 0;
 }
 
-// The gene bootstrap's read: raw device pointers of one mc_gene_bootstrap.  list: the n collected entries; cursor: nseq slots, every gene's
-// first slot in the grouped list; idx: nseq compact indices; sorted: n entries; mat: ngenes x B counters, zeroed; scale: B doubles, m of
-// them used; out: ngenes x 6 doubles.  mc_gb_plan makes cursor and idx from the count table on the host: nseq values, at read time.
-struct McGeneBootRead { int32_t nseq, ngenes; long long n; const McGbEntry *list; uint32_t *cursor; const int32_t *idx; McGbEntry *sorted; unsigned long long *mat;
-                        const double *scale; int32_t B, m; uint64_t seed; double *out; };
+// A list bootstrap's read: raw device pointers of one read.  list: the n collected entries; cursor: nseq slots, every gene's first slot in
+// the grouped list; idx: nseq compact indices; sorted: n entries; mat: ngenes x B counters - the gene bootstrap's replicate counts, the tie
+// bootstrap's shares in units of 2^-32 (both zeroed), the coverage bootstrap's covered residues; scale: B doubles, m of them used (the
+// tie bootstrap's: scale x 2^-32, mc_tb_scale; the coverage bootstrap's: B ones, m == B); out: ngenes x 6 doubles.  mc_gb_plan makes cursor
+// and idx on the host from a pair table - the count table, or the head of the tie table (`candidates` where the other holds `reads`).
+template <class E> struct McBootRead { int32_t nseq, ngenes; long long n; const E *list; uint32_t *cursor; const int32_t *idx; E *sorted; unsigned long long *mat;
+                                       const double *scale; int32_t B, m; uint64_t seed; double *out; };
+using McGeneBootRead = McBootRead<McGbEntry>; using McTieBootRead = McBootRead<McTbEntry>;
 // start[s]: the exclusive scan of reads[s]; idx[s]: the compact index of a gene with reads, -1 of one without.  Returns the genes with reads
 static int32_t mc_gb_plan(const unsigned long long *tab, int32_t nseq, uint32_t *start, int32_t *idx, unsigned long long *total)
 {
@@ -129,60 +128,45 @@ static int32_t mc_gb_plan(const unsigned long long *tab, int32_t nseq, uint32_t 
     *total = at;
     return ng;
 }
-// The three kernels of a read between ev[0] and ev[1], in `st`: the scatter and the sums with n > 0, the summary with ngenes > 0
-static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
+// the kernels of an entry type (the coverage bootstrap has no sums: k_covboot_cover takes their place, mc_covboot_launch)
+template <class E> struct McBootKernels;
+template <> struct McBootKernels<McGbEntry> { static constexpr auto scatter = k_geneboot_scatter; static constexpr auto sums = k_geneboot_sums; };
+template <> struct McBootKernels<McTbEntry> { static constexpr auto scatter = k_tieboot_scatter; static constexpr auto sums = k_tieboot_sums; };
+template <> struct McBootKernels<McCbEntry> { static constexpr auto scatter = k_covboot_scatter; };
+// The kernels of a read between ev[0] and ev[1], in `st`: the entry type's scatter with n > 0, what `middle` issues on the grouped list,
+// and k_geneboot_summary on R.mat and R.scale with ngenes > 0
+template <class E, class Middle> static int mc_boot_read_launch(const McBootRead<E> &R, hipStream_t st, const hipEvent_t (&ev)[2], Middle middle)
 {
     HIPCK(hipEventRecord(ev[0], st));
-    if (R.n > 0) {
-        k_geneboot_scatter<<<dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st>>>(R.list, R.n, R.nseq, R.cursor, R.idx, R.sorted);
-        const long long per = mc_gb_per_tile(R.n, R.B);
-        k_geneboot_sums<<<dim3((unsigned)((R.n + per - 1) / per), (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.n, per, R.B, R.seed, (uint32_t)R.ngenes, R.mat);
-    }
+    if (R.n > 0) McBootKernels<E>::scatter<<<dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st>>>(R.list, R.n, R.nseq, R.cursor, R.idx, R.sorted);
+    middle();
     if (R.ngenes > 0) k_geneboot_summary<<<dim3((unsigned)R.ngenes), dim3(MC_GB_THREADS), 0, st>>>(R.mat, R.scale, R.B, R.m, R.out);
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(ev[1], st));
     return 0;
 }
-
-// The tie bootstrap's read: raw device pointers of one mc_tie_bootstrap, McGeneBootRead on the other entry.  list: the n collected entries;
-// cursor, idx: made by mc_gb_plan from the TIE table on the host (its pairs hold `candidates` where the count table holds `reads`);
-// sorted: n entries; mat: ngenes x B shares in units of 2^-32, zeroed; s32: B doubles, scale x 2^-32 (mc_tb_scale), m of them used
-struct McTieBootRead { int32_t nseq, ngenes; long long n; const McTbEntry *list; uint32_t *cursor; const int32_t *idx; McTbEntry *sorted; unsigned long long *mat;
-                       const double *s32; int32_t B, m; uint64_t seed; double *out; };
-// The three kernels of a read between ev[0] and ev[1], in `st`: the scatter and the sums with n > 0, k_geneboot_summary - the gene
-// bootstrap's own kernel, on this matrix and these scales - with ngenes > 0
-static int mc_tieboot_launch(const McTieBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
+// The gene and the tie bootstrap's read: the middle is the entry type's sums, with n > 0
+template <class E> static int mc_boot_launch(const McBootRead<E> &R, hipStream_t st, const hipEvent_t (&ev)[2])
 {
-    HIPCK(hipEventRecord(ev[0], st));
-    if (R.n > 0) {
-        k_tieboot_scatter<<<dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st>>>(R.list, R.n, R.nseq, R.cursor, R.idx, R.sorted);
+    return mc_boot_read_launch(R, st, ev, [&] {
+        if (R.n <= 0) return;
         const long long per = mc_gb_per_tile(R.n, R.B);
-        k_tieboot_sums<<<dim3((unsigned)((R.n + per - 1) / per), (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.n, per, R.B, R.seed, (uint32_t)R.ngenes, R.mat);
-    }
-    if (R.ngenes > 0) k_geneboot_summary<<<dim3((unsigned)R.ngenes), dim3(MC_GB_THREADS), 0, st>>>(R.mat, R.s32, R.B, R.m, R.out);
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(ev[1], st));
-    return 0;
+        McBootKernels<E>::sums<<<dim3((unsigned)((R.n + per - 1) / per), (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.n, per, R.B, R.seed, (uint32_t)R.ngenes, R.mat);
+    });
 }
-
-// The coverage bootstrap's read (mc_covboot.h): raw device pointers of one mc_coverage_bootstrap.  list: the n collected entries; cursor, idx:
-// made by mc_gb_plan from the count table on the host; sorted: n entries; genes: the ngenes genes with reads - slice, residues, need (0: no
-// detection) - made on the host; mat: ngenes x B covered residues; det: ngenes counts, zeroed, or null; ones: B doubles of 1.0; out: ngenes x 6
+static int mc_geneboot_launch(const McGeneBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2]) { return mc_boot_launch(R, st, ev); }
+static int mc_tieboot_launch(const McTieBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2]) { return mc_boot_launch(R, st, ev); }
+// The coverage bootstrap's read (mc_covboot.h): the fields of McBootRead (ones: its scales, B doubles of 1.0 - every replicate is used) and
+// genes: the ngenes genes with reads - slice, residues, need (0: no detection) - made on the host; det: ngenes counts, zeroed, or null
 struct McCovBootRead { int32_t nseq, ngenes; long long n; const McCbEntry *list; uint32_t *cursor; const int32_t *idx; McCbEntry *sorted; const McCbGene *genes; unsigned long long *mat;
                        unsigned long long *det; const double *ones; int32_t B; uint64_t seed; double *out; };
-// The three kernels of a read between ev[0] and ev[1], in `st`: the scatter with n > 0, the cover kernel and k_geneboot_summary - the gene
-// bootstrap's own kernel, on this matrix, every replicate used - with ngenes > 0
+// the middle is the cover kernel, with ngenes > 0
 static int mc_covboot_launch(const McCovBootRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
 {
-    HIPCK(hipEventRecord(ev[0], st));
-    if (R.n > 0) k_covboot_scatter<<<dim3((unsigned)((R.n + 255) / 256)), dim3(256), 0, st>>>(R.list, R.n, R.nseq, R.cursor, R.idx, R.sorted);
-    if (R.ngenes > 0) {
-        k_covboot_cover<<<dim3((unsigned)R.ngenes, (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.genes, R.B, R.seed, R.mat, R.det);
-        k_geneboot_summary<<<dim3((unsigned)R.ngenes), dim3(MC_GB_THREADS), 0, st>>>(R.mat, R.ones, R.B, R.B, R.out);
-    }
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(ev[1], st));
-    return 0;
+    const McBootRead<McCbEntry> L = {R.nseq, R.ngenes, R.n, R.list, R.cursor, R.idx, R.sorted, R.mat, R.ones, R.B, R.B, R.seed, R.out};
+    return mc_boot_read_launch(L, st, ev, [&] {
+        if (R.ngenes > 0) k_covboot_cover<<<dim3((unsigned)R.ngenes, (unsigned)((R.B + MC_GB_LANES - 1) / MC_GB_LANES)), dim3(MC_GB_LANES), 0, st>>>(R.sorted, R.genes, R.B, R.seed, R.mat, R.det);
+    });
 }
 
 // The group bootstrap's read (mc_groupboot.h): raw device pointers of one mc_group_bootstrap, behind a read that left mat.  mat: ngenes x B
@@ -215,6 +199,109 @@ static int mc_identity_launch(const McIdentRead &R, hipStream_t st, const hipEve
     return 0;
 }
 
+// ---- A list bootstrap's state -------------------------------------------------------------------------------------------------
+template <class Tp> static int fit_one(McDev<Tp> &d, bool want, size_t n) { if (!want) d.reset(); return want && !d ? d.alloc(n) : 0; }
+static int fit_one(McEvent &e, bool want) { if (!want) e.reset(); return want && !e ? e.create() : 0; }
+
+// The nouns of a read's two refusals: what the list holds, and which pair table sizes its slices and what that table counts
+struct McBootWords { const char *entries, *table, *counted, *tail; };
+static const McBootWords MC_BOOT_OF_READS = {"assigned reads", "count", "assigned reads", ""}, MC_BOOT_OF_TIES = {"entries", "tie", "candidates", " entries"};
+// What the prologue of a read learns on the host: the pair table, every gene's first slot and compact index (mc_gb_plan), the genes with
+// entries, the used replicates and the entries of the list
+struct McBootPlan { std::vector<unsigned long long> tab; std::vector<uint32_t> start; std::vector<int32_t> idx; int32_t ng = 0, m = 0; long long n = 0; };
+
+// The read's epilogue, from the compact rows of the genes (or groups) with entries to one row each, idx.size() of them: the ng x 6 doubles
+// of d_out into stats, a row without a compact index getting `empty` ..
+static int mc_boot_stats(const std::vector<int32_t> &idx, int32_t ng, const double *d_out, double empty, double *stats)
+{
+    std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
+    if (ng) HIPCK(hipMemcpy(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < idx.size(); s++)
+        for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * s + k] = idx[s] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)idx[s] + k] : empty;
+    return 0;
+}
+// .. and the ng x B counters of d_mat into rows, a row without a compact index getting zeros
+template <class T> static int mc_boot_rows(const std::vector<int32_t> &idx, int32_t ng, int32_t B, const unsigned long long *d_mat, T *rows)
+{
+    const size_t need = (size_t)ng * (size_t)B;
+    std::vector<unsigned long long> mat(need);
+    if (need) HIPCK(hipMemcpy(mat.data(), d_mat, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < idx.size(); s++)
+        for (size_t b = 0; b < (size_t)B; b++) rows[s * (size_t)B + b] = idx[s] >= 0 ? (T)mat[(size_t)idx[s] * (size_t)B + b] : 0;
+    return 0;
+}
+
+// What the gene, the tie and the coverage bootstrap each hold, for their entry E: the switch and the list's capacity; the list, its cursor
+// and dropped counter, the grouped list, the genes' cursors and compact indices, the scales, the output; the matrix and what it holds;
+// the event behind the collect kernel and the two around the kernels of a read; the collect kernel's and the reads' time since the last
+// zeroing.
+template <class E> struct McBootList {
+    bool on = false; int64_t cap = 0;
+    McDev<E> d_list, d_sorted; McDev<unsigned long long> d_cur, d_mat; McDev<uint32_t> d_cursor; McDev<int32_t> d_idx; McDev<double> d_scale, d_out;
+    size_t mat_slots = 0;                                          // what d_mat holds: a read grows it to ngenes x B
+    McEvent ev, ev_read[2];
+    float collect_ms = 0, read_ms = 0;
+    operator bool() const { return on; }
+
+    // its part of THE BUFFER RULE (McAbundance::fit): the switch is `want`; the buffers exist while it is on, the matrix once a read has sized it
+    int fit(bool want, size_t ns)
+    {
+        on = want;
+        if (!on) { cap = 0; collect_ms = read_ms = 0.f; d_mat.reset(); mat_slots = 0; }
+        return fit_one(d_list, on, (size_t)cap) || fit_one(d_sorted, on, (size_t)cap) || fit_one(d_cur, on, 2) || fit_one(d_cursor, on, ns) || fit_one(d_idx, on, ns) ||
+               fit_one(d_scale, on, MC_GB_MAXB) || fit_one(d_out, on, (size_t)MC_GB_NOUT * ns) || fit_one(ev, on) || fit_one(ev_read[0], on) || fit_one(ev_read[1], on);
+    }
+    int reset()                                                    // an empty list
+    {
+        if (d_cur) HIPCK(hipMemset(d_cur, 0, sizeof(unsigned long long) * 2));
+        collect_ms = read_ms = 0.f;
+        return 0;
+    }
+    McBootBufs<E> bufs() const { return {d_list, (unsigned long long)cap, d_cur, ev}; }
+    // A read's prologue on the host, under the caller's name `who`: the cursor (dropped: what did not fit the list - not zero: an error that
+    // names it, and nothing else is done), the pair table d_tab of nseq genes, mc_gb_plan (table and list disagree: an error), and the B
+    // scales, which go to the device.  setter: the switch's function, for the message
+    int plan(const char *who, const char *setter, const McBootWords &W, const unsigned long long *d_tab, int32_t nseq, int32_t B, const double *scale, McBootPlan &P, int64_t *dropped)
+    {
+        const size_t ns = (size_t)nseq;
+        unsigned long long cur[2];
+        HIPCK(hipMemcpy(cur, d_cur, sizeof cur, hipMemcpyDeviceToHost));
+        if (dropped) *dropped = (int64_t)cur[1];
+        if (cur[1] || cur[0] > (unsigned long long)cap) {
+            g_err = std::string(who) + ": " + std::to_string(cur[1]) + " " + W.entries + " did not fit the list of " + std::to_string(cap) + " entries (" + setter + "): dropped, no replicate is whole";
+            return -1;
+        }
+        P.tab.resize(mc_pair_slots(ns)); P.start.resize(ns); P.idx.resize(ns);
+        HIPCK(hipMemcpy(P.tab.data(), d_tab, P.tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        unsigned long long total = 0;
+        P.ng = mc_gb_plan(P.tab.data(), nseq, P.start.data(), P.idx.data(), &total);
+        if (total != cur[0]) { g_err = std::string(who) + ": the " + W.table + " table holds " + std::to_string(total) + " " + W.counted + ", the list " + std::to_string(cur[0]) + W.tail; return -1; }
+        P.n = (long long)cur[0]; P.m = 0;
+        for (int32_t b = 0; b < B; b++) P.m += mc_gb_used(scale[b]) ? 1 : 0;
+        HIPCK(hipMemcpy(d_scale, scale, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
+        return 0;
+    }
+    // .. and on the device: the matrix grown to ng x B, the genes' cursors and compact indices uploaded, the matrix zeroed in stream 0
+    // (zero; the cover kernel writes every counter).  What the kernels of the read take is returned in R
+    int stage(const McBootPlan &P, int32_t nseq, int32_t B, uint64_t seed, bool zero, McBootRead<E> &R)
+    {
+        const size_t ns = (size_t)nseq, need = (size_t)P.ng * (size_t)B;
+        if (need > mat_slots) { mat_slots = 0; if (d_mat.alloc(need)) return -1; mat_slots = need; }
+        HIPCK(hipMemcpy(d_cursor, P.start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_idx, P.idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
+        if (zero && need) HIPCK(hipMemsetAsync(d_mat, 0, sizeof(unsigned long long) * need, 0));
+        R = {nseq, P.ng, P.n, d_list, d_cursor, d_idx, d_sorted, d_mat, d_scale, B, P.m, seed, d_out};
+        return 0;
+    }
+    // the read's kernels, issued between ev_read[0] and ev_read[1], are waited for and their time is added to `ms`
+    int finish(float &ms)
+    {
+        HIPCK(hipEventSynchronize(ev_read[1]));
+        ms += ev_ms(ev_read[0], ev_read[1]);
+        return 0;
+    }
+};
+
 // ---- Owner --------------------------------------------------------------------------------------------------------------------
 // The nine switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
@@ -224,16 +311,9 @@ static int mc_identity_launch(const McIdentRead &R, hipStream_t st, const hipEve
 //     the any-depth's difference array                                           coverage and ties are on
 //     the curve's points, bin table, scan output, its three events                the curve is on
 //     the curve's first ids                                                       the curve and coverage are on
-//     the bootstrap's list, its cursor and dropped counter, the grouped list,
-//     the genes' cursors and compact indices, the scales, the output, its three events   the gene bootstrap is on
-//     the bootstrap's matrix of replicate counts                                  the gene bootstrap is on and a read has sized it
+//     a list bootstrap's buffers and three events (McBootList::fit)               it is on; its matrix once a read has sized it
+//     the coverage bootstrap's gene records and need's counts                     the coverage bootstrap is on
 //     the group bootstrap's CSR, gene_kb, output and its three events; its values and counts   the gene bootstrap is on and a group read has sized them
-//     the tie bootstrap's list, its cursor and dropped counter, the grouped list,
-//     the genes' cursors and compact indices, the scales, the output, its three events   the tie bootstrap is on
-//     the tie bootstrap's matrix of replicate shares                              the tie bootstrap is on and a read has sized it
-//     the coverage bootstrap's list, its cursor and dropped counter, the grouped list, the genes' cursors,
-//     compact indices and records, the ones, need's counts, the output, its three events   the coverage bootstrap is on
-//     the coverage bootstrap's matrix of covered residues                         the coverage bootstrap is on and a read has sized it
 //     the per-class table (k_abund_classes.h), its event                          the counts may ride on class runs
 //     the identity's histogram, sum records, scan output, levels, its three events   the identity is on
 //     the segment records, the genes' offsets, the edge counter, its two events   a gene fold is set (set_fold; with the counts on or off)
@@ -246,31 +326,21 @@ static int mc_identity_launch(const McIdentRead &R, hipStream_t st, const hipEve
 // frees its buffers and zeroes nothing of the others; the counts going off take the others with them.
 struct McAbundance {
     int32_t nseq = 0; size_t nres = 0; const uint32_t *off = nullptr;   // the database: bind(), once the index is on the device
-    bool on = false, cov = false, ties = false, curve = false, gboot = false; int32_t ngroups = 0, K = 0; int64_t gcap = 0;
+    bool on = false, cov = false, ties = false, curve = false; int32_t ngroups = 0, K = 0;
     McAbundPars pars = {};
     McDev<unsigned long long> d_counts, d_covout, d_ties, d_pts, d_bins, d_curveout; McDev<uint32_t> d_diff, d_diff_any, d_first; McDev<int32_t> d_group;
     McEvent ev_count[2], ev_cov[2], ev_ties;                       // around the counting kernel of a range; around a scan; behind k_ties
     McEvent ev_curve, ev_cscan[2];                                 // behind k_curve; around a scan of the curve
     float curve_ms = 0, cscan_ms = 0;                              // k_curve's, the curve scans' time since the last zeroing
-    McDev<McGbEntry> d_glist, d_gsorted; McDev<unsigned long long> d_gcur, d_gmat; McDev<uint32_t> d_gcursor; McDev<int32_t> d_gidx; McDev<double> d_gscale, d_gout;
-    size_t gmat_slots = 0;                                         // what d_gmat holds: a read grows it to ngenes x B
-    McEvent ev_gboot, ev_gread[2];                                 // behind k_geneboot_collect; around the kernels of a read
-    float gboot_ms = 0, gread_ms = 0;                              // k_geneboot_collect's, the reads' time since the last zeroing
-    // what d_gmat holds, so that a group read may take it over from the read before it: the replicates, the seed and the entries of the read that
+    McBootList<McGbEntry> gboot;                                   // the gene bootstrap (mc_geneboot.h)
+    // what gboot.d_mat holds, so that a group read may take it over from the read before it: the replicates, the seed and the entries of the read that
     // made it; gmat_n < 0: nothing - no read yet, or a range, a reset or a switch since (launch, reset, fit)
     int32_t gmat_B = 0; uint64_t gmat_seed = 0; long long gmat_n = -1;
-    // the tie bootstrap (mc_tieboot.h): the switch, the list's capacity, and the gene bootstrap's set of buffers once more on the other entry
-    bool tboot = false; int64_t tcap = 0;
-    McDev<McTbEntry> d_tlist, d_tsorted; McDev<unsigned long long> d_tcur, d_tmat; McDev<uint32_t> d_tcursor; McDev<int32_t> d_tidx; McDev<double> d_tscale, d_tout;
-    size_t tmat_slots = 0;                                         // what d_tmat holds: a read grows it to ngenes x B
-    McEvent ev_tboot, ev_tread[2];                                 // behind k_tieboot_collect; around the kernels of a read
-    float tboot_ms = 0, tread_ms = 0;                              // k_tieboot_collect's, the reads' time since the last zeroing
-    // the coverage bootstrap (mc_covboot.h): the switch, the list's capacity, and the gene bootstrap's set of buffers once more on the third entry
-    bool cboot = false; int64_t ccap = 0;
-    McDev<McCbEntry> d_clist, d_csorted; McDev<unsigned long long> d_ccur, d_cmat, d_cdet; McDev<uint32_t> d_ccursor; McDev<int32_t> d_cidx; McDev<McCbGene> d_cgene; McDev<double> d_cones, d_cout;
-    size_t cmat_slots = 0;                                         // what d_cmat holds: a read grows it to ngenes x B
-    McEvent ev_cboot, ev_cread[2];                                 // behind k_covboot_collect; around the kernels of a read
-    float cboot_ms = 0, cread_ms = 0;                              // k_covboot_collect's, the reads' time since the last zeroing
+    McBootList<McTbEntry> tboot;                                   // the tie bootstrap (mc_tieboot.h)
+    McBootList<McCbEntry> cboot;                                   // the coverage bootstrap (mc_covboot.h); its scales are B ones
+    McDev<McCbGene> d_cgene; McDev<unsigned long long> d_cdet;     // its genes with reads, and how many replicates reach need
+    // the names the unit harnesses of tests/emul/ read the owner's lists and the gene reads' time by
+    McDev<McGbEntry> &d_glist = gboot.d_list; McDev<unsigned long long> &d_gcur = gboot.d_cur; McDev<McCbEntry> &d_clist = cboot.d_list; float &gread_ms = gboot.read_ms;
     // the group bootstrap (mc_groupboot.h): the CSR of the groups with reads, the members' gene_kb, the replicate values and counts, the output
     McDev<uint32_t> d_grstart, d_grmember; McDev<double> d_grkb, d_grval, d_grout; McDev<unsigned long long> d_grcnt;
     size_t grval_slots = 0, grcnt_slots = 0;                       // what d_grval, d_grcnt hold: a group read grows them to ngrp x B
@@ -319,30 +389,11 @@ struct McAbundance {
         if (mc_owned_ck(hipMemcpy(d_pts, points, sizeof(unsigned long long) * (size_t)K, hipMemcpyHostToDevice), "hipMemcpy(d_pts, points)")) { (void)turn(curve, false); return -1; }
         return 0;
     }
-    // capacity: entries of the list, checked by the caller (mc_set_gene_bootstrap); 0: off.  On while on: a list of another size
-    int set_gene_bootstrap(int64_t capacity)
-    {
-        (void)turn(gboot, false);
-        if (capacity == 0) return 0;
-        gcap = capacity;
-        return turn(gboot, true);
-    }
-    // capacity: entries of the tie list, checked by the caller (mc_set_tie_bootstrap: ties and the gene bootstrap are on); 0: off.  On while on: a list of another size
-    int set_tie_bootstrap(int64_t capacity)
-    {
-        (void)turn(tboot, false);
-        if (capacity == 0) return 0;
-        tcap = capacity;
-        return turn(tboot, true);
-    }
-    // capacity: entries of the coverage list, checked by the caller (mc_set_coverage_bootstrap: counts and coverage are on); 0: off.  On while on: a list of another size
-    int set_coverage_bootstrap(int64_t capacity)
-    {
-        (void)turn(cboot, false);
-        if (capacity == 0) return 0;
-        ccap = capacity;
-        return turn(cboot, true);
-    }
+    // capacity: entries of the list, checked by the caller (mc_set_gene_bootstrap; mc_set_tie_bootstrap: ties and the gene bootstrap are on;
+    // mc_set_coverage_bootstrap: counts and coverage are on); 0: off.  On while on: a list of another size
+    int set_gene_bootstrap(int64_t capacity) { return set_list(gboot, capacity); }
+    int set_tie_bootstrap(int64_t capacity) { return set_list(tboot, capacity); }
+    int set_coverage_bootstrap(int64_t capacity) { return set_list(cboot, capacity); }
     // on: refused by the caller while the curve is on (mc_set_abundance_classes)
     int set_classes(bool to) { return turn(classes, to); }
     int set_identity(bool to) { return turn(ident, to); }
@@ -379,15 +430,13 @@ struct McAbundance {
         if (d_diff_any) HIPCK(hipMemset(d_diff_any, 0, sizeof(uint32_t) * mc_diff_slots(nres, (size_t)nseq)));
         if (d_bins) HIPCK(hipMemset(d_bins, 0, sizeof(unsigned long long) * mc_curve_bin_slots((size_t)K, (size_t)nseq)));
         if (d_first) HIPCK(hipMemset(d_first, 0xFF, sizeof(uint32_t) * nres));
-        if (d_gcur) HIPCK(hipMemset(d_gcur, 0, sizeof(unsigned long long) * 2));
-        if (d_tcur) HIPCK(hipMemset(d_tcur, 0, sizeof(unsigned long long) * 2));
-        if (d_ccur) HIPCK(hipMemset(d_ccur, 0, sizeof(unsigned long long) * 2));
+        if (gboot.reset() || tboot.reset() || cboot.reset()) return -1;
         if (d_cls) HIPCK(hipMemset(d_cls, 0, sizeof(unsigned long long) * MC_AC_SLOTS));
         if (d_edge) HIPCK(hipMemset(d_edge, 0, sizeof(unsigned long long)));
         if (d_idhist) HIPCK(hipMemset(d_idhist, 0, sizeof(uint32_t) * mc_id_hist_slots((size_t)nseq)));
         if (d_idsums) HIPCK(hipMemset(d_idsums, 0, sizeof(McIdSums) * (size_t)nseq));
         fold_ms = ident_ms = iscan_ms = 0.f;
-        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = gboot_ms = gread_ms = cls_ms = tboot_ms = tread_ms = cboot_ms = cread_ms = 0.f;
+        searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = cls_ms = 0.f;
         gmat_n = -1; grp_ms = grp_values_ms = grp_summary_ms = 0.f;
         return 0;
     }
@@ -409,10 +458,10 @@ struct McAbundance {
         const McAbundBufs B = {nseq, off, d_counts, d_diff, d_ties, d_group, d_diff_any};
         const hipEvent_t ev[3] = {ev_count[0], ev_count[1], ev_ties};
         const McCurveBufs C = {K, d_pts, d_bins, d_first, ev_curve};
-        const McGeneBootBufs G = {d_glist, (unsigned long long)gcap, d_gcur, ev_gboot};
+        const McGeneBootBufs G = gboot.bufs();
         const McClassRide R = {map, d_cls, map_K, piece_k, (unsigned long long)nreads, ev_cls};
-        const McTieBootBufs T = {d_tlist, (unsigned long long)tcap, d_tcur, ev_tboot};
-        const McCovBootBufs V = {d_clist, (unsigned long long)ccap, d_ccur, ev_cboot};
+        const McTieBootBufs T = tboot.bufs();
+        const McCovBootBufs V = cboot.bufs();
         const McIdentBufs I = {d_idhist, d_idsums, ev_ident};
         return mc_abund_launch(pars, B, rows, nr, st, ev, curve ? &C : nullptr, gboot ? &G : nullptr, riding() ? &R : nullptr, tboot ? &T : nullptr, cboot ? &V : nullptr, ident ? &I : nullptr);
     }
@@ -442,13 +491,11 @@ struct McAbundance {
     {
         add_searched(nreads); ms += ev_ms(ev_count[0], ev_count[1]);
         if (fold) fold_ms += ev_ms(ev_fold[0], ev_fold[1]);
-        if (ties) ties_ms += ev_ms(ev_count[1], ev_ties);
-        if (curve) curve_ms += ev_ms(ties ? ev_ties : ev_count[1], ev_curve);
-        if (gboot) gboot_ms += ev_ms(curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_gboot);
-        if (tboot) tboot_ms += ev_ms(ev_gboot, ev_tboot);          // (on only with the gene bootstrap)
-        if (cboot) cboot_ms += ev_ms(tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cboot);
-        if (ident) ident_ms += ev_ms(cboot ? ev_cboot : tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_ident);
-        if (riding()) cls_ms += ev_ms(ident ? ev_ident : cboot ? ev_cboot : tboot ? ev_tboot : gboot ? ev_gboot : curve ? ev_curve : ties ? ev_ties : ev_count[1], ev_cls);
+        hipEvent_t prev = ev_count[1];                              // the last event recorded, in mc_abund_launch's order
+        const auto part = [&prev](bool is_on, hipEvent_t e, float &t) { if (is_on) { t += ev_ms(prev, e); prev = e; } };
+        part(ties, ev_ties, ties_ms); part(curve, ev_curve, curve_ms);
+        part(gboot.on, gboot.ev, gboot.collect_ms); part(tboot.on, tboot.ev, tboot.collect_ms); part(cboot.on, cboot.ev, cboot.collect_ms);
+        part(ident, ev_ident, ident_ms); part(riding(), ev_cls, cls_ms);
     }
     void add_searched(int64_t nreads) { if (on) searched += nreads; }   // (mc_search_varlen: reads too short to have a frame are searched, and have no rows)
 
@@ -502,66 +549,24 @@ struct McAbundance {
     // and nothing else is computed.
     int read_gene_bootstrap(int32_t B, uint64_t seed, const double *scale, int64_t *counts, double *stats, int64_t *dropped)
     {
-        const size_t ns = (size_t)nseq;
-        std::vector<int32_t> idx(ns);
-        int32_t ng = 0, m = 0; float took = 0.f;
-        if (make_mat("mc_gene_bootstrap", B, seed, scale, false, idx, &ng, &m, dropped, &took)) return -1;
-        gread_ms += took;
-        const size_t need = (size_t)ng * (size_t)B;
-        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
-        if (ng) HIPCK(hipMemcpy(out.data(), d_gout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < ns; s++)                            // (a gene without reads: zero in every replicate)
-            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * s + k] = idx[s] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)idx[s] + k] : m ? 0.0 : mc_gb_nan();
-        if (!counts) return 0;
-        std::vector<unsigned long long> mat(need);
-        if (need) HIPCK(hipMemcpy(mat.data(), d_gmat, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < ns; s++)
-            for (size_t b = 0; b < (size_t)B; b++) counts[s * (size_t)B + b] = idx[s] >= 0 ? (int64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
-        return 0;
+        McBootPlan P;
+        if (make_mat("mc_gene_bootstrap", B, seed, scale, false, P, dropped, gboot.read_ms)) return -1;
+        if (mc_boot_stats(P.idx, P.ng, gboot.d_out, P.m ? 0.0 : mc_gb_nan(), stats)) return -1;   // (a gene without reads: zero in every replicate)
+        return counts ? mc_boot_rows(P.idx, P.ng, B, gboot.d_mat, counts) : 0;
     }
-    // The bootstrap of the tie shares as they stand (mc_tieboot.h): read_gene_bootstrap's contract on the other list.  shares (or null): nseq x B
-    // replicate shares in units of 2^-32; stats: nseq x 6 doubles of the values share x scale x 2^-32; dropped: the entries that did not fit the
-    // list - not zero: an error that names it, and nothing else is computed.
+    // The bootstrap of the tie shares as they stand (mc_tieboot.h): read_gene_bootstrap's contract on the tie list, its slices sized by the head of
+    // the tie table.  shares (or null): nseq x B replicate shares in units of 2^-32; stats: nseq x 6 doubles of the values share x scale x 2^-32;
+    // dropped: the entries that did not fit the list - not zero: an error that names it, and nothing else is computed.
     int read_tie_bootstrap(int32_t B, uint64_t seed, const double *scale, uint64_t *shares, double *stats, int64_t *dropped)
     {
-        const size_t ns = (size_t)nseq;
-        unsigned long long cur[2];
-        HIPCK(hipMemcpy(cur, d_tcur, sizeof cur, hipMemcpyDeviceToHost));
-        if (dropped) *dropped = (int64_t)cur[1];
-        if (cur[1] || cur[0] > (unsigned long long)tcap) {
-            g_err = "mc_tie_bootstrap: " + std::to_string(cur[1]) + " entries did not fit the list of " + std::to_string(tcap) + " entries (mc_set_tie_bootstrap): dropped, no replicate is whole";
-            return -1;
-        }
-        std::vector<unsigned long long> tab(mc_pair_slots(ns));      // (the head of the tie table: candidates where the count table has reads)
-        HIPCK(hipMemcpy(tab.data(), d_ties, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> start(ns); std::vector<int32_t> idx(ns);
-        unsigned long long total = 0;
-        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
-        if (total != cur[0]) { g_err = "mc_tie_bootstrap: the tie table holds " + std::to_string(total) + " candidates, the list " + std::to_string(cur[0]) + " entries"; return -1; }
         std::vector<double> s32((size_t)B);
-        int32_t m = 0;
-        for (int32_t b = 0; b < B; b++) { s32[(size_t)b] = mc_tb_scale(scale[b]); m += mc_gb_used(s32[(size_t)b]) ? 1 : 0; }
-        const size_t need = (size_t)ng * (size_t)B;
-        if (need > tmat_slots) { tmat_slots = 0; if (d_tmat.alloc(need)) return -1; tmat_slots = need; }
-        HIPCK(hipMemcpy(d_tscale, s32.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(d_tcursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(d_tidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
-        if (need) HIPCK(hipMemsetAsync(d_tmat, 0, sizeof(unsigned long long) * need, 0));
-        const McTieBootRead R = {nseq, ng, (long long)cur[0], d_tlist, d_tcursor, d_tidx, d_tsorted, d_tmat, d_tscale, B, m, seed, d_tout};
-        const hipEvent_t ev[2] = {ev_tread[0], ev_tread[1]};
-        if (mc_tieboot_launch(R, 0, ev)) return -1;
-        HIPCK(hipEventSynchronize(ev_tread[1]));
-        tread_ms += ev_ms(ev_tread[0], ev_tread[1]);
-        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
-        if (ng) HIPCK(hipMemcpy(out.data(), d_tout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < ns; s++)                            // (a gene without candidates: zero in every replicate)
-            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * s + k] = idx[s] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)idx[s] + k] : m ? 0.0 : mc_gb_nan();
-        if (!shares) return 0;
-        std::vector<unsigned long long> mat(need);
-        if (need) HIPCK(hipMemcpy(mat.data(), d_tmat, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < ns; s++)
-            for (size_t b = 0; b < (size_t)B; b++) shares[s * (size_t)B + b] = idx[s] >= 0 ? (uint64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
-        return 0;
+        for (int32_t b = 0; b < B; b++) s32[(size_t)b] = mc_tb_scale(scale[b]);
+        McBootPlan P; McBootRead<McTbEntry> R;
+        if (tboot.plan("mc_tie_bootstrap", "mc_set_tie_bootstrap", MC_BOOT_OF_TIES, d_ties, nseq, B, s32.data(), P, dropped) || tboot.stage(P, nseq, B, seed, true, R)) return -1;
+        const hipEvent_t ev[2] = {tboot.ev_read[0], tboot.ev_read[1]};
+        if (mc_tieboot_launch(R, 0, ev) || tboot.finish(tboot.read_ms)) return -1;
+        if (mc_boot_stats(P.idx, P.ng, tboot.d_out, P.m ? 0.0 : mc_gb_nan(), stats)) return -1;   // (a gene without candidates: zero in every replicate)
+        return shares ? mc_boot_rows(P.idx, P.ng, B, tboot.d_mat, shares) : 0;
     }
     // The bootstrap of the coverage columns as they stand (mc_covboot.h): B replicates under `seed`.  need (or null): nseq values, none of them 0,
     // checked by the caller; covered (or null): nseq x B covered residues; stats: nseq x 6 doubles of those values, every replicate used;
@@ -570,51 +575,23 @@ struct McAbundance {
     int read_coverage_bootstrap(int32_t B, uint64_t seed, const uint32_t *need, int64_t *covered, double *stats, int64_t *detected, int64_t *dropped)
     {
         const size_t ns = (size_t)nseq;
-        unsigned long long cur[2];
-        HIPCK(hipMemcpy(cur, d_ccur, sizeof cur, hipMemcpyDeviceToHost));
-        if (dropped) *dropped = (int64_t)cur[1];
-        if (cur[1] || cur[0] > (unsigned long long)ccap) {
-            g_err = "mc_coverage_bootstrap: " + std::to_string(cur[1]) + " assigned reads did not fit the list of " + std::to_string(ccap) + " entries (mc_set_coverage_bootstrap): dropped, no replicate is whole";
-            return -1;
-        }
-        std::vector<unsigned long long> tab(mc_pair_slots(ns));
-        HIPCK(hipMemcpy(tab.data(), d_counts, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> start(ns), hoff(ns + 1); std::vector<int32_t> idx(ns);
-        unsigned long long total = 0;
-        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
-        if (total != cur[0]) { g_err = "mc_coverage_bootstrap: the count table holds " + std::to_string(total) + " assigned reads, the list " + std::to_string(cur[0]); return -1; }
-        HIPCK(hipMemcpy(hoff.data(), off, sizeof(uint32_t) * (ns + 1), hipMemcpyDeviceToHost));   // (the genes' residues: the index's offsets, or the fold's)
-        std::vector<McCbGene> genes((size_t)ng);
-        for (size_t s = 0; s < ns; s++)
-            if (idx[s] >= 0) genes[(size_t)idx[s]] = {start[s], (uint32_t)tab[mc_pair_at(s)], hoff[s + 1] - hoff[s], need ? need[s] : 0u};
         const std::vector<double> ones((size_t)B, 1.0);
-        const size_t want = (size_t)ng * (size_t)B;
-        if (want > cmat_slots) { cmat_slots = 0; if (d_cmat.alloc(want)) return -1; cmat_slots = want; }
-        HIPCK(hipMemcpy(d_cones, ones.data(), sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(d_ccursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(d_cidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
-        if (ng) HIPCK(hipMemcpy(d_cgene, genes.data(), sizeof(McCbGene) * (size_t)ng, hipMemcpyHostToDevice));
-        HIPCK(hipMemsetAsync(d_cdet, 0, sizeof(unsigned long long) * ns, 0));
-        const McCovBootRead R = {nseq, ng, (long long)cur[0], d_clist, d_ccursor, d_cidx, d_csorted, d_cgene, d_cmat, need ? d_cdet.get() : nullptr, d_cones, B, seed, d_cout};
-        const hipEvent_t ev[2] = {ev_cread[0], ev_cread[1]};
-        if (mc_covboot_launch(R, 0, ev)) return -1;
-        HIPCK(hipEventSynchronize(ev_cread[1]));
-        cread_ms += ev_ms(ev_cread[0], ev_cread[1]);
-        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ng);
-        if (ng) HIPCK(hipMemcpy(out.data(), d_cout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t s = 0; s < ns; s++)                            // (a gene without reads: nothing covered in any replicate)
-            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * s + k] = idx[s] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)idx[s] + k] : 0.0;
-        if (detected) {
-            std::vector<unsigned long long> det((size_t)ng);
-            if (ng) HIPCK(hipMemcpy(det.data(), d_cdet, sizeof(unsigned long long) * (size_t)ng, hipMemcpyDeviceToHost));
-            for (size_t s = 0; s < ns; s++) detected[s] = idx[s] >= 0 ? (int64_t)det[(size_t)idx[s]] : 0;
-        }
-        if (!covered) return 0;
-        std::vector<unsigned long long> mat(want);
-        if (want) HIPCK(hipMemcpy(mat.data(), d_cmat, want * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        McBootPlan P; McBootRead<McCbEntry> R;
+        if (cboot.plan("mc_coverage_bootstrap", "mc_set_coverage_bootstrap", MC_BOOT_OF_READS, d_counts, nseq, B, ones.data(), P, dropped)) return -1;
+        std::vector<uint32_t> hoff(ns + 1);
+        HIPCK(hipMemcpy(hoff.data(), off, sizeof(uint32_t) * (ns + 1), hipMemcpyDeviceToHost));   // (the genes' residues: the index's offsets, or the fold's)
+        std::vector<McCbGene> genes((size_t)P.ng);
         for (size_t s = 0; s < ns; s++)
-            for (size_t b = 0; b < (size_t)B; b++) covered[s * (size_t)B + b] = idx[s] >= 0 ? (int64_t)mat[(size_t)idx[s] * (size_t)B + b] : 0;
-        return 0;
+            if (P.idx[s] >= 0) genes[(size_t)P.idx[s]] = {P.start[s], (uint32_t)P.tab[mc_pair_at(s)], hoff[s + 1] - hoff[s], need ? need[s] : 0u};
+        if (cboot.stage(P, nseq, B, seed, false, R)) return -1;
+        if (P.ng) HIPCK(hipMemcpy(d_cgene, genes.data(), sizeof(McCbGene) * (size_t)P.ng, hipMemcpyHostToDevice));
+        HIPCK(hipMemsetAsync(d_cdet, 0, sizeof(unsigned long long) * ns, 0));
+        const hipEvent_t ev[2] = {cboot.ev_read[0], cboot.ev_read[1]};
+        const McCovBootRead C = {R.nseq, R.ngenes, R.n, R.list, R.cursor, R.idx, R.sorted, d_cgene, R.mat, need ? d_cdet.get() : nullptr, R.scale, B, seed, R.out};
+        if (mc_covboot_launch(C, 0, ev) || cboot.finish(cboot.read_ms)) return -1;
+        if (mc_boot_stats(P.idx, P.ng, cboot.d_out, 0.0, stats)) return -1;   // (a gene without reads: nothing covered in any replicate)
+        if (detected && mc_boot_rows(P.idx, P.ng, 1, d_cdet, detected)) return -1;
+        return covered ? mc_boot_rows(P.idx, P.ng, B, cboot.d_mat, covered) : 0;
     }
     // The bootstrap of the GROUPS (mc_groupboot.h) on the counts as they stand: group_of: nseq groups below ngroups_, gene_kb: nseq doubles, all
     // checked by the caller (mc_group_bootstrap).  counts (or null): ngroups_ x B group replicate counts; stats: ngroups_ x 6 doubles.  mat is
@@ -622,11 +599,11 @@ struct McAbundance {
     int read_group_bootstrap(int32_t B, uint64_t seed, const double *scale, const int32_t *group_of, int32_t ngroups_, const double *gene_kb, int64_t *counts, double *stats, int64_t *dropped)
     {
         const size_t ns = (size_t)nseq, ngr = (size_t)ngroups_;
-        std::vector<int32_t> idx(ns);
-        int32_t ng = 0, m = 0; float took = 0.f;
-        if (make_mat("mc_group_bootstrap", B, seed, scale, true, idx, &ng, &m, dropped, &took)) return -1;
+        McBootPlan P; float took = 0.f;
+        if (make_mat("mc_group_bootstrap", B, seed, scale, true, P, dropped, took)) return -1;
+        const int32_t ng = P.ng;
         std::vector<int32_t> gidx(ngr); std::vector<uint32_t> start(ngr + 1), member((size_t)ng); std::vector<double> kb((size_t)ng);
-        const int32_t ngrp = mc_grb_plan(idx.data(), nseq, group_of, ngroups_, gene_kb, gidx.data(), start.data(), member.data(), kb.data());
+        const int32_t ngrp = mc_grb_plan(P.idx.data(), nseq, group_of, ngroups_, gene_kb, gidx.data(), start.data(), member.data(), kb.data());
         const size_t need = (size_t)ngrp * (size_t)B;
         if (!d_grstart && (d_grstart.alloc(ns + 1) || d_grmember.alloc(ns) || d_grkb.alloc(ns) || d_grout.alloc((size_t)MC_GB_NOUT * ns) || ev_grp[0].create() || ev_grp[1].create() || ev_grp[2].create())) {
             d_grstart.reset(); return -1;
@@ -636,22 +613,14 @@ struct McAbundance {
         HIPCK(hipMemcpy(d_grstart, start.data(), sizeof(uint32_t) * ((size_t)ngrp + 1), hipMemcpyHostToDevice));
         if (ng) HIPCK(hipMemcpy(d_grmember, member.data(), sizeof(uint32_t) * (size_t)ng, hipMemcpyHostToDevice));
         if (ng) HIPCK(hipMemcpy(d_grkb, kb.data(), sizeof(double) * (size_t)ng, hipMemcpyHostToDevice));
-        const McGroupBootRead R = {ng, ngrp, d_gmat, d_grstart, d_grmember, d_grkb, d_grval, counts ? d_grcnt.get() : nullptr, d_gscale, B, m, d_grout};
+        const McGroupBootRead R = {ng, ngrp, gboot.d_mat, d_grstart, d_grmember, d_grkb, d_grval, counts ? d_grcnt.get() : nullptr, gboot.d_scale, B, P.m, d_grout};
         const hipEvent_t ev[3] = {ev_grp[0], ev_grp[1], ev_grp[2]};
         if (mc_groupboot_launch(R, 0, ev)) return -1;
         HIPCK(hipEventSynchronize(ev_grp[1]));
         const float tv = ev_ms(ev_grp[0], ev_grp[2]), ts = ev_ms(ev_grp[2], ev_grp[1]);
         grp_values_ms += tv; grp_summary_ms += ts; grp_ms += took + tv + ts;
-        std::vector<double> out((size_t)MC_GB_NOUT * (size_t)ngrp);
-        if (ngrp) HIPCK(hipMemcpy(out.data(), d_grout, out.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t G = 0; G < ngr; G++)                           // (a group without reads: zero in every replicate)
-            for (int k = 0; k < MC_GB_NOUT; k++) stats[MC_GB_NOUT * G + k] = gidx[G] >= 0 ? out[(size_t)MC_GB_NOUT * (size_t)gidx[G] + k] : m ? 0.0 : mc_gb_nan();
-        if (!counts) return 0;
-        std::vector<unsigned long long> cm(need);
-        if (need) HIPCK(hipMemcpy(cm.data(), d_grcnt, need * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (size_t G = 0; G < ngr; G++)
-            for (size_t b = 0; b < (size_t)B; b++) counts[G * (size_t)B + b] = gidx[G] >= 0 ? (int64_t)cm[(size_t)gidx[G] * (size_t)B + b] : 0;
-        return 0;
+        if (mc_boot_stats(gidx, ngrp, d_grout, P.m ? 0.0 : mc_gb_nan(), stats)) return -1;   // (a group without reads: zero in every replicate)
+        return counts ? mc_boot_rows(gidx, ngrp, B, d_grcnt, counts) : 0;
     }
     // the per-class table as it stands: n pairs, class 0 .. n - 2 and the rows below the lowest class (the caller knows its K: n = K + 1)
     int read_classes(int64_t *rows, int64_t *assigned, int32_t n) const
@@ -698,62 +667,40 @@ struct McAbundance {
     }
 
 private:
-    // mat of the counts as they stand - genes with reads x B replicate counts under `seed` - and the six doubles of every gene with reads in d_gout,
-    // through ONE copy of the count table: the list's refusals under the caller's name `who`, mc_gb_plan, the three kernels of mc_geneboot_launch.
-    // idx: nseq compact indices; ng: the genes with reads; m: the used replicates; took: the kernels' milliseconds.  With reuse, a mat that is
-    // still this one's (gmat_*) is kept and nothing is launched: the scales alone go to the device.
-    int make_mat(const char *who, int32_t B, uint64_t seed, const double *scale, bool reuse, std::vector<int32_t> &idx, int32_t *ng_out, int32_t *m_out, int64_t *dropped, float *took)
+    // mat of the counts as they stand - genes with reads x B replicate counts under `seed` - and the six doubles of every gene with reads in gboot.d_out,
+    // through ONE copy of the count table: the list's refusals under the caller's name `who`, the plan P, the three kernels of mc_geneboot_launch,
+    // their milliseconds added to `took`.  With reuse, a mat that is still this one's (gmat_*) is kept and nothing is launched: the scales alone
+    // go to the device.
+    int make_mat(const char *who, int32_t B, uint64_t seed, const double *scale, bool reuse, McBootPlan &P, int64_t *dropped, float &took)
     {
-        const size_t ns = (size_t)nseq;
-        unsigned long long cur[2];
-        HIPCK(hipMemcpy(cur, d_gcur, sizeof cur, hipMemcpyDeviceToHost));
-        if (dropped) *dropped = (int64_t)cur[1];
-        if (cur[1] || cur[0] > (unsigned long long)gcap) {
-            g_err = std::string(who) + ": " + std::to_string(cur[1]) + " assigned reads did not fit the list of " + std::to_string(gcap) + " entries (mc_set_gene_bootstrap): dropped, no replicate is whole";
-            return -1;
-        }
-        std::vector<unsigned long long> tab(mc_pair_slots(ns));
-        HIPCK(hipMemcpy(tab.data(), d_counts, tab.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::vector<uint32_t> start(ns);
-        unsigned long long total = 0;
-        const int32_t ng = mc_gb_plan(tab.data(), nseq, start.data(), idx.data(), &total);
-        if (total != cur[0]) { g_err = std::string(who) + ": the count table holds " + std::to_string(total) + " assigned reads, the list " + std::to_string(cur[0]); return -1; }
-        int32_t m = 0;
-        for (int32_t b = 0; b < B; b++) m += mc_gb_used(scale[b]) ? 1 : 0;
-        *ng_out = ng; *m_out = m; *took = 0.f;
-        HIPCK(hipMemcpy(d_gscale, scale, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
-        if (reuse && gmat_n == (long long)cur[0] && gmat_B == B && gmat_seed == seed) return 0;
+        if (gboot.plan(who, "mc_set_gene_bootstrap", MC_BOOT_OF_READS, d_counts, nseq, B, scale, P, dropped)) return -1;
+        if (reuse && gmat_n == P.n && gmat_B == B && gmat_seed == seed) return 0;
         gmat_n = -1;
-        const size_t need = (size_t)ng * (size_t)B;
-        if (need > gmat_slots) { gmat_slots = 0; if (d_gmat.alloc(need)) return -1; gmat_slots = need; }
-        HIPCK(hipMemcpy(d_gcursor, start.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(d_gidx, idx.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice));
-        if (need) HIPCK(hipMemsetAsync(d_gmat, 0, sizeof(unsigned long long) * need, 0));
-        const McGeneBootRead R = {nseq, ng, (long long)cur[0], d_glist, d_gcursor, d_gidx, d_gsorted, d_gmat, d_gscale, B, m, seed, d_gout};
-        const hipEvent_t ev[2] = {ev_gread[0], ev_gread[1]};
-        if (mc_geneboot_launch(R, 0, ev)) return -1;
-        HIPCK(hipEventSynchronize(ev_gread[1]));
-        *took = ev_ms(ev_gread[0], ev_gread[1]);
-        gmat_B = B; gmat_seed = seed; gmat_n = (long long)cur[0];
+        McBootRead<McGbEntry> R;
+        if (gboot.stage(P, nseq, B, seed, true, R)) return -1;
+        const hipEvent_t ev[2] = {gboot.ev_read[0], gboot.ev_read[1]};
+        if (mc_geneboot_launch(R, 0, ev) || gboot.finish(took)) return -1;
+        gmat_B = B; gmat_seed = seed; gmat_n = P.n;
         return 0;
     }
-    template <class Tp> static int fit_one(McDev<Tp> &d, bool want, size_t n) { if (!want) d.reset(); return want && !d ? d.alloc(n) : 0; }
-    static int fit_one(McEvent &e, bool want) { if (!want) e.reset(); return want && !e ? e.create() : 0; }
+    template <class E> int set_list(McBootList<E> &L, int64_t capacity)
+    {
+        (void)turn(L.on, false);
+        if (capacity == 0) return 0;
+        L.cap = capacity;
+        return turn(L.on, true);
+    }
     // the switches as they stand, made consistent; then the buffer rule: what they need is made where it is missing, everything else freed
     int fit()
     {
-        if (!on) { cov = ties = curve = gboot = classes = ident = false; searched = 0; ms = 0.f; }
+        if (!on) { cov = ties = curve = gboot.on = classes = ident = false; searched = 0; ms = 0.f; }
         if (!ident) ident_ms = iscan_ms = 0.f;
-        if (!ties || !gboot) tboot = false;
-        if (!cov) cboot = false;
-        if (!cboot) { ccap = 0; cboot_ms = cread_ms = 0.f; d_cmat.reset(); cmat_slots = 0; }
-        if (!tboot) { tcap = 0; tboot_ms = tread_ms = 0.f; d_tmat.reset(); tmat_slots = 0; }
         if (!classes) { cls_ms = 0.f; ride_end(); }
         if (!cov) cov_ms = 0.f;
         if (!ties) { ngroups = 0; ties_ms = 0.f; }
         if (!curve) { K = 0; curve_ms = cscan_ms = 0.f; }
-        if (!gboot) {
-            gcap = 0; gboot_ms = gread_ms = grp_ms = grp_values_ms = grp_summary_ms = 0.f; d_gmat.reset(); gmat_slots = 0; gmat_n = -1;
+        if (!gboot.on) {
+            grp_ms = grp_values_ms = grp_summary_ms = 0.f; gmat_n = -1;
             d_grstart.reset(); d_grmember.reset(); d_grkb.reset(); d_grval.reset(); d_grcnt.reset(); d_grout.reset(); grval_slots = grcnt_slots = 0;
             for (McEvent &e : ev_grp) e.reset();
         }
@@ -764,13 +711,7 @@ private:
                fit_one(d_diff_any, cov && ties, slots) ||
                fit_one(d_pts, curve, MC_CURVE_MAXK) || fit_one(d_bins, curve, mc_curve_bin_slots((size_t)K, ns)) || fit_one(d_curveout, curve, mc_curve_out_slots((size_t)K, ns)) ||
                fit_one(ev_curve, curve) || fit_one(ev_cscan[0], curve) || fit_one(ev_cscan[1], curve) || fit_one(d_first, curve && cov, nres) ||
-               fit_one(d_glist, gboot, (size_t)gcap) || fit_one(d_gsorted, gboot, (size_t)gcap) || fit_one(d_gcur, gboot, 2) || fit_one(d_gcursor, gboot, ns) || fit_one(d_gidx, gboot, ns) ||
-               fit_one(d_gscale, gboot, MC_GB_MAXB) || fit_one(d_gout, gboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_gboot, gboot) || fit_one(ev_gread[0], gboot) || fit_one(ev_gread[1], gboot) ||
-               fit_one(d_tlist, tboot, (size_t)tcap) || fit_one(d_tsorted, tboot, (size_t)tcap) || fit_one(d_tcur, tboot, 2) || fit_one(d_tcursor, tboot, ns) || fit_one(d_tidx, tboot, ns) ||
-               fit_one(d_tscale, tboot, MC_GB_MAXB) || fit_one(d_tout, tboot, (size_t)MC_GB_NOUT * ns) || fit_one(ev_tboot, tboot) || fit_one(ev_tread[0], tboot) || fit_one(ev_tread[1], tboot) ||
-               fit_one(d_clist, cboot, (size_t)ccap) || fit_one(d_csorted, cboot, (size_t)ccap) || fit_one(d_ccur, cboot, 2) || fit_one(d_ccursor, cboot, ns) || fit_one(d_cidx, cboot, ns) ||
-               fit_one(d_cgene, cboot, ns) || fit_one(d_cdet, cboot, ns) || fit_one(d_cones, cboot, MC_GB_MAXB) || fit_one(d_cout, cboot, (size_t)MC_GB_NOUT * ns) ||
-               fit_one(ev_cboot, cboot) || fit_one(ev_cread[0], cboot) || fit_one(ev_cread[1], cboot) ||
+               gboot.fit(gboot.on, ns) || tboot.fit(tboot.on && ties && gboot.on, ns) || cboot.fit(cboot.on && cov, ns) || fit_one(d_cgene, cboot.on, ns) || fit_one(d_cdet, cboot.on, ns) ||
                fit_one(d_cls, classes, MC_AC_SLOTS) || fit_one(ev_cls, classes) ||
                fit_one(d_idhist, ident, mc_id_hist_slots(ns)) || fit_one(d_idsums, ident, ns) || fit_one(d_idout, ident, mc_id_out_slots(ns)) || fit_one(d_idlev, ident, MC_ID_LEVELS) ||
                fit_one(ev_ident, ident) || fit_one(ev_iscan[0], ident) || fit_one(ev_iscan[1], ident);

@@ -1431,9 +1431,9 @@ extern "C" int mc_search_varlen(mc_handle *h, const uint8_t *bases, const int64_
     if (nreads > 0x7fffffff) { g_err = "more than 2^31 - 1 reads in one call"; return -1; }
     if (h->pipe_nout) { g_err = "ranges begun with mc_range_begin() are still in flight"; return -1; }
     if (h->ab.curve) { g_err = "mc_search_varlen: refused while the curve is on (mc_set_curve, K = " + std::to_string(h->ab.K) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
-    if (h->ab.cboot) { g_err = "mc_search_varlen: refused while the coverage bootstrap is on (mc_set_coverage_bootstrap, capacity = " + std::to_string(h->ab.ccap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
-    if (h->ab.tboot) { g_err = "mc_search_varlen: refused while the tie bootstrap is on (mc_set_tie_bootstrap, capacity = " + std::to_string(h->ab.tcap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
-    if (h->ab.gboot) { g_err = "mc_search_varlen: refused while the gene bootstrap is on (mc_set_gene_bootstrap, capacity = " + std::to_string(h->ab.gcap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
+    if (h->ab.cboot.on) { g_err = "mc_search_varlen: refused while the coverage bootstrap is on (mc_set_coverage_bootstrap, capacity = " + std::to_string(h->ab.cboot.cap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
+    if (h->ab.tboot.on) { g_err = "mc_search_varlen: refused while the tie bootstrap is on (mc_set_tie_bootstrap, capacity = " + std::to_string(h->ab.tboot.cap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
+    if (h->ab.gboot.on) { g_err = "mc_search_varlen: refused while the gene bootstrap is on (mc_set_gene_bootstrap, capacity = " + std::to_string(h->ab.gboot.cap) + ") - its rows carry the sorted position, not the caller's read id"; return -1; }
     bool one = true;
     for (int64_t i = 0; i < nreads; i++) {
         const int64_t len = offsets[i + 1] - offsets[i];
@@ -2101,7 +2101,7 @@ extern "C" int mc_set_gene_bootstrap(mc_handle *h, int64_t capacity)
 extern "C" int mc_gene_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale, int64_t *counts, double *stats, int64_t *dropped)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->ab.gboot) { g_err = "mc_gene_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap)"; return -1; }
+    if (!h->ab.gboot.on) { g_err = "mc_gene_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap)"; return -1; }
     if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_gene_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
     if (!scale || !stats) { g_err = "mc_gene_bootstrap: B = " + std::to_string(B) + " and a NULL scale or stats array"; return -1; }
     if (h->pipe_nout) { g_err = "mc_gene_bootstrap: a range begun with mc_range_begin() is still in flight"; return -1; }
@@ -2114,7 +2114,7 @@ extern "C" int mc_group_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const 
                                   double *stats, int64_t *dropped)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->ab.gboot) { g_err = "mc_group_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap)"; return -1; }
+    if (!h->ab.gboot.on) { g_err = "mc_group_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap)"; return -1; }
     if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_group_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
     if (!scale || !stats || !group_of || !gene_kb) { g_err = "mc_group_bootstrap: B = " + std::to_string(B) + " and a NULL scale, group_of, gene_kb or stats array"; return -1; }
     const int32_t nseq = h->ab.nseq;
@@ -2138,7 +2138,7 @@ extern "C" int mc_set_tie_bootstrap(mc_handle *h, int64_t capacity)
     if (capacity == 0) return h->ab.set_tie_bootstrap(0);
     if (capacity < 0 || capacity > (int64_t)MC_TB_MAXCAP) { g_err = "mc_set_tie_bootstrap: capacity " + std::to_string(capacity) + " is not a number of entries from 0 to 2^27"; return -1; }
     if (!h->ab.ties) { g_err = "mc_set_tie_bootstrap: ties are off (mc_set_ties) - the entries are the tied sets it counts (capacity = " + std::to_string(capacity) + ")"; return -1; }
-    if (!h->ab.gboot) { g_err = "mc_set_tie_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap) - the replicates are its replicates (capacity = " + std::to_string(capacity) + ")"; return -1; }
+    if (!h->ab.gboot.on) { g_err = "mc_set_tie_bootstrap: the gene bootstrap is off (mc_set_gene_bootstrap) - the replicates are its replicates (capacity = " + std::to_string(capacity) + ")"; return -1; }
     return h->ab.set_tie_bootstrap(capacity);
 }
 
@@ -2146,7 +2146,7 @@ extern "C" int mc_set_tie_bootstrap(mc_handle *h, int64_t capacity)
 extern "C" int mc_tie_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const double *scale, uint64_t *shares, double *stats, int64_t *dropped)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->ab.tboot) { g_err = "mc_tie_bootstrap: the tie bootstrap is off (mc_set_tie_bootstrap)"; return -1; }
+    if (!h->ab.tboot.on) { g_err = "mc_tie_bootstrap: the tie bootstrap is off (mc_set_tie_bootstrap)"; return -1; }
     if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_tie_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
     if (!scale || !stats) { g_err = "mc_tie_bootstrap: B = " + std::to_string(B) + " and a NULL scale or stats array"; return -1; }
     if (h->pipe_nout) { g_err = "mc_tie_bootstrap: a range begun with mc_range_begin() is still in flight"; return -1; }
@@ -2172,7 +2172,7 @@ extern "C" int mc_set_coverage_bootstrap(mc_handle *h, int64_t capacity)
 extern "C" int mc_coverage_bootstrap(mc_handle *h, int32_t B, uint64_t seed, const uint32_t *need, int64_t *covered, double *stats, int64_t *detected, int64_t *dropped)
 {
     if (!h) { g_err = "null handle"; return -1; }
-    if (!h->ab.cboot) { g_err = "mc_coverage_bootstrap: the coverage bootstrap is off (mc_set_coverage_bootstrap)"; return -1; }
+    if (!h->ab.cboot.on) { g_err = "mc_coverage_bootstrap: the coverage bootstrap is off (mc_set_coverage_bootstrap)"; return -1; }
     if (B < 1 || B > MC_GB_MAXB) { g_err = "mc_coverage_bootstrap: B " + std::to_string(B) + " is not a number of replicates from 1 to " + std::to_string(MC_GB_MAXB); return -1; }
     if (!stats) { g_err = "mc_coverage_bootstrap: B = " + std::to_string(B) + " and a NULL stats array"; return -1; }
     if (detected && !need) { g_err = "mc_coverage_bootstrap: detected without need (B = " + std::to_string(B) + ") - a replicate detects a gene that covers need[g] residues"; return -1; }
@@ -2322,20 +2322,20 @@ extern "C" int mc_abundance_classes_read(mc_handle *h, int64_t *rows, int64_t *a
 extern "C" float mc_abundance_classes_ms(const mc_handle *h) { return h ? h->ab.cls_ms : 0.0f; }
 
 // k_geneboot_collect's time over the completed ranges plus the reads' kernels, since the last zeroing
-extern "C" float mc_gene_bootstrap_ms(const mc_handle *h) { return h ? h->ab.gboot_ms + h->ab.gread_ms : 0.0f; }
+extern "C" float mc_gene_bootstrap_ms(const mc_handle *h) { return h ? h->ab.gboot.collect_ms + h->ab.gboot.read_ms : 0.0f; }
 // k_tieboot_collect's time over the completed ranges plus the tie reads' kernels, since the last zeroing; the two parts (either may be NULL)
-extern "C" float mc_tie_bootstrap_ms(const mc_handle *h) { return h ? h->ab.tboot_ms + h->ab.tread_ms : 0.0f; }
+extern "C" float mc_tie_bootstrap_ms(const mc_handle *h) { return h ? h->ab.tboot.collect_ms + h->ab.tboot.read_ms : 0.0f; }
 extern "C" void mc_tie_bootstrap_kernels_ms(const mc_handle *h, float *collect_ms, float *read_ms)
 {
-    if (collect_ms) *collect_ms = h ? h->ab.tboot_ms : 0.0f;
-    if (read_ms) *read_ms = h ? h->ab.tread_ms : 0.0f;
+    if (collect_ms) *collect_ms = h ? h->ab.tboot.collect_ms : 0.0f;
+    if (read_ms) *read_ms = h ? h->ab.tboot.read_ms : 0.0f;
 }
 // k_covboot_collect's time over the completed ranges plus the coverage reads' kernels, since the last zeroing; the two parts (either may be NULL)
-extern "C" float mc_coverage_bootstrap_ms(const mc_handle *h) { return h ? h->ab.cboot_ms + h->ab.cread_ms : 0.0f; }
+extern "C" float mc_coverage_bootstrap_ms(const mc_handle *h) { return h ? h->ab.cboot.collect_ms + h->ab.cboot.read_ms : 0.0f; }
 extern "C" void mc_coverage_bootstrap_kernels_ms(const mc_handle *h, float *collect_ms, float *read_ms)
 {
-    if (collect_ms) *collect_ms = h ? h->ab.cboot_ms : 0.0f;
-    if (read_ms) *read_ms = h ? h->ab.cread_ms : 0.0f;
+    if (collect_ms) *collect_ms = h ? h->ab.cboot.collect_ms : 0.0f;
+    if (read_ms) *read_ms = h ? h->ab.cboot.read_ms : 0.0f;
 }
 // the group reads' kernels since the last zeroing: k_groupboot_values and k_groupboot_summary, and the kernels of a mat a group read had to make
 extern "C" float mc_group_bootstrap_ms(const mc_handle *h) { return h ? h->ab.grp_ms : 0.0f; }
