@@ -1341,7 +1341,8 @@ class Engine:
     def debug_stage(self, what):
         """Test aid: what a stage of the last run_range() left on the device (0 frames, 1 seed hits, 2 gap tasks, 3 HSP pool, 4 the
         gapped chain's three counts: gap_counts(), 5 the form of k_translate_seg that was launched: 1 staged, 0 direct, one uint32,
-        6 its instantiation: 1 narrow - frames of at most 63 residues -, 0 wide, one uint32) as a (records, record_bytes) uint8 array."""
+        6 its instantiation: 1 narrow - frames of at most 63 residues -, 0 wide, one uint32, 7 waves per workgroup x workgroups per CU
+        of the last seed launch, one uint32) as a (records, record_bytes) uint8 array."""
         rec = C.c_int32(0)
         n = self.lib.mc_debug_stage(self.h, what, None, 0, C.byref(rec))
         if n < 0:

@@ -66,6 +66,7 @@ struct McCtx {
     int64_t cap_reads = 0; int pool_len = 0;                       // the pools hold cap_reads reads of up to pool_len bases
     int ts_staged = -1;                                            // the form of k_translate_seg the last range launched (mc_debug_stage 5)
     int ts_narrow = -1;                                            // ... and whether it was the narrow instantiation (mc_debug_stage 6)
+    int seed_shape = -1;                                           // waves per workgroup x workgroups per CU of the last seed launch (mc_debug_stage 7)
     uint32_t cap_tasks = 0, cap_gaps = 0, cap_hsps = 0, cap_rows = 0;
     // Two frame buffers (mc_ahead.h): d_frames is the RUNNING range's - the one every reader means - and a lookahead writes the other;
     // a range_begin that takes a lookahead makes that buffer the current one (frames_use).  Views 64 bytes in, behind an apron of MC_INV:
@@ -679,8 +680,9 @@ static int stage_a0(mc_handle *h, McCtx &c, hipStream_t st, const uint8_t *reads
 }
 
 // A: the counters cleared, then A0 of the reads no lookahead has translated (range_begin: `covered` of them it has, from the range's
-// first), then A1: seed enumeration, seed evaluation (gate, growth, ungapped X-drop)
-static int stage_a(mc_handle *h, McCtx &c, int64_t covered)
+// first), then A1: seed enumeration, seed evaluation (gate, growth, ungapped X-drop).  beside_lookahead: range_begin is about to issue
+// a lookahead beside the seed kernel, which leaves it room (mc_enumerate_launch)
+static int stage_a(mc_handle *h, McCtx &c, int64_t covered, bool beside_lookahead)
 {
     const int64_t n = c.n;
     hipStream_t st = c.stream;
@@ -696,7 +698,7 @@ static int stage_a(mc_handle *h, McCtx &c, int64_t covered)
     const McRun R = run_of(h);
     const McSeedBufs B = carve_seed(h, c);
     const McSeedKernel kind = !h->fast_enum ? MC_SEED_PLAIN : h->count_traffic ? MC_SEED_COUNTING : MC_SEED_QUEUES;
-    if (mc_enumerate_launch(R, B, n, kind, st)) return -1;
+    if (mc_enumerate_launch(R, B, n, kind, st, beside_lookahead, &c.seed_shape)) return -1;
     HIPCK(hipEventRecord(c.ev[2], st));
     if (mc_eval_seeds_launch(R, B, kind == MC_SEED_QUEUES, st)) return -1;
     HIPCK(hipEventRecord(c.ev[3], st));
@@ -831,6 +833,7 @@ extern "C" int mc_run_range(mc_handle *h, int64_t first, int64_t count, int64_t 
 // range before: what the host still reads of it lies in pinned host memory (rows: two buffers in turn; best hits; the counters
 // were taken at range_end), and the rows still leaving the device are waited for by stage D (ev_rows).
 static int ahead_issue(mc_handle *h, McCtx &c, int64_t first, int64_t count, hipEvent_t behind);
+static bool ahead_fits(const mc_handle *h, const McCtx &c, int64_t first, int64_t count);
 // predicts: the range issues the lookahead for the range that follows it contiguously in its set (mc_ahead_predict) itself, behind its
 // own A1 launches; otherwise its range_end is told the next range, or there is none (mc_run_range).
 static int range_begin(mc_handle *h, McCtx &c, int64_t first, int64_t count, int64_t first_read_id, bool predicts)
@@ -851,12 +854,15 @@ static int range_begin(mc_handle *h, McCtx &c, int64_t first, int64_t count, int
     h->ahead_wait = false;
     c.ahead_from = covered ? h->ahead_p : -1;
     if (covered) { h->ahead_used++; h->ahead_p ^= 1; }              // (the lookahead behind this range takes the other pair of events)
-    int rc = stage_a(h, c, covered);
+    // (the range expected next is known before the seed kernel is launched: beside a lookahead the kernel takes another shape.  The
+    // shape is chosen on that prediction: a range whose lookahead is then given up - a walk that leaves the order, a mc_debug_stage
+    // between two ranges - has run with twelve waves and nothing beside it, about 0.35 ms per 1 M reads slower; its results are the same)
+    int64_t next_first = 0;
+    const int64_t next_count = predicts && MC_AHEAD_ON ? mc_ahead_predict(first, count, h->nreads, &next_first) : 0;
+    int rc = stage_a(h, c, covered, ahead_fits(h, c, next_first, next_count));
     if (rc) { (void)hipStreamSynchronize(c.stream); return rc; }
     c.busy = true;
-    if (predicts && MC_AHEAD_ON) {
-        int64_t next_first = 0;
-        const int64_t next_count = mc_ahead_predict(first, count, h->nreads, &next_first);
+    if (next_count > 0) {
         if ((rc = ahead_issue(h, c, next_first, next_count, c.ev[1])) != 0) { (void)hipStreamSynchronize(c.stream); c.busy = false; return rc; }
     }
     return 0;
@@ -865,15 +871,22 @@ static int range_begin(mc_handle *h, McCtx &c, int64_t first, int64_t count, int
 // The translation of the range expected next - reads [first, first + count) of the resident set as it is now - beside the running
 // range, into the frame buffer that range does not use: no reader of d_frames has to be waited for.  behind: an event of the running
 // range's stream the kernel starts behind, or none.  range_begin gives ev[1], the event in front of its seed kernel: the seed kernel,
-// launched right behind it on its own queue, is resident first - 16 waves per CU, the LDS nearly full - so the translation gets what
-// is left of the CUs beside it and floods them when the seed kernel's grid runs out, beside k_eval_seeds.  Without the event the two
+// launched right behind it on its own queue, is resident first - beside a lookahead of reads up to 191 bp with 12 waves per CU in one
+// workgroup, which leave room for eight translation waves instead of six (mc_enumerate_launch), otherwise with 16, the LDS nearly full -
+// so the translation gets what is left of the CUs beside it and floods them when the seed kernel's grid runs out, beside k_eval_seeds.
+// Holding k_eval_seeds back until the translation has ended was measured and
+// lost: the tail takes 2.3 ms per 2 M reads alone, more than the two cost each other.  Without the event the two
 // race for the CUs and the step has two speeds; behind the seed kernel's END it finds k_eval_seeds resident, waits for that and runs
 // beside the gapped stage, which then takes as much longer as the translation lasts.  A grid BOUNDED to 256 x G one-wave workgroups
 // that loop over the blocks was built and measured too, and lost: a wave takes 110 us per block of ten reads however empty its CU is.
 // All of it: DESIGN.md 5.5.  No range larger than the pools.
+static bool ahead_fits(const mc_handle *h, const McCtx &c, int64_t first, int64_t count)
+{
+    return count > 0 && count <= c.cap_reads && h->read_len <= c.pool_len && first >= 0 && first + count <= h->nreads && h->reads_dev;
+}
 static int ahead_issue(mc_handle *h, McCtx &c, int64_t first, int64_t count, hipEvent_t behind)
 {
-    if (count <= 0 || count > c.cap_reads || h->read_len > c.pool_len || first < 0 || first + count > h->nreads || !h->reads_dev) return 0;
+    if (!ahead_fits(h, c, first, count)) return 0;
     ahead_drop(h);                                                  // (nothing to wait for: range_begin has made the range's stream wait for the lookahead before this one)
     if (behind) HIPCK(hipStreamWaitEvent(h->ahead_stream, behind, 0));
     h->ahead_wait = true;                                           // (from here on something may be in the stream)
@@ -1022,10 +1035,11 @@ extern "C" int mc_ranges_in_flight(const mc_handle *h) { return h ? h->pipe_nout
 // kernels touch these three, and the block is cleared by the next range's stage A.  Defined for a range that ran unsplit (after a
 // split they are the last piece's).
 // 5: the form of k_translate_seg the last range launched, one uint32 - 1 reads staged in LDS, 0 read from global memory.  6: its
-// instantiation, one uint32 - 1 narrow (frames of at most 63 residues: reads up to 191 bp), 0 wide.
+// instantiation, one uint32 - 1 narrow (frames of at most 63 residues: reads up to 191 bp), 0 wide.  7: waves per workgroup x workgroups
+// per CU of the last seed launch, one uint32 (0: k_enumerate, whose grid is per read).
 extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap_bytes, int32_t *record_bytes)
 {
-    if (!h || !h->run_set || what < 0 || what > 6) { g_err = "mc_debug_stage: bad argument"; return -1; }
+    if (!h || !h->run_set || what < 0 || what > 7) { g_err = "mc_debug_stage: bad argument"; return -1; }
     if (h->pipe_nout) { g_err = "mc_debug_stage: ranges are in flight"; return -1; }
     HIPCK(hipSetDevice(h->device));
     ahead_drop(h);
@@ -1037,9 +1051,15 @@ extern "C" int64_t mc_debug_stage(mc_handle *h, int what, void *dst, int64_t cap
         if (dst && (int64_t)sizeof v <= cap_bytes) memcpy(dst, v, sizeof v);
         return (int64_t)sizeof v;
     }
-    if (what == 5 || what == 6) {
-        if (c.ts_staged < 0 || c.ts_narrow < 0) { g_err = "mc_debug_stage: no range has run"; return -1; }
-        const uint32_t v = (uint32_t)(what == 5 ? c.ts_staged : c.ts_narrow);
+    if (what >= 5) {
+        int host = -1;                                              // (a host field of McCtx; -1 until a range has run)
+        switch (what) {
+        case 5: host = c.ts_staged; break;
+        case 6: host = c.ts_narrow; break;
+        default: host = c.seed_shape; break;
+        }
+        if (host < 0) { g_err = "mc_debug_stage: no range has run"; return -1; }
+        const uint32_t v = (uint32_t)host;
         if (record_bytes) *record_bytes = (int32_t)sizeof v;
         if (dst && (int64_t)sizeof v <= cap_bytes) memcpy(dst, &v, sizeof v);
         return (int64_t)sizeof v;

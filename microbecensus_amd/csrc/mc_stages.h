@@ -76,9 +76,12 @@ struct McSeedBufs {
 };
 enum McSeedKernel { MC_SEED_PLAIN, MC_SEED_QUEUES, MC_SEED_COUNTING };   // k_enumerate, k_enumerate_q, k_enumerate_count
 
-static int mc_enumerate_launch(const McRun &R, const McSeedBufs &B, int64_t n, McSeedKernel kind, hipStream_t st)
+// beside_lookahead: a translation of the next range is about to run beside the kernel.  shape_out (if given) receives waves per
+// workgroup x workgroups per CU of the launch (0: k_enumerate).
+static int mc_enumerate_launch(const McRun &R, const McSeedBufs &B, int64_t n, McSeedKernel kind, hipStream_t st, bool beside_lookahead = false, int *shape_out = nullptr)
 {
     const int L = R.L, FP = R.FP;
+    if (shape_out) *shape_out = 0;
     if (kind != MC_SEED_PLAIN) {
         // k_enumerate_q (round 5: queues that persist across the reads of a chunk) is the kernel of the product path; the counting form
         // (mc_set_counting: what the reference would read) is k_enumerate_count (rounds 2 - 4's one-wave-per-read kernel without filters).
@@ -92,11 +95,19 @@ static int mc_enumerate_launch(const McRun &R, const McSeedBufs &B, int64_t n, M
         {
             static const int shapes_q[][2] = {{8, 2}, {4, 4}, {16, 1}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
             static const int shapes_c[][2] = {{12, 2}, {8, 3}, {4, 6}, {4, 5}, {16, 1}, {8, 2}, {4, 4}, {12, 1}, {4, 3}, {8, 1}, {4, 2}, {4, 1}};
+            // Beside a lookahead's narrow translation (reads up to 191 bp) TWELVE waves in one workgroup, tried first: at 150 bp 79,840 B
+            // of LDS instead of 2 x 53,248 leave room for nine translation workgroups of 8,960 B instead of six, and 3 x 80 registers of
+            // a SIMD's lanes leave 272 for two translation waves of 96 - eight waves per CU, as many as the registers allow.  The seed
+            // kernel takes 0.35 ms per 1 M reads longer and k_eval_seeds, beside which less of the translation is left, 0.6 less.
+            // The arithmetic is that of 150 bp and the rule was measured at 100 and 150 bp only: for shorter reads, whose per-wave LDS is
+            // smaller, it is an extrapolation - safe for the results, which no shape changes, and not known to be the fastest shape there
+            if (enq && beside_lookahead && L / 3 <= MC_NARROW_MAXAA && 64 + 12 * per_wave <= 160 * 1024) { waves = 12; bpc = 1; }
             if (enq) { for (const auto &sh : shapes_q) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; } }
             else for (const auto &sh : shapes_c) if (!waves && (size_t)sh[1] * (64 + sh[0] * per_wave) <= 160 * 1024) { waves = sh[0]; bpc = sh[1]; }
         }
         if (!waves) { g_err = "reads too long for the seed kernel's LDS layout"; return -1; }
         const size_t lds2 = 64 + waves * per_wave;
+        if (shape_out) *shape_out = waves * bpc;
 #define MC_LAUNCH_EN(KERNEL, WV)                                                                                                                   \
     do {                                                                                                                                           \
         HIPCK(hipFuncSetAttribute((const void *)KERNEL<WV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));                               \

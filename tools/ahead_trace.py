@@ -12,7 +12,10 @@ each stage against the parent's;
 per step of this build, where k_translate_seg of the NEXT range runs (the lookahead of a step: the translation that starts between the
 end of the range before, its k_emit_rows, and the end of this one, and not in front of the seed kernel on its queue - that is a
 range's own A0): its start behind the step's seed kernel's start, its duration,
-the share of its interval that lies inside each foreground stage, its end against the end of k_emit_rows, and how long the next seed
+the share of its interval that lies inside each foreground stage, its tail (translate_tail_alone_ms: from the end of the seed kernel
+to the end of the translation, 0 where it ended inside the seed kernel) and the start of k_eval_seeds behind the later of the two ends
+(eval_start_after_translate_end_ms: negative where k_eval_seeds started beside the translation; eval_ms, end of the seed kernel to the
+end of k_eval_seeds, holds the tail in a build whose k_eval_seeds waits for it - DESIGN.md 5.12), its end against the end of k_emit_rows, and how long the next seed
 kernel waited for it (translation's end behind the end of this range's last dispatch on the seed kernel's own queue, its last copy
 to the host; 0 where it ended earlier; an upper bound, the host's pause between two ranges lies in it);
 
@@ -80,6 +83,11 @@ def steps(ks):
             rec["translate_end_after_emit_rows_ms"] = (t1 - rows[2]) / 1e6
             for name, (a, b) in marks.items():
                 rec["translate_share_in_" + name[:-3]] = sum(overlap(k[1], k[2], a, b) for k in tr) / span
+            # the translation's tail: what is left of it when the seed kernel has ended (0: it ended inside the seed kernel), and where
+            # k_eval_seeds starts against its end - negative while the two run beside each other, as they do in the tree; at least 0 (the
+            # dispatch's delay) in a build whose k_eval_seeds waits for the lookahead's end (measured and not kept)
+            rec["translate_tail_alone_ms"] = max(0.0, (t1 - s[2]) / 1e6)
+            rec["eval_start_after_translate_end_ms"] = (ev[1] - max(t1, s[2])) / 1e6 if t1 <= ev[1] else (ev[1] - t1) / 1e6
             # What the next range has to follow apart from the lookahead: the dispatches of THIS range on the seed kernel's own queue,
             # the range's stream - its kernels (the side streams join it) and its copies to the host, the last of which ends the
             # range.  Not the lookaheads' queue, not the rows' copy, which goes on beside the next range, and not what the next
