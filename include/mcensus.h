@@ -717,7 +717,7 @@ float mc_abundance_classes_ms(const mc_handle *h);
  * Nothing else reads them; refused: stat_nseq < 1 or stat_nres < stat_nseq.
  * mc_set_gene_fold(): seg_gene[s] and seg_off[s], the gene and the offset in it of sequence s of the index; gene_len[g], the residues of
  * gene g; ngenes == 0 turns the fold off.  While it is on every size of the abundance ABI above - the arrays of mc_abundance_read,
- * mc_coverage_read, mc_coverage_depth, mc_ties_read (and group_of), mc_ties_coverage_read, mc_curve_read and mc_gene_bootstrap - is
+ * mc_coverage_read, mc_coverage_depth, mc_depth_stats, mc_ties_read (and group_of), mc_ties_coverage_read, mc_curve_read and mc_gene_bootstrap - is
  * the GENES': mc_abundance_count() sequences, mc_abundance_residues() residues (the index's while it is off).  Rows handed to the host
  * (mc_result_rows, m8) stay what the engine produced.  Set it BEFORE mc_set_abundance: with the counts on it is refused unless the
  * tables keep their sizes, and then it zeroes every counter like the other switches.
@@ -762,6 +762,24 @@ int mc_identity_hist(mc_handle *h, uint32_t *hist /* [nseq * 101] */);
  * mc_identity_read. */
 float mc_identity_ms(const mc_handle *h);
 float mc_identity_scan_ms(const mc_handle *h);
+
+/* ---- Is the gene there, and how many copies?  Order statistics of a gene's depth (csrc/mc_depthstats.h states the rule) ----------------
+ * "Reads mapped to gene" (README "Normalization") and mean_depth both rise when a few hundred reads pile on one conserved domain; an order
+ * statistic of the per-residue depth does not.  With d the depth of mc_set_coverage, sorted to x[0] <= ... <= x[len - 1] (zeros included),
+ * and cut = len * (100 - keep_percent) / 200 in integer division, lo = cut, hi = len - cut:
+ *     median = x[(len - 1) / 2] (the LOWER median)     low = x[lo]     high = x[hi - 1]     trimmed_sum = x[lo] + ... + x[hi - 1]
+ * trimmed_sum / (hi - lo) is the truncated average depth ("TAD80" at keep_percent 80); divided by the genome equivalents of the README's
+ * "Normalization" it estimates the gene's copies per genome.  Exact integers, whatever the batches, ranges and launch geometry; a sequence
+ * without reads has four zeros.  keep_percent 100 gives trimmed_sum == spanned of mc_coverage_read; low <= median <= high <= max_depth.
+ * One selection kernel per call, a workgroup per sequence (csrc/k_depthstats.h): no residue's depth leaves the device - the other route,
+ * mc_coverage_depth and a sort on the host, copies all of them.  any != 0 reads the any-depth of mc_set_ties instead (the sequences with
+ * candidates are walked).  Arrays of mc_abundance_count() values; any of the four may be NULL.  The state is only read: ranges may follow.
+ * Refused, with a message naming the value: keep_percent outside 1 .. 100; coverage off; any != 0 while ties are off; a range in flight. */
+int mc_depth_stats(mc_handle *h, int32_t keep_percent, int any, int64_t *median /* [nseq] */, int64_t *trimmed_sum /* [nseq] */, int64_t *low /* [nseq] */,
+                   int64_t *high /* [nseq] */);
+/* Milliseconds the selection kernels of mc_depth_stats took since the last reset (HIP events) - the device cost of the depth columns beside the
+ * README's "Normalization" numerators. */
+float mc_depth_stats_ms(const mc_handle *h);
 
 #ifdef __cplusplus
 }

@@ -273,6 +273,9 @@ def load_library():
     lib.mc_abundance_count.argtypes = [C.c_void_p]
     lib.mc_abundance_residues.restype = C.c_int64
     lib.mc_abundance_residues.argtypes = [C.c_void_p]
+    lib.mc_depth_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mc_depth_stats_ms.restype = C.c_float
+    lib.mc_depth_stats_ms.argtypes = [C.c_void_p]
     lib.mc_set_identity.argtypes = [C.c_void_p, C.c_int]
     lib.mc_identity_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mc_identity_hist.argtypes = [C.c_void_p, C.c_void_p]
@@ -297,7 +300,7 @@ EXPORTED_SYMBOLS = ["mc_last_error", "mc_device_count", "mc_open", "mc_close", "
                     "mc_community_times",
                     "mc_set_run_classes", "mc_search_classes", "mc_result_best_classes", "mc_result_class_reads", "mc_debug_classes_prologue", "mc_reader_open_classes", "mc_reader_stride",
                     "mc_set_abundance", "mc_abundance_reset", "mc_abundance_read", "mc_abundance_ms",
-                    "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms",
+                    "mc_set_coverage", "mc_coverage_read", "mc_coverage_depth", "mc_coverage_ms", "mc_depth_stats", "mc_depth_stats_ms",
                     "mc_set_ties", "mc_ties_read", "mc_ties_coverage_read", "mc_ties_ms",
                     "mc_set_curve", "mc_curve_read", "mc_curve_k", "mc_curve_ms",
                     "mc_set_gene_bootstrap", "mc_gene_bootstrap", "mc_gene_bootstrap_ms", "mc_group_bootstrap", "mc_group_bootstrap_ms", "mc_group_bootstrap_kernels_ms",
@@ -1037,6 +1040,21 @@ class Engine:
     def coverage_ms(self):
         """milliseconds the coverage scan kernels took since the last reset (HIP events); the marks are part of abundance_ms()"""
         return float(self.lib.mc_coverage_ms(self.h))
+
+    def depth_stats(self, keep=80, any=False):
+        """Order statistics of every gene's depth as it stands (mc_depth_stats; csrc/mc_depthstats.h states the rule; one selection kernel, no
+        residue's depth leaves the device): {"median", "trimmed_sum", "low", "high"}, int64[nseq] each, and "keep" - with the depths sorted to x,
+        cut = len x (100 - keep) // 200, lo = cut, hi = len - cut: median = x[(len - 1) // 2], low = x[lo], high = x[hi - 1], trimmed_sum = the sum
+        of x[lo .. hi - 1].  any: of the any-depth of set_ties.  Refused: keep outside 1 .. 100, coverage off, any without ties."""
+        n = self.abundance_count()
+        out = {k: np.zeros(n, np.int64) for k in ("median", "trimmed_sum", "low", "high")}
+        self._check(self.lib.mc_depth_stats(self.h, int(keep), 1 if any else 0, *(out[k].ctypes.data_as(C.c_void_p) for k in ("median", "trimmed_sum", "low", "high"))), "mc_depth_stats")
+        out["keep"] = int(keep)
+        return out
+
+    def depth_stats_ms(self):
+        """milliseconds the selection kernels of depth_stats() took since the last reset (HIP events)"""
+        return float(self.lib.mc_depth_stats_ms(self.h))
 
     def set_identity(self, on=True):
         """The alignment identity of the assigned reads beside the counts (mc_set_identity; csrc/mc_identity.h states the rule): from now on

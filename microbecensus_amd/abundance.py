@@ -90,7 +90,21 @@ rows' identical, mismatched and gap-opening columns, and the gene table gets, be
 and per level T of ident_levels reads_ident_ge<T> - the reads whose best row has an identity of at least T percent - and rpkg_ident_ge<T>, the
 rpkg formula on them.  That is NOT the reads column of a run with min_ident T: there a lower-scoring row of higher identity may win a read
 whose best row fails the cut-off; the two agree for a read with one row.  ident_out writes the histogram (gene, ident, reads: one line per
-non-empty bin).  The figures are whole-sample figures of the best row: not rarefied, not bootstrapped, not shared among tied genes."""
+non-empty bin).  The figures are whole-sample figures of the best row: not rarefied, not bootstrapped, not shared among tied genes.
+
+Is the gene there, and how many copies?  reads, rpkg, mean_depth and max_depth all rise when a few hundred reads pile on one conserved domain.
+With depth_stats (Engine.depth_stats; csrc/mc_depthstats.h states the rule; implies coverage) the device selects, per gene, order statistics
+of the per-residue depth - zeros included, nothing sorted, no residue's depth copied out - and the gene table gets, behind every other column,
+
+    median_depth (the lower median)     tad<P> = trimmed_sum / (hi - lo)     tad<P>_per_ge = tad<P> / genome_equivalents_sampled
+
+where P is tad_keep (an integer percent, 1 .. 100, default 80; it implies depth_stats), cut = length_aa x (100 - P) // 200, lo = cut, hi =
+length_aa - cut and trimmed_sum the sum of the sorted depths at the ranks lo .. hi - 1: the "truncated average depth", TAD80 at the default.
+Neither moves when a domain is piled on; both are 0 for a gene covered over less than half (the median) or less than cut residues short of
+all (tad) of its length.  With ties median_depth_any and tad<P>_any follow, from the any-depth.  tad<P>_per_ge is roughly the gene's copies per
+genome - a single-copy gene present in every cell has a depth of about genome_equivalents_sampled - and it is biased LOW: reads that overlap a
+gene's end too shortly to align, and reads that failed the cut-offs, are missing from the depth.  Whole-sample figures: not rarefied, not
+bootstrapped, not summed into the groups table (a group has no depth)."""
 import gzip
 import math
 import os
@@ -135,6 +149,7 @@ IDENT_COLUMNS = ("matched_aa", "mismatched_aa", "gap_opens", "ident_mean", "iden
 IDENT_OUT_COLUMNS = ("gene", "ident", "reads")
 IDENT_BINS = 101                                                                     # MC_ID_BINS (csrc/mc_identity.h)
 MAX_IDENT_LEVELS = 8                                                                 # MC_ID_LEVELS
+TAD_KEEP = 80                                                                        # tad_keep's default: the central 80 % of the sorted depths ("TAD80")
 PIPELINE_KEYS = ("seqfiles", "nreads", "read_length", "min_quality", "mean_quality", "filter_dups", "max_unknown", "threads", "device", "model_dir", "verbose")
 TEXT = {"s": str, "d": lambda v: "%d" % v, "f": lambda v: repr(float(v)), "n": lambda v: "NA" if v is None else repr(float(v)),
         "i": lambda v: "NA" if v is None else "%d" % v}   # a value in a table, by its column's kind
@@ -436,6 +451,34 @@ def identity_columns(idn, reads, aligned, length_aa, ge):
     return cols
 
 
+def tad_kept(length_aa, keep):
+    """hi - lo of csrc/mc_depthstats.h: the ranks the truncated average keeps, length_aa - 2 x (length_aa x (100 - keep) // 200) - at least 1"""
+    ln = np.asarray(length_aa, dtype=np.int64)
+    return ln - 2 * (ln * (100 - int(keep)) // 200)
+
+
+def tad(trimmed_sum, length_aa, keep):
+    """the truncated average depth: trimmed_sum / (hi - lo) in float64"""
+    return np.asarray(trimmed_sum, dtype=np.float64) / tad_kept(length_aa, keep).astype(np.float64)
+
+
+def depth_stat_columns(ds, ds_any, length_aa, ge):
+    """The depth-statistics columns of the gene table from Engine.depth_stats()'s arrays (ds; ds_any: those of the any-depth, or None):
+    median_depth as it is, tad<P> = trimmed_sum / (hi - lo), tad<P>_per_ge = tad<P> / ge, and with ds_any median_depth_any and tad<P>_any."""
+    P = int(ds["keep"])
+    t = tad(ds["trimmed_sum"], length_aa, P)
+    cols = {"median_depth": ds["median"], "tad%d" % P: t, "tad%d_per_ge" % P: t / np.float64(ge)}
+    if ds_any is not None:
+        cols.update({"median_depth_any": ds_any["median"], "tad%d_any" % P: tad(ds_any["trimmed_sum"], length_aa, P)})
+    return cols
+
+
+def depth_stat_column_kinds(table):
+    """[(column, kind)] of the depth statistics, from the table's tad_keep; the _any columns only where the table has them"""
+    P = table["tad_keep"]
+    return [("median_depth", "d"), ("tad%d" % P, "f"), ("tad%d_per_ge" % P, "f")] + ([("median_depth_any", "d"), ("tad%d_any" % P, "f")] if table.get("median_depth_any") is not None else [])
+
+
 def level_columns(levels):
     """[(column, kind)] of the levels: reads_ident_ge<T> and rpkg_ident_ge<T> per level, in the levels' order"""
     return [c for t in levels for c in (("reads_ident_ge%d" % t, "d"), ("rpkg_ident_ge%d" % t, "f"))]
@@ -592,7 +635,8 @@ def table_columns(table):
               (has("covered_any_aa"), TIES_COVERAGE_COLUMNS, "df"), (has("detected_any"), ("detected_any",), "d"), (has("rpkg_boot_se"), BOOT_COLUMNS, "fff"),
               (has("rpkg_shared_boot_se"), TIE_BOOT_COLUMNS, "fff"), (has("breadth_boot_se"), COV_BOOT_COLUMNS, "ffff"), (has("detected_support"), ("detected_support",), "f"),
               (has("identity"), IDENT_COLUMNS, "dddniii"))
-    return [c for on, names, kinds in groups if on for c in zip(names, kinds)] + (level_columns(table["ident_levels"]) if has("identity") else [])
+    return ([c for on, names, kinds in groups if on for c in zip(names, kinds)] + (level_columns(table["ident_levels"]) if has("identity") else []) +
+            (depth_stat_column_kinds(table) if has("depth_stats") else []))
 
 
 def group_columns(table):
@@ -629,6 +673,8 @@ def write_table(path, args, table):
             out.write("# bootstrap_coverage:\ton\n")
         if table.get("identity") is not None:
             out.writelines(ident_header_lines(table))
+        if table.get("depth_stats") is not None:
+            out.writelines(["# depth_stats:\ton\n", "# tad_keep:\t%d\n" % table["tad_keep"]])
         columns = table_columns(table)
         _write_rows(out, columns, [table[name] for name, _ in columns])
 
@@ -740,7 +786,8 @@ def check_request(args):
     for key, default in (("min_ident", 0), ("min_aln", 0), ("min_bits", 0.0), ("groups", None), ("ags", None), ("ags_report", None),
                          ("coverage", False), ("min_breadth", None), ("depth_out", None), ("ties", False), ("curve", None), ("curve_genes", None),
                          ("bootstrap", None), ("bootstrap_seed", None), ("bootstrap_groups", False), ("mixed_lengths", None), ("long_genes", False),
-                         ("bootstrap_ties", False), ("tie_list_factor", None), ("bootstrap_coverage", False), ("identity", False), ("ident_levels", None), ("ident_out", None)):
+                         ("bootstrap_ties", False), ("tie_list_factor", None), ("bootstrap_coverage", False), ("identity", False), ("ident_levels", None), ("ident_out", None),
+                         ("depth_stats", False), ("tad_keep", None)):
         args.setdefault(key, default)
     mixed = microbe_census.mixed_lengths_on(args)
     if mixed:
@@ -798,7 +845,13 @@ def check_request(args):
         if not args["bootstrap_ties"]:
             raise AbundanceError("--tie-list-factor %s needs --bootstrap-ties: it sizes the list of tie entries" % (args["tie_list_factor"],))
         _check_int(args, "tie_list_factor", 1, MAX_TIE_FACTOR, "1 to %d" % MAX_TIE_FACTOR)
-    args["coverage"] = bool(args["coverage"]) or args["min_breadth"] is not None or args["depth_out"] is not None
+    _check_switch(args, "depth_stats")
+    if args["tad_keep"] is not None:
+        _check_int(args, "tad_keep", 1, 100, "1 to 100")
+    args["depth_stats"] = args["depth_stats"] or args["tad_keep"] is not None
+    if args["depth_stats"] and args["tad_keep"] is None:
+        args["tad_keep"] = TAD_KEEP
+    args["coverage"] = bool(args["coverage"]) or args["min_breadth"] is not None or args["depth_out"] is not None or args["depth_stats"]
     _check_switch(args, "bootstrap_coverage")
     if args["bootstrap_coverage"]:
         if args["bootstrap"] is None:
@@ -950,7 +1003,7 @@ def _replicate_scale(args, sample, ab, ac):
 
 def device_pass(args, sample, names, seqs, group_of):
     """Stage 2 - the record `counts`, from the only place that opens a reader or an engine: what the device counted as numpy arrays and ints - ab,
-    ac, cov, depth, ti, tcov, cu and points, gb, gbg (the groups') and scale, idn (the identity's figures, with the histogram under "hist" for ident_out), fold_stats (None: not asked for), sampled, gids and gnames, search_ms and the *_ms"""
+    ac, cov, depth, ti, tcov, cu and points, gb, gbg (the groups') and scale, idn (the identity's figures, with the histogram under "hist" for ident_out), ds and ds_any (the depth statistics), fold_stats (None: not asked for), sampled, gids and gnames, search_ms and the *_ms"""
     pargs, classes, fold = sample["pargs"], sample["classes"], args["gene_fold"]
     sampler = (pargs["nreads"], pargs["file_type"] == "fastq", pargs.get("quality_offset") or 0, pargs["min_quality"], pargs["mean_quality"], pargs["max_unknown"], pargs["filter_dups"])
     rd = _native.Reader.with_classes(pargs["seqfiles"], classes, *sampler) if classes is not None else _native.Reader(pargs["seqfiles"], sample["L"], *sampler)
@@ -958,7 +1011,7 @@ def device_pass(args, sample, names, seqs, group_of):
     try:                        # (long_genes: the engine on the segments, with the genes' statistics)
         db = {"names": names, "seqs": seqs} if fold is None else {"names": fold["seg_names"], "seqs": fold["seg_seqs"], "stats": fold["stats"]}
         eng = _native.Engine(device=int(args.get("device") or 0), marker_family=[0] * len(db["names"]), nfam=1, **db)
-        c = dict.fromkeys(("ac", "gb", "gbg", "scale", "tb", "cb", "idn"))
+        c = dict.fromkeys(("ac", "gb", "gbg", "scale", "tb", "cb", "idn", "ds", "ds_any"))
         c["gids"], c["gnames"] = _set_switches(eng, args, sample, names, group_of)
         try:
             c["cu"], c["points"] = _search_once(eng, rd, args, sample)
@@ -1001,6 +1054,10 @@ def device_pass(args, sample, names, seqs, group_of):
         c["depth"] = eng.coverage_depth() if args["depth_out"] is not None else None
         c["ti"] = eng.ties() if args["ties"] else None
         c["tcov"] = eng.ties_coverage() if args["ties"] and args["coverage"] else None
+        if args.get("depth_stats"):                                 # the selection runs on the device: four integers per gene come over, no depth
+            c["ds"] = eng.depth_stats(args["tad_keep"])
+            c["ds_any"] = eng.depth_stats(args["tad_keep"], any=True) if args["ties"] else None
+            c["depth_stats_ms"] = eng.depth_stats_ms()
         if args.get("identity"):                                    # the scan runs on the device; the histogram itself comes over only for ident_out
             c["idn"] = eng.identity(args["ident_levels"] or ())
             if args["ident_out"] is not None:
@@ -1095,8 +1152,14 @@ def build_table(args, sample, counts, names, seqs, group_of):
         table.update({"identity": idn, "ident_levels": list(idn["levels"])})
         if group_of is not None:
             table["groups_ident"] = group_ident_table(names, group_of, table)
+    ds = counts.get("ds")                                          # (a record from before the switch has no such key)
+    if ds is not None:                                              # whole-sample figures of the genes: nothing of them enters the groups or the curve
+        table.update(depth_stat_columns(ds, counts.get("ds_any"), length_aa, ge))
+        table.update({"depth_stats": ds, "tad_keep": int(ds["keep"])})
+        if counts.get("ds_any") is not None:
+            table["depth_stats_any"] = counts["ds_any"]
     gbg = counts.get("gbg")                                        # (a record from before the switch has no such key)
-    if gbg is not None:                                             # (group_ids numbers the groups in group_table's order)
+    if gbg is not None:                                           # (group_ids numbers the groups in group_table's order)
         table.update({"groups_boot": list(zip(*(col.tolist() for col in group_boot_columns(gbg["stats"], gbg["used"])))), "groups_boot_stats": gbg["stats"]})
     if cu is not None:
         points = [int(n) for n in counts["points"]]
@@ -1144,7 +1207,10 @@ def run_abundance(args):
     list of 1 .. 8 ascending integer percents) and ident_out (a path; both imply identity: matched_aa, mismatched_aa, gap_opens, ident_mean,
     ident_median, ident_min, ident_max and per level reads_ident_ge<T>, rpkg_ident_ge<T> behind every column of the gene table, matched_aa,
     ident_mean and the levels' columns behind every column of <outfile>.groups.tsv, table['identity'] - Engine.identity()'s arrays -; leaves
-    args['identity_ms']).  Four stages with two
+    args['identity_ms']), depth_stats with tad_keep (P, an integer percent 1 .. 100, default 80; it implies depth_stats, both imply coverage:
+    median_depth, tad<P> and tad<P>_per_ge behind every column of the gene table, identity's included, with ties median_depth_any and tad<P>_any;
+    table['depth_stats'] - Engine.depth_stats()'s arrays -, table['tad_keep']; the groups, curve and depth files are what they are without it;
+    leaves args['depth_stats_ms']).  Four stages with two
     records between them - DESIGN.md 13, "How a run is laid out on the host".  Writes args['outfile'] (and <outfile>.groups.tsv with groups)
     when it is set; leaves in args the sampler's options as imputed, sampled_reads, search_ms and the *_ms of every switch that ran; returns
     (table, args) - table: the columns as arrays, the header's values, and 'groups' [(group, genes, reads, rpkg)] with a map."""

@@ -4,9 +4,9 @@
 // assigned reads (mc_set_identity) and the counts on class runs (mc_set_abundance_classes): where their tables lie, how their kernels
 // are launched on the rows of a range, and which buffer exists when.
 // With a gene fold (mc_set_gene_fold, mc_fold.h) it also owns the fold of a range's rows from segments onto genes (k_fold.h), in front of everything else.
-// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_covboot.h, k_groupboot.h, k_identity.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
+// k_abundance.h, k_coverage.h, k_ties.h, k_curve.h, k_geneboot.h, k_tieboot.h, k_covboot.h, k_groupboot.h, k_identity.h, k_depthstats.h and k_abund_classes.h state the rules and hold the kernels; mc_hip.hip keeps the C ABI as thin wrappers (arguments,
 // hipSetDevice, a call here) and the harnesses of tests/emul/ launch through mc_abund_launch like range_end, and through mc_geneboot_launch,
-// mc_tieboot_launch, mc_covboot_launch, mc_groupboot_launch and mc_identity_launch like the reads.
+// mc_tieboot_launch, mc_covboot_launch, mc_groupboot_launch, mc_identity_launch and mc_depthstats_launch like the reads.
 #pragma once
 #include "k_abundance.h"
 #include "k_coverage.h"
@@ -19,6 +19,7 @@
 #include "k_abund_classes.h"
 #include "k_fold.h"
 #include "k_identity.h"
+#include "k_depthstats.h"
 #include "mc_owned.h"
 
 // ---- Layout: every size and offset of the four tables (k_ties.h, k_coverage.h and k_curve.h, "Layout", say what the slots hold) -----------------
@@ -199,6 +200,20 @@ static int mc_identity_launch(const McIdentRead &R, hipStream_t st, const hipEve
     return 0;
 }
 
+// The depth statistics' read (mc_depthstats.h): raw device pointers of one mc_depth_stats.  tab: the pair table that says which genes have reads -
+// the count table, or the head of the tie table for the any-depth; off: the genes' residue offsets; diff: that depth's difference array; P: the
+// percent kept, 1 .. 100, checked by the caller; out: nseq x MC_DS_NOUT values
+struct McDepthRead { const unsigned long long *tab; const uint32_t *off; const uint32_t *diff; int32_t nseq, P; unsigned long long *out; };
+// The selection between ev[0] and ev[1], in `st`, a workgroup per gene; with nseq == 0 only the events
+static int mc_depthstats_launch(const McDepthRead &R, hipStream_t st, const hipEvent_t (&ev)[2])
+{
+    HIPCK(hipEventRecord(ev[0], st));
+    if (R.nseq > 0) k_depth_select<<<dim3((unsigned)R.nseq), dim3(MC_DS_THREADS), 0, st>>>(R.tab, R.off, R.diff, R.nseq, R.P, R.out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(ev[1], st));
+    return 0;
+}
+
 // ---- A list bootstrap's state -------------------------------------------------------------------------------------------------
 template <class Tp> static int fit_one(McDev<Tp> &d, bool want, size_t n) { if (!want) d.reset(); return want && !d ? d.alloc(n) : 0; }
 static int fit_one(McEvent &e, bool want) { if (!want) e.reset(); return want && !e ? e.create() : 0; }
@@ -306,6 +321,7 @@ template <class E> struct McBootList {
 // The nine switches and everything that hangs on them.  THE BUFFER RULE, kept by fit() and by nobody else:
 //     the count table, its two events                              exist while   counts are on
 //     the difference array, the scan's output, its two events                    coverage is on
+//     the depth statistics' output, its two events                               coverage is on
 //     the tie table, its event                                                   ties are on
 //     the group map                                                              ties are on with ngroups > 0
 //     the any-depth's difference array                                           coverage and ties are on
@@ -362,6 +378,7 @@ struct McAbundance {
     McDev<McFoldSeg> d_seg; McDev<uint32_t> d_goff; McDev<McRow> d_folded; McDev<unsigned long long> d_edge;
     McEvent ev_fold[2]; float fold_ms = 0;                          // around k_fold of a range; its time since the last zeroing
     float ms = 0, cov_ms = 0, ties_ms = 0;                         // the counting kernels', the scans', k_ties' time since the last zeroing
+    McDev<unsigned long long> d_dsout; McEvent ev_ds[2]; float dstat_ms = 0;   // the depth statistics (mc_depthstats.h): the selection's output; around a read; the reads' time since the last zeroing
 
     void bind(int32_t nseq_, size_t nres_, const uint32_t *d_off) { nseq = ix_nseq = nseq_; nres = ix_nres = nres_; off = ix_off = d_off; }
     bool active() const { return on; }
@@ -435,7 +452,7 @@ struct McAbundance {
         if (d_edge) HIPCK(hipMemset(d_edge, 0, sizeof(unsigned long long)));
         if (d_idhist) HIPCK(hipMemset(d_idhist, 0, sizeof(uint32_t) * mc_id_hist_slots((size_t)nseq)));
         if (d_idsums) HIPCK(hipMemset(d_idsums, 0, sizeof(McIdSums) * (size_t)nseq));
-        fold_ms = ident_ms = iscan_ms = 0.f;
+        fold_ms = ident_ms = iscan_ms = dstat_ms = 0.f;
         searched = 0; ms = cov_ms = ties_ms = curve_ms = cscan_ms = cls_ms = 0.f;
         gmat_n = -1; grp_ms = grp_values_ms = grp_summary_ms = 0.f;
         return 0;
@@ -524,6 +541,23 @@ struct McAbundance {
         const size_t ns = (size_t)nseq; std::vector<unsigned long long> out(3 * ns);
         HIPCK(hipMemcpy(out.data(), d_covout, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         for (size_t s = 0; s < ns; s++) { if (covered) covered[s] = (int64_t)out[3 * s]; if (spanned) spanned[s] = (int64_t)out[3 * s + 1]; if (max_depth) max_depth[s] = (int64_t)out[3 * s + 2]; }
+        return 0;
+    }
+    // The order statistics of every gene's depth as they stand (mc_depthstats.h): of the depth, or (any) of the any-depth with the head of the tie
+    // table saying which genes have candidates - as read_figures takes its tables.  P: the percent kept, checked by the caller (mc_depth_stats).
+    // median, trimmed_sum, low, high: nseq values each, every one or null.  The selection runs on the device: no residue's depth comes to the host
+    int read_depth_stats(bool any, int32_t P, int64_t *median, int64_t *trimmed_sum, int64_t *low, int64_t *high)
+    {
+        const McDepthRead R = {any ? d_ties.get() : d_counts.get(), off, any ? d_diff_any.get() : d_diff.get(), nseq, P, d_dsout};
+        const hipEvent_t ev[2] = {ev_ds[0], ev_ds[1]};
+        if (mc_depthstats_launch(R, 0, ev)) return -1;
+        HIPCK(hipEventSynchronize(ev_ds[1]));
+        dstat_ms += ev_ms(ev_ds[0], ev_ds[1]);
+        const size_t ns = (size_t)nseq; std::vector<unsigned long long> out(mc_ds_out_slots(ns));
+        HIPCK(hipMemcpy(out.data(), d_dsout, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        int64_t *const to[MC_DS_NOUT] = {median, trimmed_sum, low, high};      // (MC_DS_MEDIAN, MC_DS_SUM, MC_DS_LOW, MC_DS_HIGH)
+        for (size_t s = 0; s < ns; s++)
+            for (int k = 0; k < MC_DS_NOUT; k++) if (to[k]) to[k][s] = (int64_t)out[MC_DS_NOUT * s + (size_t)k];
         return 0;
     }
     // the curve as it stands: reads, aligned and (or null) covered as K x nseq values, point by point; assigned: K values; beyond: one
@@ -696,7 +730,7 @@ private:
         if (!on) { cov = ties = curve = gboot.on = classes = ident = false; searched = 0; ms = 0.f; }
         if (!ident) ident_ms = iscan_ms = 0.f;
         if (!classes) { cls_ms = 0.f; ride_end(); }
-        if (!cov) cov_ms = 0.f;
+        if (!cov) cov_ms = dstat_ms = 0.f;
         if (!ties) { ngroups = 0; ties_ms = 0.f; }
         if (!curve) { K = 0; curve_ms = cscan_ms = 0.f; }
         if (!gboot.on) {
@@ -707,6 +741,7 @@ private:
         const size_t ns = (size_t)nseq, slots = mc_diff_slots(nres, ns);
         return fit_one(d_counts, on, mc_pair_slots(ns)) || fit_one(ev_count[0], on) || fit_one(ev_count[1], on) ||
                fit_one(d_diff, cov, slots) || fit_one(d_covout, cov, 3 * ns) || fit_one(ev_cov[0], cov) || fit_one(ev_cov[1], cov) ||
+               fit_one(d_dsout, cov, mc_ds_out_slots(ns)) || fit_one(ev_ds[0], cov) || fit_one(ev_ds[1], cov) ||
                fit_one(d_ties, ties, mc_tie_slots(ns, (size_t)ngroups)) || fit_one(ev_ties, ties) || fit_one(d_group, ties && ngroups > 0, ns) ||
                fit_one(d_diff_any, cov && ties, slots) ||
                fit_one(d_pts, curve, MC_CURVE_MAXK) || fit_one(d_bins, curve, mc_curve_bin_slots((size_t)K, ns)) || fit_one(d_curveout, curve, mc_curve_out_slots((size_t)K, ns)) ||

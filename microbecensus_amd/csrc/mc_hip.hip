@@ -24,6 +24,7 @@
 //   k_geneboot.h           the bootstrap of the counts beside them: a device list of (read id, gene), per-gene replicate sums, sort and summary at read time (mc_set_gene_bootstrap)
 //   k_groupboot.h          the bootstrap of the groups table behind it: every group's replicate values walked over its members' rows of the replicate sums, sort and summary (mc_group_bootstrap)
 //   k_identity.h, mc_identity.h   the identity of the assigned reads: a histogram and three sums per gene on the rows of a range, min / median / max and levels by a scan at read time (mc_set_identity)
+//   k_depthstats.h, mc_depthstats.h   the median and the truncated average of every gene's depth: a radix selection over the difference array at read time (mc_depth_stats)
 //   k_abund_classes.h      the per-class table of the counts on class runs (mc_set_abundance_classes)
 //   k_fold.h, mc_fold.h    genes longer than one sequence of the engine: segments, and the fold of a range's rows onto the genes (mc_set_gene_fold)
 //   mc_abund.h             (host) the owner of those five: the tables' layout, the launch on a range's rows, which buffer exists when, the readers
@@ -2068,6 +2069,20 @@ extern "C" int mc_ties_coverage_read(mc_handle *h, int64_t *covered_any, int64_t
     HIPCK(hipSetDevice(h->device));
     return h->ab.read_figures(true, covered_any, spanned_any, max_depth_any);
 }
+
+// the lower median and the truncated sum of every gene's depth (mc_depthstats.h), of the depth or (any != 0) of the any-depth: one selection kernel
+extern "C" int mc_depth_stats(mc_handle *h, int32_t keep_percent, int any, int64_t *median, int64_t *trimmed_sum, int64_t *low, int64_t *high)
+{
+    if (!h) { g_err = "null handle"; return -1; }
+    if (h->pipe_nout) { g_err = "mc_depth_stats: a range begun with mc_range_begin() is still in flight (keep_percent = " + std::to_string(keep_percent) + ")"; return -1; }
+    if (!mc_ds_keep_ok(keep_percent)) { g_err = "mc_depth_stats: keep_percent " + std::to_string(keep_percent) + " is not a percent from 1 to 100"; return -1; }
+    if (!h->ab.cov) { g_err = "mc_depth_stats: coverage is off (mc_set_coverage) - the depths are its difference array's (keep_percent = " + std::to_string(keep_percent) + ")"; return -1; }
+    if (any && !h->ab.ties) { g_err = "mc_depth_stats: any = " + std::to_string(any) + " while ties are off (mc_set_ties) - the any-depth is theirs"; return -1; }
+    HIPCK(hipSetDevice(h->device));
+    return h->ab.read_depth_stats(any != 0, keep_percent, median, trimmed_sum, low, high);
+}
+// the selection kernels' time over the reads since the last zeroing
+extern "C" float mc_depth_stats_ms(const mc_handle *h) { return h ? h->ab.dstat_ms : 0.0f; }
 
 // the rarefaction curve: K points (ascending, each >= 1) turn it on and zero every counter; K == 0 turns it off
 extern "C" int mc_set_curve(mc_handle *h, int32_t K, const int64_t *points)

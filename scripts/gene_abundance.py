@@ -76,6 +76,12 @@ def parse_arguments(argv=None):
                    help="per level T add reads_ident_ge<T> and rpkg_ident_ge<T>: the reads whose BEST ROW has at least T percent identity (1 - 8 integers, 0 - 100, ascending); "
                         "not the reads of a run with --min-ident T, where a lower-scoring row of higher identity may win; implies --identity")
     p.add_argument("--ident-out", dest="ident_out", type=str, default=None, metavar="FILE", help="write the identity histogram as gene, ident, reads: one line per gene and percent that has reads; implies --identity")
+    p.add_argument("--depth-stats", dest="depth_stats", action="store_true", default=False,
+                   help="add median_depth, tad<P> and tad<P>_per_ge behind every column of the gene table: the lower median and the truncated average of the per-residue depth "
+                        "(zeros included), which a pile of reads on one conserved domain does not move, and that average per genome equivalent - roughly the gene's copies per "
+                        "genome, biased low (with --ties also median_depth_any and tad<P>_any); implies --coverage")
+    p.add_argument("--tad-keep", dest="tad_keep", type=int, default=None, metavar="P",
+                   help="the percent of the sorted depths the truncated average keeps, (100 - P) / 2 percent cut at either end (an integer, 1 - 100; default = 80: tad80); implies --depth-stats")
     args = vars(p.parse_args(argv))
     args["seqfiles"] = args["seqfiles"].split(",")
     for k in ("device", "model_dir", "threads"):
